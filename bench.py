@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the CASS-NAT inference hot path on MI355X (BASELINE.json: utterances/sec + RTF).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 One "step" = one pass of the hot path (CassNAT.beam_decode: conv subsampling -> 12L encoder -> CTC greedy
@@ -11,9 +11,16 @@ with fp32 accumulation, random-init weights of the named architecture (seeded; b
 token count).  With N > 1 every rank decodes its own shard (weak scaling); rank 0 packs the checkpoint once and
 the weight blob is broadcast over RCCL; each step ends with one all-gather of the hypothesis records.
 
-Rank 0 prints ONE JSON line.  `roofline` describes the dominant kernel (timed live with HIP events on the launch
-stream inside the timed region); `cpu_baseline` is the oracle (torch-CPU restatement of the reference's ATen op
-sequence, kind "port") timed on this host's cores on a bounded sample of the same workload.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the headline (`value`,
+`ms_per_step`, `rtfx`, ...); the fields of the other legs are null.  `--full` adds them: `roofline` describes the
+dominant kernel (timed live with HIP events on the launch stream inside the timed region, which costs the headline a
+few percent); `cpu_baseline` is the oracle (torch-CPU restatement of the reference's ATen op sequence, kind "port")
+timed on this host's cores on a bounded sample of the same workload; then the per-stage times, the other engines and
+the one-batch-per-pass, steady-state and ragged-set legs.
+
+`--dump-outputs DIR` writes what the last timed step handed its caller (rank 0: every rank's utterances, rank-major)
+as DIR/tokens.npy (float32, one row per utterance: sos + hypothesis, 0 past its length), DIR/lengths.npy (float32)
+and DIR/scores.npy (float64).  Weights and features are seeded: the same arguments give the same inputs on every run.
 """
 import argparse
 import json
@@ -58,7 +65,7 @@ def main():
     ap.add_argument("--no-parity-engine", action="store_true",
                     help="skip timing the engines that meet the parity gate (fp32 MFMA, split-bf16) beside the headline")
     ap.add_argument("--cpu-batches", type=int, default=3)
-    ap.add_argument("--stage-profile", action="store_true", help="also print a per-kernel-tag table to stderr")
+    ap.add_argument("--stage-profile", action="store_true", help="with --full: also print a per-kernel-tag table to stderr")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="gloo = rehearsal of the N>1 path on one GPU")
     ap.add_argument("--streams", type=int, default=2,
                     help="decode pipelines per GPU (own engine handle, HIP stream and host thread each): keeps the GPU fed "
@@ -82,7 +89,14 @@ def main():
     ap.add_argument("--cpu-threads", type=int, default=16, help="upper bound on the host threads of the cpu_baseline leg")
     ap.add_argument("--host-timeline", action="store_true", help="stderr: what the pipelines' host threads did when, in the timed region")
     ap.add_argument("--plan", default="", help="explicit pass sizes of the timed run, e.g. 8,8,4 (default: equal shares)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: roofline events in the timed region, per-stage times, cpu_baseline, the other "
+                         "engines and the extra legs (the --no-* switches and --stage-profile refine a --full run)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's hypotheses (tokens, lengths, scores) as DIR/<name>.npy")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import numpy as np
     import torch
@@ -189,8 +203,9 @@ def main():
     ROOF_TAGS = ["row_chain", "row_chain_dec", "conv2"]
     # HIP-event pairs on the launch stream around these kernels only, on ONE of the pipelines (22 pairs per step: on all
     # of them the event traffic itself costs a few percent of throughput)
-    for e in engines[:1]:
-        e.profile_begin(ROOF_TAGS)
+    if a.full:
+        for e in engines[:1]:
+            e.profile_begin(ROOF_TAGS)
     if a.host_timeline:
         pipes.timeline = []
     t0 = time.perf_counter()
@@ -204,6 +219,14 @@ def main():
             print("%9.3f ms  %-12s %s" % ((t - t0) * 1e3, label, "" if k < 0 else "pipeline %d" % k), file=sys.stderr)
         print("%9.3f ms  run_steps returned\n%9.3f ms  fenced" % ((t_run - t0) * 1e3, elapsed * 1e3), file=sys.stderr)
     pass_stats = {k: pipes.stats[k] - stats0[k] for k in stats0}
+    (toks_, lens_), scores = last[0]
+    if a.dump_outputs and rank == 0:
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        # (positions past a hypothesis' length are not part of it: written as 0 whatever the record held there)
+        toks_out = np.where(np.arange(toks_.shape[1])[None, :] < lens_[:, None], toks_, 0)
+        for name, arr in (("tokens", toks_out.astype(np.float32)), ("lengths", lens_.astype(np.float32)),
+                          ("scores", np.asarray(scores, dtype=np.float64))):
+            np.save(os.path.join(a.dump_outputs, name + ".npy"), arr)
     if a.exit_after_timed:
         if rank == 0:
             print(json.dumps({"value": round(a.steps * B * world / elapsed, 2), "ms_per_step": round(elapsed / a.steps * 1e3, 4), "steps": a.steps}))
@@ -212,13 +235,12 @@ def main():
             dist.destroy_process_group()
         return
     prof = {t: {"count": 0, "ms": 0.0, "flops": 0.0, "bytes": 0.0} for t in ROOF_TAGS}
-    for e in engines[:1]:
+    for e in engines[:1] if a.full else []:
         got = e.profile_end()
         for t in ROOF_TAGS:
             if got.get(t):
                 for k in prof[t]:
                     prof[t][k] += got[t][k]
-    (toks_, lens_), scores = last[0]
     hyps = [toks_[b, : lens_[b]].tolist() for b in range(toks_.shape[0])]  # the last step's hypotheses, as token lists
     if dist_on:
         tt = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
@@ -226,23 +248,24 @@ def main():
         elapsed = float(tt.item())
 
     # ---- per-stage breakdown outside the timed region
-    eng.profile_begin(None)
-    for _ in range(3):  # one pipeline, the GPU to itself
-        cdist.unpack_records(cdist.pack_records(*model.decode_device(feats, sizes, args, engine=eng)))
-    stages = eng.profile_end()
-    best_gpu = eng.fetch("best_paths")[:B]  # the timed engine's CTC arg-max per frame on the benchmark batch (for cpu_baseline)
-    stage_ms = {k: round(v["ms"] / 3, 4) for k, v in sorted(stages.items(), key=lambda kv: -kv[1]["ms"])}
-    # ... and the roofline kernels once more with the GPU to themselves at the WIDTH of the timed run (CO batches per pass)
-    stages_wide = {}
+    stages, stages_wide, stage_ms, best_gpu = {}, {}, None, None
     COW = min(CO, int(eng.cfg.max_batch) // B)  # (the workspace is sized by area: at --frames > 1024 it holds fewer batches than CO)
-    if COW > 1:
-        fw, sw = torch.cat([feats] * COW, 0), torch.cat([sizes] * COW, 0)
-        model.decode_device(fw, sw, args, 1, engine=eng, sub_batch=B)
-        eng.profile_begin(ROOF_TAGS)
-        for _ in range(2):
-            cdist.unpack_records(cdist.pack_records(*model.decode_device(fw, sw, args, 1, engine=eng, sub_batch=B)))
-        stages_wide = eng.profile_end()
-        del fw, sw
+    if a.full:
+        eng.profile_begin(None)
+        for _ in range(3):  # one pipeline, the GPU to itself
+            cdist.unpack_records(cdist.pack_records(*model.decode_device(feats, sizes, args, engine=eng)))
+        stages = eng.profile_end()
+        best_gpu = eng.fetch("best_paths")[:B]  # the timed engine's CTC arg-max per frame on the benchmark batch (for cpu_baseline)
+        stage_ms = {k: round(v["ms"] / 3, 4) for k, v in sorted(stages.items(), key=lambda kv: -kv[1]["ms"])}
+        # ... and the roofline kernels once more with the GPU to themselves at the WIDTH of the timed run (CO batches per pass)
+        if COW > 1:
+            fw, sw = torch.cat([feats] * COW, 0), torch.cat([sizes] * COW, 0)
+            model.decode_device(fw, sw, args, 1, engine=eng, sub_batch=B)
+            eng.profile_begin(ROOF_TAGS)
+            for _ in range(2):
+                cdist.unpack_records(cdist.pack_records(*model.decode_device(fw, sw, args, 1, engine=eng, sub_batch=B)))
+            stages_wide = eng.profile_end()
+            del fw, sw
     if a.stage_profile and rank == 0:
         for k, v in sorted(stages.items(), key=lambda kv: -kv[1]["ms"]):
             tf = v["flops"] / (v["ms"] * 1e-3) / 1e12 if v["ms"] > 0 else 0
@@ -251,7 +274,7 @@ def main():
 
     # ---- extra (never `value`; N = 1 only): the same steps with one batch per engine pass
     uncoalesced = None
-    if not a.no_uncoalesced and CO > 1 and world == 1:  # (like cpu_baseline: at N = 1 only)
+    if a.full and not a.no_uncoalesced and CO > 1 and world == 1:  # (like cpu_baseline: at N = 1 only)
         NS1 = max(NS, 3)  # one batch per pass needs more pipelines in flight than wide passes do
         pipes2 = DecodePipelines(model, NS1, B, T, coalesce=1, share_from=engines[0])  # (the same device copy of the weights)
 
@@ -272,7 +295,7 @@ def main():
     # ---- extra (never `value`; N = 1 only): the same pipelines over ten times as many steps - at the driver's 20 steps the timed
     # region is one engine pass per pipeline (~15 ms: the first launch's wake-up and the last pass's copy home are 10 % of it)
     steady = None
-    if world == 1 and not dist_on and a.steps < 100 and not a.no_uncoalesced:
+    if a.full and world == 1 and not dist_on and a.steps < 100 and not a.no_uncoalesced:
         run_steps(10 * a.steps)  # (once untimed: the passes of a longer list are cut differently)
         fence()
         c0 = time.perf_counter()
@@ -285,7 +308,7 @@ def main():
     # ---- extra (never `value`; N = 1 only): what decode_asr meets - a length-sorted list of batches of DIFFERENT frame counts
     # (300..1500, every batch padded to its own longest utterance), merged into engine passes by workspace area
     ragged_leg = None
-    if not a.no_ragged_leg and world == 1 and not dist_on and a.precision in ("bf16", "bf16x3", "fp16"):
+    if a.full and not a.no_ragged_leg and world == 1 and not dist_on and a.precision in ("bf16", "bf16x3", "fp16"):
         rng = np.random.default_rng(99)
         n_b = 192  # 6144 utterances: the size of a test set (dev-clean + dev-other); neighbouring batches of the sorted list differ by ~6 frames
         lens = np.sort(rng.integers(300, 1501, size=n_b * B))[::-1]
@@ -437,7 +460,7 @@ def main():
                 "flip_rate_margin_ge_0.2": round(m["flip_rate_margin_ge_0.2"], 5), "frames_margin_ge_0.2": m["frames_margin_ge_0.2"]}
 
     cpu, ref = None, None
-    if not a.no_cpu_baseline and world == 1:
+    if a.full and not a.no_cpu_baseline and world == 1:
         from oracle import cassnat_oracle as orc
 
         # host threads: this process's CPU share, not the machine's core count (a 1-GPU box gets 16 cores)
@@ -505,7 +528,7 @@ def main():
         return r
 
     parity_engine, fp32_engine = None, None
-    if world == 1 and not a.no_parity_engine and a.precision == "bf16":
+    if a.full and world == 1 and not a.no_parity_engine and a.precision == "bf16":
         fp32_engine = time_engine("fp32")
         fp32_engine["mfma_peak_tflops"] = 157.3
         fp32_engine["mfma_frac_end_to_end"] = round(flops / B * fp32_engine["value"] / 157.3e12, 5)
@@ -526,7 +549,7 @@ def main():
     # rate, operand roundings 8 x smaller - CTC log-posteriors within north_star's 1e-3 of the fp32 reference
     # (tests/test_gpu_pipeline.py::test_fp16_engine_meets_the_logit_tolerance); range +-65504
     fp16_engine = None
-    if world == 1 and not a.no_parity_engine and a.precision == "bf16":
+    if a.full and world == 1 and not a.no_parity_engine and a.precision == "bf16":
         fp16_engine = time_engine("fp16")
         fp16_engine["speedup_over_value"] = round(fp16_engine["value"] / value, 3)
         fp16_engine["note"] = ("half-precision (11-bit) MFMA operands in the bf16 engine's kernels, fp32 accumulation / residual stream / "
@@ -536,7 +559,7 @@ def main():
     # e4m3 conv front-end on the block-scaled K = 64 MFMA) through the same pipelines - a throughput form without a parity
     # claim (its agreement with the fp32 reference is measured by tests/test_gpu_pipeline.py::test_config5_fp8_encoder_products)
     fp8_engine = None
-    if world == 1 and not a.no_parity_engine and a.precision == "bf16":
+    if a.full and world == 1 and not a.no_parity_engine and a.precision == "bf16":
         fp8_engine = time_engine("fp8")
         fp8_engine["note"] = ("e4m3fn operands for the encoder's feed-forward products and both subsampling convolutions (v_mfma_scale_f32_32x32x64_"
                               "f8f6f4), everything else as the bf16 engine; `hyp_agreement` as for the other engines")
