@@ -1,5 +1,7 @@
 // Fused position-wise feed-forward sublayer for gfx950 (bf16 MFMA, d_model = 256):
-//     x <- x + W2 . relu(W1 . LN(x) + b1) + b2          [and optionally  xn_next <- LN_next(x)]
+//     x <- x + W2 . act(W1 . LN(x) + b1) + b2          [and optionally  xn_next <- LN_next(x)]
+// act = ReLU (transformer blocks) or Swish h * sigmoid(h) (the conformer AST's decoder layers, src/models/conformer.py:30; residual
+// scale 1 - not the macaron half), a compile-time choice: the ReLU instantiation is the kernel as it always was.
 // Replaces SublayerConnection(LayerNorm -> PositionwiseFeedForward) of the reference
 // (src/models/modules/utils.py:23-32, positionff.py:15-16, norm.py:15-18) - four launches (LN, w_1+ReLU,
 // w_2+residual, next LN) and a 2 x M x d_ff round trip of the hidden activations through HBM.
@@ -53,6 +55,14 @@ template <int MT> constexpr int ff_lds_bytes() { return MT * 16384 + 4 * FF_RING
 static_assert(4 * 32 * FF_P_STRIDE * 4 <= ff_lds_bytes<1>(), "partials must fit");
 static_assert(ff_lds_bytes<2>() <= 160 * 1024, "LDS budget");
 
+// the hidden activation, on h = W1 . LN(x) + b1 in fp32 before the 16-bit pack
+template <int ACT> __device__ __forceinline__ float ff_act(float h) {
+    if constexpr (ACT == FF_ACT_SWISH)
+        return h * (1.f / (1.f + __expf(-h)));
+    else
+        return fmaxf(h, 0.f);
+}
+
 __device__ __forceinline__ void ln_row_to(const f32x4 v, float mean, float denom, const f32x4 g, const f32x4 bb,
                                           float* o) {
 #pragma unroll
@@ -62,7 +72,8 @@ __device__ __forceinline__ void ln_row_to(const f32x4 v, float mean, float denom
 // MT = 32-row M-tiles per workgroup (1 or 2).  With MT = 2 every streamed weight fragment feeds two MFMAs, which halves
 // the L2->LDS bytes per row - the resource this kernel is bound by.
 // DBG: timing experiments only (1 = no DMA refills, 2 = no MFMAs, 3 = DMA stream only; results are wrong); 0 in production
-template <int MT, int DBG>
+// ACT: FF_ACT_RELU or FF_ACT_SWISH
+template <int MT, int DBG, int ACT = FF_ACT_RELU>
 __global__ __launch_bounds__(256) void ffn_fused_kernel(FfnParams p) {
     constexpr int BM = 32 * MT;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -241,15 +252,15 @@ __global__ __launch_bounds__(256) void ffn_fused_kernel(FfnParams p) {
             acc[0][0][0] += (float)wf0[0] + (float)wf1[0] + (float)wf2[0] + (float)wf3[0];                    \
         }                                                                                                     \
     }
-    // bias + ReLU on hidden unit f = 32*tile + acc_row(r, lane), then pack as the B operand of phase B
-#define FF_RELU_PACK(pos)                                                                                     \
+    // bias + activation on hidden unit f = 32*tile + acc_row(r, lane), then pack as the B operand of phase B
+#define FF_ACT_PACK(pos)                                                                                     \
     bf16x8 pb[MT][2];                                                                                         \
     {                                                                                                         \
         const int src0 = 32 * ((pos) & 1) + 4 * half;                                                         \
         _Pragma("unroll") for (int g = 0; g < 4; ++g) _Pragma("unroll") for (int e = 0; e < 4; ++e) {         \
             const float bv = __shfl(bq[0], src0 + 8 * g + e);                                                 \
             _Pragma("unroll") for (int mt = 0; mt < MT; ++mt)                                                 \
-                pb[mt][g >> 1][4 * (g & 1) + e] = (bf16)fmaxf(xh[mt][4 * g + e] + bv, 0.f);                   \
+                pb[mt][g >> 1][4 * (g & 1) + e] = (bf16)ff_act<ACT>(xh[mt][4 * g + e] + bv);                   \
         }                                                                                                     \
         if ((pos) & 1) { _Pragma("unroll") for (int j = 0; j < 7; ++j) bq[j] = bq[j + 1]; }                   \
     }
@@ -270,7 +281,7 @@ __global__ __launch_bounds__(256) void ffn_fused_kernel(FfnParams p) {
         }
         tnext = FF_TT(t + 1);
         FF_PHASE_A(1, 24, FF_REFILL_W1(0)) FF_PHASE_A(2, 24, FF_REFILL_W1(1)) FF_PHASE_A(3, 24, FF_REFILL_W1(2))
-        FF_RELU_PACK(t)
+        FF_ACT_PACK(t)
         FF_PHASE_B(0, 24, FF_REFILL_W1(3)) FF_PHASE_B(1, 24, FF_REFILL_W2(0)) FF_PHASE_B(2, 24, FF_REFILL_W2(1))
         FF_PHASE_B(3, 24, FF_REFILL_W2(2))
     }
@@ -282,14 +293,14 @@ __global__ __launch_bounds__(256) void ffn_fused_kernel(FfnParams p) {
             FF_PHASE_A(0, 24, FF_REFILL_W2(3))
         }
         FF_PHASE_A(1, 24, ) FF_PHASE_A(2, 20, ) FF_PHASE_A(3, 16, )
-        FF_RELU_PACK(t)
+        FF_ACT_PACK(t)
         FF_PHASE_B(0, 12, ) FF_PHASE_B(1, 8, ) FF_PHASE_B(2, 4, ) FF_PHASE_B(3, 0, )
     }
 #undef FF_PHASE_A
 #undef FF_REFILL_W1
 #undef FF_REFILL_W2
 #undef FF_PHASE_B
-#undef FF_RELU_PACK
+#undef FF_ACT_PACK
 #undef FF_ZERO_XH
 #undef FF_MFMA
 #undef FF_TT
@@ -360,15 +371,15 @@ __global__ __launch_bounds__(256) void ffn_fused_kernel(FfnParams p) {
     }
 }
 
-template <int MT, int DBG> static int launch_ffn_variant(const FfnParams& p, hipStream_t s) {
+template <int MT, int DBG, int ACT = FF_ACT_RELU> static int launch_ffn_variant(const FfnParams& p, hipStream_t s) {
     constexpr int lds = ff_lds_bytes<MT>();
     static CnAttrOnce attr_once;
     int attr_dev;
     if (attr_once.need(&attr_dev)) {
-        CN_HIP_CHECK(hipFuncSetAttribute((const void*)ffn_fused_kernel<MT, DBG>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        CN_HIP_CHECK(hipFuncSetAttribute((const void*)ffn_fused_kernel<MT, DBG, ACT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         attr_once.mark(attr_dev);
     }
-    hipLaunchKernelGGL((ffn_fused_kernel<MT, DBG>), dim3(cn_ceil_div(p.M, 32 * MT), p.nslice), dim3(256), lds, s, p);
+    hipLaunchKernelGGL((ffn_fused_kernel<MT, DBG, ACT>), dim3(cn_ceil_div(p.M, 32 * MT), p.nslice), dim3(256), lds, s, p);
     CN_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -402,6 +413,12 @@ int launch_ffn_fused(const FfnFusedArgs& a, hipStream_t s) {
     static const int dbg = cn_exp_env("CASSNAT_FFN_DEBUG") ? atoi(cn_exp_env("CASSNAT_FFN_DEBUG")) : 0;  // (magic statics: thread-safe)
     static const int force_mt = cn_exp_env("CASSNAT_FFN_MT") ? atoi(cn_exp_env("CASSNAT_FFN_MT")) : 0;
     const int mt = force_mt ? force_mt : (a.M > 32 ? 2 : 1);
+    if (a.act == FF_ACT_SWISH)  // (production variants only: the timing experiments are the ReLU kernel's)
+        return mt == 2 ? launch_ffn_variant<2, 0, FF_ACT_SWISH>(p, s) : launch_ffn_variant<1, 0, FF_ACT_SWISH>(p, s);
+    if (a.act != FF_ACT_RELU) {
+        cn_set_error("ffn_fused: unknown activation");
+        return -1;
+    }
     if (mt == 2) {
         if (dbg == 3) return launch_ffn_variant<2, 3>(p, s);
         return launch_ffn_variant<2, 0>(p, s);

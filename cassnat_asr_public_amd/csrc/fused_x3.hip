@@ -1,5 +1,6 @@
 // Fused position-wise feed-forward sublayer of the split-bf16 ("bf16x3") engine, gfx950, d_model = 256:
 //     x <- x + W2 . relu(W1 . LN(x) + b1) + b2          [and optionally  xn_next <- LN_next(x), split-bf16]
+// (SWISH, plain form only: h * sigmoid(h) instead of relu(h) - the conformer AST's decoder layers, src/models/conformer.py:30)
 // Same sublayer and the same structure as fused.hip (SublayerConnection(LayerNorm -> PositionwiseFeedForward): src/models/
 // modules/utils.py:23-32, positionff.py:15-16, norm.py:15-18), in the parity-grade precision: every operand is a (bf16 hi,
 // bf16 lo) pair and every product three MFMAs (lo.hi + hi.lo + hi.hi, fp32 accumulation; common.h split_t).  The generic
@@ -93,8 +94,9 @@ static_assert(FX_LDS_TAIL == 160 * 1024, "LDS budget (row-chain form)");
 // stream, the register sets, the LDS planes and the request / read pattern are the split form's: a weight group is
 // [hi(k0)][e4m3 bytes 0-15][hi(k1)][e4m3 bytes 16-31] per lane, the second LDS plane holds the activations' e4m3 fragments.
 // The hidden tile's e4m3 operand needs every lane's 32 hidden units: the half-waves trade their 16 (v_permlane32_swap).
-template <bool PRO, bool TAIL, bool MIXF = false>
+template <bool PRO, bool TAIL, bool MIXF = false, bool SWISH = false>
 __global__ __launch_bounds__(256) void ffn_x3_kernel(FfnX3Params p) {
+    static_assert(!SWISH || (!PRO && !TAIL && !MIXF), "Swish: the plain split form only");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* xn_s = smem;                                          // [plane][mt][16 k-steps][64 lanes][16 B]
     float* b1_s = reinterpret_cast<float*>(smem + 2 * FX_PLANE);         // [dff]
@@ -312,7 +314,8 @@ __global__ __launch_bounds__(256) void ffn_x3_kernel(FfnX3Params p) {
     {                                                                                                  \
         const f32x4 bv = *reinterpret_cast<const f32x4*>(b1_s + 32 * (ft0 + (tile)) + 4 * half + 8 * (g)); \
         _Pragma("unroll") for (int e = 0; e < 4; ++e) _Pragma("unroll") for (int mt = 0; mt < FX_MT; ++mt) { \
-            const float h_ = fmaxf(xh[mt][4 * (g) + e] + bv[e], 0.f);                                  \
+            const float v_ = xh[mt][4 * (g) + e] + bv[e];                                              \
+            const float h_ = SWISH ? v_ * (1.f / (1.f + __expf(-v_))) : fmaxf(v_, 0.f);                \
             const bf16 hh_ = (bf16)h_;                                                                 \
             pbh[mt][(g) >> 1][4 * ((g) & 1) + e] = hh_;                                                \
             pbl[mt][(g) >> 1][4 * ((g) & 1) + e] = (bf16)(h_ - (float)hh_);                            \
@@ -646,26 +649,35 @@ int launch_ffn_x3(const FfnX3Args& a, hipStream_t s) {
     p.tail = PxPhase{reinterpret_cast<const unsigned char*>(a.tail_p), a.tail_b, a.tail_out, a.ld_tail, nullptr, 0, 1.f, a.M, a.tail_n};
     const dim3 grid(cn_ceil_div(p.M, 32 * FX_MT));
     p.mixq = reinterpret_cast<const int*>(reinterpret_cast<const unsigned char*>(a.wst) + (size_t)(a.dff / 32) * 64 * 1024);
-#define FX_LAUNCH(PRO_, TAIL_, MIX_, LDS_)                                                                                 \
+#define FX_LAUNCH(PRO_, TAIL_, MIX_, SW_, LDS_)                                                                            \
     {                                                                                                                      \
         static CnAttrOnce attr_once;                                                                                       \
         int attr_dev;                                                                                                      \
         if (attr_once.need(&attr_dev)) {                                                                                   \
-            CN_HIP_CHECK(hipFuncSetAttribute((const void*)ffn_x3_kernel<PRO_, TAIL_, MIX_>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_)); \
+            CN_HIP_CHECK(hipFuncSetAttribute((const void*)ffn_x3_kernel<PRO_, TAIL_, MIX_, SW_>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_)); \
             attr_once.mark(attr_dev);                                                                                      \
         }                                                                                                                  \
-        hipLaunchKernelGGL((ffn_x3_kernel<PRO_, TAIL_, MIX_>), grid, dim3(256), LDS_, s, p);                                \
+        hipLaunchKernelGGL((ffn_x3_kernel<PRO_, TAIL_, MIX_, SW_>), grid, dim3(256), LDS_, s, p);                    \
     }
-    if (a.mix) {
-        if (pro && tail) FX_LAUNCH(true, true, true, FX_LDS_TAIL)
-        else if (pro) FX_LAUNCH(true, false, true, FX_LDS)
-        else if (tail) FX_LAUNCH(false, true, true, FX_LDS_TAIL)
-        else FX_LAUNCH(false, false, true, FX_LDS)
+    if (a.act == FF_ACT_SWISH) {
+        if (a.mix || pro || tail) {
+            cn_set_error("ffn_x3: the Swish activation runs in the plain split form only (no mixed arithmetic, no row-chain form)");
+            return -1;
+        }
+        FX_LAUNCH(false, false, false, true, FX_LDS)
+    } else if (a.act != FF_ACT_RELU) {
+        cn_set_error("ffn_x3: unknown activation");
+        return -1;
+    } else if (a.mix) {
+        if (pro && tail) FX_LAUNCH(true, true, true, false, FX_LDS_TAIL)
+        else if (pro) FX_LAUNCH(true, false, true, false, FX_LDS)
+        else if (tail) FX_LAUNCH(false, true, true, false, FX_LDS_TAIL)
+        else FX_LAUNCH(false, false, true, false, FX_LDS)
     } else {
-        if (pro && tail) FX_LAUNCH(true, true, false, FX_LDS_TAIL)
-        else if (pro) FX_LAUNCH(true, false, false, FX_LDS)
-        else if (tail) FX_LAUNCH(false, true, false, FX_LDS_TAIL)
-        else FX_LAUNCH(false, false, false, FX_LDS)
+        if (pro && tail) FX_LAUNCH(true, true, false, false, FX_LDS_TAIL)
+        else if (pro) FX_LAUNCH(true, false, false, false, FX_LDS)
+        else if (tail) FX_LAUNCH(false, true, false, false, FX_LDS_TAIL)
+        else FX_LAUNCH(false, false, false, false, FX_LDS)
     }
 #undef FX_LAUNCH
     CN_HIP_CHECK(hipGetLastError());

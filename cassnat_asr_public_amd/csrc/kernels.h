@@ -226,6 +226,8 @@ int launch_logsoftmax_topk(const float* logits, int M, int V, int ldl, float tem
 
 // ---- fused FFN sublayer, bf16 / d_model == 256                                     (fused.hip)
 //   x <- x + W2 relu(W1 LN(x) + b1) + b2 ;  optionally xn_out <- LN_next(x) in bf16
+// hidden activation of the fused feed-forward kernels: ReLU (transformer blocks) or Swish (the conformer AST's decoder layers)
+enum { FF_ACT_RELU = 0, FF_ACT_SWISH = 1 };
 struct FfnFusedArgs {
     float* x = nullptr;
     const float *ln_a = nullptr, *ln_b = nullptr;
@@ -242,6 +244,7 @@ struct FfnFusedArgs {
     // are not used by the split launch itself
     int nslice = 1;
     float* partial = nullptr;
+    int act = FF_ACT_RELU;
 };
 int launch_ffn_fused(const FfnFusedArgs& a, hipStream_t s);
 int launch_ffn_reduce(float* x, const float* partial, int nslice, const float* b2, const float* nln_a, const float* nln_b,
@@ -272,6 +275,9 @@ struct FfnX3Args {
     const float* tail_b = nullptr;
     void* tail_out = nullptr;
     int tail_n = 0, ld_tail = 0;
+    // FF_ACT_SWISH: Swish hidden activation, in the plain split form only - not mix (its e4m3 cross terms have no range guard on
+    // the hidden operands) and not the row-chain form
+    int act = FF_ACT_RELU;
 };
 bool ffn_x3_applies(int d, int dff);
 int launch_ffn_x3(const FfnX3Args& a, hipStream_t s);

@@ -101,6 +101,7 @@ struct Layer {
     Linear w1, w2;
     void *w1p = nullptr, *w2p = nullptr;  // fused-FFN fragment streams (bf16, d_model == 256); then w1/w2 hold biases only
     void* wx3 = nullptr;  // split-bf16 engine: the fused-FFN stream of fused_x3.hip (hi and lo fragments); w1/w2 hold biases only
+    bool ff_swish = false;  // feed_forward's hidden activation is Swish, residual scale 1 (the conformer AST's decoder layers) - else ReLU
     bool has_self = false, has_src = false;
 };
 
@@ -518,7 +519,8 @@ struct Packer {
         for (int i = 0; i < nnorm; ++i) L.n[i] = norm(p + ".sublayer." + std::to_string(i) + ".norm", d);
         return L;
     }
-    // feed-forward weights: fragment streams for the fused kernel when it applies, plain matrices otherwise
+    // feed-forward weights: fragment streams for the fused kernel when it applies, plain matrices otherwise (L.ff_swish set
+    // before: a Swish layer's split-bf16 stream is the plain split form's, never the mixed arithmetic's)
     void ffn(Layer& L, const std::string& p, int64_t dff, int64_t d) {
         const bool fused = m->prec == CN_PREC_BF16 && d == 256 && dff % 128 == 0 && dff <= 2048;
         if (m->prec == CN_PREC_X3 && ffn_x3_applies((int)d, (int)dff)) {
@@ -526,7 +528,8 @@ struct Packer {
             if (fill) {
                 const HostTensor* t1 = find(p + ".feed_forward.w_1.weight", {dff, d});
                 const HostTensor* t2 = find(p + ".feed_forward.w_2.weight", {d, dff});
-                if (t1 && t2) pack_ffn_x3(t1->data.data(), t2->data.data(), (int)dff, reinterpret_cast<uint16_t*>(&host[ax]), ffn_mix_applies());
+                if (t1 && t2)
+                    pack_ffn_x3(t1->data.data(), t2->data.data(), (int)dff, reinterpret_cast<uint16_t*>(&host[ax]), !L.ff_swish && ffn_mix_applies());
             }
             L.wx3 = reinterpret_cast<void*>(ax);
             L.w1.N = (int)dff;
@@ -916,9 +919,10 @@ int build_weights(cn_model* m) {
             m->linear_f8q = reinterpret_cast<int*>(qat);
         }
     }
-    auto self_layer = [&](const std::string& p, const std::string& att, int64_t dff, int nnorm) {
+    auto self_layer = [&](const std::string& p, const std::string& att, int64_t dff, int nnorm, bool ff_swish = false) {
         Layer L;
         L.has_self = true;
+        L.ff_swish = ff_swish;
         L.qkv = pk.linear({p + "." + att + ".linears.0", p + "." + att + ".linears.1", p + "." + att + ".linears.2"}, d, d);
         L.self_o = pk.linear({p + "." + att + ".linears.3"}, d, d);
         pk.ffn(L, p, dff, d);
@@ -1071,7 +1075,8 @@ int build_weights(cn_model* m) {
             add_src(L, p);
             m->mad.push_back(L);
         } else {
-            Layer L = self_layer(p, "self_attn", c.d_decff, 3);
+            // (cfg.ast == 1 with conf_enc: the reference's models/conformer.py - transformer decoder layers with Swish FFNs)
+            Layer L = self_layer(p, "self_attn", c.d_decff, 3, c.ast == 1 && c.conf_enc);
             add_src(L, p);
             m->mad.push_back(L);
         }
@@ -1452,7 +1457,7 @@ int run_ln(cn_model* m, const Norm& n, const float* x, void* y, int M, hipStream
 int run_ffn(cn_model* m, const Layer& L, const Norm& n, float* x, int M, const Norm* next, void* next_out,
             hipStream_t s) {
     const int d = m->cfg.d_model;
-    if (L.wx3) {  // split-bf16 engine: LN + w_1 + ReLU + w_2 + residual (+ next LN) in one launch, 3 MFMAs per product
+    if (L.wx3) {  // split-bf16 engine: LN + w_1 + ReLU / Swish + w_2 + residual (+ next LN) in one launch, 3 MFMAs per product
         ProfScope ps(m, "ffn_fused_x3", 4.0 * M * (double)L.w1.N * d,
                      (double)M * d * 8 + 2.0 * L.w1.N * d * 4 + (next ? (double)M * d * 4 : 0.0), s);
         FfnX3Args a;
@@ -1460,7 +1465,8 @@ int run_ffn(cn_model* m, const Layer& L, const Norm& n, float* x, int M, const N
         a.ln_a = n.a;
         a.ln_b = n.b;
         a.wst = L.wx3;
-        a.mix = ffn_mix_applies();
+        a.mix = !L.ff_swish && ffn_mix_applies();  // (as pk.ffn packed the stream)
+        a.act = L.ff_swish ? FF_ACT_SWISH : FF_ACT_RELU;
         a.b1 = L.w1.b;
         a.b2 = L.w2.b;
         if (next) {
@@ -1492,10 +1498,14 @@ int run_ffn(cn_model* m, const Layer& L, const Norm& n, float* x, int M, const N
         a.M = M;
         a.d = d;
         a.dff = L.w1.N;
+        a.act = L.ff_swish ? FF_ACT_SWISH : FF_ACT_RELU;
         return launch_ffn_fused(a, s);
     }
     CN_TRY(run_ln(m, n, x, m->xn, M, s));
-    CN_TRY(run_linear(m, "ffn_w1_relu", L.w1, m->xn, d, m->hbuf, L.w1.N, 0, M, CN_EPI_RELU, nullptr, 0, s));
+    if (L.ff_swish)
+        CN_TRY(run_linear(m, "ffn_w1_swish", L.w1, m->xn, d, m->hbuf, L.w1.N, 0, M, CN_EPI_SWISH, nullptr, 0, s));
+    else
+        CN_TRY(run_linear(m, "ffn_w1_relu", L.w1, m->xn, d, m->hbuf, L.w1.N, 0, M, CN_EPI_RELU, nullptr, 0, s));
     CN_TRY(run_linear(m, "ffn_w2_resid", L.w2, m->hbuf, L.w1.N, x, d, 1, M, CN_EPI_RESID, x, d, s));
     if (next) CN_TRY(run_ln(m, *next, x, next_out, M, s));
     return 0;
@@ -1505,7 +1515,7 @@ int run_ffn(cn_model* m, const Layer& L, const Norm& n, float* x, int M, const N
 // attention kernel  x += Wo . ctx + bo;  x += FFN(LN1 x);  then either LN_next(x) -> next_out (split-bf16 rows) or, with `tail`, the
 // next attention's projection of it -> tail_out (the activations between the three products never leave LDS / registers).
 bool x3_chain_applies(const cn_model* m, const Layer& L, const Linear* tail) {
-    return m->prec == CN_PREC_X3 && L.wx3 && L.self_o.px3 && L.self_o.N == 256 && L.self_o.K == 256 &&
+    return m->prec == CN_PREC_X3 && L.wx3 && !L.ff_swish && L.self_o.px3 && L.self_o.N == 256 && L.self_o.K == 256 &&
            (!tail || (tail->px3 && tail->K == 256 && tail->N % 128 == 0 && tail->N <= 1024));
 }
 int run_x3_chain(cn_model* m, const Layer& L, const Norm& n1, float* x, int M, const Norm& next, void* next_out, const Linear* tail,
@@ -2395,6 +2405,14 @@ extern "C" int cn_model_create(const cn_config* cfg, cn_model** out) {
     }
     if (c.fp8_scope < 0 || c.fp8_scope > 7 || ((c.fp8_scope & CN_FP8_LINEAR) && !(c.fp8_scope & CN_FP8_CONV2)) || c.fp8_ffn_first_layer < 0) {
         cn_set_error("cn_model_create: fp8_scope is a mask of CN_FP8_CONV2 | CN_FP8_LINEAR | CN_FP8_FFN (LINEAR needs CONV2), fp8_ffn_first_layer >= 0");
+        return -1;
+    }
+    // cfg.ast == 1 with conf_enc = the reference's models/conformer.py (conformer encoder, transformer decoder with Swish FFNs);
+    // the reference has no autoregressive model with conformer decoder blocks, and no conformer TransformerLM
+    if ((c.ast == 1 && c.conf_dec) || (c.ast == 2 && (c.conf_enc || c.conf_dec))) {
+        cn_set_error(c.ast == 1 ? "cn_model_create: the autoregressive model (ast = 1) has no conformer decoder (conf_dec = 1): the reference "
+                                  "defines none (models/conformer.py keeps transformer decoder layers)"
+                                : "cn_model_create: the TransformerLM (ast = 2) has no conformer blocks");
         return -1;
     }
     if (c.input_size < 4 || c.vocab_size < 4 || c.max_batch < 1 || c.max_frames < 4 || c.n_enc < 0 || c.n_extra < 0 ||
@@ -3738,10 +3756,13 @@ extern "C" int cn_op_logsoftmax_topk(const float* logits, int32_t M, int32_t V, 
     return launch_logsoftmax_topk(logits, M, V, V, temperature, k, idx, val, (hipStream_t)stream);
 }
 
-extern "C" int cn_op_ffn_fused(float* x_dev, const float* ln_a_dev, const float* ln_b_dev, const float* w1_host,
-                               const float* b1_dev, const float* w2_host, const float* b2_dev, const float* nln_a_dev,
-                               const float* nln_b_dev, void* xn_out_dev, int32_t M, int32_t dff, float eps,
-                               int32_t nslice, void* stream) {
+static int op_ffn_fused_impl(float* x_dev, const float* ln_a_dev, const float* ln_b_dev, const float* w1_host, const float* b1_dev,
+                             const float* w2_host, const float* b2_dev, const float* nln_a_dev, const float* nln_b_dev, void* xn_out_dev,
+                             int32_t M, int32_t dff, float eps, int32_t nslice, int32_t act, void* stream) {
+    if (act != CN_ACT_RELU && act != CN_ACT_SWISH) {
+        cn_set_error("cn_op_ffn_fused_act: act must be CN_ACT_RELU or CN_ACT_SWISH");
+        return -1;
+    }
     if (dff <= 0 || dff % 128 != 0 || dff > 2048) {
         cn_set_error("cn_op_ffn_fused: d_ff must be a positive multiple of 128, at most 2048");
         return -1;
@@ -3770,6 +3791,7 @@ extern "C" int cn_op_ffn_fused(float* x_dev, const float* ln_a_dev, const float*
     a.d = 256;
     a.dff = dff;
     a.eps = eps;
+    a.act = act == CN_ACT_SWISH ? FF_ACT_SWISH : FF_ACT_RELU;
     void* part = nullptr;
     if (nslice > 1) {  // d_ff split + reduce (the decode-step form)
         CN_HIP_CHECK(hipMalloc(&part, (size_t)nslice * M * 256 * 4));
@@ -3790,10 +3812,30 @@ extern "C" int cn_op_ffn_fused(float* x_dev, const float* ln_a_dev, const float*
     return rc;
 }
 
+extern "C" int cn_op_ffn_fused(float* x_dev, const float* ln_a_dev, const float* ln_b_dev, const float* w1_host,
+                               const float* b1_dev, const float* w2_host, const float* b2_dev, const float* nln_a_dev,
+                               const float* nln_b_dev, void* xn_out_dev, int32_t M, int32_t dff, float eps,
+                               int32_t nslice, void* stream) {
+    return op_ffn_fused_impl(x_dev, ln_a_dev, ln_b_dev, w1_host, b1_dev, w2_host, b2_dev, nln_a_dev, nln_b_dev, xn_out_dev, M, dff, eps,
+                             nslice, CN_ACT_RELU, stream);
+}
+
+extern "C" int cn_op_ffn_fused_act(float* x_dev, const float* ln_a_dev, const float* ln_b_dev, const float* w1_host,
+                                   const float* b1_dev, const float* w2_host, const float* b2_dev, const float* nln_a_dev,
+                                   const float* nln_b_dev, void* xn_out_dev, int32_t M, int32_t dff, float eps,
+                                   int32_t nslice, int32_t act, void* stream) {
+    return op_ffn_fused_impl(x_dev, ln_a_dev, ln_b_dev, w1_host, b1_dev, w2_host, b2_dev, nln_a_dev, nln_b_dev, xn_out_dev, M, dff, eps,
+                             nslice, act, stream);
+}
+
 // the same sublayer in the split-bf16 precision (fused_x3.hip); xn_out_dev: split-bf16 [M][256] or NULL
-extern "C" int cn_op_ffn_x3(float* x_dev, const float* ln_a_dev, const float* ln_b_dev, const float* w1_host, const float* b1_dev,
-                            const float* w2_host, const float* b2_dev, const float* nln_a_dev, const float* nln_b_dev,
-                            void* xn_out_dev, int32_t M, int32_t dff, float eps, int32_t mix, void* stream) {
+static int op_ffn_x3_impl(float* x_dev, const float* ln_a_dev, const float* ln_b_dev, const float* w1_host, const float* b1_dev,
+                          const float* w2_host, const float* b2_dev, const float* nln_a_dev, const float* nln_b_dev, void* xn_out_dev,
+                          int32_t M, int32_t dff, float eps, int32_t mix, int32_t act, void* stream) {
+    if (act != CN_ACT_RELU && (act != CN_ACT_SWISH || mix)) {
+        cn_set_error("cn_op_ffn_x3_act: act must be CN_ACT_RELU, or CN_ACT_SWISH without the mixed arithmetic");
+        return -1;
+    }
     if (!ffn_x3_applies(256, dff)) {
         cn_set_error("cn_op_ffn_x3: d_ff must be a positive multiple of 128, at most 2048");
         return -1;
@@ -3819,6 +3861,7 @@ extern "C" int cn_op_ffn_x3(float* x_dev, const float* ln_a_dev, const float* ln
     a.d = 256;
     a.dff = dff;
     a.eps = eps;
+    a.act = act == CN_ACT_SWISH ? FF_ACT_SWISH : FF_ACT_RELU;
     int rc = launch_ffn_x3(a, (hipStream_t)stream);
     hipError_t e = hipStreamSynchronize((hipStream_t)stream);
     (void)hipFree(dw);
@@ -3827,6 +3870,20 @@ extern "C" int cn_op_ffn_x3(float* x_dev, const float* ln_a_dev, const float* ln
         rc = -2;
     }
     return rc;
+}
+
+extern "C" int cn_op_ffn_x3(float* x_dev, const float* ln_a_dev, const float* ln_b_dev, const float* w1_host, const float* b1_dev,
+                            const float* w2_host, const float* b2_dev, const float* nln_a_dev, const float* nln_b_dev,
+                            void* xn_out_dev, int32_t M, int32_t dff, float eps, int32_t mix, void* stream) {
+    return op_ffn_x3_impl(x_dev, ln_a_dev, ln_b_dev, w1_host, b1_dev, w2_host, b2_dev, nln_a_dev, nln_b_dev, xn_out_dev, M, dff, eps, mix,
+                          CN_ACT_RELU, stream);
+}
+
+extern "C" int cn_op_ffn_x3_act(float* x_dev, const float* ln_a_dev, const float* ln_b_dev, const float* w1_host, const float* b1_dev,
+                                const float* w2_host, const float* b2_dev, const float* nln_a_dev, const float* nln_b_dev,
+                                void* xn_out_dev, int32_t M, int32_t dff, float eps, int32_t mix, int32_t act, void* stream) {
+    return op_ffn_x3_impl(x_dev, ln_a_dev, ln_b_dev, w1_host, b1_dev, w2_host, b2_dev, nln_a_dev, nln_b_dev, xn_out_dev, M, dff, eps, mix,
+                          act, stream);
 }
 
 // The row-chain form of the split-bf16 engine as one op (fused_x3.hip PRO / TAIL): x += Wo . ctx + bo; x += FFN(LN1 x); then
@@ -4340,6 +4397,7 @@ int ast_step_run(cn_model* m, int n, int pos, const int32_t* tok_dev, const int3
             a.dff = L.w1.N;
             a.nslice = ffn_slices;
             a.partial = reinterpret_cast<float*>(m->hbuf);  // [slices][n][256] fp32 <= the [rows][d_ff] hidden buffer
+            a.act = L.ff_swish ? FF_ACT_SWISH : FF_ACT_RELU;
             CN_TRY(launch_ffn_fused(a, s));
             CN_TRY(launch_ffn_reduce(x, a.partial, ffn_slices, L.w2.b, nx.a, nx.b, last ? m->dec_h : m->xn, n, 1e-6f, s));
             have_ln = true;

@@ -80,6 +80,16 @@ PRESETS_AST = {
     # BASELINE configs[3]: AST beam=10 on the config-2 encoder
     "config4": dict(input_size=80, d_model=256, n_head=4, d_ff=2048, d_encff=2048, N_enc=12, N_dec=6, vocab_size=5000),
 }
+# The conformer AST model (src/models/conformer.py; egs/librispeech/conf/rank_model.yaml's family): conformer encoder with
+# relative positions under transformer decoder layers whose FFN is Swish.  The widths are d_encff / d_decff (d_ff is unused).
+CONFORMER_AST = dict(model_type="conformer", use_conv_enc=True, pos_type="relative", share_ff=False)
+PRESETS_AST.update({
+    "tiny_conf_ast": dict(input_size=80, d_model=128, n_head=2, d_ff=256, d_encff=256, d_decff=256, N_enc=2, N_dec=2, vocab_size=40,
+                          enc_kernel_size=7, enc_max_relative_len=5, **CONFORMER_AST),
+    # config 4's decoder (d 256, 6 layers of d_ff 2048, V 5000) behind the shipped ranker's conformer encoder shape at d 256
+    "config4_conf": dict(input_size=80, d_model=256, n_head=4, d_ff=2048, d_encff=1024, d_decff=2048, N_enc=12, N_dec=6,
+                         vocab_size=5000, enc_kernel_size=31, enc_max_relative_len=20, **CONFORMER_AST),
+})
 AST_DECODE_DEFAULTS = dict(ctc_weight=0.3, max_decode_ratio=0.3, T=1.0, ctc_beam=15, beam_width=10, lm_weight=0,
                            length_penalty=0, ctc_alpha=1, interctc_alpha=0, interctc_layer=0, decode_type="ctc_att")
 
@@ -162,6 +172,72 @@ def param_shapes_ast(args):
     norm("decoder.norm")
     lin("ctc_generator.proj", V, d)
     lin("att_generator.proj", V, d)
+    return shapes
+
+
+def param_shapes_conformer_ast(args):
+    """Named parameters of the reference's conformer AST model (src/models/conformer.py:18-45 on models/transformer.py's
+    registration order): the conformer encoder of blocks/conformer_blocks.py (self_attn, feed_forward1, conv_module,
+    feed_forward2, sublayer.0-3) and the transformer decoder layers with FFNs of width d_decff."""
+    d, V, F = args.d_model, args.vocab_size, args.input_size
+    f2 = ((F - 1) // 2) // 2 + 1
+    dk = d // args.n_head
+    shapes = OrderedDict()
+
+    def lin(prefix, n_out, n_in):
+        shapes[prefix + ".weight"] = (n_out, n_in)
+        shapes[prefix + ".bias"] = (n_out,)
+
+    def mha(prefix):
+        for i in range(4):
+            lin(f"{prefix}.linears.{i}", d, d)
+
+    def norm(prefix):
+        shapes[prefix + ".a_2"] = (d,)
+        shapes[prefix + ".b_2"] = (d,)
+
+    shapes["src_embed.conv.0.weight"] = (d, 1, 3, 3)
+    shapes["src_embed.conv.0.bias"] = (d,)
+    shapes["src_embed.conv.2.weight"] = (d, d, 3, 3)
+    shapes["src_embed.conv.2.bias"] = (d,)
+    lin("src_embed.linear_out", d, d * f2)
+    shapes["src_embed.pos_enc.embedding.weight"] = (2 * args.enc_max_relative_len + 1, d)
+    shapes["tgt_embed.0.lut.weight"] = (V, d)
+    for n in range(args.N_enc):
+        p = f"encoder.layers.{n}"
+        shapes[p + ".self_attn.pos_bias_u"] = (args.n_head, dk)
+        shapes[p + ".self_attn.pos_bias_v"] = (args.n_head, dk)
+        mha(p + ".self_attn")
+        shapes[p + ".self_attn.linear_pos.weight"] = (d, d)
+        lin(p + ".feed_forward1.w_1", args.d_encff, d)
+        lin(p + ".feed_forward1.w_2", d, args.d_encff)
+        shapes[p + ".conv_module.pointwise_conv1.weight"] = (2 * d, d, 1)
+        shapes[p + ".conv_module.pointwise_conv1.bias"] = (2 * d,)
+        shapes[p + ".conv_module.depthwise_conv.weight"] = (d, 1, args.enc_kernel_size)
+        shapes[p + ".conv_module.depthwise_conv.bias"] = (d,)
+        shapes[p + ".conv_module.norm.weight"] = (d,)
+        shapes[p + ".conv_module.norm.bias"] = (d,)
+        shapes[p + ".conv_module.pointwise_conv2.weight"] = (d, d, 1)
+        shapes[p + ".conv_module.pointwise_conv2.bias"] = (d,)
+        lin(p + ".feed_forward2.w_1", args.d_encff, d)
+        lin(p + ".feed_forward2.w_2", d, args.d_encff)
+        for i in range(4):
+            norm(p + f".sublayer.{i}.norm")
+    norm("encoder.norm")
+    for n in range(args.N_dec):
+        p = f"decoder.layers.{n}"
+        mha(p + ".self_attn")
+        mha(p + ".src_attn")
+        lin(p + ".feed_forward.w_1", args.d_decff, d)
+        lin(p + ".feed_forward.w_2", d, args.d_decff)
+        for i in range(3):
+            norm(p + f".sublayer.{i}.norm")
+    norm("decoder.norm")
+    lin("ctc_generator.proj", V, d)
+    lin("att_generator.proj", V, d)
+    if getattr(args, "interctc_alpha", 0) > 0:  # Generator(add_norm=True): proj, then norm
+        lin("interctc_generator.proj", V, d)
+        norm("interctc_generator.norm")
     return shapes
 
 
@@ -343,7 +419,7 @@ def make_state(args, seed=0, blank_bias=0.0, gain=1.0):
     rng = np.random.default_rng(seed)
     state = OrderedDict()
     if hasattr(args, "N_dec"):
-        shapes = param_shapes_ast(args)
+        shapes = param_shapes_conformer_ast(args) if getattr(args, "use_conv_enc", False) else param_shapes_ast(args)
     elif hasattr(args, "N") and not hasattr(args, "N_enc"):
         shapes = param_shapes_lm(args)
     elif getattr(args, "use_conv_dec", False) or getattr(args, "use_conv_enc", False):

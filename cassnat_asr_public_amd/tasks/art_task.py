@@ -22,7 +22,7 @@ import torch.distributed as dist
 
 from .. import dist as cdist
 from ..data.vocab import Vocab
-from ..models import make_transformer
+from ..models import make_conformer, make_transformer
 from ..utils import util
 from ..utils.beam_decode import ctc_beam_decode
 from .base_task import BaseTask
@@ -69,9 +69,12 @@ class ArtTask(BaseTask):
 
     def set_model(self, args):
         assert args.input_size == (args.left_ctx + args.right_ctx + 1) // args.skip_frame * args.n_features
-        if args.model_type != "transformer":
-            raise NotImplementedError("only model_type 'transformer' is on the accelerated AST path")
-        self.model = make_transformer(args.input_size, args)
+        if args.model_type == "transformer":
+            self.model = make_transformer(args.input_size, args)
+        elif args.model_type == "conformer":  # src/tasks/art_task.py:32-35
+            self.model = make_conformer(args.input_size, args)
+        else:
+            raise NotImplementedError("model_type '%s' (the accelerated AST path knows transformer, conformer)" % args.model_type)
 
     def load_lm_model(self, args):
         if getattr(args, "lm_weight", 0) > 0:

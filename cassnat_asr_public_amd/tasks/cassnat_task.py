@@ -148,9 +148,13 @@ class CassNATTask(BaseTask):
 
                 lm_model = make_lm_model(lm_args)
             else:
-                if getattr(lm_args, "model_type", "transformer") != "transformer":
-                    raise NotImplementedError("the conformer AST baseline is outside the accelerated path")
-                from ..models.transformer import make_model as make_ast_model
+                model_type = getattr(lm_args, "model_type", "transformer")
+                if model_type == "transformer":
+                    from ..models.transformer import make_model as make_ast_model
+                elif model_type == "conformer":  # src/tasks/cassnat_task.py:109-115 (egs/librispeech/conf/rank_model.yaml)
+                    from ..models.conformer import make_model as make_ast_model
+                else:
+                    raise NotImplementedError("at_baseline model_type '%s' is not on the accelerated path" % model_type)
 
                 lm_args.interctc_alpha = 0
                 lm_model = make_ast_model(args.input_size, lm_args)

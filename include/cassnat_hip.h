@@ -46,7 +46,12 @@ typedef struct cn_config {
     int32_t max_frames;
     int32_t device; /* HIP device ordinal */
     int32_t ast;    /* 1: autoregressive (AST) model: n_mix_dec = N_dec decoder layers + tgt_embed (src/models/transformer.py);
-                       2: TransformerLM (src/models/lm.py): n_enc layers of width d_encff + text_embed + out_generator */
+                       2: TransformerLM (src/models/lm.py): n_enc layers of width d_encff + text_embed + out_generator.
+                       ast = 1 with conf_enc = 1 is the reference's conformer AST model (src/models/conformer.py, pos_type
+                       "relative"): the conformer encoder below (enc_max_rel, enc_kernel, d_encff; relative positions, no absolute
+                       PE on the source side) under transformer decoder layers whose feed-forward (width d_decff) is Swish with
+                       residual scale 1; the target side keeps the absolute sinusoid table.  ast = 1 with conf_dec = 1 and ast = 2
+                       with either conformer flag are refused by cn_model_create (the reference defines no such model). */
     /* conformer variants (src/models/cassnat.py:29-57, pos_type "relative"): macaron Swish FFNs, relative-position self
      * attention, convolution module.  conf_enc / conf_dec = args.use_conv_enc / use_conv_dec. */
     int32_t conf_enc, conf_dec;
@@ -378,6 +383,17 @@ int cn_op_ffn_fused(float* x_dev, const float* ln_a_dev, const float* ln_b_dev, 
 int cn_op_ffn_x3(float* x_dev, const float* ln_a_dev, const float* ln_b_dev, const float* w1_host, const float* b1_dev,
                  const float* w2_host, const float* b2_dev, const float* nln_a_dev, const float* nln_b_dev, void* xn_out_dev,
                  int32_t M, int32_t dff, float eps, int32_t mix, void* stream);
+/* The two sublayers above with a choice of hidden activation: act = CN_ACT_RELU (what cn_op_ffn_fused / cn_op_ffn_x3 run) or
+ * CN_ACT_SWISH, h * sigmoid(h) on h = W1 . LN(x) + b1 with residual scale 1 - the decoder feed-forward of the conformer AST model
+ * (src/models/conformer.py:30).  cn_op_ffn_x3_act: Swish needs mix == 0 (the engine runs Swish in the plain split form only). */
+enum { CN_ACT_RELU = 0, CN_ACT_SWISH = 1 };
+int cn_op_ffn_fused_act(float* x_dev, const float* ln_a_dev, const float* ln_b_dev, const float* w1_host,
+                        const float* b1_dev, const float* w2_host, const float* b2_dev, const float* nln_a_dev,
+                        const float* nln_b_dev, void* xn_out_dev, int32_t M, int32_t dff, float eps, int32_t nslice,
+                        int32_t act, void* stream);
+int cn_op_ffn_x3_act(float* x_dev, const float* ln_a_dev, const float* ln_b_dev, const float* w1_host, const float* b1_dev,
+                     const float* w2_host, const float* b2_dev, const float* nln_a_dev, const float* nln_b_dev, void* xn_out_dev,
+                     int32_t M, int32_t dff, float eps, int32_t mix, int32_t act, void* stream);
 /* the row-chain form of the split-bf16 engine (fused_x3.hip): attention output projection + residual, feed-forward sublayer, next
  * LayerNorm and (wt_host != null) the next attention's projection of it, in one launch; ctx_dev split-bf16 [M][256] or null;
  * weight matrices on the host, vectors on the device (positionff.py:15-16, attention.py:57-66, norm.py:15-18) */

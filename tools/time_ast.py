@@ -1,8 +1,11 @@
 """Timing of the autoregressive (AST) path at BASELINE configs[3] shape: same 12-layer encoder, 6 decoder layers, beam 10,
 ctc_beam 15, joint CTC/attention scoring; B utterances x 1000 frames.  Not the headline bench (bench.py measures
 configs[1]); prints one JSON line with utterances/s, ms per decode step and where a step's wall time goes.
+``--model conformer``: the conformer AST (models/conformer.py, synth preset config4_conf) - the same decoder (6 layers, d_decff
+2048, now Swish) behind a 12-layer conformer encoder.  Both models report the encoder pass (cn_ast_begin: encoder, cross K|V, CTC
+preparation) apart from the decoder steps: ``decoder_ms_per_step`` = (search - encoder) / steps.
 
-    python tools/time_ast.py [--batch 32] [--frames 1000] [--precision bf16] [--ctc-weight 0.3] [--ratio 0.3]
+    python tools/time_ast.py [--model transformer|conformer] [--batch 32] [--frames 1000] [--precision bf16] [--ctc-weight 0.3] [--ratio 0.3]
 """
 import argparse
 import json
@@ -13,8 +16,9 @@ import time
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from cassnat_asr_public_amd import synth  # noqa: E402
-from cassnat_asr_public_amd.models.transformer import make_model  # noqa: E402
+from cassnat_asr_public_amd import hip, synth  # noqa: E402
+from cassnat_asr_public_amd.models.conformer import make_model as make_conformer  # noqa: E402
+from cassnat_asr_public_amd.models.transformer import make_model as make_transformer  # noqa: E402
 
 
 class Vocab:
@@ -23,6 +27,7 @@ class Vocab:
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--model", choices=("transformer", "conformer"), default="transformer")
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--frames", type=int, default=1000)
     ap.add_argument("--precision", default="bf16")
@@ -33,7 +38,9 @@ def main():
                     help="decode pipelines (engine handle + HIP stream + host thread each) working on independent batches: a decode "
                          "step occupies a handful of CUs, so throughput - not latency - scales with pipelines")
     a = ap.parse_args()
-    args = synth.make_args_ast("config4", ctc_weight=a.ctc_weight, max_decode_ratio=a.ratio)
+    args = synth.make_args_ast("config4" if a.model == "transformer" else "config4_conf", ctc_weight=a.ctc_weight,
+                               max_decode_ratio=a.ratio)
+    make_model = make_transformer if a.model == "transformer" else make_conformer
     args.hip_precision = a.precision
     args.hip_max_batch = a.batch
     args.hip_max_frames = a.frames
@@ -54,7 +61,22 @@ def main():
         times.append(time.perf_counter() - t0)
     best = min(times[1:])
     steps = max(len(b[0]["hyp"]) for b in beams) - 1
+    # the encoder pass alone, on the same handle and workspace
+    eng = model.engine(a.batch, a.frames)
+    opts = hip.CnDecodeOpts(padding_idx=int(args.padding_idx), sos=1, beam_width=1)
+    use_ctc = a.ctc_weight > 0
+    enc = []
+    for r in range(a.reps + 1):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        eng.ast_begin(src, opts, use_ctc, steps + 1, a.batch * int(args.beam_width), int(args.ctc_beam) if use_ctc else 0)
+        torch.cuda.synchronize()
+        enc.append(time.perf_counter() - t0)
+    enc_best = min(enc[1:])
     out = {"workload": "BASELINE configs[3]: AST beam search, 12L enc / 6L dec, beam 10, ctc_beam 15",
+           "model": a.model, "encoder": "conformer (d_encff 1024, kernel 31, max_rel 20)" if a.model == "conformer" else "transformer",
+           "decoder_ffn": "swish" if a.model == "conformer" else "relu",
+           "encoder_ms": round(1e3 * enc_best, 3), "decoder_ms_per_step": round(1e3 * (best - enc_best) / max(steps, 1), 3),
            "batch": a.batch, "frames": a.frames, "precision": a.precision, "ctc_weight": a.ctc_weight,
            "decode_steps": steps, "sec_per_batch": round(best, 4), "utt_per_sec": round(a.batch / best, 2),
            "rtf": round(best / (a.batch * a.frames * 0.01), 6), "ms_per_decode_step": round(1e3 * best / max(steps, 1), 3),
