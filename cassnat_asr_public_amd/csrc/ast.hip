@@ -350,9 +350,11 @@ __global__ void ast_beam_init_kernel(AstBeamState st, int cur, int B, int bw, in
     if (s == 0) *st.live = B;
 }
 
-constexpr int BEAM_MAXW = 16, BEAM_MAXC = BEAM_MAXW + BEAM_MAXW * BEAM_MAXW;
+// beams and candidate lists up to 32 wide (conf/decode.yaml: beam_width 20, ctc_beam 30): at 32 / 32 the candidate list is 1056
+// entries, 38 KB of LDS
+constexpr int BEAM_MAXW = 32, BEAM_MAXC = BEAM_MAXW + BEAM_MAXW * BEAM_MAXW, BEAM_THREADS = 256;
 
-__global__ __launch_bounds__(128) void ast_beam_update_kernel(AstBeamState st, AstBeamStep q) {
+__global__ __launch_bounds__(BEAM_THREADS) void ast_beam_update_kernel(AstBeamState st, AstBeamStep q) {
     const int b = blockIdx.x, tid = threadIdx.x;
     const int bw = q.bw, K = q.K, L = q.L, cur = q.cur, nxt = cur ^ 1;
     __shared__ double ckey[BEAM_MAXC], cscore[BEAM_MAXC];
@@ -381,16 +383,19 @@ __global__ __launch_bounds__(128) void ast_beam_update_kernel(AstBeamState st, A
         cpar[tid] = fin_idx[tid];
         ccand[tid] = -1;
     }
-    for (int i = tid; i < nl * K; i += 128) {
+    for (int i = tid; i < nl * K; i += BEAM_THREADS) {
         const int li = i / K, c = i - li * K;
         const int s = b * bw + live_idx[li];
         const float att = q.att[(long long)s * K + c];
         // local = ctc_weight * (ctc - prev) + (1 - ctc_weight) * att, float32, one rounding per operation (transformer.py:205-206)
-        loc[li][c] = q.use_ctc ? __fadd_rn(__fmul_rn(q.w, __fsub_rn(q.ctc[(long long)s * K + c], st.ctc_prev[cur][s])), __fmul_rn(q.u, att))
-                               : att;
+        float v = q.use_ctc ? __fadd_rn(__fmul_rn(q.w, __fsub_rn(q.ctc[(long long)s * K + c], st.ctc_prev[cur][s])), __fmul_rn(q.u, att))
+                            : att;
+        // local += lm_weight * lm_prob.gather(1, indices) (transformer.py:208-209); without CTC `att` already holds the fused sum
+        if (q.use_lm && q.use_ctc) v = __fadd_rn(v, __fmul_rn(q.lw, q.lm[(long long)s * K + c]));
+        loc[li][c] = v;
     }
     __syncthreads();
-    for (int i = tid; i < nl * K; i += 128) {
+    for (int i = tid; i < nl * K; i += BEAM_THREADS) {
         const int li = i / K, c = i - li * K;
         const float v = loc[li][c];
         int r = 0;
@@ -408,7 +413,7 @@ __global__ __launch_bounds__(128) void ast_beam_update_kernel(AstBeamState st, A
     }
     __syncthreads();
     const int ncand = nf + nl * (K < bw ? K : bw);
-    for (int e = tid; e < ncand; e += 128) {
+    for (int e = tid; e < ncand; e += BEAM_THREADS) {
         const double k = ckey[e];
         int r = 0;
         for (int e2 = 0; e2 < ncand; ++e2) r += (ckey[e2] > k) || (ckey[e2] == k && e2 < e);
@@ -420,7 +425,7 @@ __global__ __launch_bounds__(128) void ast_beam_update_kernel(AstBeamState st, A
         const int e = newslot[qn];
         const int sn = b * bw + qn;
         if (e < 0) {  // fewer candidates than beam slots: an unused slot with harmless inputs for the next step
-            for (int t = tid; t < L; t += 128) st.anc[nxt][(long long)sn * L + t] = sn;
+            for (int t = tid; t < L; t += BEAM_THREADS) st.anc[nxt][(long long)sn * L + t] = sn;
             if (tid == 0) {
                 st.valid[nxt][sn] = 0;
                 st.len[nxt][sn] = 1;
@@ -434,7 +439,7 @@ __global__ __launch_bounds__(128) void ast_beam_update_kernel(AstBeamState st, A
         const int so = b * bw + cpar[e];
         const int len_o = st.len[cur][so];
         const bool grown = ccand[e] >= 0;
-        for (int t = tid; t < L; t += 128) {
+        for (int t = tid; t < L; t += BEAM_THREADS) {
             int tk = st.tok[cur][(long long)so * L + t], an = st.anc[cur][(long long)so * L + t];
             unsigned char ko = st.keyok[cur][(long long)so * L + t];
             if (grown) {
@@ -470,11 +475,11 @@ int launch_ast_beam_init(const AstBeamState& st, int cur, int B, int bw, int L, 
 
 int launch_ast_beam_update(const AstBeamState& st, const AstBeamStep& q, int B, hipStream_t s) {
     if (q.bw < 1 || q.bw > BEAM_MAXW || q.K < 1 || q.K > BEAM_MAXW) {
-        cn_set_error("ast beam: beam_width and candidate count must be in 1..16");
+        cn_set_error("ast beam: beam_width and candidate count must be in 1..32");
         return -1;
     }
     CN_HIP_CHECK(hipMemsetAsync(st.live, 0, sizeof(int), s));
-    hipLaunchKernelGGL(ast_beam_update_kernel, dim3(B), dim3(128), 0, s, st, q);
+    hipLaunchKernelGGL(ast_beam_update_kernel, dim3(B), dim3(BEAM_THREADS), 0, s, st, q);
     CN_HIP_CHECK(hipGetLastError());
     return 0;
 }

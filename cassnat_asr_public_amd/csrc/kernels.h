@@ -223,6 +223,11 @@ int launch_topk(const float* logp, int M, int V, int ldl, int k, int* idx, float
 // log_softmax(logits / T) and its per-row top-k in one pass (the (M, V) log-probabilities are not written)
 int launch_logsoftmax_topk(const float* logits, int M, int V, int ldl, float temperature, int k, int* idx, float* val,
                            hipStream_t s);
+// LM shallow fusion of the AST beam search (src/models/transformer.py:190-192, 208-209): top-k over V of
+// log_softmax(att / T) + fl(w * log_softmax(lm)) (no CTC), and the LM's log-probability at k given candidates (with CTC)
+int launch_logsoftmax_fuse_topk(const float* att, const float* lm, int M, int V, int ldl, float temperature, float w, int k,
+                                int* idx, float* val, hipStream_t s);
+int launch_logsoftmax_gather(const float* logits, int M, int V, int ldl, const int* cand, int k, float* out, hipStream_t s);
 
 // ---- fused FFN sublayer, bf16 / d_model == 256                                     (fused.hip)
 //   x <- x + W2 relu(W1 LN(x) + b1) + b2 ;  optionally xn_out <- LN_next(x) in bf16
@@ -451,8 +456,10 @@ struct AstBeamStep {
     const int* idx;    // [S][K] candidate tokens of this step
     const float* att;  // [S][K] their attention log-probabilities (sorted, best first)
     const float* ctc;  // [S][K] CTC prefix scores (use_ctc)
-    int cur, pos, bw, K, L, eos, sos, pad, use_ctc, use_lp;
+    const float* lm = nullptr;  // [S][K] LM log-probabilities at the candidates (use_lm with use_ctc; without CTC att holds the fused sum)
+    int cur, pos, bw, K, L, eos, sos, pad, use_ctc, use_lp, use_lm = 0;
     float w, u;        // ctc_weight, 1 - ctc_weight as float32
+    float lw = 0.f;    // lm_weight as float32
     double lp;
 };
 int launch_ast_beam_init(const AstBeamState& st, int cur, int B, int bw, int L, int sos, int pad, hipStream_t s);

@@ -14,6 +14,7 @@
 #include "kernels.h"
 
 static thread_local std::string g_last_error;
+static const int g_lib_tag = 0;  // its address tells this library's handles from the other build's
 void cn_set_error(const std::string& msg) { g_last_error = msg; }
 extern "C" const char* cn_last_error(void) { return g_last_error.c_str(); }
 extern "C" const char* cn_version(void) { return "cassnat_hip 0.1 (gfx950, 16-bit operand " CN_OP16_NAME ")"; }
@@ -245,7 +246,11 @@ struct cn_model {
     AstBeamState beam;  // device-side beam search state (cn_decode_ast)
     int beam_S = 0, beam_L = 0, beam_K = 0;
     int *beam_idx = nullptr;
-    float *beam_val = nullptr, *beam_ctc = nullptr;
+    float *beam_val = nullptr, *beam_ctc = nullptr, *beam_lm = nullptr;
+    // LM shallow fusion (cn_ast_attach_lm): the TransformerLM handle whose step runs beside this decoder's.  On an LM handle
+    // (cfg.ast = 2) the ast_ck / ast_cv / ast_logits fields above hold ITS step cache [layer][pos][slot][d] and logits.
+    cn_model* ast_lm = nullptr;
+    const void* lib_tag = nullptr;  // which of the two libraries created the handle (an attach never crosses them)
 
     // last call
     int B = 0, T = 0, T1 = 0, Tp = 0, U = 0, last_k = 0;
@@ -2423,6 +2428,7 @@ extern "C" int cn_model_create(const cn_config* cfg, cn_model** out) {
     CN_HIP_CHECK(hipSetDevice(c.device));
     cn_model* m = new cn_model();
     m->cfg = c;
+    m->lib_tag = &g_lib_tag;
     // fp8: a bf16 engine (storage, decoder side, conv front-end) whose encoder-layer products take e4m3fn operands
     m->fp8_enc = c.precision == CN_PRECISION_FP8;
     m->fp8_scope = c.fp8_scope ? c.fp8_scope : (CN_FP8_CONV2 | CN_FP8_LINEAR | CN_FP8_FFN);
@@ -4252,22 +4258,163 @@ int ast_prepare_buffers(cn_model* m, int max_len, int max_slots, int ctc_beam) {
     m->ast_Tp_cap = m->maxTp;
     return 0;
 }
+
+// the TransformerLM's step cache [layer][pos][slot][d] (K and V) and its logits [slot][V], on the LM handle
+int lm_prepare_buffers(cn_model* lm, int max_len, int max_slots) {
+    CN_TRY(build_workspace(lm));
+    if (lm->ast_max_len >= max_len && lm->ast_slots >= max_slots) return 0;
+    for (void* q : lm->ast_allocs) (void)hipFree(q);
+    lm->ast_allocs.clear();
+    lm->ast_ck.clear();
+    lm->ast_cv.clear();
+    const size_t d = lm->cfg.d_model, V = lm->cfg.vocab_size, es = lm->es;
+    for (size_t l = 0; l < lm->enc.size(); ++l) {
+        void *ck = nullptr, *cv = nullptr;
+        CN_TRY(ast_alloc(lm, &ck, (size_t)max_len * max_slots * d * es));
+        CN_TRY(ast_alloc(lm, &cv, (size_t)max_len * max_slots * d * es));
+        lm->ast_ck.push_back(ck);
+        lm->ast_cv.push_back(cv);
+    }
+    CN_TRY(ast_alloc(lm, (void**)&lm->ast_logits, (size_t)max_slots * V * 4));
+    lm->ast_max_len = max_len;
+    lm->ast_slots = max_slots;
+    return 0;
+}
+
+int lm_check_step(const cn_model* lm, int max_len, int max_slots, const char* who) {
+    if (!lm || lm->cfg.ast != 2 || !lm->finalized || !lm->tgt_lut) {
+        cn_set_error(std::string(who) + ": the LM must be a finalized TransformerLM handle (cfg.ast = 2)");
+        return -1;
+    }
+    if ((size_t)max_slots > (size_t)lm->maxB * (lm->maxTp + 1) || max_len > lm->pe_rows) {
+        cn_set_error(std::string(who) + ": the LM handle's workspace (max_batch x max_frames) or position table is too small for "
+                     "the beam's slots / max_len");
+        return -1;
+    }
+    return 0;
+}
+
+// TransformerLM (src/models/lm.py:52-56) on the newest position of n hypotheses -> logits [n][V] fp32 in lm->ast_logits.  The
+// reference runs lm_model(ys, tgt_mask) on the whole prefix under the decoder's mask (ys != padding_idx) & subsequent_mask
+// (transformer.py:186-191); here the keys / values of earlier positions come from the LM's own cache through the SAME ancestor
+// and key-mask tables as the decoder's.  Per layer (pre-norm encoder layer): LN, fused QKV, cached self-attention (appends this
+// position), out-proj + residual, FFN sublayer; then encoder.norm and out_generator.proj.
+int lm_step_run(cn_model* lm, int n, int pos, const int32_t* tok_dev, const int32_t* anc_dev, const uint8_t* keyok_dev,
+                int table_stride, hipStream_t s) {
+    const cn_config& c = lm->cfg;
+    const int d = c.d_model, V = c.vocab_size, H = c.n_head;
+    const float scale = 1.0f / sqrtf((float)(d / H));
+    float* x = lm->x;
+    CN_TRY(launch_ast_embed(tok_dev, lm->tgt_lut, lm->pe + (size_t)pos * d, x, n, d, sqrtf((float)d), s));
+    // bf16 / d_model 256 (lm_small): the decode step's d_ff split of the fused FFN kernel, as in ast_step_run
+    static const bool no_split = cn_exp_env("CASSNAT_AST_NO_FFN_SPLIT") != nullptr;
+    const int dff = c.d_encff;
+    const int ffn_slices = (lm->enc.empty() || !lm->enc[0].w1p || no_split) ? 1 : (dff % (128 * 8) == 0 ? 8 : (dff % (128 * 4) == 0 ? 4 : 1));
+    const size_t hbuf_bytes = (size_t)lm->maxB * (lm->maxTp + 1) * std::max(1, c.esa_group) *
+                              (size_t)std::max(std::max(c.d_encff, c.d_decff), c.d_ff) * lm->es;
+    const bool split_now = ffn_slices > 1 && n <= 2048 && (size_t)ffn_slices * n * d * 4 <= hbuf_bytes;
+    bool have_ln = false;
+    for (size_t l = 0; l < lm->enc.size(); ++l) {
+        const Layer& L = lm->enc[l];
+        if (!have_ln) CN_TRY(run_ln(lm, L.n[0], x, lm->xn, n, s));
+        have_ln = false;
+        CN_TRY(run_linear(lm, "lm_qkv_proj", L.qkv, lm->xn, d, lm->qkv, 3 * d, 0, n, 0, nullptr, 0, s));
+        GatherAttnArgs a;
+        a.append_pos = pos;
+        a.q = lm->qkv;
+        a.ldq = 3 * d;
+        a.k = lm->ast_ck[l];
+        a.v = lm->ast_cv[l];
+        a.o = lm->ctx;
+        a.ldo = d;
+        a.n = n;
+        a.H = H;
+        a.nkeys = pos + 1;
+        a.slots = lm->ast_slots;
+        a.d = d;
+        a.table_stride = table_stride;
+        a.anc = anc_dev;
+        a.keyok = keyok_dev;
+        a.scale = scale;
+        {
+            ProfScope ps(lm, "lm_cache_attention", 4.0 * n * H * (pos + 1) * 64, 2.0 * n * (pos + 1) * d * lm->es, s);
+            CN_TRY(launch_ast_gather_attn(lm->prec, 0, a, s));
+        }
+        CN_TRY(run_linear(lm, "lm_out_proj_resid", L.self_o, lm->ctx, d, x, d, 1, n, CN_EPI_RESID, x, d, s));
+        if (split_now) {
+            const bool last = l + 1 == lm->enc.size();
+            const Norm& nx = last ? lm->enc_norm : lm->enc[l + 1].n[0];
+            ProfScope ps(lm, "lm_ffn_split", 4.0 * n * (double)L.w1.N * d, 2.0 * L.w1.N * d * 2 + (double)n * d * (8 + 4 * ffn_slices), s);
+            FfnFusedArgs f;
+            f.x = x;
+            f.ln_a = L.n[1].a;
+            f.ln_b = L.n[1].b;
+            f.w1p = L.w1p;
+            f.b1 = L.w1.b;
+            f.w2p = L.w2p;
+            f.b2 = L.w2.b;
+            f.M = n;
+            f.d = d;
+            f.dff = L.w1.N;
+            f.nslice = ffn_slices;
+            f.partial = reinterpret_cast<float*>(lm->hbuf);
+            f.act = FF_ACT_RELU;
+            CN_TRY(launch_ffn_fused(f, s));
+            CN_TRY(launch_ffn_reduce(x, f.partial, ffn_slices, L.w2.b, nx.a, nx.b, last ? lm->enc_h : lm->xn, n, 1e-6f, s));
+            have_ln = true;
+        } else {
+            CN_TRY(run_ffn(lm, L, L.n[1], x, n, nullptr, nullptr, s));
+        }
+    }
+    if (!have_ln) CN_TRY(run_ln(lm, lm->enc_norm, x, lm->enc_h, n, s));
+    return run_linear(lm, "lm_generator_proj", lm->att_gen, lm->enc_h, d, lm->ast_logits, V, 1, n, 0, nullptr, 0, s);
+}
 }  // namespace
+
+// src/tasks/art_task.py:67-90 + transformer.py:186-209: the LM whose step ast_step fuses when lm_weight > 0 (NULL detaches).
+extern "C" int cn_ast_attach_lm(cn_model* m, cn_model* lm) {
+    if (!m || m->cfg.ast != 1) {
+        cn_set_error("cn_ast_attach_lm: the first handle must be an autoregressive model (cfg.ast = 1)");
+        return -1;
+    }
+    if (!lm) {
+        m->ast_lm = nullptr;
+        return 0;
+    }
+    if (lm->lib_tag != m->lib_tag) {
+        cn_set_error("cn_ast_attach_lm: the two handles come from different libraries");
+        return -1;
+    }
+    if (lm->cfg.ast != 2 || !lm->finalized) {
+        cn_set_error("cn_ast_attach_lm: the LM handle must be a finalized TransformerLM (cfg.ast = 2)");
+        return -1;
+    }
+    if (lm->cfg.vocab_size != m->cfg.vocab_size || lm->cfg.device != m->cfg.device) {
+        cn_set_error("cn_ast_attach_lm: the LM must have the decoder's vocabulary and device");
+        return -1;
+    }
+    m->ast_lm = lm;
+    return 0;
+}
 
 extern "C" int cn_ast_begin(cn_model* m, const float* feats_dev, int32_t B, int32_t T, int32_t F, const cn_decode_opts* opts,
                             int32_t want_ctc, int32_t max_len, int32_t max_slots, int32_t ctc_beam, void* stream) {
     CN_TRY(check_call(m, B, T, F));
-    if (!m->cfg.ast || !m->tgt_lut) {
+    if (m->cfg.ast != 1 || !m->tgt_lut) {
         cn_set_error("cn_ast_begin: the model was not created with cfg.ast = 1");
         return -1;
     }
-    if (max_len < 2 || max_slots < 1 || (size_t)max_slots > (size_t)m->maxB * (m->maxTp + 1) || ctc_beam < 0 || ctc_beam > 16) {
+    if (max_len < 2 || max_slots < 1 || (size_t)max_slots > (size_t)m->maxB * (m->maxTp + 1) || ctc_beam < 0 || ctc_beam > 32) {
         cn_set_error("cn_ast_begin: bad max_len / max_slots / ctc_beam");
         return -1;
     }
     hipStream_t s = (hipStream_t)stream;
     CN_HIP_CHECK(hipSetDevice(m->cfg.device));
     CN_TRY(ast_prepare_buffers(m, max_len, max_slots, ctc_beam));
+    if (m->ast_lm) {  // the attached LM's step cache, sized like the decoder's
+        CN_TRY(lm_check_step(m->ast_lm, max_len, max_slots, "cn_ast_begin"));
+        CN_TRY(lm_prepare_buffers(m->ast_lm, max_len, max_slots));
+    }
     m->ast_blank = opts->padding_idx;
     CN_TRY(stage_encode(m, feats_dev, B, T, F, opts, s));
     const int d = m->cfg.d_model, Mmem = B * m->Tp, V = m->cfg.vocab_size;
@@ -4287,7 +4434,7 @@ namespace {
 // dense_bw > 0: the rows are the dense slots b * dense_bw + j of the device beam (utt[row] = row / dense_bw)
 int ast_step_run(cn_model* m, int n, int pos, const int32_t* tok_dev, const int32_t* utt_dev, const int32_t* anc_dev,
                  const uint8_t* keyok_dev, int table_stride, float temperature, int K, int32_t* topk_idx_dev,
-                 float* topk_val_dev, int dense_bw, hipStream_t s) {
+                 float* topk_val_dev, int dense_bw, hipStream_t s, float lm_weight = 0.f, float* lm_val_dev = nullptr) {
     const cn_config& c = m->cfg;
     const int d = c.d_model, V = c.vocab_size, H = c.n_head;
     const float scale = 1.0f / sqrtf((float)(d / H));
@@ -4407,6 +4554,16 @@ int ast_step_run(cn_model* m, int n, int pos, const int32_t* tok_dev, const int3
     }
     if (!have_ln) CN_TRY(run_ln(m, m->dec_norm, x, m->dec_h, n, s));
     CN_TRY(run_linear(m, "generator_proj", m->att_gen, m->dec_h, d, m->ast_logits, V, 1, n, 0, nullptr, 0, s));
+    if (lm_weight > 0.f) {  // shallow fusion (transformer.py:186-209): the LM step on the same rows, tables and position
+        cn_model* lm = m->ast_lm;
+        CN_TRY(lm_step_run(lm, n, pos, tok_dev, anc_dev, keyok_dev, table_stride, s));
+        ProfScope ps(m, "lm_fusion", 0, 2.0 * n * V * 4, s);
+        if (!lm_val_dev)  // no CTC: top-K of att + lm_weight * lm over the vocabulary
+            return launch_logsoftmax_fuse_topk(m->ast_logits, lm->ast_logits, n, V, V, temperature, lm_weight, K, topk_idx_dev,
+                                               topk_val_dev, s);
+        CN_TRY(launch_logsoftmax_topk(m->ast_logits, n, V, V, temperature, K, topk_idx_dev, topk_val_dev, s));
+        return launch_logsoftmax_gather(lm->ast_logits, n, V, V, topk_idx_dev, K, lm_val_dev, s);
+    }
     CN_TRY(launch_logsoftmax_topk(m->ast_logits, n, V, V, temperature, K, topk_idx_dev, topk_val_dev, s));
     return 0;
 }
@@ -4419,7 +4576,7 @@ extern "C" int cn_ast_step(cn_model* m, int32_t n, int32_t pos, const int32_t* t
         cn_set_error("cn_ast_step: call cn_ast_begin first");
         return -1;
     }
-    if (n < 1 || n > m->ast_slots || pos < 0 || pos >= m->ast_max_len || pos >= m->pe_rows || K < 1 || K > 16 ||
+    if (n < 1 || n > m->ast_slots || pos < 0 || pos >= m->ast_max_len || pos >= m->pe_rows || K < 1 || K > 32 ||
         table_stride <= pos) {
         cn_set_error("cn_ast_step: live rows / position / K outside the configured cache");
         return -1;
@@ -4427,6 +4584,58 @@ extern "C" int cn_ast_step(cn_model* m, int32_t n, int32_t pos, const int32_t* t
     CN_HIP_CHECK(hipSetDevice(m->cfg.device));
     return ast_step_run(m, n, pos, tok_dev, utt_dev, anc_dev, keyok_dev, table_stride, temperature, K, topk_idx_dev, topk_val_dev, 0,
                         (hipStream_t)stream);
+}
+
+extern "C" int cn_ast_step_lm(cn_model* m, int32_t n, int32_t pos, const int32_t* tok_dev, const int32_t* utt_dev,
+                              const int32_t* anc_dev, const uint8_t* keyok_dev, int32_t table_stride, float temperature, int32_t K,
+                              float lm_weight, int32_t use_ctc, int32_t* topk_idx_dev, float* topk_val_dev, float* lm_val_dev,
+                              void* stream) {
+    if (!m || m->cfg.ast != 1 || m->ast_slots == 0) {
+        cn_set_error("cn_ast_step_lm: call cn_ast_begin first");
+        return -1;
+    }
+    if (!(lm_weight > 0.f) || !m->ast_lm || m->ast_lm->ast_slots < m->ast_slots || m->ast_lm->ast_max_len < m->ast_max_len) {
+        cn_set_error("cn_ast_step_lm: needs lm_weight > 0 and an LM attached (cn_ast_attach_lm) before cn_ast_begin");
+        return -1;
+    }
+    if (n < 1 || n > m->ast_slots || pos < 0 || pos >= m->ast_max_len || pos >= m->pe_rows || K < 1 || K > 32 ||
+        table_stride <= pos || (use_ctc && !lm_val_dev)) {
+        cn_set_error("cn_ast_step_lm: live rows / position / K outside the configured cache (or use_ctc without lm_val_dev)");
+        return -1;
+    }
+    CN_HIP_CHECK(hipSetDevice(m->cfg.device));
+    return ast_step_run(m, n, pos, tok_dev, utt_dev, anc_dev, keyok_dev, table_stride, temperature, K, topk_idx_dev, topk_val_dev, 0,
+                        (hipStream_t)stream, lm_weight, use_ctc ? lm_val_dev : nullptr);
+}
+
+// kernel-test entry of the LM step: log_softmax of the LM's logits at position pos of n rows -> logp_dev [n][V]
+extern "C" int cn_lm_step_begin(cn_model* lm, int32_t max_len, int32_t max_slots) {
+    CN_TRY(lm_check_step(lm, max_len, max_slots, "cn_lm_step_begin"));
+    if (max_len < 1 || max_slots < 1) {
+        cn_set_error("cn_lm_step_begin: bad max_len / max_slots");
+        return -1;
+    }
+    CN_HIP_CHECK(hipSetDevice(lm->cfg.device));
+    return lm_prepare_buffers(lm, max_len, max_slots);
+}
+
+extern "C" int cn_lm_step(cn_model* lm, int32_t n, int32_t pos, const int32_t* tok_dev, const int32_t* anc_dev,
+                          const uint8_t* keyok_dev, int32_t table_stride, float* logp_dev, void* stream) {
+    if (!lm || lm->cfg.ast != 2 || lm->ast_slots == 0) {
+        cn_set_error("cn_lm_step: call cn_lm_step_begin first");
+        return -1;
+    }
+    if (n < 1 || n > lm->ast_slots || pos < 0 || pos >= lm->ast_max_len || pos >= lm->pe_rows || table_stride <= pos) {
+        cn_set_error("cn_lm_step: rows / position outside the configured cache");
+        return -1;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    CN_HIP_CHECK(hipSetDevice(lm->cfg.device));
+    const int V = lm->cfg.vocab_size;
+    CN_TRY(lm_step_run(lm, n, pos, tok_dev, anc_dev, keyok_dev, table_stride, s));
+    CN_TRY(launch_logsoftmax_argmax(lm->ast_logits, n, V, V, lm->best, lm->ctc_maxlp, 1, s));
+    CN_HIP_CHECK(hipMemcpyAsync(logp_dev, lm->ast_logits, (size_t)n * V * 4, hipMemcpyDeviceToDevice, s));
+    return 0;
 }
 
 extern "C" int cn_ast_ctc_score(cn_model* m, int32_t n, int32_t out_len, const int32_t* utt_dev, const int32_t* last_tok_dev,
@@ -4470,8 +4679,13 @@ extern "C" int cn_decode_ast(cn_model* m, const float* feats_dev, int32_t B, int
     }
     const int bw = ao->beam_width, want_ctc = ao->ctc_weight > 0.f ? 1 : 0;
     const int K = want_ctc ? ao->ctc_beam : bw;
-    if (bw < 1 || bw > 16 || K < bw || K > 16 || ao->max_step < 1 || max_len < ao->max_step + 1) {
-        cn_set_error("cn_decode_ast: need 1 <= beam_width <= ctc_beam <= 16 and max_len > max_step");
+    if (bw < 1 || bw > 32 || K < bw || K > 32 || ao->max_step < 1 || max_len < ao->max_step + 1) {
+        cn_set_error("cn_decode_ast: need 1 <= beam_width <= ctc_beam <= 32 and max_len > max_step");
+        return -1;
+    }
+    const bool use_lm = ao->lm_weight > 0.f;
+    if (use_lm && !m->ast_lm) {
+        cn_set_error("cn_decode_ast: lm_weight > 0 needs an LM attached with cn_ast_attach_lm");
         return -1;
     }
     const int S = B * bw, L = max_len;
@@ -4495,6 +4709,7 @@ extern "C" int cn_decode_ast(cn_model* m, const float* feats_dev, int32_t B, int
         CN_TRY(ast_alloc(m, (void**)&m->beam_idx, (size_t)S * K * 4));
         CN_TRY(ast_alloc(m, (void**)&m->beam_val, (size_t)S * K * 4));
         CN_TRY(ast_alloc(m, (void**)&m->beam_ctc, (size_t)S * K * 4));
+        CN_TRY(ast_alloc(m, (void**)&m->beam_lm, (size_t)S * K * 4));
         m->beam_S = S;
         m->beam_L = L;
         m->beam_K = K;
@@ -4504,7 +4719,7 @@ extern "C" int cn_decode_ast(cn_model* m, const float* feats_dev, int32_t B, int
     CN_TRY(launch_ast_beam_init(st, cur, B, bw, L, opts->sos, opts->padding_idx, s));
     for (int pos = 0; pos < ao->max_step; ++pos) {
         CN_TRY(ast_step_run(m, S, pos, st.cur_tok, st.utt, st.anc[cur], st.keyok[cur], L, ao->temperature, K, m->beam_idx,
-                            m->beam_val, bw, s));
+                            m->beam_val, bw, s, use_lm ? ao->lm_weight : 0.f, use_lm && want_ctc ? m->beam_lm : nullptr));
         if (want_ctc)
             CN_TRY(cn_ast_ctc_score(m, S, pos, st.utt, st.cur_tok, m->beam_idx, K, st.ctc_ref[cur], pos & 1, ao->eos, m->beam_ctc,
                                     stream));
@@ -4522,6 +4737,9 @@ extern "C" int cn_decode_ast(cn_model* m, const float* feats_dev, int32_t B, int
         q.pad = opts->padding_idx;
         q.use_ctc = want_ctc;
         q.use_lp = ao->use_length_penalty;
+        q.use_lm = use_lm;
+        q.lm = m->beam_lm;
+        q.lw = ao->lm_weight;
         q.w = ao->ctc_weight;
         q.u = ao->one_minus_ctc_weight;
         q.lp = ao->length_penalty;

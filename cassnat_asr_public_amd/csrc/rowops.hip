@@ -285,8 +285,15 @@ int launch_topk(const float* logp, int M, int V, int ldl, int k, int* idx, float
 // row maximum, the sum of expf(x - max) in the same partition and order, (x - max) - lse per entry (in LDS) - without
 // writing the (M, V) log-probabilities back and with the k selection rounds working on cached per-thread maxima (only the
 // thread that owned the previous winner rescans its V / 256 entries).
+//
+// FUSE (LM shallow fusion without CTC, src/models/transformer.py:190-192, 214): a second row `lm` of LM logits (temperature 1)
+// is staged beside it; its own maximum and log-sum-exp (same partition and order), then every entry becomes
+// att_logp + fl(w * lm_logp) in float32 with one rounding per operation (torch's `att_prob + lm_weight * lm_prob`), and the k
+// rounds select on that sum - the candidate set is the fused one, not the attention top-k.
+template <bool FUSE>
 __global__ __launch_bounds__(256) void logsoftmax_topk_kernel(const float* __restrict__ logits, int V, int ldl, float temperature,
-                                                              int k, int* __restrict__ idx, float* __restrict__ val) {
+                                                              int k, int* __restrict__ idx, float* __restrict__ val,
+                                                              const float* __restrict__ lm, float w) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float* row = reinterpret_cast<float*>(smem);
     __shared__ float s_val[4], s_sum[4];
@@ -349,7 +356,32 @@ __global__ __launch_bounds__(256) void logsoftmax_topk_kernel(const float* __res
     const float lse = logf((s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]));
     // the selection ranks the LOG-PROBABILITIES, as the two-kernel form and the reference do: two logits one ulp apart can
     // round to the same log-probability, and the tie then goes to the lower index
-    for (int i = tid; i < V; i += 256) row[i] = (row[i] - rmax) - lse;
+    if constexpr (FUSE) {
+        float* lrow = row + V;
+        const float* pl = lm + (long long)blockIdx.x * ldl;
+        float lbest = -INFINITY;
+        for (int i = tid; i < V; i += 256) {
+            const float v = pl[i];
+            lrow[i] = v;
+            lbest = fmaxf(lbest, v);
+        }
+        lbest = wave_max(lbest);
+        __syncthreads();  // s_sum of the attention row has been read by every thread
+        if (lane == 0) s_val[wave] = lbest;
+        __syncthreads();
+        const float lmax = fmaxf(fmaxf(s_val[0], s_val[1]), fmaxf(s_val[2], s_val[3]));
+        float lsum = 0.f;
+        for (int i = tid; i < V; i += 256) lsum += expf(lrow[i] - lmax);
+        lsum = wave_sum(lsum);
+        if (lane == 0) s_sum[wave] = lsum;
+        __syncthreads();
+        const float llse = logf((s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]));
+        __syncthreads();  // s_val is rewritten by the selection rounds
+        for (int i = tid; i < V; i += 256)
+            row[i] = __fadd_rn(__fsub_rn(__fsub_rn(row[i], rmax), lse), __fmul_rn(w, __fsub_rn(__fsub_rn(lrow[i], lmax), llse)));
+    } else {
+        for (int i = tid; i < V; i += 256) row[i] = (row[i] - rmax) - lse;
+    }
     local_best(mybest, myidx);
     for (int r = 0; r < k; ++r) {
         best = mybest;
@@ -368,13 +400,69 @@ __global__ __launch_bounds__(256) void logsoftmax_topk_kernel(const float* __res
 
 int launch_logsoftmax_topk(const float* logits, int M, int V, int ldl, float temperature, int k, int* idx, float* val,
                            hipStream_t s) {
-    if (k < 1 || k > 16 || V > 16384) {
-        cn_set_error("logsoftmax_topk: need 1 <= k <= 16 and V <= 16384");
+    if (k < 1 || k > 32 || V > 16384) {
+        cn_set_error("logsoftmax_topk: need 1 <= k <= 32 and V <= 16384");
         return -1;
     }
     if (M <= 0) return 0;
-    hipLaunchKernelGGL(logsoftmax_topk_kernel, dim3(M), dim3(256), (size_t)V * sizeof(float), s, logits, V, ldl, temperature, k, idx,
-                       val);
+    hipLaunchKernelGGL(logsoftmax_topk_kernel<false>, dim3(M), dim3(256), (size_t)V * sizeof(float), s, logits, V, ldl, temperature, k,
+                       idx, val, nullptr, 0.f);
+    CN_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int launch_logsoftmax_fuse_topk(const float* att, const float* lm, int M, int V, int ldl, float temperature, float w, int k,
+                                int* idx, float* val, hipStream_t s) {
+    if (k < 1 || k > 32 || V > 8192) {
+        cn_set_error("logsoftmax_fuse_topk: need 1 <= k <= 32 and V <= 8192");
+        return -1;
+    }
+    if (M <= 0) return 0;
+    hipLaunchKernelGGL(logsoftmax_topk_kernel<true>, dim3(M), dim3(256), (size_t)2 * V * sizeof(float), s, att, V, ldl, temperature, k,
+                       idx, val, lm, w);
+    CN_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// LM shallow fusion with CTC (src/models/transformer.py:208-209, lm_prob.gather(1, indices)): per row the log-sum-exp of the LM
+// logits (temperature 1; same partition and order as logsoftmax_topk_kernel), then out[r][c] = (x[cand[r][c]] - max) - lse for
+// the k attention candidates.  One workgroup per row; the row is read once, into LDS.
+__global__ __launch_bounds__(256) void logsoftmax_gather_kernel(const float* __restrict__ logits, int V, int ldl,
+                                                                const int* __restrict__ cand, int k, float* __restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    float* row = reinterpret_cast<float*>(smem);
+    __shared__ float s_val[4], s_sum[4];
+    const float* p = logits + (long long)blockIdx.x * ldl;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    float best = -INFINITY;
+    for (int i = tid; i < V; i += 256) {
+        const float v = p[i];
+        row[i] = v;
+        best = fmaxf(best, v);
+    }
+    best = wave_max(best);
+    if (lane == 0) s_val[wave] = best;
+    __syncthreads();
+    const float rmax = fmaxf(fmaxf(s_val[0], s_val[1]), fmaxf(s_val[2], s_val[3]));
+    float sum = 0.f;
+    for (int i = tid; i < V; i += 256) sum += expf(row[i] - rmax);
+    sum = wave_sum(sum);
+    if (lane == 0) s_sum[wave] = sum;
+    __syncthreads();
+    const float lse = logf((s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]));
+    if (tid < k) {
+        const int c = cand[(long long)blockIdx.x * k + tid];
+        out[(long long)blockIdx.x * k + tid] = (c >= 0 && c < V) ? (row[c] - rmax) - lse : -INFINITY;
+    }
+}
+
+int launch_logsoftmax_gather(const float* logits, int M, int V, int ldl, const int* cand, int k, float* out, hipStream_t s) {
+    if (k < 1 || k > 256 || V > 16384) {
+        cn_set_error("logsoftmax_gather: need 1 <= k <= 256 and V <= 16384");
+        return -1;
+    }
+    if (M <= 0) return 0;
+    hipLaunchKernelGGL(logsoftmax_gather_kernel, dim3(M), dim3(256), (size_t)V * sizeof(float), s, logits, V, ldl, cand, k, out);
     CN_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -59,7 +59,7 @@ class CnDecodeOpts(C.Structure):
 class CnAstOpts(C.Structure):
     _fields_ = [("ctc_weight", C.c_float), ("temperature", C.c_float), ("ctc_beam", C.c_int32), ("beam_width", C.c_int32),
                 ("max_step", C.c_int32), ("eos", C.c_int32), ("use_length_penalty", C.c_int32), ("one_minus_ctc_weight", C.c_float),
-                ("length_penalty", C.c_double), ("reserved", C.c_int32 * 4)]
+                ("length_penalty", C.c_double), ("lm_weight", C.c_float), ("reserved", C.c_int32 * 3)]
 
 
 class CnFbankOpts(C.Structure):
@@ -169,6 +169,11 @@ def lib(flavour=None):
                                C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
     L.cn_ast_step.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                               C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.cn_ast_attach_lm.argtypes = [C.c_void_p, C.c_void_p]
+    L.cn_ast_step_lm.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                 C.c_float, C.c_int32, C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.cn_lm_step_begin.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
+    L.cn_lm_step.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     L.cn_fbank_default_opts.argtypes = [C.POINTER(CnFbankOpts)]
     L.cn_fbank_default_opts.restype = None
     L.cn_fbank_num_frames.argtypes = [C.POINTER(CnFbankOpts), C.c_int32]
@@ -396,6 +401,26 @@ class Engine:
     def ast_step(self, pos, tok, utt, anc, keyok, temperature, K, topk_idx, topk_val):
         self._chk(self.L.cn_ast_step(self.handle, tok.shape[0], pos, _ptr(tok), _ptr(utt), _ptr(anc), _ptr(keyok), anc.shape[1],
                                  float(temperature), K, _ptr(topk_idx), _ptr(topk_val), current_stream()), "cn_ast_step")
+
+    def ast_attach_lm(self, lm):
+        """LM shallow fusion: ``lm`` (an Engine of a TransformerLM, same library) runs beside this engine's decoder steps; None
+        detaches.  The caller keeps ``lm`` open while attached."""
+        if lm is not None and lm.L is not self.L:
+            raise HipError("cn_ast_attach_lm: the LM engine comes from the other library")
+        self._chk(self.L.cn_ast_attach_lm(self.handle, lm.handle if lm is not None else None), "cn_ast_attach_lm")
+        self._lm = lm
+
+    def ast_step_lm(self, pos, tok, utt, anc, keyok, temperature, K, lm_weight, use_ctc, topk_idx, topk_val, lm_val=None):
+        self._chk(self.L.cn_ast_step_lm(self.handle, tok.shape[0], pos, _ptr(tok), _ptr(utt), _ptr(anc), _ptr(keyok), anc.shape[1],
+                                    float(temperature), K, float(lm_weight), int(use_ctc), _ptr(topk_idx), _ptr(topk_val),
+                                    _ptr(lm_val) if lm_val is not None else None, current_stream()), "cn_ast_step_lm")
+
+    def lm_step_begin(self, max_len, max_slots):
+        self._chk(self.L.cn_lm_step_begin(self.handle, int(max_len), int(max_slots)), "cn_lm_step_begin")
+
+    def lm_step(self, pos, tok, anc, keyok, logp):
+        self._chk(self.L.cn_lm_step(self.handle, tok.shape[0], pos, _ptr(tok), _ptr(anc), _ptr(keyok), anc.shape[1], _ptr(logp),
+                                current_stream()), "cn_lm_step")
 
     def ast_ctc_score(self, out_len, utt, last_tok, cand, prev_ref, parity, eos, score):
         self._chk(self.L.cn_ast_ctc_score(self.handle, cand.shape[0], out_len, _ptr(utt), _ptr(last_tok), _ptr(cand), cand.shape[1],

@@ -1,10 +1,12 @@
 """Drop-in for the inference use of the reference's ``models.lm`` (src/models/lm.py): the TransformerLM that ranks the ESA
-samples of CASS-NAT decoding (src/models/cassnat.py:499-523, ``rank_model == 'lm'``).
+samples of CASS-NAT decoding (src/models/cassnat.py:499-523, ``rank_model == 'lm'``), and the LM that the AST beam search
+fuses (src/models/transformer.py:186-209, ``lm_weight > 0``).
 
 ``make_model(args) -> TransformerLM`` holds the reference's parameter names (``text_embed.0.lut.weight``, ``encoder.*``,
 ``out_generator.proj.*``; checkpoint keys of src/tasks/cassnat_task.py:85-125).  No arithmetic lives here:
 ``score_tokens`` hands the tokens to libcassnat_hip.so (``cn_lm_score``: embedding, encoder stack under the causal + length
-mask, generator, log-softmax, gather of the target's log-probability)."""
+mask, generator, log-softmax, gather of the target's log-probability).  For shallow fusion ``step_engine`` / ``new_engine`` give
+handles whose incremental step (``cn_ast_attach_lm``) runs beside an AST engine's decoder step."""
 from types import SimpleNamespace
 
 import torch
@@ -54,6 +56,19 @@ class TransformerLM(nn.Module):
             eng.load_state({k: v.detach() for k, v in self.named_parameters()}, self.pe)
             self._engine, self._engine_key = eng, key
         return self._engine
+
+    def step_engine(self, slots):
+        """The model's own engine, sized for an LM step over ``slots`` beam slots (max_batch * (max_frames / 4 + 1) rows)."""
+        if self._engine is not None and self._engine.cfg.max_batch * ((self._engine.cfg.max_frames - 1) // 4 + 2) >= slots:
+            key = (tuple(p._version for p in self.parameters()), self.hip_precision)
+            if self._engine_key == key:
+                return self._engine
+        return self.engine(max(1, slots), 4)
+
+    def new_engine(self, slots, share):
+        """A further handle (own workspace and step cache) on the device weights of ``share``: what a decode pipeline owns."""
+        return hip.Engine(SimpleNamespace(**self._hyper), precision=self.hip_precision, max_batch=max(1, slots), max_frames=4,
+                          device=getattr(self, "_device", torch.cuda.current_device()), share_with=share)
 
     def score_tokens(self, lm_input, target, length, U, max_frames=2048):
         """lm_input / target int32 cuda (N, ld), length int32 cuda (N,) -> float32 cuda (N, ld): log p(target[n][u] | lm_input[n][..u])

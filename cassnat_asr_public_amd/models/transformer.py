@@ -8,6 +8,8 @@ the prefix come from a KV cache addressed through per-hypothesis ancestor tables
 on the whole prefix), generator + log-softmax + top-k, the CTC prefix scorer and the beam bookkeeping
 (transformer.py:157-240) - no host round trip per step.  ``args.hip_host_beam = True`` keeps the bookkeeping in
 Python over ``cn_ast_begin / cn_ast_step / cn_ast_ctc_score`` (same results; used to cross-check the device beam).
+With ``args.lm_weight > 0`` the TransformerLM ``lm_model`` (models.lm) is fused (transformer.py:186-209): its incremental
+step runs beside the decoder's on the same ancestor / key-mask tables (``cn_ast_attach_lm``, ``cn_ast_step_lm``).
 """
 from types import SimpleNamespace
 
@@ -117,11 +119,22 @@ class Transformer(nn.Module):
             self.build_engine(batch, frames)
         return self._engine
 
-    def beam_decode(self, src, src_mask, vocab, args, lm_model=None, engine=None):
-        """Same contract as the reference's Transformer.beam_decode (src/models/transformer.py:122-241), lm_weight == 0.
-        ``engine``: run on this handle (a decode pipeline's, see ``new_engine``) instead of the model's own."""
-        if getattr(args, "lm_weight", 0) > 0:
-            raise NotImplementedError("LM fusion is outside the accelerated path")
+    def beam_decode(self, src, src_mask, vocab, args, lm_model=None, engine=None, lm_engine=None):
+        """Same contract as the reference's Transformer.beam_decode (src/models/transformer.py:122-241), LM shallow fusion
+        included (``args.lm_weight > 0`` with ``lm_model`` a models.lm.TransformerLM).  ``engine``: run on this handle (a decode
+        pipeline's, see ``new_engine``) instead of the model's own; ``lm_engine``: the pipeline's LM handle
+        (TransformerLM.new_engine) instead of the LM's own."""
+        lm_weight = float(getattr(args, "lm_weight", 0) or 0)
+        if lm_weight <= 0:
+            return self._beam_decode(src, args, vocab, engine, None, 0.0)
+        if lm_model is None:
+            raise ValueError("beam_decode: lm_weight > 0 needs lm_model")
+        bw = int(args.beam_width)
+        B = src.shape[0]
+        lm_eng = lm_engine if lm_engine is not None else lm_model.step_engine(B * bw)
+        return self._beam_decode(src, args, vocab, engine, lm_eng, lm_weight)
+
+    def _beam_decode(self, src, args, vocab, engine, lm_eng, lm_weight):
         sos, eos = vocab.word2index["sos"], vocab.word2index["eos"]
         assert vocab.word2index["blank"] == args.padding_idx
         dev = torch.device("cuda", getattr(self, "_device", torch.cuda.current_device()))
@@ -135,12 +148,23 @@ class Transformer(nn.Module):
         max_step = int(args.max_decode_ratio * Tp) if args.max_decode_ratio > 0 else Tp
         max_len = max_step + 1
         opts = hip.CnDecodeOpts(padding_idx=int(args.padding_idx), sos=sos, beam_width=1)
+        eng.ast_attach_lm(lm_eng)  # (None detaches: a handle never keeps an LM from an earlier call)
+        try:
+            return self._beam_search(eng, feats, opts, args, sos, eos, bw, K, use_ctc, max_step, lm_weight, dev)
+        finally:
+            if lm_eng is not None:
+                eng.ast_attach_lm(None)
+
+    def _beam_search(self, eng, feats, opts, args, sos, eos, bw, K, use_ctc, max_step, lm_weight, dev):
+        B = feats.shape[0]
+        max_len = max_step + 1
+        use_lm = lm_weight > 0
         lp = args.length_penalty
         if not getattr(args, "hip_host_beam", False):
             ao = hip.CnAstOpts(ctc_weight=float(args.ctc_weight) if use_ctc else 0.0, temperature=float(args.T), ctc_beam=K,
                                beam_width=bw, max_step=max_step, eos=eos, use_length_penalty=int(lp is not None),
                                one_minus_ctc_weight=float(1 - args.ctc_weight),
-                               length_penalty=float(lp) if lp is not None else 0.0)
+                               length_penalty=float(lp) if lp is not None else 0.0, lm_weight=lm_weight)
             hyp = torch.empty(B, bw, max_len, dtype=torch.int32, device=dev)
             hlen = torch.empty(B, bw, dtype=torch.int32, device=dev)
             score = torch.empty(B, bw, dtype=torch.float64, device=dev)
@@ -158,11 +182,13 @@ class Transformer(nn.Module):
         eng.ast_begin(feats, opts, use_ctc, max_len, B * bw, K if use_ctc else 0)
         w32 = np.float32(args.ctc_weight)
         u32 = np.float32(1 - args.ctc_weight)
+        lw32 = np.float32(lm_weight)
 
         beams = [[{"score": 0.0, "hyp": [sos], "anc": [], "ctc_ref": -1 - b, "ctc_prev": np.float32(0.0)}] for b in range(B)]
         idx_d = torch.empty(B * bw, K, dtype=torch.int32, device=dev)
         val_d = torch.empty(B * bw, K, dtype=torch.float32, device=dev)
         ctc_d = torch.empty(B * bw, K, dtype=torch.float32, device=dev)
+        lm_d = torch.empty(B * bw, K, dtype=torch.float32, device=dev)
         for i in range(max_step):
             live = [(b, s) for b in range(B) for s in beams[b] if s["hyp"][-1] != eos]
             if not live:
@@ -178,7 +204,10 @@ class Transformer(nn.Module):
                 keyok[k, : i + 1] = [t != args.padding_idx for t in s["hyp"]]
             tok_d, utt_d = torch.from_numpy(tok).to(dev), torch.from_numpy(utt).to(dev)
             anc_d, keyok_d = torch.from_numpy(anc).to(dev), torch.from_numpy(keyok).to(dev)
-            eng.ast_step(i, tok_d, utt_d, anc_d, keyok_d, args.T, K, idx_d[:n], val_d[:n])
+            if use_lm:  # no CTC: val = top-K of att + lm_weight * lm; with CTC: attention top-K and the LM at those candidates
+                eng.ast_step_lm(i, tok_d, utt_d, anc_d, keyok_d, args.T, K, lm_weight, use_ctc, idx_d[:n], val_d[:n], lm_d[:n])
+            else:
+                eng.ast_step(i, tok_d, utt_d, anc_d, keyok_d, args.T, K, idx_d[:n], val_d[:n])
             if use_ctc:
                 ref_d = torch.from_numpy(np.array([s["ctc_ref"] for _, s in live], np.int32)).to(dev)
                 eng.ast_ctc_score(i, utt_d, tok_d, idx_d[:n], ref_d, i & 1, eos, ctc_d[:n])
@@ -187,6 +216,8 @@ class Transformer(nn.Module):
             if use_ctc:
                 prev = np.array([s["ctc_prev"] for _, s in live], np.float32)[:, None]
                 local = w32 * (ctc - prev) + u32 * att  # float32, same op order as transformer.py:205-206
+                if use_lm:
+                    local = local + lw32 * lm_d[:n].cpu().numpy()  # transformer.py:208-209
                 local_idx = np.argsort(-local, axis=1, kind="stable")[:, :bw]
                 local_scores = np.take_along_axis(local, local_idx, 1)
                 tokens = np.take_along_axis(indices, local_idx, 1)

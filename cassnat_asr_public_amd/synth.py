@@ -42,6 +42,8 @@ PRESETS.update(PRESETS_CONF)
 PRESETS_LM = {
     "tiny_lm": dict(d_model=128, n_head=2, d_ff=256, N=2, vocab_size=40, dropout=0.0),
     "lm_small": dict(d_model=256, n_head=4, d_ff=1024, N=4, vocab_size=5000, dropout=0.0),
+    # egs/librispeech/conf/lm.yaml: the LM that run_art.sh stage 3 fuses into the AST beam search (pairs with config4 / config4_conf)
+    "lm_recipe": dict(d_model=512, n_head=8, d_ff=2048, N=16, vocab_size=5000, dropout=0.0),
 }
 
 

@@ -4,7 +4,9 @@
 Same constructor / decode surface and result-file lines ("<utt> tok tok ...").  All three decode types of the reference
 (art_task.py:252-259): ``ctc_att`` (joint CTC/attention beam search, src/models/transformer.py:122-241), ``ctc_only`` (CTC prefix
 beam search on the encoder, utils.beam_decode.ctc_beam_decode) and ``ctc_correct`` (the decoder as a correction model over the CTC
-greedy hypothesis, transformer.py:243-342); LM fusion and the conformer AST raise.  A decode step keeps a handful of CUs busy, so a test set goes through
+greedy hypothesis, transformer.py:243-342).  ``ctc_att`` with ``--lm_weight > 0`` fuses the TransformerLM of ``--lm_config`` /
+``--rnnlm`` (art_task.py:67-90, transformer.py:186-209) on the device; LM fusion in ``ctc_only`` / ``ctc_correct`` raises.
+A decode step keeps a handful of CUs busy, so a test set goes through
 ``args.hip_pipelines`` (default 4) engine handles (own workspace + KV cache, ONE shared device copy of the weights) on their
 own HIP streams and host threads - batches pulled from the loader by the workers, result lines written in input order.
 With torch.distributed initialised (one process per GPU) the utterances are dealt over the ranks by length exactly as
@@ -77,9 +79,43 @@ class ArtTask(BaseTask):
             raise NotImplementedError("model_type '%s' (the accelerated AST path knows transformer, conformer)" % args.model_type)
 
     def load_lm_model(self, args):
-        if getattr(args, "lm_weight", 0) > 0:
-            raise NotImplementedError("LM shallow fusion (lm_weight > 0) is outside the accelerated path")
+        """src/tasks/art_task.py:67-90: models.lm.make_model from ``--lm_config`` with the vocabulary's size, weights from the
+        ``"state_dict"`` key of ``--rnnlm`` (names with or without the "module." prefix).  The LM runs in the AST's precision.
+        Only ``ctc_att`` fuses it (transformer.py:186-209); the CTC prefix beam search's in-loop LM (ctc_lm_weight) is not on the
+        accelerated path."""
         self.lm_model = None
+        if getattr(args, "ctc_lm_weight", 0) > 0 and getattr(args, "decode_type", "ctc_att") == "ctc_only":
+            raise NotImplementedError("CTC beam search with in-loop LM fusion (ctc_lm_weight > 0) is outside the accelerated path")
+        if not getattr(args, "lm_weight", 0) > 0:
+            return
+        if getattr(args, "decode_type", "ctc_att") != "ctc_att":
+            raise NotImplementedError("LM fusion with decode_type '%s' is outside the accelerated path (ctc_att fuses the LM)"
+                                      % args.decode_type)
+        import yaml
+        from types import SimpleNamespace
+
+        from ..models.lm import make_model as make_lm_model
+
+        with open(args.lm_config) as f:
+            lm_args = SimpleNamespace(**yaml.safe_load(f))
+        lm_args.vocab_size = self.vocab.n_words
+        lm_args.hip_precision = getattr(args, "hip_precision", "bf16")
+        lm_model = make_lm_model(lm_args)
+        print("Loading language model from {}".format(args.rnnlm))
+        state = torch.load(args.rnnlm, map_location="cpu")["state_dict"]
+        with torch.no_grad():
+            for name, param in lm_model.named_parameters():
+                param.copy_(state[name] if name in state else state["module." + name])
+        lm_model.cuda(getattr(self.model, "_device", None))
+        self.lm_model = lm_model
+
+    def _lm_engines(self, n, args):
+        """One LM handle per pipeline (own step cache), all on the LM's one device copy of the weights."""
+        if self.lm_model is None:
+            return [None] * n
+        slots = int(args.batch_size) * int(args.beam_width)
+        lm0 = self.lm_model.step_engine(slots)
+        return [lm0] + [self.lm_model.new_engine(slots, share=lm0) for _ in range(n - 1)]
 
     def _engines(self, n, args):
         """n engine handles on ONE device copy of the weights; with several ranks that copy is rank 0's, broadcast once."""
@@ -100,6 +136,7 @@ class ArtTask(BaseTask):
         progress = util.ProgressMeter(len(self.test_loader), batch_time)
         n = max(1, min(int(getattr(args, "hip_pipelines", 4)), max(1, len(self.test_loader))))
         engines = self._engines(n, args)
+        lm_engines = self._lm_engines(n, args)
         it = iter(enumerate(self.test_loader))
         lock = threading.Lock()
         done = {}
@@ -123,7 +160,8 @@ class ArtTask(BaseTask):
                         elif args.decode_type == "ctc_correct":
                             recog = self.model.fast_decode_with_ctc(feats, src_mask, self.vocab, args, self.lm_model, engine=engines[k])
                         else:
-                            recog = self.model.beam_decode(feats, src_mask, self.vocab, args, self.lm_model, engine=engines[k])
+                            recog = self.model.beam_decode(feats, src_mask, self.vocab, args, self.lm_model, engine=engines[k],
+                                                           lm_engine=lm_engines[k])
                         lines = [utt + " " + " ".join(hyp_to_words(seqs[0]["hyp"], self.vocab, args.padding_idx))
                                  for utt, seqs in zip(utt_list, recog)]
                         with cv:
@@ -155,7 +193,7 @@ class ArtTask(BaseTask):
                 progress.print(i)
         for t in threads:
             t.join()
-        for e in engines[1:]:
+        for e in engines[1:] + [e for e in lm_engines[1:] if e is not None]:
             e.close()
         if i >= 0 and self.rank == 0:
             progress.print(i)

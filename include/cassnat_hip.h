@@ -180,8 +180,31 @@ int cn_ast_ctc_score(cn_model* m, int32_t n_live, int32_t out_len, const int32_t
                      const int32_t* cand_dev, int32_t K, const int32_t* prev_ref_dev, int32_t parity, int32_t eos,
                      float* score_dev, void* stream);
 
-/* The whole joint CTC / attention beam search of Transformer.beam_decode (src/models/transformer.py:122-241, lm_weight == 0)
- * on the device: no host round trip inside the step loop (the host polls a live-hypothesis counter every 8 steps).
+/* LM shallow fusion (src/models/transformer.py:186-209; the LM of src/tasks/art_task.py:67-90): `lm` (a finalized TransformerLM
+ * handle, cfg.ast = 2, same vocabulary, device and library; its own precision) runs one incremental step beside every decoder
+ * step of `ast` (cfg.ast = 1): the newest position of every slot, keys / values of earlier positions from the LM's own cache
+ * [layer][pos][slot][d] (allocated by cn_ast_begin, sized like the decoder's; freed with the LM handle) through the decoder's
+ * ancestor and key-mask tables - the reference's lm_model(ys, tgt_mask)[:, -1] with tgt_mask = (ys != padding_idx) &
+ * subsequent_mask.  NULL detaches.  The LM handle must stay alive while attached; its workspace (max_batch x max_frames) must
+ * hold the beam's slots, its position table max_len.  One LM handle per AST handle (the cache is per handle). */
+int cn_ast_attach_lm(cn_model* ast, cn_model* lm);
+/* cn_ast_step with the attached LM fused, lm_weight > 0 (after cn_ast_begin):
+ * use_ctc == 0 (transformer.py:190-192, 214): topk_idx / topk_val = top-K over V of
+ *   log_softmax(att / T) + fl32(lm_weight * log_softmax(lm)) (float32, one rounding per operation; ties: lower index first);
+ * use_ctc != 0 (transformer.py:199-209): topk_idx / topk_val = top-K of log_softmax(att / T) as cn_ast_step, and
+ *   lm_val_dev [n_live][K] = log_softmax(lm) at those candidates (the caller adds fl32(lm_weight * lm) after the CTC terms). */
+int cn_ast_step_lm(cn_model* m, int32_t n_live, int32_t pos, const int32_t* tok_dev, const int32_t* utt_dev,
+                   const int32_t* anc_dev, const uint8_t* keyok_dev, int32_t table_stride, float temperature, int32_t K,
+                   float lm_weight, int32_t use_ctc, int32_t* topk_idx_dev, float* topk_val_dev, float* lm_val_dev, void* stream);
+/* kernel-test entry of the LM step alone: cn_lm_step_begin sizes the LM's step cache; cn_lm_step runs position pos of n rows
+ * (tables as cn_ast_step) and writes log_softmax(out_generator(h)) [n][V] fp32 to logp_dev. */
+int cn_lm_step_begin(cn_model* lm, int32_t max_len, int32_t max_slots);
+int cn_lm_step(cn_model* lm, int32_t n, int32_t pos, const int32_t* tok_dev, const int32_t* anc_dev, const uint8_t* keyok_dev,
+               int32_t table_stride, float* logp_dev, void* stream);
+
+/* The whole joint CTC / attention beam search of Transformer.beam_decode (src/models/transformer.py:122-241) on the device,
+ * with LM shallow fusion when lm_weight > 0 (an LM attached with cn_ast_attach_lm; an error without one): no host round trip
+ * inside the step loop (the host polls a live-hypothesis counter every 8 steps).  1 <= beam_width <= ctc_beam <= 32.
  * hyp_out_dev [B][beam_width][max_len] int32 (sos first, padded with padding_idx), hyp_len_dev [B][beam_width],
  * score_dev [B][beam_width] double; beams best first, same ordering rules as the reference (stable ties). */
 typedef struct cn_ast_opts {
@@ -194,7 +217,8 @@ typedef struct cn_ast_opts {
     int32_t use_length_penalty;  /* 0: args.length_penalty is None */
     float one_minus_ctc_weight;  /* float32(1 - ctc_weight) as the reference computes it (in double, then cast) */
     double length_penalty;
-    int32_t reserved[4];
+    float lm_weight;             /* > 0: LM shallow fusion (args.lm_weight); 0 = no LM.  Takes the place of reserved[0] */
+    int32_t reserved[3];
 } cn_ast_opts;
 int cn_decode_ast(cn_model* m, const float* feats_dev, int32_t B, int32_t T, int32_t F, const cn_decode_opts* opts,
                   const cn_ast_opts* ast_opts, int32_t* hyp_out_dev, int32_t max_len, int32_t* hyp_len_dev, double* score_dev,

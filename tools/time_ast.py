@@ -5,7 +5,12 @@ configs[1]); prints one JSON line with utterances/s, ms per decode step and wher
 2048, now Swish) behind a 12-layer conformer encoder.  Both models report the encoder pass (cn_ast_begin: encoder, cross K|V, CTC
 preparation) apart from the decoder steps: ``decoder_ms_per_step`` = (search - encoder) / steps.
 
+``--lm lm_small|lm_recipe``: LM shallow fusion (transformer.py:186-209) with a seeded TransformerLM of that synth preset
+(lm_recipe = conf/lm.yaml: 16 layers, d 512); ``lm_ms_per_step`` times the LM step alone (cn_lm_step over the same slots and
+positions).  ``--beam`` / ``--ctc-beam``: run_art.sh stage 3 uses 20 / 30.
+
     python tools/time_ast.py [--model transformer|conformer] [--batch 32] [--frames 1000] [--precision bf16] [--ctc-weight 0.3] [--ratio 0.3]
+                             [--lm none|lm_small|lm_recipe] [--lm-weight 0.6] [--beam 10] [--ctc-beam 15]
 """
 import argparse
 import json
@@ -18,6 +23,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from cassnat_asr_public_amd import hip, synth  # noqa: E402
 from cassnat_asr_public_amd.models.conformer import make_model as make_conformer  # noqa: E402
+from cassnat_asr_public_amd.models.lm import make_model as make_lm  # noqa: E402
 from cassnat_asr_public_amd.models.transformer import make_model as make_transformer  # noqa: E402
 
 
@@ -37,9 +43,14 @@ def main():
     ap.add_argument("--streams", type=int, default=1,
                     help="decode pipelines (engine handle + HIP stream + host thread each) working on independent batches: a decode "
                          "step occupies a handful of CUs, so throughput - not latency - scales with pipelines")
+    ap.add_argument("--lm", choices=("none", "lm_small", "lm_recipe"), default="none")
+    ap.add_argument("--lm-weight", type=float, default=0.6)
+    ap.add_argument("--beam", type=int, default=10)
+    ap.add_argument("--ctc-beam", type=int, default=15)
     a = ap.parse_args()
     args = synth.make_args_ast("config4" if a.model == "transformer" else "config4_conf", ctc_weight=a.ctc_weight,
-                               max_decode_ratio=a.ratio)
+                               max_decode_ratio=a.ratio, beam_width=a.beam, ctc_beam=a.ctc_beam,
+                               lm_weight=a.lm_weight if a.lm != "none" else 0)
     make_model = make_transformer if a.model == "transformer" else make_conformer
     args.hip_precision = a.precision
     args.hip_max_batch = a.batch
@@ -50,13 +61,22 @@ def main():
     with torch.no_grad():
         for k, p in model.named_parameters():
             p.copy_(torch.from_numpy(state[k]))
+    lm = None
+    if a.lm != "none":
+        lm_args = synth.make_args_lm(a.lm, vocab_size=args.vocab_size)
+        lm_args.hip_precision = a.precision
+        lm = make_lm(lm_args).cuda()
+        lm_state = synth.make_state(lm_args, seed=9)
+        with torch.no_grad():
+            for k, p in lm.named_parameters():
+                p.copy_(torch.from_numpy(lm_state[k]))
     src = torch.from_numpy(feats).cuda()
     mask = (src[:, :, 0] != args.padding_idx).unsqueeze(1)
     times = []
     for r in range(a.reps + 1):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        beams = model.beam_decode(src, mask, Vocab, args)
+        beams = model.beam_decode(src, mask, Vocab, args, lm)
         torch.cuda.synchronize()
         times.append(time.perf_counter() - t0)
     best = min(times[1:])
@@ -73,7 +93,26 @@ def main():
         torch.cuda.synchronize()
         enc.append(time.perf_counter() - t0)
     enc_best = min(enc[1:])
-    out = {"workload": "BASELINE configs[3]: AST beam search, 12L enc / 6L dec, beam 10, ctc_beam 15",
+    lm_ms = None
+    if lm is not None:  # the LM step alone on the beam's slots, position after position (identity ancestor table)
+        S = a.batch * int(args.beam_width)
+        leng = lm.step_engine(S)
+        leng.lm_step_begin(steps + 1, S)
+        tok = torch.full((S,), 5, dtype=torch.int32, device="cuda")
+        anc = torch.arange(S, dtype=torch.int32, device="cuda").view(S, 1).repeat(1, steps + 1).contiguous()
+        keyok = torch.ones(S, steps + 1, dtype=torch.uint8, device="cuda")
+        logp = torch.empty(S, args.vocab_size, dtype=torch.float32, device="cuda")
+        lt = []
+        for r in range(a.reps + 1):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for pos in range(steps):
+                leng.lm_step(pos, tok, anc, keyok, logp)
+            torch.cuda.synchronize()
+            lt.append(time.perf_counter() - t0)
+        lm_ms = round(1e3 * min(lt[1:]) / max(steps, 1), 3)
+    out = {"workload": "BASELINE configs[3]: AST beam search, 12L enc / 6L dec, beam %d, ctc_beam %d" % (args.beam_width, args.ctc_beam),
+           "lm": a.lm, "lm_weight": args.lm_weight, "lm_ms_per_step": lm_ms,
            "model": a.model, "encoder": "conformer (d_encff 1024, kernel 31, max_rel 20)" if a.model == "conformer" else "transformer",
            "decoder_ffn": "swish" if a.model == "conformer" else "relu",
            "encoder_ms": round(1e3 * enc_best, 3), "decoder_ms_per_step": round(1e3 * (best - enc_best) / max(steps, 1), 3),
@@ -91,12 +130,15 @@ def main():
                 for k, p in m2.named_parameters():
                     p.copy_(torch.from_numpy(state[k]))
             models.append(m2)
+        S = a.batch * int(args.beam_width)  # one LM handle (own step cache) per pipeline, one copy of the LM weights
+        lm_engs = [None] * a.streams if lm is None else [lm.step_engine(S)] + [lm.new_engine(S, share=lm.step_engine(S))
+                                                                                 for _ in range(a.streams - 1)]
 
         def worker(i, n):
             st = torch.cuda.Stream()
             with torch.cuda.stream(st):
                 for _ in range(n):
-                    models[i].beam_decode(src, mask, Vocab, args)
+                    models[i].beam_decode(src, mask, Vocab, args, lm, lm_engine=lm_engs[i])
                 st.synchronize()
 
         for n in (1, a.reps):  # warm-up round (engine builds), then the timed one
