@@ -316,6 +316,11 @@ __global__ void ast_ctc_prefix_kernel(CtcPrefixArgs a) {
 }
 
 int launch_ast_ctc_prefix(const CtcPrefixArgs& a, hipStream_t s) {
+    // out_len > Tp: the first loop would write states past the candidate's Tp x 2 block (the reference raises IndexError there)
+    if (a.Tp < 1 || a.out_len < 0 || a.out_len > a.Tp) {
+        cn_set_error("ast_ctc_prefix: need 0 <= out_len <= Tp (a hypothesis longer than the CTC frames)");
+        return -1;
+    }
     if (a.n <= 0 || a.K <= 0) return 0;
     hipLaunchKernelGGL(ast_ctc_prefix_kernel, dim3(cn_ceil_div(a.n * a.K, 64)), dim3(64), 0, s, a);
     CN_HIP_CHECK(hipGetLastError());
@@ -379,7 +384,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void ast_beam_update_kernel(AstBeamSt
         const int s = b * bw + fin_idx[tid];
         const double sc = st.score[cur][s];
         cscore[tid] = sc;
-        ckey[tid] = q.use_lp ? sc + (double)(st.len[cur][s] - 1) * q.lp : sc;
+        ckey[tid] = q.use_lp ? sc + cn_mul_rn((double)(st.len[cur][s] - 1), q.lp) : sc;
         cpar[tid] = fin_idx[tid];
         ccand[tid] = -1;
     }
@@ -388,10 +393,11 @@ __global__ __launch_bounds__(BEAM_THREADS) void ast_beam_update_kernel(AstBeamSt
         const int s = b * bw + live_idx[li];
         const float att = q.att[(long long)s * K + c];
         // local = ctc_weight * (ctc - prev) + (1 - ctc_weight) * att, float32, one rounding per operation (transformer.py:205-206)
-        float v = q.use_ctc ? __fadd_rn(__fmul_rn(q.w, __fsub_rn(q.ctc[(long long)s * K + c], st.ctc_prev[cur][s])), __fmul_rn(q.u, att))
+        // (cn_mul_rn: the products are rounded before the sums - hipcc would otherwise contract them into FMAs)
+        float v = q.use_ctc ? __fadd_rn(cn_mul_rn(q.w, __fsub_rn(q.ctc[(long long)s * K + c], st.ctc_prev[cur][s])), cn_mul_rn(q.u, att))
                             : att;
         // local += lm_weight * lm_prob.gather(1, indices) (transformer.py:208-209); without CTC `att` already holds the fused sum
-        if (q.use_lm && q.use_ctc) v = __fadd_rn(v, __fmul_rn(q.lw, q.lm[(long long)s * K + c]));
+        if (q.use_lm && q.use_ctc) v = __fadd_rn(v, cn_mul_rn(q.lw, q.lm[(long long)s * K + c]));
         loc[li][c] = v;
     }
     __syncthreads();
@@ -404,7 +410,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void ast_beam_update_kernel(AstBeamSt
             const int j = live_idx[li], s = b * bw + j, e = nf + li * bw + r;
             const double sc = st.score[cur][s] + (double)v;
             cscore[e] = sc;
-            ckey[e] = q.use_lp ? sc + (double)st.len[cur][s] * q.lp : sc;  // new length - 1 = old length
+            ckey[e] = q.use_lp ? sc + cn_mul_rn((double)st.len[cur][s], q.lp) : sc;  // new length - 1 = old length
             cpar[e] = j;
             ccand[e] = c;
             ctok[e] = q.idx[(long long)s * K + c];
@@ -474,8 +480,9 @@ int launch_ast_beam_init(const AstBeamState& st, int cur, int B, int bw, int L, 
 }
 
 int launch_ast_beam_update(const AstBeamState& st, const AstBeamStep& q, int B, hipStream_t s) {
-    if (q.bw < 1 || q.bw > BEAM_MAXW || q.K < 1 || q.K > BEAM_MAXW) {
-        cn_set_error("ast beam: beam_width and candidate count must be in 1..32");
+    // (K < bw: the candidate list would have holes - e = nf + li * bw + r, r < K - and torch.topk refuses it too)
+    if (q.bw < 1 || q.bw > BEAM_MAXW || q.K < q.bw || q.K > BEAM_MAXW) {
+        cn_set_error("ast beam: need 1 <= beam_width <= candidate count <= 32");
         return -1;
     }
     CN_HIP_CHECK(hipMemsetAsync(st.live, 0, sizeof(int), s));

@@ -93,6 +93,19 @@ __host__ __device__ static inline long long cn_blk16_off(long long m, int c, int
 
 #define CN_WAVE 64
 #define CN_NEG_FILL (-3.4028234663852886e38f) /* float32 min: the reference's masked_fill value */
+// A product rounded on its own: the empty asm makes the value opaque, so the compiler cannot contract a * b + c into one FMA
+// (hipcc contracts across __fmul_rn / __fadd_rn, which are plain operators in HIP, even under #pragma clang fp contract(off)).
+// For arithmetic that must round like torch's separate elementwise ops or Python floats.
+__device__ __forceinline__ float cn_mul_rn(float a, float b) {
+    float p = a * b;
+    __asm__ volatile("" : "+v"(p));
+    return p;
+}
+__device__ __forceinline__ double cn_mul_rn(double a, double b) {
+    double p = a * b;
+    __asm__ volatile("" : "+v"(p));
+    return p;
+}
 
 // ----------------------------------------------------------------------------------------------
 // 16-byte fragment of the GEMM K dimension as one wave lane sees it.

@@ -3762,6 +3762,195 @@ extern "C" int cn_op_logsoftmax_topk(const float* logits, int32_t M, int32_t V, 
     return launch_logsoftmax_topk(logits, M, V, V, temperature, k, idx, val, (hipStream_t)stream);
 }
 
+extern "C" int cn_op_logsoftmax_fuse_topk(const float* att, const float* lm, int32_t M, int32_t V, float temperature, float w,
+                                          int32_t k, int32_t* idx, float* val, void* stream) {
+    if (M < 0 || V < 1 || (M > 0 && (!att || !lm || !idx || !val))) {
+        cn_set_error("cn_op_logsoftmax_fuse_topk: bad argument");
+        return -1;
+    }
+    return launch_logsoftmax_fuse_topk(att, lm, M, V, V, temperature, w, k, idx, val, (hipStream_t)stream);
+}
+
+extern "C" int cn_op_logsoftmax_gather(const float* logits, int32_t M, int32_t V, const int32_t* cand, int32_t k, float* out,
+                                       void* stream) {
+    if (M < 0 || V < 1 || (M > 0 && (!logits || !cand || !out))) {
+        cn_set_error("cn_op_logsoftmax_gather: bad argument");
+        return -1;
+    }
+    return launch_logsoftmax_gather(logits, M, V, V, cand, k, out, (hipStream_t)stream);
+}
+
+// ---- kernel-test entries of the AST beam search's step kernels (ast.hip)
+extern "C" int cn_op_ast_gather_attn(int32_t precision, int32_t mode, const void* q, int32_t ldq, void* k, void* v, void* o,
+                                     int32_t ldo, int32_t n, int32_t H, int32_t nkeys, int32_t slots, int32_t d, int32_t table_stride,
+                                     const int32_t* anc, const uint8_t* keyok, const int32_t* utt, const uint8_t* keymask, float scale,
+                                     int32_t append_pos, void* stream) {
+    if ((precision = cn_own_precision(precision, "cn_op_ast_gather_attn")) < 0) return -1;
+    if (precision != CN_PREC_F32 && precision != CN_PREC_BF16 && precision != CN_PREC_X3) {
+        cn_set_error("cn_op_ast_gather_attn: precision must be F32, BF16 (F16 in the half-precision build) or BF16X3");
+        return -1;
+    }
+    if (mode != 0 && mode != 1) {
+        cn_set_error("cn_op_ast_gather_attn: mode must be 0 (cache) or 1 (source memory)");
+        return -1;
+    }
+    if (n < 0 || H < 1 || H > 16 || d != 64 * H || nkeys < 1 || ldo < d || ldq < (mode == 0 ? 3 * d : d) || !q || !k || !v ||
+        (n > 0 && !o)) {
+        cn_set_error("cn_op_ast_gather_attn: need 1 <= H <= 16, d = 64 * H, nkeys >= 1, ldo >= d and ldq >= 3d (mode 0) / d (mode 1)");
+        return -1;
+    }
+    if (mode == 0 && (slots < n || table_stride < nkeys || append_pos < -1 || append_pos >= nkeys || !anc || !keyok)) {
+        cn_set_error("cn_op_ast_gather_attn: mode 0 needs slots >= n, table_stride >= nkeys, -1 <= append_pos < nkeys, anc and keyok");
+        return -1;
+    }
+    if (mode == 1 && (!utt || !keymask)) {
+        cn_set_error("cn_op_ast_gather_attn: mode 1 needs utt and keymask");
+        return -1;
+    }
+    GatherAttnArgs a;
+    a.q = q;
+    a.ldq = ldq;
+    a.k = k;
+    a.v = v;
+    a.o = o;
+    a.ldo = ldo;
+    a.n = n;
+    a.H = H;
+    a.nkeys = nkeys;
+    a.slots = slots;
+    a.d = d;
+    a.table_stride = table_stride;
+    a.anc = anc;
+    a.keyok = keyok;
+    a.utt = utt;
+    a.keymask = keymask;
+    a.scale = scale;
+    a.append_pos = mode == 0 ? append_pos : -1;
+    return launch_ast_gather_attn(precision, mode, a, (hipStream_t)stream);
+}
+
+extern "C" int cn_op_ast_ctc_prepare(float* logp, const uint8_t* keymask, float* r0, int32_t B, int32_t Tp, int32_t V, int32_t blank,
+                                     void* stream) {
+    if (B < 1 || Tp < 1 || V < 1 || blank < 0 || blank >= V || !logp || !keymask || !r0) {
+        cn_set_error("cn_op_ast_ctc_prepare: need B, Tp, V >= 1, 0 <= blank < V and non-null buffers");
+        return -1;
+    }
+    return launch_ast_ctc_prepare(logp, keymask, r0, B, Tp, V, blank, (hipStream_t)stream);
+}
+
+extern "C" int cn_op_ast_ctc_prefix(const float* logp, const float* r0, const float* r_prev, float* r_new, const int32_t* utt,
+                                    const int32_t* last_tok, const int32_t* cand, const int32_t* prev_ref, float* score, int32_t n,
+                                    int32_t K, int32_t Tp, int32_t V, int32_t blank, int32_t eos, int32_t out_len, void* stream) {
+    if (n < 0 || K < 1 || Tp < 1 || V < 1 || blank < 0 || blank >= V || out_len < 0 || out_len > Tp ||
+        (n > 0 && (!logp || !r0 || !r_new || !utt || !last_tok || !cand || !prev_ref || !score))) {
+        cn_set_error("cn_op_ast_ctc_prefix: need n >= 0, K, Tp, V >= 1, 0 <= blank < V, 0 <= out_len <= Tp and non-null buffers");
+        return -1;
+    }
+    CtcPrefixArgs a;
+    a.logp = logp;
+    a.r0 = r0;
+    a.r_prev = r_prev;
+    a.r_new = r_new;
+    a.utt = utt;
+    a.last_tok = last_tok;
+    a.cand = cand;
+    a.prev_ref = prev_ref;
+    a.score = score;
+    a.n = n;
+    a.K = K;
+    a.Tp = Tp;
+    a.V = V;
+    a.blank = blank;
+    a.eos = eos;
+    a.out_len = out_len;
+    return launch_ast_ctc_prefix(a, (hipStream_t)stream);
+}
+
+static int ast_beam_state_of(AstBeamState& st, int32_t* tok0, int32_t* tok1, int32_t* anc0, int32_t* anc1, uint8_t* keyok0,
+                             uint8_t* keyok1, int32_t* len0, int32_t* len1, double* score0, double* score1, int32_t* valid0,
+                             int32_t* valid1, int32_t* ctc_ref0, int32_t* ctc_ref1, float* ctc_prev0, float* ctc_prev1, int32_t* cur_tok,
+                             int32_t* utt, int32_t* live, const char* who) {
+    const void* all[] = {tok0, tok1, anc0, anc1, keyok0, keyok1, len0, len1, score0, score1, valid0, valid1, ctc_ref0, ctc_ref1,
+                         ctc_prev0, ctc_prev1, cur_tok, utt, live};
+    for (const void* ptr : all)
+        if (!ptr) {
+            cn_set_error(std::string(who) + ": null state array");
+            return -1;
+        }
+    st.tok[0] = tok0;
+    st.tok[1] = tok1;
+    st.anc[0] = anc0;
+    st.anc[1] = anc1;
+    st.keyok[0] = keyok0;
+    st.keyok[1] = keyok1;
+    st.len[0] = len0;
+    st.len[1] = len1;
+    st.score[0] = score0;
+    st.score[1] = score1;
+    st.valid[0] = valid0;
+    st.valid[1] = valid1;
+    st.ctc_ref[0] = ctc_ref0;
+    st.ctc_ref[1] = ctc_ref1;
+    st.ctc_prev[0] = ctc_prev0;
+    st.ctc_prev[1] = ctc_prev1;
+    st.cur_tok = cur_tok;
+    st.utt = utt;
+    st.live = live;
+    return 0;
+}
+
+extern "C" int cn_op_ast_beam_init(int32_t* tok0, int32_t* tok1, int32_t* anc0, int32_t* anc1, uint8_t* keyok0, uint8_t* keyok1,
+                                   int32_t* len0, int32_t* len1, double* score0, double* score1, int32_t* valid0, int32_t* valid1,
+                                   int32_t* ctc_ref0, int32_t* ctc_ref1, float* ctc_prev0, float* ctc_prev1, int32_t* cur_tok, int32_t* utt,
+                                   int32_t* live, int32_t cur, int32_t B, int32_t bw, int32_t L, int32_t sos, int32_t pad, void* stream) {
+    if (B < 1 || bw < 1 || bw > 32 || L < 1 || (cur != 0 && cur != 1)) {
+        cn_set_error("cn_op_ast_beam_init: need B >= 1, 1 <= beam_width <= 32, L >= 1 and cur 0 or 1");
+        return -1;
+    }
+    AstBeamState st;
+    CN_TRY(ast_beam_state_of(st, tok0, tok1, anc0, anc1, keyok0, keyok1, len0, len1, score0, score1, valid0, valid1, ctc_ref0, ctc_ref1,
+                             ctc_prev0, ctc_prev1, cur_tok, utt, live, "cn_op_ast_beam_init"));
+    return launch_ast_beam_init(st, cur, B, bw, L, sos, pad, (hipStream_t)stream);
+}
+
+extern "C" int cn_op_ast_beam_update(int32_t* tok0, int32_t* tok1, int32_t* anc0, int32_t* anc1, uint8_t* keyok0, uint8_t* keyok1,
+                                     int32_t* len0, int32_t* len1, double* score0, double* score1, int32_t* valid0, int32_t* valid1,
+                                     int32_t* ctc_ref0, int32_t* ctc_ref1, float* ctc_prev0, float* ctc_prev1, int32_t* cur_tok,
+                                     int32_t* utt, int32_t* live, const int32_t* idx, const float* att, const float* ctc, const float* lm,
+                                     int32_t cur, int32_t pos, int32_t bw, int32_t K, int32_t L, int32_t eos, int32_t sos, int32_t pad,
+                                     int32_t use_ctc, int32_t use_lp, int32_t use_lm, float w, float u, float lw, double lp, int32_t B,
+                                     void* stream) {
+    if (B < 1 || bw < 1 || bw > 32 || K < bw || K > 32 || L < 1 || (cur != 0 && cur != 1) || !idx || !att || (use_ctc && !ctc) ||
+        (use_ctc && use_lm && !lm)) {
+        cn_set_error("cn_op_ast_beam_update: need B >= 1, 1 <= beam_width <= K <= 32, L >= 1, cur 0 or 1 and the step's arrays");
+        return -1;
+    }
+    AstBeamState st;
+    CN_TRY(ast_beam_state_of(st, tok0, tok1, anc0, anc1, keyok0, keyok1, len0, len1, score0, score1, valid0, valid1, ctc_ref0, ctc_ref1,
+                             ctc_prev0, ctc_prev1, cur_tok, utt, live, "cn_op_ast_beam_update"));
+    AstBeamStep q;
+    q.idx = idx;
+    q.att = att;
+    q.ctc = ctc;
+    q.lm = lm;
+    q.cur = cur;
+    q.pos = pos;
+    q.bw = bw;
+    q.K = K;
+    q.L = L;
+    q.eos = eos;
+    q.sos = sos;
+    q.pad = pad;
+    q.use_ctc = use_ctc;
+    q.use_lp = use_lp;
+    q.use_lm = use_lm;
+    q.w = w;
+    q.u = u;
+    q.lw = lw;
+    q.lp = lp;
+    return launch_ast_beam_update(st, q, B, (hipStream_t)stream);
+}
+
 static int op_ffn_fused_impl(float* x_dev, const float* ln_a_dev, const float* ln_b_dev, const float* w1_host, const float* b1_dev,
                              const float* w2_host, const float* b2_dev, const float* nln_a_dev, const float* nln_b_dev, void* xn_out_dev,
                              int32_t M, int32_t dff, float eps, int32_t nslice, int32_t act, void* stream) {
@@ -4577,8 +4766,8 @@ extern "C" int cn_ast_step(cn_model* m, int32_t n, int32_t pos, const int32_t* t
         return -1;
     }
     if (n < 1 || n > m->ast_slots || pos < 0 || pos >= m->ast_max_len || pos >= m->pe_rows || K < 1 || K > 32 ||
-        table_stride <= pos) {
-        cn_set_error("cn_ast_step: live rows / position / K outside the configured cache");
+        K > m->cfg.vocab_size || table_stride <= pos) {
+        cn_set_error("cn_ast_step: live rows / position / K outside the configured cache (K <= 32 and <= the vocabulary)");
         return -1;
     }
     CN_HIP_CHECK(hipSetDevice(m->cfg.device));
@@ -4599,8 +4788,9 @@ extern "C" int cn_ast_step_lm(cn_model* m, int32_t n, int32_t pos, const int32_t
         return -1;
     }
     if (n < 1 || n > m->ast_slots || pos < 0 || pos >= m->ast_max_len || pos >= m->pe_rows || K < 1 || K > 32 ||
-        table_stride <= pos || (use_ctc && !lm_val_dev)) {
-        cn_set_error("cn_ast_step_lm: live rows / position / K outside the configured cache (or use_ctc without lm_val_dev)");
+        K > m->cfg.vocab_size || table_stride <= pos || (use_ctc && !lm_val_dev)) {
+        cn_set_error("cn_ast_step_lm: live rows / position / K outside the configured cache (K <= 32 and <= the vocabulary; or use_ctc "
+                     "without lm_val_dev)");
         return -1;
     }
     CN_HIP_CHECK(hipSetDevice(m->cfg.device));
@@ -4681,6 +4871,18 @@ extern "C" int cn_decode_ast(cn_model* m, const float* feats_dev, int32_t B, int
     const int K = want_ctc ? ao->ctc_beam : bw;
     if (bw < 1 || bw > 32 || K < bw || K > 32 || ao->max_step < 1 || max_len < ao->max_step + 1) {
         cn_set_error("cn_decode_ast: need 1 <= beam_width <= ctc_beam <= 32 and max_len > max_step");
+        return -1;
+    }
+    if (K > m->cfg.vocab_size) {
+        cn_set_error("cn_decode_ast: the candidate count (ctc_beam, or beam_width without CTC) exceeds the vocabulary");
+        return -1;
+    }
+    // step pos scores prefixes of pos tokens: the CTC prefix scorer is defined up to out_len == T' (the reference raises
+    // IndexError beyond it), so the last step, max_step - 1, must not pass the subsampled frame count
+    const int Tp = ((T - 1) / 2 + 1 - 1) / 2 + 1;
+    if (want_ctc && ao->max_step > Tp + 1) {
+        cn_set_error("cn_decode_ast: with CTC, max_step may not exceed the subsampled frame count + 1 (max_decode_ratio too large: "
+                     "the CTC prefix score of a hypothesis longer than the frames is undefined)");
         return -1;
     }
     const bool use_lm = ao->lm_weight > 0.f;

@@ -270,8 +270,8 @@ __global__ __launch_bounds__(256) void topk_kernel(const float* __restrict__ log
 }
 
 int launch_topk(const float* logp, int M, int V, int ldl, int k, int* idx, float* val, hipStream_t s) {
-    if (k < 1 || k > 64 || V > 16384) {
-        cn_set_error("topk: need 1 <= k <= 64 and V <= 16384");
+    if (k < 1 || k > 64 || k > V || V > 16384) {
+        cn_set_error("topk: need 1 <= k <= min(64, V) and V <= 16384");
         return -1;
     }
     if (M <= 0) return 0;
@@ -378,7 +378,7 @@ __global__ __launch_bounds__(256) void logsoftmax_topk_kernel(const float* __res
         const float llse = logf((s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]));
         __syncthreads();  // s_val is rewritten by the selection rounds
         for (int i = tid; i < V; i += 256)
-            row[i] = __fadd_rn(__fsub_rn(__fsub_rn(row[i], rmax), lse), __fmul_rn(w, __fsub_rn(__fsub_rn(lrow[i], lmax), llse)));
+            row[i] = __fadd_rn(__fsub_rn(__fsub_rn(row[i], rmax), lse), cn_mul_rn(w, __fsub_rn(__fsub_rn(lrow[i], lmax), llse)));
     } else {
         for (int i = tid; i < V; i += 256) row[i] = (row[i] - rmax) - lse;
     }
@@ -400,8 +400,8 @@ __global__ __launch_bounds__(256) void logsoftmax_topk_kernel(const float* __res
 
 int launch_logsoftmax_topk(const float* logits, int M, int V, int ldl, float temperature, int k, int* idx, float* val,
                            hipStream_t s) {
-    if (k < 1 || k > 32 || V > 16384) {
-        cn_set_error("logsoftmax_topk: need 1 <= k <= 32 and V <= 16384");
+    if (k < 1 || k > 32 || k > V || V > 16384) {  // (k > V: a round would pick a retired entry again)
+        cn_set_error("logsoftmax_topk: need 1 <= k <= min(32, V) and V <= 16384");
         return -1;
     }
     if (M <= 0) return 0;
@@ -413,8 +413,8 @@ int launch_logsoftmax_topk(const float* logits, int M, int V, int ldl, float tem
 
 int launch_logsoftmax_fuse_topk(const float* att, const float* lm, int M, int V, int ldl, float temperature, float w, int k,
                                 int* idx, float* val, hipStream_t s) {
-    if (k < 1 || k > 32 || V > 8192) {
-        cn_set_error("logsoftmax_fuse_topk: need 1 <= k <= 32 and V <= 8192");
+    if (k < 1 || k > 32 || k > V || V > 8192) {
+        cn_set_error("logsoftmax_fuse_topk: need 1 <= k <= min(32, V) and V <= 8192");
         return -1;
     }
     if (M <= 0) return 0;

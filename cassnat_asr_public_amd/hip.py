@@ -135,6 +135,15 @@ def lib(flavour=None):
     L.cn_op_unpack_rows.argtypes = [C.c_void_p] * 4 + [C.c_int32] * 3 + [C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
     L.cn_op_quantize_fp8.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_void_p]
     L.cn_op_logsoftmax_topk.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.cn_op_logsoftmax_fuse_topk.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_int32, C.c_void_p,
+                                             C.c_void_p, C.c_void_p]
+    L.cn_op_logsoftmax_gather.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    L.cn_op_ast_gather_attn.argtypes = ([C.c_int32, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 3 + [C.c_int32] * 7 +
+                                        [C.c_void_p] * 4 + [C.c_float, C.c_int32, C.c_void_p])
+    L.cn_op_ast_ctc_prepare.argtypes = [C.c_void_p] * 3 + [C.c_int32] * 4 + [C.c_void_p]
+    L.cn_op_ast_ctc_prefix.argtypes = [C.c_void_p] * 9 + [C.c_int32] * 7 + [C.c_void_p]
+    L.cn_op_ast_beam_init.argtypes = [C.c_void_p] * 19 + [C.c_int32] * 6 + [C.c_void_p]
+    L.cn_op_ast_beam_update.argtypes = ([C.c_void_p] * 23 + [C.c_int32] * 11 + [C.c_float] * 3 + [C.c_double, C.c_int32, C.c_void_p])
     L.cn_model_create.argtypes = [C.POINTER(CnConfig), C.POINTER(C.c_void_p)]
     L.cn_model_create_shared.argtypes = [C.POINTER(CnConfig), C.c_void_p, C.POINTER(C.c_void_p)]
     L.cn_model_destroy.argtypes = [C.c_void_p]

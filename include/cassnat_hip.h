@@ -472,6 +472,45 @@ int cn_op_quantize_fp8(const void* src_bf16_dev, int32_t ld, void* dst_dev, int3
  * top-k (sorted descending, ties: lower index) in one pass; the logits [M][V] are left untouched */
 int cn_op_logsoftmax_topk(const float* logits, int32_t M, int32_t V, float temperature, int32_t k, int32_t* idx, float* val,
                           void* stream);
+/* LM shallow fusion tails (src/models/transformer.py:190-192, 208-209), rows of V fp32 logits:
+ * cn_op_logsoftmax_fuse_topk: top-k (1 <= k <= min(32, V), V <= 8192) over V of log_softmax(att / T) + fl32(w * log_softmax(lm)),
+ *   float32 with one rounding per operation, sorted descending (ties: lower index);
+ * cn_op_logsoftmax_gather: out [M][k] = log_softmax(logits) at cand [M][k] (k <= 256, V <= 16384; a candidate outside [0, V): -inf) */
+int cn_op_logsoftmax_fuse_topk(const float* att, const float* lm, int32_t M, int32_t V, float temperature, float w, int32_t k,
+                               int32_t* idx, float* val, void* stream);
+int cn_op_logsoftmax_gather(const float* logits, int32_t M, int32_t V, const int32_t* cand, int32_t k, float* out, void* stream);
+/* The step kernels of the AST beam search one at a time (cn_decode_ast runs them inside its loop).
+ * cn_op_ast_gather_attn: single-query attention of n rows over gathered keys, d = 64 * H (head h at columns 64h..), elements of
+ *   the precision's type.  mode 0 (decoder self-attention over the KV cache k / v [pos][slots][d]): key j of row r is cache row
+ *   (j, anc[r][j]), allowed iff keyok[r][j] (tables [n][table_stride]); q rows hold the fused projection Q | K | V (ldq >= 3d) and
+ *   append_pos >= 0 also writes row r's K | V to cache row (append_pos, slot r) and reads key append_pos from q's row.  mode 1
+ *   (source attention): k / v point at the K and V columns of rows [B * nkeys] of stride 2d; key j of row r is row
+ *   utt[r] * nkeys + j, allowed iff keymask[utt[r]][j].  Masked keys score float32 min (a row without an allowed key averages all). */
+int cn_op_ast_gather_attn(int32_t precision, int32_t mode, const void* q, int32_t ldq, void* k, void* v, void* o, int32_t ldo, int32_t n,
+                          int32_t H, int32_t nkeys, int32_t slots, int32_t d, int32_t table_stride, const int32_t* anc, const uint8_t* keyok,
+                          const int32_t* utt, const uint8_t* keymask, float scale, int32_t append_pos, void* stream);
+/* CTC side (src/utils/ctc_prefix.py): prepare masks logp [B][Tp][V] in place (frames with keymask 0: logzero, blank 0) and writes
+ * the initial states r0 [B][Tp][2]; prefix scores the K candidates cand [n][K] of n prefixes of out_len tokens (0 <= out_len <= Tp)
+ * -> score [n][K] and states r_new [n * K][Tp][2]; prev_ref[h] >= 0 takes row prev_ref[h] of r_prev, < 0 the initial state of
+ * utterance -1 - prev_ref[h]. */
+int cn_op_ast_ctc_prepare(float* logp, const uint8_t* keymask, float* r0, int32_t B, int32_t Tp, int32_t V, int32_t blank, void* stream);
+int cn_op_ast_ctc_prefix(const float* logp, const float* r0, const float* r_prev, float* r_new, const int32_t* utt, const int32_t* last_tok,
+                         const int32_t* cand, const int32_t* prev_ref, float* score, int32_t n, int32_t K, int32_t Tp, int32_t V,
+                         int32_t blank, int32_t eos, int32_t out_len, void* stream);
+/* Beam bookkeeping on the device state of cn_decode_ast, both parities of every double-buffered array passed separately
+ * (S = B * bw slots, L tokens per slot): tok / anc int32 [S][L], keyok uint8 [S][L], len / valid / ctc_ref int32 [S], score double
+ * [S], ctc_prev float [S]; cur_tok / utt int32 [S]; live int32 [1].  init fills parity cur; update reads parity cur and this
+ * step's candidates (idx / att / ctc / lm [S][K]) and writes parity cur ^ 1.  1 <= bw <= K <= 32. */
+int cn_op_ast_beam_init(int32_t* tok0, int32_t* tok1, int32_t* anc0, int32_t* anc1, uint8_t* keyok0, uint8_t* keyok1, int32_t* len0,
+                        int32_t* len1, double* score0, double* score1, int32_t* valid0, int32_t* valid1, int32_t* ctc_ref0, int32_t* ctc_ref1,
+                        float* ctc_prev0, float* ctc_prev1, int32_t* cur_tok, int32_t* utt, int32_t* live, int32_t cur, int32_t B, int32_t bw,
+                        int32_t L, int32_t sos, int32_t pad, void* stream);
+int cn_op_ast_beam_update(int32_t* tok0, int32_t* tok1, int32_t* anc0, int32_t* anc1, uint8_t* keyok0, uint8_t* keyok1, int32_t* len0,
+                          int32_t* len1, double* score0, double* score1, int32_t* valid0, int32_t* valid1, int32_t* ctc_ref0,
+                          int32_t* ctc_ref1, float* ctc_prev0, float* ctc_prev1, int32_t* cur_tok, int32_t* utt, int32_t* live,
+                          const int32_t* idx, const float* att, const float* ctc, const float* lm, int32_t cur, int32_t pos, int32_t bw,
+                          int32_t K, int32_t L, int32_t eos, int32_t sos, int32_t pad, int32_t use_ctc, int32_t use_lp, int32_t use_lm,
+                          float w, float u, float lw, double lp, int32_t B, void* stream);
 
 #ifdef __cplusplus
 }

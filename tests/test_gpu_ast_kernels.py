@@ -1,0 +1,736 @@
+"""The step kernels of the device AST beam search (csrc/ast.hip, csrc/rowops.hip), one at a time, against plain models of the same
+operation: float64 attention and CTC prefix scores, a Python restatement of the beam bookkeeping of Transformer.beam_decode
+(src/models/transformer.py:157-240) and a float32 emulation of the LM-fusion tails.  Inputs are seeded and built to reach the
+edges: beams and candidate lists of 21-32, finished hypotheses beside live ones under a length penalty, exact ties, rows whose keys
+are all masked, frame counts that are not multiples of the CTC kernel's 8-frame load batch, prefixes as long as the frames.
+
+Run with -s to see the measured worst-case errors against the float64 models."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+from cassnat_asr_public_amd import hip
+from oracle import ast_oracle
+
+pytestmark = pytest.mark.gpu
+
+EPS = 2.0 ** -24  # float32 unit roundoff
+NEG_FILL = float(np.finfo(np.float32).min)  # masked attention score (the reference's masked_fill value)
+LOGZERO = np.float32(-1e10)
+
+
+def p(t):
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def stream():
+    return hip.current_stream()
+
+
+def gamma(n):
+    return n * EPS / (1 - n * EPS)
+
+
+def ulp32(x):
+    return np.spacing(np.abs(np.asarray(x, np.float32))).astype(np.float64)
+
+
+# ============================================================================================ LM-fusion tails (rowops.hip)
+def logsoftmax32(x, T=1.0):
+    """float32 log_softmax(x / T) in torch's order: (x / T - max) - lse, lse = log(sum exp(x / T - max)) rounded once."""
+    y = (x / np.float32(T)).astype(np.float32) if T != 1.0 else x.astype(np.float32)
+    m = y.max(1, keepdims=True)
+    d = (y - m).astype(np.float32)
+    lse = np.log(np.exp(d.astype(np.float64)).sum(1, keepdims=True)).astype(np.float32)
+    return (d - lse).astype(np.float32), lse
+
+
+def logsoftmax64(x, T=1.0):
+    y = x.astype(np.float64) / T
+    y = y - y.max(1, keepdims=True)
+    return y - np.log(np.exp(y).sum(1, keepdims=True))
+
+
+def fusion_rows(M, V, seed):
+    """att / lm logits; row 0: the attention top-k is pushed out by the LM (fused set != attention set); row 1: exact ties in
+    both rows (lower index must win); row 2: quantised logits (ties all the way down the ranking)."""
+    g = np.random.default_rng(seed)
+    att = (g.standard_normal((M, V)) * 3).astype(np.float32)
+    lm = (g.standard_normal((M, V)) * 3).astype(np.float32)
+    top = np.argsort(-att[0], kind="stable")[:10]
+    lm[0, top] = -40.0  # the attention favourites are very unlikely under the LM
+    att[1, [7, 3, V - 1]] = att[1].max() + 1.0
+    lm[1, [7, 3, V - 1]] = lm[1].max() + 1.0
+    att[2] = np.round(att[2] * 2) / 2
+    lm[2] = np.round(lm[2] * 2) / 2
+    return att, lm
+
+
+def gather_rows(x, cand):
+    """cn_op_logsoftmax_gather: log_softmax(x) (fp32 rows) at cand (any number of columns, in calls of <= 256)."""
+    M, V = x.shape
+    xd = torch.from_numpy(np.ascontiguousarray(x)).cuda()
+    out = np.empty(cand.shape, np.float32)
+    for c0 in range(0, cand.shape[1], 256):
+        cd = torch.from_numpy(np.ascontiguousarray(cand[:, c0:c0 + 256], np.int32)).cuda()
+        od = torch.empty(cd.shape, dtype=torch.float32, device="cuda")
+        hip.check(hip.lib().cn_op_logsoftmax_gather(p(xd), M, V, p(cd), cd.shape[1], p(od), stream()))
+        torch.cuda.synchronize()
+        out[:, c0:c0 + 256] = od.cpu().numpy()
+    return out
+
+
+@pytest.mark.parametrize("V", [40, 1028, 5000, 8192])
+def test_logsoftmax_fuse_topk_bit_for_bit_and_against_float64(V):
+    """The fused row must be fl(att_logp + fl(w * lm_logp)) bit for bit, with the two log-probabilities as the gather kernel
+    computes them (same partition and order of the max / log-sum-exp; att / T divided as the kernel divides); the indices are its
+    stable descending order (ties: lower index), the set of the FUSED ranking - not the attention top-k."""
+    M = 12
+    att, lm = fusion_rows(M, V, seed=V)
+    att_d, lm_d = torch.from_numpy(att).cuda(), torch.from_numpy(lm).cuda()
+    every = np.tile(np.arange(V, dtype=np.int32), (M, 1))
+    l_lp = gather_rows(lm, every)
+    worst64 = 0.0
+    for T in (1.0, 1.3):
+        a_lp = gather_rows((att / np.float32(T)).astype(np.float32) if T != 1.0 else att, every)
+        assert np.abs(a_lp - logsoftmax64(att, T)).max() < 1e-5
+        for w in (1e-3, 0.6, 2.0):
+            fused = (a_lp + np.float32(w) * l_lp).astype(np.float32)  # float32, two roundings (numpy does not contract)
+            order = np.argsort(-fused, axis=1, kind="stable")
+            e64 = logsoftmax64(att, T) + w * logsoftmax64(lm)
+            for k in (1, 20, 30, 32):
+                idx = torch.empty(M, k, dtype=torch.int32, device="cuda")
+                val = torch.empty(M, k, dtype=torch.float32, device="cuda")
+                hip.check(hip.lib().cn_op_logsoftmax_fuse_topk(p(att_d), p(lm_d), M, V, T, w, k, p(idx), p(val), stream()))
+                torch.cuda.synchronize()
+                idx, val = idx.cpu().numpy(), val.cpu().numpy()
+                assert np.array_equal(idx, order[:, :k]), (V, k, T, w, np.argwhere(idx != order[:, :k])[:4].tolist())
+                want = np.take_along_axis(fused, order[:, :k], 1)
+                assert np.array_equal(val.view(np.int32), want.view(np.int32)), (V, k, T, w)
+                if k >= 20 and w >= 0.6:  # the fused candidates, not the attention top-k
+                    assert set(idx[0].tolist()) != set(np.argsort(-att[0], kind="stable")[:k].tolist())
+                assert idx[1, :3].tolist() == [3, 7, V - 1][:k]  # exact ties: lower index first
+                ref = np.take_along_axis(e64, idx.astype(np.int64), 1)
+                worst64 = max(worst64, float((np.abs(val - ref) / np.maximum(1.0, np.abs(ref))).max()))
+    print(f"fuse_topk V={V}: bit-exact against the composition; worst relative error vs float64 {worst64:.2e}")
+    assert worst64 < 1e-6
+
+
+@pytest.mark.parametrize("V,k", [(40, 1), (40, 32), (1028, 30), (5000, 32), (8192, 20), (16384, 256)])
+def test_logsoftmax_gather_against_float32_emulation(V, k):
+    M = 9
+    g = np.random.default_rng(V + k)
+    lm = (g.standard_normal((M, V)) * 3).astype(np.float32)
+    cand = g.integers(0, V, (M, k)).astype(np.int32)
+    cand[:, 0] = -1
+    cand[1, -1] = V
+    cand[2, :] = V - 1  # duplicates
+    if k > 2:
+        cand[3, 1] = V
+        cand[3, 2] = 0
+    out = torch.empty(M, k, dtype=torch.float32, device="cuda")
+    lm_d, cand_d = torch.from_numpy(lm).cuda(), torch.from_numpy(cand).cuda()
+    hip.check(hip.lib().cn_op_logsoftmax_gather(p(lm_d), M, V, p(cand_d), k, p(out), stream()))
+    torch.cuda.synchronize()
+    out = out.cpu().numpy()
+    bad = (cand < 0) | (cand >= V)
+    assert np.isneginf(out[bad]).all()
+    l32, llse = logsoftmax32(lm)
+    e = np.take_along_axis(l32, np.clip(cand, 0, V - 1).astype(np.int64), 1)
+    # the log-sum-exp: a float32 sum of V / 256 terms per thread, then 8 levels of reduction (its relative error is the lse's
+    # absolute error), device expf / logf; then one rounding of the difference
+    tol = np.broadcast_to((-(-V // 256) + 10) * 2.0 ** -23 + 2 * ulp32(llse) + ulp32(e), e.shape)
+    err = np.abs(out - e)
+    assert (err[~bad] <= tol[~bad]).all(), float((err[~bad] - tol[~bad]).max())
+    ref = np.take_along_axis(logsoftmax64(lm), np.clip(cand, 0, V - 1).astype(np.int64), 1)
+    err64 = float((np.abs(out - ref)[~bad] / np.maximum(1.0, np.abs(ref[~bad]))).max())
+    print(f"logsoftmax_gather V={V} k={k}: worst {float((err / ulp32(e))[~bad].max()):.1f} ulp vs emulation, {err64:.2e} vs float64")
+    assert err64 < 1e-6
+
+
+# ============================================================================================ gather attention (ast.hip)
+LAYOUTS = {  # name: (library flavour, CN_PRECISION_*, operand name the library must report)
+    "fp32": (None, 0, "bf16"),
+    "bf16": (None, 1, "bf16"),
+    "fp16": ("f16", 4, "fp16"),
+    "bf16x3": (None, 3, "bf16"),
+}
+
+
+def to_layout(x, layout):
+    """float32 tensor (rows of C columns) -> (device tensor in the layout's element bytes, float64 operand the kernel sees)."""
+    if layout == "fp32":
+        return x.cuda(), x.double()
+    if layout in ("bf16", "fp16"):
+        h = x.to(torch.bfloat16 if layout == "bf16" else torch.float16)
+        return h.cuda(), h.double()
+    hi = x.to(torch.bfloat16)
+    lo = (x - hi.float()).to(torch.bfloat16)
+    sh = x.shape[:-1] + (x.shape[-1] // 32, 1, 32)
+    packed = torch.cat([hi.reshape(sh), lo.reshape(sh)], dim=-2).reshape(x.shape[:-1] + (2 * x.shape[-1],))
+    return packed.cuda(), hi.double() + lo.double()
+
+
+def from_layout(t, layout):
+    if layout != "bf16x3":
+        return t.cpu().double()
+    c = t.shape[-1] // 2
+    g = t.cpu().reshape(t.shape[:-1] + (c // 32, 2, 32))
+    return (g[..., 0, :].double() + g[..., 1, :].double()).reshape(t.shape[:-1] + (c,))
+
+
+def attn_model(q, Kg, Vg, allowed, H, scale):
+    """float64 softmax(q . k^T * scale) . v per head; q (n, d), Kg / Vg (n, nkeys, d), allowed (n, nkeys) -> (out, fp32 bound)."""
+    n, nk, d = Kg.shape
+    qh = q.reshape(n, H, 64)
+    Kh, Vh = Kg.reshape(n, nk, H, 64), Vg.reshape(n, nk, H, 64)
+    s = torch.einsum("nhi,njhi->nhj", qh, Kh) * scale
+    a = torch.einsum("nhi,njhi->nhj", qh.abs(), Kh.abs()) * scale
+    ok = allowed[:, None, :]
+    s = torch.where(ok, s, torch.full_like(s, NEG_FILL))
+    pr = torch.softmax(s, dim=-1)
+    out = torch.einsum("nhj,njhi->nhi", pr, Vh)
+    # fp32 accumulation in the kernel's order: 64-term dot products (+ the scale), exp, a sequential nkeys-term sum per output
+    ds = torch.where(ok, gamma(65) * a + EPS * s.abs(), torch.zeros_like(s)).amax(-1, keepdim=True) + 4 * EPS
+    spread = torch.einsum("nhj,njhi->nhi", pr, (Vh - out[:, None]).abs())
+    mass = torch.einsum("nhj,njhi->nhi", pr, Vh.abs())
+    bound = 2 * (2 * ds * spread + gamma(nk + 2) * (mass + out.abs()) + 2 * EPS * out.abs())
+    return out.reshape(n, d), bound.reshape(n, d)
+
+
+def out_ulp(ref, layout):
+    """One ulp of the output element at |ref| (split-bf16: the bound of its hi + lo rounding, ~17 significant bits)."""
+    sp = torch.from_numpy(ulp32(ref.numpy()))  # float32 ulp: 2^(e - 23)
+    if layout == "fp32":
+        return torch.zeros_like(ref)
+    if layout == "bf16x3":
+        return ref.abs() * 2.0 ** -16 + 1e-38
+    if layout == "bf16":
+        return sp * 2.0 ** 16
+    return torch.clamp(sp * 2.0 ** 13, min=2.0 ** -24)
+
+
+ATTN_SHAPES = [(H, nk) for H in (1, 2, 4, 8, 16) for nk in (1, 63, 64, 65, 200, 16384 // H)]
+
+
+@pytest.mark.parametrize("layout", list(LAYOUTS))
+@pytest.mark.parametrize("mode", [0, 1])
+def test_gather_attention_against_float64(layout, mode):
+    flavour, prec, operand = LAYOUTS[layout]
+    L = hip.lib(flavour)
+    assert L.cn_operand16().decode() == operand
+    g = torch.Generator().manual_seed(17 + mode)
+    worst_ratio, worst_abs = 0.0, 0.0
+    for ci, (H, nkeys) in enumerate(ATTN_SHAPES):
+        d = 64 * H
+        n = int(max(2, min(640, (1 << 21) // (nkeys * d))))
+        pad = 32 if layout == "bf16x3" else 16  # row strides beyond the data (whole groups of 32 for split-bf16)
+        ldq = (3 * d if mode == 0 else d) + pad
+        ldo = d + pad
+        scale = 0.125
+        qf = torch.randn(n, ldq, generator=g) * 2
+        q_d, q64 = to_layout(qf, layout)
+        if mode == 0:
+            slots = n + 3
+            append_pos = (-1, 0, nkeys - 1)[ci % 3]
+            ts = nkeys + 5
+            kc = torch.randn(nkeys, slots, d, generator=g)
+            vc = torch.randn(nkeys, slots, d, generator=g)
+            k_d, k64 = to_layout(kc, layout)
+            v_d, v64 = to_layout(vc, layout)
+            k0, v0 = k_d.clone(), v_d.clone()
+            anc = torch.randint(0, slots - 1, (n, ts), generator=g, dtype=torch.int32)
+            anc = anc + (anc >= torch.arange(n, dtype=torch.int32)[:, None]).int()  # another slot than the row's own
+            keyok = (torch.rand(n, ts, generator=g) < 0.8).to(torch.uint8)
+            keyok[0] = 0  # a row with no allowed key: float-min scores everywhere, a uniform average
+            if n > 2:
+                keyok[2] = 1
+            anc_d, keyok_d = anc.cuda(), keyok.cuda()
+            o = torch.zeros(n, 2 * ldo if layout == "bf16x3" else ldo, dtype=q_d.dtype, device="cuda")
+            hip.check(L.cn_op_ast_gather_attn(prec, 0, p(q_d), ldq, p(k_d), p(v_d), p(o), ldo, n, H, nkeys, slots, d, ts, p(anc_d),
+                                              p(keyok_d), None, None, scale, append_pos, stream()), "cn_op_ast_gather_attn", L)
+            torch.cuda.synchronize()
+            jj = torch.arange(nkeys)
+            Kg = k64[jj[None, :], anc[:, :nkeys].long()]
+            Vg = v64[jj[None, :], anc[:, :nkeys].long()]
+            allowed = keyok[:, :nkeys] != 0
+            if append_pos >= 0:  # this step's K | V come from the projection row itself ...
+                Kg[:, append_pos] = q64[:, d:2 * d]
+                Vg[:, append_pos] = q64[:, 2 * d:3 * d]
+                # ... and are written to cache row (append_pos, slot r) byte for byte; nothing else in the cache changes
+                es = q_d.element_size() * (2 if layout == "bf16x3" else 1)
+                qb = q_d.view(torch.uint8).reshape(n, -1)
+                k0.view(torch.uint8).reshape(nkeys, slots, -1)[append_pos, :n] = qb[:, d * es:2 * d * es]
+                v0.view(torch.uint8).reshape(nkeys, slots, -1)[append_pos, :n] = qb[:, 2 * d * es:3 * d * es]
+            assert torch.equal(k_d.view(torch.uint8), k0.view(torch.uint8)), (H, nkeys, append_pos)
+            assert torch.equal(v_d.view(torch.uint8), v0.view(torch.uint8)), (H, nkeys, append_pos)
+        else:
+            B = 3
+            kv = torch.randn(B * nkeys, 2 * d, generator=g)
+            kv_d, kv64 = to_layout(kv, layout)
+            lens = [nkeys, max(1, nkeys - 7), 0]  # ragged, and one utterance with no valid frame
+            keymask = torch.zeros(B, nkeys, dtype=torch.uint8)
+            for b, ln in enumerate(lens):
+                keymask[b, :ln] = 1
+            utt = torch.randint(0, B, (n,), generator=g, dtype=torch.int32)
+            utt[:3] = torch.tensor([0, 2, 1], dtype=torch.int32)[: min(3, n)]
+            utt_d, km_d = utt.cuda(), keymask.cuda()
+            es = kv_d.element_size() * (2 if layout == "bf16x3" else 1)
+            v_ptr = C.c_void_p(kv_d.data_ptr() + d * es)
+            o = torch.zeros(n, 2 * ldo if layout == "bf16x3" else ldo, dtype=q_d.dtype, device="cuda")
+            hip.check(L.cn_op_ast_gather_attn(prec, 1, p(q_d), ldq, p(kv_d), v_ptr, p(o), ldo, n, H, nkeys, 0, d, 0, None, None,
+                                              p(utt_d), p(km_d), scale, -1, stream()), "cn_op_ast_gather_attn", L)
+            torch.cuda.synchronize()
+            rows = utt.long()[:, None] * nkeys + torch.arange(nkeys)[None, :]
+            Kg, Vg = kv64[rows, :d], kv64[rows, d:]
+            allowed = keymask[utt.long()] != 0
+        ref, bound = attn_model(q64[:, :d], Kg, Vg, allowed, H, scale)
+        got = from_layout(o, layout)[:, :d]
+        err = (got - ref).abs()
+        tol = bound + out_ulp(ref, layout)
+        assert (err <= tol).all(), (layout, mode, H, nkeys, float(err.max()), float((err - tol).max()))
+        assert torch.equal(from_layout(o, layout)[:, d:], torch.zeros(n, ldo - d, dtype=torch.float64))  # nothing past d
+        worst_ratio = max(worst_ratio, float((err / tol).max()))
+        worst_abs = max(worst_abs, float(err.max()))
+    print(f"gather_attn {layout} mode {mode}: worst |out - fp64| {worst_abs:.2e} ({worst_ratio:.2f} of the fp32 bound)")
+
+
+# ============================================================================================ CTC prefix scorer (ast.hip)
+def ctc_inputs(B, Tp, V, seed, blank=0):
+    g = np.random.default_rng(seed)
+    logp = torch.log_softmax(torch.from_numpy(g.standard_normal((B, Tp, V)).astype(np.float32) * 2), -1).numpy()
+    lens = [Tp, max(1, Tp - 3), max(1, Tp // 2)][:B]
+    km = np.zeros((B, Tp), np.uint8)
+    for b, ln in enumerate(lens):
+        km[b, :ln] = 1
+    masked = logp.copy()
+    masked[km == 0] = LOGZERO
+    masked[..., blank][km == 0] = 0.0
+    return logp, km, masked
+
+
+def ctc_prepare(logp, km, blank):
+    B, Tp, V = logp.shape
+    x = torch.from_numpy(logp).cuda()
+    r0 = torch.empty(B, Tp, 2, dtype=torch.float32, device="cuda")
+    km_d = torch.from_numpy(km).cuda()
+    hip.check(hip.lib().cn_op_ast_ctc_prepare(p(x), p(km_d), p(r0), B, Tp, V, blank, stream()))
+    torch.cuda.synchronize()
+    return x, r0
+
+
+def ctc_prefix(x, r0, r_prev, utt, last, cand, ref, Tp, V, blank, eos, out_len, r_new=None):
+    n, K = cand.shape
+    if r_new is None:
+        r_new = torch.full((n * K, Tp, 2), 7.0, dtype=torch.float32, device="cuda")
+    score = torch.empty(n, K, dtype=torch.float32, device="cuda")
+    dv = [torch.from_numpy(np.ascontiguousarray(a, np.int32)).cuda() for a in (utt, last, cand, ref)]
+    hip.check(hip.lib().cn_op_ast_ctc_prefix(p(x), p(r0), p(r_prev), p(r_new), *[p(t) for t in dv], p(score), n, K, Tp, V, blank,
+                                             eos, out_len, stream()))
+    torch.cuda.synchronize()
+    return score.cpu().numpy(), r_new.cpu().numpy().reshape(n, K, Tp, 2)
+
+
+def oracle_prefix(x64, r_prev64, utt, last, cand, blank, eos, out_len, sos=1):
+    n = len(utt)
+    y = torch.full((n, out_len + 1), sos, dtype=torch.long)
+    y[:, -1] = torch.from_numpy(np.asarray(last, np.int64))
+    psi, r = ast_oracle.ctc_prefix_score(y, torch.from_numpy(np.asarray(cand, np.int64)), x64[torch.from_numpy(np.asarray(utt)).long()],
+                                         r_prev64, blank, eos, dtype=torch.float64)
+    return psi.numpy(), r.numpy()
+
+
+def ctc_compare(got, ref, Tp, steps, what):
+    """logzero-class (< -1e9) on one side iff on the other; finite values within a relative bound of fp32 log-domain recurrences
+    over Tp frames.  Returns the worst finite error as a fraction of that bound."""
+    cg, cr = got < -1e9, ref < -1e9
+    assert np.array_equal(cg, cr), (what, int((cg != cr).sum()))
+    f = ~cr
+    tol = 8 * EPS * (Tp + 2) * steps * (np.abs(ref[f]) + 8)
+    err = np.abs(got[f].astype(np.float64) - ref[f])
+    assert (err <= tol).all(), (what, float((err / tol).max()))
+    return float((err / tol).max()) if err.size else 0.0, float(err.max()) if err.size else 0.0
+
+
+def make_candidates(g, last, K, V, blank, eos):
+    n = len(last)
+    cand = g.integers(0, V, (n, K)).astype(np.int32)
+    cand[:, 0] = last            # the `same` branch
+    cand[:, 1] = eos
+    cand[:, 2] = blank
+    cand[:, 3] = cand[:, 4]      # a duplicate
+    for h in range(n):
+        g.shuffle(cand[h])
+    return cand
+
+
+@pytest.mark.parametrize("V", [40, 5000])
+@pytest.mark.parametrize("Tp", [1, 2, 7, 8, 9, 61, 250])
+def test_ctc_prefix_single_step_against_float64(Tp, V):
+    blank, eos, B, n, K = 0, 2, 3, 6, 10
+    logp, km, masked = ctc_inputs(B, Tp, V, seed=Tp * 7 + V)
+    x, r0 = ctc_prepare(logp, km, blank)
+    assert np.array_equal(x.cpu().numpy().view(np.int32), masked.view(np.int32))  # ast_ctc_mask_kernel
+    r0h = r0.cpu().numpy()
+    assert (r0h[..., 0] == LOGZERO).all()
+    assert np.array_equal(r0h[..., 1], np.add.accumulate(masked[..., blank], axis=1, dtype=np.float32))  # sequential fp32 cumsum
+    g = np.random.default_rng(Tp + V)
+    R = 8  # rows of a previous step's states: decreasing log-probabilities, a logzero head on the non-blank side
+    r_prev = -np.cumsum(np.abs(g.standard_normal((R, Tp, 2))) * 2, axis=1).astype(np.float32)
+    r_prev[:, : max(1, Tp // 3), 0] = LOGZERO
+    r_prev_d = torch.from_numpy(r_prev).cuda()
+    x64 = torch.from_numpy(masked).double()
+    worst = (0.0, 0.0)
+    for out_len in sorted({0, 1, 2, Tp // 2, Tp - 1, Tp} & set(range(Tp + 1))):
+        utt = g.integers(0, B, n).astype(np.int32)
+        last = g.integers(3, V, n).astype(np.int32)
+        last[0] = blank
+        last[1] = 1 if out_len == 0 else last[1]
+        cand = make_candidates(g, last, K, V, blank, eos)
+        ref = np.where(np.arange(n) % 2 == 0, -1 - utt, g.integers(0, R, n)).astype(np.int32)
+        score, r_new = ctc_prefix(x, r0, r_prev_d, utt, last, cand, ref, Tp, V, blank, eos, out_len)
+        prev64 = torch.from_numpy(np.stack([r0h[-1 - rf] if rf < 0 else r_prev[rf] for rf in ref])).double()
+        psi, r = oracle_prefix(x64, prev64, utt, last, cand, blank, eos, out_len)
+        w1 = ctc_compare(score, psi, Tp, 1, ("score", out_len))
+        w2 = ctc_compare(r_new, r, Tp, 1, ("r_new", out_len))
+        worst = max(worst, w1, w2)
+        if out_len == Tp:  # a prefix as long as the frames: nothing left to emit
+            assert (score[cand != eos] == LOGZERO).all() and (r_new == LOGZERO).all()
+    print(f"ctc_prefix Tp={Tp} V={V}: worst finite error {worst[1]:.2e} ({worst[0]:.3f} of the fp32 bound)")
+
+
+@pytest.mark.parametrize("Tp,V", [(9, 40), (61, 5000), (250, 40)])
+def test_ctc_prefix_chained_five_steps_against_float64_chain(Tp, V):
+    """Five steps, each extending candidates of the last one through prev_ref, the state buffers alternating (both parities);
+    the oracle is chained in float64 from its own float64 initial state."""
+    blank, eos, B, n, K = 0, 2, 3, 6, 8
+    logp, km, masked = ctc_inputs(B, Tp, V, seed=Tp + 3 * V)
+    x, r0 = ctc_prepare(logp, km, blank)
+    x64 = torch.from_numpy(masked).double()
+    init64 = ast_oracle.ctc_initial_state(x64, blank, dtype=torch.float64)
+    g = np.random.default_rng(Tp * V)
+    utt = np.array([0, 0, 1, 1, 2, 2], np.int32)
+    last = np.ones(n, np.int32)
+    ref = (-1 - utt).astype(np.int32)
+    prev64 = init64[torch.from_numpy(utt).long()]
+    bufs = [torch.zeros(n * K, Tp, 2, dtype=torch.float32, device="cuda") for _ in range(2)]  # the two parities
+    worst = (0.0, 0.0)
+    for step in range(5):
+        cand = make_candidates(g, last, K, V, blank, eos)
+        # step s reads the states of step s - 1 from buffer (s & 1) ^ 1 and writes buffer s & 1 (cn_ast_ctc_score's parity)
+        score, r_new = ctc_prefix(x, r0, bufs[(step & 1) ^ 1], utt, last, cand, ref, Tp, V, blank, eos, step, r_new=bufs[step & 1])
+        psi, r = oracle_prefix(x64, prev64, utt, last, cand, blank, eos, step)
+        worst = max(worst, ctc_compare(score, psi, Tp, step + 1, ("score", step)), ctc_compare(r_new, r, Tp, step + 1, ("r_new", step)))
+        # next hypotheses: children of this step's candidates (same utterance), through their state rows
+        par = np.array([g.choice(np.flatnonzero(utt == utt[h])) for h in range(n)])
+        c = g.integers(0, K, n)
+        last = cand[par, c].astype(np.int32)
+        ref = (par * K + c).astype(np.int32)
+        utt = utt[par]
+        prev64 = torch.from_numpy(r[par, c])
+    print(f"ctc_prefix chain Tp={Tp} V={V}: worst finite error {worst[1]:.2e} ({worst[0]:.3f} of the fp32 bound)")
+
+
+# ============================================================================================ beam bookkeeping (ast.hip)
+FIELDS = [("tok", torch.int32, True), ("anc", torch.int32, True), ("keyok", torch.uint8, True), ("len", torch.int32, False),
+          ("score", torch.float64, False), ("valid", torch.int32, False), ("ctc_ref", torch.int32, False), ("ctc_prev", torch.float32, False)]
+SENTINEL = {"tok": -7, "anc": -9, "keyok": 7, "len": -3, "score": 12345.5, "valid": 9, "ctc_ref": -77777, "ctc_prev": 3.25}
+
+
+class DevBeam:
+    """Both parities of every state array of cn_decode_ast's device beam (filled with sentinels), cur_tok, utt and live."""
+
+    def __init__(self, B, bw, L):
+        S = B * bw
+        self.B, self.bw, self.L = B, bw, L
+        self.t = {}
+        for name, dt, per_tok in FIELDS:
+            shape = (S, L) if per_tok else (S,)
+            self.t[name] = [torch.full(shape, SENTINEL[name], dtype=dt, device="cuda") for _ in range(2)]
+        self.cur_tok = torch.full((S,), -5, dtype=torch.int32, device="cuda")
+        self.utt = torch.full((S,), -6, dtype=torch.int32, device="cuda")
+        self.live = torch.full((16,), -4, dtype=torch.int32, device="cuda")
+
+    def ptrs(self):
+        out = []
+        for name, _, _ in FIELDS:
+            out += [p(self.t[name][0]), p(self.t[name][1])]
+        return out + [p(self.cur_tok), p(self.utt), p(self.live)]
+
+    def host(self):
+        h = {name: [self.t[name][i].cpu().numpy() for i in range(2)] for name, _, _ in FIELDS}
+        h["cur_tok"], h["utt"], h["live"] = self.cur_tok.cpu().numpy(), self.utt.cpu().numpy(), self.live.cpu().numpy()
+        return h
+
+    def load(self, h):
+        for name, _, _ in FIELDS:
+            for i in range(2):
+                self.t[name][i].copy_(torch.from_numpy(h[name][i]))
+        self.cur_tok.copy_(torch.from_numpy(h["cur_tok"]))
+        self.utt.copy_(torch.from_numpy(h["utt"]))
+
+
+def copy_state(h):
+    return {k: ([a.copy() for a in v] if isinstance(v, list) else v.copy()) for k, v in h.items()}
+
+
+def model_init(h, cur, B, bw, L, sos, pad):
+    h = copy_state(h)
+    for s in range(B * bw):
+        b, j = divmod(s, bw)
+        h["tok"][cur][s] = [sos] + [pad] * (L - 1)
+        h["anc"][cur][s] = s
+        h["keyok"][cur][s] = [1 if (t == 0 and sos != pad) else 0 for t in range(L)]
+        h["len"][cur][s], h["score"][cur][s], h["valid"][cur][s] = 1, 0.0, int(j == 0)
+        h["ctc_ref"][cur][s], h["ctc_prev"][cur][s] = -1 - b, 0.0
+        h["cur_tok"][s], h["utt"][s] = sos, b
+    h["live"][0] = B
+    return h
+
+
+def model_update(h, q, B):
+    """Transformer.beam_decode's bookkeeping (src/models/transformer.py:157-240) restated on the slot arrays: finished hypotheses
+    first, then every live hypothesis's stable top-bw of its K candidates; local scores in float32 with one rounding per operation,
+    scores and sort keys as Python floats; a stable sort by key, descending; the best bw become the next beam."""
+    bw, K, L, cur = q["bw"], q["K"], q["L"], q["cur"]
+    nxt = cur ^ 1
+    o = copy_state(h)
+    f32 = np.float32
+    live_total = 0
+    for b in range(B):
+        cands = []  # (key, score, parent j, candidate c or -1, token, ctc)
+        for j in range(bw):
+            s = b * bw + j
+            if not h["valid"][cur][s]:
+                continue
+            if h["tok"][cur][s, h["len"][cur][s] - 1] == q["eos"]:
+                sc = float(h["score"][cur][s])
+                cands.append((sc + float(h["len"][cur][s] - 1) * q["lp"] if q["use_lp"] else sc, sc, j, -1, 0, f32(0)))
+        for j in range(bw):
+            s = b * bw + j
+            if not h["valid"][cur][s] or h["tok"][cur][s, h["len"][cur][s] - 1] == q["eos"]:
+                continue
+            loc = []
+            for c in range(K):
+                if q["use_ctc"]:
+                    v = f32(f32(q["w"] * f32(q["ctc"][s, c] - h["ctc_prev"][cur][s])) + f32(q["u"] * q["att"][s, c]))
+                    if q["use_lm"]:
+                        v = f32(v + f32(q["lw"] * q["lm"][s, c]))
+                else:
+                    v = q["att"][s, c]
+                loc.append(v)
+            for c in sorted(range(K), key=lambda c: -float(loc[c]))[:bw]:
+                sc = float(h["score"][cur][s]) + float(loc[c])
+                key = sc + float(h["len"][cur][s]) * q["lp"] if q["use_lp"] else sc
+                cands.append((key, sc, j, c, int(q["idx"][s, c]), q["ctc"][s, c] if q["use_ctc"] else f32(0)))
+        best = sorted(range(len(cands)), key=lambda e: -cands[e][0])[:bw]
+        for qn in range(bw):
+            sn = b * bw + qn
+            if qn >= len(best):  # fewer candidates than slots: tok / keyok of the slot are left as they were
+                o["anc"][nxt][sn] = sn
+                o["valid"][nxt][sn], o["len"][nxt][sn], o["score"][nxt][sn] = 0, 1, 0.0
+                o["ctc_ref"][nxt][sn], o["ctc_prev"][nxt][sn], o["cur_tok"][sn] = -1 - b, 0.0, q["sos"]
+                continue
+            _, sc, j, c, tk, cv = cands[best[qn]]
+            so = b * bw + j
+            lo = h["len"][cur][so]
+            tok, anc, ko = h["tok"][cur][so].copy(), h["anc"][cur][so].copy(), h["keyok"][cur][so].copy()
+            grown = c >= 0
+            if grown:
+                if lo < L:
+                    tok[lo], ko[lo] = tk, int(tk != q["pad"])
+                if 0 <= q["pos"] < L:
+                    anc[q["pos"]] = so
+                if 0 <= q["pos"] + 1 < L:
+                    anc[q["pos"] + 1] = sn
+            o["tok"][nxt][sn], o["anc"][nxt][sn], o["keyok"][nxt][sn] = tok, anc, ko
+            o["valid"][nxt][sn], o["len"][nxt][sn], o["score"][nxt][sn] = 1, lo + int(grown), sc
+            o["ctc_ref"][nxt][sn] = so * K + c if grown else h["ctc_ref"][cur][so]
+            o["ctc_prev"][nxt][sn] = cv if grown else h["ctc_prev"][cur][so]
+            o["cur_tok"][sn] = tk if grown else q["eos"]
+            live_total += int(grown and tk != q["eos"])
+    o["live"][0] = live_total
+    return o
+
+
+def assert_state_equal(got, want, what):
+    for name, _, _ in FIELDS:
+        for i in range(2):
+            a, b = got[name][i], want[name][i]
+            if a.dtype.kind == "f":  # bit for bit
+                a, b = a.view(np.int64 if a.itemsize == 8 else np.int32), b.view(np.int64 if b.itemsize == 8 else np.int32)
+            assert np.array_equal(a, b), (what, name, i, np.argwhere(a != b)[:5].tolist())
+    for name in ("cur_tok", "utt"):
+        assert np.array_equal(got[name], want[name]), (what, name)
+    assert got["live"][0] == want["live"][0], (what, "live", got["live"][0], want["live"][0])
+
+
+def step_inputs(g, S, K, V, step, use_ctc, use_lm):
+    """Candidates of one step: tokens over a small vocabulary (eos and pad come up often); even steps quantised values with
+    weights 0.5 / 0.5 / 0.25 (exact arithmetic: ties in local scores and in sort keys), odd steps continuous values with the
+    recipe's float32 weights; a logzero CTC score here and there."""
+    idx = g.integers(0, V, (S, K)).astype(np.int32)
+    if step % 2 == 0:
+        att = -np.round(g.exponential(1.5, (S, K)) * 4).astype(np.float32) / 4
+        ctc = -np.round(g.exponential(3.0, (S, K)) * 4).astype(np.float32) / 4
+        lm = -np.round(g.exponential(2.0, (S, K)) * 4).astype(np.float32) / 4
+        w, u, lw = np.float32(0.5), np.float32(0.5), np.float32(0.25)
+    else:
+        att = -g.exponential(1.5, (S, K)).astype(np.float32)
+        ctc = -g.exponential(3.0, (S, K)).astype(np.float32)
+        lm = -g.exponential(2.0, (S, K)).astype(np.float32)
+        w, u, lw = np.float32(0.3), np.float32(1 - 0.3), np.float32(0.6)
+    att = -np.sort(-att, axis=1)  # the attention top-K arrives sorted, best first
+    ctc[g.random((S, K)) < 0.05] = LOGZERO
+    return dict(idx=idx, att=att, ctc=ctc if use_ctc else None, lm=lm if use_lm else None, w=w, u=u, lw=lw)
+
+
+def run_update(db, q, B):
+    d = {k: (torch.from_numpy(np.ascontiguousarray(q[k])).cuda() if q[k] is not None else None) for k in ("idx", "att", "ctc", "lm")}
+    hip.check(hip.lib().cn_op_ast_beam_update(*db.ptrs(), p(d["idx"]), p(d["att"]), p(d["ctc"]), p(d["lm"]), q["cur"], q["pos"], q["bw"],
+                                              q["K"], q["L"], q["eos"], q["sos"], q["pad"], q["use_ctc"], q["use_lp"], q["use_lm"],
+                                              float(q["w"]), float(q["u"]), float(q["lw"]), float(q["lp"]), B, stream()))
+    torch.cuda.synchronize()
+
+
+BEAM_PAIRS = sorted({(bw, K) for bw in (1, 2, 3, 10, 16, 17, 20, 31, 32) for K in (bw, 30, 32) if K >= bw})
+EOS, SOS, PAD = 2, 1, 0
+
+
+@pytest.mark.parametrize("bw,K", BEAM_PAIRS)
+def test_beam_update_four_steps_bit_for_bit(bw, K):
+    L, V = 7, 9
+    for use_ctc in (0, 1):
+        for use_lm in (0, 1):
+            for use_lp in (0, 1):
+                for B in (1, 3):
+                    g = np.random.default_rng([bw, K, use_ctc, use_lm, use_lp, B])
+                    lp = -0.25 if B == 3 else 0.5
+                    db = DevBeam(B, bw, L)
+                    h = db.host()
+                    hip.check(hip.lib().cn_op_ast_beam_init(*db.ptrs(), 0, B, bw, L, SOS, PAD, stream()))
+                    torch.cuda.synchronize()
+                    want = model_init(h, 0, B, bw, L, SOS, PAD)
+                    h = db.host()
+                    assert_state_equal(h, want, "init")
+                    cur = 0
+                    for step in range(4):
+                        q = step_inputs(g, B * bw, K, V, step, use_ctc, use_lm)
+                        q.update(cur=cur, pos=step, bw=bw, K=K, L=L, eos=EOS, sos=SOS, pad=PAD, use_ctc=use_ctc, use_lp=use_lp,
+                                 use_lm=use_lm, lp=lp)
+                        run_update(db, q, B)
+                        want = model_update(h, q, B)
+                        h = db.host()
+                        assert_state_equal(h, want, (bw, K, B, use_ctc, use_lm, use_lp, step))
+                        cur ^= 1
+
+
+def crafted_state(g, B, bw, L, V, kinds):
+    """A state in parity 0 whose slots are given per utterance as 'f' (finished: last token eos), 'l' (live) or '-' (unused);
+    quantised scores (ties in the sort keys), lengths 1..L-2, the other parity holding sentinels."""
+    h = {name: [np.full((B * bw, L) if per_tok else (B * bw,), SENTINEL[name], dtype=torch.empty(0, dtype=dt).numpy().dtype)
+                for _ in range(2)] for name, dt, per_tok in FIELDS}
+    h["cur_tok"] = np.full(B * bw, -5, np.int32)
+    h["utt"] = np.repeat(np.arange(B, dtype=np.int32), bw)
+    h["live"] = np.full(16, -4, np.int32)
+    for b in range(B):
+        for j, kind in enumerate(kinds[b]):
+            s = b * bw + j
+            ln = int(g.integers(1, L - 1))
+            tok = g.integers(3, V, L).astype(np.int32)
+            tok[0] = SOS
+            tok[ln:] = PAD
+            if kind == "f":
+                tok[ln - 1] = EOS if ln > 1 else tok[ln - 1]
+                if ln == 1:
+                    ln, tok[1] = 2, EOS
+            h["tok"][0][s], h["len"][0][s] = tok, ln
+            h["anc"][0][s] = g.integers(0, B * bw, L)
+            h["keyok"][0][s] = (tok != PAD).astype(np.uint8)
+            h["valid"][0][s] = int(kind != "-")
+            h["score"][0][s] = -float(g.integers(0, 12)) / 4
+            h["ctc_ref"][0][s] = int(g.integers(-B, B * bw * 4))
+            h["ctc_prev"][0][s] = -np.float32(g.integers(0, 40)) / 4
+    return h
+
+
+@pytest.mark.parametrize("use_lp,lp", [(0, 0.0), (1, -0.5), (1, 0.75)])
+def test_beam_update_crafted_states(use_lp, lp):
+    """Finished hypotheses carried beside live ones under a length penalty; unused slots; and utterances with fewer candidates
+    than slots (only finished hypotheses), where the kernel's newslot < 0 branch fills the rest with harmless dummies."""
+    L, V = 9, 9
+    cases = [(2, 4, 5, ["ff--", "f-f-"]),                        # fewer candidates than slots in both utterances
+             (3, 5, 5, ["flf-l", "-----", "fffff"]),             # an utterance with nothing valid; one with only finished
+             (1, 32, 32, ["".join("fl-"[i % 3] for i in range(32))]),
+             (2, 21, 30, ["l" * 10 + "f" * 11, "f" * 20 + "l"])]
+    for B, bw, K, kinds in cases:
+        for use_ctc, use_lm in ((1, 1), (1, 0), (0, 0)):
+            g = np.random.default_rng([B, bw, K, use_ctc, use_lm, int(lp * 4) + 8])
+            db = DevBeam(B, bw, L)
+            h = crafted_state(g, B, bw, L, V, kinds)
+            db.load(h)
+            torch.cuda.synchronize()
+            for step, cur in ((3, 0), (4, 1)):
+                q = step_inputs(g, B * bw, K, V, step - 3, use_ctc, use_lm)
+                q.update(cur=cur, pos=step, bw=bw, K=K, L=L, eos=EOS, sos=SOS, pad=PAD, use_ctc=use_ctc, use_lp=use_lp, use_lm=use_lm, lp=lp)
+                run_update(db, q, B)
+                want = model_update(h, q, B)
+                h = db.host()
+                assert_state_equal(h, want, (B, bw, K, kinds, use_ctc, use_lm, step))
+
+
+# ============================================================================================ entry-point refusals with a model
+def test_decode_refuses_max_step_beyond_the_ctc_frames_and_k_beyond_the_vocabulary():
+    """cn_decode_ast with CTC and max_step > T' + 1 would score prefixes longer than the frames (the CTC kernel's states run past
+    their block); K > V would make the top-k select retired entries.  Both are refused before anything is launched, and
+    beam_decode raises instead of decoding."""
+    from conftest import ast_tiny_case
+
+    from cassnat_asr_public_amd.models.transformer import make_model
+
+    args, state, feats = ast_tiny_case(vocab_size=20)
+    args.hip_precision = "fp32"
+    model = make_model(args.input_size, args).cuda()
+    with torch.no_grad():
+        for k, prm in model.named_parameters():
+            prm.copy_(torch.from_numpy(state[k]))
+
+    class Vocab:
+        word2index = {"blank": 0, "sos": 1, "eos": 2, "unk": 3}
+
+    src = torch.from_numpy(feats).cuda()
+    T = feats.shape[1]
+    Tp = ((T - 1) // 2 + 1 - 1) // 2 + 1
+    args.max_decode_ratio = (Tp + 2.5) / Tp  # max_step = Tp + 2: one step past the last prefix the scorer is defined for
+    with pytest.raises(hip.HipError, match="max_step"):
+        model.beam_decode(src, None, Vocab, args)
+    args.max_decode_ratio = (Tp + 1.5) / Tp  # max_step = Tp + 1: the last step scores prefixes of exactly Tp tokens
+    out = model.beam_decode(src, None, Vocab, args)
+    assert len(out) == feats.shape[0]
+    eng = model.engine(feats.shape[0], T)
+    opts = hip.CnDecodeOpts(padding_idx=0, sos=1, beam_width=1)
+    V = args.vocab_size
+    assert V < 32
+    ao = hip.CnAstOpts(ctc_weight=0.0, temperature=1.0, ctc_beam=V + 1, beam_width=V + 1, max_step=3, eos=2, one_minus_ctc_weight=1.0)
+    hyp = torch.empty(feats.shape[0], 32, 8, dtype=torch.int32, device="cuda")
+    hl = torch.empty(feats.shape[0], 32, dtype=torch.int32, device="cuda")
+    sc = torch.empty(feats.shape[0], 32, dtype=torch.float64, device="cuda")
+    with pytest.raises(hip.HipError, match="vocabulary"):
+        eng.ast_decode(src, opts, ao, hyp, hl, sc)
+    # the step entries: K beyond the vocabulary, and the CTC scorer: out_len beyond the frames
+    eng.ast_begin(src, opts, 1, 8, 6, 5)
+    tok = torch.ones(2, dtype=torch.int32, device="cuda")
+    utt = torch.zeros(2, dtype=torch.int32, device="cuda")
+    anc = torch.zeros(2, 8, dtype=torch.int32, device="cuda")
+    keyok = torch.ones(2, 8, dtype=torch.uint8, device="cuda")
+    idx = torch.zeros(2, 32, dtype=torch.int32, device="cuda")
+    val = torch.zeros(2, 32, dtype=torch.float32, device="cuda")
+    with pytest.raises(hip.HipError, match="vocabulary"):
+        eng.ast_step(0, tok, utt, anc, keyok, 1.0, V + 1, idx, val)
+    ref = torch.full((2,), -1, dtype=torch.int32, device="cuda")
+    cand = torch.zeros(2, 5, dtype=torch.int32, device="cuda")
+    with pytest.raises(hip.HipError, match="out_len"):
+        eng.ast_ctc_score(Tp + 1, utt, tok, cand, ref, 0, 2, val)
+    torch.cuda.synchronize()
