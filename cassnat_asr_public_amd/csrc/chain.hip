@@ -1249,6 +1249,7 @@ unsigned char cn_f32_to_e4m3_host(float f) {
     const int bits = ((E + 7) << 3) | r;
     return sign | (unsigned char)(bits > 0x7e ? 0x7e : bits);
 }
+int cn_e4m3_exp(float mx) { return mx > 0.f ? (int)std::floor(std::log2(448.f / mx)) : 0; }
 
 // F8 units (e4m3 bytes at `scale`).  An A operand of the K = 64 MFMA is 32 bytes per lane = pieces 2 t, 2 t + 1 of the unit
 // (piece = [lane][16 B]); byte e = 16 (piece & 1) + j.  Row of the accumulator layout behind byte position (half, r = e & 15):
@@ -1279,7 +1280,7 @@ static void ch_pack_w2_f8(const float* w2, int dff, int p, float scale, unsigned
 static float ch_f8_scale(const float* w, size_t n) {
     float mx = 0.f;
     for (size_t i = 0; i < n; ++i) mx = std::max(mx, std::fabs(w[i]));
-    return mx > 0.f ? std::ldexp(1.f, (int)std::floor(std::log2(448.f / mx))) : 1.f;
+    return std::ldexp(1.f, cn_e4m3_exp(mx));
 }
 
 void pack_chain(const ChainWeights& w, uint16_t* stream, float* tab, int* f8_q) {

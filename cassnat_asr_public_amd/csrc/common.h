@@ -282,6 +282,9 @@ __device__ __forceinline__ float wave_max(float v) {
 // ----------------------------------------------------------------------------------------------
 #include <string>
 void cn_set_error(const std::string& msg);
+// The internal precision of a public CN_PRECISION_* request, or -1 (error set, prefixed with `who`) when it belongs to the
+// other build of the library (model.hip)
+int cn_own_precision(int32_t precision, const char* who);
 #define CN_HIP_CHECK(expr)                                                                        \
     do {                                                                                          \
         hipError_t _e = (expr);                                                                   \

@@ -20,7 +20,10 @@
 //     consecutive channels of one row; the tile goes through LDS once and leaves as 8-KiB contiguous row runs.
 //   * All LDS reads of the main loop are issued from inline asm (hipcc drains vmcnt before LDS accesses it can see
 //     while an LDS-DMA is in flight).
+#include <algorithm>
+#include <cmath>
 #include <cstdlib>
+#include <cstring>
 
 #include "kernels.h"
 
@@ -816,4 +819,41 @@ int launch_linear256_dma(const void* A, int lda, const void* W, const float* bia
     hipLaunchKernelGGL(conv2_kernel<true>, dim3(p.ntiles), dim3(256), C2_LDS, s, p);
     CN_HIP_CHECK(hipGetLastError());
     return 0;
+}
+
+// ---- host: conv2's weight matrices in the e4m3 forms (the model's weight blob and the test entries of ops.hip)
+// f(position in the [co][tap][ci] order, source element) over the C x 9 x C weights
+template <typename F>
+static void c2_each_weight(const float* w, int C, long long s_co, long long s_tap, long long s_ci, F f) {
+    size_t e = 0;
+    for (int co = 0; co < C; ++co)
+        for (int tap = 0; tap < 9; ++tap)
+            for (int ci = 0; ci < C; ++ci) f(e++, w[co * s_co + tap * s_tap + ci * s_ci]);
+}
+static int c2_e4m3_exp(const float* w, int C, long long s_co, long long s_tap, long long s_ci) {
+    float mx = 0.f;
+    c2_each_weight(w, C, s_co, s_tap, s_ci, [&](size_t, float v) { mx = std::max(mx, std::fabs(v)); });
+    return cn_e4m3_exp(mx);
+}
+
+int pack_conv2_f8(const float* w, int C, long long s_co, long long s_tap, long long s_ci, unsigned char* out) {
+    const int lg = c2_e4m3_exp(w, C, s_co, s_tap, s_ci);
+    const float scale = std::ldexp(1.f, lg);
+    c2_each_weight(w, C, s_co, s_tap, s_ci, [&](size_t e, float v) { out[e] = cn_f32_to_e4m3_host(v * scale); });
+    return lg;
+}
+
+void pack_conv2_mix(const float* w, int C, long long s_co, long long s_tap, long long s_ci, unsigned char* out, int* q8) {
+    const size_t n = (size_t)C * 9 * C;
+    // q: the largest power-of-two scale that keeps the weights inside e4m3; l: |w - half(w)| <= 2^-11 |w|
+    const int lg = c2_e4m3_exp(w, C, s_co, s_tap, s_ci);
+    const float sq = std::ldexp(1.f, lg), sl = std::ldexp(1.f, lg + 11);
+    c2_each_weight(w, C, s_co, s_tap, s_ci, [&](size_t e, float v) {
+        const _Float16 h = (_Float16)v;
+        std::memcpy(&out[2 * e], &h, 2);
+        out[2 * n + e] = cn_f32_to_e4m3_host(v * sq);
+        out[3 * n + e] = cn_f32_to_e4m3_host((v - (float)h) * sl);
+    });
+    const int q[4] = {127 - lg, 127 - MIX_LG_AL, 127 - (lg + 11), 127 - MIX_LG_AQ};
+    std::memcpy(q8, q, 16);
 }

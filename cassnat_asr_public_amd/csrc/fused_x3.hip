@@ -715,7 +715,7 @@ static void pack_ffn_mix(const float* w1, const float* w2, int dff, unsigned cha
     auto hval = [](float v) { return (float)(_Float16)v; };
     float m1 = 0.f, m2 = 0.f;
     for (size_t i = 0; i < (size_t)dff * FX_D; ++i) { m1 = std::max(m1, std::fabs(w1[i])); m2 = std::max(m2, std::fabs(w2[i])); }
-    const int lg1 = m1 > 0.f ? (int)std::floor(std::log2(448.f / m1)) : 0, lg2 = m2 > 0.f ? (int)std::floor(std::log2(448.f / m2)) : 0;
+    const int lg1 = cn_e4m3_exp(m1), lg2 = cn_e4m3_exp(m2);
     const float s1q = std::ldexp(1.f, lg1), s1l = std::ldexp(1.f, lg1 + 11), s2q = std::ldexp(1.f, lg2), s2l = std::ldexp(1.f, lg2 + 11);
     for (int ft = 0; ft < dff / 32; ++ft) {
         unsigned char* tile = out + (size_t)ft * 64 * 1024;

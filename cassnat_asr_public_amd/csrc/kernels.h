@@ -312,6 +312,16 @@ int launch_linear256_f8(const void* A8, const void* W8, const int* q8_dev, const
 bool conv2_mix_applies(int prec, int C, int N);
 int launch_conv2_mix(const void* img, const void* w_hi, const void* w8q, const void* w8l, const int* q8_dev, const float* bias, void* out,
                      int B, int T1, int F1, int T2, int F2, hipStream_t s);
+// conv2's MIX form: fixed power-of-two scales of the image's e4m3 planes - q = e4m3(v 2^MIX_LG_AQ) holds conv1 outputs up to 448
+// (beyond it the cross term a_q w_l saturates: the product falls back towards half precision, not apart) and
+// l = e4m3((v - half(v)) 2^MIX_LG_AL), |v - half(v)| <= 2^-11 |v|
+constexpr int MIX_LG_AQ = 0, MIX_LG_AL = 11;
+// conv2's weights from fp32 w[co * s_co + tap * s_tap + ci * s_ci] (C x 9 x C elements; tap = kh * 3 + kw), written in the
+// [co][tap][ci] order of the kernels' weight matrices.  F8 form: e4m3(w 2^lg) bytes, lg = cn_e4m3_exp(max |w|); returns lg.
+int pack_conv2_f8(const float* w, int C, long long s_co, long long s_tap, long long s_ci, unsigned char* out);
+// MIX form: three planes in that order - half(w) (2 bytes each), e4m3(w 2^lg), e4m3((w - half(w)) 2^(lg + 11)) - and q8 = the
+// four E8M0 bytes {W_q, A_l, W_l, A_q} launch_conv2_mix reads
+void pack_conv2_mix(const float* w, int C, long long s_co, long long s_tap, long long s_ci, unsigned char* out, int* q8);
 bool conv2_x3_applies(int prec, int C, int N);
 int launch_conv2_x3(const void* in_hi, const void* in_lo, const void* w_hi, const void* w_lo, const float* bias, void* out, int B,
                     int T1, int F1, int T2, int F2, hipStream_t s);
@@ -362,6 +372,8 @@ size_t chain_stream_units(int has_outproj, int dff, int tail_n, int f8 = 0);
 void pack_chain(const ChainWeights& w, uint16_t* stream, float* tab, int* f8_q = nullptr);
 // float -> OCP e4m3fn byte, round to nearest even, saturating at +-448 (host side; the device's v_cvt_pk_fp8_f32 after a clamp)
 unsigned char cn_f32_to_e4m3_host(float f);
+// the exponent of a tensor's e4m3 scale: the largest lg with max |w| 2^lg <= 448, 0 for an all-zero tensor (mx = max |w|)
+int cn_e4m3_exp(float mx);
 
 // ---- d_model-deep projections of the split-bf16 engine (K = 256): C = A . W^T + bias, split-bf16 or fp32 (+ residual) output   (proj_x3.hip)
 struct ProjX3Args {

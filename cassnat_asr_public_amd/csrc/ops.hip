@@ -1,0 +1,1068 @@
+// C-ABI entry points of libcassnat_hip.so that take no model handle: the Kaldi fbank front end, the host gather of the packed
+// reader and the single-kernel entries (cn_op_*) through which the tests drive every hand-written kernel.  See
+// include/cassnat_hip.h for the contract; the handle, weight packing and decode paths are model.hip.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "../../include/cassnat_hip.h"
+#include "kernels.h"
+
+namespace {
+
+// Device scratch of one entry: alloc / upload, launch, then finish(rc).  The destructor drains the stream and frees every
+// buffer, so each exit path - a failed hip call after the first allocation included - gives them back.
+class Scratch {
+  public:
+    Scratch(const char* who, hipStream_t s) : who_(who), s_(s) {}
+    Scratch(const Scratch&) = delete;
+    Scratch& operator=(const Scratch&) = delete;
+    ~Scratch() {
+        (void)hipStreamSynchronize(s_);
+        for (void* p : bufs_) (void)hipFree(p);
+    }
+    // false (error set) once an allocation or upload of this guard failed; the later ones are not attempted
+    bool ok() const { return ok_; }
+    void* alloc(size_t bytes) {
+        if (!ok_) return nullptr;
+        void* p = nullptr;
+        const hipError_t e = hipMalloc(&p, bytes);
+        if (e != hipSuccess) return fail("hipMalloc", bytes, e);
+        bufs_.push_back(p);
+        return p;
+    }
+    void* upload(const void* host, size_t bytes) {
+        void* p = alloc(bytes);
+        if (!p) return nullptr;
+        const hipError_t e = hipMemcpy(p, host, bytes, hipMemcpyHostToDevice);
+        return e == hipSuccess ? p : fail("hipMemcpy", bytes, e);
+    }
+    // rc of the launches, or -2 (error set) when they were accepted and the stream then failed
+    int finish(int rc) {
+        const hipError_t e = hipStreamSynchronize(s_);
+        if (rc == 0 && e != hipSuccess) {
+            cn_set_error(std::string(who_) + ": " + hipGetErrorString(e));
+            return -2;
+        }
+        return rc;
+    }
+
+  private:
+    void* fail(const char* what, size_t bytes, hipError_t e) {
+        cn_set_error(std::string(who_) + ": " + what + " of " + std::to_string(bytes) + " bytes failed: " + hipGetErrorString(e));
+        ok_ = false;
+        return nullptr;
+    }
+    const char* who_;
+    hipStream_t s_;
+    std::vector<void*> bufs_;
+    bool ok_ = true;
+};
+
+// fp32 [M][256] -> split-bf16 rows (hi + lo halves, 1 KiB per row) as the split-bf16 kernels read them
+std::vector<unsigned char> split_rows256(const float* x, int M) {
+    std::vector<unsigned char> hx((size_t)M * 1024);
+    for (size_t r = 0; r < (size_t)M; ++r)
+        for (size_t c = 0; c < 256; ++c) {
+            const float v = x[r * 256 + c];
+            const uint16_t hi = cn_host_op16(v);
+            const uint32_t hbits = (uint32_t)hi << 16;
+            float hf;
+            std::memcpy(&hf, &hbits, 4);
+            const uint16_t lo = cn_host_op16(v - hf);
+            std::memcpy(&hx[r * 1024 + cn_split_off(c)], &hi, 2);
+            std::memcpy(&hx[r * 1024 + cn_split_off(c) + 64], &lo, 2);
+        }
+    return hx;
+}
+
+}  // namespace
+
+// ---- single-kernel entry points ------------------------------------------------------------------
+static FbankOpts fbank_opts_from(const cn_fbank_opts* o) {
+    FbankOpts f;
+    f.sample_rate = o->sample_rate;
+    f.frame_length_ms = o->frame_length_ms;
+    f.frame_shift_ms = o->frame_shift_ms;
+    f.preemph = o->preemph;
+    f.low_freq = o->low_freq;
+    f.high_freq = o->high_freq;
+    f.num_mel = o->num_mel;
+    f.window_type = o->window_type;
+    f.remove_dc = o->remove_dc;
+    f.use_power = o->use_power;
+    f.use_log = o->use_log;
+    return f;
+}
+
+extern "C" void cn_fbank_default_opts(cn_fbank_opts* o) {
+    if (!o) return;
+    const FbankOpts f;
+    std::memset(o, 0, sizeof(*o));
+    o->sample_rate = f.sample_rate;
+    o->frame_length_ms = f.frame_length_ms;
+    o->frame_shift_ms = f.frame_shift_ms;
+    o->preemph = f.preemph;
+    o->low_freq = f.low_freq;
+    o->high_freq = f.high_freq;
+    o->num_mel = f.num_mel;
+    o->window_type = f.window_type;
+    o->remove_dc = f.remove_dc;
+    o->use_power = f.use_power;
+    o->use_log = f.use_log;
+}
+
+extern "C" int32_t cn_fbank_num_frames(const cn_fbank_opts* o, int32_t num_samples) {
+    return o ? fbank_num_frames(fbank_opts_from(o), num_samples) : 0;
+}
+
+extern "C" int cn_fbank(const cn_fbank_opts* o, const float* wave_dev, const int32_t* num_samples_dev, int32_t B,
+                        int32_t max_samples, const float* cmvn_mean_dev, const float* cmvn_istd_dev, float* feats_dev,
+                        int32_t Tmax, float pad_value, void* stream) {
+    if (!o || !wave_dev || !num_samples_dev || !feats_dev || B < 0 || max_samples < 0 || Tmax < 0) {
+        cn_set_error("cn_fbank: bad argument");
+        return -1;
+    }
+    return launch_fbank(fbank_opts_from(o), wave_dev, num_samples_dev, B, max_samples, cmvn_mean_dev, cmvn_istd_dev, feats_dev,
+                        Tmax, pad_value, (hipStream_t)stream);
+}
+
+extern "C" int cn_op_gemm(int32_t precision, const void* A, int32_t lda, const void* W, const float* bias, void* C,
+                          int32_t ldc, int32_t c_is_f32, int32_t M, int32_t N, int32_t K, int32_t relu,
+                          const float* resid, int32_t ldr, const float* pe, int32_t pe_period, float scale,
+                          void* stream) {
+    if ((precision = cn_own_precision(precision, "cn_op_gemm")) < 0) return -1;
+    GemmArgs g;
+    g.A = A;
+    g.lda = lda;
+    g.W = W;
+    g.bias = bias;
+    g.C = C;
+    g.ldc = ldc;
+    g.c_f32 = c_is_f32;
+    g.M = M;
+    g.N = N;
+    g.K = K;
+    g.epi = (relu ? CN_EPI_RELU : 0) | (resid ? CN_EPI_RESID : 0) | (pe ? CN_EPI_EMBED : 0);
+    g.resid = resid;
+    g.ldr = ldr;
+    g.pe = pe;
+    g.pe_period = pe_period;
+    g.scale = scale;
+    return launch_gemm(precision, g, (hipStream_t)stream);
+}
+
+extern "C" int cn_op_convert(int32_t precision, const void* src, void* dst, int64_t n, int32_t to_f32, void* stream) {
+    if ((precision = cn_own_precision(precision, "cn_op_convert")) < 0) return -1;
+    if (n < 0 || !src || !dst) {
+        cn_set_error("cn_op_convert: bad argument");
+        return -1;
+    }
+    return to_f32 ? launch_convert_back(precision, src, (float*)dst, (size_t)n, (hipStream_t)stream)
+                  : launch_convert(precision, (const float*)src, dst, (size_t)n, (hipStream_t)stream);
+}
+
+extern "C" int cn_op_conv1(int32_t precision, const float* x, const float* w9c, const float* bias, void* out, int32_t B,
+                           int32_t T, int32_t F, int32_t C, void* stream) {
+    if ((precision = cn_own_precision(precision, "cn_op_conv1")) < 0) return -1;
+    return launch_conv1(precision, x, w9c, bias, out, B, T, F, (T - 1) / 2 + 1, (F - 1) / 2 + 1, C, 0, (hipStream_t)stream);
+}
+
+// the bf16 engine's bordered image ([B][T1 + 2][F1 + 2][C] bf16, zero border) as conv2's LDS-DMA kernel reads it, from the
+// matrix-core kernel (C == 256, (F - 1) / 2 + 3 >= 32)
+extern "C" int cn_op_conv1_bordered(const float* x, const float* w9c, const float* bias, void* out, int32_t B, int32_t T, int32_t F,
+                                    int32_t C, void* stream) {
+    return launch_conv1_bordered_bf16(x, w9c, bias, out, B, T, F, (T - 1) / 2 + 1, (F - 1) / 2 + 1, C, (hipStream_t)stream);
+}
+
+// conv front-end of the fp8 engine through the ABI (config 5): conv1 -> e4m3fn image at `img_scale` (bordered) -> conv2 on e4m3
+// operands; w2_host fp32 [C][3][3][C] (k = (kh * 3 + kw) * C + ci) is quantised here at the largest power-of-two scale that keeps it
+// in range.  img8_out_dev (optional): the bordered image [B][T1 + 2][F1 + 2][C] bytes.  out: bf16 [B * T2 * F2][C], or with
+// out8_scale > 0 e4m3fn bytes at that scale (what linear_out's e4m3 form reads)
+extern "C" int cn_op_conv_frontend_fp8(const float* x_dev, const float* w1_9c_dev, const float* b1_dev, const float* w2_host,
+                                       const float* b2_dev, void* out_dev, void* img8_out_dev, int32_t B, int32_t T, int32_t F,
+                                       int32_t C, float img_scale, float out8_scale, float* w_scale_out, void* stream) {
+    if (!conv2_f8_applies(C, C)) {
+        cn_set_error("cn_op_conv_frontend_fp8: 256 channels only");
+        return -1;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const int T1 = (T - 1) / 2 + 1, F1 = (F - 1) / 2 + 1, T2 = (T1 - 1) / 2 + 1, F2 = (F1 - 1) / 2 + 1;
+    std::vector<unsigned char> w8((size_t)C * 9 * C);
+    const int lg = pack_conv2_f8(w2_host, C, 9 * C, C, 1, w8.data());
+    if (w_scale_out) *w_scale_out = std::ldexp(1.f, lg);
+    const int q[4] = {127 - lg, 127 - (int)std::lround(std::log2(img_scale)), 0, 0};
+    const size_t img_bytes = (size_t)B * (T1 + 2) * (F1 + 2) * C;
+    Scratch sc("cn_op_conv_frontend_fp8", s);
+    void* dw = sc.upload(w8.data(), w8.size());
+    void* dq = sc.upload(q, 16);
+    void* img = sc.alloc(img_bytes);
+    if (!sc.ok()) return -2;
+    CN_HIP_CHECK(hipMemsetAsync(img, 0xff, img_bytes, s));  // (NaN bytes: the kernel must write every cell, border included)
+    int rc = launch_conv1_f8(x_dev, w1_9c_dev, b1_dev, img, B, T, F, T1, F1, C, 1, img_scale, s);
+    if (rc == 0) rc = launch_conv2_f8(img, dw, (const int*)dq, b2_dev, out_dev, B, T1, F1, T2, F2, s, out8_scale);
+    if (rc == 0 && img8_out_dev) CN_HIP_CHECK(hipMemcpyAsync(img8_out_dev, img, img_bytes, hipMemcpyDeviceToDevice, s));
+    return sc.finish(rc);
+}
+
+// The split-bf16 engine's conv front-end in the MIX arithmetic through the ABI (conv1.hip MIXP planes + conv2.hip MIX): x fp32 [B][T][F],
+// w2_host fp32 [C][3][3][C] (k = (kh * 3 + kw) * C + ci); out_dev: split-bf16 rows [B * T2 * F2][C] (cn_op_convert turns them into fp32);
+// img_out_dev (optional): conv1's three bordered planes, 4 bytes per cell of [B][T1 + 2][F1 + 2][C] (half values, l bytes, q bytes)
+extern "C" int cn_op_conv_frontend_mix(const float* x_dev, const float* w1_9c_dev, const float* b1_dev, const float* w2_host,
+                                       const float* b2_dev, void* out_dev, void* img_out_dev, int32_t B, int32_t T, int32_t F, int32_t C,
+                                       void* stream) {
+    if (!conv2_mix_applies(CN_PREC_X3, C, C)) {
+        cn_set_error("cn_op_conv_frontend_mix: 256 channels only (and not in the half-precision build of the library)");
+        return -1;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const int T1 = (T - 1) / 2 + 1, F1 = (F - 1) / 2 + 1, T2 = (T1 - 1) / 2 + 1, F2 = (F1 - 1) / 2 + 1;
+    const size_t n = (size_t)C * 9 * C;
+    std::vector<unsigned char> w(4 * n);
+    int q[4];
+    pack_conv2_mix(w2_host, C, 9 * C, C, 1, w.data(), q);
+    const size_t img_bytes = (size_t)B * (T1 + 2) * (F1 + 2) * C * 4;
+    Scratch sc("cn_op_conv_frontend_mix", s);
+    void* dw = sc.upload(w.data(), w.size());
+    void* dq = sc.upload(q, 16);
+    void* img = sc.alloc(img_bytes);
+    if (!sc.ok()) return -2;
+    CN_HIP_CHECK(hipMemsetAsync(img, 0xff, img_bytes, s));  // (NaN bytes: conv1 must write every cell of every plane, border included)
+    int rc = launch_conv1_mixplanes(x_dev, w1_9c_dev, b1_dev, img, B, T, F, T1, F1, C, 1, std::ldexp(1.f, MIX_LG_AL), std::ldexp(1.f, MIX_LG_AQ), s);
+    if (rc == 0)
+        rc = launch_conv2_mix(img, dw, (const unsigned char*)dw + 2 * n, (const unsigned char*)dw + 3 * n, (const int*)dq, b2_dev, out_dev, B, T1, F1,
+                              T2, F2, s);
+    if (rc == 0 && img_out_dev) CN_HIP_CHECK(hipMemcpyAsync(img_out_dev, img, img_bytes, hipMemcpyDeviceToDevice, s));
+    return sc.finish(rc);
+}
+
+// linear_out of the fp8 engine through the ABI: a8_dev [M][K] e4m3fn at a_scale (K = 5120), w_host fp32 [256][K] quantised here at
+// the largest power-of-two scale in range; out fp32 [M][256] = (a . w^T / (a_scale w_scale) + bias) * out_scale + pe[m % pe_period]
+extern "C" int cn_op_linear256_fp8(const void* a8_dev, const float* w_host, const float* bias_dev, float* out_dev, int32_t M, int32_t K,
+                                   float a_scale, float out_scale, const float* pe_dev, int32_t pe_period, float* w_scale_out,
+                                   void* stream) {
+    if (!linear256_f8_applies(256, K)) {
+        cn_set_error("cn_op_linear256_fp8: K must be 5120");
+        return -1;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    float mx = 0.f;
+    for (size_t i = 0; i < (size_t)256 * K; ++i) mx = std::max(mx, std::fabs(w_host[i]));
+    const int lg = cn_e4m3_exp(mx);
+    const float ws = std::ldexp(1.f, lg);
+    if (w_scale_out) *w_scale_out = ws;
+    std::vector<unsigned char> w8((size_t)256 * K);
+    for (size_t i = 0; i < w8.size(); ++i) w8[i] = cn_f32_to_e4m3_host(w_host[i] * ws);
+    const int q[4] = {127 - lg, 127 - (int)std::lround(std::log2(a_scale)), 0, 0};
+    Scratch sc("cn_op_linear256_fp8", s);
+    void* dw = sc.upload(w8.data(), w8.size());
+    void* dq = sc.upload(q, 16);
+    if (!sc.ok()) return -2;
+    return sc.finish(launch_linear256_f8(a8_dev, dw, (const int*)dq, bias_dev, out_dev, M, K, out_scale, pe_dev, pe_period, s));
+}
+
+extern "C" int cn_op_conv2(int32_t precision, const void* conv1_out, const void* w_khwc, const float* bias, void* out,
+                           int32_t B, int32_t T1, int32_t F1, int32_t C, void* stream) {
+    if ((precision = cn_own_precision(precision, "cn_op_conv2")) < 0) return -1;
+    GemmArgs g;
+    const int T2 = (T1 - 1) / 2 + 1, F2 = (F1 - 1) / 2 + 1;
+    g.A = conv1_out;
+    g.W = w_khwc;
+    g.bias = bias;
+    g.C = out;
+    g.ldc = C;
+    g.M = B * T2 * F2;
+    g.N = C;
+    g.K = 9 * C;
+    g.epi = CN_EPI_RELU;
+    g.conv = 1;
+    g.cB = B;
+    g.cT1 = T1;
+    g.cF1 = F1;
+    g.cC = C;
+    g.cT2 = T2;
+    g.cF2 = F2;
+    if (!conv2_dma_applies(precision, C, C)) return launch_gemm(precision, g, (hipStream_t)stream);
+    // bf16, 256 channels: the LDS-DMA kernel reads an image with a one-cell zero halo (the model has conv1 write it that
+    // way); this test entry pads a copy of the plain image
+    const size_t cell = (size_t)C * 2, prow = (size_t)(F1 + 2) * cell;
+    Scratch sc("cn_op_conv2", (hipStream_t)stream);
+    void* padded = sc.alloc((size_t)B * (T1 + 2) * prow);
+    if (!sc.ok()) return -2;
+    CN_HIP_CHECK(hipMemsetAsync(padded, 0, (size_t)B * (T1 + 2) * prow, (hipStream_t)stream));
+    for (int b = 0; b < B; ++b)
+        CN_HIP_CHECK(hipMemcpy2DAsync((unsigned char*)padded + ((size_t)b * (T1 + 2) + 1) * prow + cell, prow,
+                                      (const unsigned char*)conv1_out + (size_t)b * T1 * F1 * cell, (size_t)F1 * cell,
+                                      (size_t)F1 * cell, T1, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    g.A = padded;
+    g.conv_halo = 1;
+    return sc.finish(launch_gemm(precision, g, (hipStream_t)stream));
+}
+
+extern "C" int cn_op_layernorm(int32_t precision, const float* x, const float* a2, const float* b2, void* y, int32_t M,
+                               int32_t d, float eps, void* stream) {
+    if ((precision = cn_own_precision(precision, "cn_op_layernorm")) < 0) return -1;
+    return launch_layernorm(precision, x, a2, b2, y, 0, M, d, eps, (hipStream_t)stream);
+}
+
+extern "C" int cn_op_attention(int32_t precision, const void* Q, int32_t ldq, const void* K, int32_t ldk, const void* V,
+                               int32_t ldv, void* O, int32_t ldo, int32_t B, int32_t H, int32_t Lq, int32_t Lk,
+                               const uint8_t* keymask, const int32_t* klen, const int32_t* intervals, int32_t iv_stride,
+                               int32_t causal, float scale, void* stream) {
+    if ((precision = cn_own_precision(precision, "cn_op_attention")) < 0) return -1;
+    AttnArgs a;
+    a.Q = Q;
+    a.K = K;
+    a.V = V;
+    a.O = O;
+    a.ldq = ldq;
+    a.ldk = ldk;
+    a.ldv = ldv;
+    a.ldo = ldo;
+    a.B = B;
+    a.H = H;
+    a.Lq = Lq;
+    a.Lk = Lk;
+    a.keymask = keymask;
+    a.klen = klen;
+    a.intervals = intervals;
+    a.iv_stride = iv_stride;
+    a.causal = causal;
+    a.scale = scale;
+    int rc = launch_attention(precision, a, (hipStream_t)stream);
+    if (rc == 0 && cn_exp_env("CASSNAT_ATTN_STAMPS")) {
+        (void)hipStreamSynchronize((hipStream_t)stream);
+        (void)attention_print_stamps();
+    }
+    return rc;
+}
+
+extern "C" int cn_op_logsoftmax_argmax(float* logits, int32_t M, int32_t V, int32_t* arg, float* maxlp,
+                                       int32_t write_logp, void* stream) {
+    return launch_logsoftmax_argmax(logits, M, V, V, arg, maxlp, write_logp, (hipStream_t)stream);
+}
+
+extern "C" int cn_op_ctc_align(const int32_t* best, const uint8_t* keymask, const float* size_ratio, int32_t B,
+                               int32_t Tp, int32_t blank, int32_t left, int32_t right, int32_t* shift,
+                               int32_t* src_size, int32_t* ylen, int32_t* ymax, int32_t* intervals, void* stream) {
+    AlignArgs a;
+    a.best = best;
+    a.keymask = keymask;
+    a.size_ratio = size_ratio;
+    a.B = B;
+    a.Tp = Tp;
+    a.blank = blank;
+    a.left = left;
+    a.right = right;
+    a.shift = shift;
+    a.src_size = src_size;
+    a.ylen = ylen;
+    a.ymax = ymax;
+    a.intervals = intervals;
+    return launch_ctc_align(a, (hipStream_t)stream);
+}
+
+// the two kernels of decode_type ctc_only / ctc_att on given log-posteriors (test entries; all pointers device)
+extern "C" int cn_op_ctc_prefix_beam(const float* logp, const float* size_ratio, int32_t B, int32_t Tp, int32_t V, int32_t beam,
+                                     int32_t pruning, double length_penalty, int32_t blank, int32_t* hyp, int32_t hyp_cap,
+                                     int32_t* hyp_len, double* score, double* p_blk, double* p_nblk, int32_t* nbeam, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    const size_t M = (size_t)B * Tp;
+    const int P = pruning > 0 ? pruning : 1;
+    Scratch sc("cn_op_ctc_prefix_beam", s);
+    int* top_idx = (int*)sc.alloc(M * P * 4);
+    float* top_val = (float*)sc.alloc(M * P * 4);
+    unsigned char* hpar = (unsigned char*)sc.alloc(M * (size_t)std::max(beam, 1));
+    int* htok = (int*)sc.alloc(M * (size_t)std::max(beam, 1) * 4);
+    if (!sc.ok()) return -2;
+    int rc = pruning > 0 ? launch_topk(logp, (int)M, V, V, pruning, top_idx, top_val, s) : 0;
+    if (rc == 0) {
+        CtcBeamArgs a;
+        a.logp = logp;
+        a.top_idx = top_idx;
+        a.size_ratio = size_ratio;
+        a.B = B;
+        a.Tp = Tp;
+        a.V = V;
+        a.P = pruning;
+        a.W = beam;
+        a.blank = blank;
+        a.Lmax = hyp_cap;
+        a.lp = length_penalty;
+        a.hist_parent = hpar;
+        a.hist_tok = htok;
+        a.hyp = hyp;
+        a.hyp_len = hyp_len;
+        a.score = score;
+        a.p_blk = p_blk;
+        a.p_nblk = p_nblk;
+        a.n_out = nbeam;
+        rc = launch_ctc_prefix_beam(a, s);
+    }
+    return sc.finish(rc);
+}
+
+extern "C" int cn_op_ctc_viterbi(const float* logp, const uint8_t* keymask, const float* size_ratio, const int32_t* labels,
+                                 const int32_t* label_len, int32_t B, int32_t Tp, int32_t V, int32_t ld, int32_t ymax, int32_t blank,
+                                 int32_t* out_path, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    Scratch sc("cn_op_ctc_viterbi", s);
+    unsigned char* bp = (unsigned char*)sc.alloc((size_t)B * Tp * (2 * (size_t)ymax + 1));
+    if (!sc.ok()) return -2;
+    ViterbiArgs v;
+    v.logp = logp;
+    v.keymask = keymask;
+    v.size_ratio = size_ratio;
+    v.labels = labels;
+    v.label_len = label_len;
+    v.B = B;
+    v.Tp = Tp;
+    v.V = V;
+    v.ld = ld;
+    v.ymax = ymax;
+    v.blank = blank;
+    v.bp = bp;
+    v.out_path = out_path;
+    return sc.finish(launch_ctc_viterbi(v, s));
+}
+
+extern "C" int cn_op_greedy_pack(const int32_t* tok, const float* val, const int32_t* ylen, int32_t B, int32_t U,
+                                 int32_t sos, int32_t hyp_stride, int32_t* hyp, int32_t* hyp_len, double* score,
+                                 void* stream) {
+    return launch_greedy_pack(tok, val, ylen, B, U, sos, hyp_stride, hyp, hyp_len, score, (hipStream_t)stream);
+}
+
+extern "C" int cn_op_topk(const float* logp, int32_t M, int32_t V, int32_t k, int32_t* idx, float* val, void* stream) {
+    return launch_topk(logp, M, V, V, k, idx, val, (hipStream_t)stream);
+}
+
+// fp8 product through the ABI (config 5): A bf16 on the device is quantised at a_scale, W (HOST fp32 [N][K]) at the largest
+// power-of-two scale that fits e4m3fn (as cn_model_finalize does); C = relu?(A_q . W_q^T / scales + bias), fp32 [M][N]
+extern "C" int cn_op_gemm_fp8(const void* a_bf16_dev, int32_t lda, const float* w_host, const float* bias_dev, float* c_dev,
+                              int32_t M, int32_t N, int32_t K, float a_scale, int32_t relu, float* w_scale_out, void* stream) {
+    if (M < 1 || N < 1 || K < 128 || K % 128 != 0) {
+        cn_set_error("cn_op_gemm_fp8: K must be a positive multiple of 128");
+        return -1;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    float mx = 0.f;
+    for (size_t i = 0; i < (size_t)N * K; ++i) mx = std::max(mx, std::fabs(w_host[i]));
+    const float ws = std::ldexp(1.f, cn_e4m3_exp(mx));
+    if (w_scale_out) *w_scale_out = ws;
+    std::vector<unsigned char> w8((size_t)N * K);
+    for (size_t i = 0; i < w8.size(); ++i) w8[i] = cn_f32_to_e4m3_host(w_host[i] * ws);
+    Scratch sc("cn_op_gemm_fp8", s);
+    void* dw = sc.upload(w8.data(), w8.size());
+    void* da = sc.alloc((size_t)M * K);
+    if (!sc.ok()) return -2;
+    int rc = launch_quantize_fp8(a_bf16_dev, lda, da, M, K, a_scale, s);
+    if (rc == 0) {
+        GemmArgs g;
+        g.A = da;
+        g.lda = K;
+        g.W = dw;
+        g.bias = bias_dev;
+        g.C = c_dev;
+        g.ldc = N;
+        g.c_f32 = 1;
+        g.M = M;
+        g.N = N;
+        g.K = K;
+        g.epi = relu ? CN_EPI_RELU : 0;
+        g.ab_fp8 = 1;
+        g.acc_scale = 1.f / (a_scale * ws);
+        rc = launch_gemm(CN_PREC_BF16, g, s);
+    }
+    return sc.finish(rc);
+}
+
+extern "C" int cn_op_cmvn(float* feats_dev, const int32_t* len_dev, const double* mean_dev, const double* std_dev, int32_t B, int32_t T,
+                          int32_t F, void* stream) {
+    if (!feats_dev || !len_dev || !mean_dev || !std_dev) {
+        cn_set_error("cn_op_cmvn: null argument");
+        return -1;
+    }
+    return launch_cmvn(feats_dev, len_dev, mean_dev, std_dev, B, T, F, (hipStream_t)stream);
+}
+
+// Host side of the packed reader: n byte ranges (an utterance's rows inside the memory map of an archive) copied back to back into a
+// page-locked staging buffer in ONE call - ctypes releases the GIL for its duration, so the decode pipelines' host threads copy side
+// by side (numpy's slice assignment holds it: two threads took turns, 5 ms a turn).  threads > 1: the ranges are dealt over that
+// many std::threads in equal byte shares (--load_data_workers on this path).
+extern "C" int cn_host_gather(void* dst, const uint64_t* src_ptrs, const uint64_t* dst_offsets, const uint64_t* nbytes, int32_t n,
+                              int32_t threads) {
+    if (!dst || !src_ptrs || !dst_offsets || !nbytes || n < 0) {
+        cn_set_error("cn_host_gather: null argument");
+        return -1;
+    }
+    auto run = [&](int lo, int hi) {
+        for (int i = lo; i < hi; ++i)
+            memcpy(static_cast<unsigned char*>(dst) + dst_offsets[i], reinterpret_cast<const void*>(src_ptrs[i]), nbytes[i]);
+    };
+    const int nt = std::max(1, std::min<int>(threads, n));
+    if (nt == 1) {
+        run(0, n);
+        return 0;
+    }
+    uint64_t total = 0;
+    for (int i = 0; i < n; ++i) total += nbytes[i];
+    std::vector<std::thread> pool;
+    int lo = 0;
+    uint64_t acc = 0;
+    for (int t = 0; t < nt; ++t) {
+        int hi = lo;
+        const uint64_t want = total * (uint64_t)(t + 1) / (uint64_t)nt;
+        while (hi < n && (t + 1 == nt || acc + nbytes[hi] <= want || hi == lo)) acc += nbytes[hi++];
+        if (t + 1 < nt) pool.emplace_back(run, lo, hi);
+        else run(lo, hi);
+        lo = hi;
+    }
+    for (auto& th : pool) th.join();
+    return 0;
+}
+
+extern "C" int cn_op_unpack_rows(const float* packed_dev, const int32_t* off_dev, const int32_t* len_dev, float* out_dev, int32_t rows,
+                                 int32_t T, int32_t F, float pad, const double* mean_dev, const double* std_dev, void* stream) {
+    if (!packed_dev || !off_dev || !len_dev || !out_dev || (!mean_dev) != (!std_dev)) {
+        cn_set_error("cn_op_unpack_rows: null argument (mean and std come together)");
+        return -1;
+    }
+    return launch_unpack_rows(packed_dev, off_dev, len_dev, out_dev, rows, T, F, pad, mean_dev, std_dev, (hipStream_t)stream);
+}
+
+extern "C" int cn_op_quantize_fp8(const void* src_bf16_dev, int32_t ld, void* dst_dev, int32_t M, int32_t K, float scale,
+                                  void* stream) {
+    return launch_quantize_fp8(src_bf16_dev, ld, dst_dev, M, K, scale, (hipStream_t)stream);
+}
+
+extern "C" int cn_op_logsoftmax_topk(const float* logits, int32_t M, int32_t V, float temperature, int32_t k, int32_t* idx,
+                                     float* val, void* stream) {
+    return launch_logsoftmax_topk(logits, M, V, V, temperature, k, idx, val, (hipStream_t)stream);
+}
+
+extern "C" int cn_op_logsoftmax_fuse_topk(const float* att, const float* lm, int32_t M, int32_t V, float temperature, float w,
+                                          int32_t k, int32_t* idx, float* val, void* stream) {
+    if (M < 0 || V < 1 || (M > 0 && (!att || !lm || !idx || !val))) {
+        cn_set_error("cn_op_logsoftmax_fuse_topk: bad argument");
+        return -1;
+    }
+    return launch_logsoftmax_fuse_topk(att, lm, M, V, V, temperature, w, k, idx, val, (hipStream_t)stream);
+}
+
+extern "C" int cn_op_logsoftmax_gather(const float* logits, int32_t M, int32_t V, const int32_t* cand, int32_t k, float* out,
+                                       void* stream) {
+    if (M < 0 || V < 1 || (M > 0 && (!logits || !cand || !out))) {
+        cn_set_error("cn_op_logsoftmax_gather: bad argument");
+        return -1;
+    }
+    return launch_logsoftmax_gather(logits, M, V, V, cand, k, out, (hipStream_t)stream);
+}
+
+// ---- kernel-test entries of the AST beam search's step kernels (ast.hip)
+extern "C" int cn_op_ast_gather_attn(int32_t precision, int32_t mode, const void* q, int32_t ldq, void* k, void* v, void* o,
+                                     int32_t ldo, int32_t n, int32_t H, int32_t nkeys, int32_t slots, int32_t d, int32_t table_stride,
+                                     const int32_t* anc, const uint8_t* keyok, const int32_t* utt, const uint8_t* keymask, float scale,
+                                     int32_t append_pos, void* stream) {
+    if ((precision = cn_own_precision(precision, "cn_op_ast_gather_attn")) < 0) return -1;
+    if (precision != CN_PREC_F32 && precision != CN_PREC_BF16 && precision != CN_PREC_X3) {
+        cn_set_error("cn_op_ast_gather_attn: precision must be F32, BF16 (F16 in the half-precision build) or BF16X3");
+        return -1;
+    }
+    if (mode != 0 && mode != 1) {
+        cn_set_error("cn_op_ast_gather_attn: mode must be 0 (cache) or 1 (source memory)");
+        return -1;
+    }
+    if (n < 0 || H < 1 || H > 16 || d != 64 * H || nkeys < 1 || ldo < d || ldq < (mode == 0 ? 3 * d : d) || !q || !k || !v ||
+        (n > 0 && !o)) {
+        cn_set_error("cn_op_ast_gather_attn: need 1 <= H <= 16, d = 64 * H, nkeys >= 1, ldo >= d and ldq >= 3d (mode 0) / d (mode 1)");
+        return -1;
+    }
+    if (mode == 0 && (slots < n || table_stride < nkeys || append_pos < -1 || append_pos >= nkeys || !anc || !keyok)) {
+        cn_set_error("cn_op_ast_gather_attn: mode 0 needs slots >= n, table_stride >= nkeys, -1 <= append_pos < nkeys, anc and keyok");
+        return -1;
+    }
+    if (mode == 1 && (!utt || !keymask)) {
+        cn_set_error("cn_op_ast_gather_attn: mode 1 needs utt and keymask");
+        return -1;
+    }
+    GatherAttnArgs a;
+    a.q = q;
+    a.ldq = ldq;
+    a.k = k;
+    a.v = v;
+    a.o = o;
+    a.ldo = ldo;
+    a.n = n;
+    a.H = H;
+    a.nkeys = nkeys;
+    a.slots = slots;
+    a.d = d;
+    a.table_stride = table_stride;
+    a.anc = anc;
+    a.keyok = keyok;
+    a.utt = utt;
+    a.keymask = keymask;
+    a.scale = scale;
+    a.append_pos = mode == 0 ? append_pos : -1;
+    return launch_ast_gather_attn(precision, mode, a, (hipStream_t)stream);
+}
+
+extern "C" int cn_op_ast_ctc_prepare(float* logp, const uint8_t* keymask, float* r0, int32_t B, int32_t Tp, int32_t V, int32_t blank,
+                                     void* stream) {
+    if (B < 1 || Tp < 1 || V < 1 || blank < 0 || blank >= V || !logp || !keymask || !r0) {
+        cn_set_error("cn_op_ast_ctc_prepare: need B, Tp, V >= 1, 0 <= blank < V and non-null buffers");
+        return -1;
+    }
+    return launch_ast_ctc_prepare(logp, keymask, r0, B, Tp, V, blank, (hipStream_t)stream);
+}
+
+extern "C" int cn_op_ast_ctc_prefix(const float* logp, const float* r0, const float* r_prev, float* r_new, const int32_t* utt,
+                                    const int32_t* last_tok, const int32_t* cand, const int32_t* prev_ref, float* score, int32_t n,
+                                    int32_t K, int32_t Tp, int32_t V, int32_t blank, int32_t eos, int32_t out_len, void* stream) {
+    if (n < 0 || K < 1 || Tp < 1 || V < 1 || blank < 0 || blank >= V || out_len < 0 || out_len > Tp ||
+        (n > 0 && (!logp || !r0 || !r_new || !utt || !last_tok || !cand || !prev_ref || !score))) {
+        cn_set_error("cn_op_ast_ctc_prefix: need n >= 0, K, Tp, V >= 1, 0 <= blank < V, 0 <= out_len <= Tp and non-null buffers");
+        return -1;
+    }
+    CtcPrefixArgs a;
+    a.logp = logp;
+    a.r0 = r0;
+    a.r_prev = r_prev;
+    a.r_new = r_new;
+    a.utt = utt;
+    a.last_tok = last_tok;
+    a.cand = cand;
+    a.prev_ref = prev_ref;
+    a.score = score;
+    a.n = n;
+    a.K = K;
+    a.Tp = Tp;
+    a.V = V;
+    a.blank = blank;
+    a.eos = eos;
+    a.out_len = out_len;
+    return launch_ast_ctc_prefix(a, (hipStream_t)stream);
+}
+
+static int ast_beam_state_of(AstBeamState& st, int32_t* tok0, int32_t* tok1, int32_t* anc0, int32_t* anc1, uint8_t* keyok0,
+                             uint8_t* keyok1, int32_t* len0, int32_t* len1, double* score0, double* score1, int32_t* valid0,
+                             int32_t* valid1, int32_t* ctc_ref0, int32_t* ctc_ref1, float* ctc_prev0, float* ctc_prev1, int32_t* cur_tok,
+                             int32_t* utt, int32_t* live, const char* who) {
+    const void* all[] = {tok0, tok1, anc0, anc1, keyok0, keyok1, len0, len1, score0, score1, valid0, valid1, ctc_ref0, ctc_ref1,
+                         ctc_prev0, ctc_prev1, cur_tok, utt, live};
+    for (const void* ptr : all)
+        if (!ptr) {
+            cn_set_error(std::string(who) + ": null state array");
+            return -1;
+        }
+    st.tok[0] = tok0;
+    st.tok[1] = tok1;
+    st.anc[0] = anc0;
+    st.anc[1] = anc1;
+    st.keyok[0] = keyok0;
+    st.keyok[1] = keyok1;
+    st.len[0] = len0;
+    st.len[1] = len1;
+    st.score[0] = score0;
+    st.score[1] = score1;
+    st.valid[0] = valid0;
+    st.valid[1] = valid1;
+    st.ctc_ref[0] = ctc_ref0;
+    st.ctc_ref[1] = ctc_ref1;
+    st.ctc_prev[0] = ctc_prev0;
+    st.ctc_prev[1] = ctc_prev1;
+    st.cur_tok = cur_tok;
+    st.utt = utt;
+    st.live = live;
+    return 0;
+}
+
+extern "C" int cn_op_ast_beam_init(int32_t* tok0, int32_t* tok1, int32_t* anc0, int32_t* anc1, uint8_t* keyok0, uint8_t* keyok1,
+                                   int32_t* len0, int32_t* len1, double* score0, double* score1, int32_t* valid0, int32_t* valid1,
+                                   int32_t* ctc_ref0, int32_t* ctc_ref1, float* ctc_prev0, float* ctc_prev1, int32_t* cur_tok, int32_t* utt,
+                                   int32_t* live, int32_t cur, int32_t B, int32_t bw, int32_t L, int32_t sos, int32_t pad, void* stream) {
+    if (B < 1 || bw < 1 || bw > 32 || L < 1 || (cur != 0 && cur != 1)) {
+        cn_set_error("cn_op_ast_beam_init: need B >= 1, 1 <= beam_width <= 32, L >= 1 and cur 0 or 1");
+        return -1;
+    }
+    AstBeamState st;
+    CN_TRY(ast_beam_state_of(st, tok0, tok1, anc0, anc1, keyok0, keyok1, len0, len1, score0, score1, valid0, valid1, ctc_ref0, ctc_ref1,
+                             ctc_prev0, ctc_prev1, cur_tok, utt, live, "cn_op_ast_beam_init"));
+    return launch_ast_beam_init(st, cur, B, bw, L, sos, pad, (hipStream_t)stream);
+}
+
+extern "C" int cn_op_ast_beam_update(int32_t* tok0, int32_t* tok1, int32_t* anc0, int32_t* anc1, uint8_t* keyok0, uint8_t* keyok1,
+                                     int32_t* len0, int32_t* len1, double* score0, double* score1, int32_t* valid0, int32_t* valid1,
+                                     int32_t* ctc_ref0, int32_t* ctc_ref1, float* ctc_prev0, float* ctc_prev1, int32_t* cur_tok,
+                                     int32_t* utt, int32_t* live, const int32_t* idx, const float* att, const float* ctc, const float* lm,
+                                     int32_t cur, int32_t pos, int32_t bw, int32_t K, int32_t L, int32_t eos, int32_t sos, int32_t pad,
+                                     int32_t use_ctc, int32_t use_lp, int32_t use_lm, float w, float u, float lw, double lp, int32_t B,
+                                     void* stream) {
+    if (B < 1 || bw < 1 || bw > 32 || K < bw || K > 32 || L < 1 || (cur != 0 && cur != 1) || !idx || !att || (use_ctc && !ctc) ||
+        (use_ctc && use_lm && !lm)) {
+        cn_set_error("cn_op_ast_beam_update: need B >= 1, 1 <= beam_width <= K <= 32, L >= 1, cur 0 or 1 and the step's arrays");
+        return -1;
+    }
+    AstBeamState st;
+    CN_TRY(ast_beam_state_of(st, tok0, tok1, anc0, anc1, keyok0, keyok1, len0, len1, score0, score1, valid0, valid1, ctc_ref0, ctc_ref1,
+                             ctc_prev0, ctc_prev1, cur_tok, utt, live, "cn_op_ast_beam_update"));
+    AstBeamStep q;
+    q.idx = idx;
+    q.att = att;
+    q.ctc = ctc;
+    q.lm = lm;
+    q.cur = cur;
+    q.pos = pos;
+    q.bw = bw;
+    q.K = K;
+    q.L = L;
+    q.eos = eos;
+    q.sos = sos;
+    q.pad = pad;
+    q.use_ctc = use_ctc;
+    q.use_lp = use_lp;
+    q.use_lm = use_lm;
+    q.w = w;
+    q.u = u;
+    q.lw = lw;
+    q.lp = lp;
+    return launch_ast_beam_update(st, q, B, (hipStream_t)stream);
+}
+
+extern "C" int cn_op_ffn_fused(float* x_dev, const float* ln_a_dev, const float* ln_b_dev, const float* w1_host,
+                               const float* b1_dev, const float* w2_host, const float* b2_dev, const float* nln_a_dev,
+                               const float* nln_b_dev, void* xn_out_dev, int32_t M, int32_t dff, float eps,
+                               int32_t nslice, void* stream) {
+    return cn_op_ffn_fused_act(x_dev, ln_a_dev, ln_b_dev, w1_host, b1_dev, w2_host, b2_dev, nln_a_dev, nln_b_dev, xn_out_dev, M, dff, eps,
+                               nslice, CN_ACT_RELU, stream);
+}
+
+extern "C" int cn_op_ffn_fused_act(float* x_dev, const float* ln_a_dev, const float* ln_b_dev, const float* w1_host,
+                                   const float* b1_dev, const float* w2_host, const float* b2_dev, const float* nln_a_dev,
+                                   const float* nln_b_dev, void* xn_out_dev, int32_t M, int32_t dff, float eps,
+                                   int32_t nslice, int32_t act, void* stream) {
+    if (act != CN_ACT_RELU && act != CN_ACT_SWISH) {
+        cn_set_error("cn_op_ffn_fused_act: act must be CN_ACT_RELU or CN_ACT_SWISH");
+        return -1;
+    }
+    if (dff <= 0 || dff % 128 != 0 || dff > 2048) {
+        cn_set_error("cn_op_ffn_fused: d_ff must be a positive multiple of 128, at most 2048");
+        return -1;
+    }
+    const size_t n = (size_t)dff * 256;
+    std::vector<uint16_t> h1(n), h2(n);
+    pack_ffn_w1(w1_host, dff, h1.data());
+    pack_ffn_w2(w2_host, dff, h2.data());
+    Scratch sc("cn_op_ffn_fused", (hipStream_t)stream);
+    FfnFusedArgs a;
+    a.x = x_dev;
+    a.ln_a = ln_a_dev;
+    a.ln_b = ln_b_dev;
+    a.w1p = sc.upload(h1.data(), n * 2);
+    a.b1 = b1_dev;
+    a.w2p = sc.upload(h2.data(), n * 2);
+    a.b2 = b2_dev;
+    a.nln_a = nln_a_dev;
+    a.nln_b = nln_b_dev;
+    a.xn_out = xn_out_dev;
+    a.M = M;
+    a.d = 256;
+    a.dff = dff;
+    a.eps = eps;
+    a.act = act == CN_ACT_SWISH ? FF_ACT_SWISH : FF_ACT_RELU;
+    if (nslice > 1) {  // d_ff split + reduce (the decode-step form)
+        a.nslice = nslice;
+        a.partial = (float*)sc.alloc((size_t)nslice * M * 256 * 4);
+    }
+    if (!sc.ok()) return -2;
+    int rc = launch_ffn_fused(a, (hipStream_t)stream);
+    if (rc == 0 && nslice > 1)
+        rc = launch_ffn_reduce(x_dev, a.partial, nslice, b2_dev, nln_a_dev, nln_b_dev, xn_out_dev, M, eps, (hipStream_t)stream);
+    return sc.finish(rc);
+}
+
+// the same sublayer in the split-bf16 precision (fused_x3.hip); xn_out_dev: split-bf16 [M][256] or NULL
+extern "C" int cn_op_ffn_x3(float* x_dev, const float* ln_a_dev, const float* ln_b_dev, const float* w1_host, const float* b1_dev,
+                            const float* w2_host, const float* b2_dev, const float* nln_a_dev, const float* nln_b_dev,
+                            void* xn_out_dev, int32_t M, int32_t dff, float eps, int32_t mix, void* stream) {
+    return cn_op_ffn_x3_act(x_dev, ln_a_dev, ln_b_dev, w1_host, b1_dev, w2_host, b2_dev, nln_a_dev, nln_b_dev, xn_out_dev, M, dff, eps, mix,
+                            CN_ACT_RELU, stream);
+}
+
+extern "C" int cn_op_ffn_x3_act(float* x_dev, const float* ln_a_dev, const float* ln_b_dev, const float* w1_host, const float* b1_dev,
+                                const float* w2_host, const float* b2_dev, const float* nln_a_dev, const float* nln_b_dev,
+                                void* xn_out_dev, int32_t M, int32_t dff, float eps, int32_t mix, int32_t act, void* stream) {
+    if (act != CN_ACT_RELU && (act != CN_ACT_SWISH || mix)) {
+        cn_set_error("cn_op_ffn_x3_act: act must be CN_ACT_RELU, or CN_ACT_SWISH without the mixed arithmetic");
+        return -1;
+    }
+    if (!ffn_x3_applies(256, dff)) {
+        cn_set_error("cn_op_ffn_x3: d_ff must be a positive multiple of 128, at most 2048");
+        return -1;
+    }
+    const size_t bytes = ffn_x3_stream_bytes(dff);
+    std::vector<uint16_t> h(bytes / 2);
+    pack_ffn_x3(w1_host, w2_host, dff, h.data(), mix != 0);
+    Scratch sc("cn_op_ffn_x3", (hipStream_t)stream);
+    FfnX3Args a;
+    a.x = x_dev;
+    a.ln_a = ln_a_dev;
+    a.ln_b = ln_b_dev;
+    a.wst = sc.upload(h.data(), bytes);
+    a.mix = mix != 0;
+    a.b1 = b1_dev;
+    a.b2 = b2_dev;
+    a.nln_a = nln_a_dev;
+    a.nln_b = nln_b_dev;
+    a.xn_out = xn_out_dev;
+    a.M = M;
+    a.d = 256;
+    a.dff = dff;
+    a.eps = eps;
+    a.act = act == CN_ACT_SWISH ? FF_ACT_SWISH : FF_ACT_RELU;
+    if (!sc.ok()) return -2;
+    return sc.finish(launch_ffn_x3(a, (hipStream_t)stream));
+}
+
+// The row-chain form of the split-bf16 engine as one op (fused_x3.hip PRO / TAIL): x += Wo . ctx + bo; x += FFN(LN1 x); then
+// LN_next(x) -> xn_out_dev (wt_host null) or its projection Wt . LN_next(x) + bt -> tail_out_dev (split-bf16 rows of tail_n
+// elements).  ctx_dev: split-bf16 [M][256] or null (no output projection); weight matrices on the host (fp32, nn.Linear layout),
+// vectors on the device.
+extern "C" int cn_op_x3_chain(float* x_dev, const void* ctx_dev, const float* wo_host, const float* bo_dev, const float* ln_a_dev,
+                              const float* ln_b_dev, const float* w1_host, const float* b1_dev, const float* w2_host,
+                              const float* b2_dev, const float* nln_a_dev, const float* nln_b_dev, void* xn_out_dev,
+                              const float* wt_host, const float* bt_dev, void* tail_out_dev, int32_t tail_n, int32_t M, int32_t dff,
+                              float eps, int32_t mix, void* stream) {
+    if (!ffn_x3_applies(256, dff) || (wt_host && !proj_x3_applies(tail_n, 256))) {
+        cn_set_error("cn_op_x3_chain: d_ff a multiple of 128 (<= 2048), tail_n a multiple of 32 (<= 1024)");
+        return -1;
+    }
+    Scratch sc("cn_op_x3_chain", (hipStream_t)stream);
+    FfnX3Args a;
+    {
+        std::vector<uint16_t> h(ffn_x3_stream_bytes(dff) / 2);
+        pack_ffn_x3(w1_host, w2_host, dff, h.data(), mix != 0);
+        a.wst = sc.upload(h.data(), h.size() * 2);
+        a.mix = mix != 0;
+    }
+    if (ctx_dev) {
+        std::vector<unsigned char> h((size_t)256 * 1024);
+        pack_proj_x3(wo_host, 256, h.data());
+        a.ctx = ctx_dev;
+        a.wo_p = sc.upload(h.data(), h.size());
+        a.bo = bo_dev;
+    }
+    if (wt_host) {
+        std::vector<unsigned char> h((size_t)tail_n * 1024);
+        pack_proj_x3(wt_host, tail_n, h.data());
+        a.tail_p = sc.upload(h.data(), h.size());
+        a.tail_b = bt_dev;
+        a.tail_out = tail_out_dev;
+        a.tail_n = tail_n;
+        a.ld_tail = tail_n;
+    }
+    a.x = x_dev;
+    a.ln_a = ln_a_dev;
+    a.ln_b = ln_b_dev;
+    a.b1 = b1_dev;
+    a.b2 = b2_dev;
+    a.nln_a = nln_a_dev;
+    a.nln_b = nln_b_dev;
+    a.xn_out = xn_out_dev;
+    a.M = M;
+    a.d = 256;
+    a.dff = dff;
+    a.eps = eps;
+    if (!sc.ok()) return -2;
+    return sc.finish(launch_ffn_x3(a, (hipStream_t)stream));
+}
+
+extern "C" int cn_op_chain(float* x_dev, const void* ctx_dev, int32_t ldctx, const float* wo_host, const float* bo_host,
+                           const float* ln1_a_host, const float* ln1_b_host, const float* w1_host, const float* b1_host,
+                           const float* w2_host, const float* b2_host, const float* nln_a_host, const float* nln_b_host,
+                           const float* wt_host, const float* bt_host, void* out_dev, int32_t ldo, int32_t M, int32_t dff,
+                           int32_t tail_n, float eps, int32_t x_mode, void* stream) {
+    if (dff < 0 || dff % 32 != 0 || dff > 2048 || tail_n < 0 || tail_n % 32 != 0 || tail_n > 1536) {
+        cn_set_error("cn_op_chain: d_ff and the tail width must be multiples of 32 (<= 2048 / <= 1536)");
+        return -1;
+    }
+    ChainWeights w;
+    w.wo = ctx_dev ? wo_host : nullptr;
+    w.bo = bo_host;
+    w.ln1_a = ln1_a_host;
+    w.ln1_b = ln1_b_host;
+    w.w1 = w1_host;
+    w.b1 = b1_host;
+    w.w2 = w2_host;
+    w.b2 = b2_host;
+    w.nln_a = nln_a_host;
+    w.nln_b = nln_b_host;
+    w.wt = wt_host;
+    w.bt = bt_host;
+    w.dff = dff;
+    w.tail_n = tail_n;
+    const int f8 = (x_mode & 32) != 0;
+    if (f8 && (dff <= 0 || dff % 256 != 0 || (x_mode & 8))) {
+        cn_set_error("cn_op_chain: the e4m3 feed-forward form (x_mode bit 32) needs d_ff % 256 == 0 and the ReLU activation");
+        return -1;
+    }
+    const size_t units = chain_stream_units(ctx_dev != nullptr, dff, tail_n, f8);
+    std::vector<uint16_t> hs((units + 7) * (CHAIN_UNIT_BYTES / 2));  // (seven spare units: the kernel's dummy refills read them)
+    std::vector<float> ht(CHAIN_TAB_FLOATS + 4);  // the table, then the four scale bytes of the e4m3 form
+    int hq[4] = {127, 127, 127, 127};
+    pack_chain(w, hs.data(), ht.data(), f8 ? hq : nullptr);
+    std::memcpy(&ht[CHAIN_TAB_FLOATS], hq, 16);
+    Scratch sc("cn_op_chain", (hipStream_t)stream);
+    void* ds = sc.upload(hs.data(), hs.size() * 2);
+    const float* dt = (const float*)sc.upload(ht.data(), ht.size() * 4);
+    if (!sc.ok()) return -2;
+    ChainArgs a;
+    a.x = x_dev;
+    a.ctx = ctx_dev;
+    a.ldctx = ldctx;
+    a.wstream = ds;
+    a.tab = dt;
+    a.out = out_dev;
+    a.ldo = ldo;
+    a.M = M;
+    a.d = 256;
+    a.dff = dff;
+    a.tail_n = tail_n;
+    a.has_next = nln_a_host != nullptr;
+    a.eps = eps;
+    a.x_in_blocked = (x_mode & 1) != 0;
+    a.x_out_blocked = (x_mode & 2) != 0;
+    a.store_x = (x_mode & 4) == 0;
+    a.swish = (x_mode & 8) != 0;
+    a.out_blocked = (x_mode & 16) != 0;
+    a.f8 = f8;
+    a.f8_q = f8 ? reinterpret_cast<const int*>(dt + CHAIN_TAB_FLOATS) : nullptr;
+    int rc = launch_chain(a, (hipStream_t)stream);
+    if (const char* rep = cn_exp_env("CASSNAT_CHAIN_REPEAT")) {  // timing runs only: x keeps being updated
+        // CASSNAT_CHAIN_STREAMS = n: the repeats go round-robin onto n private streams (how do concurrent launches share
+        // the chip?); they race on x, which a timing run does not look at
+        const int ns = cn_exp_env("CASSNAT_CHAIN_STREAMS") ? atoi(cn_exp_env("CASSNAT_CHAIN_STREAMS")) : 0;
+        std::vector<hipStream_t> ss(ns > 0 ? ns : 0);
+        for (auto& q : ss) (void)hipStreamCreateWithFlags(&q, hipStreamNonBlocking);
+        (void)hipStreamSynchronize((hipStream_t)stream);
+        for (int i = 1; i < atoi(rep) && rc == 0; ++i) rc = launch_chain(a, ns > 0 ? ss[i % ns] : (hipStream_t)stream);
+        for (auto& q : ss) {
+            (void)hipStreamSynchronize(q);
+            (void)hipStreamDestroy(q);
+        }
+    }
+    rc = sc.finish(rc);
+    if (cn_exp_env("CASSNAT_CHAIN_STAMPS")) (void)chain_print_stamps();
+    return rc;
+}
+
+static int op_genmax_impl(const void* h_dev, const float* w_host, const float* b_host, int32_t M, int32_t V,
+                          int32_t* arg_dev, float* maxlp_dev, const int32_t* tgt_dev, float* tgt_lp_dev, int32_t U, int32_t ld,
+                          void* stream) {
+    const int vtw = genmax_vtw(V);
+    if (vtw > 48) {
+        cn_set_error("cn_op_genmax: V too large");
+        return -1;
+    }
+    std::vector<uint16_t> hw((size_t)4 * vtw * 16 * 512);
+    std::vector<float> hb((size_t)4 * vtw * 32);
+    pack_genmax(w_host, b_host, V, hw.data(), hb.data());
+    Scratch sc("cn_op_genmax", (hipStream_t)stream);
+    GenmaxArgs a;
+    a.h = h_dev;
+    a.wp = sc.upload(hw.data(), hw.size() * 2);
+    a.bp = (const float*)sc.upload(hb.data(), hb.size() * 4);
+    if (!sc.ok()) return -2;
+    a.arg = arg_dev;
+    a.maxlp = maxlp_dev;
+    a.M = M;
+    a.V = V;
+    a.d = 256;
+    a.tgt = tgt_dev;
+    a.tgt_lp = tgt_lp_dev;
+    a.tgt_U = U;
+    a.tgt_ld = ld;
+    int rc = launch_genmax(a, (hipStream_t)stream);
+    if (const char* rep = cn_exp_env("CASSNAT_GENMAX_REPEAT"))  // timing runs only
+        for (int i = 1, n = atoi(rep); rc == 0 && i < n; ++i) rc = launch_genmax(a, (hipStream_t)stream);
+    return sc.finish(rc);
+}
+
+extern "C" int cn_op_genmax(const void* h_dev, const float* w_host, const float* b_host, int32_t M, int32_t V,
+                            int32_t* arg_dev, float* maxlp_dev, void* stream) {
+    return op_genmax_impl(h_dev, w_host, b_host, M, V, arg_dev, maxlp_dev, nullptr, nullptr, 0, 0, stream);
+}
+
+extern "C" int cn_op_genmax_gather(const void* h_dev, const float* w_host, const float* b_host, int32_t B, int32_t U, int32_t V,
+                                   const int32_t* tgt_dev, int32_t ld, float* tgt_lp_dev, void* stream) {
+    return op_genmax_impl(h_dev, w_host, b_host, B * U, V, nullptr, nullptr, tgt_dev, tgt_lp_dev, U, ld, stream);
+}
+
+// the split-bf16 form (CN_PRECISION_BF16X3): h_host fp32 [M][256] is split into hi + lo halves and uploaded by the call;
+// tgt_dev == NULL: arg-max (+ maxlp when maxlp_dev), else the target gather with M = rows, U per sequence, ld the target stride
+extern "C" int cn_op_genmax_x3(const float* h_host, const float* w_host, const float* b_host, int32_t M, int32_t V, int32_t* arg_dev,
+                               float* maxlp_dev, const int32_t* tgt_dev, int32_t U, int32_t ld, float* tgt_lp_dev, void* stream) {
+    if (!genmax_applies(CN_PREC_X3, 256, V) || M < 1) {
+        cn_set_error("cn_op_genmax_x3: V too large");
+        return -1;
+    }
+    const int vtw = genmax_x3_vtw(V);
+    std::vector<uint16_t> hw((size_t)8 * vtw * 16 * 1024);
+    std::vector<float> hb((size_t)8 * vtw * 32);
+    pack_genmax_x3(w_host, b_host, V, hw.data(), hb.data());
+    const std::vector<unsigned char> hx = split_rows256(h_host, M);
+    Scratch sc("cn_op_genmax_x3", (hipStream_t)stream);
+    GenmaxArgs a;
+    a.x3 = true;
+    a.h = sc.upload(hx.data(), hx.size());
+    a.wp = sc.upload(hw.data(), hw.size() * 2);
+    a.bp = (const float*)sc.upload(hb.data(), hb.size() * 4);
+    if (!sc.ok()) return -2;
+    a.arg = arg_dev;
+    a.maxlp = maxlp_dev;
+    a.M = M;
+    a.V = V;
+    a.d = 256;
+    a.tgt = tgt_dev;
+    a.tgt_lp = tgt_lp_dev;
+    a.tgt_U = U;
+    a.tgt_ld = ld;
+    int rc = launch_genmax(a, (hipStream_t)stream);
+    if (const char* rep = cn_exp_env("CASSNAT_GENMAX_REPEAT"))  // timing runs only
+        for (int i = 1, n = atoi(rep); rc == 0 && i < n; ++i) rc = launch_genmax(a, (hipStream_t)stream);
+    return sc.finish(rc);
+}
+
+// d_model-deep projection of the split-bf16 engine (proj_x3.hip): a_host fp32 [M][256] and w_host fp32 [N][256] are split into
+// hi + lo halves, packed and uploaded by the call; bias_host [N].  split_out == 0: c_dev fp32 [M][N] = (resid_dev ? resid +
+// resid_scale * : ) (A . W^T + bias), resid_dev fp32 [M][N] may alias c_dev;  split_out == 1: c_dev receives split-bf16 rows
+// (M * N * 4 bytes: per 32 columns 64 bytes of hi halves, then 64 bytes of lo halves)
+extern "C" int cn_op_proj_x3(const float* a_host, const float* w_host, const float* bias_host, const float* resid_dev,
+                             float resid_scale, void* c_dev, int32_t M, int32_t N, int32_t split_out, void* stream) {
+    if (!proj_x3_applies(N, 256) || M < 1) {
+        cn_set_error("cn_op_proj_x3: N must be a multiple of 32, at most 1024");
+        return -1;
+    }
+    std::vector<unsigned char> hw((size_t)N * 1024);
+    pack_proj_x3(w_host, N, hw.data());
+    const std::vector<unsigned char> hx = split_rows256(a_host, M);
+    Scratch sc("cn_op_proj_x3", (hipStream_t)stream);
+    ProjX3Args a;
+    a.A = sc.upload(hx.data(), hx.size());
+    a.lda = 256;
+    a.wp = sc.upload(hw.data(), hw.size());
+    a.bias = (const float*)sc.upload(bias_host, (size_t)N * 4);
+    if (!sc.ok()) return -2;
+    a.C = c_dev;
+    a.ldc = N;
+    a.c_f32 = split_out ? 0 : 1;
+    a.resid = resid_dev;
+    a.ldr = N;
+    a.resid_scale = resid_scale;
+    a.M = M;
+    a.N = N;
+    return sc.finish(launch_proj_x3(a, (hipStream_t)stream));
+}

@@ -164,6 +164,8 @@ def lib(flavour=None):
                            C.POINTER(C.c_int32)]
     L.cn_op_ffn_fused.argtypes = [C.c_void_p] * 10 + [C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_void_p]
     L.cn_op_ffn_x3.argtypes = [C.c_void_p] * 10 + [C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_void_p]
+    L.cn_op_ffn_fused_act.argtypes = [C.c_void_p] * 10 + [C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_void_p]
+    L.cn_op_ffn_x3_act.argtypes = [C.c_void_p] * 10 + [C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_void_p]
     L.cn_op_x3_chain.argtypes = [C.c_void_p] * 16 + [C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_void_p]
     L.cn_op_chain.argtypes = ([C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 13 +
                               [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_void_p])
