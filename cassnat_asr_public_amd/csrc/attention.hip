@@ -601,7 +601,7 @@ template <typename T> static int run_attention(const AttnArgs& a, hipStream_t s)
     p.q_n = a.q_n;
     p.kv_n = a.kv_n;
     if ((a.q_blocked || a.kv_blocked || a.o_blocked) && (sizeof(T) != 2 || __is_same(T, split_t) || a.rel_pos || (a.q_blocked && a.q_n % 32) ||
-                                          (a.kv_blocked && a.kv_n % 32))) {
+                                          (a.kv_blocked && a.kv_n % 32) || (a.o_blocked && a.ldo % 32))) {
         cn_set_error("attention: blocked operands exist for the bf16 kernels without relative positions; column counts % 32 == 0");
         return -1;
     }
@@ -663,7 +663,25 @@ int launch_attention(int prec, const AttnArgs& a, hipStream_t s) {
             cn_set_error("attention: split-bf16 rows need strides that are multiples of 32 elements");
             return -1;
         }
-        return run_attention<split_t>(a, s);
     }
+    // head h reads / writes columns 64 h .. 64 h + 63 of a row: narrower rows would overlap the next row's heads, a blocked
+    // window past its matrix the next 32-row block
+    const long long w = 64LL * a.H;
+    if ((!a.q_blocked && a.ldq < w) || (!a.kv_blocked && (a.ldk < w || a.ldv < w)) || a.ldo < w) {
+        cn_set_error("attention: row strides ldq / ldk / ldv / ldo must be >= 64 * H");
+        return -1;
+    }
+    if (a.rel_pos && a.ld_pos < w) {
+        cn_set_error("attention: the relative-position table needs ld_pos >= 64 * H");
+        return -1;
+    }
+    auto bad_window = [w](int col, int n) { return col < 0 || col % 8 || col + w > n; };
+    if ((a.q_blocked && bad_window(a.q_col, a.q_n)) ||
+        (a.kv_blocked && (bad_window(a.k_col, a.kv_n) || bad_window(a.v_col, a.kv_n)))) {
+        cn_set_error("attention: a blocked operand's columns col .. col + 64 * H - 1 must lie inside its q_n / kv_n columns "
+                     "(col >= 0, col % 8 == 0)");
+        return -1;
+    }
+    if (prec == CN_PREC_X3) return run_attention<split_t>(a, s);
     return prec == CN_PREC_F32 ? run_attention<float>(a, s) : run_attention<bf16>(a, s);
 }

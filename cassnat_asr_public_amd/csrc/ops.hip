@@ -340,6 +340,53 @@ extern "C" int cn_op_attention(int32_t precision, const void* Q, int32_t ldq, co
     return rc;
 }
 
+extern "C" int cn_op_attention_desc(int32_t precision, const cn_attn_desc* d, void* stream) {
+    if ((precision = cn_own_precision(precision, "cn_op_attention_desc")) < 0) return -1;
+    if (!d) {
+        cn_set_error("cn_op_attention_desc: null descriptor");
+        return -1;
+    }
+    AttnArgs a;
+    a.Q = d->Q;
+    a.K = d->K;
+    a.V = d->V;
+    a.O = d->O;
+    a.ldq = d->ldq;
+    a.ldk = d->ldk;
+    a.ldv = d->ldv;
+    a.ldo = d->ldo;
+    a.B = d->B;
+    a.H = d->H;
+    a.Lq = d->Lq;
+    a.Lk = d->Lk;
+    a.keymask = d->keymask;
+    a.kv_mod = d->kv_mod;
+    a.kv_index = d->kv_index;
+    a.klen = d->klen;
+    a.kcap = d->kcap;
+    a.kcap_stride = d->kcap_stride;
+    a.q_blocked = d->q_blocked;
+    a.kv_blocked = d->kv_blocked;
+    a.q_col = d->q_col;
+    a.k_col = d->k_col;
+    a.v_col = d->v_col;
+    a.q_n = d->q_n;
+    a.kv_n = d->kv_n;
+    a.o_blocked = d->o_blocked;
+    a.intervals = d->intervals;
+    a.iv_stride = d->iv_stride;
+    a.causal = d->causal;
+    a.scale = d->scale;
+    a.rel_pos = d->rel_pos;
+    a.rel_u = d->rel_u;
+    a.rel_v = d->rel_v;
+    a.rel_R = d->rel_R;
+    a.ld_pos = d->ld_pos;
+    return launch_attention(precision, a, (hipStream_t)stream);
+}
+
+extern "C" int32_t cn_attn_desc_size(void) { return (int32_t)sizeof(cn_attn_desc); }
+
 extern "C" int cn_op_logsoftmax_argmax(float* logits, int32_t M, int32_t V, int32_t* arg, float* maxlp,
                                        int32_t write_logp, void* stream) {
     return launch_logsoftmax_argmax(logits, M, V, V, arg, maxlp, write_logp, (hipStream_t)stream);

@@ -68,6 +68,17 @@ class CnFbankOpts(C.Structure):
                [("reserved", C.c_int32 * 5)]
 
 
+class CnAttnDesc(C.Structure):
+    """cn_attn_desc: every option of the fused attention kernel (cn_op_attention_desc)."""
+    _fields_ = [("Q", C.c_void_p), ("K", C.c_void_p), ("V", C.c_void_p), ("O", C.c_void_p)] + \
+               [(n, C.c_int32) for n in ("ldq", "ldk", "ldv", "ldo", "B", "H", "Lq", "Lk")] + \
+               [("keymask", C.c_void_p), ("kv_mod", C.c_int32), ("kv_index", C.c_void_p), ("klen", C.c_void_p), ("kcap", C.c_void_p),
+                ("kcap_stride", C.c_int32)] + \
+               [(n, C.c_int32) for n in ("q_blocked", "kv_blocked", "q_col", "k_col", "v_col", "q_n", "kv_n", "o_blocked")] + \
+               [("intervals", C.c_void_p), ("iv_stride", C.c_int32), ("causal", C.c_int32), ("scale", C.c_float),
+                ("rel_pos", C.c_void_p), ("rel_u", C.c_void_p), ("rel_v", C.c_void_p), ("rel_R", C.c_int32), ("ld_pos", C.c_int32)]
+
+
 class HipError(RuntimeError):
     pass
 
@@ -120,6 +131,8 @@ def lib(flavour=None):
     L.cn_op_attention.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
                                   C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_void_p]
+    L.cn_op_attention_desc.argtypes = [C.c_int32, C.POINTER(CnAttnDesc), C.c_void_p]
+    L.cn_attn_desc_size.argtypes = []
     L.cn_op_logsoftmax_argmax.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     L.cn_op_ctc_align.argtypes = [C.c_void_p] * 3 + [C.c_int32] * 5 + [C.c_void_p] * 6
     L.cn_op_greedy_pack.argtypes = [C.c_void_p] * 3 + [C.c_int32] * 4 + [C.c_void_p] * 4

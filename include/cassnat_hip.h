@@ -375,6 +375,39 @@ int cn_op_attention(int32_t precision, const void* Q, int32_t ldq, const void* K
                     int32_t ldv, void* O, int32_t ldo, int32_t B, int32_t H, int32_t Lq, int32_t Lk,
                     const uint8_t* keymask, const int32_t* klen, const int32_t* intervals, int32_t iv_stride,
                     int32_t causal, float scale, void* stream);
+/* Every option of the fused attention kernel (the internal AttnArgs, field for field): Q / K / V / O rows of the precision's
+ * elements with head h at columns 64h.. (row-major: ld* >= 64 * H); keymask [entries][Lk]; kv_mod > 0 / kv_index: query set b
+ * reads K / V / keymask / kcap of entry b % kv_mod / kv_index[b]; klen [B]; kcap: entry e holds kcap[e * kcap_stride] <= Lk keys,
+ * later ones are absent (-inf); q_blocked / kv_blocked / o_blocked (16-bit layouts, no rel_pos): blocked matrices of q_n / kv_n /
+ * ldo columns, head 0 at q_col / k_col / v_col; intervals [B][iv_stride][4]; causal; rel_pos [2R+1][ld_pos] fp32 with rel_u /
+ * rel_v [64 H] fp32 (relative-position self attention, Lq == Lk, R <= 31).  cn_attn_desc_size() is sizeof(cn_attn_desc). */
+typedef struct cn_attn_desc {
+    const void* Q;
+    const void* K;
+    const void* V;
+    void* O;
+    int32_t ldq, ldk, ldv, ldo;
+    int32_t B, H, Lq, Lk;
+    const uint8_t* keymask;
+    int32_t kv_mod;
+    const int32_t* kv_index;
+    const int32_t* klen;
+    const int32_t* kcap;
+    int32_t kcap_stride;
+    int32_t q_blocked, kv_blocked;
+    int32_t q_col, k_col, v_col, q_n, kv_n;
+    int32_t o_blocked;
+    const int32_t* intervals;
+    int32_t iv_stride;
+    int32_t causal;
+    float scale;
+    const float* rel_pos;
+    const float* rel_u;
+    const float* rel_v;
+    int32_t rel_R, ld_pos;
+} cn_attn_desc;
+int cn_op_attention_desc(int32_t precision, const cn_attn_desc* a, void* stream);
+int32_t cn_attn_desc_size(void);
 int cn_op_logsoftmax_argmax(float* logits, int32_t M, int32_t V, int32_t* arg, float* maxlp, int32_t write_logp,
                             void* stream);
 int cn_op_ctc_align(const int32_t* best, const uint8_t* keymask, const float* size_ratio, int32_t B, int32_t Tp,

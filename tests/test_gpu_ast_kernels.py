@@ -11,13 +11,12 @@ import numpy as np
 import pytest
 import torch
 
+from attention_model import EPS, LAYOUTS, NEG_FILL, from_layout, gamma, out_ulp, to_layout, ulp32
 from cassnat_asr_public_amd import hip
 from oracle import ast_oracle
 
 pytestmark = pytest.mark.gpu
 
-EPS = 2.0 ** -24  # float32 unit roundoff
-NEG_FILL = float(np.finfo(np.float32).min)  # masked attention score (the reference's masked_fill value)
 LOGZERO = np.float32(-1e10)
 
 
@@ -27,14 +26,6 @@ def p(t):
 
 def stream():
     return hip.current_stream()
-
-
-def gamma(n):
-    return n * EPS / (1 - n * EPS)
-
-
-def ulp32(x):
-    return np.spacing(np.abs(np.asarray(x, np.float32))).astype(np.float64)
 
 
 # ============================================================================================ LM-fusion tails (rowops.hip)
@@ -151,36 +142,6 @@ def test_logsoftmax_gather_against_float32_emulation(V, k):
 
 
 # ============================================================================================ gather attention (ast.hip)
-LAYOUTS = {  # name: (library flavour, CN_PRECISION_*, operand name the library must report)
-    "fp32": (None, 0, "bf16"),
-    "bf16": (None, 1, "bf16"),
-    "fp16": ("f16", 4, "fp16"),
-    "bf16x3": (None, 3, "bf16"),
-}
-
-
-def to_layout(x, layout):
-    """float32 tensor (rows of C columns) -> (device tensor in the layout's element bytes, float64 operand the kernel sees)."""
-    if layout == "fp32":
-        return x.cuda(), x.double()
-    if layout in ("bf16", "fp16"):
-        h = x.to(torch.bfloat16 if layout == "bf16" else torch.float16)
-        return h.cuda(), h.double()
-    hi = x.to(torch.bfloat16)
-    lo = (x - hi.float()).to(torch.bfloat16)
-    sh = x.shape[:-1] + (x.shape[-1] // 32, 1, 32)
-    packed = torch.cat([hi.reshape(sh), lo.reshape(sh)], dim=-2).reshape(x.shape[:-1] + (2 * x.shape[-1],))
-    return packed.cuda(), hi.double() + lo.double()
-
-
-def from_layout(t, layout):
-    if layout != "bf16x3":
-        return t.cpu().double()
-    c = t.shape[-1] // 2
-    g = t.cpu().reshape(t.shape[:-1] + (c // 32, 2, 32))
-    return (g[..., 0, :].double() + g[..., 1, :].double()).reshape(t.shape[:-1] + (c,))
-
-
 def attn_model(q, Kg, Vg, allowed, H, scale):
     """float64 softmax(q . k^T * scale) . v per head; q (n, d), Kg / Vg (n, nkeys, d), allowed (n, nkeys) -> (out, fp32 bound)."""
     n, nk, d = Kg.shape
@@ -198,18 +159,6 @@ def attn_model(q, Kg, Vg, allowed, H, scale):
     mass = torch.einsum("nhj,njhi->nhi", pr, Vh.abs())
     bound = 2 * (2 * ds * spread + gamma(nk + 2) * (mass + out.abs()) + 2 * EPS * out.abs())
     return out.reshape(n, d), bound.reshape(n, d)
-
-
-def out_ulp(ref, layout):
-    """One ulp of the output element at |ref| (split-bf16: the bound of its hi + lo rounding, ~17 significant bits)."""
-    sp = torch.from_numpy(ulp32(ref.numpy()))  # float32 ulp: 2^(e - 23)
-    if layout == "fp32":
-        return torch.zeros_like(ref)
-    if layout == "bf16x3":
-        return ref.abs() * 2.0 ** -16 + 1e-38
-    if layout == "bf16":
-        return sp * 2.0 ** 16
-    return torch.clamp(sp * 2.0 ** 13, min=2.0 ** -24)
 
 
 ATTN_SHAPES = [(H, nk) for H in (1, 2, 4, 8, 16) for nk in (1, 63, 64, 65, 200, 16384 // H)]
