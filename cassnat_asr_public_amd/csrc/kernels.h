@@ -476,4 +476,35 @@ struct AstBeamStep {
 };
 int launch_ast_beam_init(const AstBeamState& st, int cur, int B, int bw, int L, int sos, int pad, hipStream_t s);
 int launch_ast_beam_update(const AstBeamState& st, const AstBeamStep& q, int B, hipStream_t s);
+// CASS-NAT finish loop with LM shallow fusion (natlm.hip).  Fused row of slot s = b * bw + j at step `step`:
+// att[b][step][:] (log-probabilities; all zero when zlen && step >= zlen[b]) + fl32(w * log_softmax(lm[s][:])) -> its k best
+struct NatFuseArgs {
+    const float* att;   // [B][U][V] log-probability rows of the decode pass
+    const float* lm;    // [S][V] LM logits of this step
+    const int* last;    // [B] last step of every utterance (later steps: the slot is skipped), or null
+    const int* zlen;    // [B] rows at or past it read as zero (ESA), or null
+    int* idx;           // [S][k]
+    float* val;         // [S][k]
+    int U, V, bw, step, k;
+    float w;
+};
+int launch_nat_lm_fuse_topk(const NatFuseArgs& a, int slots, hipStream_t s);
+// device-side beam state of that loop (double buffered); S = B * beam_width slots of L tokens
+struct NatBeamState {
+    int* tok[2];              // [S][L] hypothesis tokens (sos first)
+    int* anc[2];              // [S][L] LM cache slot that produced each position
+    unsigned char* keyok[2];  // [S][L] token != padding_idx
+    double* score[2];         // [S]
+    int* cur_tok;             // [S] newest token = the next LM step's input
+};
+struct NatBeamStep {
+    const int* idx;    // [S][bw] candidate tokens of this step (best first)
+    const float* val;  // [S][bw] their fused values
+    const int* last;   // [B] last step of every utterance
+    int cur, step, bw, L, pad, use_lp;
+    double lp;
+};
+int launch_nat_beam_init(const NatBeamState& st, const int* ylen, int ymax, int* last, int* hyp_len, int B, int bw, int L, int sos,
+                         int pad, hipStream_t s);
+int launch_nat_beam_update(const NatBeamState& st, const NatBeamStep& q, int B, hipStream_t s);
 int launch_logsoftmax_temp(float* logits, int M, int V, int ldl, float temperature, int* arg, float* maxlp, hipStream_t s);

@@ -243,13 +243,15 @@ struct cn_model {
     int beam_S = 0, beam_L = 0, beam_K = 0;
     int *beam_idx = nullptr;
     float *beam_val = nullptr, *beam_ctc = nullptr, *beam_lm = nullptr;
-    // LM shallow fusion (cn_ast_attach_lm): the TransformerLM handle whose step runs beside this decoder's.  On an LM handle
+    // LM shallow fusion (cn_ast_attach_lm; cn_nat_attach_lm on a CASS-NAT handle, whose finish loop steps it): the TransformerLM
+    // handle whose step runs beside this decoder's.  On an LM handle
     // (cfg.ast = 2) the ast_ck / ast_cv / ast_logits fields above hold ITS step cache [layer][pos][slot][d] and logits.
     cn_model* ast_lm = nullptr;
     const void* lib_tag = nullptr;  // which of the two libraries created the handle (an attach never crosses them)
 
     // last call
     int B = 0, T = 0, T1 = 0, Tp = 0, U = 0, last_k = 0;
+    int att_rows_U = 0;  // > 0: m->logits holds the decoder's log-probability rows [B][att_rows_U][V] of the last pass (cn_nat_lm_finish)
     int dec_group = 1;  // decoder-side batch = B * dec_group (ESA: that many alignments per utterance in one pass), else 1
     std::map<std::string, Capture> captures;
 
@@ -1952,6 +1954,7 @@ int stage_encode(cn_model* m, const float* feats, int B, int T, int F, const cn_
     m->T1 = T1;
     m->Tp = Tp;
     m->U = 0;
+    m->att_rows_U = 0;
     CN_TRY(launch_keymask(feats, B, T, F, Tp, 4, (float)o->padding_idx, m->keymask, s));
     // (fp16 engines: the features against the half range; split-bf16 engines: against the e4m3 range of conv2's mixed arithmetic)
     if (m->op16_fault && m->op16_feat_limit) CN_TRY(launch_feature_range(feats, (size_t)B * T * F, m->op16_feat_limit, m->op16_fault, s));
@@ -2331,7 +2334,11 @@ int stage_decode_tail(cn_model* m, int U, const cn_decode_opts* o, int32_t* hyp,
     const bool cap = o->capture != 0;
     if (cap) CN_TRY(capture(m, "dec_h", m->dec_h, true, CN_DTYPE_F32, {B, U, d}, s));
     const int k = o->beam_width;
-    CN_TRY(run_generator(m, m->att_gen, m->dec_h, MU, m->tok, m->val, cap || k > 1, s));
+    const bool keep_rows = o->reserved[0] != 0;  // cn_decode_opts.reserved[0]: the LM-fused finish reads the full rows at any beam width
+    CN_TRY(run_generator(m, m->att_gen, m->dec_h, MU, m->tok, m->val, cap || k > 1 || keep_rows, s));
+    // (a merged / coalesced / row-predicted pass is not offered to cn_nat_lm_finish: its utterances count their rows per batch)
+    const bool plain_pass = m->dec_group == 1 && !m->ragged && !m->u_predicted && o->sub_batch == 0;
+    m->att_rows_U = (cap || k > 1 || keep_rows) && plain_pass ? U : 0;
     if (cap) CN_TRY(capture(m, "att_out", m->logits, false, CN_DTYPE_F32, {B, U, c.vocab_size}, s));
     m->last_k = 0;
     if (k > 1) {
@@ -3758,6 +3765,121 @@ extern "C" int cn_decode_ast(cn_model* m, const float* feats_dev, int32_t B, int
     }
     CN_HIP_CHECK(hipMemcpyAsync(hyp_out_dev, st.tok[cur], (size_t)S * L * 4, hipMemcpyDeviceToDevice, s));
     CN_HIP_CHECK(hipMemcpyAsync(hyp_len_dev, st.len[cur], (size_t)S * 4, hipMemcpyDeviceToDevice, s));
+    CN_HIP_CHECK(hipMemcpyAsync(score_dev, st.score[cur], (size_t)S * 8, hipMemcpyDeviceToDevice, s));
+    return 0;
+}
+
+// ---- CASS-NAT + LM: the finish loop of CassNAT.beam_decode with args.lm_weight > 0 (src/models/cassnat.py:574-637) ------------
+// src/tasks/cassnat_task.py:85-127 + cassnat.py:603-607: the TransformerLM whose step the finish loop fuses (NULL detaches).
+extern "C" int cn_nat_attach_lm(cn_model* m, cn_model* lm) {
+    if (!m || m->cfg.ast != 0) {
+        cn_set_error("cn_nat_attach_lm: the first handle must be a CASS-NAT model (cfg.ast = 0)");
+        return -1;
+    }
+    if (!lm) {
+        m->ast_lm = nullptr;
+        return 0;
+    }
+    if (lm->lib_tag != m->lib_tag) {
+        cn_set_error("cn_nat_attach_lm: the two handles come from different libraries");
+        return -1;
+    }
+    if (lm->cfg.ast != 2 || !lm->finalized) {
+        cn_set_error("cn_nat_attach_lm: the LM handle must be a finalized TransformerLM (cfg.ast = 2)");
+        return -1;
+    }
+    if (lm->cfg.vocab_size != m->cfg.vocab_size || lm->cfg.device != m->cfg.device) {
+        cn_set_error("cn_nat_attach_lm: the LM must have the decoder's vocabulary and device");
+        return -1;
+    }
+    m->ast_lm = lm;
+    return 0;
+}
+
+// ymax steps of [LM step on every slot -> fused row top-k -> beam update]; the step count and every utterance's last step are
+// known before the loop starts, so nothing is read back inside it.
+extern "C" int cn_nat_lm_finish(cn_model* m, const cn_decode_opts* opts, int32_t ymax, int32_t beam_width, float lm_weight,
+                                int32_t use_length_penalty, double length_penalty, int32_t zero_past_len, int32_t* hyp_out_dev,
+                                int32_t max_len, int32_t* hyp_len_dev, double* score_dev, void* stream) {
+    if (!m || !opts || !hyp_out_dev || !hyp_len_dev || !score_dev) {
+        cn_set_error("cn_nat_lm_finish: null argument");
+        return -1;
+    }
+    cn_model* lm = m->ast_lm;
+    if (m->cfg.ast != 0 || !lm || !(lm_weight > 0.f)) {
+        cn_set_error("cn_nat_lm_finish: needs lm_weight > 0 and an LM attached with cn_nat_attach_lm");
+        return -1;
+    }
+    const int bw = beam_width, B = m->B, U = m->att_rows_U, V = m->cfg.vocab_size, L = max_len;
+    if (U < 1 || B < 1) {
+        cn_set_error("cn_nat_lm_finish: the last decode pass kept no log-probability rows (set cn_decode_opts.reserved[0], one "
+                     "alignment per utterance)");
+        return -1;
+    }
+    if (bw < 1 || bw > 16 || bw > V || ymax < 1 || ymax > U || L < ymax + 1) {
+        cn_set_error("cn_nat_lm_finish: need 1 <= beam_width <= 16, 1 <= ymax <= rows of the pass and max_len >= ymax + 1");
+        return -1;
+    }
+    const int S = B * bw;
+    hipStream_t s = (hipStream_t)stream;
+    CN_HIP_CHECK(hipSetDevice(m->cfg.device));
+    CN_TRY(lm_check_step(lm, L, S, "cn_nat_lm_finish"));
+    CN_TRY(lm_prepare_buffers(lm, L, S));
+    NatBeamState st;
+    void* p = nullptr;
+    for (int i = 0; i < 2; ++i) {
+        CN_TRY(scratch_buf(m, i ? "nat_tok1" : "nat_tok0", (size_t)S * L * 4, &p));
+        st.tok[i] = (int*)p;
+        CN_TRY(scratch_buf(m, i ? "nat_anc1" : "nat_anc0", (size_t)S * L * 4, &p));
+        st.anc[i] = (int*)p;
+        CN_TRY(scratch_buf(m, i ? "nat_keyok1" : "nat_keyok0", (size_t)S * L, &p));
+        st.keyok[i] = (unsigned char*)p;
+        CN_TRY(scratch_buf(m, i ? "nat_score1" : "nat_score0", (size_t)S * 8, &p));
+        st.score[i] = (double*)p;
+    }
+    CN_TRY(scratch_buf(m, "nat_cur_tok", (size_t)S * 4, &p));
+    st.cur_tok = (int*)p;
+    int *last = nullptr, *cidx = nullptr;
+    float* cval = nullptr;
+    CN_TRY(scratch_buf(m, "nat_last", (size_t)B * 4, (void**)&last));
+    CN_TRY(scratch_buf(m, "nat_cand_idx", (size_t)S * bw * 4, (void**)&cidx));
+    CN_TRY(scratch_buf(m, "nat_cand_val", (size_t)S * bw * 4, (void**)&cval));
+    CN_TRY(launch_nat_beam_init(st, m->ylen, ymax, last, hyp_len_dev, B, bw, L, opts->sos, opts->padding_idx, s));
+    int cur = 0;
+    for (int step = 0; step < ymax; ++step) {
+        CN_TRY(lm_step_run(lm, S, step, st.cur_tok, st.anc[cur], st.keyok[cur], L, s));
+        NatFuseArgs f;
+        f.att = m->logits;
+        f.lm = lm->ast_logits;
+        f.last = last;
+        f.zlen = zero_past_len ? m->ylen : nullptr;
+        f.idx = cidx;
+        f.val = cval;
+        f.U = U;
+        f.V = V;
+        f.bw = bw;
+        f.step = step;
+        f.k = bw;
+        f.w = lm_weight;
+        {
+            ProfScope ps(m, "nat_lm_fuse_topk", 0, 2.0 * S * V * 4, s);
+            CN_TRY(launch_nat_lm_fuse_topk(f, S, s));
+        }
+        NatBeamStep q;
+        q.idx = cidx;
+        q.val = cval;
+        q.last = last;
+        q.cur = cur;
+        q.step = step;
+        q.bw = bw;
+        q.L = L;
+        q.pad = opts->padding_idx;
+        q.use_lp = use_length_penalty;
+        q.lp = length_penalty;
+        CN_TRY(launch_nat_beam_update(st, q, B, s));
+        cur ^= 1;
+    }
+    CN_HIP_CHECK(hipMemcpyAsync(hyp_out_dev, st.tok[cur], (size_t)S * L * 4, hipMemcpyDeviceToDevice, s));
     CN_HIP_CHECK(hipMemcpyAsync(score_dev, st.score[cur], (size_t)S * 8, hipMemcpyDeviceToDevice, s));
     return 0;
 }

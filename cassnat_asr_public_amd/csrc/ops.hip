@@ -779,6 +779,63 @@ extern "C" int cn_op_ast_beam_update(int32_t* tok0, int32_t* tok1, int32_t* anc0
     return launch_ast_beam_update(st, q, B, (hipStream_t)stream);
 }
 
+// natlm.hip one kernel at a time (cn_nat_lm_finish runs them inside its loop); every array is the caller's, on the device
+extern "C" int cn_op_nat_lm_fuse_topk(const float* att, const float* lm, const int32_t* last, const int32_t* zlen, int32_t B, int32_t U,
+                                      int32_t V, int32_t bw, int32_t step, float w, int32_t k, int32_t* idx, float* val, void* stream) {
+    if (B < 1 || V < 1 || !att || !lm || !idx || !val) {
+        cn_set_error("cn_op_nat_lm_fuse_topk: bad argument");
+        return -1;
+    }
+    NatFuseArgs a;
+    a.att = att;
+    a.lm = lm;
+    a.last = last;
+    a.zlen = zlen;
+    a.idx = idx;
+    a.val = val;
+    a.U = U;
+    a.V = V;
+    a.bw = bw;
+    a.step = step;
+    a.k = k;
+    a.w = w;
+    return launch_nat_lm_fuse_topk(a, B * bw, (hipStream_t)stream);
+}
+
+extern "C" int cn_op_nat_beam_update(int32_t* tok0, int32_t* tok1, int32_t* anc0, int32_t* anc1, uint8_t* keyok0, uint8_t* keyok1,
+                                     double* score0, double* score1, int32_t* cur_tok, const int32_t* idx, const float* val,
+                                     const int32_t* last, int32_t cur, int32_t step, int32_t bw, int32_t L, int32_t pad, int32_t use_lp,
+                                     double lp, int32_t B, void* stream) {
+    const void* all[] = {tok0, tok1, anc0, anc1, keyok0, keyok1, score0, score1, cur_tok, idx, val, last};
+    for (const void* ptr : all)
+        if (!ptr) {
+            cn_set_error("cn_op_nat_beam_update: null array");
+            return -1;
+        }
+    NatBeamState st;
+    st.tok[0] = tok0;
+    st.tok[1] = tok1;
+    st.anc[0] = anc0;
+    st.anc[1] = anc1;
+    st.keyok[0] = keyok0;
+    st.keyok[1] = keyok1;
+    st.score[0] = score0;
+    st.score[1] = score1;
+    st.cur_tok = cur_tok;
+    NatBeamStep q;
+    q.idx = idx;
+    q.val = val;
+    q.last = last;
+    q.cur = cur;
+    q.step = step;
+    q.bw = bw;
+    q.L = L;
+    q.pad = pad;
+    q.use_lp = use_lp;
+    q.lp = lp;
+    return launch_nat_beam_update(st, q, B, (hipStream_t)stream);
+}
+
 extern "C" int cn_op_ffn_fused(float* x_dev, const float* ln_a_dev, const float* ln_b_dev, const float* w1_host,
                                const float* b1_dev, const float* w2_host, const float* b2_dev, const float* nln_a_dev,
                                const float* nln_b_dev, void* xn_out_dev, int32_t M, int32_t dff, float eps,

@@ -196,6 +196,11 @@ def lib(flavour=None):
     L.cn_ast_attach_lm.argtypes = [C.c_void_p, C.c_void_p]
     L.cn_ast_step_lm.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                  C.c_float, C.c_int32, C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.cn_nat_attach_lm.argtypes = [C.c_void_p, C.c_void_p]
+    L.cn_nat_lm_finish.argtypes = [C.c_void_p, C.POINTER(CnDecodeOpts), C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_double, C.c_int32,
+                                   C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.cn_op_nat_lm_fuse_topk.argtypes = [C.c_void_p] * 4 + [C.c_int32] * 5 + [C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.cn_op_nat_beam_update.argtypes = [C.c_void_p] * 12 + [C.c_int32] * 6 + [C.c_double, C.c_int32, C.c_void_p]
     L.cn_lm_step_begin.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
     L.cn_lm_step.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     L.cn_fbank_default_opts.argtypes = [C.POINTER(CnFbankOpts)]
@@ -439,6 +444,22 @@ class Engine:
                                     float(temperature), K, float(lm_weight), int(use_ctc), _ptr(topk_idx), _ptr(topk_val),
                                     _ptr(lm_val) if lm_val is not None else None, current_stream()), "cn_ast_step_lm")
 
+    # ---- CASS-NAT + LM: the finish loop with LM shallow fusion
+    def nat_attach_lm(self, lm):
+        """``lm`` (an Engine of a TransformerLM, same library) is the lm_model of this NAT engine's fused finish loop; None
+        detaches.  The caller keeps ``lm`` open while attached."""
+        if lm is not None and lm.L is not self.L:
+            raise HipError("cn_nat_attach_lm: the LM engine comes from the other library")
+        self._chk(self.L.cn_nat_attach_lm(self.handle, lm.handle if lm is not None else None), "cn_nat_attach_lm")
+        self._lm = lm
+
+    def nat_lm_finish(self, opts, ymax, beam_width, lm_weight, length_penalty, zero_past_len, hyp, hyp_len, score):
+        """The finish loop with the attached LM after a pass that kept its rows (``opts.reserved[0] = 1``): hyp int32
+        (B, beam, max_len), hyp_len int32 (B, beam), score float64 (B, beam) cuda tensors; ``length_penalty`` None sorts on the score."""
+        self._chk(self.L.cn_nat_lm_finish(self.handle, C.byref(opts), int(ymax), int(beam_width), float(lm_weight),
+                                          int(length_penalty is not None), float(length_penalty or 0.0), int(bool(zero_past_len)),
+                                          _ptr(hyp), hyp.shape[2], _ptr(hyp_len), _ptr(score), current_stream()), "cn_nat_lm_finish")
+
     def lm_step_begin(self, max_len, max_slots):
         self._chk(self.L.cn_lm_step_begin(self.handle, int(max_len), int(max_slots)), "cn_lm_step_begin")
 
@@ -535,6 +556,13 @@ class Engine:
         buf = C.create_string_buffer(1 << 16)
         self._chk(self.L.cn_profile_end(self.handle, buf, len(buf)), "cn_profile_end")
         return json.loads(buf.value.decode())
+
+    def shape(self, name):
+        """Shape of a tensor ``fetch`` would return, without copying it (``shape("tok")[1]``: the row count of the last pass)."""
+        shape = (C.c_int64 * 4)()
+        ndim, dtype = C.c_int32(), C.c_int32()
+        self._chk(self.L.cn_fetch(self.handle, name.encode(), None, 0, shape, C.byref(ndim), C.byref(dtype)), f"shape {name}")
+        return tuple(shape[i] for i in range(ndim.value))
 
     def fetch(self, name):
         shape = (C.c_int64 * 4)()

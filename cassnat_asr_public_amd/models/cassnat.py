@@ -368,8 +368,15 @@ class CassNAT(nn.Module):
         if dtype == "ctc_att" and getattr(args, "sample_num", 0) > 1:
             raise NotImplementedError("ctc_att with sample_num > 1 (the n best CTC hypotheses ranked by a language model) needs the "
                                       "in-loop LM fusion of ctc_beam_decode, which is outside the accelerated path")
-        if getattr(args, "lm_weight", 0) > 0 and lm_model is not None:
-            raise NotImplementedError("LM shallow fusion in the finish loop is outside the accelerated path")
+        if getattr(args, "lm_weight", 0) > 0:
+            # LM shallow fusion in the finish loop (src/models/cassnat.py:600-607): the loop runs on the device (_lm_finish)
+            if lm_model is None:
+                raise ValueError("beam_decode: lm_weight > 0 needs lm_model (a models.lm.TransformerLM)")
+            if not hasattr(lm_model, "step_engine") or (getattr(args, "sample_num", 0) > 1 and getattr(args, "rank_model", "lm") != "lm"):
+                raise NotImplementedError("lm_weight > 0 fuses a models.lm.TransformerLM; with rank_model 'at_baseline' / 'n-gram' the "
+                                          "reference calls lm_model(ys, mask) on the ranker and fails")
+            if not 1 <= int(args.beam_width) <= 16:
+                raise NotImplementedError("lm_weight > 0: beam_width must be in [1, 16]")
         if getattr(args, "sample_num", 0) > 1:
             rank = getattr(args, "rank_model", "lm")
             ok = (lm_model is not None and ((rank == "lm" and hasattr(lm_model, "score_tokens")) or
@@ -405,6 +412,8 @@ class CassNAT(nn.Module):
         eng = engine if engine is not None else self.engine(B, T)
         opts = hip.Engine.make_opts(args, capture=getattr(args, "hip_capture", False))
         opts.sos = sos
+        if getattr(args, "lm_weight", 0) > 0:  # the fused finish reads the pass's full rows; the per-row top-k tables are not its input
+            opts.reserved[0], opts.beam_width = 1, 1
         opts.sub_batch = int(sub_batch)  # coalesced batches of that size each (pipeline.DecodePipelines): per-batch hypotheses
         stride = ((T - 1) // 2 + 1 - 1) // 2 + 1 + 2
         hyp = torch.empty(B, stride, dtype=torch.int32, device=dev)
@@ -419,7 +428,9 @@ class CassNAT(nn.Module):
     def beam_decode(self, src, x_mask, src_size, vocab, args, lm_model=None, ctc_top_seqs=None, labels=None,
                     label_sizes=None):
         """Same contract as the reference's CassNAT.beam_decode (src/models/cassnat.py:420-637) for
-        ``use_trigger=True, sample_num<=1, decode_type='att_only', lm_weight==0`` (anything else raises).
+        ``decode_type`` 'att_only' / 'ctc_att', ``sample_num`` > 1 (ESA) and ``use_trigger=False``; ``lm_weight > 0`` with a
+        ``models.lm.TransformerLM`` as ``lm_model`` runs the finish loop with LM shallow fusion on the device (``_lm_finish``).
+        Anything else raises.
 
         ``x_mask`` is accepted for signature compatibility; like the reference's caller
         (src/tasks/cassnat_task.py:328) the padding mask is ``src[:,:,0] != padding_idx`` and is re-derived on
@@ -437,6 +448,12 @@ class CassNAT(nn.Module):
             hyp, hyp_len, score = self._decode_forced(src, src_size, args, sos, ctc_top_seqs)
         else:
             hyp, hyp_len, score = self.decode_device(src, src_size, args, sos)
+        if getattr(args, "lm_weight", 0) > 0:
+            eng = self._engine
+            opts = hip.Engine.make_opts(args)
+            opts.sos = sos
+            out = self._lm_finish(eng, opts, args, lm_model, src.shape[0], eng.shape("tok")[1], False)
+            return out, args
         if args.beam_width > 1:
             out = self._host_beam(self._engine, args, sos)
             self._range_ok()
@@ -470,6 +487,8 @@ class CassNAT(nn.Module):
         eng = self.engine(B, T)
         opts = hip.Engine.make_opts(args, capture=getattr(args, "hip_capture", False))
         opts.sos = sos
+        if getattr(args, "lm_weight", 0) > 0:  # (as decode_device)
+            opts.reserved[0], opts.beam_width = 1, 1
         hyp = torch.empty(B, Tp + 2, dtype=torch.int32, device=dev)
         hyp_len = torch.empty(B, dtype=torch.int32, device=dev)
         score = torch.empty(B, dtype=torch.float64, device=dev)
@@ -547,6 +566,15 @@ class CassNAT(nn.Module):
         ylen_sel = ylen_h.gather(1, pick).squeeze(1).numpy()
         ymax = int(ylen_sel.max())
         ys = torch.ones(1, 1).fill_(sos).long()
+        if getattr(args, "lm_weight", 0) > 0:
+            # the finish loop fuses the ranker itself (the reference passes one lm_model to both): one more decoder pass over the
+            # selected alignments keeps their rows (as _esa_beam_finish), rows at or past a sample's own count read as zero (:536)
+            sel = select.gather(0, pick.reshape(1, B, 1).expand(1, B, select.shape[2]).to(select.device)).contiguous()
+            opts.reserved[0] = 1  # (beam_width stays 1: the rows are what the finish reads, not a top-k table)
+            one = [torch.zeros(1, B, stride, dtype=t, device=dev) for t in (torch.int32, torch.float32)]
+            eng.esa_sample(sel, args.threshold, ratio, opts, one[0], one[1], torch.zeros(1, B, dtype=torch.int32, device=dev), force_U=force)
+            opts.reserved[0] = 0
+            return self._lm_finish(eng, opts, args, lm_model, B, ymax, True)
         if bw > 1:
             return self._esa_beam_finish(eng, select, pick, args, ratio, opts, bw, force, ylen_sel, ymax, sos)
         out = []
@@ -590,6 +618,35 @@ class CassNAT(nn.Module):
                 else:
                     cand.sort(key=lambda s: s["score"], reverse=True)
                 beams = cand[:bw]
+            out.append(beams)
+        return out
+
+    def _lm_finish(self, eng, opts, args, lm_model, B, ymax, zero_past_len):
+        """The finish loop with LM shallow fusion (src/models/cassnat.py:574-637, lm_weight > 0) on the device, after a pass of
+        ``eng`` that kept its log-probability rows: per step the TransformerLM's incremental step on every beam slot, the fused
+        row top-k and the beam update (``cn_nat_lm_finish``).  Returns the reference's records, ``'ys'`` grown with the hypothesis."""
+        bw = int(args.beam_width)
+        dev = torch.device("cuda", getattr(self, "_device", torch.cuda.current_device()))
+        lm_eng = lm_model.step_engine(B * bw)
+        lm_eng.lm_step_begin(ymax + 1, B * bw)
+        hyp = torch.empty(B, bw, ymax + 1, dtype=torch.int32, device=dev)
+        hyp_len = torch.empty(B, bw, dtype=torch.int32, device=dev)
+        score = torch.empty(B, bw, dtype=torch.float64, device=dev)
+        eng.nat_attach_lm(lm_eng)
+        try:
+            eng.nat_lm_finish(opts, ymax, bw, args.lm_weight, args.length_penalty, zero_past_len, hyp, hyp_len, score)
+            hyp_h, len_h, score_h = hyp.cpu().numpy(), hyp_len.cpu().numpy(), score.cpu().numpy()
+        finally:
+            eng.nat_attach_lm(None)  # (the LM model may rebuild its engine before the next call)
+        self._range_ok()
+        if "fp16" in (self.hip_precision, lm_model.hip_precision):
+            hip.check_fp16_range(score_h, "beam_decode")
+        out = []
+        for b in range(B):
+            beams = []
+            for j in range(bw):
+                h = hyp_h[b, j, : len_h[b, j]].tolist()
+                beams.append({"ys": torch.tensor([h], dtype=torch.long), "score": float(score_h[b, j]), "hyp": h})
             out.append(beams)
         return out
 

@@ -122,13 +122,15 @@ class CassNATTask(BaseTask):
     def load_lm_model(self, args):
         """src/tasks/cassnat_task.py:85-125: the model that ranks ESA samples - a TransformerLM (rank_model 'lm'), the
         autoregressive baseline (rank_model 'at_baseline': models.transformer, scoring teacher-forced) or a kenlm n-gram model
-        (rank_model 'n-gram', scored on the host as the reference does).  LM shallow fusion (lm_weight > 0) is outside the
-        accelerated path."""
+        (rank_model 'n-gram', scored on the host as the reference does).  ``lm_weight > 0`` loads the same way (:86): the
+        TransformerLM that the finish loop fuses (models.cassnat.CassNAT._lm_finish), which needs rank_model 'lm' - the reference
+        calls lm_model(ys, mask) on whatever it loaded and fails on the other two."""
         self.lm_model = None
-        if args.lm_weight > 0:
-            raise NotImplementedError("LM shallow fusion (lm_weight > 0) is outside the accelerated path")
-        if getattr(args, "ctc_lm_weight", 0) > 0:
-            rank = getattr(args, "rank_model", "lm")
+        rank = getattr(args, "rank_model", "lm")
+        if args.lm_weight > 0 and rank != "lm":
+            raise NotImplementedError("lm_weight > 0 needs rank_model 'lm': the finish loop fuses a TransformerLM (the reference "
+                                      "fails on rank_model '%s' there)" % rank)
+        if args.lm_weight > 0 or getattr(args, "ctc_lm_weight", 0) > 0:
             if rank == "n-gram":
                 import kenlm  # (not a dependency of this package: needed for this ranker only, as in the reference)
 
@@ -167,15 +169,18 @@ class CassNATTask(BaseTask):
     def _decode_plain(self, args, results, batch_time, progress):
         """The reference's loop (src/tasks/cassnat_task.py:317-356): one beam_decode call per batch."""
         frames, i, end = 0, -1, time.time()
+        # the reference's ctc_beam_decode reads its lm_model only when ctc_lm_weight > 0 (src/utils/beam_decode.py); the LM that
+        # lm_weight > 0 loaded is for the finish loop of beam_decode alone
+        ctc_lm = self.lm_model if getattr(args, "ctc_lm_weight", 0) > 0 else None
         with torch.no_grad():
             self.model.eval()
             for i, (utt_list, feats, labels, feat_sizes, label_sizes) in enumerate(self.test_loader):
                 frames += int(feats.shape[0] * feats.shape[1])
                 src_mask = (feats[:, :, 0] != args.padding_idx).unsqueeze(1)
                 if args.decode_type == "ctc_only":  # src/tasks/cassnat_task.py:335-336
-                    recog = ctc_beam_decode(self.model, feats, src_mask, feat_sizes, self.vocab, args, self.lm_model)
+                    recog = ctc_beam_decode(self.model, feats, src_mask, feat_sizes, self.vocab, args, ctc_lm)
                 elif args.decode_type == "ctc_att":  # :338-340
-                    top = ctc_beam_decode(self.model, feats, src_mask, feat_sizes, self.vocab, args, self.lm_model)
+                    top = ctc_beam_decode(self.model, feats, src_mask, feat_sizes, self.vocab, args, ctc_lm)
                     recog, args = self.model.beam_decode(feats, src_mask, feat_sizes, self.vocab, args, self.lm_model, top,
                                                          labels=labels, label_sizes=label_sizes)
                 else:
@@ -296,10 +301,11 @@ class CassNATTask(BaseTask):
         batch_time = util.AverageMeter("Time", ":6.3f")
         progress = util.ProgressMeter(len(self.test_loader), batch_time)
         results = {}
-        # args.hip_pipelines (default 2; 1 = the plain loop): beam search, ESA and capture runs keep the plain loop
+        # args.hip_pipelines (default 2; 1 = the plain loop): beam search, ESA, LM fusion and capture runs keep the plain loop
+        # (beam_width 1 with lm_weight > 0 is not the greedy finish: every step takes the arg-max of the FUSED row)
         n_pipes = int(getattr(args, "hip_pipelines", 2))
         plain_greedy = (args.beam_width == 1 and getattr(args, "sample_num", 0) <= 1 and not getattr(args, "hip_capture", False)
-                        and args.decode_type == "att_only")
+                        and args.decode_type == "att_only" and not getattr(args, "lm_weight", 0) > 0)
         # Both branches issue the same collectives (one weight broadcast; the result gather below), and the choice is made from
         # rank-invariant data: the snake deal can leave ranks with batch counts that differ by one.
         n_batches = len(self.test_loader)

@@ -87,7 +87,8 @@ typedef struct cn_decode_opts {
                            Transformer blocks only (a conformer's GroupNorm sees the padded rows) */
     int32_t no_trigger; /* args.use_trigger == False (src/models/cassnat.py:469-473): the extractor attends over every valid frame
                            (trigger_mask = src_mask) and the row counts are best_path_align's own (no EOS row).  0 = use_trigger */
-    int32_t reserved[6];
+    int32_t reserved[6]; /* reserved[0] != 0: keep the decoder's full log-probability rows of the pass at any beam_width (what
+                            cn_nat_lm_finish reads; beam_width 1 otherwise keeps the arg-max alone).  The others must be 0 */
 } cn_decode_opts;
 
 const char* cn_last_error(void);
@@ -223,6 +224,27 @@ typedef struct cn_ast_opts {
 int cn_decode_ast(cn_model* m, const float* feats_dev, int32_t B, int32_t T, int32_t F, const cn_decode_opts* opts,
                   const cn_ast_opts* ast_opts, int32_t* hyp_out_dev, int32_t max_len, int32_t* hyp_len_dev, double* score_dev,
                   void* stream);
+
+/* ---- CASS-NAT + LM: the finish loop of CassNAT.beam_decode with args.lm_weight > 0 (src/models/cassnat.py:574-637) on the device.
+ * cn_nat_attach_lm: `lm` (a finalized TransformerLM handle, cfg.ast = 2, same vocabulary, device and library; its own precision,
+ * loaded as src/tasks/cassnat_task.py:85-127 loads it) is the lm_model of the finish loop of `nat` (cfg.ast = 0).  NULL detaches.
+ * The LM handle must stay alive while attached; its workspace must hold B * beam_width slots, its position table max_len.
+ * cn_nat_lm_finish runs the loop (:580-636) after a cn_decode_nast / cn_decode_nast_forced / cn_esa_sample pass of one alignment
+ * per utterance that kept its log-probability rows (opts->reserved[0] != 0, or beam_width > 1; a plain pass: not
+ * cn_decode_nast_merged with sub-batches or u_hint, not opts->sub_batch > 0 - those are refused): for i < ymax every live hypothesis
+ * of an utterance with i <= ylen[b] takes row att_out[b][i] + fl32(lm_weight * lm_model(ys, (ys != padding_idx) & subsequent_mask)
+ * [:, -1]) (float32, one rounding per operation), its beam_width best continuations (ties: lower index), and the utterance keeps
+ * the beam_width best of them by score + (len(hyp) - 1) * length_penalty (double; the score alone when use_length_penalty == 0;
+ * ties in list order).  The LM runs one incremental step per i on every slot b * beam_width + j (keys / values of earlier
+ * positions from its cache); nothing returns to the host inside the loop.  ymax: the reference's ymax (<= the rows of the pass;
+ * ESA: the largest ylen of the selected samples).  zero_past_len != 0: rows i >= ylen[b] read as all-zero (ESA, :536).
+ * 1 <= beam_width <= 16; beam_width 1 takes the arg-max of the fused row (not the greedy path of cn_decode_nast).
+ * hyp_out_dev [B][beam_width][max_len] int32 (sos first, padded with padding_idx; max_len >= ymax + 1), hyp_len_dev [B][beam_width],
+ * score_dev [B][beam_width] double; beams best first. */
+int cn_nat_attach_lm(cn_model* nat, cn_model* lm);
+int cn_nat_lm_finish(cn_model* m, const cn_decode_opts* opts, int32_t ymax, int32_t beam_width, float lm_weight,
+                     int32_t use_length_penalty, double length_penalty, int32_t zero_past_len, int32_t* hyp_out_dev, int32_t max_len,
+                     int32_t* hyp_len_dev, double* score_dev, void* stream);
 
 /* ---- ESA: error-based sampling of alignments + TransformerLM ranking (src/models/cassnat.py:370-376, 441-445, 499-561) --
  * cn_esa_begin: encoder + CTC generator once; the two best labels of every frame are kept.
@@ -545,6 +567,19 @@ int cn_op_ast_beam_update(int32_t* tok0, int32_t* tok1, int32_t* anc0, int32_t* 
                           int32_t K, int32_t L, int32_t eos, int32_t sos, int32_t pad, int32_t use_ctc, int32_t use_lp, int32_t use_lm,
                           float w, float u, float lw, double lp, int32_t B, void* stream);
 
+/* The two kernels of cn_nat_lm_finish one at a time.  cn_op_nat_lm_fuse_topk: slot s = b * bw + j of B * bw slots takes
+ * att [B][U][V] row (b, step) - log-probabilities, NOT normalised again; all zero when zlen && step >= zlen[b] - plus
+ * fl32(w * log_softmax(lm [B * bw][V] row s)) and writes its k best (1 <= k <= min(32, V), V <= 8192; sorted descending, ties: lower
+ * index) to idx / val [B * bw][k]; slots of an utterance with step > last[b] are skipped (last / zlen [B] may be NULL).
+ * cn_op_nat_beam_update: one step of the bookkeeping (src/models/cassnat.py:613-636) on double-buffered state (S = B * bw slots
+ * of L tokens: tok / anc int32 [S][L], keyok uint8 [S][L], score double [S]; cur_tok int32 [S]): reads parity cur and the step's
+ * candidates idx / val [S][bw], writes parity cur ^ 1; one live beam per utterance at step 0, bw afterwards; an utterance with
+ * step > last[b] carries its beams.  1 <= bw <= 16, step <= L - 2. */
+int cn_op_nat_lm_fuse_topk(const float* att, const float* lm, const int32_t* last, const int32_t* zlen, int32_t B, int32_t U, int32_t V,
+                           int32_t bw, int32_t step, float w, int32_t k, int32_t* idx, float* val, void* stream);
+int cn_op_nat_beam_update(int32_t* tok0, int32_t* tok1, int32_t* anc0, int32_t* anc1, uint8_t* keyok0, uint8_t* keyok1, double* score0,
+                          double* score1, int32_t* cur_tok, const int32_t* idx, const float* val, const int32_t* last, int32_t cur,
+                          int32_t step, int32_t bw, int32_t L, int32_t pad, int32_t use_lp, double lp, int32_t B, void* stream);
 #ifdef __cplusplus
 }
 #endif
