@@ -213,6 +213,146 @@ int launch_ast_gather_attn(int prec, int mode, const GatherAttnArgs& a, hipStrea
 }
 
 // ---------------------------------------------------------------------------------------------
+// The same two kernels with a position PER ROW (ctc_lm.hip: the hypotheses of a CTC prefix beam have different lengths).
+//   embed:     x[h][:] = lut[tok[h]][:] * sqrt(d) + pe[pos[h]][:]
+//   attention: row h has pos[h] + 1 keys; key j is cache row rowid[h][j] (an absolute row of ck / cv, row length d), every key
+//              allowed (a CTC hypothesis holds no padding token).  stay[h] == 0: the row's own K | V (still in the projection
+//              buffer) are written to cache row rowid[h][pos[h]] and key pos[h] is read from the projection buffer, as MODE 0
+//              does with append_pos.  stay[h] != 0: the hypothesis did not change - its LM row is carried by the caller - so the
+//              workgroup appends nothing and writes a zero context row (rows are independent in everything downstream).
+// ---------------------------------------------------------------------------------------------
+__global__ void ast_embed_rows_kernel(const int* __restrict__ tok, const float* __restrict__ lut, const float* __restrict__ pe,
+                                      const int* __restrict__ pos, float* __restrict__ x, int n, int d, float scale, int max_pos) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n * d) return;
+    const int h = i / d, c = i - h * d;
+    const int q = pos[h] < 0 ? 0 : (pos[h] > max_pos ? max_pos : pos[h]);  // (a position outside the table reads its last row, never past it)
+    x[i] = lut[(long long)tok[h] * d + c] * scale + pe[(long long)q * d + c];
+}
+
+int launch_ast_embed_rows(const int* tok, const float* lut, const float* pe, const int* pos, float* x, int n, int d, float scale,
+                          int max_pos, hipStream_t s) {
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL(ast_embed_rows_kernel, dim3(cn_ceil_div(n * d, 256)), dim3(256), 0, s, tok, lut, pe, pos, x, n, d, scale, max_pos);
+    CN_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+struct GatherRowsParams {
+    const void* q;  // [n][ldq]: Q | K | V of the fused projection
+    int ldq;
+    void* k;
+    void* v;
+    void* o;
+    int ldo;
+    int d, table_stride, max_keys;
+    const int* rowid;  // [n][table_stride]
+    const int* pos;    // [n]
+    const int* stay;   // [n]
+    float scale;
+};
+
+template <typename T>
+__global__ void ast_gather_attn_rows_kernel(GatherRowsParams p) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int h = blockIdx.x, lane = threadIdx.x & 63, hd = threadIdx.x >> 6;
+    constexpr int ES = __is_same(T, split_t) ? 4 : (int)sizeof(T);
+    unsigned char* orow = reinterpret_cast<unsigned char*>(p.o) + ((long long)h * p.ldo + hd * 64) * ES;
+    const int apos = p.pos[h], nkeys = apos + 1;
+    if (p.stay[h] || apos < 0 || apos >= p.max_keys) {  // (a position outside the score buffer: nothing is read or written through it)
+        ga_store<T>(orow, lane, 0.f);
+        return;
+    }
+    float* sc = reinterpret_cast<float*>(smem) + (long long)hd * p.max_keys;
+    const unsigned char* qrow = reinterpret_cast<const unsigned char*>(p.q) + ((long long)h * p.ldq + hd * 64) * ES;
+    float q[64];
+#pragma unroll
+    for (int i = 0; i < 64; ++i) q[i] = ga_load<T>(qrow, i);
+    const int* ids = p.rowid + (long long)h * p.table_stride;
+    const unsigned char* new_k = qrow + (long long)p.d * ES;
+    const unsigned char* new_v = qrow + (long long)2 * p.d * ES;
+    unsigned char* kb = reinterpret_cast<unsigned char*>(p.k);
+    unsigned char* vb = reinterpret_cast<unsigned char*>(p.v);
+    {
+        const long long crow = ((long long)ids[apos] * p.d + hd * 64) * ES + lane * ES;
+        if constexpr (ES == 4) {
+            *reinterpret_cast<unsigned*>(kb + crow) = *reinterpret_cast<const unsigned*>(new_k + lane * 4);
+            *reinterpret_cast<unsigned*>(vb + crow) = *reinterpret_cast<const unsigned*>(new_v + lane * 4);
+        } else {
+            *reinterpret_cast<unsigned short*>(kb + crow) = *reinterpret_cast<const unsigned short*>(new_k + lane * 2);
+            *reinterpret_cast<unsigned short*>(vb + crow) = *reinterpret_cast<const unsigned short*>(new_v + lane * 2);
+        }
+    }
+    float lmax = -INFINITY;
+    for (int j = lane; j < nkeys; j += 64) {
+        const unsigned char* kr = j == apos ? new_k : kb + ((long long)ids[j] * p.d + hd * 64) * ES;
+        float dot = 0.f;
+#pragma unroll
+        for (int i = 0; i < 64; ++i) dot = fmaf(q[i], ga_load<T>(kr, i), dot);
+        const float s = dot * p.scale;
+        sc[j] = s;
+        lmax = fmaxf(lmax, s);
+    }
+    lmax = wave_max(lmax);
+    float lsum = 0.f;
+    for (int j = lane; j < nkeys; j += 64) {
+        const float e = expf(sc[j] - lmax);
+        sc[j] = e;
+        lsum += e;
+    }
+    lsum = wave_sum(lsum);
+    __builtin_amdgcn_wave_barrier();
+    const float inv = 1.f / lsum;
+    float acc = 0.f;
+    for (int j = 0; j < nkeys; ++j) {
+        const unsigned char* vr = j == apos ? new_v : vb + ((long long)ids[j] * p.d + hd * 64) * ES;
+        acc = fmaf(sc[j], ga_load<T>(vr, lane), acc);
+    }
+    ga_store<T>(orow, lane, acc * inv);
+}
+
+int launch_ast_gather_attn_rows(int prec, const GatherRowsArgs& a, hipStream_t s) {
+    if (a.n <= 0) return 0;
+    if (a.H < 1 || a.H > 16 || a.max_keys < 1 || a.table_stride < a.max_keys || !a.rowid || !a.pos || !a.stay) {
+        cn_set_error("ast_gather_attn_rows: need 1 <= heads <= 16, 1 <= max_keys <= table_stride and the row tables");
+        return -1;
+    }
+    GatherRowsParams p;
+    p.q = a.q;
+    p.ldq = a.ldq;
+    p.k = a.k;
+    p.v = a.v;
+    p.o = a.o;
+    p.ldo = a.ldo;
+    p.d = a.d;
+    p.table_stride = a.table_stride;
+    p.max_keys = a.max_keys;
+    p.rowid = a.rowid;
+    p.pos = a.pos;
+    p.stay = a.stay;
+    p.scale = a.scale;
+    const size_t lds = (size_t)a.H * a.max_keys * sizeof(float);
+    if (lds > 64 * 1024) {
+        cn_set_error("ast_gather_attn_rows: too many keys for the score buffer");
+        return -1;
+    }
+    const dim3 grid(a.n), block(64 * a.H);
+    if (prec == CN_PREC_F32) {
+        hipLaunchKernelGGL((ast_gather_attn_rows_kernel<float>), grid, block, lds, s, p);
+    } else if (prec == CN_PREC_X3) {
+        if (a.ldq % 32 || a.ldo % 32 || a.d % 32) {
+            cn_set_error("ast_gather_attn_rows: split-bf16 rows need strides that are multiples of 32 elements");
+            return -1;
+        }
+        hipLaunchKernelGGL((ast_gather_attn_rows_kernel<split_t>), grid, block, lds, s, p);
+    } else {
+        hipLaunchKernelGGL((ast_gather_attn_rows_kernel<bf16>), grid, block, lds, s, p);
+    }
+    CN_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
 // CTC side of joint decoding (src/models/transformer.py:135-141, src/utils/ctc_prefix.py).
 // ---------------------------------------------------------------------------------------------
 #define CN_LOGZERO (-1e10f)

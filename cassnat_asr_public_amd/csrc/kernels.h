@@ -436,6 +436,24 @@ struct GatherAttnArgs {
     int append_pos = -1;  // mode 0: >= 0 appends this step's K | V (columns d.. / 2d.. of q's rows) to the cache at that position
 };
 int launch_ast_gather_attn(int prec, int mode, const GatherAttnArgs& a, hipStream_t s);  // mode 0: cache, 1: source memory
+// the same with a position per row (ctc_lm.hip): row h has pos[h] + 1 keys, key j = cache row rowid[h][j]; rows with stay[h] != 0
+// append nothing and give a zero context row
+int launch_ast_embed_rows(const int* tok, const float* lut, const float* pe, const int* pos, float* x, int n, int d, float scale,
+                          int max_pos, hipStream_t s);
+struct GatherRowsArgs {
+    const void* q = nullptr;  // [n][ldq] fused Q | K | V projection
+    int ldq = 0;
+    void* k = nullptr;        // cache rows [rows][d]
+    void* v = nullptr;
+    void* o = nullptr;
+    int ldo = 0;
+    int n = 0, H = 0, d = 0, table_stride = 0, max_keys = 0;  // max_keys: bound of pos[h] + 1 (sizes the score buffer)
+    const int* rowid = nullptr;  // [n][table_stride]
+    const int* pos = nullptr;    // [n]
+    const int* stay = nullptr;   // [n]
+    float scale = 0.125f;
+};
+int launch_ast_gather_attn_rows(int prec, const GatherRowsArgs& a, hipStream_t s);
 int launch_ast_ctc_prepare(float* logp, const unsigned char* keymask, float* r0, int B, int Tp, int V, int blank, hipStream_t s);
 struct CtcPrefixArgs {
     const float* logp;   // [B][Tp][V] masked CTC log-posteriors
@@ -507,4 +525,49 @@ struct NatBeamStep {
 int launch_nat_beam_init(const NatBeamState& st, const int* ylen, int ymax, int* last, int* hyp_len, int B, int bw, int L, int sos,
                          int pad, hipStream_t s);
 int launch_nat_beam_update(const NatBeamState& st, const NatBeamStep& q, int B, hipStream_t s);
+// CTC prefix beam search with in-loop LM fusion (ctc_lm.hip).  S = B * ctc_beam slots; one loop iteration per processed frame.
+struct CtcLmState {
+    double* pb;     // [S] p_blk
+    double* pnb;    // [S] p_nblk
+    double* sctc;   // [S] score_ctc
+    double* slm;    // [S] score_lm
+    int* len;       // [S] labels of the hypothesis
+    int* last;      // [S] its last label (-1: empty)
+    int* nb;        // [B] kept hypotheses
+    // tables of the next LM step
+    int* tok;       // [S] input token: the last label (sos: empty hypothesis / unused slot)
+    int* pos;       // [S] its position = len
+    int* parent;    // [S] slot of the parent in the previous beam (whose LM row a "stay" hypothesis copies)
+    int* stay;      // [S] 1: the hypothesis did not change (or the slot is unused): no LM step needed
+    int* rowid[2];  // [S][Lt] LM cache row of every prefix position; iteration k reads [k & 1], the frame step writes [(k + 1) & 1]
+};
+struct CtcLmFrame {
+    const float* logp;    // [B][Tp][V] CTC log-posteriors
+    const int* top_idx;   // [B][Tp][P] pruned labels per frame, best first
+    const float* lmrow;   // [S][V] LM log-probability row of every kept hypothesis
+    const int* frames;    // [B][Tp] processed frames
+    const int* count;     // [B] their number
+    unsigned char* hist_parent;  // [B][hist_stride][W]
+    int* hist_tok;               // [B][hist_stride][W]
+    int B, Tp, V, P, W, blank, sos, iter, Lt, hist_stride;
+    double lp, lm_weight;
+};
+struct CtcLmOut {
+    int* hyp;       // [S][Lmax]
+    int* hyp_len;   // [S]
+    double* score;  // [S] score_ctc
+    double* score_lm;
+    double* p_blk;
+    double* p_nblk;
+    int* n_out;     // [B]
+    int Lmax;
+};
+int launch_ctc_lm_schedule(const float* logp, const float* size_ratio, int B, int Tp, int V, int blank, int* frames, int* count,
+                           hipStream_t s);
+int launch_ctc_lm_init(const CtcLmState& st, int B, int W, int Lt, int sos, hipStream_t s);
+int launch_ctc_lm_rows(const float* fresh, const float* prv, float* nxt, const int* parent, const int* stay, const int* count, int iter,
+                       int slots, int W, int V, hipStream_t s);
+int launch_ctc_lm_frame(const CtcLmState& st, const CtcLmFrame& a, hipStream_t s);
+int launch_ctc_lm_finish(const CtcLmState& st, const CtcLmOut& o, const int* count, const unsigned char* hist_parent, const int* hist_tok,
+                         int hist_stride, int B, int W, hipStream_t s);
 int launch_logsoftmax_temp(float* logits, int M, int V, int ldl, float temperature, int* arg, float* maxlp, hipStream_t s);

@@ -3298,13 +3298,19 @@ int lm_check_step(const cn_model* lm, int max_len, int max_slots, const char* wh
 // (transformer.py:186-191); here the keys / values of earlier positions come from the LM's own cache through the SAME ancestor
 // and key-mask tables as the decoder's.  Per layer (pre-norm encoder layer): LN, fused QKV, cached self-attention (appends this
 // position), out-proj + residual, FFN sublayer; then encoder.norm and out_generator.proj.
+// With row_pos / row_stay (the CTC prefix beam search, whose hypotheses differ in length): row h sits at position row_pos[h] <= pos,
+// anc_dev holds its cache ROW ids (one per prefix position, any row of the cache), every key is allowed (keyok_dev unused), and a
+// row with row_stay[h] != 0 appends nothing - its logits are garbage the caller discards.
 int lm_step_run(cn_model* lm, int n, int pos, const int32_t* tok_dev, const int32_t* anc_dev, const uint8_t* keyok_dev,
-                int table_stride, hipStream_t s) {
+                int table_stride, hipStream_t s, const int32_t* row_pos = nullptr, const int32_t* row_stay = nullptr) {
     const cn_config& c = lm->cfg;
     const int d = c.d_model, V = c.vocab_size, H = c.n_head;
     const float scale = 1.0f / sqrtf((float)(d / H));
     float* x = lm->x;
-    CN_TRY(launch_ast_embed(tok_dev, lm->tgt_lut, lm->pe + (size_t)pos * d, x, n, d, sqrtf((float)d), s));
+    if (row_pos)
+        CN_TRY(launch_ast_embed_rows(tok_dev, lm->tgt_lut, lm->pe, row_pos, x, n, d, sqrtf((float)d), pos, s));
+    else
+        CN_TRY(launch_ast_embed(tok_dev, lm->tgt_lut, lm->pe + (size_t)pos * d, x, n, d, sqrtf((float)d), s));
     // bf16 / d_model 256 (lm_small): the decode step's d_ff split of the fused FFN kernel, as in ast_step_run
     static const bool no_split = cn_exp_env("CASSNAT_AST_NO_FFN_SPLIT") != nullptr;
     const int dff = c.d_encff;
@@ -3335,7 +3341,26 @@ int lm_step_run(cn_model* lm, int n, int pos, const int32_t* tok_dev, const int3
         a.anc = anc_dev;
         a.keyok = keyok_dev;
         a.scale = scale;
-        {
+        if (row_pos) {
+            GatherRowsArgs r;
+            r.q = lm->qkv;
+            r.ldq = 3 * d;
+            r.k = lm->ast_ck[l];
+            r.v = lm->ast_cv[l];
+            r.o = lm->ctx;
+            r.ldo = d;
+            r.n = n;
+            r.H = H;
+            r.d = d;
+            r.table_stride = table_stride;
+            r.max_keys = pos + 1;
+            r.rowid = anc_dev;
+            r.pos = row_pos;
+            r.stay = row_stay;
+            r.scale = scale;
+            ProfScope ps(lm, "lm_cache_attention_rows", 4.0 * n * H * (pos + 1) * 64, 2.0 * n * (pos + 1) * d * lm->es, s);
+            CN_TRY(launch_ast_gather_attn_rows(lm->prec, r, s));
+        } else {
             ProfScope ps(lm, "lm_cache_attention", 4.0 * n * H * (pos + 1) * 64, 2.0 * n * (pos + 1) * d * lm->es, s);
             CN_TRY(launch_ast_gather_attn(lm->prec, 0, a, s));
         }
@@ -3638,6 +3663,33 @@ extern "C" int cn_lm_step(cn_model* lm, int32_t n, int32_t pos, const int32_t* t
     return 0;
 }
 
+// kernel-test entry of the LM step with a position per row (cn_ctc_beam_lm's): row h holds token tok_dev[h] at position
+// pos_dev[h] <= max_pos; rowid_dev [n][table_stride] names the cache row of every prefix position (any row below the
+// max_len * max_slots of cn_lm_step_begin; the caller keeps them in range - they are not read back here); rows with stay_dev[h]
+// != 0 append nothing and their output is unspecified.  logp_dev [n][V]: log_softmax of the logits, as cn_lm_step's.
+extern "C" int cn_lm_step_rows(cn_model* lm, int32_t n, int32_t max_pos, const int32_t* tok_dev, const int32_t* pos_dev,
+                               const int32_t* stay_dev, const int32_t* rowid_dev, int32_t table_stride, float* logp_dev, void* stream) {
+    if (!lm || lm->cfg.ast != 2 || lm->ast_slots == 0) {
+        cn_set_error("cn_lm_step_rows: call cn_lm_step_begin first");
+        return -1;
+    }
+    if (!tok_dev || !pos_dev || !stay_dev || !rowid_dev || !logp_dev) {
+        cn_set_error("cn_lm_step_rows: null array");
+        return -1;
+    }
+    if (n < 1 || n > lm->ast_slots || max_pos < 0 || max_pos >= lm->ast_max_len || max_pos >= lm->pe_rows || table_stride <= max_pos) {
+        cn_set_error("cn_lm_step_rows: rows / position outside the configured cache");
+        return -1;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    CN_HIP_CHECK(hipSetDevice(lm->cfg.device));
+    const int V = lm->cfg.vocab_size;
+    CN_TRY(lm_step_run(lm, n, max_pos, tok_dev, rowid_dev, nullptr, table_stride, s, pos_dev, stay_dev));
+    CN_TRY(launch_logsoftmax_argmax(lm->ast_logits, n, V, V, lm->best, lm->ctc_maxlp, 1, s));
+    CN_HIP_CHECK(hipMemcpyAsync(logp_dev, lm->ast_logits, (size_t)n * V * 4, hipMemcpyDeviceToDevice, s));
+    return 0;
+}
+
 extern "C" int cn_ast_ctc_score(cn_model* m, int32_t n, int32_t out_len, const int32_t* utt_dev, const int32_t* last_tok_dev,
                                 const int32_t* cand_dev, int32_t K, const int32_t* prev_ref_dev, int32_t parity, int32_t eos,
                                 float* score_dev, void* stream) {
@@ -3882,4 +3934,146 @@ extern "C" int cn_nat_lm_finish(cn_model* m, const cn_decode_opts* opts, int32_t
     CN_HIP_CHECK(hipMemcpyAsync(hyp_out_dev, st.tok[cur], (size_t)S * L * 4, hipMemcpyDeviceToDevice, s));
     CN_HIP_CHECK(hipMemcpyAsync(score_dev, st.score[cur], (size_t)S * 8, hipMemcpyDeviceToDevice, s));
     return 0;
+}
+
+// ---- CTC prefix beam search with the TransformerLM in the frame loop (src/utils/beam_decode.py:8-93, args.ctc_lm_weight > 0) ----
+// One iteration per processed frame: [LM step on every slot, a position per row -> log-softmax -> LM rows of the beam -> frame
+// step]; which frames an utterance processes is known from ctc_out, so the host reads the iteration count once and nothing
+// returns inside the loop (kernels and cache addressing: ctc_lm.hip).  Outputs as cn_ctc_beam plus score_lm_dev [B][beam].
+extern "C" int cn_ctc_beam_lm(cn_model* m, cn_model* lm, const float* feats_dev, const float* size_ratio_dev, int32_t B, int32_t T,
+                              int32_t F, const cn_decode_opts* opts, int32_t beam, int32_t pruning, double length_penalty,
+                              double lm_weight, int32_t* hyp_out_dev, int32_t hyp_cap, int32_t* hyp_len_dev, double* score_dev,
+                              double* score_lm_dev, double* p_blk_dev, double* p_nblk_dev, int32_t* nbeam_dev, int32_t* iterations_host,
+                              void* stream) {
+    CN_TRY(check_call(m, B, T, F));
+    if (!opts || m->cfg.ast == 2 || !m->ctc_gen.W || beam < 1 || beam > 32 || pruning < 0 || pruning > 32 || !hyp_out_dev || !hyp_len_dev ||
+        !score_dev || !score_lm_dev || !p_blk_dev || !p_nblk_dev || !nbeam_dev) {
+        cn_set_error("cn_ctc_beam_lm: needs a model with a CTC head, 1 <= ctc_beam <= 32, 0 <= ctc_pruning <= 32 and all output buffers");
+        return -1;
+    }
+    if (!lm || lm->cfg.ast != 2 || !lm->finalized) {
+        cn_set_error("cn_ctc_beam_lm: the LM handle must be a finalized TransformerLM (cfg.ast = 2)");
+        return -1;
+    }
+    if (lm->lib_tag != m->lib_tag) {
+        cn_set_error("cn_ctc_beam_lm: the two handles come from different libraries");
+        return -1;
+    }
+    if (lm->cfg.vocab_size != m->cfg.vocab_size || lm->cfg.device != m->cfg.device) {
+        cn_set_error("cn_ctc_beam_lm: the LM must have the model's vocabulary and device");
+        return -1;
+    }
+    const int V = m->cfg.vocab_size, blank = opts->padding_idx, sos = opts->sos;
+    if (!(lm_weight == lm_weight) || blank < 0 || blank >= V || sos < 0 || sos >= V || sos == blank) {
+        cn_set_error("cn_ctc_beam_lm: lm_weight must be a number; blank and sos two different ids of the vocabulary");
+        return -1;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    CN_HIP_CHECK(hipSetDevice(m->cfg.device));
+    CN_TRY(stage_encode_ctc_rows(m, feats_dev, B, T, F, opts, s));
+    const int Tp = m->Tp, M = B * Tp, W = beam, S = B * W;
+    if (hyp_cap < Tp + 1) {
+        cn_set_error("cn_ctc_beam_lm: hyp_cap must be at least T' + 1");
+        return -1;
+    }
+    // (a capture run keeps the log-posteriors the search ran on: cn_fetch "ctc_out", as after cn_decode_nast_forced)
+    if (opts->capture) CN_TRY(capture(m, "ctc_out", m->logits, false, CN_DTYPE_F32, {B, Tp, V}, s));
+    void *top_idx = nullptr, *top_val = nullptr, *p = nullptr;
+    const int P = pruning > 0 ? pruning : 1;
+    CN_TRY(scratch_buf(m, "cb_top_idx", (size_t)M * P * 4, &top_idx));
+    CN_TRY(scratch_buf(m, "cb_top_val", (size_t)M * P * 4, &top_val));
+    if (pruning > 0) {
+        ProfScope ps(m, "ctc_topk", 0, (double)M * V * 4, s);
+        CN_TRY(launch_topk(m->logits, M, V, V, pruning, (int*)top_idx, (float*)top_val, s));
+    }
+    int *frames = nullptr, *count = nullptr;
+    CN_TRY(scratch_buf(m, "cl_frames", (size_t)M * 4, (void**)&frames));
+    CN_TRY(scratch_buf(m, "cl_count", (size_t)B * 4, (void**)&count));
+    CN_TRY(launch_ctc_lm_schedule(m->logits, size_ratio_dev, B, Tp, V, blank, frames, count, s));
+    // the one host read: the iteration count (the passes sync once for their row count too)
+    std::vector<int> hcount(B);
+    CN_HIP_CHECK(hipMemcpyAsync(hcount.data(), count, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    CN_HIP_CHECK(hipStreamSynchronize(s));
+    const int K = *std::max_element(hcount.begin(), hcount.end());
+    if (iterations_host) *iterations_host = K;
+    // a hypothesis gains at most one label per iteration: prefixes reach K + 1 tokens, LM positions K; K * S cache rows per layer
+    const int Lt = K + 2;
+    if (lm_check_step(lm, K + 1, S, "cn_ctc_beam_lm") != 0) {
+        cn_set_error("cn_ctc_beam_lm: the LM handle is too small: " + std::to_string(S) + " beam slots (B x ctc_beam) need max_batch x "
+                     "(max_frames / 4 + 1) >= " + std::to_string(S) + " (have " + std::to_string((size_t)lm->maxB * (lm->maxTp + 1)) +
+                     "), " + std::to_string(K) + " processed frames need a position table of " + std::to_string(K + 1) + " rows (have " +
+                     std::to_string(lm->pe_rows) + ")");
+        return -1;
+    }
+    CN_TRY(lm_prepare_buffers(lm, K + 1, S));
+    CtcLmState st;
+    CN_TRY(scratch_buf(m, "cl_pb", (size_t)S * 8, &p));
+    st.pb = (double*)p;
+    CN_TRY(scratch_buf(m, "cl_pnb", (size_t)S * 8, &p));
+    st.pnb = (double*)p;
+    CN_TRY(scratch_buf(m, "cl_sctc", (size_t)S * 8, &p));
+    st.sctc = (double*)p;
+    CN_TRY(scratch_buf(m, "cl_slm", (size_t)S * 8, &p));
+    st.slm = (double*)p;
+    int** ints[] = {&st.len, &st.last, &st.tok, &st.pos, &st.parent, &st.stay};
+    const char* names[] = {"cl_len", "cl_last", "cl_tok", "cl_pos", "cl_parent", "cl_stay"};
+    for (int i = 0; i < 6; ++i) {
+        CN_TRY(scratch_buf(m, names[i], (size_t)S * 4, &p));
+        *ints[i] = (int*)p;
+    }
+    CN_TRY(scratch_buf(m, "cl_nb", (size_t)B * 4, &p));
+    st.nb = (int*)p;
+    float* lmrow[2];
+    for (int i = 0; i < 2; ++i) {
+        CN_TRY(scratch_buf(m, i ? "cl_rowid1" : "cl_rowid0", (size_t)S * Lt * 4, &p));
+        st.rowid[i] = (int*)p;
+        CN_TRY(scratch_buf(m, i ? "cl_lmrow1" : "cl_lmrow0", (size_t)S * V * 4, &p));
+        lmrow[i] = (float*)p;
+        CN_HIP_CHECK(hipMemsetAsync(p, 0, (size_t)S * V * 4, s));  // (an unused slot copies its own row: never uninitialised memory)
+    }
+    const int hs = K > 0 ? K : 1;
+    void *hpar = nullptr, *htok = nullptr;
+    CN_TRY(scratch_buf(m, "cl_hist_par", (size_t)B * hs * W, &hpar));
+    CN_TRY(scratch_buf(m, "cl_hist_tok", (size_t)B * hs * W * 4, &htok));
+    CN_TRY(launch_ctc_lm_init(st, B, W, Lt, sos, s));
+    for (int k = 0; k < K; ++k) {
+        CN_TRY(lm_step_run(lm, S, k, st.tok, st.rowid[k & 1], nullptr, Lt, s, st.pos, st.stay));
+        CN_TRY(launch_logsoftmax_argmax(lm->ast_logits, S, V, V, lm->best, lm->ctc_maxlp, 1, s));
+        {
+            ProfScope ps(m, "ctc_lm_rows", 0, 2.0 * S * V * 4, s);
+            CN_TRY(launch_ctc_lm_rows(lm->ast_logits, lmrow[(k & 1) ^ 1], lmrow[k & 1], st.parent, st.stay, count, k, S, W, V, s));
+        }
+        CtcLmFrame a;
+        a.logp = m->logits;
+        a.top_idx = (const int*)top_idx;
+        a.lmrow = lmrow[k & 1];
+        a.frames = frames;
+        a.count = count;
+        a.hist_parent = (unsigned char*)hpar;
+        a.hist_tok = (int*)htok;
+        a.B = B;
+        a.Tp = Tp;
+        a.V = V;
+        a.P = pruning;
+        a.W = W;
+        a.blank = blank;
+        a.sos = sos;
+        a.iter = k;
+        a.Lt = Lt;
+        a.hist_stride = hs;
+        a.lp = length_penalty;
+        a.lm_weight = lm_weight;
+        ProfScope ps(m, "ctc_lm_frame", 0, (double)S * (pruning + 1) * 8, s);
+        CN_TRY(launch_ctc_lm_frame(st, a, s));
+    }
+    CtcLmOut o;
+    o.hyp = hyp_out_dev;
+    o.hyp_len = hyp_len_dev;
+    o.score = score_dev;
+    o.score_lm = score_lm_dev;
+    o.p_blk = p_blk_dev;
+    o.p_nblk = p_nblk_dev;
+    o.n_out = nbeam_dev;
+    o.Lmax = hyp_cap;
+    return launch_ctc_lm_finish(st, o, count, (const unsigned char*)hpar, (const int*)htok, hs, B, W, s);
 }

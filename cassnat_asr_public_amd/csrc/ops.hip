@@ -836,6 +836,70 @@ extern "C" int cn_op_nat_beam_update(int32_t* tok0, int32_t* tok1, int32_t* anc0
     return launch_nat_beam_update(st, q, B, (hipStream_t)stream);
 }
 
+// ctc_lm.hip one kernel at a time (cn_ctc_beam_lm runs them inside its loop); every array is the caller's, on the device
+extern "C" int cn_op_ctc_lm_frame(double* pb, double* pnb, double* sctc, double* slm, int32_t* len, int32_t* last, int32_t* nb, int32_t* tok,
+                                  int32_t* pos, int32_t* parent, int32_t* stay, const int32_t* rowid_cur, int32_t* rowid_nxt,
+                                  uint8_t* hist_parent, int32_t* hist_tok, const float* logp, const int32_t* top_idx, const float* lmrow,
+                                  const int32_t* frames, const int32_t* count, int32_t B, int32_t Tp, int32_t V, int32_t W, int32_t P,
+                                  int32_t blank, int32_t sos, int32_t iter, int32_t Lt, int32_t hist_stride, double lp, double lm_weight,
+                                  void* stream) {
+    const void* all[] = {pb, pnb, sctc, slm, len, last, nb, tok, pos, parent, stay, rowid_cur, rowid_nxt, hist_parent, hist_tok, logp,
+                         top_idx, lmrow, frames, count};
+    for (const void* ptr : all)
+        if (!ptr) {
+            cn_set_error("cn_op_ctc_lm_frame: null array");
+            return -1;
+        }
+    if (B < 1 || V < 1 || sos < 0 || sos >= V) {
+        cn_set_error("cn_op_ctc_lm_frame: need B >= 1 and sos inside the vocabulary");
+        return -1;
+    }
+    CtcLmState st;
+    st.pb = pb;
+    st.pnb = pnb;
+    st.sctc = sctc;
+    st.slm = slm;
+    st.len = len;
+    st.last = last;
+    st.nb = nb;
+    st.tok = tok;
+    st.pos = pos;
+    st.parent = parent;
+    st.stay = stay;
+    st.rowid[iter & 1] = const_cast<int32_t*>(rowid_cur);
+    st.rowid[(iter & 1) ^ 1] = rowid_nxt;
+    CtcLmFrame a;
+    a.logp = logp;
+    a.top_idx = top_idx;
+    a.lmrow = lmrow;
+    a.frames = frames;
+    a.count = count;
+    a.hist_parent = hist_parent;
+    a.hist_tok = hist_tok;
+    a.B = B;
+    a.Tp = Tp;
+    a.V = V;
+    a.P = P;
+    a.W = W;
+    a.blank = blank;
+    a.sos = sos;
+    a.iter = iter;
+    a.Lt = Lt;
+    a.hist_stride = hist_stride;
+    a.lp = lp;
+    a.lm_weight = lm_weight;
+    return launch_ctc_lm_frame(st, a, (hipStream_t)stream);
+}
+
+extern "C" int cn_op_ctc_lm_rows(const float* fresh, const float* prv, float* nxt, const int32_t* parent, const int32_t* stay,
+                                 const int32_t* count, int32_t iter, int32_t slots, int32_t W, int32_t V, void* stream) {
+    if (!fresh || !prv || !nxt || !parent || !stay) {
+        cn_set_error("cn_op_ctc_lm_rows: null array");
+        return -1;
+    }
+    return launch_ctc_lm_rows(fresh, prv, nxt, parent, stay, count, iter, slots, W, V, (hipStream_t)stream);
+}
+
 extern "C" int cn_op_ffn_fused(float* x_dev, const float* ln_a_dev, const float* ln_b_dev, const float* w1_host,
                                const float* b1_dev, const float* w2_host, const float* b2_dev, const float* nln_a_dev,
                                const float* nln_b_dev, void* xn_out_dev, int32_t M, int32_t dff, float eps,

@@ -203,6 +203,13 @@ def lib(flavour=None):
     L.cn_op_nat_beam_update.argtypes = [C.c_void_p] * 12 + [C.c_int32] * 6 + [C.c_double, C.c_int32, C.c_void_p]
     L.cn_lm_step_begin.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
     L.cn_lm_step.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    L.cn_lm_step_rows.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                  C.c_void_p]
+    L.cn_ctc_beam_lm.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(CnDecodeOpts),
+                                 C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_void_p, C.c_int32] + [C.c_void_p] * 6 + \
+                                [C.POINTER(C.c_int32), C.c_void_p]
+    L.cn_op_ctc_lm_frame.argtypes = [C.c_void_p] * 20 + [C.c_int32] * 10 + [C.c_double, C.c_double, C.c_void_p]
+    L.cn_op_ctc_lm_rows.argtypes = [C.c_void_p] * 6 + [C.c_int32] * 4 + [C.c_void_p]
     L.cn_fbank_default_opts.argtypes = [C.POINTER(CnFbankOpts)]
     L.cn_fbank_default_opts.restype = None
     L.cn_fbank_num_frames.argtypes = [C.POINTER(CnFbankOpts), C.c_int32]
@@ -518,6 +525,30 @@ class Engine:
                                  float(length_penalty), _ptr(hyp), cap, _ptr(hlen), _ptr(sc), _ptr(pb), _ptr(pnb), _ptr(nb),
                                  current_stream()), "cn_ctc_beam")
         return hyp, hlen, sc, pb, pnb, nb
+
+    def ctc_beam_lm(self, lm, feats, size_ratio, opts, beam, pruning, length_penalty, lm_weight):
+        """CTC prefix beam search with the TransformerLM engine ``lm`` (same library) in the frame loop (``cn_ctc_beam_lm``) ->
+        ``ctc_beam``'s tuple with score_lm (B, beam) float64 behind score_ctc, and the loop's iteration count last."""
+        import torch
+
+        if lm is None or lm.L is not self.L:
+            raise HipError("cn_ctc_beam_lm: the LM engine comes from the other library")
+        B, T, F = feats.shape
+        cap = ((T - 1) // 2 + 1 - 1) // 2 + 1 + 1
+        dev = feats.device
+        hyp = torch.empty(B, beam, cap, dtype=torch.int32, device=dev)
+        hlen = torch.empty(B, beam, dtype=torch.int32, device=dev)
+        sc, slm, pb, pnb = (torch.empty(B, beam, dtype=torch.float64, device=dev) for _ in range(4))
+        nb = torch.empty(B, dtype=torch.int32, device=dev)
+        iters = C.c_int32()
+        self._chk(self.L.cn_ctc_beam_lm(self.handle, lm.handle, _ptr(feats), _ptr(size_ratio), B, T, F, C.byref(opts), int(beam),
+                                        int(pruning), float(length_penalty), float(lm_weight), _ptr(hyp), cap, _ptr(hlen), _ptr(sc),
+                                        _ptr(slm), _ptr(pb), _ptr(pnb), _ptr(nb), C.byref(iters), current_stream()), "cn_ctc_beam_lm")
+        return hyp, hlen, sc, slm, pb, pnb, nb, iters.value
+
+    def lm_step_rows(self, max_pos, tok, pos, stay, rowid, logp):
+        self._chk(self.L.cn_lm_step_rows(self.handle, tok.shape[0], int(max_pos), _ptr(tok), _ptr(pos), _ptr(stay), _ptr(rowid),
+                                         rowid.shape[1], _ptr(logp), current_stream()), "cn_lm_step_rows")
 
     def decode_forced(self, feats, size_ratio, opts, labels, label_len, max_label_len, hyp, hyp_len, score):
         B, T, F = feats.shape

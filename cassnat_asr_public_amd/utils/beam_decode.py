@@ -4,8 +4,12 @@ decoder to (src/tasks/cassnat_task.py:335-341).
 
 Same call and the same result - per utterance a best-first list of ``{'ys', 'p_blk', 'p_nblk', 'score_ctc', 'score_lm',
 'hyp'}`` (``hyp`` without sos) - but the encoder, the CTC generator, the per-frame pruning and the whole frame loop run on
-the device (``cn_ctc_beam``; csrc/ctc_beam.hip).  The in-loop language-model fusion of the reference (which its own comment
-calls "not applicable temporarily") is outside the accelerated path: ``lm_model`` must be None.
+the device (``cn_ctc_beam``; csrc/ctc_beam.hip).
+
+With ``lm_model`` a ``models.lm.TransformerLM`` and ``args.ctc_lm_weight > 0`` the reference's in-loop LM fusion runs on the
+device too (``cn_ctc_beam_lm``; csrc/ctc_lm.hip): one LM step per processed frame over all kept hypotheses, ``score_lm`` the
+reference's running sum over the pruned labels (it is not reset between the candidates of a hypothesis).  ``ctc_lm_weight == 0``
+with an LM at hand is the LM-free search (the reference runs the LM and adds zeros).  Any other ``lm_model`` object is refused.
 """
 import torch
 
@@ -17,8 +21,9 @@ logzero, logone = -1e10, 0  # src/utils/ctc_prefix.py:11-12
 def ctc_beam_decode(model, src, src_mask, src_size, vocab, args, lm_model=None, engine=None):
     """``model``: a CassNAT (src/tasks/cassnat_task.py:335-341) or the autoregressive Transformer with its CTC head
     (src/tasks/art_task.py:252-253).  ``engine``: run on this handle (a decode pipeline's) instead of the model's own."""
-    if lm_model is not None:
-        raise NotImplementedError("CTC beam search with in-loop LM fusion is outside the accelerated path (ctc_lm_weight must be 0)")
+    if lm_model is not None and not hasattr(lm_model, "step_engine"):
+        raise NotImplementedError("CTC beam search with in-loop LM fusion needs a models.lm.TransformerLM as lm_model (rank_model 'lm'); "
+                                  "%s is outside the accelerated path" % type(lm_model).__name__)
     if args.ctc_lp is None:
         raise TypeError("ctc_lp must be a number (with None the reference's sort key is a lambda and sorted() fails)")
     sos = vocab.word2index["sos"]
@@ -32,7 +37,15 @@ def ctc_beam_decode(model, src, src_mask, src_size, vocab, args, lm_model=None, 
     # so that `ctc_out` fetched after a later call of the same engine is the tensor this search ran on)
     opts = hip.Engine.make_opts(args, capture=getattr(args, "hip_capture", False))
     opts.sos = sos
-    hyp, hlen, sc, pb, pnb, nb = eng.ctc_beam(feats, ratio, opts, int(args.ctc_beam), int(args.ctc_pruning), float(args.ctc_lp))
+    lm_weight = float(getattr(args, "ctc_lm_weight", 0) or 0)
+    slm = None
+    if lm_model is not None and lm_weight != 0:
+        lm_eng = lm_model.step_engine(B * int(args.ctc_beam))  # (one LM engine kept per model, as CassNAT._lm_finish's)
+        hyp, hlen, sc, slm, pb, pnb, nb, _ = eng.ctc_beam_lm(lm_eng, feats, ratio, opts, int(args.ctc_beam), int(args.ctc_pruning),
+                                                             float(args.ctc_lp), lm_weight)
+        slm = slm.cpu().numpy()
+    else:
+        hyp, hlen, sc, pb, pnb, nb = eng.ctc_beam(feats, ratio, opts, int(args.ctc_beam), int(args.ctc_pruning), float(args.ctc_lp))
     hyp, hlen, sc, pb, pnb, nb = (t.cpu().numpy() for t in (hyp, hlen, sc, pb, pnb, nb))
     out = []
     for b in range(B):
@@ -40,6 +53,6 @@ def ctc_beam_decode(model, src, src_mask, src_size, vocab, args, lm_model=None, 
         for j in range(int(nb[b])):
             h = hyp[b, j, : hlen[b, j]].tolist()
             seqs.append({"ys": torch.tensor([[sos] + h], dtype=torch.long), "p_blk": float(pb[b, j]), "p_nblk": float(pnb[b, j]),
-                         "score_ctc": float(sc[b, j]), "score_lm": 0.0, "hyp": h})
+                         "score_ctc": float(sc[b, j]), "score_lm": float(slm[b, j]) if slm is not None else 0.0, "hyp": h})
         out.append(seqs)
     return out

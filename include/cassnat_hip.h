@@ -202,6 +202,12 @@ int cn_ast_step_lm(cn_model* m, int32_t n_live, int32_t pos, const int32_t* tok_
 int cn_lm_step_begin(cn_model* lm, int32_t max_len, int32_t max_slots);
 int cn_lm_step(cn_model* lm, int32_t n, int32_t pos, const int32_t* tok_dev, const int32_t* anc_dev, const uint8_t* keyok_dev,
                int32_t table_stride, float* logp_dev, void* stream);
+/* The LM step with a position per row (cn_ctc_beam_lm's): row h holds tok_dev[h] at position pos_dev[h] <= max_pos and reads
+ * pos_dev[h] + 1 keys, key j from cache row rowid_dev[h][j] (any row below max_len * max_slots of cn_lm_step_begin, all keys
+ * allowed); a row with stay_dev[h] == 0 writes its K / V to cache row rowid_dev[h][pos_dev[h]], one with stay_dev[h] != 0 writes
+ * nothing and its output row is unspecified.  logp_dev [n][V] as cn_lm_step. */
+int cn_lm_step_rows(cn_model* lm, int32_t n, int32_t max_pos, const int32_t* tok_dev, const int32_t* pos_dev, const int32_t* stay_dev,
+                    const int32_t* rowid_dev, int32_t table_stride, float* logp_dev, void* stream);
 
 /* The whole joint CTC / attention beam search of Transformer.beam_decode (src/models/transformer.py:122-241) on the device,
  * with LM shallow fusion when lm_weight > 0 (an LM attached with cn_ast_attach_lm; an error without one): no host round trip
@@ -277,6 +283,20 @@ int cn_ctc_beam(cn_model* m, const float* feats_dev, const float* size_ratio_dev
                 const cn_decode_opts* opts, int32_t beam, int32_t pruning, double length_penalty, int32_t* hyp_out_dev,
                 int32_t hyp_cap, int32_t* hyp_len_dev, double* score_dev, double* p_blk_dev, double* p_nblk_dev, int32_t* nbeam_dev,
                 void* stream);
+/* The same search with the TransformerLM in the frame loop (ctc_beam_decode(..., lm_model) with args.ctc_lm_weight): m a CASS-NAT
+ * or autoregressive handle with a CTC head, lm a finalized cfg.ast = 2 handle of the same library, device and vocabulary (an
+ * argument: independent of cn_nat_attach_lm / cn_ast_attach_lm).  One loop iteration per processed frame - LM step with a position
+ * per row on all B * beam slots, the LM rows of the beam, the frame step -, queued by the host without a read-back; the host reads
+ * the iteration count (the largest number of processed frames of an utterance; *iterations_host when not NULL) once before the
+ * loop.  score_lm is the reference's running sum: the j-th non-blank candidate of a hypothesis carries the parent's score_lm plus
+ * double(lm_prob[c]) * lm_weight over the non-blank pruned labels up to its own, in list order; the sort key is (score_ctc +
+ * score_lm) + length_penalty * len(hyp).  The LM's step cache takes iterations x B x beam rows per layer; the LM handle needs
+ * max_batch x (max_frames / 4 + 1) >= B x beam and a position table of iterations + 1 rows.  Outputs as cn_ctc_beam, plus
+ * score_lm_dev [B][beam].  With opts->capture the log-posteriors the search ran on are kept (cn_fetch "ctc_out"). */
+int cn_ctc_beam_lm(cn_model* m, cn_model* lm, const float* feats_dev, const float* size_ratio_dev, int32_t B, int32_t T, int32_t F,
+                   const cn_decode_opts* opts, int32_t beam, int32_t pruning, double length_penalty, double lm_weight,
+                   int32_t* hyp_out_dev, int32_t hyp_cap, int32_t* hyp_len_dev, double* score_dev, double* score_lm_dev,
+                   double* p_blk_dev, double* p_nblk_dev, int32_t* nbeam_dev, int32_t* iterations_host, void* stream);
 /* CassNAT.beam_decode for decode_type 'ctc_att' with sample_num 1 (src/models/cassnat.py:446-448): the trigger mask comes from
  * the forced (Viterbi) alignment of labels_dev [B][ld] / label_len_dev [B] (beam_path_align -> viterbi_align, :391-414,
  * 272-353) instead of the greedy path; max_label_len = the largest label_len (the width of the reference's label tensor).
@@ -580,6 +600,23 @@ int cn_op_nat_lm_fuse_topk(const float* att, const float* lm, const int32_t* las
 int cn_op_nat_beam_update(int32_t* tok0, int32_t* tok1, int32_t* anc0, int32_t* anc1, uint8_t* keyok0, uint8_t* keyok1, double* score0,
                           double* score1, int32_t* cur_tok, const int32_t* idx, const float* val, const int32_t* last, int32_t cur,
                           int32_t step, int32_t bw, int32_t L, int32_t pad, int32_t use_lp, double lp, int32_t B, void* stream);
+
+/* The kernels of cn_ctc_beam_lm's loop one at a time (ctc_lm.hip); every array is the caller's, on the device.  S = B * W slots.
+ * cn_op_ctc_lm_frame: iteration `iter` of the frame step on given log-posteriors logp [B][Tp][V], pruned labels top_idx [B][Tp][P],
+ * LM rows lmrow [S][V] and schedule frames [B][Tp] / count [B].  Beam state, updated in place: pb / pnb / sctc / slm double [S],
+ * len / last int32 [S] (last -1: empty), nb int32 [B]; LM tables written for the next step: tok / pos / parent / stay int32 [S],
+ * rowid_nxt [S][Lt] from rowid_cur [S][Lt] (the parent's ids, plus (iter + 1) * S + slot for an appended label); back-pointers
+ * hist_parent uint8 / hist_tok int32 [B][hist_stride][W] at row iter.  An utterance with iter >= count[b] only sets stay.
+ * 1 <= W <= 32, 0 <= P <= 32, Lt >= iter + 2, iter < hist_stride.
+ * cn_op_ctc_lm_rows: nxt[s] = stay[s] ? prv[parent[s]] : fresh[s] over [S][V] rows; slots of an utterance with iter >= count[b]
+ * are skipped (count may be NULL). */
+int cn_op_ctc_lm_frame(double* pb, double* pnb, double* sctc, double* slm, int32_t* len, int32_t* last, int32_t* nb, int32_t* tok,
+                       int32_t* pos, int32_t* parent, int32_t* stay, const int32_t* rowid_cur, int32_t* rowid_nxt, uint8_t* hist_parent,
+                       int32_t* hist_tok, const float* logp, const int32_t* top_idx, const float* lmrow, const int32_t* frames,
+                       const int32_t* count, int32_t B, int32_t Tp, int32_t V, int32_t W, int32_t P, int32_t blank, int32_t sos,
+                       int32_t iter, int32_t Lt, int32_t hist_stride, double lp, double lm_weight, void* stream);
+int cn_op_ctc_lm_rows(const float* fresh, const float* prv, float* nxt, const int32_t* parent, const int32_t* stay, const int32_t* count,
+                      int32_t iter, int32_t slots, int32_t W, int32_t V, void* stream);
 #ifdef __cplusplus
 }
 #endif
