@@ -49,6 +49,8 @@ struct AttnParams {
     const float* rel_u;
     const float* rel_v;
     int rel_R, ld_pos;
+    const int* row_off;  // (last: the other fields keep their offsets) packed query and, kv_packed, key rows: AttnArgs.row_off
+    int kv_packed;
 };
 
 template <typename T> struct AttnCfg;
@@ -89,7 +91,8 @@ __device__ long long attn_stamps[8];
 // (split-bf16, the staged 4-wave form - the split-bf16 engine's encoder self attention: left alone the allocator takes 300 registers
 // = one wave per SIMD = ONE 256-thread workgroup per CU, with two barriers and a global load round trip per key tile and nothing to
 // overlap them with; bounded to 256 registers two workgroups share a CU)
-template <typename T, int NW, bool RES, bool REL = false>
+// PK: packed rows (AttnArgs.row_off) - a form of its own, so that the launches without them keep their code
+template <typename T, int NW, bool RES, bool REL = false, bool PK = false>
 __global__ __launch_bounds__(64 * NW, (RES && NW == 8) ? 4 : ((__is_same(T, split_t) && NW == 4 && !REL) ? 2 : 1)) void attention_kernel(AttnParams p) {
     typedef AttnCfg<T> Cfg;
     typedef typename Frag<T>::type frag_t;
@@ -113,14 +116,21 @@ __global__ __launch_bounds__(64 * NW, (RES && NW == 8) ? 4 : ((__is_same(T, spli
     const int half = lane >> 5, l31 = lane & 31;
     const int b = blockIdx.z, h = blockIdx.y;
     AT_STAMP(0)
+    // the entry's query rows: Lq of them from row b * Lq on, or (packed) its own count from row_off[b] on - a workgroup past the
+    // count leaves before anything is requested (uniform over the workgroup)
+    const long long q0 = PK ? (long long)p.row_off[b] : (long long)b * p.Lq;
+    const int Lq = PK ? p.row_off[b + 1] - p.row_off[b] : p.Lq;
+    if constexpr (PK) {
+        if ((int)blockIdx.x * (32 * NW) >= Lq) return;
+    }
     const int q_row = blockIdx.x * (32 * NW) + wave * 32 + l31;
-    const bool wave_active = (blockIdx.x * (32 * NW) + wave * 32) < p.Lq;
-    const int qc = q_row < p.Lq ? q_row : p.Lq - 1;
+    const bool wave_active = (blockIdx.x * (32 * NW) + wave * 32) < Lq;
+    const int qc = q_row < Lq ? q_row : Lq - 1;
 
     // ---- query fragments (B operand of S^T = K.Q^T): lane holds Q[q][16-byte chunk 2s+half]
     frag_t qf[NF];
     {
-        const unsigned char* qp = p.Q + ((long long)b * p.Lq + qc) * p.ldq_b + (long long)h * KROW;
+        const unsigned char* qp = p.Q + (q0 + qc) * p.ldq_b + (long long)h * KROW;
         if constexpr (SPLIT) {
 #pragma unroll
             for (int s = 0; s < NF; ++s) {  // k-step s: group s >> 1, chunk 2 (s & 1) + half of its hi quarter; lo 64 B further
@@ -128,8 +138,17 @@ __global__ __launch_bounds__(64 * NW, (RES && NW == 8) ? 4 : ((__is_same(T, spli
                 qf[s].hi = as_frag<bf16>(ld16(c));
                 qf[s].lo = as_frag<bf16>(ld16(c + 64));
             }
+        } else if constexpr (PK) {
+            // one load per fragment whatever the layout: the address is selected, not the load
+            const long long qm = q0 + qc;
+#pragma unroll
+            for (int s = 0; s < NF; ++s) {
+                const unsigned char* src = qp + (2 * s + half) * 16;
+                src = p.q_blk ? p.Q + cn_blk16_off(qm, p.q_col + h * 64 + (2 * s + half) * 8, p.q_n) : src;
+                qf[s] = as_frag<T>(ld16(src));
+            }
         } else if (p.q_blk) {
-            const long long qm = (long long)b * p.Lq + qc;
+            const long long qm = q0 + qc;
 #pragma unroll
             for (int s = 0; s < NF; ++s) qf[s] = as_frag<T>(ld16(p.Q + cn_blk16_off(qm, p.q_col + h * 64 + (2 * s + half) * 8, p.q_n)));
         } else {
@@ -197,22 +216,28 @@ __global__ __launch_bounds__(64 * NW, (RES && NW == 8) ? 4 : ((__is_same(T, spli
     // ---- staging registers for the next K/V tile
     uint4 k_reg[ST_IT], v_reg[ST_IT];
     const int bk = p.kv_index ? p.kv_index[b] : (p.kv_mod > 0 ? b % p.kv_mod : b);
-    const int kcap = p.kcap ? p.kcap[(long long)bk * p.kcap_stride] : p.Lk;
+    // the entry's keys: Lk rows from row bk * Lk on, or (kv_packed) its own count from row_off[bk] on; rows behind its own are
+    // never loaded (they belong to the next entry or to nobody) and count as absent
+    const bool kpk = PK && p.kv_packed;
+    const long long k0 = kpk ? (long long)p.row_off[bk] : (long long)bk * p.Lk;
+    const int krows = kpk ? p.row_off[bk + 1] - p.row_off[bk] : p.Lk;
+    int kcap = p.kcap ? p.kcap[(long long)bk * p.kcap_stride] : p.Lk;
+    if (krows < kcap) kcap = krows;
     // key tiles that hold at least one key of the entry's own batch: a later tile's keys all carry probability exactly 0 (code
     // 2, -inf) - in a merged pass of ragged batches most tiles of a short utterance (round 3 still loaded and multiplied them)
     const int kvalid = kcap < p.Lk ? kcap : p.Lk;
     const int nkt = kvalid > 0 ? (kvalid + 63) / 64 : 1;
-    const unsigned char* kbase = p.K + (long long)bk * p.Lk * p.ldk_b + (long long)h * KROW;
-    const unsigned char* vbase = p.V + (long long)bk * p.Lk * p.ldv_b + (long long)h * KROW;
+    const unsigned char* kbase = p.K + k0 * p.ldk_b + (long long)h * KROW;
+    const unsigned char* vbase = p.V + k0 * p.ldv_b + (long long)h * KROW;
     auto load_tile = [&](int kt) {
 #pragma unroll
         for (int i = 0; i < ST_IT; ++i) {
             const int cidx = tid + NT * i;
             const int row = cidx / CPR, ch = cidx % CPR;
             const int key = kt * 64 + row;
-            if (key < p.Lk) {
+            if (key < krows) {
                 if (p.kv_blk) {
-                    const long long km = (long long)bk * p.Lk + key;
+                    const long long km = k0 + key;
                     k_reg[i] = ld16(p.K + cn_blk16_off(km, p.k_col + h * 64 + ch * 8, p.kv_n));
                     v_reg[i] = ld16(p.V + cn_blk16_off(km, p.v_col + h * 64 + ch * 8, p.kv_n));
                 } else {
@@ -264,11 +289,11 @@ __global__ __launch_bounds__(64 * NW, (RES && NW == 8) ? 4 : ((__is_same(T, spli
             const int kt2 = piece >> 4, is_v = (piece >> 3) & 1, j = piece & 7;
             const int row = 8 * j + r8;
             int key = kt2 * 64 + row;
-            if (key >= p.Lk) key = p.Lk - 1;  // finite filler; its probability is exactly 0 (mask code 2)
+            if (key >= krows) key = krows - 1;  // finite filler; its probability is exactly 0 (mask code 2)
             const int chunk = is_v ? (cp ^ (((row >> 1) & 1) << 2)) : (cp ^ Cfg::swz(row));
             const unsigned char* src;
             if (p.kv_blk)
-                src = (is_v ? p.V : p.K) + cn_blk16_off((long long)bk * p.Lk + key, (is_v ? p.v_col : p.k_col) + h * 64 + chunk * 8, p.kv_n);
+                src = (is_v ? p.V : p.K) + cn_blk16_off(k0 + key, (is_v ? p.v_col : p.k_col) + h * 64 + chunk * 8, p.kv_n);
             else
                 src = is_v ? vbase + (long long)key * p.ldv_b + (chunk << 4) : kbase + (long long)key * p.ldk_b + (chunk << 4);
             unsigned char* dst = (is_v ? Vs_all + kt2 * VT_BYTES : Ks_all + kt2 * KT_BYTES) + j * 1024;
@@ -501,7 +526,7 @@ __global__ __launch_bounds__(64 * NW, (RES && NW == 8) ? 4 : ((__is_same(T, spli
         // 8 consecutive channels: eight 16-byte stores (the tail is bound by store instructions, not bytes).  The swap needs all
         // 64 lanes, so it runs for rows past Lq too; only the stores are guarded.
         typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-        T* orow = reinterpret_cast<T*>(p.O) + ((long long)b * p.Lq + qc) * p.ldo + h * 64 + 8 * half;
+        T* orow = reinterpret_cast<T*>(p.O) + (q0 + qc) * p.ldo + h * 64 + 8 * half;
 #pragma unroll
         for (int d = 0; d < 2; ++d) {
 #pragma unroll
@@ -515,9 +540,9 @@ __global__ __launch_bounds__(64 * NW, (RES && NW == 8) ? 4 : ((__is_same(T, spli
                 const uint2 lo_ = __builtin_bit_cast(uint2, o0), hi_ = __builtin_bit_cast(uint2, o1);
                 const auto s0_ = __builtin_amdgcn_permlane32_swap(lo_.x, hi_.x, false, false);
                 const auto s1_ = __builtin_amdgcn_permlane32_swap(lo_.y, hi_.y, false, false);
-                if (q_row < p.Lq) {
+                if (q_row < Lq) {
                     if (p.o_blk) {  // channels h * 64 + 32 d + 16 gp + 8 half .. + 7 = k-step 4 h + 2 d + gp of the chain's B operand
-                        const long long om = (long long)b * p.Lq + q_row;
+                        const long long om = q0 + q_row;
                         unsigned char* ob = reinterpret_cast<unsigned char*>(p.O) +
                                             ((om >> 5) * (p.ldo >> 4) + (4 * h + 2 * d + gp)) * 1024 + ((half << 5) + (int)(om & 31)) * 16;
                         *reinterpret_cast<u32x4*>(ob) = u32x4{s0_[0], s1_[0], s0_[1], s1_[1]};
@@ -529,8 +554,8 @@ __global__ __launch_bounds__(64 * NW, (RES && NW == 8) ? 4 : ((__is_same(T, spli
         }
         return;
     }
-    if (q_row < p.Lq) {
-        T* orow = reinterpret_cast<T*>(p.O) + ((long long)b * p.Lq + q_row) * p.ldo + h * 64;
+    if (q_row < Lq) {
+        T* orow = reinterpret_cast<T*>(p.O) + (q0 + q_row) * p.ldo + h * 64;
 #pragma unroll
         for (int d = 0; d < 2; ++d) {
 #pragma unroll
@@ -572,6 +597,7 @@ int attention_print_stamps() {
 }
 
 template <typename T> static int run_attention(const AttnArgs& a, hipStream_t s) {
+    constexpr bool PKT = sizeof(T) == 2 && !__is_same(T, split_t);  // the packed-row forms exist for the 16-bit kernels
     AttnParams p;
     p.Q = (const unsigned char*)a.Q;
     p.K = (const unsigned char*)a.K;
@@ -605,6 +631,14 @@ template <typename T> static int run_attention(const AttnArgs& a, hipStream_t s)
         cn_set_error("attention: blocked operands exist for the bf16 kernels without relative positions; column counts % 32 == 0");
         return -1;
     }
+    p.row_off = a.row_off;
+    p.kv_packed = a.kv_packed;
+    if ((a.row_off && (a.rel_pos || sizeof(T) != 2 || __is_same(T, split_t))) ||
+        (a.kv_packed && (!a.row_off || a.kv_mod > 0 || a.kv_index || a.keymask || a.Lq != a.Lk))) {
+        cn_set_error("attention: packed rows exist for the 16-bit kernels without relative positions; packed keys are the entry's own "
+                     "rows (self attention without a key mask, kv_mod or kv_index)");
+        return -1;
+    }
     p.iv = a.intervals;
     p.iv_stride = a.iv_stride;
     p.causal = a.causal;
@@ -633,7 +667,14 @@ template <typename T> static int run_attention(const AttnArgs& a, hipStream_t s)
             // workgroups mean less CU time per launch (what counts when several decode pipelines share the GPU).
             static const int nw = cn_exp_env("CASSNAT_ATTN_NW") ? atoi(cn_exp_env("CASSNAT_ATTN_NW")) : 0;
             const int use = nw ? nw : (a.Lq > 128 ? 8 : (a.Lq > 64 ? 4 : 2));
-            if (use >= 8)
+            if (a.row_off) {
+                if (use >= 8)
+                    hipLaunchKernelGGL((attention_kernel<T, 8, true, false, PKT>), dim3(cn_ceil_div(a.Lq, 256), a.H, a.B), dim3(512), 0, s, p);
+                else if (use >= 4)
+                    hipLaunchKernelGGL((attention_kernel<T, 4, true, false, PKT>), dim3(cn_ceil_div(a.Lq, 128), a.H, a.B), dim3(256), 0, s, p);
+                else
+                    hipLaunchKernelGGL((attention_kernel<T, 2, true, false, PKT>), dim3(cn_ceil_div(a.Lq, 64), a.H, a.B), dim3(128), 0, s, p);
+            } else if (use >= 8)
                 hipLaunchKernelGGL((attention_kernel<T, 8, true>), dim3(cn_ceil_div(a.Lq, 256), a.H, a.B), dim3(512), 0, s, p);
             else if (use >= 4)
                 hipLaunchKernelGGL((attention_kernel<T, 4, true>), dim3(cn_ceil_div(a.Lq, 128), a.H, a.B), dim3(256), 0, s, p);
@@ -643,7 +684,12 @@ template <typename T> static int run_attention(const AttnArgs& a, hipStream_t s)
             return 0;
         }
     }
-    if (big_grid >= 1024)
+    if (a.row_off) {
+        if (big_grid >= 1024)
+            hipLaunchKernelGGL((attention_kernel<T, 4, false, false, PKT>), dim3(cn_ceil_div(a.Lq, 128), a.H, a.B), dim3(256), 0, s, p);
+        else
+            hipLaunchKernelGGL((attention_kernel<T, 2, false, false, PKT>), dim3(cn_ceil_div(a.Lq, 64), a.H, a.B), dim3(128), 0, s, p);
+    } else if (big_grid >= 1024)
         hipLaunchKernelGGL((attention_kernel<T, 4, false>), dim3(cn_ceil_div(a.Lq, 128), a.H, a.B), dim3(256), 0, s, p);
     else
         hipLaunchKernelGGL((attention_kernel<T, 2, false>), dim3(cn_ceil_div(a.Lq, 64), a.H, a.B), dim3(128), 0, s, p);

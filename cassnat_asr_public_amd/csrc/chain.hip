@@ -77,6 +77,7 @@ struct ChainParams {
     // F8 form (template): E8M0 scale bytes of the feed-forward products (v_mfma_scale_f32_32x32x64_f8f6f4: the product is
     // multiplied by 2^(qa - 127) 2^(qb - 127)) - W1 . LN1(x) and W2 . hidden
     const int* f8_q;  // [4]: qa1, qb1, qa2, qb2
+    const int* m_dev;  // (last: the other fields keep their offsets) null, or the device word that holds the true row count <= M (ChainArgs.m_dev)
 };
 
 #define CH_STR2(x) #x
@@ -582,15 +583,22 @@ __device__ __forceinline__ void ch_layernorm_pack8(f32x16 (&acc)[8], unsigned ta
 
 // SWISH: the feed-forward activation is x * sigmoid(x) (the conformer's macaron halves) instead of ReLU
 // F8: the two feed-forward products run on e4m3 operands (BASELINE config 5), everything else as in the bf16 form
-template <bool SWISH, bool F8>
+// DEVM: the row count comes from the device (ChainArgs.m_dev) - a form of its own, so that the other launches keep their code
+template <bool SWISH, bool F8, bool DEVM = false>
 __global__ __launch_bounds__(256) void chain_kernel(ChainParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int half = lane >> 5, l31 = lane & 31;
+    // rows of the launch: the host's count, or the device's (packed decoder rows: the host sized the grid by the capacity) - a
+    // workgroup without rows leaves here, before its first request (uniform over the workgroup: one scalar load)
+    const int M = DEVM ? *p.m_dev : p.M;
+    if constexpr (DEVM) {
+        if ((int)blockIdx.x * 128 >= M) return;
+    }
     const int m = blockIdx.x * 128 + 32 * wave + l31;
-    const int mc = m < p.M ? m : p.M - 1;
-    const bool live = m < p.M;
+    const int mc = m < M ? m : M - 1;
+    const bool live = m < M;
 #define CH_STAMP(i)                                                                              \
     if (p.stamps && (int)blockIdx.x == p.stamp_block && tid == 0) ch_stamps[i] = (long long)__builtin_amdgcn_s_memtime();
     CH_STAMP(0)
@@ -624,7 +632,7 @@ __global__ __launch_bounds__(256) void chain_kernel(ChainParams p) {
     // (accumulator layout) and ctx (B operands) are loaded and waited for (ch_load_rows): the requests travel meanwhile
     f32x4 xr[32];
     bf16x8 bop[16];
-    const int rb = blockIdx.x * 4 + wave, nrb = (p.M + 31) >> 5;  // this wave's 32-row block; blocks that hold rows
+    const int rb = blockIdx.x * 4 + wave, nrb = (M + 31) >> 5;  // this wave's 32-row block; blocks that hold rows
     {
         const uint4* ts = reinterpret_cast<const uint4*>(p.tab) + 5 * wave * 64 + lane;
 #pragma unroll
@@ -1159,6 +1167,7 @@ int launch_chain(const ChainArgs& a, hipStream_t s) {
     p.ln_out = reinterpret_cast<bf16*>(a.ln_out ? a.ln_out : (a.tail_n == 0 ? a.out : nullptr));
     p.ld_ln = a.ln_out ? a.ld_ln : a.ldo;
     p.M = a.M;
+    p.m_dev = a.m_dev;
     p.ffn_tiles = a.dff / 32;
     p.tail_tiles = a.tail_n / 32;
     p.has_next = a.has_next;
@@ -1187,9 +1196,20 @@ int launch_chain(const ChainArgs& a, hipStream_t s) {
         CN_HIP_CHECK(hipFuncSetAttribute((const void*)chain_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, CH_LDS));
         CN_HIP_CHECK(hipFuncSetAttribute((const void*)chain_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, CH_LDS));
         CN_HIP_CHECK(hipFuncSetAttribute((const void*)chain_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, CH_LDS));
+        CN_HIP_CHECK(hipFuncSetAttribute((const void*)chain_kernel<false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, CH_LDS));
+        CN_HIP_CHECK(hipFuncSetAttribute((const void*)chain_kernel<false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, CH_LDS));
         attr_once.mark(attr_dev);
     }
-    if (a.f8)
+    if (a.m_dev) {
+        if (a.swish) {
+            cn_set_error("chain: a device-side row count exists for the ReLU forms (the transformer decoder side)");
+            return -1;
+        }
+        if (a.f8)
+            hipLaunchKernelGGL((chain_kernel<false, true, true>), dim3(cn_ceil_div(p.M, 128)), dim3(256), CH_LDS, s, p);
+        else
+            hipLaunchKernelGGL((chain_kernel<false, false, true>), dim3(cn_ceil_div(p.M, 128)), dim3(256), CH_LDS, s, p);
+    } else if (a.f8)
         hipLaunchKernelGGL((chain_kernel<false, true>), dim3(cn_ceil_div(p.M, 128)), dim3(256), CH_LDS, s, p);
     else if (a.swish)
         hipLaunchKernelGGL((chain_kernel<true, false>), dim3(cn_ceil_div(p.M, 128)), dim3(256), CH_LDS, s, p);

@@ -174,7 +174,8 @@ int launch_ctc_collapse(const int* best, const unsigned char* km, int B, int Tp,
 __global__ __launch_bounds__(64) void greedy_pack_kernel(const int* __restrict__ tok, const float* __restrict__ val,
                                                          const int* __restrict__ ylen, int B, int U, int sos, int hyp_stride,
                                                          int* __restrict__ hyp, int* __restrict__ hyp_len, double* __restrict__ score, int sub,
-                                                         const UttMeta* __restrict__ utt_meta, const int* __restrict__ ymax_dev) {
+                                                         const UttMeta* __restrict__ utt_meta, const int* __restrict__ ymax_dev,
+                                                         const int* __restrict__ row_off) {
     // one wave per utterance (round 2: one THREAD per utterance - 16 to 45 us for a merged pass): the lanes share the scan over
     // the batch's row counts and the token copy; the score stays ONE sequential double sum, in row order, on lane 0 (the
     // reference accumulates a Python float row by row: any other order differs in the last bits)
@@ -203,20 +204,82 @@ __global__ __launch_bounds__(64) void greedy_pack_kernel(const int* __restrict__
     if (n > ulim) n = ulim;
     if (n > hyp_stride - 1) n = hyp_stride - 1;
     int* h = hyp + (long long)b * hyp_stride;
-    for (int i = lane; i < hyp_stride; i += 64) h[i] = i == 0 ? sos : (i <= n ? tok[(long long)b * U + i - 1] : 0);
+    const long long r0 = row_off ? (long long)row_off[b] : (long long)b * U;  // (packed rows: launch_row_plan's offsets)
+    for (int i = lane; i < hyp_stride; i += 64) h[i] = i == 0 ? sos : (i <= n ? tok[r0 + i - 1] : 0);
     if (lane == 0) {
         double sc = 0.0;
-        for (int i = 0; i < n; ++i) sc = sc + (double)val[(long long)b * U + i];
+        for (int i = 0; i < n; ++i) sc = sc + (double)val[r0 + i];
         hyp_len[b] = n + 1;
         score[b] = sc;
     }
 }
 
 int launch_greedy_pack(const int* tok, const float* val, const int* ylen, int B, int U, int sos, int hyp_stride,
-                       int* hyp, int* hyp_len, double* score, hipStream_t s, int sub, const UttMeta* utt_meta, const int* ymax_dev) {
+                       int* hyp, int* hyp_len, double* score, hipStream_t s, int sub, const UttMeta* utt_meta, const int* ymax_dev,
+                       const int* row_off) {
     if (B <= 0) return 0;
     hipLaunchKernelGGL(greedy_pack_kernel, dim3(B), dim3(64), 0, s, tok, val, ylen, B, U, sos,
-                       hyp_stride, hyp, hyp_len, score, sub, utt_meta, ymax_dev);
+                       hyp_stride, hyp, hyp_len, score, sub, utt_meta, ymax_dev, row_off);
+    CN_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// Row plan of a packed decoder side: the rows greedy_pack_kernel reads of every utterance (the SAME limit rule - keep the two in
+// step) and their exclusive prefix sum.  One workgroup: the scan over the utterances is serial in 256-wide chunks.
+__global__ __launch_bounds__(256) void row_plan_kernel(const int* __restrict__ ylen, int B, int U, int hyp_stride, int sub,
+                                                       const UttMeta* __restrict__ utt_meta, const int* __restrict__ ymax_dev,
+                                                       int* __restrict__ row_off) {
+    __shared__ int s_scan[256];
+    __shared__ int s_carry;
+    const int tid = threadIdx.x;
+    int ulim0 = U;
+    if (ymax_dev && *ymax_dev < ulim0) ulim0 = *ymax_dev;
+    if (tid == 0) s_carry = 0;
+    __syncthreads();
+    for (int base = 0; base < B; base += 256) {
+        const int b = base + tid;
+        int n = 0;
+        if (b < B) {
+            int ulim = ulim0;
+            if (utt_meta || (sub > 0 && sub < B)) {
+                int b0, b1;
+                if (utt_meta) {
+                    b0 = utt_meta[b].sub_lo;
+                    b1 = utt_meta[b].sub_hi;
+                } else {
+                    b0 = (b / sub) * sub;
+                    b1 = b0 + sub < B ? b0 + sub : B;
+                }
+                int um = 0;
+                for (int j = b0; j < b1; ++j) um = ylen[j] > um ? ylen[j] : um;
+                if (um < ulim) ulim = um;
+            }
+            n = ylen[b] + 1;
+            if (n > ulim) n = ulim;
+            if (n > hyp_stride - 1) n = hyp_stride - 1;
+            if (n < 0) n = 0;
+        }
+        s_scan[tid] = n;
+        __syncthreads();
+        for (int o = 1; o < 256; o <<= 1) {
+            const int v = tid >= o ? s_scan[tid - o] : 0;
+            __syncthreads();
+            s_scan[tid] += v;
+            __syncthreads();
+        }
+        const int carry = s_carry;
+        if (b < B) row_off[b] = carry + s_scan[tid] - n;
+        __syncthreads();
+        if (tid == 255) s_carry = carry + s_scan[255];
+        __syncthreads();
+    }
+    if (tid == 0) row_off[B] = s_carry;
+}
+
+int launch_row_plan(const int* ylen, int B, int U, int hyp_stride, int sub, const UttMeta* utt_meta, const int* ymax_dev, int* row_off,
+                    hipStream_t s) {
+    if (B <= 0) return 0;
+    hipLaunchKernelGGL(row_plan_kernel, dim3(1), dim3(256), 0, s, ylen, B, U, hyp_stride, sub, utt_meta, ymax_dev, row_off);
     CN_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -25,6 +25,7 @@ struct GenmaxParams {
     int* arg;           // [M]
     float* maxlp;       // [M]
     int M, V, vtw;      // vtw = vocabulary tiles per wave (even)
+    const int* m_dev;   // null, or the device word with the true row count <= M (GenmaxArgs.m_dev)
     // GATHER variant (language-model scoring): instead of the arg-max, the log-probability of a given target per row:
     // row m = b * tgt_U + u reads tgt[b * tgt_ld + u] and writes tgt_lp[b * tgt_ld + u]
     const int* tgt;
@@ -64,7 +65,7 @@ _Pragma("unroll") \
         } \
     } \
     __syncthreads(); \
-    if (tid < BM && m0 + tid < p.M) { \
+    if (tid < BM && m0 + tid < gM) { \
         float bm = merge[tid * 4 + 0], bs = merge[tid * 4 + 1]; \
         int bi = __float_as_int(merge[tid * 4 + 2]); \
         float bt = merge[tid * 4 + 3]; \
@@ -96,6 +97,9 @@ __global__ __launch_bounds__(256, 2) void genmax_kernel(GenmaxParams p) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int half = lane >> 5, l31 = lane & 31;
     const int m0 = blockIdx.x * BM;
+    // rows of the launch: the host's count or the device's (GenmaxArgs.m_dev); a workgroup without rows leaves before its first request
+    const int gM = p.m_dev ? *p.m_dev : p.M;
+    if (m0 >= gM) return;
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
     unsigned char* xs = smem;                                         // [MT][16 k-steps][64 lanes][16 B]: B fragments of the rows
     float* bias_s = reinterpret_cast<float*>(smem + MT * 16384);      // [4][vtw * 32]
@@ -142,7 +146,7 @@ __global__ __launch_bounds__(256, 2) void genmax_kernel(GenmaxParams p) {
         for (int i = 0; i < BM / 8; ++i) {
             const int c = tid + 256 * i, r = c >> 5, ch = c & 31;
             int m = m0 + r;
-            if (m >= p.M) m = p.M - 1;
+            if (m >= gM) m = gM - 1;
             stage[i] = ld16(reinterpret_cast<const unsigned char*>(p.h + (long long)m * 256) + 16 * ch);
         }
 #pragma unroll
@@ -172,7 +176,7 @@ __global__ __launch_bounds__(256, 2) void genmax_kernel(GenmaxParams p) {
         tv[mt] = -INFINITY;
         if constexpr (GATHER) {
             int m = m0 + 32 * mt + l31;
-            if (m >= p.M) m = p.M - 1;
+            if (m >= gM) m = gM - 1;
             tg[mt] = p.tgt[(long long)(m / p.tgt_U) * p.tgt_ld + (m % p.tgt_U)];
         }
     }
@@ -282,6 +286,9 @@ __global__ __launch_bounds__(512, 1) void genmax_x3_kernel(GenmaxParams p) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int half = lane >> 5, l31 = lane & 31;
     const int m0 = blockIdx.x * BM;
+    // rows of the launch: the host's count or the device's (GenmaxArgs.m_dev); a workgroup without rows leaves before its first request
+    const int gM = p.m_dev ? *p.m_dev : p.M;
+    if (m0 >= gM) return;
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
     unsigned char* xs = smem;                                         // [MT][16 k-steps][hi, lo][64 lanes][16 B]
     float* bias_s = reinterpret_cast<float*>(smem + MT * 32768);      // [8][vtw * 32]
@@ -309,7 +316,7 @@ __global__ __launch_bounds__(512, 1) void genmax_x3_kernel(GenmaxParams p) {
         for (int i = 0; i < BM / 8; ++i) {
             const int c = tid + 512 * i, r = c >> 6, ch = c & 63;
             int m = m0 + r;
-            if (m >= p.M) m = p.M - 1;
+            if (m >= gM) m = gM - 1;
             stage[i] = ld16(reinterpret_cast<const unsigned char*>(p.h) + (long long)m * 1024 + 16 * ch);
         }
 #pragma unroll
@@ -340,7 +347,7 @@ __global__ __launch_bounds__(512, 1) void genmax_x3_kernel(GenmaxParams p) {
         tv[mt] = -INFINITY;
         if constexpr (GATHER) {
             int m = m0 + 32 * mt + l31;
-            if (m >= p.M) m = p.M - 1;
+            if (m >= gM) m = gM - 1;
             tg[mt] = p.tgt[(long long)(m / p.tgt_U) * p.tgt_ld + (m % p.tgt_U)];
         }
     }
@@ -457,6 +464,7 @@ int launch_genmax(const GenmaxArgs& a, hipStream_t s) {
     p.arg = a.arg;
     p.maxlp = a.maxlp;
     p.M = a.M;
+    p.m_dev = a.m_dev;
     p.V = a.V;
     p.vtw = vtw;
     p.tgt = a.tgt;

@@ -97,6 +97,9 @@ int launch_keymask(const float* feats, int B, int T, int F, int Tp, int stride, 
                    hipStream_t s);
 // out[b][u][:] = table[u][:]  (extractor queries), optional shift for use_unimask handled by caller
 int launch_fill_queries(const float* table, float* out, int B, int U, int d, hipStream_t s);
+// packed decoder rows: out[row_off[b] + u][:] = table[u][:] for u < row_off[b + 1] - row_off[b]; the rows from row_off[B] to the
+// end of its 128-row block (inside the cap_rows the buffer holds) get table[0] - finite filler for the row kernels' last block
+int launch_fill_queries_packed(const float* table, float* out, const int* row_off, int B, int cap_rows, int d, hipStream_t s);
 // use_unimask: y[b][0] = 0 ; y[b][u] = x[b][u-1]
 int launch_shift_right(const float* x, float* y, int B, int U, int d, hipStream_t s);
 int launch_esa_paths(const int* top2_idx, const float* top2_val, const unsigned char* select, float threshold, int* best, int M,
@@ -135,6 +138,14 @@ struct AttnArgs {
     // (bit 3 of the channel) + row % 32][8 bf16], i.e. a blocked matrix of 64-byte-wide column tiles: byte offset of the chunk at
     // (row m, channel c) = ((m >> 5) * (ldo / 16) + (c >> 4)) * 1024 + (((c >> 3) & 1) * 32 + (m & 31)) * 16
     int o_blocked = 0;
+    // packed query rows (null: entry b owns rows b * Lq .. b * Lq + Lq - 1): entry b owns the row_off[b + 1] - row_off[b] <= Lq rows
+    // from row_off[b] on, of Q and of O alike (row-major or blocked); Lq then only sizes the grid, and waves past an entry's own
+    // count leave.  `intervals` keeps its [B][iv_stride] layout.  kv_packed (self attention; needs row_off, no kv_mod / kv_index):
+    // K / V entry b likewise holds its own count of keys at row_off[b]; keys at or past the count are absent (as keys past kcap:
+    // probability exactly 0, the same bits a masked key gives a row that has an allowed one) and are never loaded - the rows
+    // behind an entry's own belong to the next entry or to nobody
+    const int* row_off = nullptr;
+    int kv_packed = 0;
     const int* intervals = nullptr;          // [B][iv_stride][4] (s1,e1,s2,e2) per query row, or null
     int iv_stride = 0;
     int causal = 0;  // key j allowed only if j <= i
@@ -180,6 +191,11 @@ struct AlignArgs {
     int no_trigger = 0;
 };
 int launch_ctc_align(const AlignArgs& a, hipStream_t s);
+// Row plan of a packed decoder side, on the device: r[b] = the rows launch_greedy_pack reads of utterance b = min(ylen[b] + 1,
+// limit of b's own batch, hyp_stride - 1) with the limit min(U, *ymax_dev if given, largest ylen of b's batch (sub / utt_meta as
+// in launch_greedy_pack)); row_off[0 .. B] = exclusive prefix sum of r, row_off[B] the total (<= B * U)
+int launch_row_plan(const int* ylen, int B, int U, int hyp_stride, int sub, const UttMeta* utt_meta, const int* ymax_dev, int* row_off,
+                    hipStream_t s);
 // CTC greedy hypothesis compacted behind sos (Transformer.fast_decode_with_ctc's decoder input)
 int launch_ctc_collapse(const int* best, const unsigned char* km, int B, int Tp, int sos, int pad, int ld, int* tgt, int* len, int* keylen,
                         int* maxlen, hipStream_t s);
@@ -214,10 +230,11 @@ struct ViterbiArgs {
 int launch_ctc_viterbi(const ViterbiArgs& a, hipStream_t s);
 // hyp[b] = [sos] + tok[b][0 .. min(ylen[b]+1, U)) ; score = sequential double sum of val
 // sub > 0: equal-sized coalesced batches of `sub` utterances; utt_meta: the batches of a merged pass (any sizes); ymax_dev
-// (may be null): the true row count of the call when U is a prediction (hypotheses are limited by min(U, *ymax_dev))
+// (may be null): the true row count of the call when U is a prediction (hypotheses are limited by min(U, *ymax_dev));
+// row_off (may be null): packed rows - utterance b's tok / val start at row_off[b] instead of b * U (launch_row_plan)
 int launch_greedy_pack(const int* tok, const float* val, const int* ylen, int B, int U, int sos, int hyp_stride,
                        int* hyp, int* hyp_len, double* score, hipStream_t s, int sub = 0, const UttMeta* utt_meta = nullptr,
-                       const int* ymax_dev = nullptr);
+                       const int* ymax_dev = nullptr, const int* row_off = nullptr);
 // per row top-k (k <= 16) of log-probs [M][V] -> idx/val [M][k], sorted descending (ties: lower index first)
 int launch_topk(const float* logp, int M, int V, int ldl, int k, int* idx, float* val, hipStream_t s);
 // log_softmax(logits / T) and its per-row top-k in one pass (the (M, V) log-probabilities are not written)
@@ -347,6 +364,9 @@ struct ChainArgs {
     void* ln_out = nullptr;         // optional: LNn(x) itself [M][ld_ln] bf16 IN ADDITION to a tail projection
     int ld_ln = 0;
     int M = 0, d = 0, dff = 0, tail_n = 0, has_next = 0;
+    // device word (may be null): the launch's true row count <= M, known only on the device (packed decoder rows).  M then sizes
+    // the grid alone; a workgroup whose first row is at or past *m_dev leaves before its first request
+    const int* m_dev = nullptr;
     // x layout: row-major [M][256], or blocked: 32-row blocks of [32 pieces i = 4 nt + g][64 lanes][4 floats] where lane =
     // (row % 32) + 32 half holds channels 32 nt + 8 g + 4 half + (0..3) - each load/store instruction moves 1 KiB contiguous
     // (buffer must hold ceil(M / 32) * 32 rows).  store_x = 0: x is not written back (nothing reads it afterwards)
@@ -404,6 +424,7 @@ struct GenmaxArgs {
     int* arg = nullptr;
     float* maxlp = nullptr;
     int M = 0, V = 0, d = 0;
+    const int* m_dev = nullptr;  // device word (may be null): the true row count <= M (M sizes the grid; see ChainArgs.m_dev)
     // language-model scoring: tgt != null -> tgt_lp[b * tgt_ld + u] = log_softmax(W h[b * tgt_U + u] + b)[tgt[b * tgt_ld + u]]
     // (arg / maxlp unused)
     const int* tgt = nullptr;

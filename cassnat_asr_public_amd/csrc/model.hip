@@ -189,6 +189,8 @@ struct cn_model {
     std::map<std::string, size_t> ws_cap;  // bytes allocated per workspace buffer: every call is checked against it (ws_check)
     // merged engine pass (cn_decode_nast_merged): per-utterance records of the reference batches it carries
     UttMeta* utt_meta = nullptr;
+    int* row_off = nullptr;    // [utterances + 1] packed decoder rows of the current pass (launch_row_plan); row_off[B] = their total
+    bool rows_packed = false;  // the last decoder pass ran on them (tok / val are then not [B][U])
     bool ragged = false;       // the current call has them
     bool ragged_next = false;  // set by cn_decode_nast_merged right before its encoder stage
     bool u_predicted = false;  // the current call's decoder side runs on a predicted row count (>= the true one, or the ticket says so)
@@ -1265,6 +1267,7 @@ void ws_needs(const cn_model* m, const WsDims& v, WsList& out) {
     out.push_back({"src_size", v.Bu * G * 4});
     out.push_back({"ylen", v.Bu * G * 4});
     out.push_back({"utt_meta", v.Bu * sizeof(UttMeta)});
+    out.push_back({"row_off", (v.Bu * G + 1) * 4});
     out.push_back({"ymax", 256});
     out.push_back({"intervals", B * G * (Tp + 1) * 16});
     out.push_back({"tok", M * 4});
@@ -1315,6 +1318,7 @@ int build_workspace(cn_model* m) {
     m->src_size = (int*)get("src_size");
     m->ylen = (int*)get("ylen");
     m->utt_meta = (UttMeta*)get("utt_meta");
+    m->row_off = (int*)get("row_off");
     m->ymax = (int*)get("ymax");
     m->intervals = (int*)get("intervals");
     m->tok = (int*)get("tok");
@@ -1529,8 +1533,9 @@ int run_x3_chain(cn_model* m, const Layer& L, const Norm& n1, float* x, int M, c
 }
 
 // ctx <- Attn(q, k, v) on the fused [M][3d] projection buffer m->qkv
+// row_off: packed rows (AttnArgs.row_off; queries AND keys are the entry's own rows) - the decoder side of a packed pass
 int run_self_attn_core(cn_model* m, int B, int Lseq, const unsigned char* keymask, const int* klen, int causal,
-                       hipStream_t s, bool blocked = false) {
+                       hipStream_t s, bool blocked = false, const int* row_off = nullptr) {
     const int d = m->cfg.d_model, M = B * Lseq;
     AttnArgs a;
     const size_t es = m->es;
@@ -1555,6 +1560,8 @@ int run_self_attn_core(cn_model* m, int B, int Lseq, const unsigned char* keymas
     a.Lq = a.Lk = Lseq;
     a.keymask = keymask;
     a.klen = klen;
+    a.row_off = row_off;
+    a.kv_packed = row_off ? 1 : 0;
     if (m->ragged && keymask == m->keymask) {  // encoder self-attention of a merged pass
         a.kcap = &m->utt_meta[0].tp;
         a.kcap_stride = (int)(sizeof(UttMeta) / sizeof(int));
@@ -1584,7 +1591,8 @@ enum { CHX_IN_BLK = 1, CHX_OUT_BLK = 2, CHX_NO_STORE = 4 };
 // tag: the profile row of the launch ("row_chain": encoder-side, full-width launches; "row_chain_dec": the decoder side's - a
 // tenth of the rows, a quarter of the CUs: bench.py prices the two apart)
 int run_chain(cn_model* m, const ChainRef& r, float* x, int M, void* out, int ldo, bool with_next, int x_mode,
-              hipStream_t s, void* ln_out = nullptr, int ld_ln = 0, bool out_blocked = false, const char* tag = "row_chain") {
+              hipStream_t s, void* ln_out = nullptr, int ld_ln = 0, bool out_blocked = false, const char* tag = "row_chain",
+              const int* m_dev = nullptr) {
     const int d = m->cfg.d_model;
     const int tail_n = with_next ? r.tail_n : 0;
     const double macs = (r.has_wo ? (double)d * d : 0.0) + 2.0 * d * r.dff + (double)d * tail_n;
@@ -1601,6 +1609,7 @@ int run_chain(cn_model* m, const ChainRef& r, float* x, int M, void* out, int ld
     a.ln_out = ln_out;
     a.ld_ln = ld_ln;
     a.M = M;
+    a.m_dev = m_dev;  // (packed decoder rows: M is the capacity, the device word the rows that exist)
     a.d = d;
     a.dff = r.dff;
     a.tail_n = tail_n;
@@ -1761,7 +1770,8 @@ int run_conformer_self_layer(cn_model* m, const Layer& L, float* x, int B, int L
 
 int run_src_attn(cn_model* m, const Layer& L, const Norm* pre, float* x, int B, int U, int Tp, const int* intervals,
                  hipStream_t s);
-int run_src_attn_core(cn_model* m, const Layer& L, int B, int U, int Tp, const int* intervals, hipStream_t s, bool q_blocked = false);
+int run_src_attn_core(cn_model* m, const Layer& L, int B, int U, int Tp, const int* intervals, hipStream_t s, bool q_blocked = false,
+                      const int* row_off = nullptr);
 
 // A conformer layer on the row-chain kernel (chains packed by conf_layer_chains in build_weights): A -> relative-position
 // attention -> B -> GLU / depthwise conv / GroupNorm + Swish -> C [-> source attention -> D for a mixed-attention layer].
@@ -1790,7 +1800,8 @@ int run_conformer_layer_chain(cn_model* m, const Layer& L, float* x, int B, int 
 }
 
 // ctx <- Attn(m->qd, enc_h Wk, enc_h Wv) with the padding mask and (optionally) trigger intervals
-int run_src_attn_core(cn_model* m, const Layer& L, int B, int U, int Tp, const int* intervals, hipStream_t s, bool q_blocked) {
+int run_src_attn_core(cn_model* m, const Layer& L, int B, int U, int Tp, const int* intervals, hipStream_t s, bool q_blocked,
+                      const int* row_off) {
     const int d = m->cfg.d_model;
     // (B counts query sets: dec_group of them share the keys / values of one utterance)
     AttnArgs a;
@@ -1833,6 +1844,7 @@ int run_src_attn_core(cn_model* m, const Layer& L, int B, int U, int Tp, const i
     }
     a.intervals = intervals;
     a.iv_stride = Tp + 1;
+    a.row_off = row_off;  // (packed query rows; the keys are encoder frames either way)
     a.scale = 1.0f / sqrtf((float)(d / m->cfg.n_head));
     ProfScope ps(m, "src_attention", 4.0 * B * a.H * (double)U * Tp * 64,
                  ((double)B * U * 2 * d + (double)B * Tp * 2 * d) * m->es, s);
@@ -1852,7 +1864,7 @@ int run_src_attn(cn_model* m, const Layer& L, const Norm* pre, float* x, int B, 
 
 // generator tail: argmax + max log-prob per row.  Fused kernel (no logits tensor) unless full rows are needed.
 int run_generator(cn_model* m, const Linear& g, const void* h, int M, int* arg, float* maxlp, bool need_rows,
-                  hipStream_t s) {
+                  hipStream_t s, const int* m_dev = nullptr) {
     const int d = m->cfg.d_model, V = m->cfg.vocab_size;
     if (g.gm_w && !need_rows) {
         const bool x3 = m->prec == CN_PREC_X3;
@@ -1865,6 +1877,7 @@ int run_generator(cn_model* m, const Linear& g, const void* h, int M, int* arg, 
         a.arg = arg;
         a.maxlp = maxlp;
         a.M = M;
+        a.m_dev = m_dev;
         a.V = V;
         a.d = d;
         return launch_genmax(a, s);
@@ -2160,10 +2173,27 @@ int stage_decode(cn_model* m, int U, const cn_decode_opts* o, int32_t* hyp, int 
     }
     // every decoder-side buffer against B x alignments-per-utterance x rows (host-side, before anything is launched)
     CN_TRY(ws_check(m, m->B, m->T, m->dec_group, "decoder side"));
-    CN_TRY(launch_fill_queries(m->pe, m->xd, B, U, d, s));
+    const bool uni = o->use_unimask != 0;
+    // Packed decoder rows: on the greedy row-chain path every utterance owns only the rows its hypothesis reads -
+    // launch_row_plan's r[b], one utterance behind the other - instead of U rows; nothing reads the rest.  The capacity stays
+    // B x U (the grids are sized by it); the row kernels take the true count from row_off[B] on the device, the attention
+    // launches the per-utterance windows from row_off.  cn_decode_opts.reserved[1] asks for the padded layout.  (use_trigger
+    // off stays padded: an utterance without any token then has every key masked and attends uniformly over the U padded rows.)
+    static const bool no_chain_p = cn_exp_env("CASSNAT_NO_CHAIN") != nullptr;
+    const bool packed = !c.conf_dec && !m->dec_steps.empty() && !no_chain_p && hyp && !cap && !uni && o->beam_width == 1 &&
+                        o->reserved[0] == 0 && o->reserved[1] == 0 && !o->no_trigger && m->dec_group == 1;
+    m->rows_packed = packed;
+    const int* roff = packed ? m->row_off : nullptr;
+    const int* rows_dev = packed ? m->row_off + B : nullptr;
+    if (packed) {
+        CN_TRY(launch_row_plan(m->ylen, B, U, hyp_stride, o->sub_batch, m->ragged ? m->utt_meta : nullptr,
+                               m->u_predicted ? m->ymax : nullptr, m->row_off, s));
+        CN_TRY(launch_fill_queries_packed(m->pe, m->xd, m->row_off, B, MU, d, s));
+    } else {
+        CN_TRY(launch_fill_queries(m->pe, m->xd, B, U, d, s));
+    }
     // The LayerNorm that follows an FFN is produced by that FFN (-> m->xn); `pending` says whether the next
     // sublayer may skip its own LayerNorm.  use_unimask shifts the stream between SAD and MAD, so no carry there.
-    const bool uni = o->use_unimask != 0;
     auto first_norm_after = [&](int stage, size_t idx) -> const Norm* {  // stage 0 extractor, 1 SAD, 2 MAD
         if (stage == 0 && idx + 1 < m->extra.size()) return &m->extra[idx + 1].n[0];
         if (stage <= 0 && !m->sad.empty()) return &m->sad[0].n[0];
@@ -2264,13 +2294,13 @@ int stage_decode(cn_model* m, int U, const cn_decode_opts* o, int32_t* hyp, int 
                 void* out;
                 int ldo;
                 proj_out(st, out, ldo);
-                CN_TRY(run_chain(m, st.entry, xdec, MU, out, ldo, true, CHX_NO_STORE, s, nullptr, 0, blkd, "row_chain_dec"));  // reads row-major x, writes none
+                CN_TRY(run_chain(m, st.entry, xdec, MU, out, ldo, true, CHX_NO_STORE, s, nullptr, 0, blkd, "row_chain_dec", rows_dev));  // reads row-major x, writes none
             }
             if (st.self)
-                CN_TRY(run_self_attn_core(m, B, U, nullptr, m->ylen, (st.stack == 2 && uni) ? 1 : 0, s, blkd));
+                CN_TRY(run_self_attn_core(m, B, U, nullptr, m->ylen, (st.stack == 2 && uni) ? 1 : 0, s, blkd, roff));
             else
                 CN_TRY(run_src_attn_core(m, L, B, U, Tp,
-                                         st.stack == 0 ? m->intervals : (o->src_trigger ? m->intervals : nullptr), s, blkd));
+                                         st.stack == 0 ? m->intervals : (o->src_trigger ? m->intervals : nullptr), s, blkd, roff));
             const bool final = k + 1 == n;
             // use_unimask shifts the stream between the last SAD layer and the first MAD layer: nothing carries over
             const bool carry = final || !(uni && m->dec_steps[k + 1].stack == 2 && m->dec_steps[k + 1].layer == 0 &&
@@ -2283,7 +2313,7 @@ int stage_decode(cn_model* m, int U, const cn_decode_opts* o, int32_t* hyp, int 
             const bool in_rm = k == 0 || (first_mad && uni);
             const bool out_rm = !final && !carry;
             const int xm = cap ? 0 : ((in_rm ? 0 : CHX_IN_BLK) | (final ? CHX_NO_STORE : (out_rm ? 0 : CHX_OUT_BLK)));
-            CN_TRY(run_chain(m, st.chain, xdec, MU, out, ldo, carry, xm, s, nullptr, 0, blkd && !final, "row_chain_dec"));
+            CN_TRY(run_chain(m, st.chain, xdec, MU, out, ldo, carry, xm, s, nullptr, 0, blkd && !final, "row_chain_dec", rows_dev));
             if (cap && st.stack == 0 && (k + 1 == n || m->dec_steps[k + 1].stack != 0))
                 CN_TRY(capture(m, "ac_embed", m->xd, false, CN_DTYPE_F32, {B, U, d}, s));
         }
@@ -2335,7 +2365,9 @@ int stage_decode_tail(cn_model* m, int U, const cn_decode_opts* o, int32_t* hyp,
     if (cap) CN_TRY(capture(m, "dec_h", m->dec_h, true, CN_DTYPE_F32, {B, U, d}, s));
     const int k = o->beam_width;
     const bool keep_rows = o->reserved[0] != 0;  // cn_decode_opts.reserved[0]: the LM-fused finish reads the full rows at any beam width
-    CN_TRY(run_generator(m, m->att_gen, m->dec_h, MU, m->tok, m->val, cap || k > 1 || keep_rows, s));
+    // (packed rows: the fused generator takes the row count from the device; tok / val are packed as dec_h is)
+    CN_TRY(run_generator(m, m->att_gen, m->dec_h, MU, m->tok, m->val, cap || k > 1 || keep_rows, s,
+                         m->rows_packed ? m->row_off + B : nullptr));
     // (a merged / coalesced / row-predicted pass is not offered to cn_nat_lm_finish: its utterances count their rows per batch)
     const bool plain_pass = m->dec_group == 1 && !m->ragged && !m->u_predicted && o->sub_batch == 0;
     m->att_rows_U = (cap || k > 1 || keep_rows) && plain_pass ? U : 0;
@@ -2347,7 +2379,8 @@ int stage_decode_tail(cn_model* m, int U, const cn_decode_opts* o, int32_t* hyp,
     }
     if (hyp)
         CN_TRY(launch_greedy_pack(m->tok, m->val, m->ylen, B, U, o->sos, hyp_stride, hyp, hyp_len, score, s, o->sub_batch,
-                                  m->ragged ? m->utt_meta : nullptr, m->u_predicted ? m->ymax : nullptr));
+                                  m->ragged ? m->utt_meta : nullptr, m->u_predicted ? m->ymax : nullptr,
+                                  m->rows_packed ? m->row_off : nullptr));
     return 0;
 }
 
@@ -3173,6 +3206,9 @@ extern "C" int cn_fetch(cn_model* m, const char* name, void* host_dst, int64_t m
     } else if (n == "ylen") { src = m->ylen; dtype = CN_DTYPE_I32; shape = {B};
     } else if (n == "ymax") { src = m->ymax; dtype = CN_DTYPE_I32; shape = {1};
     } else if (n == "intervals") { src = m->intervals; dtype = CN_DTYPE_I32; shape = {B, Tp + 1, 4};
+    } else if ((n == "tok" || n == "val") && m->rows_packed) {
+        cn_set_error("cn_fetch: the last pass packed its decoder rows (tok / val are not [B][U]); decode with cn_decode_opts.reserved[1]");
+        return -1;
     } else if (n == "tok") { src = m->tok; dtype = CN_DTYPE_I32; shape = {B, U};
     } else if (n == "val") { src = m->val; shape = {B, U};
     } else if (n == "topk_idx") { src = m->topk_idx; dtype = CN_DTYPE_I32; shape = {B, U, m->last_k};

@@ -340,13 +340,16 @@ extern "C" int cn_op_attention(int32_t precision, const void* Q, int32_t ldq, co
     return rc;
 }
 
-extern "C" int cn_op_attention_desc(int32_t precision, const cn_attn_desc* d, void* stream) {
-    if ((precision = cn_own_precision(precision, "cn_op_attention_desc")) < 0) return -1;
+static int op_attention_desc(const char* who, int32_t precision, const cn_attn_desc* d, const int32_t* row_off, int32_t kv_packed,
+                             void* stream) {
+    if ((precision = cn_own_precision(precision, who)) < 0) return -1;
     if (!d) {
-        cn_set_error("cn_op_attention_desc: null descriptor");
+        cn_set_error(std::string(who) + ": null descriptor");
         return -1;
     }
     AttnArgs a;
+    a.row_off = row_off;
+    a.kv_packed = kv_packed;
     a.Q = d->Q;
     a.K = d->K;
     a.V = d->V;
@@ -383,6 +386,30 @@ extern "C" int cn_op_attention_desc(int32_t precision, const cn_attn_desc* d, vo
     a.rel_R = d->rel_R;
     a.ld_pos = d->ld_pos;
     return launch_attention(precision, a, (hipStream_t)stream);
+}
+
+extern "C" int cn_op_attention_desc(int32_t precision, const cn_attn_desc* d, void* stream) {
+    return op_attention_desc("cn_op_attention_desc", precision, d, nullptr, 0, stream);
+}
+
+extern "C" int cn_op_attention_packed(int32_t precision, const cn_attn_desc* d, const int32_t* row_off_dev, int32_t kv_packed,
+                                      void* stream) {
+    if (!row_off_dev) {
+        cn_set_error("cn_op_attention_packed: null row_off");
+        return -1;
+    }
+    return op_attention_desc("cn_op_attention_packed", precision, d, row_off_dev, kv_packed, stream);
+}
+
+extern "C" int cn_op_row_plan(const int32_t* ylen_dev, int32_t B, int32_t U, int32_t hyp_stride, int32_t sub, const int32_t* utt_meta_dev,
+                              const int32_t* ymax_dev, int32_t* row_off_dev, void* stream) {
+    static_assert(sizeof(UttMeta) == 4 * sizeof(int32_t), "cn_op_row_plan: utt_meta is [B][4] int32");
+    if (!ylen_dev || !row_off_dev || B < 1 || U < 0 || sub < 0) {
+        cn_set_error("cn_op_row_plan: null argument or B < 1");
+        return -1;
+    }
+    return launch_row_plan(ylen_dev, B, U, hyp_stride, sub, reinterpret_cast<const UttMeta*>(utt_meta_dev), ymax_dev, row_off_dev,
+                           (hipStream_t)stream);
 }
 
 extern "C" int32_t cn_attn_desc_size(void) { return (int32_t)sizeof(cn_attn_desc); }
@@ -1048,11 +1075,11 @@ extern "C" int cn_op_x3_chain(float* x_dev, const void* ctx_dev, const float* wo
     return sc.finish(launch_ffn_x3(a, (hipStream_t)stream));
 }
 
-extern "C" int cn_op_chain(float* x_dev, const void* ctx_dev, int32_t ldctx, const float* wo_host, const float* bo_host,
-                           const float* ln1_a_host, const float* ln1_b_host, const float* w1_host, const float* b1_host,
-                           const float* w2_host, const float* b2_host, const float* nln_a_host, const float* nln_b_host,
-                           const float* wt_host, const float* bt_host, void* out_dev, int32_t ldo, int32_t M, int32_t dff,
-                           int32_t tail_n, float eps, int32_t x_mode, void* stream) {
+static int op_chain(float* x_dev, const void* ctx_dev, int32_t ldctx, const float* wo_host, const float* bo_host,
+                    const float* ln1_a_host, const float* ln1_b_host, const float* w1_host, const float* b1_host,
+                    const float* w2_host, const float* b2_host, const float* nln_a_host, const float* nln_b_host,
+                    const float* wt_host, const float* bt_host, void* out_dev, int32_t ldo, int32_t M, int32_t dff,
+                    int32_t tail_n, float eps, int32_t x_mode, const int32_t* m_dev, void* stream) {
     if (dff < 0 || dff % 32 != 0 || dff > 2048 || tail_n < 0 || tail_n % 32 != 0 || tail_n > 1536) {
         cn_set_error("cn_op_chain: d_ff and the tail width must be multiples of 32 (<= 2048 / <= 1536)");
         return -1;
@@ -1096,6 +1123,7 @@ extern "C" int cn_op_chain(float* x_dev, const void* ctx_dev, int32_t ldctx, con
     a.out = out_dev;
     a.ldo = ldo;
     a.M = M;
+    a.m_dev = m_dev;
     a.d = 256;
     a.dff = dff;
     a.tail_n = tail_n;
@@ -1125,6 +1153,28 @@ extern "C" int cn_op_chain(float* x_dev, const void* ctx_dev, int32_t ldctx, con
     rc = sc.finish(rc);
     if (cn_exp_env("CASSNAT_CHAIN_STAMPS")) (void)chain_print_stamps();
     return rc;
+}
+
+extern "C" int cn_op_chain(float* x_dev, const void* ctx_dev, int32_t ldctx, const float* wo_host, const float* bo_host,
+                           const float* ln1_a_host, const float* ln1_b_host, const float* w1_host, const float* b1_host,
+                           const float* w2_host, const float* b2_host, const float* nln_a_host, const float* nln_b_host,
+                           const float* wt_host, const float* bt_host, void* out_dev, int32_t ldo, int32_t M, int32_t dff,
+                           int32_t tail_n, float eps, int32_t x_mode, void* stream) {
+    return op_chain(x_dev, ctx_dev, ldctx, wo_host, bo_host, ln1_a_host, ln1_b_host, w1_host, b1_host, w2_host, b2_host, nln_a_host,
+                    nln_b_host, wt_host, bt_host, out_dev, ldo, M, dff, tail_n, eps, x_mode, nullptr, stream);
+}
+
+extern "C" int cn_op_chain_rows(float* x_dev, const void* ctx_dev, int32_t ldctx, const float* wo_host, const float* bo_host,
+                                const float* ln1_a_host, const float* ln1_b_host, const float* w1_host, const float* b1_host,
+                                const float* w2_host, const float* b2_host, const float* nln_a_host, const float* nln_b_host,
+                                const float* wt_host, const float* bt_host, void* out_dev, int32_t ldo, int32_t M, int32_t dff,
+                                int32_t tail_n, float eps, int32_t x_mode, const int32_t* rows_dev, void* stream) {
+    if (!rows_dev) {
+        cn_set_error("cn_op_chain_rows: null row count");
+        return -1;
+    }
+    return op_chain(x_dev, ctx_dev, ldctx, wo_host, bo_host, ln1_a_host, ln1_b_host, w1_host, b1_host, w2_host, b2_host, nln_a_host,
+                    nln_b_host, wt_host, bt_host, out_dev, ldo, M, dff, tail_n, eps, x_mode, rows_dev, stream);
 }
 
 static int op_genmax_impl(const void* h_dev, const float* w_host, const float* b_host, int32_t M, int32_t V,

@@ -527,6 +527,37 @@ int launch_fill_queries(const float* table, float* out, int B, int U, int d, hip
     return 0;
 }
 
+// packed rows (launch_row_plan): one wave per row of the capacity; the row's utterance by bisection of row_off
+__global__ __launch_bounds__(256) void fill_queries_packed_kernel(const float* __restrict__ table, float* __restrict__ out,
+                                                                  const int* __restrict__ row_off, int B, int cap_rows, int d) {
+    const int total = row_off[B];
+    int end = (total + 127) & ~127;  // the row kernels' last 128-row block: finite rows behind the total
+    if (end > cap_rows) end = cap_rows;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= end) return;
+    int u = 0;
+    if (row < total) {
+        int lo = 0, hi = B;  // largest b with row_off[b] <= row (entries without rows share an offset: the last of them owns none)
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (row_off[mid] <= row) lo = mid;
+            else hi = mid;
+        }
+        u = row - row_off[lo];
+    }
+    const f32x4* src = reinterpret_cast<const f32x4*>(table + (long long)u * d);
+    f32x4* dst = reinterpret_cast<f32x4*>(out + (long long)row * d);
+    for (int i = lane; i < d / 4; i += 64) dst[i] = src[i];
+}
+
+int launch_fill_queries_packed(const float* table, float* out, const int* row_off, int B, int cap_rows, int d, hipStream_t s) {
+    if (B <= 0 || cap_rows <= 0) return 0;
+    hipLaunchKernelGGL(fill_queries_packed_kernel, dim3((unsigned)((cap_rows + 3) / 4)), dim3(256), 0, s, table, out, row_off, B,
+                       cap_rows, d);
+    CN_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
 // use_unimask (src/models/cassnat.py:486-488): prepend a zero embedding, drop the last row
 __global__ void shift_right_kernel(const float* __restrict__ x, float* __restrict__ y, int B, int U, int d) {
     const long long n = (long long)B * U * d;

@@ -133,6 +133,8 @@ def lib(flavour=None):
                                   C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_void_p]
     L.cn_op_attention_desc.argtypes = [C.c_int32, C.POINTER(CnAttnDesc), C.c_void_p]
     L.cn_attn_desc_size.argtypes = []
+    L.cn_op_attention_packed.argtypes = [C.c_int32, C.POINTER(CnAttnDesc), C.c_void_p, C.c_int32, C.c_void_p]
+    L.cn_op_row_plan.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.cn_op_logsoftmax_argmax.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     L.cn_op_ctc_align.argtypes = [C.c_void_p] * 3 + [C.c_int32] * 5 + [C.c_void_p] * 6
     L.cn_op_greedy_pack.argtypes = [C.c_void_p] * 3 + [C.c_int32] * 4 + [C.c_void_p] * 4
@@ -182,6 +184,8 @@ def lib(flavour=None):
     L.cn_op_x3_chain.argtypes = [C.c_void_p] * 16 + [C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_void_p]
     L.cn_op_chain.argtypes = ([C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 13 +
                               [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_void_p])
+    L.cn_op_chain_rows.argtypes = ([C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 13 +
+                                   [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_void_p, C.c_void_p])
     L.cn_op_genmax.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     L.cn_op_genmax_gather.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
                                       C.c_void_p, C.c_void_p]
@@ -373,10 +377,14 @@ class Engine:
     @staticmethod
     def make_opts(args, capture=False):
         # (an autoregressive model's args carry no trigger options: ctc_beam_decode runs on either kind of model)
-        return CnDecodeOpts(padding_idx=int(args.padding_idx), sos=1, left_trigger=int(getattr(args, "left_trigger", 0)),
+        # args.hip_padded_rows: cn_decode_opts.reserved[1] - the decoder side on padded [B][U] rows where it would pack each
+        # utterance's own rows (same results bit for bit; the A/B switch of the two layouts)
+        opts = CnDecodeOpts(padding_idx=int(args.padding_idx), sos=1, left_trigger=int(getattr(args, "left_trigger", 0)),
                             right_trigger=int(getattr(args, "right_trigger", 0)), src_trigger=int(bool(getattr(args, "src_trigger", False))),
                             use_unimask=int(bool(getattr(args, "use_unimask", False))), beam_width=int(args.beam_width),
                             capture=int(bool(capture)), no_trigger=int(not getattr(args, "use_trigger", True)))
+        opts.reserved[1] = int(bool(getattr(args, "hip_padded_rows", False)))
+        return opts
 
     def decode(self, feats, size_ratio, opts, hyp, hyp_len, score):
         """feats (B,T,F) f32 cuda, size_ratio (B,) f32 cuda; outputs are caller-owned cuda tensors."""

@@ -218,7 +218,10 @@ class DecodePipelines:
         if r is None:
             return 0
         tp = subsampled(T)
-        # margin over the largest tokens-per-frame ratio seen: extra decoder rows cost ~0.1 % of a pass each, a miss a whole pass.
+        # margin over the largest tokens-per-frame ratio seen: a miss costs a whole pass.  Extra rows of U used to cost ~0.1 % of a
+        # pass each (every utterance ran U decoder rows); with packed decoder rows U is only the CAPACITY - spare rows
+        # cost the launch and immediate return of the row kernels' surplus workgroups, not their work.  (The margins below are
+        # still the ones chosen under the old cost.)
         # It follows the spread of the recent passes' ratios: 8 % when they barely move (a test set of similar speech), up to 40 %
         spread = (max(hist) - min(hist)) / max(hist) if len(hist) >= 4 and max(hist) > 0 else 0.2
         margin = min(1.4, max(1.08, 1.05 + 1.5 * spread))

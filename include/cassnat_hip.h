@@ -88,7 +88,13 @@ typedef struct cn_decode_opts {
     int32_t no_trigger; /* args.use_trigger == False (src/models/cassnat.py:469-473): the extractor attends over every valid frame
                            (trigger_mask = src_mask) and the row counts are best_path_align's own (no EOS row).  0 = use_trigger */
     int32_t reserved[6]; /* reserved[0] != 0: keep the decoder's full log-probability rows of the pass at any beam_width (what
-                            cn_nat_lm_finish reads; beam_width 1 otherwise keeps the arg-max alone).  The others must be 0 */
+                            cn_nat_lm_finish reads; beam_width 1 otherwise keeps the arg-max alone).
+                            reserved[1] != 0: padded decoder rows.  A greedy pass of a 16-bit engine with the row-chain decoder
+                            (d_model 256, transformer blocks; no capture, no use_unimask, use_trigger, no kept rows) otherwise
+                            PACKS its decoder side: utterance b owns only the rows its hypothesis reads - min(ylen[b] + 1, row
+                            count of its own batch) - one utterance behind the other, instead of U rows each.  Hypotheses,
+                            lengths and scores are the same bit for bit either way; the switch is there to compare the two
+                            layouts in one library.  The others must be 0 */
 } cn_decode_opts;
 
 const char* cn_last_error(void);
@@ -352,6 +358,13 @@ int cn_op_chain(float* x_dev, const void* ctx_dev, int32_t ldctx, const float* w
                 const float* w2_host, const float* b2_host, const float* nln_a_host, const float* nln_b_host,
                 const float* wt_host, const float* bt_host, void* out_dev, int32_t ldo, int32_t M, int32_t dff,
                 int32_t tail_n, float eps, int32_t x_mode, void* stream);
+/* cn_op_chain whose row count lives on the device: M sizes the grid (and the buffers), *rows_dev <= M rows exist - workgroups
+ * past them leave at once, the guards use the device value (the packed decoder side's launches). */
+int cn_op_chain_rows(float* x_dev, const void* ctx_dev, int32_t ldctx, const float* wo_host, const float* bo_host,
+                     const float* ln1_a_host, const float* ln1_b_host, const float* w1_host, const float* b1_host,
+                     const float* w2_host, const float* b2_host, const float* nln_a_host, const float* nln_b_host,
+                     const float* wt_host, const float* bt_host, void* out_dev, int32_t ldo, int32_t M, int32_t dff,
+                     int32_t tail_n, float eps, int32_t x_mode, const int32_t* rows_dev, void* stream);
 
 /* ---- front-end: waveform -> log-mel filterbank features (+ global CMVN), padded batch out ----------------------
  * What the reference leaves to Kaldi's compute-fbank-feats (egs/librispeech/conf/fbank.conf:1-6: hamming window, 16 kHz,
@@ -450,6 +463,17 @@ typedef struct cn_attn_desc {
 } cn_attn_desc;
 int cn_op_attention_desc(int32_t precision, const cn_attn_desc* a, void* stream);
 int32_t cn_attn_desc_size(void);
+/* The same kernel on PACKED query rows: entry b owns row_off_dev[b + 1] - row_off_dev[b] <= Lq rows of Q and O from row
+ * row_off_dev[b] on (row-major or blocked) instead of Lq rows from b * Lq on; Lq only sizes the grid; `intervals` keeps its
+ * [B][iv_stride] layout.  kv_packed != 0 (self attention: Lq == Lk, no keymask / kv_mod / kv_index): K / V entry b likewise
+ * holds its own count of keys from row_off_dev[b] on; keys at or past the count are absent and never loaded. */
+int cn_op_attention_packed(int32_t precision, const cn_attn_desc* a, const int32_t* row_off_dev, int32_t kv_packed, void* stream);
+/* Row plan of a packed decoder side: r[b] = min(ylen[b] + 1, limit, hyp_stride - 1), the rows cn_op_greedy_pack reads, with
+ * limit = min(U, *ymax_dev if non-null, largest ylen of b's own batch: utt_meta_dev [B][4] int32 (frames, T', first utterance,
+ * one past the last) if non-null, else blocks of `sub` utterances if 0 < sub < B, else the whole call);
+ * row_off_dev[0 .. B] = exclusive prefix sum of r (row_off_dev[B]: the total). */
+int cn_op_row_plan(const int32_t* ylen_dev, int32_t B, int32_t U, int32_t hyp_stride, int32_t sub, const int32_t* utt_meta_dev,
+                   const int32_t* ymax_dev, int32_t* row_off_dev, void* stream);
 int cn_op_logsoftmax_argmax(float* logits, int32_t M, int32_t V, int32_t* arg, float* maxlp, int32_t write_logp,
                             void* stream);
 int cn_op_ctc_align(const int32_t* best, const uint8_t* keymask, const float* size_ratio, int32_t B, int32_t Tp,
