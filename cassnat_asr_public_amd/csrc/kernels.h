@@ -89,6 +89,10 @@ int launch_feature_range(const float* x, size_t n, const float* limit, unsigned 
 // packed archive rows of a pass -> padded (rows, T, F) batch, optional global CMVN in float64 (the reader's collate on the device)
 int launch_unpack_rows(const float* packed, const int* off, const int* len, float* out, int rows, int T, int F, float pad,
                        const double* mean, const double* sd, hipStream_t s);
+// the same for Kaldi compressed matrices: payload r (global header + data of kind[r] = 1 / 2 / 3: CM / CM2 / CM3) at byte off[r]
+// (a multiple of 16) of `staged` -> decompressed in Kaldi's float32 arithmetic, normalised, padded
+int launch_unpack_compressed(const unsigned char* staged, const int* off, const int* len, const int* kind, float* out, int rows, int T,
+                             int F, float pad, const double* mean, const double* sd, hipStream_t s);
 // per row of logits [M][V] (fp32): first-index argmax, max log-prob; optionally rewrites the row as log-softmax.
 int launch_logsoftmax_argmax(float* logits, int M, int V, int ldl, int* arg, float* maxlp, int write_logp,
                              hipStream_t s);

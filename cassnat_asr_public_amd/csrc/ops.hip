@@ -607,6 +607,21 @@ extern "C" int cn_op_unpack_rows(const float* packed_dev, const int32_t* off_dev
     return launch_unpack_rows(packed_dev, off_dev, len_dev, out_dev, rows, T, F, pad, mean_dev, std_dev, (hipStream_t)stream);
 }
 
+extern "C" int cn_op_unpack_compressed(const void* staged_dev, const int32_t* off_dev, const int32_t* len_dev, const int32_t* kind_dev,
+                                       float* out_dev, int32_t rows, int32_t T, int32_t F, float pad, const double* mean_dev,
+                                       const double* std_dev, void* stream) {
+    if (!staged_dev || !off_dev || !len_dev || !kind_dev || !out_dev || (!mean_dev) != (!std_dev)) {
+        cn_set_error("cn_op_unpack_compressed: null argument (mean and std come together)");
+        return -1;
+    }
+    if (((size_t)staged_dev) & 15) {
+        cn_set_error("cn_op_unpack_compressed: the staging buffer must start on a 16-byte boundary");
+        return -1;
+    }
+    return launch_unpack_compressed(static_cast<const unsigned char*>(staged_dev), off_dev, len_dev, kind_dev, out_dev, rows, T, F, pad,
+                                    mean_dev, std_dev, (hipStream_t)stream);
+}
+
 extern "C" int cn_op_quantize_fp8(const void* src_bf16_dev, int32_t ld, void* dst_dev, int32_t M, int32_t K, float scale,
                                   void* stream) {
     return launch_quantize_fp8(src_bf16_dev, ld, dst_dev, M, K, scale, (hipStream_t)stream);

@@ -797,6 +797,140 @@ int launch_unpack_rows(const float* packed, const int* off, const int* len, floa
     return 0;
 }
 
+// ---- the same hand-over for Kaldi COMPRESSED matrices (matrix/compressed-matrix.{h,cc}; data/kaldi_io.py restates the format) ----
+// What `copy-feats --compress=true` and steps/make_fbank.sh write: one byte (or two) per value.  The utterances of a pass arrive as
+// the archive holds them - each payload (16-byte global header: float min_value, float range, int32 num_rows, int32 num_cols; then
+// the kind's data) at a 16-byte-aligned byte offset off[r] of the staging buffer - and are decompressed, normalised and padded here:
+//   out[r][t][:] = t < len[r] ? norm(decompress(payload_r)[t][:]) : pad          (norm as in unpack_rows_kernel)
+// Decompression is Kaldi's float32 arithmetic, every operation rounded on its own (its x86 builds have no fused multiply-add): the
+// helpers below switch contraction off, since hipcc would otherwise fuse `a + b * c` and change the last bit of about one value in
+// eleven of format 1's third segment.
+__device__ __forceinline__ float uc_scale(float range, float k) {
+#pragma clang fp contract(off)
+    return range * k;
+}
+__device__ __forceinline__ float uc_linear(float mn, float inc, unsigned v) {  // uint16 (formats 1 headers, 2) / uint8 (format 3) -> float
+#pragma clang fp contract(off)
+    return mn + inc * (float)v;
+}
+__device__ __forceinline__ float uc_byte(float p0, float p25, float p75, float p100, unsigned b) {  // format 1: CharToFloat
+#pragma clang fp contract(off)
+    if (b <= 64) return p0 + ((p25 - p0) * (float)b) * (1 / 64.0f);
+    if (b <= 192) return p25 + ((p75 - p25) * (float)(b - 64)) * (1 / 128.0f);
+    return p75 + ((p100 - p75) * (float)(b - 192)) * (1 / 63.0f);
+}
+
+// One workgroup per (utterance, 64-frame tile); the kind is uniform per workgroup.
+// Format 1 (kind 1) is column-major - byte[c * num_rows + t] behind num_cols headers of four uint16 - with an arbitrary column
+// stride, so a column's run starts at any byte.  The tile is 64 frames = one wavefront: a wave takes a column at a time, its lanes
+// run along time, and one load instruction covers one contiguous 64-byte run of the column (at most two cache lines, no alignment
+// needed for byte loads); a shorter tile would halve the run, a longer one only adds LDS.  The dequantised (and normalised) values
+// go through LDS - [frame][column], row stride 97 floats: the column-wise writes hit 64 different banks - and leave row-major, 16
+// bytes per store when F % 4 == 0.  Columns are walked in chunks of 96 (one chunk for 80- and 83-dimensional features).
+// Formats 2 and 3 (uint16 / uint8, row-major) need no transpose.  Reads stay inside the payload its own header describes (which the
+// host has checked against the bytes it staged): frames t < min(len[r], num_rows, T) only.
+#define UC_TILE 64
+#define UC_COLS 96
+__global__ __launch_bounds__(256) void unpack_compressed_kernel(const unsigned char* __restrict__ staged, const int* __restrict__ off,
+                                                                const int* __restrict__ len, const int* __restrict__ kind,
+                                                                float* __restrict__ out, int T, int F, float pad,
+                                                                const double* __restrict__ mean, const double* __restrict__ sd) {
+    __shared__ float tile[UC_TILE][UC_COLS + 1];
+    __shared__ float quart[UC_COLS][4];
+    const int r = blockIdx.y;
+    const long long t0 = (long long)blockIdx.x * UC_TILE;
+    if (t0 >= T) return;
+    const int tn = (int)((T - t0) < UC_TILE ? (T - t0) : UC_TILE);
+    const unsigned char* p = staged + (long long)off[r];
+    const float mn = *reinterpret_cast<const float*>(p), range = *reinterpret_cast<const float*>(p + 4);
+    const int nr = *reinterpret_cast<const int*>(p + 8);
+    const int k = kind[r];
+    int n = len[r] < nr ? len[r] : nr;
+    n = n < 0 ? 0 : (n > T ? T : n);
+    if (k < 1 || k > 3) n = 0;
+    const int valid = (int)((n - t0) <= 0 ? 0 : ((n - t0) < tn ? (n - t0) : tn));  // frames of this tile that hold data
+    float* dst = out + ((long long)r * T + t0) * F;
+    const bool quads = (F & 3) == 0 && ((size_t)dst & 15) == 0;
+    if (k == 1) {
+        const unsigned short* hdr = reinterpret_cast<const unsigned short*>(p + 16);
+        const unsigned char* data = p + 16 + (long long)8 * F + t0;
+        const float inc = uc_scale(range, 1.52590218966964e-05f);
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        for (int c0 = 0; c0 < F; c0 += UC_COLS) {
+            const int cn = (F - c0) < UC_COLS ? (F - c0) : UC_COLS;
+            if (valid > 0)
+                for (int i = threadIdx.x; i < 4 * cn; i += 256) quart[i >> 2][i & 3] = uc_linear(mn, inc, hdr[4 * c0 + i]);
+            __syncthreads();
+            for (int c = wave; c < cn; c += 4) {
+                float v = pad;
+                if (lane < valid) {
+                    v = uc_byte(quart[c][0], quart[c][1], quart[c][2], quart[c][3], data[(long long)(c0 + c) * nr + lane]);
+                    if (mean) v = (float)(((double)v - mean[c0 + c]) / sd[c0 + c]);
+                }
+                tile[lane][c] = v;
+            }
+            __syncthreads();
+            if (quads) {  // (cn is a multiple of 4: F and UC_COLS are)
+                const int q = cn >> 2;
+                for (int i = threadIdx.x; i < tn * q; i += 256) {
+                    const int t = i / q, c = (i - t * q) * 4;
+                    const f32x4 v = {tile[t][c], tile[t][c + 1], tile[t][c + 2], tile[t][c + 3]};
+                    *reinterpret_cast<f32x4*>(dst + (long long)t * F + c0 + c) = v;
+                }
+            } else {
+                for (int i = threadIdx.x; i < tn * cn; i += 256) {
+                    const int t = i / cn, c = i - t * cn;
+                    dst[(long long)t * F + c0 + c] = tile[t][c];
+                }
+            }
+            __syncthreads();  // (the next chunk of columns overwrites the tile)
+        }
+        return;
+    }
+    // formats 2 (uint16) and 3 (uint8), row-major behind the 16-byte header (the payload starts on a 16-byte boundary: the uint16
+    // are aligned)
+    const float inc = uc_scale(range, k == 2 ? 1.52590218966964e-05f : (1 / 255.0f));
+    const unsigned char* d8 = p + 16 + t0 * F;
+    const unsigned short* d16 = reinterpret_cast<const unsigned short*>(p + 16) + t0 * F;
+    const int total = tn * F, nvalid = valid * F;
+    if (quads) {
+        for (int i = 4 * threadIdx.x; i < total; i += 4 * 256) {
+            f32x4 v = {pad, pad, pad, pad};
+            if (i < nvalid) {  // (nvalid is a multiple of F, F of 4: a quad never straddles the utterance's end)
+                const int f = i % F;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    v[e] = uc_linear(mn, inc, k == 2 ? (unsigned)d16[i + e] : (unsigned)d8[i + e]);
+                    if (mean) v[e] = (float)(((double)v[e] - mean[f + e]) / sd[f + e]);
+                }
+            }
+            *reinterpret_cast<f32x4*>(dst + i) = v;
+        }
+    } else {
+        for (int i = threadIdx.x; i < total; i += 256) {
+            float v = pad;
+            if (i < nvalid) {
+                v = uc_linear(mn, inc, k == 2 ? (unsigned)d16[i] : (unsigned)d8[i]);
+                if (mean) v = (float)(((double)v - mean[i % F]) / sd[i % F]);
+            }
+            dst[i] = v;
+        }
+    }
+}
+
+int launch_unpack_compressed(const unsigned char* staged, const int* off, const int* len, const int* kind, float* out, int rows, int T,
+                             int F, float pad, const double* mean, const double* sd, hipStream_t s) {
+    if (rows <= 0 || T <= 0 || F <= 0) return 0;
+    if (rows > 65535) {
+        cn_set_error("unpack_compressed: more than 65535 utterances in one pass");
+        return -1;
+    }
+    hipLaunchKernelGGL(unpack_compressed_kernel, dim3((unsigned)cn_ceil_div(T, UC_TILE), (unsigned)rows), dim3(256), 0, s, staged, off,
+                       len, kind, out, T, F, pad, mean, sd);
+    CN_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
 int launch_cmvn(float* x, const int* len, const double* mean, const double* sd, int B, int T, int F, hipStream_t s) {
     if (B <= 0 || T <= 0 || F <= 0) return 0;
     const int per = cn_ceil_div(T * F, 256);

@@ -148,6 +148,7 @@ def lib(flavour=None):
     L.cn_op_cmvn.argtypes = [C.c_void_p] * 4 + [C.c_int32] * 3 + [C.c_void_p]
     L.cn_host_gather.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]
     L.cn_op_unpack_rows.argtypes = [C.c_void_p] * 4 + [C.c_int32] * 3 + [C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.cn_op_unpack_compressed.argtypes = [C.c_void_p] * 5 + [C.c_int32] * 3 + [C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
     L.cn_op_quantize_fp8.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_void_p]
     L.cn_op_logsoftmax_topk.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     L.cn_op_logsoftmax_fuse_topk.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_int32, C.c_void_p,
@@ -285,14 +286,25 @@ def cmvn_(feats, lens, mean, std):
     return feats
 
 
-def host_gather(dst_ptr, srcs, threads=1):
-    """Copy the numpy arrays ``srcs`` (C-contiguous; e.g. read-only views into a memory-mapped archive) back to back to the host
-    address ``dst_ptr`` in one GIL-free call (cn_host_gather); returns the byte offsets of the pieces."""
+def gather_offsets(sizes, align=1):
+    """Byte offsets of pieces of ``sizes`` bytes laid one after the other, each starting on a multiple of ``align``, and the end
+    of the last one."""
+    sizes = np.asarray(sizes, dtype=np.uint64)
+    a = np.uint64(max(1, int(align)))
+    step = (sizes + (a - np.uint64(1))) // a * a
+    offs = np.zeros(sizes.size, np.uint64)
+    np.cumsum(step[:-1], out=offs[1:])
+    return offs, int(offs[-1] + sizes[-1]) if sizes.size else 0
+
+
+def host_gather(dst_ptr, srcs, threads=1, align=1):
+    """Copy the numpy arrays ``srcs`` (C-contiguous; e.g. read-only views into a memory-mapped archive) to the host address
+    ``dst_ptr`` in one GIL-free call (cn_host_gather), back to back - or, with ``align`` = a > 1, each piece at the next multiple
+    of a bytes (the gaps are left as they are); returns the byte offsets of the pieces."""
     n = len(srcs)
     ptrs = np.fromiter((a.ctypes.data for a in srcs), np.uint64, n)
     sizes = np.fromiter((a.nbytes for a in srcs), np.uint64, n)
-    offs = np.zeros(n, np.uint64)
-    np.cumsum(sizes[:-1], out=offs[1:])
+    offs, _ = gather_offsets(sizes, align)
     check(lib().cn_host_gather(C.c_void_p(int(dst_ptr)), ptrs.ctypes.data_as(C.c_void_p), offs.ctypes.data_as(C.c_void_p),
                                sizes.ctypes.data_as(C.c_void_p), n, int(threads)), "cn_host_gather")
     return offs
@@ -306,6 +318,20 @@ def unpack_rows(packed, off, lens, out, pad, mean=None, std=None):
     assert out.is_contiguous() and packed.is_contiguous() and off.numel() >= rows and lens.numel() >= rows
     check(lib().cn_op_unpack_rows(_ptr(packed), _ptr(off), _ptr(lens), _ptr(out), rows, T, F, float(pad), _ptr(mean), _ptr(std),
                                   current_stream()), "cn_op_unpack_rows")
+    return out
+
+
+def unpack_compressed(staged, off, lens, kinds, out, pad, mean=None, std=None):
+    """The reader's collate for Kaldi compressed matrices on the device (cn_op_unpack_compressed): ``staged`` uint8 CUDA bytes holding
+    the archive payloads (``data.kaldi_io.mat_payload``: global header + data) of the utterances, payload r of kind kinds[r]
+    (1 / 2 / 3 = CM / CM2 / CM3) with lens[r] rows at BYTE offset off[r], a multiple of 16 -> the padded (rows, T, F) batch ``out`` on
+    the current stream, decompressed in Kaldi's float32 arithmetic; with ``mean`` / ``std`` (float64, (F,)) the global CMVN is
+    applied in float64 on the way.  The caller has checked the payloads' headers against F, lens and their sizes."""
+    rows, T, F = out.shape
+    assert out.is_contiguous() and staged.is_contiguous() and staged.element_size() == 1
+    assert off.numel() >= rows and lens.numel() >= rows and kinds.numel() >= rows
+    check(lib().cn_op_unpack_compressed(_ptr(staged), _ptr(off), _ptr(lens), _ptr(kinds), _ptr(out), rows, T, F, float(pad), _ptr(mean),
+                                        _ptr(std), current_stream()), "cn_op_unpack_compressed")
     return out
 
 

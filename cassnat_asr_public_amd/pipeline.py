@@ -57,26 +57,91 @@ class PackedBatch:
     (B, T, F) tensor of ``SuperviseLoader.collate_fn`` (src/data/speech_loader.py:327-356) would: ``shape`` is that tensor's shape,
     ``ratios()`` its float32 length ratios.  The decode pipelines copy the rows of a whole engine pass back to back into page-locked
     memory (one straight memcpy per utterance, no padding), send them with one DMA and spread them over the padded batch on the
-    device (``hip.unpack_rows``: padding and, when asked for, the global CMVN in float64 happen there)."""
+    device (``hip.unpack_rows``: padding and, when asked for, the global CMVN in float64 happen there).
 
-    __slots__ = ("views", "lens", "shape", "dtype", "is_cuda")
+    The COMPRESSED form (``from_payloads`` on Kaldi `CM` / `CM2` / `CM3` entries; ``kinds`` is then a list, otherwise None) keeps
+    per utterance the payload as the archive holds it - a read-only uint8 view from min_value on (``data.kaldi_io.mat_payload``) -
+    its kind (1 / 2 / 3) and its rows; shape, lengths and ratios come from the headers.  The pipelines stage the payloads as they
+    are, a quarter of the float32 bytes, and ``hip.unpack_compressed`` decompresses on the device; ``padded()`` - host
+    decompression with ``kaldi_io.decompress`` - is the definition of what it must produce."""
 
-    def __init__(self, views):
+    __slots__ = ("views", "lens", "shape", "dtype", "is_cuda", "kinds", "utts")
+
+    def __init__(self, views, utts=None):
         self.views = views
+        self.kinds = None
+        self.utts = utts
         self.lens = [int(v.shape[0]) for v in views]
         self.shape = (len(views), max(self.lens), int(views[0].shape[1]))
         self.dtype = torch.float32
         self.is_cuda = False
+
+    @classmethod
+    def from_payloads(cls, entries, utts=None, compressed=None, cols=None):
+        """``entries``: one ``kaldi_io.mat_payload`` tuple (kind, rows, cols, payload) per utterance - all `FM` (the float32 form,
+        as ``PackedBatch(views)``) or all of the compressed kinds, which may mix.  Every header is checked: an entry of the other
+        family (``compressed`` = True / False: the family the caller expects; None: the first entry's), of another column count
+        (``cols``; None: the first entry's) or whose payload is not the size its header gives raises a ValueError that names the
+        utterance - nothing is strided on a guess."""
+        from .data.kaldi_io import COMPRESSED_KINDS
+
+        def name(b):
+            return "utterance %s" % (utts[b] if utts is not None else "#%d of the batch" % b)
+
+        if not entries:
+            raise ValueError("PackedBatch: an empty batch")
+        want_c = (entries[0][0] in COMPRESSED_KINDS) if compressed is None else bool(compressed)
+        want_cols = int(entries[0][2]) if cols is None else int(cols)
+        views, kinds, lens = [], [], []
+        for b, (kind, rows, ncols, payload) in enumerate(entries):
+            is_c = kind in COMPRESSED_KINDS
+            if kind != "FM" and not is_c:
+                raise ValueError("PackedBatch: %s holds a %r matrix, which the packed reader does not take" % (name(b), kind))
+            if is_c != want_c:
+                raise ValueError("PackedBatch: %s holds a %r matrix in a batch of %s ones" % (name(b), kind, "compressed" if want_c else "float32"))
+            if int(ncols) != want_cols:
+                raise ValueError("PackedBatch: %s has %d columns, the batch %d" % (name(b), ncols, want_cols))
+            rows, ncols = int(rows), int(ncols)
+            if not is_c:
+                if rows < 0 or payload.nbytes != 4 * rows * ncols:
+                    raise ValueError("PackedBatch: %s: payload of %d bytes for %d x %d float32" % (name(b), payload.nbytes, rows, ncols))
+                views.append(payload.view("<f4").reshape(rows, ncols))
+                continue
+            need = 16 + {"CM": 8 * ncols + rows * ncols, "CM2": 2 * rows * ncols, "CM3": rows * ncols}[kind]
+            if rows < 0 or payload.dtype != np.uint8 or payload.ndim != 1 or payload.nbytes != need:
+                raise ValueError("PackedBatch: %s: payload of %d bytes for a %d x %d %s matrix (%d)" % (name(b), payload.nbytes, rows, ncols, kind, need))
+            if tuple(np.frombuffer(payload[8:16].tobytes(), "<i4")) != (rows, ncols):  # (the device strides by the payload's own header)
+                raise ValueError("PackedBatch: %s: the payload's header does not say %d x %d" % (name(b), rows, ncols))
+            views.append(payload)
+            kinds.append(COMPRESSED_KINDS[kind])
+            lens.append(rows)
+        if not want_c:
+            return cls(views, utts)
+        self = cls.__new__(cls)
+        self.views, self.kinds, self.lens, self.utts = views, kinds, lens, utts
+        self.shape = (len(views), max(lens), want_cols)
+        self.dtype = torch.float32
+        self.is_cuda = False
+        return self
 
     def ratios(self):
         """collate's ``ratios[b] = feat.shape[0] / t_max``: the Python (double) quotient rounded to float32"""
         t_max = self.shape[1]
         return torch.tensor([n / t_max for n in self.lens], dtype=torch.float32)
 
+    def matrices(self):
+        """The utterances' float32 matrices on the host (the compressed form decompressed by ``kaldi_io.decompress``)."""
+        if self.kinds is None:
+            return self.views
+        from .data.kaldi_io import decompress
+
+        names = {1: "CM", 2: "CM2", 3: "CM3"}
+        return [decompress(names[k], n, self.shape[2], v) for k, n, v in zip(self.kinds, self.lens, self.views)]
+
     def padded(self, pad=0.0, cmvn=None):
         """The collated tensor itself (host): what the packed path must reproduce; used by the CPU rehearsal and the tests."""
         out = np.full(self.shape, float(pad), np.float32)
-        for b, v in enumerate(self.views):
+        for b, v in enumerate(self.matrices()):
             out[b, : v.shape[0]] = v if cmvn is None else ((v.astype(np.float64) - cmvn[0]) / cmvn[1]).astype(np.float32)
         return torch.from_numpy(out)
 
@@ -182,7 +247,7 @@ class DecodePipelines:
         self._rows_lock = threading.Lock()
         self._stats_lock = threading.Lock()
         self.timeline = None  # a list: the workers and the consumer append (label, pipeline, perf_counter) - bench.py --host-timeline
-        self.stats = {"passes": 0, "batches": 0, "predicted": 0, "missed": 0, "merged_ragged": 0,
+        self.stats = {"passes": 0, "batches": 0, "predicted": 0, "missed": 0, "merged_ragged": 0, "compressed_passes": 0,
                       # host seconds of the worker threads, by what they were doing (summed over the pipelines)
                       "s_take": 0.0, "s_stage": 0.0, "s_launch": 0.0, "s_retire_wait": 0.0}
 
@@ -309,7 +374,8 @@ class DecodePipelines:
             f = nxt[0]
             T = int(f.shape[1])
             hi, lo = max(tmax, T), min(tmin, T)
-            ok = (type(f) is type(f0) and tuple(f.shape[2:]) == tuple(f0.shape[2:]) and f.dtype == f0.dtype and nxt[1].dtype == items[0][1].dtype
+            ok = (type(f) is type(f0) and (getattr(f, "kinds", None) is None) == (getattr(f0, "kinds", None) is None)
+                  and tuple(f.shape[2:]) == tuple(f0.shape[2:]) and f.dtype == f0.dtype and nxt[1].dtype == items[0][1].dtype
                   and lo >= self.ragged * hi and self.fits(rows + int(f.shape[0]), hi))
             if ok and ahead.acquire(blocking=False):
                 items.append(nxt)
@@ -342,6 +408,8 @@ class DecodePipelines:
                 o += b.shape[0]
             return feats, torch.cat([x[1] for x in items], 0)
         dev_ = torch.device("cuda", device)
+        if batches[0].kinds is not None:
+            return self._stage_compressed(k, slot, items, pad, rows, tmax, F, dev_)
         views = [v for b in batches for v in b.views]
         lens = [n for b in batches for n in b.lens]
         total = sum(lens)
@@ -380,6 +448,58 @@ class DecodePipelines:
             if stats is None:
                 stats = self._cmvn_dev[device] = (torch.from_numpy(self.cmvn[0]).to(dev_), torch.from_numpy(self.cmvn[1]).to(dev_))
         hip.unpack_rows(bufs["dev"], bufs["meta_d"][:utts], bufs["meta_d"][utts:2 * utts], feats, pad, stats[0], stats[1])
+        return feats, bufs["meta_d"][2 * utts:2 * utts + rows].view(torch.float32)
+
+    def _stage_compressed(self, k, slot, items, pad, rows, tmax, F, dev_):
+        """A pass of compressed ``PackedBatch``es (Kaldi `CM` / `CM2` / `CM3`, mixed as they come): the payloads go into the slot's
+        page-locked buffer as the archive holds them, each at a 16-byte-aligned offset (one ``cn_host_gather`` call), ONE DMA of
+        those bytes - about a quarter of the float32 rows - takes them to the device, the per-utterance (byte offset, frames,
+        ratio, kind) follow in the small DMA, and ``hip.unpack_compressed`` decompresses, normalises and pads.  The buffers are
+        sized in bytes (area x F values of one byte plus the headers; grown for a pass that needs more, e.g. all `CM2`)."""
+        from . import hip
+
+        batches = [x[0] for x in items]
+        if any(b.kinds is None or b.shape[2] != F for b in batches):
+            raise ValueError("DecodePipelines: a pass mixes compressed and float32 packed batches, or feature dimensions")
+        views = [v for b in batches for v in b.views]
+        lens = [n for b in batches for n in b.lens]
+        kinds = [c for b in batches for c in b.kinds]
+        offs, total = hip.gather_offsets([v.nbytes for v in views], 16)
+        if total >= 2 ** 31:
+            raise ValueError("DecodePipelines: a pass of %d compressed bytes (the offsets are int32)" % total)
+        key = ("compressed", slot)
+        bufs = self._packed[k].get(key)
+        if bufs is None or bufs["cap"] < total or bufs["F"] != F or bufs["utts"] < rows:
+            utts = max(rows, self.max_utts)
+            cap = max(total, self.max_batch * self.frames_cap * F + utts * (32 + 8 * F))
+            bufs = {"cap": cap, "F": F, "utts": utts,
+                    "host": torch.empty(cap, dtype=torch.uint8, pin_memory=True),
+                    "dev": torch.empty(cap, dtype=torch.uint8, device=dev_),
+                    # per utterance: byte offset, frames, float32 ratio (as int32 bits), kind - one small DMA
+                    "meta_h": torch.empty(4 * utts, dtype=torch.int32, pin_memory=True),
+                    "meta_d": torch.empty(4 * utts, dtype=torch.int32, device=dev_),
+                    "out": torch.empty(max(rows * tmax, self.max_batch * self.frames_cap) * F, dtype=torch.float32, device=dev_)}
+            self._packed[k][key] = bufs
+        if bufs["out"].numel() < rows * tmax * F:
+            bufs["out"] = torch.empty(rows * tmax * F, dtype=torch.float32, device=dev_)
+        hip.host_gather(bufs["host"].data_ptr(), views, max(1, self.copy_threads), align=16)
+        meta = bufs["meta_h"].numpy()
+        utts = bufs["utts"]
+        meta[:rows] = offs
+        meta[utts:utts + rows] = lens
+        meta[2 * utts:2 * utts + rows] = torch.cat([x[1] for x in items], 0).numpy().view(np.int32)
+        meta[3 * utts:3 * utts + rows] = kinds
+        bufs["dev"][:total].copy_(bufs["host"][:total], non_blocking=True)
+        bufs["meta_d"].copy_(bufs["meta_h"], non_blocking=True)
+        feats = bufs["out"][: rows * tmax * F].view(rows, tmax, F)
+        stats = (None, None)
+        if self.cmvn is not None:
+            stats = self._cmvn_dev.get(self._device)
+            if stats is None:
+                stats = self._cmvn_dev[self._device] = (torch.from_numpy(self.cmvn[0]).to(dev_), torch.from_numpy(self.cmvn[1]).to(dev_))
+        hip.unpack_compressed(bufs["dev"], bufs["meta_d"][:utts], bufs["meta_d"][utts:2 * utts], bufs["meta_d"][3 * utts:4 * utts], feats, pad,
+                              stats[0], stats[1])
+        self._bump("compressed_passes", 1)
         return feats, bufs["meta_d"][2 * utts:2 * utts + rows].view(torch.float32)
 
     def _stage_inputs(self, k, slot, items, pad):

@@ -199,6 +199,7 @@ class CassNATTask(BaseTask):
         """Greedy NAST decoding of a test set through N decode pipelines (pipeline.DecodePipelines: engine handle, HIP stream
         and host thread each; the workers pull - load and collate - the batches): same hypotheses in the same order, the
         GPU no longer idles across the two host syncs of a batch."""
+        from ..data import kaldi_io
         from ..pipeline import DecodePipelines
 
         self.model._check_args(args, self.lm_model)
@@ -212,23 +213,33 @@ class CassNATTask(BaseTask):
         # the DataLoader altogether - its worker PROCESSES had to pickle every batch through shared memory (8.5k utt/s and nine
         # seconds to the first batch with the recipes' `--load_data_workers 4`); that flag now sets the number of copy THREADS.
         defer_ok = bool(ds is not None and hasattr(ds, "can_defer_cmvn") and ds.can_defer_cmvn() and int(getattr(args, "hip_device_cmvn", 1)))
-        packed = bool(defer_ok and int(getattr(args, "hip_packed_reader", 1)) and hasattr(self.test_loader, "batch_sampler"))
+        # ... to a test set that is float32 (`FM `) throughout, or COMPRESSED throughout (Kaldi's `CM` / `CM2` / `CM3`, what
+        # make_fbank.sh writes; the kinds may mix, as they do inside one copy-feats archive): the payloads are then staged as the
+        # archive holds them and decompressed on the device.  Decided from every utterance's header; a set that mixes the two
+        # families keeps the collated DataLoader path (which reads all of them, and still defers the CMVN)
+        kinds = ds.matrix_kinds() if defer_ok and hasattr(ds, "matrix_kinds") else frozenset(["FM"])
+        one_family = kinds <= {"FM"} or kinds <= set(kaldi_io.COMPRESSED_KINDS)
+        packed = bool(defer_ok and one_family and int(getattr(args, "hip_packed_reader", 1)) and hasattr(self.test_loader, "batch_sampler"))
+        compressed = bool(packed and not kinds <= {"FM"})  # (the packed reader's compressed form)
         dev_cmvn = bool(defer_ok and getattr(ds, "use_cmvn", False) and (packed or getattr(self.test_loader, "num_workers", 0) == 0))
         if dev_cmvn:
             ds.device_cmvn = True
         try:
-            return self._decode_pipelined_run(args, n_pipes, results, batch_time, progress, sos, (ds.mean, ds.std) if dev_cmvn else None, packed)
+            return self._decode_pipelined_run(args, n_pipes, results, batch_time, progress, sos, (ds.mean, ds.std) if dev_cmvn else None, packed, compressed)
         finally:
             if dev_cmvn:
                 ds.device_cmvn = False
 
-    def _decode_pipelined_run(self, args, n_pipes, results, batch_time, progress, sos, cmvn, packed=False):
+    def _decode_pipelined_run(self, args, n_pipes, results, batch_time, progress, sos, cmvn, packed=False, compressed=False):
         from ..data import kaldi_io
         from ..pipeline import DecodePipelines, PackedBatch
 
         ds = getattr(self.test_loader, "dataset", None)
+        feat_dim = None
         if packed:
-            first_len = max(kaldi_io.mat_rows(ds._items[i][1]) for i in list(self.test_loader.batch_sampler)[0])
+            first = [ds._items[i][1] for i in list(self.test_loader.batch_sampler)[0]]
+            first_len = max(kaldi_io.mat_rows(spec) for spec in first)
+            feat_dim = kaldi_io.mat_payload(first[0])[2]
         else:
             first_len = next(iter(self.test_loader))[1].shape[1]
         max_frames = max(getattr(args, "hip_max_frames", 4096), first_len)
@@ -240,7 +251,7 @@ class CassNATTask(BaseTask):
 
         cmvn_id = None if cmvn is None else hashlib.sha1(np.ascontiguousarray(cmvn[0]).tobytes() + np.ascontiguousarray(cmvn[1]).tobytes()).hexdigest()
         key = (n_pipes, args.batch_size, max_frames, int(getattr(args, "hip_coalesce", 10)), float(getattr(args, "hip_ragged", 0.75)),
-               cmvn_id, self.model.weights_key(), packed, int(getattr(args, "load_data_workers", 0)) if packed else 0)
+               cmvn_id, self.model.weights_key(), packed, compressed, int(getattr(args, "load_data_workers", 0)) if packed else 0)
         pipes = getattr(self, "_pipes", None)
         if pipes is None or self._pipes_key != key:  # (kept for further decode() calls on this task: engines, threads, streams)
             if pipes is not None:
@@ -256,7 +267,10 @@ class CassNATTask(BaseTask):
             if packed:  # the loader's batches (same utterances, same order) as views into the archives' memory maps
                 for j, idx in enumerate(self.test_loader.batch_sampler):
                     items = [ds._items[i] for i in idx]
-                    pb = PackedBatch([kaldi_io.load_mat_view(spec) for _, spec, _ in items])
+                    # (every header is checked against the path chosen above and the set's feature dimension: a contradiction
+                    # raises, naming the utterance)
+                    pb = PackedBatch.from_payloads([kaldi_io.mat_payload(spec) for _, spec, _ in items], utts=[u for u, _, _ in items],
+                                                   compressed=compressed, cols=feat_dim)
                     # (utt2diff reads the width of the PADDED label row, src/tasks/cassnat_task.py:358-360)
                     meta[j] = ([u for u, _, _ in items], [None] * len(items), pb.shape[0] * pb.shape[1], max(len(t) for _, _, t in items))
                     yield pb, pb.ratios(), j

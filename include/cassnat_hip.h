@@ -563,6 +563,16 @@ int cn_op_cmvn(float* feats_dev, const int32_t* len_dev, const double* mean_dev,
  * a frame becomes float((double(x) - mean) / std), the dataset's arithmetic bit for bit. */
 int cn_op_unpack_rows(const float* packed_dev, const int32_t* off_dev, const int32_t* len_dev, float* out_dev, int32_t rows, int32_t T,
                       int32_t F, float pad, const double* mean_dev, const double* std_dev, void* stream);
+/* The same hand-over for Kaldi COMPRESSED matrices (`copy-feats --compress=true`, steps/make_fbank.sh: tokens CM / CM2 / CM3,
+ * kind_dev[r] = 1 / 2 / 3; a pass may mix them).  staged_dev holds the payloads as the archive does - 16-byte global header (float
+ * min_value, float range, int32 num_rows, int32 num_cols), then for kind 1 num_cols x 4 uint16 column headers and num_cols x
+ * num_rows bytes column-major, for kind 2 / 3 num_rows x num_cols uint16 / uint8 row-major - payload r at BYTE offset off_dev[r], a
+ * multiple of 16 (staged_dev itself 16-byte aligned).  The caller has checked num_cols == F, num_rows == len_dev[r] and the
+ * payload sizes.  out_dev[r][t][:] = t < len[r] ? norm(decompress(payload r)[t][:]) : pad, the decompression in Kaldi's float32
+ * arithmetic (no fused multiply-add: the bits `copy-feats` itself gives), norm as in cn_op_unpack_rows. */
+int cn_op_unpack_compressed(const void* staged_dev, const int32_t* off_dev, const int32_t* len_dev, const int32_t* kind_dev,
+                            float* out_dev, int32_t rows, int32_t T, int32_t F, float pad, const double* mean_dev, const double* std_dev,
+                            void* stream);
 /* host side of the same reader: n byte ranges (an utterance's rows in the memory map of its archive) copied back to back into a
  * staging buffer (dst + dst_offsets[i]) by one GIL-free call; threads > 1 deals them over that many host threads */
 int cn_host_gather(void* dst, const uint64_t* src_ptrs, const uint64_t* dst_offsets, const uint64_t* nbytes, int32_t n, int32_t threads);
