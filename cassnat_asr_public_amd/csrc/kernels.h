@@ -319,6 +319,10 @@ struct FbankOpts {
 int fbank_num_frames(const FbankOpts& o, int num_samples);
 int launch_fbank(const FbankOpts& o, const float* wave, const int* num_samples, int B, int max_samples, const float* cmvn_mean,
                  const float* cmvn_istd, float* out, int Tmax, float pad_value, hipStream_t s);
+// the packed reader's form: int16 samples as the WAV files hold them, utterance r at byte off[r] of `staged`; float64 CMVN
+int fbank_frame_samples(const FbankOpts& o);
+int launch_fbank_packed(const FbankOpts& o, const unsigned char* staged, long long staged_bytes, const int* off, const int* samples,
+                        float* out, int rows, int T, float pad_value, const double* mean, const double* sd, hipStream_t s);
 
 // ---- conv2 as an LDS-DMA implicit GEMM, bf16 / 256 -> 256 channels (conv2.hip); launch_gemm dispatches to it
 bool conv2_dma_applies(int prec, int C, int N);

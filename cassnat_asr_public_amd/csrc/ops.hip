@@ -130,6 +130,26 @@ extern "C" int cn_fbank(const cn_fbank_opts* o, const float* wave_dev, const int
                         Tmax, pad_value, (hipStream_t)stream);
 }
 
+extern "C" int cn_op_fbank_packed(const cn_fbank_opts* o, const void* staged_dev, int64_t staged_bytes, const int32_t* off_dev,
+                                  const int32_t* samples_dev, float* out_dev, int32_t rows, int32_t T, float pad, const double* mean_dev,
+                                  const double* std_dev, void* stream) {
+    if (!o || !staged_dev || !off_dev || !samples_dev || !out_dev || (!mean_dev) != (!std_dev)) {
+        cn_set_error("cn_op_fbank_packed: null argument (mean and std come together)");
+        return -1;
+    }
+    if (rows <= 0 || T <= 0 || o->num_mel <= 0 || staged_bytes < 0) {
+        cn_set_error("cn_op_fbank_packed: rows, T and num_mel must be positive");
+        return -1;
+    }
+    const FbankOpts f = fbank_opts_from(o);
+    if (fbank_frame_samples(f) > 512) {
+        cn_set_error("cn_op_fbank_packed: a frame of more than 512 samples does not fit the 512-point FFT");
+        return -1;
+    }
+    return launch_fbank_packed(f, static_cast<const unsigned char*>(staged_dev), staged_bytes, off_dev, samples_dev, out_dev, rows, T, pad,
+                               mean_dev, std_dev, (hipStream_t)stream);
+}
+
 extern "C" int cn_op_gemm(int32_t precision, const void* A, int32_t lda, const void* W, const float* bias, void* C,
                           int32_t ldc, int32_t c_is_f32, int32_t M, int32_t N, int32_t K, int32_t relu,
                           const float* resid, int32_t ldr, const float* pe, int32_t pe_period, float scale,

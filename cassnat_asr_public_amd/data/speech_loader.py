@@ -10,7 +10,7 @@ import numpy as np
 import torch
 from torch.utils.data import DataLoader, Dataset
 
-from . import kaldi_io
+from . import kaldi_io, wave_io
 from .feat_op import context_feat, skip_feat
 
 
@@ -36,16 +36,106 @@ class SingleSet(object):
         return len(self.items)
 
 
+class WaveBatch(object):
+    """What a wave set's collate puts where the padded feature tensor would stand: the utterances' int16 sample views and their
+    frame counts.  ``shape`` is the padded FEATURE shape (B, longest frame count, num_mel), so that batch counting, progress
+    printing and ``first.shape[1]`` work as for a tensor; the features themselves are computed on the device, in the task's own
+    process (``Fbank.packed`` / the packed reader's wave form)."""
+
+    __slots__ = ("views", "frames", "utts", "shape", "dtype", "is_cuda")
+
+    def __init__(self, views, frames, num_mel, utts=None):
+        self.views, self.frames, self.utts = list(views), [int(n) for n in frames], utts
+        self.shape = (len(self.views), max(self.frames), int(num_mel))
+        self.dtype = torch.float32
+        self.is_cuda = False
+
+
+def front_end_options(args):
+    """The fbank option block (``hip.CnFbankOpts``) of ``--hip_fbank_conf`` (default: the built-in options)."""
+    from .fbank import Fbank
+
+    conf = getattr(args, "hip_fbank_conf", "") or ""
+    return (Fbank.from_conf(conf) if conf else Fbank()).o
+
+
+def frames_of(opts, samples):
+    """Frame count of ``samples`` samples under the option block ``opts`` (snip_edges: cn_fbank_num_frames' rule)."""
+    flen, shift = int(opts.sample_rate * 0.001 * opts.frame_length_ms), int(opts.sample_rate * 0.001 * opts.frame_shift_ms)
+    return 0 if samples < flen or shift < 1 else 1 + (samples - flen) // shift
+
+
+def sniff_wave_set(items, mode="auto"):
+    """Is the list of (utt, spec, ...) a wave set?  Decided from EVERY entry (``wave_io.entry_kind``): all RIFF/WAVE files - True;
+    none - False (``mode`` "1": an error); a command, a WAV with a `:offset`, or WAV files mixed with anything else raise a
+    ValueError that names the utterance.  ``mode`` "0": never look."""
+    mode = str(mode)
+    if mode == "0":
+        return False
+    seen = {}  # (entries of one archive share its path: one look per file)
+
+    def kind(spec):
+        spec = spec.strip()
+        if spec.endswith("|"):
+            return "pipe"
+        path, _, off = spec.rpartition(":")
+        has_off = bool(path) and off.isdigit()
+        name = path if has_off else spec
+        if name not in seen:
+            seen[name] = wave_io.is_wav(name)
+        if not seen[name]:
+            return None
+        return "wav_offset" if has_off else "wav"
+
+    kinds = [kind(it[1]) for it in items]
+    for it, k in zip(items, kinds):
+        if k in ("pipe", "wav_offset"):
+            wave_io.check_spec(it[1], it[0])
+    n_wav = sum(1 for k in kinds if k == "wav")
+    if n_wav == 0:
+        if mode == "1":
+            raise ValueError("--hip_audio 1: utterance %s (%s) is not a RIFF/WAVE file" % (items[0][0], items[0][1]) if items
+                             else "--hip_audio 1: an empty utterance list")
+        return False
+    if n_wav != len(items):
+        odd = next(it for it, k in zip(items, kinds) if k != "wav")
+        raise ValueError("the set mixes WAV files and feature matrices: utterance %s (%s) is not a RIFF/WAVE file, utterance %s is"
+                         % (odd[0], odd[1], next(it for it, k in zip(items, kinds) if k == "wav")[0]))
+    return True
+
+
 class SpeechDataset(Dataset):
     def __init__(self, vocab, data_paths, args):
         self.left_context, self.right_context = args.left_ctx, args.right_ctx
         self.skip_frame = args.skip_frame
+        self.is_wave = False
         self.use_cmvn = False
         # set (by the pipelined decoder, for the length of a decode) when the consumer applies the global CMVN itself, on the
         # device (pipeline.DecodePipelines(cmvn=...)): the fast path below then hands the features over as they are in the archive
         self.device_cmvn = False
         self.data_streams = [SingleSet(vocab, p, getattr(args, "rank", 0)) for p in data_paths]
         self._items = [it for s in self.data_streams for it in s.items]
+        if sniff_wave_set(self._items, getattr(args, "hip_audio", "auto")):
+            self._init_wave_set(args)
+
+    def _init_wave_set(self, args):
+        """A wave set: the entries are sound files, the dataset hands out (utt, int16 view, text) and the features are computed on
+        the device by the consumer.  Every header is checked here - format, rate, at least one frame - so that a bad file is named
+        before anything is decoded."""
+        if not (self.left_context == 0 and self.right_context == 0 and self.skip_frame <= 1):
+            raise NotImplementedError("audio input with left_ctx / right_ctx / skip_frame other than 0 / 0 / 1 (splicing and frame "
+                                      "skipping on audio input are not implemented)")
+        self.fbank_opts = front_end_options(args)
+        self.sample_rate, self.num_mel = float(self.fbank_opts.sample_rate), int(self.fbank_opts.num_mel)
+        self.wave_frames = []
+        for utt, spec, _ in self._items:
+            n = wave_io.num_samples(spec, self.sample_rate, utt)
+            frames = frames_of(self.fbank_opts, n)
+            if frames < 1:
+                raise ValueError("utterance %s (%s): %d samples give no frame (shorter than one analysis window)" % (utt, spec, n))
+            self.wave_frames.append(frames)
+        self.is_wave = True
+        self._kinds = frozenset(["WAV"])
 
     def _load_cmvn(self, cmvn_file):
         """Kaldi global CMVN stats: row 0 = sums (last column = frame count), row 1 = sums of squares."""
@@ -61,6 +151,8 @@ class SpeechDataset(Dataset):
 
     def __getitem__(self, idx):
         utt, spec, text = self._items[idx]
+        if self.is_wave:  # (the samples as the file holds them; normalisation happens with the features, on the device)
+            return utt, wave_io.pcm_view(spec, self.sample_rate, utt), text
         if self.left_context == 0 and self.right_context == 0 and self.skip_frame <= 1:
             # The shipped configuration (no splicing, no frame skipping).  Same values as the general path below - the CMVN in
             # float64, rounded to float32 once (where the reference's collate converts: speech_loader.py:340) - without its
@@ -89,14 +181,17 @@ class SpeechDataset(Dataset):
         holds float32 matrices: the device form computes float((double)x - mean) / std) on the float32 rows collate hands over,
         which is the reference's arithmetic bit for bit only when those rows are the archive's own values.  A float64 (`DM`)
         archive is normalised in float64 and rounded once (here, on the host, as the reference does).  Compressed matrices
-        (`CM`, `CM2`, `CM3`) decompress to float32 values: they defer like `FM `."""
+        (`CM`, `CM2`, `CM3`) decompress to float32 values: they defer like `FM `.  A wave set always defers: its features exist on
+        the device only."""
+        if self.is_wave:
+            return True
         if not (self.left_context == 0 and self.right_context == 0 and self.skip_frame <= 1):
             return False
         return "DM" not in self.matrix_kinds()
 
     def matrix_kinds(self):
         """The kinds of matrix this set holds (``kaldi_io.mat_kind``), from EVERY utterance's header: Kaldi mixes `CM` and `CM2`
-        inside one archive, and a table may point into archives of different kinds."""
+        inside one archive, and a table may point into archives of different kinds.  A wave set (sound files) is {"WAV"}."""
         if getattr(self, "_kinds", None) is None:
             self._kinds = frozenset(kaldi_io.mat_kind(spec) for _, spec, _ in self._items)
         return self._kinds
@@ -139,6 +234,24 @@ def collate(batch, padding_idx=0):
     return utts, feats, texts, ratios, sizes
 
 
+def collate_waves(batch, padding_idx=0, opts=None):
+    """``collate`` for a wave set: list of (utt, int16 samples, text) -> the same five-tuple with a ``WaveBatch`` where the padded
+    features would stand (no GPU is touched here: a loader worker process may run it)."""
+    frames = [frames_of(opts, int(x[1].shape[0])) for x in batch]
+    t_max = max(frames)
+    l_max = max(len(x[2]) for x in batch)
+    texts = torch.full((len(batch), l_max), int(padding_idx), dtype=torch.long)
+    ratios = torch.zeros(len(batch))
+    sizes = torch.zeros(len(batch), dtype=torch.long)
+    utts = []
+    for b, (utt, _, text) in enumerate(batch):
+        texts[b, : len(text)] = torch.as_tensor(text, dtype=torch.long)
+        ratios[b] = frames[b] / t_max
+        sizes[b] = len(text) - 2
+        utts.append(utt)
+    return utts, WaveBatch([x[1] for x in batch], frames, opts.num_mel, utts), texts, ratios, sizes
+
+
 def _one_thread_worker(_worker_id):
     """A loader worker reads and pads a few megabytes: one thread.  Left at torch's default, every worker starts an intra-op
     team as wide as the machine whose idle threads spin - on a box with a CPU quota the whole job (the process that launches
@@ -157,7 +270,8 @@ class SpeechDataLoader(DataLoader):
         # worker processes hand their batches over in shared memory, from which a host -> device copy is pathologically slow
         # (83 ms per 9-MB batch measured): the loader's pinning thread moves them into page-locked memory first
         super().__init__(dataset, batch_sampler=batches, num_workers=num_workers,
-                         collate_fn=functools.partial(collate, padding_idx=padding_idx),
+                         collate_fn=(functools.partial(collate_waves, padding_idx=padding_idx, opts=dataset.fbank_opts)
+                                     if getattr(dataset, "is_wave", False) else functools.partial(collate, padding_idx=padding_idx)),
                          pin_memory=bool(num_workers > 0 and torch.cuda.is_available()),
                          worker_init_fn=_one_thread_worker if num_workers > 0 else None,
                          persistent_workers=bool(num_workers > 0))

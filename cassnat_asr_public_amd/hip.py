@@ -221,6 +221,8 @@ def lib(flavour=None):
     L.cn_fbank_num_frames.restype = C.c_int32
     L.cn_fbank.argtypes = [C.POINTER(CnFbankOpts), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                            C.c_int32, C.c_float, C.c_void_p]
+    L.cn_op_fbank_packed.argtypes = [C.POINTER(CnFbankOpts), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                     C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
     L.cn_esa_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(CnDecodeOpts), C.c_void_p]
     L.cn_esa_sample.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.POINTER(CnDecodeOpts), C.c_void_p,
                                 C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_void_p]
@@ -332,6 +334,20 @@ def unpack_compressed(staged, off, lens, kinds, out, pad, mean=None, std=None):
     assert off.numel() >= rows and lens.numel() >= rows and kinds.numel() >= rows
     check(lib().cn_op_unpack_compressed(_ptr(staged), _ptr(off), _ptr(lens), _ptr(kinds), _ptr(out), rows, T, F, float(pad), _ptr(mean),
                                         _ptr(std), current_stream()), "cn_op_unpack_compressed")
+    return out
+
+
+def fbank_packed(opts, staged, staged_bytes, off, samples, out, pad, mean=None, std=None):
+    """The Kaldi fbank front-end behind the packed reader (cn_op_fbank_packed): ``staged`` uint8 CUDA bytes holding the utterances'
+    little-endian int16 samples as the WAV `data` chunks hold them, utterance r with samples[r] samples at BYTE offset off[r], a
+    multiple of 16 -> the padded (rows, T, num_mel) batch ``out`` on the current stream: frame t < num_frames(samples[r]) is
+    ``cn_fbank``'s value bit for bit, later frames are ``pad``; with ``mean`` / ``std`` (float64, (num_mel,)) the global CMVN is
+    applied in float64 on the way.  ``opts``: a ``CnFbankOpts``."""
+    rows, T, F = out.shape
+    assert out.is_contiguous() and out.element_size() == 4 and staged.is_contiguous() and staged.element_size() == 1
+    assert F == opts.num_mel and 0 <= int(staged_bytes) <= staged.numel() and off.numel() >= rows and samples.numel() >= rows
+    check(lib().cn_op_fbank_packed(opts, _ptr(staged), int(staged_bytes), _ptr(off), _ptr(samples), _ptr(out), rows, T, float(pad),
+                                   _ptr(mean), _ptr(std), current_stream()), "cn_op_fbank_packed")
     return out
 
 

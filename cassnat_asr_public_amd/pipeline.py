@@ -63,7 +63,12 @@ class PackedBatch:
     per utterance the payload as the archive holds it - a read-only uint8 view from min_value on (``data.kaldi_io.mat_payload``) -
     its kind (1 / 2 / 3) and its rows; shape, lengths and ratios come from the headers.  The pipelines stage the payloads as they
     are, a quarter of the float32 bytes, and ``hip.unpack_compressed`` decompresses on the device; ``padded()`` - host
-    decompression with ``kaldi_io.decompress`` - is the definition of what it must produce."""
+    decompression with ``kaldi_io.decompress`` - is the definition of what it must produce.
+
+    The WAVE form (``from_waves``; ``kinds`` is the string "wave") keeps per utterance a read-only '<i2' view of the samples inside the
+    memory map of its sound file (``data.wave_io.pcm_view``); ``lens`` are the frame counts of the fbank front-end and ``shape`` the
+    padded FEATURE shape.  The pipelines stage the samples as they are and ``hip.fbank_packed`` computes the features on the
+    device; there is no host fbank in the product, so ``padded()`` and ``matrices()`` raise."""
 
     __slots__ = ("views", "lens", "shape", "dtype", "is_cuda", "kinds", "utts")
 
@@ -124,6 +129,32 @@ class PackedBatch:
         self.is_cuda = False
         return self
 
+    @classmethod
+    def from_waves(cls, views, frames, num_mel, utts=None):
+        """``views``: one '<i2', one-dimensional, C-contiguous array of samples per utterance; ``frames``: their frame counts under
+        the front-end's options (``Fbank.num_frames``).  Anything else - and an utterance of zero frames - raises a ValueError that
+        names the utterance."""
+        def name(b):
+            return "utterance %s" % (utts[b] if utts is not None else "#%d of the batch" % b)
+
+        if not views:
+            raise ValueError("PackedBatch: an empty batch")
+        if len(frames) != len(views):
+            raise ValueError("PackedBatch: %d frame counts for %d utterances" % (len(frames), len(views)))
+        for b, v in enumerate(views):
+            if not isinstance(v, np.ndarray) or v.dtype != np.dtype("<i2") or v.ndim != 1 or not v.flags.c_contiguous:
+                raise ValueError("PackedBatch: %s: the samples must be a one-dimensional C-contiguous '<i2' array (got %s)"
+                                 % (name(b), "%s %s" % (getattr(v, "dtype", type(v).__name__), getattr(v, "shape", ""))))
+            if int(frames[b]) < 1:
+                raise ValueError("PackedBatch: %s: %d samples give no frame" % (name(b), v.shape[0]))
+        self = cls.__new__(cls)
+        self.views, self.kinds, self.utts = list(views), "wave", utts
+        self.lens = [int(n) for n in frames]
+        self.shape = (len(views), max(self.lens), int(num_mel))
+        self.dtype = torch.float32
+        self.is_cuda = False
+        return self
+
     def ratios(self):
         """collate's ``ratios[b] = feat.shape[0] / t_max``: the Python (double) quotient rounded to float32"""
         t_max = self.shape[1]
@@ -133,6 +164,8 @@ class PackedBatch:
         """The utterances' float32 matrices on the host (the compressed form decompressed by ``kaldi_io.decompress``)."""
         if self.kinds is None:
             return self.views
+        if self.kinds == "wave":
+            raise NotImplementedError("PackedBatch: the wave form holds samples - the features exist on the device only (hip.fbank_packed)")
         from .data.kaldi_io import decompress
 
         names = {1: "CM", 2: "CM2", 3: "CM3"}
@@ -140,10 +173,18 @@ class PackedBatch:
 
     def padded(self, pad=0.0, cmvn=None):
         """The collated tensor itself (host): what the packed path must reproduce; used by the CPU rehearsal and the tests."""
+        if self.kinds == "wave":
+            raise NotImplementedError("PackedBatch: the wave form holds samples - the features exist on the device only (hip.fbank_packed)")
         out = np.full(self.shape, float(pad), np.float32)
         for b, v in enumerate(self.matrices()):
             out[b, : v.shape[0]] = v if cmvn is None else ((v.astype(np.float64) - cmvn[0]) / cmvn[1]).astype(np.float32)
         return torch.from_numpy(out)
+
+
+def _form(f):
+    """The staging form of a batch: None (a tensor, or float32 archive rows), "compressed" or "wave"."""
+    kinds = getattr(f, "kinds", None)
+    return None if kinds is None else ("wave" if isinstance(kinds, str) else "compressed")
 
 
 class _Job:
@@ -184,7 +225,7 @@ class _Pass:
 
 class DecodePipelines:
     def __init__(self, model, n_pipelines, batch, frames, with_weights=True, after_engine=None, coalesce=1, share_from=None,
-                 ragged=0.75, predict_rows=True, area_frames=None, cmvn=None, copy_threads=0):
+                 ragged=0.75, predict_rows=True, area_frames=None, cmvn=None, copy_threads=0, fbank=None):
         """``model``: a CassNAT holding the parameters; ``batch`` x ``frames``: the largest single batch a pipeline must take.
         The pipelines of one GPU share ONE device copy of the packed weights (``cn_model_create_shared``): the first engine
         packs them - or, with ``with_weights=False`` + ``after_engine(engine)`` (multi-GPU start-up), receives them by RCCL
@@ -204,8 +245,12 @@ class DecodePipelines:
         applied on the device right behind the host-to-device copy (``hip.cmvn_``: the reference's float64 arithmetic bit for bit)
         - the loader's float64 passes over the features were three quarters of its time.
         ``copy_threads`` > 1: the archive rows of a pass of ``PackedBatch``es are copied into page-locked memory by that many host
-        threads (inside ``cn_host_gather``) - what ``--load_data_workers`` means on the packed reader path."""
+        threads (inside ``cn_host_gather``) - what ``--load_data_workers`` means on the packed reader path.
+        ``fbank``: the front-end's option block (``hip.CnFbankOpts``, e.g. ``Fbank(...).o``) for passes of wave-form ``PackedBatch``es:
+        their samples are staged as the sound files hold them and ``hip.fbank_packed`` computes the features (``cmvn``, when given, is
+        applied there - statistics over fbank features)."""
         self.model = model
+        self.fbank = fbank
         self._fp16 = getattr(model, "hip_precision", "") == "fp16"  # (its scores are checked for the half range: hip.check_fp16_range)
         self._guarded = getattr(model, "hip_precision", "") in ("fp16", "bf16x3")  # (engines with a feature-range guard: Engine.check_range)
         self.copy_threads = max(0, int(copy_threads))
@@ -247,7 +292,7 @@ class DecodePipelines:
         self._rows_lock = threading.Lock()
         self._stats_lock = threading.Lock()
         self.timeline = None  # a list: the workers and the consumer append (label, pipeline, perf_counter) - bench.py --host-timeline
-        self.stats = {"passes": 0, "batches": 0, "predicted": 0, "missed": 0, "merged_ragged": 0, "compressed_passes": 0,
+        self.stats = {"passes": 0, "batches": 0, "predicted": 0, "missed": 0, "merged_ragged": 0, "compressed_passes": 0, "wave_passes": 0,
                       # host seconds of the worker threads, by what they were doing (summed over the pipelines)
                       "s_take": 0.0, "s_stage": 0.0, "s_launch": 0.0, "s_retire_wait": 0.0}
 
@@ -374,7 +419,7 @@ class DecodePipelines:
             f = nxt[0]
             T = int(f.shape[1])
             hi, lo = max(tmax, T), min(tmin, T)
-            ok = (type(f) is type(f0) and (getattr(f, "kinds", None) is None) == (getattr(f0, "kinds", None) is None)
+            ok = (type(f) is type(f0) and _form(f) == _form(f0)
                   and tuple(f.shape[2:]) == tuple(f0.shape[2:]) and f.dtype == f0.dtype and nxt[1].dtype == items[0][1].dtype
                   and lo >= self.ragged * hi and self.fits(rows + int(f.shape[0]), hi))
             if ok and ahead.acquire(blocking=False):
@@ -400,6 +445,13 @@ class DecodePipelines:
         rows = sum(b.shape[0] for b in batches)
         tmax = max(b.shape[1] for b in batches)
         F = batches[0].shape[2]
+        forms = set(_form(b) for b in batches)
+        if "wave" in forms:
+            if len(forms) > 1:
+                raise ValueError("DecodePipelines: a pass mixes wave batches with another form of packed batch")
+            if not on_gpu:
+                raise NotImplementedError("DecodePipelines: the wave form has no CPU rehearsal (the fbank front-end runs on the device only)")
+            return self._stage_wave(k, slot, items, pad, rows, tmax, F, torch.device("cuda", device))
         if not on_gpu:  # CPU rehearsal of the host logic: the collated tensors themselves
             feats = torch.full((rows, tmax, F), float(pad))
             o = 0
@@ -500,6 +552,58 @@ class DecodePipelines:
         hip.unpack_compressed(bufs["dev"], bufs["meta_d"][:utts], bufs["meta_d"][utts:2 * utts], bufs["meta_d"][3 * utts:4 * utts], feats, pad,
                               stats[0], stats[1])
         self._bump("compressed_passes", 1)
+        return feats, bufs["meta_d"][2 * utts:2 * utts + rows].view(torch.float32)
+
+    def _stage_wave(self, k, slot, items, pad, rows, tmax, F, dev_):
+        """A pass of wave-form ``PackedBatch``es: every utterance's int16 samples go into the slot's page-locked buffer as its sound
+        file holds them, each at a 16-byte-aligned offset (one ``cn_host_gather`` call), ONE DMA takes those bytes to the device, the
+        per-utterance (byte offset, samples, ratio) follow in the small DMA, and ``hip.fbank_packed`` computes the padded
+        (rows, tmax, F) features, normalised with the pipelines' statistics when they have them.  The buffers are sized in bytes: a
+        frame shift of samples is 320 bytes at the default options, what 80 float32 features take."""
+        from . import hip
+
+        if self.fbank is None:
+            raise ValueError("DecodePipelines: a wave batch, but the pipelines were built without fbank options")
+        batches = [x[0] for x in items]
+        if F != int(self.fbank.num_mel) or any(b.shape[2] != F for b in batches):
+            raise ValueError("DecodePipelines: wave batches of %d features, the front-end computes %d" % (F, int(self.fbank.num_mel)))
+        views = [v for b in batches for v in b.views]
+        offs, total = hip.gather_offsets([v.nbytes for v in views], 16)
+        if total >= 2 ** 31:
+            raise ValueError("DecodePipelines: a pass of %d sample bytes (the offsets are int32)" % total)
+        shift = max(1, int(self.fbank.sample_rate * 0.001 * self.fbank.frame_shift_ms))
+        flen = int(self.fbank.sample_rate * 0.001 * self.fbank.frame_length_ms)
+        key = ("wave", slot)
+        bufs = self._packed[k].get(key)
+        if bufs is None or bufs["cap"] < total or bufs["F"] != F or bufs["utts"] < rows:
+            utts = max(rows, self.max_utts)
+            cap = max(total, 2 * self.max_batch * self.frames_cap * shift + utts * (2 * flen + 16))
+            bufs = {"cap": cap, "F": F, "utts": utts,
+                    "host": torch.empty(cap, dtype=torch.uint8, pin_memory=True),
+                    "dev": torch.empty(cap, dtype=torch.uint8, device=dev_),
+                    # per utterance: byte offset, samples, float32 ratio (as int32 bits) - one small DMA
+                    "meta_h": torch.empty(3 * utts, dtype=torch.int32, pin_memory=True),
+                    "meta_d": torch.empty(3 * utts, dtype=torch.int32, device=dev_),
+                    "out": torch.empty(max(rows * tmax, self.max_batch * self.frames_cap) * F, dtype=torch.float32, device=dev_)}
+            self._packed[k][key] = bufs
+        if bufs["out"].numel() < rows * tmax * F:
+            bufs["out"] = torch.empty(rows * tmax * F, dtype=torch.float32, device=dev_)
+        hip.host_gather(bufs["host"].data_ptr(), views, max(1, self.copy_threads), align=16)
+        meta = bufs["meta_h"].numpy()
+        utts = bufs["utts"]
+        meta[:rows] = offs
+        meta[utts:utts + rows] = [v.shape[0] for v in views]
+        meta[2 * utts:2 * utts + rows] = torch.cat([x[1] for x in items], 0).numpy().view(np.int32)
+        bufs["dev"][:total].copy_(bufs["host"][:total], non_blocking=True)
+        bufs["meta_d"].copy_(bufs["meta_h"], non_blocking=True)
+        feats = bufs["out"][: rows * tmax * F].view(rows, tmax, F)
+        stats = (None, None)
+        if self.cmvn is not None:
+            stats = self._cmvn_dev.get(self._device)
+            if stats is None:
+                stats = self._cmvn_dev[self._device] = (torch.from_numpy(self.cmvn[0]).to(dev_), torch.from_numpy(self.cmvn[1]).to(dev_))
+        hip.fbank_packed(self.fbank, bufs["dev"], total, bufs["meta_d"][:utts], bufs["meta_d"][utts:2 * utts], feats, pad, stats[0], stats[1])
+        self._bump("wave_passes", 1)
         return feats, bufs["meta_d"][2 * utts:2 * utts + rows].view(torch.float32)
 
     def _stage_inputs(self, k, slot, items, pad):

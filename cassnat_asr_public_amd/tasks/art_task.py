@@ -154,6 +154,7 @@ class ArtTask(BaseTask):
                                 i, (utt_list, feats, _, feat_sizes, _) = next(it)
                             except StopIteration:
                                 break
+                        feats, feat_sizes = self.wave_features(feats, feat_sizes)  # (audio input: fbank on this worker's stream)
                         src_mask = (feats[:, :, 0] != args.padding_idx).unsqueeze(1)
                         if args.decode_type == "ctc_only":
                             recog = ctc_beam_decode(self.model, feats, src_mask, feat_sizes, self.vocab, args, self.lm_model, engine=engines[k])

@@ -41,6 +41,30 @@ class BaseTask(object):
         testset = SpeechDataset(self.vocab, args.test_paths, args)
         if getattr(args, "use_cmvn", False):
             testset._load_cmvn(args.global_cmvn)
+        if testset.is_wave:  # audio input: the front-end must produce what the model reads
+            want = int(getattr(args, "n_features", getattr(args, "input_size", testset.num_mel)))
+            if want != testset.num_mel or int(getattr(args, "input_size", want)) != testset.num_mel:
+                raise ValueError("audio input: the fbank front-end computes %d mel bins, the model reads n_features / input_size = %d / %d"
+                                 % (testset.num_mel, want, int(getattr(args, "input_size", want))))
         self.test_loader = SpeechDataLoader(testset, args.batch_size, args.padding_idx,
                                             num_workers=args.load_data_workers, shuffle=False, indices=indices)
+        self._pad_value, self._fbank = float(args.padding_idx), None
         print("Finish Loading test files. Number batches: {}".format(len(self.test_loader)))
+
+    def wave_features(self, feats, feat_sizes):
+        """A wave set's batch (``WaveBatch``: int16 samples) -> (feats (B, T, num_mel) cuda, length ratios) on the caller's current
+        stream, the global CMVN applied when the dataset has statistics (``Fbank.packed``); any other batch passes through."""
+        from ..data.speech_loader import WaveBatch
+
+        if not isinstance(feats, WaveBatch):
+            return feats, feat_sizes
+        fb = getattr(self, "_fbank", None)
+        if fb is None:
+            from ..data.fbank import Fbank
+
+            ds = self.test_loader.dataset
+            o = ds.fbank_opts
+            fb = Fbank(cmvn_mean=ds.mean if ds.use_cmvn else None, cmvn_std=ds.std if ds.use_cmvn else None,
+                       pad_value=float(getattr(self, "_pad_value", 0.0)), **{name: getattr(o, name) for name, _ in o._fields_ if name != "reserved"})
+            self._fbank = fb
+        return fb.packed(feats.views, utts=feats.utts)

@@ -103,6 +103,11 @@ class CassNATTask(BaseTask):
             if all(utt in table for utt, _ in entries):
                 return np.array([table[utt] for utt, _ in entries])
         if need:
+            from ..data import speech_loader, wave_io
+
+            if speech_loader.sniff_wave_set(entries, getattr(args, "hip_audio", "auto")):  # audio input: from the WAV headers
+                opts = speech_loader.front_end_options(args)
+                return np.array([speech_loader.frames_of(opts, wave_io.num_samples(spec, opts.sample_rate, utt)) for utt, spec in entries])
             return np.array([kaldi_io.mat_rows(spec) for _, spec in entries])
         return np.zeros(len(entries))
 
@@ -176,6 +181,7 @@ class CassNATTask(BaseTask):
             self.model.eval()
             for i, (utt_list, feats, labels, feat_sizes, label_sizes) in enumerate(self.test_loader):
                 frames += int(feats.shape[0] * feats.shape[1])
+                feats, feat_sizes = self.wave_features(feats, feat_sizes)  # (audio input: fbank + CMVN on the device)
                 src_mask = (feats[:, :, 0] != args.padding_idx).unsqueeze(1)
                 if args.decode_type == "ctc_only":  # src/tasks/cassnat_task.py:335-336
                     recog = ctc_beam_decode(self.model, feats, src_mask, feat_sizes, self.vocab, args, ctc_lm)
@@ -212,31 +218,39 @@ class CassNATTask(BaseTask):
         # on the device.  It applies to the shipped configuration (float32 archives, no splicing, no frame skipping) and replaces
         # the DataLoader altogether - its worker PROCESSES had to pickle every batch through shared memory (8.5k utt/s and nine
         # seconds to the first batch with the recipes' `--load_data_workers 4`); that flag now sets the number of copy THREADS.
-        defer_ok = bool(ds is not None and hasattr(ds, "can_defer_cmvn") and ds.can_defer_cmvn() and int(getattr(args, "hip_device_cmvn", 1)))
+        # A wave set (audio input) always takes the packed reader's wave form: samples staged as the sound files hold them, fbank
+        # and CMVN on the device (--hip_packed_reader / --hip_device_cmvn choose between HOST paths, which audio does not have)
+        wave = bool(getattr(ds, "is_wave", False))
+        defer_ok = wave or bool(ds is not None and hasattr(ds, "can_defer_cmvn") and ds.can_defer_cmvn() and int(getattr(args, "hip_device_cmvn", 1)))
         # ... to a test set that is float32 (`FM `) throughout, or COMPRESSED throughout (Kaldi's `CM` / `CM2` / `CM3`, what
         # make_fbank.sh writes; the kinds may mix, as they do inside one copy-feats archive): the payloads are then staged as the
         # archive holds them and decompressed on the device.  Decided from every utterance's header; a set that mixes the two
         # families keeps the collated DataLoader path (which reads all of them, and still defers the CMVN)
         kinds = ds.matrix_kinds() if defer_ok and hasattr(ds, "matrix_kinds") else frozenset(["FM"])
-        one_family = kinds <= {"FM"} or kinds <= set(kaldi_io.COMPRESSED_KINDS)
-        packed = bool(defer_ok and one_family and int(getattr(args, "hip_packed_reader", 1)) and hasattr(self.test_loader, "batch_sampler"))
-        compressed = bool(packed and not kinds <= {"FM"})  # (the packed reader's compressed form)
+        one_family = wave or kinds <= {"FM"} or kinds <= set(kaldi_io.COMPRESSED_KINDS)
+        packed = bool(defer_ok and one_family and (wave or int(getattr(args, "hip_packed_reader", 1))) and hasattr(self.test_loader, "batch_sampler"))
+        if wave and not packed:
+            raise NotImplementedError("audio input needs the loader's batch_sampler (the packed reader's wave form)")
+        compressed = bool(packed and not wave and not kinds <= {"FM"})  # (the packed reader's compressed form)
         dev_cmvn = bool(defer_ok and getattr(ds, "use_cmvn", False) and (packed or getattr(self.test_loader, "num_workers", 0) == 0))
         if dev_cmvn:
             ds.device_cmvn = True
         try:
-            return self._decode_pipelined_run(args, n_pipes, results, batch_time, progress, sos, (ds.mean, ds.std) if dev_cmvn else None, packed, compressed)
+            return self._decode_pipelined_run(args, n_pipes, results, batch_time, progress, sos, (ds.mean, ds.std) if dev_cmvn else None, packed, compressed, wave)
         finally:
             if dev_cmvn:
                 ds.device_cmvn = False
 
-    def _decode_pipelined_run(self, args, n_pipes, results, batch_time, progress, sos, cmvn, packed=False, compressed=False):
+    def _decode_pipelined_run(self, args, n_pipes, results, batch_time, progress, sos, cmvn, packed=False, compressed=False, wave=False):
         from ..data import kaldi_io
         from ..pipeline import DecodePipelines, PackedBatch
 
         ds = getattr(self.test_loader, "dataset", None)
         feat_dim = None
-        if packed:
+        if wave:  # (frame counts from the WAV headers, read when the dataset was built)
+            first_len = max(ds.wave_frames[i] for i in list(self.test_loader.batch_sampler)[0])
+            feat_dim = ds.num_mel
+        elif packed:
             first = [ds._items[i][1] for i in list(self.test_loader.batch_sampler)[0]]
             first_len = max(kaldi_io.mat_rows(spec) for spec in first)
             feat_dim = kaldi_io.mat_payload(first[0])[2]
@@ -251,19 +265,28 @@ class CassNATTask(BaseTask):
 
         cmvn_id = None if cmvn is None else hashlib.sha1(np.ascontiguousarray(cmvn[0]).tobytes() + np.ascontiguousarray(cmvn[1]).tobytes()).hexdigest()
         key = (n_pipes, args.batch_size, max_frames, int(getattr(args, "hip_coalesce", 10)), float(getattr(args, "hip_ragged", 0.75)),
-               cmvn_id, self.model.weights_key(), packed, compressed, int(getattr(args, "load_data_workers", 0)) if packed else 0)
+               cmvn_id, self.model.weights_key(), packed, compressed, bytes(ds.fbank_opts) if wave else None,
+               int(getattr(args, "load_data_workers", 0)) if packed else 0)
         pipes = getattr(self, "_pipes", None)
         if pipes is None or self._pipes_key != key:  # (kept for further decode() calls on this task: engines, threads, streams)
             if pipes is not None:
                 pipes.close()
             pipes = DecodePipelines(self.model, n_pipes, args.batch_size, max_frames, with_weights=(self.rank == 0),
                                     after_engine=(lambda e: cdist.broadcast_weights(e, src=0)) if self.world > 1 else None,
-                                    coalesce=-max(1, key[3]), ragged=key[4], cmvn=cmvn, copy_threads=key[-1])
+                                    coalesce=-max(1, key[3]), ragged=key[4], cmvn=cmvn, copy_threads=key[-1],
+                                    fbank=ds.fbank_opts if wave else None)
             self._pipes, self._pipes_key = pipes, key
         stats0 = dict(pipes.stats)
         meta, frames, i, end = {}, 0, -1, time.time()
 
         def batches():
+            if wave:  # the loader's batches as views into the memory maps of the sound files (a map lives as long as its pass)
+                for j, idx in enumerate(self.test_loader.batch_sampler):
+                    got = [ds[i] for i in idx]
+                    pb = PackedBatch.from_waves([v for _, v, _ in got], [ds.wave_frames[i] for i in idx], feat_dim, utts=[u for u, _, _ in got])
+                    meta[j] = ([u for u, _, _ in got], [None] * len(got), pb.shape[0] * pb.shape[1], max(len(t) for _, _, t in got))
+                    yield pb, pb.ratios(), j
+                return
             if packed:  # the loader's batches (same utterances, same order) as views into the archives' memory maps
                 for j, idx in enumerate(self.test_loader.batch_sampler):
                     items = [ds._items[i] for i in idx]

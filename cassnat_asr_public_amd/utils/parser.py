@@ -50,6 +50,16 @@ class DecodeParser(object):
                        help="1 (default): the pipelined decoder applies the global CMVN on the device, behind the host-to-device copy "
                             "(float64 arithmetic, bit-identical to the dataset's), when the dataset neither splices nor skips frames "
                             "and runs without loader workers; 0: always in the dataset, as the reference does")
+        p.add_argument("--hip_audio", default="auto", choices=["auto", "0", "1"],
+                       help="decode from audio: auto (default) - a --data_path whose entries are RIFF/WAVE files (a wav.scp of plain "
+                            "paths: 16-bit PCM, one channel) is decoded from the sound files, the Kaldi fbank features computed on the "
+                            "device; 0: never look, the entries are feature matrices; 1: the entries must be WAV files")
+        p.add_argument("--hip_fbank_conf", default="", type=str,
+                       help="Kaldi option file of the fbank front-end for audio input (--name=value lines: sample-frequency, frame-length, "
+                            "frame-shift, preemphasis-coefficient, remove-dc-offset, window-type, num-mel-bins, low-freq, high-freq, "
+                            "use-power, use-log-fbank).  Default: the built-in options, which are those of the reference's conf/fbank.conf "
+                            "(hamming window, 16 kHz, 80 mel bins, no energy).  Dither is not implemented: an absent --dither means 0 "
+                            "(Kaldi's default of 1.0 adds noise that cannot be compared), a non-zero one is refused")
         p.add_argument("--hip_dist_backend", default="nccl", choices=["nccl", "gloo"],
                        help="torch.distributed backend under torch.distributed.run (nccl = RCCL over xGMI; gloo: rehearsal of the "
                             "N-rank path, also with several ranks on one GPU)")

@@ -384,6 +384,16 @@ int32_t cn_fbank_num_frames(const cn_fbank_opts* o, int32_t num_samples);
 int cn_fbank(const cn_fbank_opts* o, const float* wave_dev, const int32_t* num_samples_dev, int32_t B, int32_t max_samples,
              const float* cmvn_mean_dev, const float* cmvn_istd_dev, float* feats_dev, int32_t Tmax, float pad_value,
              void* stream);
+/* The same front-end behind the packed reader (audio input): staged_dev holds the utterances' little-endian int16 samples exactly as
+ * the WAV `data` chunks hold them, utterance r (samples_dev[r] samples) at BYTE offset off_dev[r], a multiple of 16.  Frame t of
+ * utterance r exists for t < cn_fbank_num_frames(samples[r]); out_dev[r][t][:] (rows, T, num_mel) is cn_fbank's value for it bit for
+ * bit (the two kernels share the frame arithmetic; int16 -> float is exact) and `pad` for later t.  With statistics (float64,
+ * [num_mel]) the value stored is float((double(e) - mean) / std): cn_op_unpack_rows' arithmetic, not cn_fbank's float32 form - audio
+ * plus global CMVN equals an `FM ` archive of the un-normalised features plus the same CMVN.  Nothing outside [0, staged_bytes) is
+ * read.  Refused without a launch: a null pointer, rows / T / num_mel <= 0, a frame of more than 512 samples. */
+int cn_op_fbank_packed(const cn_fbank_opts* o, const void* staged_dev, int64_t staged_bytes, const int32_t* off_dev,
+                       const int32_t* samples_dev, float* out_dev, int32_t rows, int32_t T, float pad, const double* mean_dev,
+                       const double* std_dev, void* stream);
 
 /* ---- single-kernel entry points (parity tests drive each hand-written kernel through the ABI) ---------- */
 /* all pointers device; `precision` selects the element type of activations/weights: CN_PRECISION_F32, CN_PRECISION_BF16 or
