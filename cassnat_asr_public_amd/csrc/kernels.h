@@ -93,6 +93,10 @@ int launch_unpack_rows(const float* packed, const int* off, const int* len, floa
 // (a multiple of 16) of `staged` -> decompressed in Kaldi's float32 arithmetic, normalised, padded
 int launch_unpack_compressed(const unsigned char* staged, const int* off, const int* len, const int* kind, float* out, int rows, int T,
                              int F, float pad, const double* mean, const double* sd, hipStream_t s);
+// float32 rows (utterance r: len[r] rows of F0 values at row off[r]) -> the spliced, frame-skipped, padded batch
+// (rows, T_out, (left + right + 1) * F0), optional global CMVN in float64: the dataset's context_feat / skip_feat on the device
+int launch_splice_rows(const float* src, const int* off, const int* len, float* out, int rows, int T_out, int F0, int left, int right,
+                       int skip, float pad, const double* mean, const double* sd, hipStream_t s);
 // per row of logits [M][V] (fp32): first-index argmax, max log-prob; optionally rewrites the row as log-softmax.
 int launch_logsoftmax_argmax(float* logits, int M, int V, int ldl, int* arg, float* maxlp, int write_logp,
                              hipStream_t s);

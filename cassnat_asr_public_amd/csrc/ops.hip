@@ -642,6 +642,17 @@ extern "C" int cn_op_unpack_compressed(const void* staged_dev, const int32_t* of
                                     mean_dev, std_dev, (hipStream_t)stream);
 }
 
+extern "C" int cn_op_splice_rows(const float* src_dev, const int32_t* off_dev, const int32_t* len_dev, float* out_dev, int32_t rows,
+                                 int32_t T_out, int32_t F0, int32_t left, int32_t right, int32_t skip, float pad, const double* mean_dev,
+                                 const double* std_dev, void* stream) {
+    if (!src_dev || !off_dev || !len_dev || !out_dev || (!mean_dev) != (!std_dev)) {
+        cn_set_error("cn_op_splice_rows: null argument (mean and std come together)");
+        return -1;
+    }
+    return launch_splice_rows(src_dev, off_dev, len_dev, out_dev, rows, T_out, F0, left, right, skip, pad, mean_dev, std_dev,
+                              (hipStream_t)stream);
+}
+
 extern "C" int cn_op_quantize_fp8(const void* src_bf16_dev, int32_t ld, void* dst_dev, int32_t M, int32_t K, float scale,
                                   void* stream) {
     return launch_quantize_fp8(src_bf16_dev, ld, dst_dev, M, K, scale, (hipStream_t)stream);

@@ -931,6 +931,123 @@ int launch_unpack_compressed(const unsigned char* staged, const int* off, const 
     return 0;
 }
 
+// ---- frame splicing and skipping behind the same hand-over (src/data/speech_loader.py:141-158, src/data/feat_op.py:4-31) -----------
+// The recipes' decode YAMLs read spliced frames (left_ctx 0, right_ctx 2, skip_frame 1: 240 values from 80).  Per utterance r with
+// T = len[r] source rows of F0 values at row off[r]:
+//   Tp    = skip > 1 ? T rounded up to a multiple of skip : T       (the dataset appends rows of literal zeros AFTER the CMVN)
+//   n_out = skip > 1 ? Tp / skip : T                                 (clamped to T_out)
+//   out[r][t][k * F0 + f] = pad                                      for t >= n_out, else with s = clamp(t * skip + k - left, 0, Tp - 1)
+//                         = s < T ? norm(src[off[r] + s][f]) : 0.0f  (norm as in unpack_rows_kernel; edge rows are replicated - behind
+//                                                                     appended zero rows the right edge replicates a ZERO row)
+// One workgroup per (utterance, chunk of output frames).  The chunk's source span - (chunk - 1) * skip + left + right + 1 rows - is
+// normalised into LDS once (the float64 divide runs per source element, not per copy of it); since block k of output frame i is span
+// row i * skip + k, a whole output row is ONE contiguous window of (left + right + 1) * F0 floats of the span, starting at row
+// i * skip.  Span rows that no output frame reads (skip > left + right + 1) are not staged.  Nothing at or behind row len[r] of an
+// utterance is read: a padded source whose tail holds anything at all (the second calling form, off[r] = r * T0) is fine.
+#define SP_CHUNK 32
+#define SP_LDS_FLOATS 12288  // 48 KB: the span a workgroup may hold; the launcher shrinks the chunk to fit
+#define SP_MAX_CTX 64        // left, right
+#define SP_MAX_SKIP 64
+__global__ __launch_bounds__(256) void splice_rows_kernel(const float* __restrict__ src, const int* __restrict__ off, const int* __restrict__ len,
+                                                          float* __restrict__ out, int T_out, int F0, int left, int right, int sk, int chunk,
+                                                          float pad, const double* __restrict__ mean, const double* __restrict__ sd) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    float* span = reinterpret_cast<float*>(smem);
+    const int r = blockIdx.y;
+    const long long t0 = (long long)blockIdx.x * chunk;
+    if (t0 >= T_out) return;
+    const int tn = (int)((T_out - t0) < chunk ? (T_out - t0) : chunk);
+    const int T = len[r] < 0 ? 0 : len[r];
+    const long long Tp = sk > 1 ? ((long long)T + sk - 1) / sk * sk : (long long)T;
+    long long n_out = Tp / sk;
+    if (n_out > T_out) n_out = T_out;
+    const int tv = (int)((n_out - t0) <= 0 ? 0 : ((n_out - t0) < tn ? (n_out - t0) : tn));  // output frames of this chunk that hold data
+    const int ctx = left + right, W = (ctx + 1) * F0;
+    const int span_rows = tv > 0 ? (tv - 1) * sk + ctx + 1 : 0;
+    const long long lo = t0 * sk - left;  // source row of span row 0 (before clamping)
+    const float* sb = src + (long long)off[r] * F0;
+    float* dst = out + ((long long)r * T_out + t0) * W;
+    const bool sparse = ctx + 1 < sk;  // span rows j with j % sk > ctx belong to no output frame
+    if ((F0 & 3) == 0 && (((size_t)sb | (size_t)dst) & 15) == 0) {
+        const int q = F0 >> 2;
+        for (int idx = threadIdx.x; idx < span_rows * q; idx += 256) {
+            const int j = idx / q, c = (idx - j * q) * 4;
+            if (sparse && (j % sk) > ctx) continue;
+            long long s = lo + j;
+            s = s < 0 ? 0 : (s > Tp - 1 ? Tp - 1 : s);
+            f32x4 v = {0.f, 0.f, 0.f, 0.f};
+            if (s < T) {
+                v = *reinterpret_cast<const f32x4*>(sb + s * F0 + c);
+                if (mean) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] = (float)(((double)v[e] - mean[c + e]) / sd[c + e]);
+                }
+            }
+            *reinterpret_cast<f32x4*>(span + j * F0 + c) = v;
+        }
+        __syncthreads();
+        const int wq = W >> 2;
+        for (int idx = threadIdx.x; idx < tn * wq; idx += 256) {
+            const int i = idx / wq, c = (idx - i * wq) * 4;
+            f32x4 v = {pad, pad, pad, pad};
+            if (i < tv) v = *reinterpret_cast<const f32x4*>(span + i * sk * F0 + c);
+            *reinterpret_cast<f32x4*>(dst + (long long)i * W + c) = v;
+        }
+    } else {
+        for (int idx = threadIdx.x; idx < span_rows * F0; idx += 256) {
+            const int j = idx / F0, c = idx - j * F0;
+            if (sparse && (j % sk) > ctx) continue;
+            long long s = lo + j;
+            s = s < 0 ? 0 : (s > Tp - 1 ? Tp - 1 : s);
+            float v = 0.f;
+            if (s < T) {
+                v = sb[s * F0 + c];
+                if (mean) v = (float)(((double)v - mean[c]) / sd[c]);
+            }
+            span[idx] = v;
+        }
+        __syncthreads();
+        for (int idx = threadIdx.x; idx < tn * W; idx += 256) {
+            const int i = idx / W, c = idx - i * W;
+            dst[idx] = i < tv ? span[i * sk * F0 + c] : pad;
+        }
+    }
+}
+
+int launch_splice_rows(const float* src, const int* off, const int* len, float* out, int rows, int T_out, int F0, int left, int right,
+                       int skip, float pad, const double* mean, const double* sd, hipStream_t s) {
+    if (rows <= 0 || T_out <= 0 || F0 <= 0) {
+        cn_set_error("splice_rows: rows, T_out and F0 must be positive");
+        return -1;
+    }
+    if (left < 0 || right < 0 || skip < 0 || left > SP_MAX_CTX || right > SP_MAX_CTX || skip > SP_MAX_SKIP) {
+        cn_set_error("splice_rows: need 0 <= left, right <= 64 and 0 <= skip <= 64");
+        return -1;
+    }
+    if (rows > 65535) {
+        cn_set_error("splice_rows: more than 65535 utterances in one pass");
+        return -1;
+    }
+    const int sk = skip < 1 ? 1 : skip;  // (skip_feat: 0 and 1 both keep every frame)
+    const long long W = (long long)(left + right + 1) * F0;
+    if (W > SP_LDS_FLOATS) {
+        cn_set_error("splice_rows: a spliced row of more than 12288 values does not fit the kernel's LDS");
+        return -1;
+    }
+    if ((long long)rows * T_out * W > 0x7fffffffLL || (long long)T_out * sk > 0x7fffffffLL) {
+        cn_set_error("splice_rows: the batch (rows x T_out x spliced width) overflows 32-bit indexing");
+        return -1;
+    }
+    // the largest chunk of output frames whose source span fits the LDS (32 for the recipes' shapes; 1 always fits: W floats)
+    int chunk = SP_CHUNK;
+    while (chunk > 1 && ((long long)(chunk - 1) * sk + left + right + 1) * F0 > SP_LDS_FLOATS) --chunk;
+    const size_t lds = (size_t)((chunk - 1) * sk + left + right + 1) * F0 * sizeof(float);
+    hipLaunchKernelGGL(splice_rows_kernel, dim3((unsigned)cn_ceil_div(T_out, chunk), (unsigned)rows), dim3(256), lds, s, src, off, len, out,
+                       T_out, F0, left, right, sk, chunk, pad, mean, sd);
+    CN_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
 int launch_cmvn(float* x, const int* len, const double* mean, const double* sd, int B, int T, int F, hipStream_t s) {
     if (B <= 0 || T <= 0 || F <= 0) return 0;
     const int per = cn_ceil_div(T * F, 256);

@@ -69,8 +69,12 @@ def parse_conf(path):
 
 
 class Fbank:
-    def __init__(self, cmvn_mean=None, cmvn_std=None, pad_value=0.0, device=None, **opts):
-        """opts: sample_rate, frame_length_ms, frame_shift_ms, preemph, low_freq, high_freq, num_mel, window, remove_dc, ..."""
+    def __init__(self, cmvn_mean=None, cmvn_std=None, pad_value=0.0, device=None, splice=None, **opts):
+        """opts: sample_rate, frame_length_ms, frame_shift_ms, preemph, low_freq, high_freq, num_mel, window, remove_dc, ...
+        ``splice`` = (left, right, skip): ``packed()`` splices and skips the normalised frames as the dataset does (``hip.splice_rows``)."""
+        from .speech_loader import splice_triple
+
+        self.splice = splice_triple(*splice) if splice else None
         self.L = hip.lib()
         self.o = hip.CnFbankOpts()
         self.L.cn_fbank_default_opts(self.o)
@@ -131,7 +135,21 @@ class Fbank:
             staged = host.to(self.device, non_blocking=True)
             meta_d = meta.to(self.device, non_blocking=True)
             hip.fbank_packed(self.o, staged, total, meta_d[:B], meta_d[B:], feats, self.pad_value, self.mean64, self.std64)
-        return feats, torch.tensor([n / T for n in frames], dtype=torch.float32)
+            if self.splice is None:
+                return feats, torch.tensor([n / T for n in frames], dtype=torch.float32)
+            # the set splices / skips: a second launch reads the normalised batch (utterance b at row b * T, its own frames only)
+            from .speech_loader import spliced_frames
+
+            left, right, skip = self.splice
+            n_out = [spliced_frames(n, self.splice) for n in frames]
+            sp = torch.empty(2 * B, dtype=torch.int32, pin_memory=True)
+            spv = sp.numpy()
+            spv[:B] = np.arange(B, dtype=np.int64) * T
+            spv[B:] = frames
+            sp_d = sp.to(self.device, non_blocking=True)
+            out = torch.empty(B, max(n_out), (left + right + 1) * self.o.num_mel, dtype=torch.float32, device=self.device)
+            hip.splice_rows(feats, sp_d[:B], sp_d[B:], out, left, right, skip, self.pad_value)
+        return out, torch.tensor([n / max(n_out) for n in n_out], dtype=torch.float32)
 
     def __call__(self, waves):
         """waves: list of 1-D arrays / tensors on the int16 scale (what Kaldi reads from a wav file)."""

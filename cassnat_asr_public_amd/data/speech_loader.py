@@ -36,17 +36,47 @@ class SingleSet(object):
         return len(self.items)
 
 
+def splice_triple(left, right, skip):
+    """(left, right, skip) of a set that splices or skips frames, None for one that does neither (skip 0 and 1 both keep every
+    frame: feat_op.skip_feat)."""
+    left, right, skip = int(left), int(right), max(1, int(skip))
+    return None if (left == 0 and right == 0 and skip == 1) else (left, right, skip)
+
+
+def spliced_frames(n, splice):
+    """Rows the dataset hands out for an utterance of ``n`` source rows: zero rows are appended up to a multiple of ``skip`` before
+    every ``skip``-th row is kept (src/data/speech_loader.py:150-156), so n_out = ceil(n / skip); splicing keeps the count."""
+    if not splice or splice[2] <= 1:
+        return int(n)
+    return -(-int(n) // splice[2])
+
+
+def splice_host(mat, splice, cmvn=None):
+    """Steps 1-4 of the dataset's general path on one matrix: the CMVN in float64, rows of literal zeros up to a multiple of skip,
+    ``context_feat``, ``skip_feat``.  What collate then rounds to float32 - the definition the device kernel (``hip.splice_rows``)
+    is held to."""
+    left, right, skip = splice if splice else (0, 0, 1)
+    feat = mat if cmvn is None else (mat - cmvn[0]) / cmvn[1]
+    rem = feat.shape[0] % skip if skip > 1 else 0
+    if rem:
+        feat = np.vstack([feat, np.zeros((skip - rem, feat.shape[1]))])
+    return skip_feat(context_feat(feat, left, right), skip)
+
+
 class WaveBatch(object):
     """What a wave set's collate puts where the padded feature tensor would stand: the utterances' int16 sample views and their
-    frame counts.  ``shape`` is the padded FEATURE shape (B, longest frame count, num_mel), so that batch counting, progress
-    printing and ``first.shape[1]`` work as for a tensor; the features themselves are computed on the device, in the task's own
-    process (``Fbank.packed`` / the packed reader's wave form)."""
+    frame counts.  ``shape`` is the padded FEATURE shape (B, longest frame count, num_mel) - with a ``splice`` triple the spliced one,
+    (B, longest spliced count, (left + right + 1) * num_mel); ``frames`` stay the front-end's own counts -, so that batch counting,
+    progress printing and ``first.shape[1]`` work as for a tensor; the features themselves are computed on the device, in the task's
+    own process (``Fbank.packed`` / the packed reader's wave form)."""
 
-    __slots__ = ("views", "frames", "utts", "shape", "dtype", "is_cuda")
+    __slots__ = ("views", "frames", "utts", "shape", "dtype", "is_cuda", "splice")
 
-    def __init__(self, views, frames, num_mel, utts=None):
+    def __init__(self, views, frames, num_mel, utts=None, splice=None):
         self.views, self.frames, self.utts = list(views), [int(n) for n in frames], utts
-        self.shape = (len(self.views), max(self.frames), int(num_mel))
+        self.splice = splice_triple(*splice) if splice else None
+        blocks = (self.splice[0] + self.splice[1] + 1) if self.splice else 1
+        self.shape = (len(self.views), max(spliced_frames(n, self.splice) for n in self.frames), blocks * int(num_mel))
         self.dtype = torch.float32
         self.is_cuda = False
 
@@ -122,9 +152,11 @@ class SpeechDataset(Dataset):
         """A wave set: the entries are sound files, the dataset hands out (utt, int16 view, text) and the features are computed on
         the device by the consumer.  Every header is checked here - format, rate, at least one frame - so that a bad file is named
         before anything is decoded."""
-        if not (self.left_context == 0 and self.right_context == 0 and self.skip_frame <= 1):
-            raise NotImplementedError("audio input with left_ctx / right_ctx / skip_frame other than 0 / 0 / 1 (splicing and frame "
-                                      "skipping on audio input are not implemented)")
+        if self.left_context != 0:
+            raise NotImplementedError("audio input with left_ctx = %d (right_ctx >= 0 and skip_frame >= 1 are spliced on the device; a "
+                                      "left context on audio input is not implemented)" % self.left_context)
+        if self.right_context < 0 or self.skip_frame < 0:
+            raise ValueError("audio input: right_ctx = %d, skip_frame = %d" % (self.right_context, self.skip_frame))
         self.fbank_opts = front_end_options(args)
         self.sample_rate, self.num_mel = float(self.fbank_opts.sample_rate), int(self.fbank_opts.num_mel)
         self.wave_frames = []
@@ -154,7 +186,8 @@ class SpeechDataset(Dataset):
         if self.is_wave:  # (the samples as the file holds them; normalisation happens with the features, on the device)
             return utt, wave_io.pcm_view(spec, self.sample_rate, utt), text
         if self.left_context == 0 and self.right_context == 0 and self.skip_frame <= 1:
-            # The shipped configuration (no splicing, no frame skipping).  Same values as the general path below - the CMVN in
+            # No splicing, no frame skipping (the benchmark's configuration; the recipes' decode YAMLs splice - right_ctx 2 - and
+            # take the general path below, or the packed reader's device splice).  Same values as the general path - the CMVN in
             # float64, rounded to float32 once (where the reference's collate converts: speech_loader.py:340) - without its
             # temporaries: the matrix is read in place from a memory map of the archive, the float64 intermediate lives in a
             # per-thread scratch buffer, and what is handed on is float32 (half the bytes for collate to move).
@@ -175,6 +208,24 @@ class SpeechDataset(Dataset):
             feat = np.vstack([feat, np.zeros((self.skip_frame - rem, feat.shape[1]))])
         feat = skip_feat(context_feat(feat, self.left_context, self.right_context), self.skip_frame)
         return utt, feat, text
+
+    def splice(self):
+        """(left, right, skip) when the set splices or skips frames, None when it does neither."""
+        return splice_triple(self.left_context, self.right_context, self.skip_frame)
+
+    def device_splice(self):
+        """The splice triple when the set splices or skips AND is otherwise what the packed reader takes - float32 (`FM `) or
+        compressed (`CM` / `CM2` / `CM3`) matrices throughout, or sound files: CMVN, zero rows, splice and skip then happen on the
+        device (``hip.splice_rows``), in the dataset's own order and arithmetic.  None for a set that does not splice, holds a
+        float64 (`DM`) matrix or mixes the two families: those keep the host path.  ``can_defer_cmvn()`` is a different question
+        (does the CMVN commute with what the HOST path does afterwards) and stays False for every spliced archive."""
+        triple = self.splice()
+        if triple is None:
+            return None
+        if self.is_wave:
+            return triple
+        kinds = self.matrix_kinds()
+        return triple if (kinds <= {"FM"} or kinds <= set(kaldi_io.COMPRESSED_KINDS)) else None
 
     def can_defer_cmvn(self):
         """The global CMVN commutes with everything this dataset does afterwards (no splicing, no frame skipping) AND the archive
@@ -234,11 +285,13 @@ def collate(batch, padding_idx=0):
     return utts, feats, texts, ratios, sizes
 
 
-def collate_waves(batch, padding_idx=0, opts=None):
+def collate_waves(batch, padding_idx=0, opts=None, splice=None):
     """``collate`` for a wave set: list of (utt, int16 samples, text) -> the same five-tuple with a ``WaveBatch`` where the padded
-    features would stand (no GPU is touched here: a loader worker process may run it)."""
+    features would stand (no GPU is touched here: a loader worker process may run it).  With a ``splice`` triple the ratios are the
+    spliced frame counts' (``spliced_frames``)."""
     frames = [frames_of(opts, int(x[1].shape[0])) for x in batch]
-    t_max = max(frames)
+    n_out = [spliced_frames(n, splice) for n in frames]
+    t_max = max(n_out)
     l_max = max(len(x[2]) for x in batch)
     texts = torch.full((len(batch), l_max), int(padding_idx), dtype=torch.long)
     ratios = torch.zeros(len(batch))
@@ -246,10 +299,10 @@ def collate_waves(batch, padding_idx=0, opts=None):
     utts = []
     for b, (utt, _, text) in enumerate(batch):
         texts[b, : len(text)] = torch.as_tensor(text, dtype=torch.long)
-        ratios[b] = frames[b] / t_max
+        ratios[b] = n_out[b] / t_max
         sizes[b] = len(text) - 2
         utts.append(utt)
-    return utts, WaveBatch([x[1] for x in batch], frames, opts.num_mel, utts), texts, ratios, sizes
+    return utts, WaveBatch([x[1] for x in batch], frames, opts.num_mel, utts, splice=splice), texts, ratios, sizes
 
 
 def _one_thread_worker(_worker_id):
@@ -270,7 +323,7 @@ class SpeechDataLoader(DataLoader):
         # worker processes hand their batches over in shared memory, from which a host -> device copy is pathologically slow
         # (83 ms per 9-MB batch measured): the loader's pinning thread moves them into page-locked memory first
         super().__init__(dataset, batch_sampler=batches, num_workers=num_workers,
-                         collate_fn=(functools.partial(collate_waves, padding_idx=padding_idx, opts=dataset.fbank_opts)
+                         collate_fn=(functools.partial(collate_waves, padding_idx=padding_idx, opts=dataset.fbank_opts, splice=dataset.splice())
                                      if getattr(dataset, "is_wave", False) else functools.partial(collate, padding_idx=padding_idx)),
                          pin_memory=bool(num_workers > 0 and torch.cuda.is_available()),
                          worker_init_fn=_one_thread_worker if num_workers > 0 else None,

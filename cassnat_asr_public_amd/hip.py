@@ -149,6 +149,7 @@ def lib(flavour=None):
     L.cn_host_gather.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]
     L.cn_op_unpack_rows.argtypes = [C.c_void_p] * 4 + [C.c_int32] * 3 + [C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
     L.cn_op_unpack_compressed.argtypes = [C.c_void_p] * 5 + [C.c_int32] * 3 + [C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.cn_op_splice_rows.argtypes = [C.c_void_p] * 4 + [C.c_int32] * 6 + [C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
     L.cn_op_quantize_fp8.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_void_p]
     L.cn_op_logsoftmax_topk.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     L.cn_op_logsoftmax_fuse_topk.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_int32, C.c_void_p,
@@ -334,6 +335,22 @@ def unpack_compressed(staged, off, lens, kinds, out, pad, mean=None, std=None):
     assert off.numel() >= rows and lens.numel() >= rows and kinds.numel() >= rows
     check(lib().cn_op_unpack_compressed(_ptr(staged), _ptr(off), _ptr(lens), _ptr(kinds), _ptr(out), rows, T, F, float(pad), _ptr(mean),
                                         _ptr(std), current_stream()), "cn_op_unpack_compressed")
+    return out
+
+
+def splice_rows(src, off, lens, out, left, right, skip, pad, mean=None, std=None):
+    """Frame splicing and skipping on the device (cn_op_splice_rows): ``src`` float32 CUDA rows of F0 features, utterance r at row
+    off[r] with lens[r] rows -> ``out`` (rows, T_out, (left + right + 1) * F0) on the current stream: the dataset's order - CMVN
+    (``mean`` / ``std`` float64 (F0,), when given), zero rows up to a multiple of ``skip``, ``feat_op.context_feat`` with replicated
+    edges, ``feat_op.skip_feat`` - then collate's padding.  ``src`` may be the packed archive rows of a pass, or a padded, already
+    normalised (rows, T0, F0) batch with off[r] = r * T0 (rows at or behind lens[r] are never read)."""
+    rows, T, W = out.shape
+    blocks = int(left) + int(right) + 1
+    assert blocks >= 1 and W % blocks == 0, "splice_rows: the output width is not (left + right + 1) x F0"
+    assert out.is_contiguous() and src.is_contiguous() and out.element_size() == 4 and src.element_size() == 4
+    assert off.numel() >= rows and lens.numel() >= rows
+    check(lib().cn_op_splice_rows(_ptr(src), _ptr(off), _ptr(lens), _ptr(out), rows, T, W // blocks, int(left), int(right), int(skip),
+                                  float(pad), _ptr(mean), _ptr(std), current_stream()), "cn_op_splice_rows")
     return out
 
 

@@ -68,11 +68,18 @@ class PackedBatch:
     The WAVE form (``from_waves``; ``kinds`` is the string "wave") keeps per utterance a read-only '<i2' view of the samples inside the
     memory map of its sound file (``data.wave_io.pcm_view``); ``lens`` are the frame counts of the fbank front-end and ``shape`` the
     padded FEATURE shape.  The pipelines stage the samples as they are and ``hip.fbank_packed`` computes the features on the
-    device; there is no host fbank in the product, so ``padded()`` and ``matrices()`` raise."""
+    device; there is no host fbank in the product, so ``padded()`` and ``matrices()`` raise.
 
-    __slots__ = ("views", "lens", "shape", "dtype", "is_cuda", "kinds", "utts")
+    SPLICING (``splice`` = (left, right, skip), every form): the set splices and / or skips frames (the recipes' decode YAMLs:
+    0 / 2 / 1).  ``lens`` stay the SOURCE rows and ``source_shape`` the unspliced (B, longest source count, F0); ``shape`` is what the
+    dataset's general host path collates - (B, longest n_out, (left + right + 1) * F0) with n_out = ``out_lens`` = ceil(rows / skip) -
+    and ``ratios()`` are n_out / longest n_out.  ``padded()`` applies the dataset's steps on the host (``speech_loader.splice_host``:
+    CMVN in float64, zero rows up to a multiple of skip, ``feat_op.context_feat``, ``feat_op.skip_feat``, then padding): the
+    definition ``hip.splice_rows`` is held to."""
 
-    def __init__(self, views, utts=None):
+    __slots__ = ("views", "lens", "shape", "dtype", "is_cuda", "kinds", "utts", "splice", "source_shape", "out_lens")
+
+    def __init__(self, views, utts=None, splice=None):
         self.views = views
         self.kinds = None
         self.utts = utts
@@ -80,9 +87,20 @@ class PackedBatch:
         self.shape = (len(views), max(self.lens), int(views[0].shape[1]))
         self.dtype = torch.float32
         self.is_cuda = False
+        self._set_splice(splice)
+
+    def _set_splice(self, splice):
+        """``shape`` holds the unspliced shape when this is called: keep it as ``source_shape`` and derive the spliced one."""
+        from .data.speech_loader import splice_triple, spliced_frames
+
+        self.splice = splice_triple(*splice) if splice else None
+        self.source_shape = self.shape
+        self.out_lens = [spliced_frames(n, self.splice) for n in self.lens]
+        if self.splice is not None:
+            self.shape = (self.shape[0], max(self.out_lens), (self.splice[0] + self.splice[1] + 1) * self.shape[2])
 
     @classmethod
-    def from_payloads(cls, entries, utts=None, compressed=None, cols=None):
+    def from_payloads(cls, entries, utts=None, compressed=None, cols=None, splice=None):
         """``entries``: one ``kaldi_io.mat_payload`` tuple (kind, rows, cols, payload) per utterance - all `FM` (the float32 form,
         as ``PackedBatch(views)``) or all of the compressed kinds, which may mix.  Every header is checked: an entry of the other
         family (``compressed`` = True / False: the family the caller expects; None: the first entry's), of another column count
@@ -121,16 +139,17 @@ class PackedBatch:
             kinds.append(COMPRESSED_KINDS[kind])
             lens.append(rows)
         if not want_c:
-            return cls(views, utts)
+            return cls(views, utts, splice=splice)
         self = cls.__new__(cls)
         self.views, self.kinds, self.lens, self.utts = views, kinds, lens, utts
         self.shape = (len(views), max(lens), want_cols)
         self.dtype = torch.float32
         self.is_cuda = False
+        self._set_splice(splice)
         return self
 
     @classmethod
-    def from_waves(cls, views, frames, num_mel, utts=None):
+    def from_waves(cls, views, frames, num_mel, utts=None, splice=None):
         """``views``: one '<i2', one-dimensional, C-contiguous array of samples per utterance; ``frames``: their frame counts under
         the front-end's options (``Fbank.num_frames``).  Anything else - and an utterance of zero frames - raises a ValueError that
         names the utterance."""
@@ -153,12 +172,14 @@ class PackedBatch:
         self.shape = (len(views), max(self.lens), int(num_mel))
         self.dtype = torch.float32
         self.is_cuda = False
+        self._set_splice(splice)
         return self
 
     def ratios(self):
-        """collate's ``ratios[b] = feat.shape[0] / t_max``: the Python (double) quotient rounded to float32"""
+        """collate's ``ratios[b] = feat.shape[0] / t_max``: the Python (double) quotient rounded to float32 (of the rows the dataset
+        hands out: the spliced counts when the batch splices)"""
         t_max = self.shape[1]
-        return torch.tensor([n / t_max for n in self.lens], dtype=torch.float32)
+        return torch.tensor([n / t_max for n in self.out_lens], dtype=torch.float32)
 
     def matrices(self):
         """The utterances' float32 matrices on the host (the compressed form decompressed by ``kaldi_io.decompress``)."""
@@ -169,13 +190,19 @@ class PackedBatch:
         from .data.kaldi_io import decompress
 
         names = {1: "CM", 2: "CM2", 3: "CM3"}
-        return [decompress(names[k], n, self.shape[2], v) for k, n, v in zip(self.kinds, self.lens, self.views)]
+        return [decompress(names[k], n, self.source_shape[2], v) for k, n, v in zip(self.kinds, self.lens, self.views)]
 
     def padded(self, pad=0.0, cmvn=None):
         """The collated tensor itself (host): what the packed path must reproduce; used by the CPU rehearsal and the tests."""
         if self.kinds == "wave":
             raise NotImplementedError("PackedBatch: the wave form holds samples - the features exist on the device only (hip.fbank_packed)")
         out = np.full(self.shape, float(pad), np.float32)
+        if self.splice is not None:
+            from .data.speech_loader import splice_host
+
+            for b, v in enumerate(self.matrices()):  # (the assignment rounds to float32 once, as collate does)
+                out[b, : self.out_lens[b]] = splice_host(v, self.splice, cmvn)
+            return torch.from_numpy(out)
         for b, v in enumerate(self.matrices()):
             out[b, : v.shape[0]] = v if cmvn is None else ((v.astype(np.float64) - cmvn[0]) / cmvn[1]).astype(np.float32)
         return torch.from_numpy(out)
@@ -292,7 +319,7 @@ class DecodePipelines:
         self._rows_lock = threading.Lock()
         self._stats_lock = threading.Lock()
         self.timeline = None  # a list: the workers and the consumer append (label, pipeline, perf_counter) - bench.py --host-timeline
-        self.stats = {"passes": 0, "batches": 0, "predicted": 0, "missed": 0, "merged_ragged": 0, "compressed_passes": 0, "wave_passes": 0,
+        self.stats = {"passes": 0, "batches": 0, "predicted": 0, "missed": 0, "merged_ragged": 0, "compressed_passes": 0, "wave_passes": 0, "spliced_passes": 0,
                       # host seconds of the worker threads, by what they were doing (summed over the pipelines)
                       "s_take": 0.0, "s_stage": 0.0, "s_launch": 0.0, "s_retire_wait": 0.0}
 
@@ -419,7 +446,7 @@ class DecodePipelines:
             f = nxt[0]
             T = int(f.shape[1])
             hi, lo = max(tmax, T), min(tmin, T)
-            ok = (type(f) is type(f0) and _form(f) == _form(f0)
+            ok = (type(f) is type(f0) and _form(f) == _form(f0) and getattr(f, "splice", None) == getattr(f0, "splice", None)
                   and tuple(f.shape[2:]) == tuple(f0.shape[2:]) and f.dtype == f0.dtype and nxt[1].dtype == items[0][1].dtype
                   and lo >= self.ragged * hi and self.fits(rows + int(f.shape[0]), hi))
             if ok and ahead.acquire(blocking=False):
@@ -446,6 +473,8 @@ class DecodePipelines:
         tmax = max(b.shape[1] for b in batches)
         F = batches[0].shape[2]
         forms = set(_form(b) for b in batches)
+        if len(set(b.splice for b in batches)) > 1:
+            raise ValueError("DecodePipelines: a pass mixes packed batches of different splice triples")
         if "wave" in forms:
             if len(forms) > 1:
                 raise ValueError("DecodePipelines: a pass mixes wave batches with another form of packed batch")
@@ -465,13 +494,16 @@ class DecodePipelines:
         views = [v for b in batches for v in b.views]
         lens = [n for b in batches for n in b.lens]
         total = sum(lens)
+        # a spliced pass: the staging buffers hold SOURCE rows of F0 values (skip times the output frames), `out` the spliced batch
+        splice = batches[0].splice
+        F0 = batches[0].source_shape[2]
         bufs = self._packed[k].get(slot)
-        cap = max(total, self.max_batch * self.frames_cap)
-        if bufs is None or bufs["cap"] < total or bufs["F"] != F or bufs["utts"] < rows:
+        cap = max(total, self.max_batch * self.frames_cap * (splice[2] if splice else 1))
+        if bufs is None or bufs["cap"] < total or bufs["F"] != F or bufs["F0"] != F0 or bufs["utts"] < rows:
             utts = max(rows, self.max_utts)
-            bufs = {"cap": cap, "F": F, "utts": utts,
-                    "host": torch.empty(cap * F, dtype=torch.float32, pin_memory=True),
-                    "dev": torch.empty(cap * F, dtype=torch.float32, device=dev_),
+            bufs = {"cap": cap, "F": F, "F0": F0, "utts": utts,
+                    "host": torch.empty(cap * F0, dtype=torch.float32, pin_memory=True),
+                    "dev": torch.empty(cap * F0, dtype=torch.float32, device=dev_),
                     # per utterance: row offset, frames, float32 ratio (as int32 bits) - one small DMA
                     "meta_h": torch.empty(3 * utts, dtype=torch.int32, pin_memory=True),
                     "meta_d": torch.empty(3 * utts, dtype=torch.int32, device=dev_),
@@ -491,7 +523,7 @@ class DecodePipelines:
         meta[:rows] = offs
         meta[utts:utts + rows] = lens
         meta[2 * utts:2 * utts + rows] = torch.cat([x[1] for x in items], 0).numpy().view(np.int32)
-        bufs["dev"][: total * F].copy_(bufs["host"][: total * F], non_blocking=True)
+        bufs["dev"][: total * F0].copy_(bufs["host"][: total * F0], non_blocking=True)
         bufs["meta_d"].copy_(bufs["meta_h"], non_blocking=True)
         feats = bufs["out"][: rows * tmax * F].view(rows, tmax, F)
         stats = (None, None)
@@ -499,7 +531,12 @@ class DecodePipelines:
             stats = self._cmvn_dev.get(device)
             if stats is None:
                 stats = self._cmvn_dev[device] = (torch.from_numpy(self.cmvn[0]).to(dev_), torch.from_numpy(self.cmvn[1]).to(dev_))
-        hip.unpack_rows(bufs["dev"], bufs["meta_d"][:utts], bufs["meta_d"][utts:2 * utts], feats, pad, stats[0], stats[1])
+        if splice is not None:  # ONE launch from the staging buffer: padding, CMVN, zero rows, splice and skip
+            hip.splice_rows(bufs["dev"], bufs["meta_d"][:utts], bufs["meta_d"][utts:2 * utts], feats, splice[0], splice[1], splice[2], pad,
+                            stats[0], stats[1])
+            self._bump("spliced_passes", 1)
+        else:
+            hip.unpack_rows(bufs["dev"], bufs["meta_d"][:utts], bufs["meta_d"][utts:2 * utts], feats, pad, stats[0], stats[1])
         return feats, bufs["meta_d"][2 * utts:2 * utts + rows].view(torch.float32)
 
     def _stage_compressed(self, k, slot, items, pad, rows, tmax, F, dev_):
@@ -513,6 +550,8 @@ class DecodePipelines:
         batches = [x[0] for x in items]
         if any(b.kinds is None or b.shape[2] != F for b in batches):
             raise ValueError("DecodePipelines: a pass mixes compressed and float32 packed batches, or feature dimensions")
+        splice = batches[0].splice
+        F0 = batches[0].source_shape[2]
         views = [v for b in batches for v in b.views]
         lens = [n for b in batches for n in b.lens]
         kinds = [c for b in batches for c in b.kinds]
@@ -521,10 +560,10 @@ class DecodePipelines:
             raise ValueError("DecodePipelines: a pass of %d compressed bytes (the offsets are int32)" % total)
         key = ("compressed", slot)
         bufs = self._packed[k].get(key)
-        if bufs is None or bufs["cap"] < total or bufs["F"] != F or bufs["utts"] < rows:
+        if bufs is None or bufs["cap"] < total or bufs["F"] != F or bufs["F0"] != F0 or bufs["utts"] < rows:
             utts = max(rows, self.max_utts)
-            cap = max(total, self.max_batch * self.frames_cap * F + utts * (32 + 8 * F))
-            bufs = {"cap": cap, "F": F, "utts": utts,
+            cap = max(total, self.max_batch * self.frames_cap * (splice[2] if splice else 1) * F0 + utts * (32 + 8 * F0))
+            bufs = {"cap": cap, "F": F, "F0": F0, "utts": utts,
                     "host": torch.empty(cap, dtype=torch.uint8, pin_memory=True),
                     "dev": torch.empty(cap, dtype=torch.uint8, device=dev_),
                     # per utterance: byte offset, frames, float32 ratio (as int32 bits), kind - one small DMA
@@ -549,10 +588,36 @@ class DecodePipelines:
             stats = self._cmvn_dev.get(self._device)
             if stats is None:
                 stats = self._cmvn_dev[self._device] = (torch.from_numpy(self.cmvn[0]).to(dev_), torch.from_numpy(self.cmvn[1]).to(dev_))
-        hip.unpack_compressed(bufs["dev"], bufs["meta_d"][:utts], bufs["meta_d"][utts:2 * utts], bufs["meta_d"][3 * utts:4 * utts], feats, pad,
-                              stats[0], stats[1])
+        if splice is not None:  # two launches: decompress + CMVN into the slot's scratch, then splice and skip out of it
+            mid, sp = self._splice_scratch(bufs, batches, rows, F0, splice, dev_)
+            hip.unpack_compressed(bufs["dev"], bufs["meta_d"][:utts], bufs["meta_d"][utts:2 * utts], bufs["meta_d"][3 * utts:4 * utts], mid, pad,
+                                  stats[0], stats[1])
+            hip.splice_rows(mid, sp[0], sp[1], feats, splice[0], splice[1], splice[2], pad)
+            self._bump("spliced_passes", 1)
+        else:
+            hip.unpack_compressed(bufs["dev"], bufs["meta_d"][:utts], bufs["meta_d"][utts:2 * utts], bufs["meta_d"][3 * utts:4 * utts], feats, pad,
+                                  stats[0], stats[1])
         self._bump("compressed_passes", 1)
         return feats, bufs["meta_d"][2 * utts:2 * utts + rows].view(torch.float32)
+
+    def _splice_scratch(self, bufs, batches, rows, F0, splice, dev_):
+        """The two-launch forms (compressed, wave) of a spliced pass: the slot's scratch for the UNSPLICED normalised batch - a
+        (rows, T0, F0) view, T0 the pass's longest source count; allocated with the slot's other staging buffers at the size of the
+        engines' area, grown only for a pass that needs more - and the per-utterance (row offset r * T0, source rows) that
+        ``hip.splice_rows`` reads it by, sent in one small DMA.  Rows at or behind an utterance's count are never read there."""
+        t0 = max(b.source_shape[1] for b in batches)
+        need = rows * t0 * F0
+        if bufs.get("mid") is None or bufs["mid"].numel() < need:
+            bufs["mid"] = torch.empty(max(need, self.max_batch * self.frames_cap * splice[2] * F0), dtype=torch.float32, device=dev_)
+        utts = bufs["utts"]
+        if bufs.get("sp_h") is None:
+            bufs["sp_h"] = torch.empty(2 * utts, dtype=torch.int32, pin_memory=True)
+            bufs["sp_d"] = torch.empty(2 * utts, dtype=torch.int32, device=dev_)
+        sp = bufs["sp_h"].numpy()
+        sp[:rows] = np.arange(rows, dtype=np.int64) * t0
+        sp[utts:utts + rows] = [n for b in batches for n in b.lens]
+        bufs["sp_d"].copy_(bufs["sp_h"], non_blocking=True)
+        return bufs["mid"][:need].view(rows, t0, F0), (bufs["sp_d"][:utts], bufs["sp_d"][utts:2 * utts])
 
     def _stage_wave(self, k, slot, items, pad, rows, tmax, F, dev_):
         """A pass of wave-form ``PackedBatch``es: every utterance's int16 samples go into the slot's page-locked buffer as its sound
@@ -565,8 +630,10 @@ class DecodePipelines:
         if self.fbank is None:
             raise ValueError("DecodePipelines: a wave batch, but the pipelines were built without fbank options")
         batches = [x[0] for x in items]
-        if F != int(self.fbank.num_mel) or any(b.shape[2] != F for b in batches):
-            raise ValueError("DecodePipelines: wave batches of %d features, the front-end computes %d" % (F, int(self.fbank.num_mel)))
+        splice = batches[0].splice
+        F0 = batches[0].source_shape[2]
+        if F0 != int(self.fbank.num_mel) or any(b.shape[2] != F or b.source_shape[2] != F0 for b in batches):
+            raise ValueError("DecodePipelines: wave batches of %d features, the front-end computes %d" % (F0, int(self.fbank.num_mel)))
         views = [v for b in batches for v in b.views]
         offs, total = hip.gather_offsets([v.nbytes for v in views], 16)
         if total >= 2 ** 31:
@@ -577,7 +644,7 @@ class DecodePipelines:
         bufs = self._packed[k].get(key)
         if bufs is None or bufs["cap"] < total or bufs["F"] != F or bufs["utts"] < rows:
             utts = max(rows, self.max_utts)
-            cap = max(total, 2 * self.max_batch * self.frames_cap * shift + utts * (2 * flen + 16))
+            cap = max(total, 2 * self.max_batch * self.frames_cap * (splice[2] if splice else 1) * shift + utts * (2 * flen + 16))
             bufs = {"cap": cap, "F": F, "utts": utts,
                     "host": torch.empty(cap, dtype=torch.uint8, pin_memory=True),
                     "dev": torch.empty(cap, dtype=torch.uint8, device=dev_),
@@ -602,7 +669,13 @@ class DecodePipelines:
             stats = self._cmvn_dev.get(self._device)
             if stats is None:
                 stats = self._cmvn_dev[self._device] = (torch.from_numpy(self.cmvn[0]).to(dev_), torch.from_numpy(self.cmvn[1]).to(dev_))
-        hip.fbank_packed(self.fbank, bufs["dev"], total, bufs["meta_d"][:utts], bufs["meta_d"][utts:2 * utts], feats, pad, stats[0], stats[1])
+        if splice is not None:  # two launches: fbank + CMVN into the slot's scratch, then splice and skip out of it
+            mid, sp = self._splice_scratch(bufs, batches, rows, F0, splice, dev_)
+            hip.fbank_packed(self.fbank, bufs["dev"], total, bufs["meta_d"][:utts], bufs["meta_d"][utts:2 * utts], mid, pad, stats[0], stats[1])
+            hip.splice_rows(mid, sp[0], sp[1], feats, splice[0], splice[1], splice[2], pad)
+            self._bump("spliced_passes", 1)
+        else:
+            hip.fbank_packed(self.fbank, bufs["dev"], total, bufs["meta_d"][:utts], bufs["meta_d"][utts:2 * utts], feats, pad, stats[0], stats[1])
         self._bump("wave_passes", 1)
         return feats, bufs["meta_d"][2 * utts:2 * utts + rows].view(torch.float32)
 

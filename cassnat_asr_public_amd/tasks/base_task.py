@@ -41,11 +41,18 @@ class BaseTask(object):
         testset = SpeechDataset(self.vocab, args.test_paths, args)
         if getattr(args, "use_cmvn", False):
             testset._load_cmvn(args.global_cmvn)
-        if testset.is_wave:  # audio input: the front-end must produce what the model reads
+        if testset.is_wave:  # audio input: the front-end (and the splice behind it) must produce what the model reads
+            left, right, skip = testset.splice() or (0, 0, 1)
+            blocks = left + right + 1
             want = int(getattr(args, "n_features", getattr(args, "input_size", testset.num_mel)))
-            if want != testset.num_mel or int(getattr(args, "input_size", want)) != testset.num_mel:
+            size = int(getattr(args, "input_size", want))
+            # the reference's own agreement (src/tasks/*_task.py set_model: input_size == (left + right + 1) // skip * n_features) and
+            # the width the engine is really handed, (left + right + 1) x mel bins; without frame skipping the two together say
+            # n_features == mel bins
+            if size != blocks // skip * want or size != blocks * testset.num_mel:
                 raise ValueError("audio input: the fbank front-end computes %d mel bins, the model reads n_features / input_size = %d / %d"
-                                 % (testset.num_mel, want, int(getattr(args, "input_size", want))))
+                                 " (left_ctx / right_ctx / skip_frame = %d / %d / %d: input_size must be %d x n_features and %d x mel bins)"
+                                 % (testset.num_mel, want, size, left, right, skip, blocks // skip, blocks))
         self.test_loader = SpeechDataLoader(testset, args.batch_size, args.padding_idx,
                                             num_workers=args.load_data_workers, shuffle=False, indices=indices)
         self._pad_value, self._fbank = float(args.padding_idx), None
@@ -53,7 +60,8 @@ class BaseTask(object):
 
     def wave_features(self, feats, feat_sizes):
         """A wave set's batch (``WaveBatch``: int16 samples) -> (feats (B, T, num_mel) cuda, length ratios) on the caller's current
-        stream, the global CMVN applied when the dataset has statistics (``Fbank.packed``); any other batch passes through."""
+        stream, the global CMVN applied when the dataset has statistics and the frames spliced / skipped when the set asks for it
+        (``Fbank.packed``); any other batch passes through."""
         from ..data.speech_loader import WaveBatch
 
         if not isinstance(feats, WaveBatch):
@@ -65,6 +73,6 @@ class BaseTask(object):
             ds = self.test_loader.dataset
             o = ds.fbank_opts
             fb = Fbank(cmvn_mean=ds.mean if ds.use_cmvn else None, cmvn_std=ds.std if ds.use_cmvn else None,
-                       pad_value=float(getattr(self, "_pad_value", 0.0)), **{name: getattr(o, name) for name, _ in o._fields_ if name != "reserved"})
+                       pad_value=float(getattr(self, "_pad_value", 0.0)), splice=ds.splice(), **{name: getattr(o, name) for name, _ in o._fields_ if name != "reserved"})
             self._fbank = fb
         return fb.packed(feats.views, utts=feats.utts)

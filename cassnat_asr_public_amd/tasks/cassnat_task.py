@@ -215,13 +215,22 @@ class CassNATTask(BaseTask):
         ds = getattr(self.test_loader, "dataset", None)
         # The packed reader (pipeline.PackedBatch): nothing but a copy sits between the archive and the device - the utterances'
         # rows go from the memory map of the .ark into page-locked memory as they are, a pass at a time, and padding + CMVN happen
-        # on the device.  It applies to the shipped configuration (float32 archives, no splicing, no frame skipping) and replaces
+        # on the device.  It applies to float32 and compressed archives and to sound files - unspliced (the benchmark's
+        # configuration) or spliced / frame-skipped (the recipes' decode YAMLs: right_ctx 2; hip.splice_rows) - and replaces
         # the DataLoader altogether - its worker PROCESSES had to pickle every batch through shared memory (8.5k utt/s and nine
         # seconds to the first batch with the recipes' `--load_data_workers 4`); that flag now sets the number of copy THREADS.
         # A wave set (audio input) always takes the packed reader's wave form: samples staged as the sound files hold them, fbank
         # and CMVN on the device (--hip_packed_reader / --hip_device_cmvn choose between HOST paths, which audio does not have)
         wave = bool(getattr(ds, "is_wave", False))
-        defer_ok = wave or bool(ds is not None and hasattr(ds, "can_defer_cmvn") and ds.can_defer_cmvn() and int(getattr(args, "hip_device_cmvn", 1)))
+        # A set that splices or skips frames (SpeechDataset.device_splice: float32 or compressed throughout, or sound files): CMVN,
+        # the zero rows, splice and skip all happen on the device, in the dataset's order - the packed reader is the ONLY device
+        # form (the collated DataLoader path keeps doing all of it on the host, --hip_packed_reader 0 / --hip_device_cmvn 0 choose it)
+        splice = ds.device_splice() if ds is not None and hasattr(ds, "device_splice") else None
+        if splice is not None and not wave and not (int(getattr(args, "hip_device_cmvn", 1)) and int(getattr(args, "hip_packed_reader", 1))
+                                                    and hasattr(self.test_loader, "batch_sampler")):
+            splice = None
+        defer_ok = wave or splice is not None or bool(ds is not None and hasattr(ds, "can_defer_cmvn") and ds.can_defer_cmvn()
+                                                      and int(getattr(args, "hip_device_cmvn", 1)))
         # ... to a test set that is float32 (`FM `) throughout, or COMPRESSED throughout (Kaldi's `CM` / `CM2` / `CM3`, what
         # make_fbank.sh writes; the kinds may mix, as they do inside one copy-feats archive): the payloads are then staged as the
         # archive holds them and decompressed on the device.  Decided from every utterance's header; a set that mixes the two
@@ -236,23 +245,27 @@ class CassNATTask(BaseTask):
         if dev_cmvn:
             ds.device_cmvn = True
         try:
-            return self._decode_pipelined_run(args, n_pipes, results, batch_time, progress, sos, (ds.mean, ds.std) if dev_cmvn else None, packed, compressed, wave)
+            return self._decode_pipelined_run(args, n_pipes, results, batch_time, progress, sos, (ds.mean, ds.std) if dev_cmvn else None, packed, compressed, wave,
+                                              splice if packed else None)
         finally:
             if dev_cmvn:
                 ds.device_cmvn = False
 
-    def _decode_pipelined_run(self, args, n_pipes, results, batch_time, progress, sos, cmvn, packed=False, compressed=False, wave=False):
+    def _decode_pipelined_run(self, args, n_pipes, results, batch_time, progress, sos, cmvn, packed=False, compressed=False, wave=False,
+                              splice=None):
         from ..data import kaldi_io
+        from ..data.speech_loader import spliced_frames
         from ..pipeline import DecodePipelines, PackedBatch
 
         ds = getattr(self.test_loader, "dataset", None)
         feat_dim = None
+        # (the engines work on OUTPUT frames: max_frames, the passes' area and hip_ragged all count what the dataset hands out)
         if wave:  # (frame counts from the WAV headers, read when the dataset was built)
-            first_len = max(ds.wave_frames[i] for i in list(self.test_loader.batch_sampler)[0])
+            first_len = spliced_frames(max(ds.wave_frames[i] for i in list(self.test_loader.batch_sampler)[0]), splice)
             feat_dim = ds.num_mel
         elif packed:
             first = [ds._items[i][1] for i in list(self.test_loader.batch_sampler)[0]]
-            first_len = max(kaldi_io.mat_rows(spec) for spec in first)
+            first_len = spliced_frames(max(kaldi_io.mat_rows(spec) for spec in first), splice)
             feat_dim = kaldi_io.mat_payload(first[0])[2]
         else:
             first_len = next(iter(self.test_loader))[1].shape[1]
@@ -266,7 +279,7 @@ class CassNATTask(BaseTask):
         cmvn_id = None if cmvn is None else hashlib.sha1(np.ascontiguousarray(cmvn[0]).tobytes() + np.ascontiguousarray(cmvn[1]).tobytes()).hexdigest()
         key = (n_pipes, args.batch_size, max_frames, int(getattr(args, "hip_coalesce", 10)), float(getattr(args, "hip_ragged", 0.75)),
                cmvn_id, self.model.weights_key(), packed, compressed, bytes(ds.fbank_opts) if wave else None,
-               int(getattr(args, "load_data_workers", 0)) if packed else 0)
+               splice, int(getattr(args, "load_data_workers", 0)) if packed else 0)
         pipes = getattr(self, "_pipes", None)
         if pipes is None or self._pipes_key != key:  # (kept for further decode() calls on this task: engines, threads, streams)
             if pipes is not None:
@@ -283,7 +296,8 @@ class CassNATTask(BaseTask):
             if wave:  # the loader's batches as views into the memory maps of the sound files (a map lives as long as its pass)
                 for j, idx in enumerate(self.test_loader.batch_sampler):
                     got = [ds[i] for i in idx]
-                    pb = PackedBatch.from_waves([v for _, v, _ in got], [ds.wave_frames[i] for i in idx], feat_dim, utts=[u for u, _, _ in got])
+                    pb = PackedBatch.from_waves([v for _, v, _ in got], [ds.wave_frames[i] for i in idx], feat_dim, utts=[u for u, _, _ in got],
+                                                splice=splice)
                     meta[j] = ([u for u, _, _ in got], [None] * len(got), pb.shape[0] * pb.shape[1], max(len(t) for _, _, t in got))
                     yield pb, pb.ratios(), j
                 return
@@ -293,7 +307,7 @@ class CassNATTask(BaseTask):
                     # (every header is checked against the path chosen above and the set's feature dimension: a contradiction
                     # raises, naming the utterance)
                     pb = PackedBatch.from_payloads([kaldi_io.mat_payload(spec) for _, spec, _ in items], utts=[u for u, _, _ in items],
-                                                   compressed=compressed, cols=feat_dim)
+                                                   compressed=compressed, cols=feat_dim, splice=splice)
                     # (utt2diff reads the width of the PADDED label row, src/tasks/cassnat_task.py:358-360)
                     meta[j] = ([u for u, _, _ in items], [None] * len(items), pb.shape[0] * pb.shape[1], max(len(t) for _, _, t in items))
                     yield pb, pb.ratios(), j

@@ -44,12 +44,14 @@ class DecodeParser(object):
                             "result file stays in file order.  0 (default): the reference's batches")
         p.add_argument("--hip_packed_reader", default=1, type=int,
                        help="1 (default): the pipelined decoder reads the utterances' rows straight from the memory-mapped archives into "
-                            "page-locked memory, a pass at a time, and pads / normalises on the device (float32 archives without splicing "
-                            "or frame skipping; --load_data_workers then sets the number of copy threads); 0: the DataLoader's collated batches")
+                            "page-locked memory, a pass at a time, and pads / normalises on the device - and splices / skips frames there when the "
+                            "config asks for it (left_ctx / right_ctx / skip_frame) - for float32 or compressed archives; "
+                            "--load_data_workers then sets the number of copy threads; 0: the DataLoader's collated batches")
         p.add_argument("--hip_device_cmvn", default=1, type=int,
                        help="1 (default): the pipelined decoder applies the global CMVN on the device, behind the host-to-device copy "
-                            "(float64 arithmetic, bit-identical to the dataset's), when the dataset neither splices nor skips frames "
-                            "and runs without loader workers; 0: always in the dataset, as the reference does")
+                            "(float64 arithmetic, bit-identical to the dataset's): on the packed reader, or - for a dataset that neither splices "
+                            "nor skips frames - without loader workers; 0: always in the dataset, as the reference does (a spliced set "
+                            "then keeps the host path altogether)")
         p.add_argument("--hip_audio", default="auto", choices=["auto", "0", "1"],
                        help="decode from audio: auto (default) - a --data_path whose entries are RIFF/WAVE files (a wav.scp of plain "
                             "paths: 16-bit PCM, one channel) is decoded from the sound files, the Kaldi fbank features computed on the "

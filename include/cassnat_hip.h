@@ -583,6 +583,21 @@ int cn_op_unpack_rows(const float* packed_dev, const int32_t* off_dev, const int
 int cn_op_unpack_compressed(const void* staged_dev, const int32_t* off_dev, const int32_t* len_dev, const int32_t* kind_dev,
                             float* out_dev, int32_t rows, int32_t T, int32_t F, float pad, const double* mean_dev, const double* std_dev,
                             void* stream);
+/* Frame splicing and skipping behind the same hand-over (SpeechDataset.__getitem__, src/data/speech_loader.py:141-158; context_feat /
+ * skip_feat, src/data/feat_op.py:4-31): float32 source rows, utterance r = len_dev[r] rows of F0 values at ROW off_dev[r] of src_dev,
+ * -> out_dev (rows, T_out, (left + right + 1) * F0).  With T = len[r], Tp = T rounded up to a multiple of skip (skip > 1; else T) and
+ * n_out = min(skip > 1 ? Tp / skip : T, T_out):
+ *   out[r][t][k * F0 + f] = pad for t >= n_out; otherwise, with s = clamp(t * skip + k - left, 0, Tp - 1),
+ *                         = s < T ? norm(src[off[r] + s][f]) : 0.0f     (the rows the dataset appends are zeros AFTER the CMVN)
+ * norm as in cn_op_unpack_rows (float64, one rounding; statistics over the F0 source columns), the identity without statistics.
+ * No row at or behind len[r] of an utterance is read, so the source may also be a padded, already normalised batch (rows, T0, F0)
+ * with off[r] = r * T0 and no statistics.  left = right = 0, skip <= 1 is cn_op_unpack_rows.
+ * Refused (-1, out_dev untouched): null pointers, a mean without a std, rows / T_out / F0 < 1, rows > 65535, left / right outside
+ * [0, 64], skip outside [0, 64] (0 and 1 both keep every frame), (left + right + 1) * F0 > 12288 (a spliced row must fit the
+ * kernel's 48 KB of LDS), rows * T_out * spliced width or T_out * skip beyond 2^31 - 1. */
+int cn_op_splice_rows(const float* src_dev, const int32_t* off_dev, const int32_t* len_dev, float* out_dev, int32_t rows, int32_t T_out,
+                      int32_t F0, int32_t left, int32_t right, int32_t skip, float pad, const double* mean_dev, const double* std_dev,
+                      void* stream);
 /* host side of the same reader: n byte ranges (an utterance's rows in the memory map of its archive) copied back to back into a
  * staging buffer (dst + dst_offsets[i]) by one GIL-free call; threads > 1 deals them over that many host threads */
 int cn_host_gather(void* dst, const uint64_t* src_ptrs, const uint64_t* dst_offsets, const uint64_t* nbytes, int32_t n, int32_t threads);
