@@ -28,7 +28,8 @@ struct FbankParams {
     const float* band_w;      // [num_mel][n_fft / 2] (row b: band_len[b] weights)
     const float* cmvn_mean;   // [num_mel] or null (fbank_kernel: float32 (e - mean) * istd)
     const float* cmvn_istd;   // [num_mel] or null
-    // fbank_packed_kernel: the utterances' int16 samples as the WAV data chunks hold them, utterance r at byte off[r]
+    // fbank_packed_kernel: the utterances' samples - int16 as the WAV data chunks hold them, or float32 (the resampled wave) -
+    // utterance r at byte off[r]
     const unsigned char* staged;
     const int* off;           // [B] byte offsets
     const double* mean64;     // [num_mel] or null: float((double(e) - mean) / std), the reader's arithmetic
@@ -142,7 +143,10 @@ __global__ __launch_bounds__(256) void fbank_kernel(FbankParams p) {
 // int16 -> float conversion happens on the load (exact).  A workgroup whose four frames all lie past its utterance's last frame
 // only writes padding: the launch covers the padded (rows, T) range, the arithmetic only the frames that exist.  Reads stay inside
 // [0, staged_bytes): an utterance whose (offset, samples) reach outside is cut to the samples that lie inside; sample indices
-// past samples[r] are never formed (frame t < frames_r ends at sample t * shift + frame_len - 1 < samples[r]).
+// past samples[r] are never formed (frame t < frames_r ends at sample t * shift + frame_len - 1 < samples[r]).  S = short: the WAV
+// files' samples; S = float: the wave the resampling kernel wrote (resample.hip), on the int16 scale - the same arithmetic from the
+// load on.
+template <class S>
 __global__ __launch_bounds__(256) void fbank_packed_kernel(FbankParams p) {
     __shared__ float re[4][FB_MAX_FFT], im[4][FB_MAX_FFT];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -151,7 +155,7 @@ __global__ __launch_bounds__(256) void fbank_packed_kernel(FbankParams p) {
     const long long o0 = p.off[r];
     long long ns = p.num_samples[r];
     if (o0 < 0 || o0 >= p.staged_bytes) ns = 0;
-    else if (o0 + 2 * ns > p.staged_bytes) ns = (p.staged_bytes - o0) / 2;
+    else if (o0 + (long long)sizeof(S) * ns > p.staged_bytes) ns = (p.staged_bytes - o0) / (long long)sizeof(S);
     const int T = ns < p.frame_len ? 0 : (int)(1 + (ns - p.frame_len) / p.frame_shift);  // snip_edges = true
     float* o = p.out + ((long long)r * p.Tmax + t) * p.num_mel;
     if (blockIdx.x * 4 >= T) {  // (uniform over the workgroup)
@@ -160,7 +164,7 @@ __global__ __launch_bounds__(256) void fbank_packed_kernel(FbankParams p) {
         return;
     }
     const bool have = t < T;
-    const short* x = reinterpret_cast<const short*>(p.staged + o0) + (long long)t * p.frame_shift;
+    const S* x = reinterpret_cast<const S*>(p.staged + o0) + (long long)t * p.frame_shift;
     float v[FB_MAX_FFT / 64];
 #pragma unroll
     for (int i = 0; i < FB_MAX_FFT / 64; ++i) {
@@ -316,7 +320,7 @@ int launch_fbank(const FbankOpts& o, const float* wave, const int* num_samples, 
 int fbank_frame_samples(const FbankOpts& o) { return (int)(o.sample_rate * 0.001 * o.frame_length_ms); }
 
 int launch_fbank_packed(const FbankOpts& o, const unsigned char* staged, long long staged_bytes, const int* off, const int* samples,
-                        float* out, int rows, int T, float pad_value, const double* mean, const double* sd, hipStream_t s) {
+                        float* out, int rows, int T, float pad_value, const double* mean, const double* sd, bool f32, hipStream_t s) {
     if (rows > 65535) {
         cn_set_error("fbank_packed: more than 65535 utterances in one pass");
         return -1;
@@ -329,7 +333,8 @@ int launch_fbank_packed(const FbankOpts& o, const unsigned char* staged, long lo
     p.off = off;
     p.mean64 = mean;
     p.std64 = mean ? sd : nullptr;
-    hipLaunchKernelGGL(fbank_packed_kernel, dim3(cn_ceil_div(T, 4), rows), dim3(256), 0, s, p);
+    if (f32) hipLaunchKernelGGL(fbank_packed_kernel<float>, dim3(cn_ceil_div(T, 4), rows), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(fbank_packed_kernel<short>, dim3(cn_ceil_div(T, 4), rows), dim3(256), 0, s, p);
     CN_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -323,10 +323,20 @@ struct FbankOpts {
 int fbank_num_frames(const FbankOpts& o, int num_samples);
 int launch_fbank(const FbankOpts& o, const float* wave, const int* num_samples, int B, int max_samples, const float* cmvn_mean,
                  const float* cmvn_istd, float* out, int Tmax, float pad_value, hipStream_t s);
-// the packed reader's form: int16 samples as the WAV files hold them, utterance r at byte off[r] of `staged`; float64 CMVN
+// the packed reader's form: int16 samples as the WAV files hold them - f32: float32 samples, the resampled wave - utterance r at byte
+// off[r] of `staged`; float64 CMVN
 int fbank_frame_samples(const FbankOpts& o);
 int launch_fbank_packed(const FbankOpts& o, const unsigned char* staged, long long staged_bytes, const int* off, const int* samples,
-                        float* out, int rows, int T, float pad_value, const double* mean, const double* sd, hipStream_t s);
+                        float* out, int rows, int T, float pad_value, const double* mean, const double* sd, bool f32, hipStream_t s);
+
+// ---- sample-rate conversion + channel pick in front of fbank, Kaldi's LinearResample as ResampleWaveform sets it up (resample.hip)
+long long resample_num_samples(int in_rate, int out_rate, long long in_samples);
+// the table of a rate pair as the device gets it: first / taps [out_unit], weights [max_taps][out_unit]; null arrays: the sizes alone
+int resample_table(int in_rate, int out_rate, int* in_unit, int* out_unit, int* max_taps, int* first, int* taps, float* weights,
+                   long long capacity);
+int launch_wave_resample(int in_rate, int out_rate, const unsigned char* staged, long long staged_bytes, const int* off, const int* samples,
+                         const int* channels, const int* channel, int utts, const int* rows, int n_rows, long long max_out, float* out,
+                         const int* out_off, hipStream_t s);
 
 // ---- conv2 as an LDS-DMA implicit GEMM, bf16 / 256 -> 256 channels (conv2.hip); launch_gemm dispatches to it
 bool conv2_dma_applies(int prec, int C, int N);

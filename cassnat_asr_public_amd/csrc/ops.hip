@@ -1,4 +1,4 @@
-// C-ABI entry points of libcassnat_hip.so that take no model handle: the Kaldi fbank front end, the host gather of the packed
+// C-ABI entry points of libcassnat_hip.so that take no model handle: the Kaldi fbank front end and the resampler in front of it, the host gather of the packed
 // reader and the single-kernel entries (cn_op_*) through which the tests drive every hand-written kernel.  See
 // include/cassnat_hip.h for the contract; the handle, weight packing and decode paths are model.hip.
 #include <algorithm>
@@ -130,24 +130,78 @@ extern "C" int cn_fbank(const cn_fbank_opts* o, const float* wave_dev, const int
                         Tmax, pad_value, (hipStream_t)stream);
 }
 
-extern "C" int cn_op_fbank_packed(const cn_fbank_opts* o, const void* staged_dev, int64_t staged_bytes, const int32_t* off_dev,
-                                  const int32_t* samples_dev, float* out_dev, int32_t rows, int32_t T, float pad, const double* mean_dev,
-                                  const double* std_dev, void* stream) {
+static int fbank_packed_entry(const char* who, const cn_fbank_opts* o, const void* staged_dev, int64_t staged_bytes, const int32_t* off_dev,
+                              const int32_t* samples_dev, float* out_dev, int32_t rows, int32_t T, float pad, const double* mean_dev,
+                              const double* std_dev, bool f32, void* stream) {
     if (!o || !staged_dev || !off_dev || !samples_dev || !out_dev || (!mean_dev) != (!std_dev)) {
-        cn_set_error("cn_op_fbank_packed: null argument (mean and std come together)");
+        cn_set_error(std::string(who) + ": null argument (mean and std come together)");
         return -1;
     }
     if (rows <= 0 || T <= 0 || o->num_mel <= 0 || staged_bytes < 0) {
-        cn_set_error("cn_op_fbank_packed: rows, T and num_mel must be positive");
+        cn_set_error(std::string(who) + ": rows, T and num_mel must be positive");
         return -1;
     }
     const FbankOpts f = fbank_opts_from(o);
     if (fbank_frame_samples(f) > 512) {
-        cn_set_error("cn_op_fbank_packed: a frame of more than 512 samples does not fit the 512-point FFT");
+        cn_set_error(std::string(who) + ": a frame of more than 512 samples does not fit the 512-point FFT");
         return -1;
     }
     return launch_fbank_packed(f, static_cast<const unsigned char*>(staged_dev), staged_bytes, off_dev, samples_dev, out_dev, rows, T, pad,
-                               mean_dev, std_dev, (hipStream_t)stream);
+                               mean_dev, std_dev, f32, (hipStream_t)stream);
+}
+
+extern "C" int cn_op_fbank_packed(const cn_fbank_opts* o, const void* staged_dev, int64_t staged_bytes, const int32_t* off_dev,
+                                  const int32_t* samples_dev, float* out_dev, int32_t rows, int32_t T, float pad, const double* mean_dev,
+                                  const double* std_dev, void* stream) {
+    return fbank_packed_entry("cn_op_fbank_packed", o, staged_dev, staged_bytes, off_dev, samples_dev, out_dev, rows, T, pad, mean_dev, std_dev,
+                              false, stream);
+}
+
+extern "C" int cn_op_fbank_packed_f32(const cn_fbank_opts* o, const void* wave_dev, int64_t wave_bytes, const int32_t* off_dev,
+                                      const int32_t* samples_dev, float* out_dev, int32_t rows, int32_t T, float pad, const double* mean_dev,
+                                      const double* std_dev, void* stream) {
+    return fbank_packed_entry("cn_op_fbank_packed_f32", o, wave_dev, wave_bytes, off_dev, samples_dev, out_dev, rows, T, pad, mean_dev, std_dev,
+                              true, stream);
+}
+
+extern "C" int64_t cn_resample_num_samples(int32_t in_rate, int32_t out_rate, int64_t in_samples) {
+    return resample_num_samples(in_rate, out_rate, in_samples);
+}
+
+extern "C" int cn_resample_table(int32_t in_rate, int32_t out_rate, int32_t* in_unit, int32_t* out_unit, int32_t* max_taps,
+                                 int32_t* first_host, int32_t* taps_host, float* weights_host, int64_t capacity) {
+    if (!in_unit || !out_unit || !max_taps) {
+        cn_set_error("cn_resample_table: null argument");
+        return -1;
+    }
+    return resample_table(in_rate, out_rate, in_unit, out_unit, max_taps, first_host, taps_host, weights_host, capacity);
+}
+
+extern "C" int cn_op_wave_resample(int32_t in_rate, int32_t out_rate, const void* staged_dev, int64_t staged_bytes, const int32_t* off_dev,
+                                   const int32_t* samples_dev, const int32_t* channels_dev, const int32_t* channel_dev,
+                                   const int32_t* channels_host, const int32_t* channel_host, int32_t utts, const int32_t* rows_dev,
+                                   int32_t rows, int64_t max_out, float* wave_dev, const int32_t* out_off_dev, void* stream) {
+    if (!staged_dev || !off_dev || !samples_dev || !channels_dev || !channel_dev || !channels_host || !channel_host || !wave_dev ||
+        !out_off_dev) {
+        cn_set_error("cn_op_wave_resample: null argument");
+        return -1;
+    }
+    if (in_rate <= 0 || out_rate <= 0) {
+        cn_set_error("cn_op_wave_resample: the rates must be positive");
+        return -1;
+    }
+    if (utts <= 0 || rows <= 0 || (!rows_dev && rows > utts) || max_out <= 0 || staged_bytes < 0) {
+        cn_set_error("cn_op_wave_resample: utts, rows (<= utts without a row list) and max_out must be positive");
+        return -1;
+    }
+    for (int32_t r = 0; r < utts; ++r)
+        if (channels_host[r] < 1 || channel_host[r] < 0 || channel_host[r] >= channels_host[r]) {
+            cn_set_error("cn_op_wave_resample: utterance #" + std::to_string(r) + ": channel " + std::to_string(channel_host[r]) + " of " +
+                         std::to_string(channels_host[r]));
+            return -1;
+        }
+    return launch_wave_resample(in_rate, out_rate, static_cast<const unsigned char*>(staged_dev), staged_bytes, off_dev, samples_dev, channels_dev,
+                                channel_dev, utts, rows_dev, rows, max_out, wave_dev, out_off_dev, (hipStream_t)stream);
 }
 
 extern "C" int cn_op_gemm(int32_t precision, const void* A, int32_t lda, const void* W, const float* bias, void* C,

@@ -10,6 +10,11 @@ reference's collate produces them, speech_loader.py:327-356).
 files hold them (``cn_host_gather`` into page-locked memory, one copy) and ``hip.fbank_packed`` computes the padded batch there, the
 global CMVN in the dataset's float64 arithmetic.  ``Fbank.from_conf`` reads a Kaldi option file (conf/fbank.conf).  Dither is not
 implemented: an absent ``--dither`` means 0 here, where Kaldi's default (1.0) adds noise that no two runs share.
+
+Files at another sample rate or of several channels (``--allow-downsample`` / ``--allow-upsample`` / ``--channel``, the options of
+compute-fbank-feats): ``packed(views, rates=..., channels=...)`` stages the interleaved int16 as it is, ``hip.wave_resample`` - Kaldi's
+LinearResample, one launch per distinct rate - writes the chosen channel at ``sample_rate`` as float32, and ``hip.fbank_packed_f32``
+computes the features from that.  A pass of mono files at ``sample_rate`` is the int16 path above, launch for launch.
 """
 import numpy as np
 import torch
@@ -21,7 +26,10 @@ WINDOWS = {"hamming": 0, "povey": 1, "hanning": 2, "rectangular": 3}
 CONF_OPTIONS = {"sample-frequency": ("sample_rate", float), "frame-length": ("frame_length_ms", float), "frame-shift": ("frame_shift_ms", float),
                 "preemphasis-coefficient": ("preemph", float), "remove-dc-offset": ("remove_dc", bool), "window-type": ("window", str),
                 "num-mel-bins": ("num_mel", int), "low-freq": ("low_freq", float), "high-freq": ("high_freq", float),
-                "use-power": ("use_power", bool), "use-log-fbank": ("use_log", bool)}
+                "use-power": ("use_power", bool), "use-log-fbank": ("use_log", bool),
+                # not part of the option block: which files the front-end admits (attributes of ``Fbank``)
+                "allow-downsample": ("allow_downsample", bool), "allow-upsample": ("allow_upsample", bool), "channel": ("channel", int)}
+ADMIT_OPTIONS = {"allow_downsample": False, "allow_upsample": False, "channel": -1}
 
 
 def _conf_bool(name, text):
@@ -33,7 +41,9 @@ def _conf_bool(name, text):
 def parse_conf(path):
     """A Kaldi option file (`--name=value` lines, blank lines, `#` comments) -> the keyword options of ``Fbank``.  `--use-energy=true`,
     `--snip-edges=false` and a non-zero `--dither` raise NotImplementedError (an absent `--dither` means 0: Kaldi's default adds
-    noise and cannot be compared); an option this front-end does not know raises ValueError."""
+    noise and cannot be compared); an option this front-end does not know raises ValueError.  `--allow-downsample`, `--allow-upsample`
+    and `--channel` (a Kaldi config file may hold any command-line option of the program) come back as ``allow_downsample``,
+    ``allow_upsample`` (0 / 1) and ``channel``."""
     opts = {}
     with open(path) as f:
         for raw in f:
@@ -62,18 +72,97 @@ def parse_conf(path):
                         raise ValueError("fbank conf: --window-type=%s (known: %s)" % (text, ", ".join(sorted(WINDOWS))))
                     opts[key] = text
                 else:
-                    opts[key] = kind(text)
+                    try:
+                        opts[key] = kind(text)
+                    except ValueError:
+                        raise ValueError("fbank conf: --%s=%s is not %s" % (name, text, "an integer" if kind is int else "a number"))
             else:
                 raise ValueError("fbank conf %s: unknown option --%s" % (path, name))
     return opts
 
 
+def plain_formats(sample_rate, rates, channels):
+    """Does a pass need neither resampling nor a channel pick (every rate the front-end's, every file mono)?"""
+    return (rates is None or all(int(r) == int(round(float(sample_rate))) for r in rates)) and (channels is None or all(int(c) == 1 for c in channels))
+
+
+# int32 arrays of `utts` entries each in the small DMA of a resampled pass: byte offset, samples per channel, channels, channel,
+# float offset of the resampled wave, its byte offset, its samples, the row lists of the rates (one after the other)
+RESAMPLE_META = 8
+
+
+def plan_resample(mv, U, opts, offs, lengths, rates, channels, channel, utts=None):
+    """Host side of a resampled pass.  ``mv``: int32 numpy array of at least ``RESAMPLE_META * U`` entries (page-locked: it is the
+    small DMA), filled here; ``offs`` / ``lengths``: per utterance the byte offset of the staged data chunk and its int16 values
+    (all channels); ``channel``: the front-end's ``--channel``.  -> dict: ``counts`` (samples per utterance at the front-end's
+    rate), ``wave_floats`` (the float32 wave buffer: utterance r at a multiple of 4 floats), ``groups`` [(rate, first entry of the
+    row list, rows, longest output count)], ``out_rate``."""
+    B = len(lengths)
+    if float(opts.sample_rate) != int(round(float(opts.sample_rate))) or opts.sample_rate < 1:
+        raise ValueError("fbank: resampling needs an integer --sample-frequency (it is %r)" % float(opts.sample_rate))
+    fo = int(round(float(opts.sample_rate)))
+
+    def name(b):
+        return "utterance %s" % (utts[b] if utts is not None and utts[b] is not None else "#%d" % b)
+
+    per, counts, chan = [], [], []
+    for b in range(B):
+        C = int(channels[b])
+        if C < 1 or int(lengths[b]) % C:
+            raise ValueError("%s: %d int16 values do not hold whole sample frames of %d channels" % (name(b), lengths[b], C))
+        if C > 1 and not 0 <= int(channel) < C:
+            raise ValueError("%s: %d channels, --channel=%d does not name one of them (set --channel to 0 .. %d)" % (name(b), C, channel, C - 1))
+        if int(rates[b]) < 1:
+            raise ValueError("%s: sample rate %d" % (name(b), rates[b]))
+        per.append(int(lengths[b]) // C)
+        chan.append(int(channel) if C > 1 else 0)
+        counts.append(hip.resample_num_samples(int(rates[b]), fo, per[-1]))
+    out_off = np.zeros(B, np.int64)
+    np.cumsum([(n + 3) // 4 * 4 for n in counts[:-1]], out=out_off[1:])
+    wave_floats = int(out_off[-1]) + (counts[-1] + 3) // 4 * 4
+    if 4 * wave_floats >= 2 ** 31:
+        raise ValueError("a pass of %d resampled float32 bytes (the offsets are int32)" % (4 * wave_floats))
+    mv[:B] = offs
+    mv[U:U + B] = per
+    mv[2 * U:2 * U + B] = channels
+    mv[3 * U:3 * U + B] = chan
+    mv[4 * U:4 * U + B] = out_off
+    mv[5 * U:5 * U + B] = out_off * 4
+    mv[6 * U:6 * U + B] = counts
+    groups, at = [], 0
+    for rate in sorted(set(int(r) for r in rates)):
+        rows = [b for b in range(B) if int(rates[b]) == rate]
+        mv[7 * U + at:7 * U + at + len(rows)] = rows
+        groups.append((rate, at, len(rows), max(counts[b] for b in rows)))
+        at += len(rows)
+    return {"counts": counts, "wave_floats": max(4, wave_floats), "groups": groups, "out_rate": fo, "B": B}
+
+
+def run_resampled(opts, plan, staged, total, mv, meta_d, U, wave, feats, pad, mean=None, std=None):
+    """Device side of a resampled pass, on the current stream: one ``hip.wave_resample`` per distinct rate over that rate's rows,
+    then ``hip.fbank_packed_f32`` over the float32 wave.  ``mv`` / ``meta_d``: the array ``plan_resample`` filled and its device copy."""
+    B = plan["B"]
+    for rate, at, n, max_out in plan["groups"]:
+        if max_out < 1:
+            continue
+        hip.wave_resample(rate, plan["out_rate"], staged, total, meta_d[:U], meta_d[U:2 * U], meta_d[2 * U:3 * U], meta_d[3 * U:4 * U],
+                          mv[2 * U:2 * U + B], mv[3 * U:3 * U + B], wave, meta_d[4 * U:5 * U], max_out,
+                          rows=meta_d[7 * U + at:7 * U + at + n], n_rows=n)
+    hip.fbank_packed_f32(opts, wave, 4 * plan["wave_floats"], meta_d[5 * U:6 * U], meta_d[6 * U:7 * U], feats, pad, mean, std)
+
+
 class Fbank:
     def __init__(self, cmvn_mean=None, cmvn_std=None, pad_value=0.0, device=None, splice=None, **opts):
         """opts: sample_rate, frame_length_ms, frame_shift_ms, preemph, low_freq, high_freq, num_mel, window, remove_dc, ...
-        ``splice`` = (left, right, skip): ``packed()`` splices and skips the normalised frames as the dataset does (``hip.splice_rows``)."""
+        ``splice`` = (left, right, skip): ``packed()`` splices and skips the normalised frames as the dataset does (``hip.splice_rows``).
+        ``allow_downsample`` / ``allow_upsample`` / ``channel`` (Kaldi's defaults: false, false, -1) say which files are admitted
+        (``wave_io``); they are attributes, not part of the option block: ``key()`` does not see them."""
         from .speech_loader import splice_triple
 
+        self.allow_downsample = bool(opts.pop("allow_downsample", ADMIT_OPTIONS["allow_downsample"]))
+        self.allow_upsample = bool(opts.pop("allow_upsample", ADMIT_OPTIONS["allow_upsample"]))
+        self.channel = int(opts.pop("channel", ADMIT_OPTIONS["channel"]))
+        self.resampled_passes = 0
         self.splice = splice_triple(*splice) if splice else None
         self.L = hip.lib()
         self.o = hip.CnFbankOpts()
@@ -111,10 +200,19 @@ class Fbank:
         """The option block as bytes: what tells two front-ends apart."""
         return bytes(self.o)
 
-    def packed(self, views, utts=None):
+    def admit(self):
+        """The keyword options of ``wave_io`` that say which files this front-end takes."""
+        return {"allow_downsample": self.allow_downsample, "allow_upsample": self.allow_upsample, "channel": self.channel}
+
+    def packed(self, views, utts=None, rates=None, channels=None):
         """``views``: one-dimensional int16 arrays (``wave_io.pcm_view``) -> (feats (B, T, num_mel) float32 cuda, ratios (B,) float32
         host) on the current stream.  The samples travel as they are - gathered at 16-byte-aligned offsets into page-locked memory,
-        one copy - and ``hip.fbank_packed`` computes the padded batch on the device; no padded float matrix exists on the host."""
+        one copy - and ``hip.fbank_packed`` computes the padded batch on the device; no padded float matrix exists on the host.
+        ``rates`` / ``channels``: per utterance the file's sample rate and channel count (``wave_io.pcm_frames``; the views then hold
+        the interleaved data chunks).  None, or every rate equal to ``sample_rate`` and every file mono: exactly the path above.
+        Otherwise channel ``self.channel`` of every file is brought to ``sample_rate`` on the device first (``_packed_resampled``)."""
+        if not plain_formats(self.o.sample_rate, rates, channels):
+            return self._packed_resampled(views, utts, rates, channels)
         frames = [self.num_frames(len(v)) for v in views]
         for b, n in enumerate(frames):
             if n < 1:
@@ -135,21 +233,55 @@ class Fbank:
             staged = host.to(self.device, non_blocking=True)
             meta_d = meta.to(self.device, non_blocking=True)
             hip.fbank_packed(self.o, staged, total, meta_d[:B], meta_d[B:], feats, self.pad_value, self.mean64, self.std64)
-            if self.splice is None:
-                return feats, torch.tensor([n / T for n in frames], dtype=torch.float32)
-            # the set splices / skips: a second launch reads the normalised batch (utterance b at row b * T, its own frames only)
-            from .speech_loader import spliced_frames
+            return self._spliced(feats, frames)
 
-            left, right, skip = self.splice
-            n_out = [spliced_frames(n, self.splice) for n in frames]
-            sp = torch.empty(2 * B, dtype=torch.int32, pin_memory=True)
-            spv = sp.numpy()
-            spv[:B] = np.arange(B, dtype=np.int64) * T
-            spv[B:] = frames
-            sp_d = sp.to(self.device, non_blocking=True)
-            out = torch.empty(B, max(n_out), (left + right + 1) * self.o.num_mel, dtype=torch.float32, device=self.device)
-            hip.splice_rows(feats, sp_d[:B], sp_d[B:], out, left, right, skip, self.pad_value)
+    def _spliced(self, feats, frames):
+        """The tail of ``packed``, inside its device context: (feats, ratios), spliced and skipped when the front-end has a triple."""
+        B, T = feats.shape[0], feats.shape[1]
+        if self.splice is None:
+            return feats, torch.tensor([n / T for n in frames], dtype=torch.float32)
+        # the set splices / skips: a second launch reads the normalised batch (utterance b at row b * T, its own frames only)
+        from .speech_loader import spliced_frames
+
+        left, right, skip = self.splice
+        n_out = [spliced_frames(n, self.splice) for n in frames]
+        sp = torch.empty(2 * B, dtype=torch.int32, pin_memory=True)
+        spv = sp.numpy()
+        spv[:B] = np.arange(B, dtype=np.int64) * T
+        spv[B:] = frames
+        sp_d = sp.to(self.device, non_blocking=True)
+        out = torch.empty(B, max(n_out), (left + right + 1) * self.o.num_mel, dtype=torch.float32, device=self.device)
+        hip.splice_rows(feats, sp_d[:B], sp_d[B:], out, left, right, skip, self.pad_value)
         return out, torch.tensor([n / max(n_out) for n in n_out], dtype=torch.float32)
+
+    def _packed_resampled(self, views, utts, rates, channels):
+        """``packed`` for files at other rates / of several channels: the interleaved int16 is staged as it is (same gather, same
+        single copy), one ``hip.wave_resample`` per distinct rate writes the chosen channel at ``sample_rate`` into a float32 wave
+        buffer, ``hip.fbank_packed_f32`` reads that, and the splice follows as ever."""
+        B = len(views)
+        rates = [int(round(float(self.o.sample_rate)))] * B if rates is None else [int(r) for r in rates]
+        channels = [1] * B if channels is None else [int(c) for c in channels]
+        views = [np.ascontiguousarray(v, dtype="<i2") for v in views]
+        offs, total = hip.gather_offsets([v.nbytes for v in views], 16)
+        if total >= 2 ** 31:
+            raise ValueError("Fbank.packed: a batch of %d bytes (the offsets are int32)" % total)
+        meta = torch.empty(RESAMPLE_META * B, dtype=torch.int32, pin_memory=True)
+        plan = plan_resample(meta.numpy(), B, self.o, offs, [v.shape[0] for v in views], rates, channels, self.channel, utts)
+        frames = [self.num_frames(n) for n in plan["counts"]]
+        for b, n in enumerate(frames):
+            if n < 1:
+                raise ValueError("utterance %s: %d samples at %d Hz are shorter than one analysis window"
+                                 % (utts[b] if utts is not None else "#%d" % b, plan["counts"][b], plan["out_rate"]))
+        host = torch.empty(total, dtype=torch.uint8, pin_memory=True)
+        hip.host_gather(host.data_ptr(), views, 1, align=16)
+        feats = torch.empty(B, max(frames), self.o.num_mel, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            staged = host.to(self.device, non_blocking=True)
+            meta_d = meta.to(self.device, non_blocking=True)
+            wave = torch.empty(plan["wave_floats"], dtype=torch.float32, device=self.device)
+            run_resampled(self.o, plan, staged, total, meta.numpy(), meta_d, B, wave, feats, self.pad_value, self.mean64, self.std64)
+            self.resampled_passes += 1
+            return self._spliced(feats, frames)
 
     def __call__(self, waves):
         """waves: list of 1-D arrays / tensors on the int16 scale (what Kaldi reads from a wav file)."""

@@ -68,12 +68,15 @@ class WaveBatch(object):
     frame counts.  ``shape`` is the padded FEATURE shape (B, longest frame count, num_mel) - with a ``splice`` triple the spliced one,
     (B, longest spliced count, (left + right + 1) * num_mel); ``frames`` stay the front-end's own counts -, so that batch counting,
     progress printing and ``first.shape[1]`` work as for a tensor; the features themselves are computed on the device, in the task's
-    own process (``Fbank.packed`` / the packed reader's wave form)."""
+    own process (``Fbank.packed`` / the packed reader's wave form).  ``formats``: per utterance the file's (rate, channels) - the
+    views then hold the interleaved data chunks and ``frames`` count the RESAMPLED wave's frames; None: mono files at the
+    front-end's rate."""
 
-    __slots__ = ("views", "frames", "utts", "shape", "dtype", "is_cuda", "splice")
+    __slots__ = ("views", "frames", "utts", "shape", "dtype", "is_cuda", "splice", "formats")
 
-    def __init__(self, views, frames, num_mel, utts=None, splice=None):
+    def __init__(self, views, frames, num_mel, utts=None, splice=None, formats=None):
         self.views, self.frames, self.utts = list(views), [int(n) for n in frames], utts
+        self.formats = None if formats is None else [(int(r), int(c)) for r, c in formats]
         self.splice = splice_triple(*splice) if splice else None
         blocks = (self.splice[0] + self.splice[1] + 1) if self.splice else 1
         self.shape = (len(self.views), max(spliced_frames(n, self.splice) for n in self.frames), blocks * int(num_mel))
@@ -81,12 +84,18 @@ class WaveBatch(object):
         self.is_cuda = False
 
 
-def front_end_options(args):
-    """The fbank option block (``hip.CnFbankOpts``) of ``--hip_fbank_conf`` (default: the built-in options)."""
+def front_end(args):
+    """The front-end ``--hip_fbank_conf`` describes (default: the built-in options): its option block is ``.o``, ``.admit()`` says
+    which files it takes (`--allow-downsample`, `--allow-upsample`, `--channel`)."""
     from .fbank import Fbank
 
     conf = getattr(args, "hip_fbank_conf", "") or ""
-    return (Fbank.from_conf(conf) if conf else Fbank()).o
+    return Fbank.from_conf(conf) if conf else Fbank()
+
+
+def front_end_options(args):
+    """The fbank option block (``hip.CnFbankOpts``) of ``--hip_fbank_conf`` (default: the built-in options)."""
+    return front_end(args).o
 
 
 def frames_of(opts, samples):
@@ -150,22 +159,36 @@ class SpeechDataset(Dataset):
 
     def _init_wave_set(self, args):
         """A wave set: the entries are sound files, the dataset hands out (utt, int16 view, text) and the features are computed on
-        the device by the consumer.  Every header is checked here - format, rate, at least one frame - so that a bad file is named
-        before anything is decoded."""
+        the device by the consumer.  Every header is read once and checked here - format, rate and channels against what the
+        front-end admits, at least one frame of the wave at the front-end's rate (``cn_resample_num_samples`` of the file's samples)
+        - so that a bad file is named before anything is decoded.  ``wave_formats`` keeps each file's (rate, channels)."""
         if self.left_context != 0:
             raise NotImplementedError("audio input with left_ctx = %d (right_ctx >= 0 and skip_frame >= 1 are spliced on the device; a "
                                       "left context on audio input is not implemented)" % self.left_context)
         if self.right_context < 0 or self.skip_frame < 0:
             raise ValueError("audio input: right_ctx = %d, skip_frame = %d" % (self.right_context, self.skip_frame))
-        self.fbank_opts = front_end_options(args)
+        fe = front_end(args)
+        self.fbank_opts, self.wave_admit = fe.o, fe.admit()
         self.sample_rate, self.num_mel = float(self.fbank_opts.sample_rate), int(self.fbank_opts.num_mel)
-        self.wave_frames = []
+        self.wave_frames, self.wave_formats = [], []
+        own = int(round(self.sample_rate))
         for utt, spec, _ in self._items:
-            n = wave_io.num_samples(spec, self.sample_rate, utt)
+            n, rate, channels = wave_io.wave_format(spec, self.sample_rate, utt, **self.wave_admit)
+            if rate != own:
+                if self.sample_rate != own:
+                    raise ValueError("utterance %s (%s): %d Hz, and resampling needs an integer --sample-frequency (it is %r)"
+                                     % (utt, spec, rate, self.sample_rate))
+                from .. import hip
+
+                n = hip.resample_num_samples(rate, own, n)
             frames = frames_of(self.fbank_opts, n)
             if frames < 1:
-                raise ValueError("utterance %s (%s): %d samples give no frame (shorter than one analysis window)" % (utt, spec, n))
+                raise ValueError("utterance %s (%s): %d samples%s give no frame (shorter than one analysis window)"
+                                 % (utt, spec, n, "" if rate == own else " at %d Hz (resampled from %d Hz)" % (own, rate)))
             self.wave_frames.append(frames)
+            self.wave_formats.append((rate, channels))
+        # (a set of mono files at the front-end's rate - every set there was before the options - hands out plain sample views)
+        self.wave_plain = all(f == (own, 1) for f in self.wave_formats)
         self.is_wave = True
         self._kinds = frozenset(["WAV"])
 
@@ -184,7 +207,10 @@ class SpeechDataset(Dataset):
     def __getitem__(self, idx):
         utt, spec, text = self._items[idx]
         if self.is_wave:  # (the samples as the file holds them; normalisation happens with the features, on the device)
-            return utt, wave_io.pcm_view(spec, self.sample_rate, utt), text
+            if self.wave_plain:
+                return utt, wave_io.pcm_view(spec, self.sample_rate, utt), text
+            # (the interleaved data chunk; ``wave_formats[idx]`` says what it holds, resampling and the channel pick happen on the device)
+            return utt, wave_io.pcm_frames(spec, self.sample_rate, utt, **self.wave_admit)[0], text
         if self.left_context == 0 and self.right_context == 0 and self.skip_frame <= 1:
             # No splicing, no frame skipping (the benchmark's configuration; the recipes' decode YAMLs splice - right_ctx 2 - and
             # take the general path below, or the packed reader's device splice).  Same values as the general path - the CMVN in
@@ -285,11 +311,19 @@ def collate(batch, padding_idx=0):
     return utts, feats, texts, ratios, sizes
 
 
-def collate_waves(batch, padding_idx=0, opts=None, splice=None):
+def collate_waves(batch, padding_idx=0, opts=None, splice=None, formats=None):
     """``collate`` for a wave set: list of (utt, int16 samples, text) -> the same five-tuple with a ``WaveBatch`` where the padded
     features would stand (no GPU is touched here: a loader worker process may run it).  With a ``splice`` triple the ratios are the
-    spliced frame counts' (``spliced_frames``)."""
-    frames = [frames_of(opts, int(x[1].shape[0])) for x in batch]
+    spliced frame counts' (``spliced_frames``).  ``formats``: {utt: (rate, channels)} of a set that holds other files than mono ones
+    at the front-end's rate (their samples are the interleaved data chunks; the frames are those of the resampled wave)."""
+    if formats is None:
+        frames, fmts = [frames_of(opts, int(x[1].shape[0])) for x in batch], None
+    else:
+        from .. import hip
+
+        own = int(round(float(opts.sample_rate)))
+        fmts = [formats[x[0]] for x in batch]
+        frames = [frames_of(opts, hip.resample_num_samples(r, own, int(x[1].shape[0]) // c)) for x, (r, c) in zip(batch, fmts)]
     n_out = [spliced_frames(n, splice) for n in frames]
     t_max = max(n_out)
     l_max = max(len(x[2]) for x in batch)
@@ -302,7 +336,7 @@ def collate_waves(batch, padding_idx=0, opts=None, splice=None):
         ratios[b] = n_out[b] / t_max
         sizes[b] = len(text) - 2
         utts.append(utt)
-    return utts, WaveBatch([x[1] for x in batch], frames, opts.num_mel, utts, splice=splice), texts, ratios, sizes
+    return utts, WaveBatch([x[1] for x in batch], frames, opts.num_mel, utts, splice=splice, formats=fmts), texts, ratios, sizes
 
 
 def _one_thread_worker(_worker_id):
@@ -323,7 +357,9 @@ class SpeechDataLoader(DataLoader):
         # worker processes hand their batches over in shared memory, from which a host -> device copy is pathologically slow
         # (83 ms per 9-MB batch measured): the loader's pinning thread moves them into page-locked memory first
         super().__init__(dataset, batch_sampler=batches, num_workers=num_workers,
-                         collate_fn=(functools.partial(collate_waves, padding_idx=padding_idx, opts=dataset.fbank_opts, splice=dataset.splice())
+                         collate_fn=(functools.partial(collate_waves, padding_idx=padding_idx, opts=dataset.fbank_opts, splice=dataset.splice(),
+                                                       formats=None if dataset.wave_plain else
+                                                       {it[0]: f for it, f in zip(dataset._items, dataset.wave_formats)})
                                      if getattr(dataset, "is_wave", False) else functools.partial(collate, padding_idx=padding_idx)),
                          pin_memory=bool(num_workers > 0 and torch.cuda.is_available()),
                          worker_init_fn=_one_thread_worker if num_workers > 0 else None,

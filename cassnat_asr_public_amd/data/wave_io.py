@@ -1,7 +1,9 @@
 """RIFF/WAVE files as a `wav.scp` names them: header parsing and zero-copy access to the samples.
 
 The reference never opens a sound file - its recipes run Kaldi's `compute-fbank-feats` first - so this is the part of Kaldi's
-`wave-reader.cc` the recogniser needs to start from audio: 16-bit PCM, one channel, at the front-end's sample rate.  The chunks of
+`wave-reader.cc` the recogniser needs to start from audio: 16-bit PCM; one channel at the front-end's sample rate, or - with the
+front-end's `--allow-downsample` / `--allow-upsample` / `--channel` (``wave_format``, ``pcm_frames``) - another rate and several
+interleaved channels, of which one is read.  The chunks of
 the file are walked (anything may sit before `data`: `LIST`, `fact`, ...; an odd-sized chunk is followed by a pad byte),
 `WAVE_FORMAT_EXTENSIBLE` is accepted with the PCM sub-format, and a `data` size of 0 or 0xFFFFFFFF means "to the end of the file", as
 Kaldi reads streamed files.  Everything else raises a ValueError that names the utterance and the reason; an `.scp` entry that is a
@@ -85,18 +87,30 @@ def read_header(path, utt=None):
             pos += 8 + csize + (csize & 1)
 
 
-def _checked(path, sample_rate, utt):
+def _checked(path, sample_rate, utt, allow_downsample=False, allow_upsample=False, channel=-1):
+    """-> (data offset, samples per channel, rate, channels) of a file the front-end admits; everything else raises, naming the
+    utterance and - where there is one - the option that would admit the file."""
     rate, channels, bits, tag, start, nbytes = read_header(path, utt)
     who = _who(path, utt)
     if tag != PCM:
         raise ValueError("%s: format tag %d (%s), only 16-bit PCM is read" % (who, tag, "IEEE float" if tag == IEEE_FLOAT else "not PCM"))
     if bits != 16:
         raise ValueError("%s: %d-bit samples, only 16-bit PCM is read" % (who, bits))
-    if channels != 1:
-        raise ValueError("%s: %d channels, only one channel is read" % (who, channels))
+    if channels < 1:
+        raise ValueError("%s: %d channels" % (who, channels))
+    if channels != 1 and not 0 <= int(channel) < channels:
+        if int(channel) < 0:
+            raise ValueError("%s: %d channels, only one channel is read (--channel=0 .. %d chooses it)" % (who, channels, channels - 1))
+        raise ValueError("%s: %d channels, --channel=%d does not name one of them (--channel=0 .. %d)" % (who, channels, int(channel), channels - 1))
     if sample_rate is not None and int(rate) != int(round(float(sample_rate))):
-        raise ValueError("%s: sample rate %d Hz, the front-end is set to %d Hz (no resampling)" % (who, rate, int(round(float(sample_rate)))))
-    return start, nbytes // 2
+        want = int(round(float(sample_rate)))
+        if rate < 1:
+            raise ValueError("%s: sample rate %d Hz" % (who, rate))
+        if rate > want and not allow_downsample:
+            raise ValueError("%s: sample rate %d Hz, the front-end is set to %d Hz (no resampling; --allow-downsample=true admits it)" % (who, rate, want))
+        if rate < want and not allow_upsample:
+            raise ValueError("%s: sample rate %d Hz, the front-end is set to %d Hz (no resampling; --allow-upsample=true admits it)" % (who, rate, want))
+    return start, nbytes // (2 * channels), int(rate), int(channels)
 
 
 def num_samples(path, sample_rate=None, utt=None):
@@ -107,9 +121,28 @@ def num_samples(path, sample_rate=None, utt=None):
 def pcm_view(path, sample_rate=None, utt=None):
     """A read-only '<i2' numpy view of the samples inside a memory map of the file (no copy; the descriptor is closed once the
     file is mapped, the map goes with the last view into it)."""
-    start, n = _checked(path, sample_rate, utt)
+    return _view(path, *_checked(path, sample_rate, utt)[:2])
+
+
+def _view(path, start, n):
     if n == 0:
         return np.zeros(0, "<i2")
     with open(path, "rb") as f:
         mm = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ)
     return np.frombuffer(mm, dtype="<i2", count=n, offset=start)
+
+
+def wave_format(path, sample_rate=None, utt=None, allow_downsample=False, allow_upsample=False, channel=-1):
+    """-> (samples per channel, rate, channels) from the header alone, for a front-end with Kaldi's `--allow-downsample`,
+    `--allow-upsample` and `--channel` (compute-fbank-feats): a file at a higher rate than ``sample_rate`` needs ``allow_downsample``,
+    one at a lower rate ``allow_upsample``, a file of C > 1 channels ``channel`` in [0, C).  ``channel`` = -1 with C > 1 raises: Kaldi
+    warns and takes channel 0, here the choice has to be spelled out.  At the defaults this admits what ``pcm_view`` admits."""
+    return _checked(path, sample_rate, utt, allow_downsample, allow_upsample, channel)[1:]
+
+
+def pcm_frames(path, sample_rate=None, utt=None, allow_downsample=False, allow_upsample=False, channel=-1):
+    """``pcm_view`` for such a front-end: -> (view, rate, channels), the view the read-only '<i2' INTERLEAVED data chunk (sample j of
+    channel c at j * channels + c; whole sample frames only) inside a memory map of the file.  Picking the channel and resampling
+    happen on the device (``hip.wave_resample``)."""
+    start, n, rate, channels = _checked(path, sample_rate, utt, allow_downsample, allow_upsample, channel)
+    return _view(path, start, n * channels), rate, channels

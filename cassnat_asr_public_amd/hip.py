@@ -224,6 +224,12 @@ def lib(flavour=None):
                            C.c_int32, C.c_float, C.c_void_p]
     L.cn_op_fbank_packed.argtypes = [C.POINTER(CnFbankOpts), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                      C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.cn_op_fbank_packed_f32.argtypes = L.cn_op_fbank_packed.argtypes
+    L.cn_resample_num_samples.argtypes = [C.c_int32, C.c_int32, C.c_int64]
+    L.cn_resample_num_samples.restype = C.c_int64
+    L.cn_resample_table.argtypes = [C.c_int32, C.c_int32] + [C.POINTER(C.c_int32)] * 3 + [C.c_void_p] * 3 + [C.c_int64]
+    L.cn_op_wave_resample.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_int64] + [C.c_void_p] * 6 + [C.c_int32, C.c_void_p, C.c_int32,
+                                                                                                      C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     L.cn_esa_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(CnDecodeOpts), C.c_void_p]
     L.cn_esa_sample.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.POINTER(CnDecodeOpts), C.c_void_p,
                                 C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_void_p]
@@ -366,6 +372,59 @@ def fbank_packed(opts, staged, staged_bytes, off, samples, out, pad, mean=None, 
     check(lib().cn_op_fbank_packed(opts, _ptr(staged), int(staged_bytes), _ptr(off), _ptr(samples), _ptr(out), rows, T, float(pad),
                                    _ptr(mean), _ptr(std), current_stream()), "cn_op_fbank_packed")
     return out
+
+
+def fbank_packed_f32(opts, wave, wave_bytes, off, samples, out, pad, mean=None, std=None):
+    """``fbank_packed`` for float32 samples on the int16 scale (cn_op_fbank_packed_f32): ``wave`` float32 CUDA, utterance r with
+    samples[r] samples at BYTE offset off[r], a multiple of 16 - the wave ``wave_resample`` wrote.  Same kernel, same values bit for
+    bit for the same samples."""
+    rows, T, F = out.shape
+    assert out.is_contiguous() and out.element_size() == 4 and wave.is_contiguous() and wave.element_size() == 4
+    assert F == opts.num_mel and 0 <= int(wave_bytes) <= 4 * wave.numel() and off.numel() >= rows and samples.numel() >= rows
+    check(lib().cn_op_fbank_packed_f32(opts, _ptr(wave), int(wave_bytes), _ptr(off), _ptr(samples), _ptr(out), rows, T, float(pad),
+                                       _ptr(mean), _ptr(std), current_stream()), "cn_op_fbank_packed_f32")
+    return out
+
+
+def resample_num_samples(in_rate, out_rate, samples):
+    """Outputs of Kaldi's LinearResample for ``samples`` inputs, flushed (cn_resample_num_samples; host only)."""
+    return int(lib().cn_resample_num_samples(int(in_rate), int(out_rate), int(samples)))
+
+
+def resample_table(in_rate, out_rate):
+    """The weight table of a rate pair exactly as the device gets it (cn_resample_table; host only) -> dict: ``in_unit``, ``out_unit``
+    (the phases), ``max_taps``, ``first`` / ``taps`` int32 (out_unit,), ``weights`` float32 (max_taps, out_unit), zero behind a
+    phase's taps."""
+    iu, ou, mt = C.c_int32(), C.c_int32(), C.c_int32()
+    L = lib()
+    check(L.cn_resample_table(int(in_rate), int(out_rate), C.byref(iu), C.byref(ou), C.byref(mt), None, None, None, 0), "cn_resample_table")
+    first, taps = np.zeros(ou.value, np.int32), np.zeros(ou.value, np.int32)
+    weights = np.zeros((mt.value, ou.value), np.float32)
+    check(L.cn_resample_table(int(in_rate), int(out_rate), C.byref(iu), C.byref(ou), C.byref(mt), first.ctypes.data_as(C.c_void_p),
+                              taps.ctypes.data_as(C.c_void_p), weights.ctypes.data_as(C.c_void_p), weights.size), "cn_resample_table")
+    return {"in_unit": iu.value, "out_unit": ou.value, "max_taps": mt.value, "first": first, "taps": taps, "weights": weights}
+
+
+def wave_resample(in_rate, out_rate, staged, staged_bytes, off, samples, channels, channel, channels_host, channel_host, wave, out_off,
+                  max_out, rows=None, n_rows=None):
+    """Sample-rate conversion and channel pick on the device (cn_op_wave_resample), the utterances of ONE source rate: ``staged``
+    uint8 CUDA bytes holding the data chunks as the files hold them (interleaved int16; utterance r: channels[r] channels of
+    samples[r] samples at BYTE offset off[r], a multiple of 16) -> channel channel[r] at ``out_rate``, float32, written to ``wave``
+    from float offset out_off[r] on: ``resample_num_samples`` values, nothing else.  ``rows`` (int32 CUDA): the utterances of this
+    call (None: the first ``n_rows``, default all); ``max_out``: their longest output count.  ``channels_host`` / ``channel_host``:
+    int32 numpy arrays of the same values, checked before the launch."""
+    utts = int(channels_host.shape[0])
+    assert staged.is_contiguous() and staged.element_size() == 1 and 0 <= int(staged_bytes) <= staged.numel()
+    assert wave.is_contiguous() and wave.element_size() == 4
+    assert channels_host.dtype == np.int32 and channel_host.dtype == np.int32 and channel_host.shape[0] == utts
+    assert channels_host.flags.c_contiguous and channel_host.flags.c_contiguous
+    assert min(off.numel(), samples.numel(), channels.numel(), channel.numel(), out_off.numel()) >= utts
+    n = int(rows.numel() if rows is not None and n_rows is None else (utts if n_rows is None else n_rows))
+    assert rows is None or rows.numel() >= n
+    check(lib().cn_op_wave_resample(int(in_rate), int(out_rate), _ptr(staged), int(staged_bytes), _ptr(off), _ptr(samples), _ptr(channels),
+                                    _ptr(channel), channels_host.ctypes.data_as(C.c_void_p), channel_host.ctypes.data_as(C.c_void_p), utts,
+                                    _ptr(rows), n, int(max_out), _ptr(wave), _ptr(out_off), current_stream()), "cn_op_wave_resample")
+    return wave
 
 
 class Engine:

@@ -68,7 +68,10 @@ class PackedBatch:
     The WAVE form (``from_waves``; ``kinds`` is the string "wave") keeps per utterance a read-only '<i2' view of the samples inside the
     memory map of its sound file (``data.wave_io.pcm_view``); ``lens`` are the frame counts of the fbank front-end and ``shape`` the
     padded FEATURE shape.  The pipelines stage the samples as they are and ``hip.fbank_packed`` computes the features on the
-    device; there is no host fbank in the product, so ``padded()`` and ``matrices()`` raise.
+    device; there is no host fbank in the product, so ``padded()`` and ``matrices()`` raise.  With ``formats`` - per utterance the
+    file's (rate, channels) - the views hold the INTERLEAVED data chunks of files at other rates or of several channels, ``channel``
+    is the one that is read, and ``lens`` count the frames of the wave at the front-end's rate: ``hip.wave_resample`` writes that
+    wave on the device, ``hip.fbank_packed_f32`` reads it.
 
     SPLICING (``splice`` = (left, right, skip), every form): the set splices and / or skips frames (the recipes' decode YAMLs:
     0 / 2 / 1).  ``lens`` stay the SOURCE rows and ``source_shape`` the unspliced (B, longest source count, F0); ``shape`` is what the
@@ -77,11 +80,12 @@ class PackedBatch:
     CMVN in float64, zero rows up to a multiple of skip, ``feat_op.context_feat``, ``feat_op.skip_feat``, then padding): the
     definition ``hip.splice_rows`` is held to."""
 
-    __slots__ = ("views", "lens", "shape", "dtype", "is_cuda", "kinds", "utts", "splice", "source_shape", "out_lens")
+    __slots__ = ("views", "lens", "shape", "dtype", "is_cuda", "kinds", "utts", "splice", "source_shape", "out_lens", "formats", "channel")
 
     def __init__(self, views, utts=None, splice=None):
         self.views = views
         self.kinds = None
+        self.formats, self.channel = None, -1
         self.utts = utts
         self.lens = [int(v.shape[0]) for v in views]
         self.shape = (len(views), max(self.lens), int(views[0].shape[1]))
@@ -142,6 +146,7 @@ class PackedBatch:
             return cls(views, utts, splice=splice)
         self = cls.__new__(cls)
         self.views, self.kinds, self.lens, self.utts = views, kinds, lens, utts
+        self.formats, self.channel = None, -1
         self.shape = (len(views), max(lens), want_cols)
         self.dtype = torch.float32
         self.is_cuda = False
@@ -149,10 +154,12 @@ class PackedBatch:
         return self
 
     @classmethod
-    def from_waves(cls, views, frames, num_mel, utts=None, splice=None):
+    def from_waves(cls, views, frames, num_mel, utts=None, splice=None, formats=None, channel=-1):
         """``views``: one '<i2', one-dimensional, C-contiguous array of samples per utterance; ``frames``: their frame counts under
         the front-end's options (``Fbank.num_frames``).  Anything else - and an utterance of zero frames - raises a ValueError that
-        names the utterance."""
+        names the utterance.  ``formats``: per utterance (rate, channels) of its file - the view is then the interleaved data chunk
+        (``wave_io.pcm_frames``), ``frames`` count the wave at the front-end's rate and ``channel`` (the front-end's `--channel`)
+        must name a channel of every file that has more than one; None: mono files at the front-end's rate."""
         def name(b):
             return "utterance %s" % (utts[b] if utts is not None else "#%d of the batch" % b)
 
@@ -160,14 +167,24 @@ class PackedBatch:
             raise ValueError("PackedBatch: an empty batch")
         if len(frames) != len(views):
             raise ValueError("PackedBatch: %d frame counts for %d utterances" % (len(frames), len(views)))
+        if formats is not None and len(formats) != len(views):
+            raise ValueError("PackedBatch: %d (rate, channels) pairs for %d utterances" % (len(formats), len(views)))
         for b, v in enumerate(views):
             if not isinstance(v, np.ndarray) or v.dtype != np.dtype("<i2") or v.ndim != 1 or not v.flags.c_contiguous:
                 raise ValueError("PackedBatch: %s: the samples must be a one-dimensional C-contiguous '<i2' array (got %s)"
                                  % (name(b), "%s %s" % (getattr(v, "dtype", type(v).__name__), getattr(v, "shape", ""))))
             if int(frames[b]) < 1:
                 raise ValueError("PackedBatch: %s: %d samples give no frame" % (name(b), v.shape[0]))
+            if formats is not None:
+                rate, chans = int(formats[b][0]), int(formats[b][1])
+                if rate < 1 or chans < 1 or v.shape[0] % chans:
+                    raise ValueError("PackedBatch: %s: %d int16 values at (rate, channels) = (%d, %d)" % (name(b), v.shape[0], rate, chans))
+                if chans > 1 and not 0 <= int(channel) < chans:
+                    raise ValueError("PackedBatch: %s: %d channels, channel %d is not one of them" % (name(b), chans, int(channel)))
         self = cls.__new__(cls)
         self.views, self.kinds, self.utts = list(views), "wave", utts
+        self.formats = None if formats is None else [(int(r), int(c)) for r, c in formats]
+        self.channel = int(channel)
         self.lens = [int(n) for n in frames]
         self.shape = (len(views), max(self.lens), int(num_mel))
         self.dtype = torch.float32
@@ -319,7 +336,7 @@ class DecodePipelines:
         self._rows_lock = threading.Lock()
         self._stats_lock = threading.Lock()
         self.timeline = None  # a list: the workers and the consumer append (label, pipeline, perf_counter) - bench.py --host-timeline
-        self.stats = {"passes": 0, "batches": 0, "predicted": 0, "missed": 0, "merged_ragged": 0, "compressed_passes": 0, "wave_passes": 0, "spliced_passes": 0,
+        self.stats = {"passes": 0, "batches": 0, "predicted": 0, "missed": 0, "merged_ragged": 0, "compressed_passes": 0, "wave_passes": 0, "resampled_passes": 0, "spliced_passes": 0,
                       # host seconds of the worker threads, by what they were doing (summed over the pipelines)
                       "s_take": 0.0, "s_stage": 0.0, "s_launch": 0.0, "s_retire_wait": 0.0}
 
@@ -624,8 +641,14 @@ class DecodePipelines:
         file holds them, each at a 16-byte-aligned offset (one ``cn_host_gather`` call), ONE DMA takes those bytes to the device, the
         per-utterance (byte offset, samples, ratio) follow in the small DMA, and ``hip.fbank_packed`` computes the padded
         (rows, tmax, F) features, normalised with the pipelines' statistics when they have them.  The buffers are sized in bytes: a
-        frame shift of samples is 320 bytes at the default options, what 80 float32 features take."""
+        frame shift of samples is 320 bytes at the default options, what 80 float32 features take.
+
+        A pass that holds files at other rates or of several channels (``PackedBatch.formats``) stages the interleaved data chunks
+        in the same buffers - sized in the bytes the files hold -, and on the pass's stream one ``hip.wave_resample`` per distinct
+        rate writes the chosen channel at the front-end's rate into the slot's float32 wave scratch, which ``hip.fbank_packed_f32``
+        reads (``data.fbank.plan_resample`` / ``run_resampled``).  A pass that needs neither is the pass above, launch for launch."""
         from . import hip
+        from .data.fbank import RESAMPLE_META, plain_formats, plan_resample, run_resampled
 
         if self.fbank is None:
             raise ValueError("DecodePipelines: a wave batch, but the pipelines were built without fbank options")
@@ -635,6 +658,11 @@ class DecodePipelines:
         if F0 != int(self.fbank.num_mel) or any(b.shape[2] != F or b.source_shape[2] != F0 for b in batches):
             raise ValueError("DecodePipelines: wave batches of %d features, the front-end computes %d" % (F0, int(self.fbank.num_mel)))
         views = [v for b in batches for v in b.views]
+        own = int(round(float(self.fbank.sample_rate)))
+        formats = [f for b in batches for f in (b.formats if b.formats is not None else [(own, 1)] * len(b.views))]
+        resample = not plain_formats(self.fbank.sample_rate, [r for r, _ in formats], [c for _, c in formats])
+        if resample and len(set(b.channel for b in batches if b.formats is not None)) > 1:
+            raise ValueError("DecodePipelines: a pass mixes wave batches that read different channels")
         offs, total = hip.gather_offsets([v.nbytes for v in views], 16)
         if total >= 2 ** 31:
             raise ValueError("DecodePipelines: a pass of %d sample bytes (the offsets are int32)" % total)
@@ -658,6 +686,17 @@ class DecodePipelines:
         hip.host_gather(bufs["host"].data_ptr(), views, max(1, self.copy_threads), align=16)
         meta = bufs["meta_h"].numpy()
         utts = bufs["utts"]
+        plan = None
+        if resample:  # the resampler's own small DMA (per utterance: offsets, samples, channels, where its wave goes; the rates' row lists)
+            if bufs.get("rs_h") is None:
+                bufs["rs_h"] = torch.empty(RESAMPLE_META * utts, dtype=torch.int32, pin_memory=True)
+                bufs["rs_d"] = torch.empty(RESAMPLE_META * utts, dtype=torch.int32, device=dev_)
+            channel = next(b.channel for b in batches if b.formats is not None)
+            plan = plan_resample(bufs["rs_h"].numpy(), utts, self.fbank, offs, [v.shape[0] for v in views], [r for r, _ in formats],
+                                 [c for _, c in formats], channel, [u for b in batches for u in (b.utts or [None] * len(b.views))])
+            if bufs.get("wave") is None or bufs["wave"].numel() < plan["wave_floats"]:
+                bufs["wave"] = torch.empty(max(plan["wave_floats"], bufs["cap"] // 2), dtype=torch.float32, device=dev_)
+            bufs["rs_d"].copy_(bufs["rs_h"], non_blocking=True)
         meta[:rows] = offs
         meta[utts:utts + rows] = [v.shape[0] for v in views]
         meta[2 * utts:2 * utts + rows] = torch.cat([x[1] for x in items], 0).numpy().view(np.int32)
@@ -669,13 +708,19 @@ class DecodePipelines:
             stats = self._cmvn_dev.get(self._device)
             if stats is None:
                 stats = self._cmvn_dev[self._device] = (torch.from_numpy(self.cmvn[0]).to(dev_), torch.from_numpy(self.cmvn[1]).to(dev_))
+        def fbank(out):
+            if plan is None:
+                return hip.fbank_packed(self.fbank, bufs["dev"], total, bufs["meta_d"][:utts], bufs["meta_d"][utts:2 * utts], out, pad, stats[0], stats[1])
+            run_resampled(self.fbank, plan, bufs["dev"], total, bufs["rs_h"].numpy(), bufs["rs_d"], utts, bufs["wave"], out, pad, stats[0], stats[1])
+            self._bump("resampled_passes", 1)
+
         if splice is not None:  # two launches: fbank + CMVN into the slot's scratch, then splice and skip out of it
             mid, sp = self._splice_scratch(bufs, batches, rows, F0, splice, dev_)
-            hip.fbank_packed(self.fbank, bufs["dev"], total, bufs["meta_d"][:utts], bufs["meta_d"][utts:2 * utts], mid, pad, stats[0], stats[1])
+            fbank(mid)
             hip.splice_rows(mid, sp[0], sp[1], feats, splice[0], splice[1], splice[2], pad)
             self._bump("spliced_passes", 1)
         else:
-            hip.fbank_packed(self.fbank, bufs["dev"], total, bufs["meta_d"][:utts], bufs["meta_d"][utts:2 * utts], feats, pad, stats[0], stats[1])
+            fbank(feats)
         self._bump("wave_passes", 1)
         return feats, bufs["meta_d"][2 * utts:2 * utts + rows].view(torch.float32)
 

@@ -73,6 +73,9 @@ class BaseTask(object):
             ds = self.test_loader.dataset
             o = ds.fbank_opts
             fb = Fbank(cmvn_mean=ds.mean if ds.use_cmvn else None, cmvn_std=ds.std if ds.use_cmvn else None,
-                       pad_value=float(getattr(self, "_pad_value", 0.0)), splice=ds.splice(), **{name: getattr(o, name) for name, _ in o._fields_ if name != "reserved"})
+                       pad_value=float(getattr(self, "_pad_value", 0.0)), splice=ds.splice(), **ds.wave_admit,
+                       **{name: getattr(o, name) for name, _ in o._fields_ if name != "reserved"})
             self._fbank = fb
-        return fb.packed(feats.views, utts=feats.utts)
+        if feats.formats is None:
+            return fb.packed(feats.views, utts=feats.utts)
+        return fb.packed(feats.views, utts=feats.utts, rates=[r for r, _ in feats.formats], channels=[c for _, c in feats.formats])

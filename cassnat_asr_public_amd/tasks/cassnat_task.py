@@ -297,7 +297,8 @@ class CassNATTask(BaseTask):
                 for j, idx in enumerate(self.test_loader.batch_sampler):
                     got = [ds[i] for i in idx]
                     pb = PackedBatch.from_waves([v for _, v, _ in got], [ds.wave_frames[i] for i in idx], feat_dim, utts=[u for u, _, _ in got],
-                                                splice=splice)
+                                                splice=splice, formats=None if ds.wave_plain else [ds.wave_formats[i] for i in idx],
+                                                channel=ds.wave_admit["channel"])
                     meta[j] = ([u for u, _, _ in got], [None] * len(got), pb.shape[0] * pb.shape[1], max(len(t) for _, _, t in got))
                     yield pb, pb.ratios(), j
                 return

@@ -394,6 +394,48 @@ int cn_fbank(const cn_fbank_opts* o, const float* wave_dev, const int32_t* num_s
 int cn_op_fbank_packed(const cn_fbank_opts* o, const void* staged_dev, int64_t staged_bytes, const int32_t* off_dev,
                        const int32_t* samples_dev, float* out_dev, int32_t rows, int32_t T, float pad, const double* mean_dev,
                        const double* std_dev, void* stream);
+/* cn_op_fbank_packed for float32 samples on the int16 scale (the wave cn_op_wave_resample writes): utterance r (samples_dev[r]
+ * samples) at BYTE offset off_dev[r] of wave_dev, a multiple of 16.  The two forms are one kernel, a template on the sample type:
+ * for the same float values this one, cn_op_fbank_packed and cn_fbank agree bit for bit.  Nothing outside [0, wave_bytes) is read;
+ * the same refusals. */
+int cn_op_fbank_packed_f32(const cn_fbank_opts* o, const void* wave_dev, int64_t wave_bytes, const int32_t* off_dev,
+                           const int32_t* samples_dev, float* out_dev, int32_t rows, int32_t T, float pad, const double* mean_dev,
+                           const double* std_dev, void* stream);
+
+/* ---- front-end: sample-rate conversion and channel pick in front of fbank ---------------------------------------
+ * What Kaldi's compute-fbank-feats does with a file whose rate differs from --sample-frequency (--allow-downsample /
+ * --allow-upsample: ResampleWaveform) or that holds several channels (--channel).  The arithmetic is LinearResample with
+ * num_zeros = 6 and cutoff = 0.99 * 0.5 * min(in_rate, out_rate): with g = gcd(in_rate, out_rate), in_unit = in_rate / g and
+ * out_unit = out_rate / g (the number of phases), phase i has the weights w[i][j] = filt(d) * win(d) / in_rate for the input
+ * indices j = first[i] .. last, first[i] = ceil((i / out_rate - W) * in_rate), last = floor((i / out_rate + W) * in_rate),
+ * d = j / in_rate - i / out_rate, W = num_zeros / (2 cutoff), and output k = u * out_unit + i of a wave x is
+ * sum_j w[i][j] x[first[i] + u * in_unit + j] with x = 0 outside the wave.  The tables are built on the host in double and rounded
+ * to float32 once; the kernel accumulates in float32 in ascending j (fmaf), so that per output
+ * |y - exact| <= (taps + 3) * 2^-24 * sum_j |w_j x_j|.  Equal rates: one weight 1.0, the output is exactly float(x).
+ * Host only: cn_resample_num_samples is the number of outputs for in_samples inputs (GetNumOutputSamples with flush = true:
+ * ceil(in_samples * out_unit / in_unit); 0 for a non-positive argument).  cn_resample_table gives the table exactly as the device
+ * gets it: first_host / taps_host [out_unit], weights_host [max_taps][out_unit] (tap-major; zero behind a phase's taps), `capacity`
+ * = the floats weights_host can hold; with the three arrays null only in_unit / out_unit / max_taps are set.  It refuses what
+ * cn_op_wave_resample refuses of a rate pair. */
+int64_t cn_resample_num_samples(int32_t in_rate, int32_t out_rate, int64_t in_samples);
+int cn_resample_table(int32_t in_rate, int32_t out_rate, int32_t* in_unit, int32_t* out_unit, int32_t* max_taps,
+                      int32_t* first_host, int32_t* taps_host, float* weights_host, int64_t capacity);
+/* The utterances of ONE source rate, in one launch.  staged_dev: the layout cn_op_fbank_packed reads - utterance r's data chunk as
+ * its file holds it (interleaved little-endian int16, channels[r] channels of samples[r] samples each) at BYTE offset off_dev[r], a
+ * multiple of 16.  Channel channel[r] of it is converted from in_rate to out_rate and written as float32 to wave_dev +
+ * out_off_dev[r] (an offset in FLOATS, a multiple of 4): cn_resample_num_samples(samples[r]) values, nothing else - gaps and other
+ * utterances' slots are not touched.  The per-utterance arrays have `utts` entries; rows_dev (device, `rows` utterance indices) names
+ * the utterances of this call - a pass that mixes rates makes one call per rate - or is NULL: utterances 0 .. rows - 1.  max_out:
+ * the longest output count among them (it sizes the grid).  channels_host / channel_host: the same values as channels_dev /
+ * channel_dev, on the host, checked before the launch.  Nothing outside [0, staged_bytes) is read: an utterance whose offset and
+ * length reach outside is cut to the samples that lie inside.  Refused without a launch: a null pointer, a non-positive rate, utts,
+ * rows or max_out, a channel outside [0, channels), more than 65535 rows, a rate pair whose table has more than 65536 weights or
+ * of which 256 consecutive outputs need more input samples than the kernel's LDS tile holds (4096).  The tables are kept per
+ * (device, in_rate, out_rate). */
+int cn_op_wave_resample(int32_t in_rate, int32_t out_rate, const void* staged_dev, int64_t staged_bytes, const int32_t* off_dev,
+                        const int32_t* samples_dev, const int32_t* channels_dev, const int32_t* channel_dev,
+                        const int32_t* channels_host, const int32_t* channel_host, int32_t utts, const int32_t* rows_dev,
+                        int32_t rows, int64_t max_out, float* wave_dev, const int32_t* out_off_dev, void* stream);
 
 /* ---- single-kernel entry points (parity tests drive each hand-written kernel through the ABI) ---------- */
 /* all pointers device; `precision` selects the element type of activations/weights: CN_PRECISION_F32, CN_PRECISION_BF16 or
