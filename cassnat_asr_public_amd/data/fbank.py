@@ -210,29 +210,40 @@ class Fbank:
         one copy - and ``hip.fbank_packed`` computes the padded batch on the device; no padded float matrix exists on the host.
         ``rates`` / ``channels``: per utterance the file's sample rate and channel count (``wave_io.pcm_frames``; the views then hold
         the interleaved data chunks).  None, or every rate equal to ``sample_rate`` and every file mono: exactly the path above.
-        Otherwise channel ``self.channel`` of every file is brought to ``sample_rate`` on the device first (``_packed_resampled``)."""
-        if not plain_formats(self.o.sample_rate, rates, channels):
-            return self._packed_resampled(views, utts, rates, channels)
-        frames = [self.num_frames(len(v)) for v in views]
-        for b, n in enumerate(frames):
-            if n < 1:
-                raise ValueError("utterance %s: %d samples are shorter than one analysis window" % (utts[b] if utts is not None else "#%d" % b, len(views[b])))
-        B, T = len(views), max(frames)
+        Otherwise the interleaved int16 is staged as it is (same gather, same single copy), one ``hip.wave_resample`` per distinct
+        rate writes channel ``self.channel`` at ``sample_rate`` into a float32 wave buffer and ``hip.fbank_packed_f32`` reads that.
+        The splice follows either way."""
+        resample = not plain_formats(self.o.sample_rate, rates, channels)
+        B = len(views)
         views = [np.ascontiguousarray(v, dtype="<i2") for v in views]
         offs, total = hip.gather_offsets([v.nbytes for v in views], 16)
         if total >= 2 ** 31:
             raise ValueError("Fbank.packed: a batch of %d bytes (the offsets are int32)" % total)
+        counts, at = [v.shape[0] for v in views], ""  # (the samples the front-end sees, per utterance)
+        meta = torch.empty((RESAMPLE_META if resample else 2) * B, dtype=torch.int32, pin_memory=True)
+        if resample:
+            rates = [int(round(float(self.o.sample_rate)))] * B if rates is None else [int(r) for r in rates]
+            channels = [1] * B if channels is None else [int(c) for c in channels]
+            plan = plan_resample(meta.numpy(), B, self.o, offs, counts, rates, channels, self.channel, utts)
+            counts, at = plan["counts"], " at %d Hz" % plan["out_rate"]
+        else:
+            meta.numpy()[:B], meta.numpy()[B:] = offs, counts
+        frames = [self.num_frames(n) for n in counts]
+        for b, n in enumerate(frames):
+            if n < 1:
+                raise ValueError("utterance %s: %d samples%s are shorter than one analysis window" % (utts[b] if utts is not None else "#%d" % b, counts[b], at))
         host = torch.empty(total, dtype=torch.uint8, pin_memory=True)
         hip.host_gather(host.data_ptr(), views, 1, align=16)
-        meta = torch.empty(2 * B, dtype=torch.int32, pin_memory=True)
-        mv = meta.numpy()
-        mv[:B] = offs
-        mv[B:] = [len(v) for v in views]
-        feats = torch.empty(B, T, self.o.num_mel, dtype=torch.float32, device=self.device)
+        feats = torch.empty(B, max(frames), self.o.num_mel, dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
             staged = host.to(self.device, non_blocking=True)
             meta_d = meta.to(self.device, non_blocking=True)
-            hip.fbank_packed(self.o, staged, total, meta_d[:B], meta_d[B:], feats, self.pad_value, self.mean64, self.std64)
+            if resample:
+                wave = torch.empty(plan["wave_floats"], dtype=torch.float32, device=self.device)
+                run_resampled(self.o, plan, staged, total, meta.numpy(), meta_d, B, wave, feats, self.pad_value, self.mean64, self.std64)
+                self.resampled_passes += 1
+            else:
+                hip.fbank_packed(self.o, staged, total, meta_d[:B], meta_d[B:], feats, self.pad_value, self.mean64, self.std64)
             return self._spliced(feats, frames)
 
     def _spliced(self, feats, frames):
@@ -253,35 +264,6 @@ class Fbank:
         out = torch.empty(B, max(n_out), (left + right + 1) * self.o.num_mel, dtype=torch.float32, device=self.device)
         hip.splice_rows(feats, sp_d[:B], sp_d[B:], out, left, right, skip, self.pad_value)
         return out, torch.tensor([n / max(n_out) for n in n_out], dtype=torch.float32)
-
-    def _packed_resampled(self, views, utts, rates, channels):
-        """``packed`` for files at other rates / of several channels: the interleaved int16 is staged as it is (same gather, same
-        single copy), one ``hip.wave_resample`` per distinct rate writes the chosen channel at ``sample_rate`` into a float32 wave
-        buffer, ``hip.fbank_packed_f32`` reads that, and the splice follows as ever."""
-        B = len(views)
-        rates = [int(round(float(self.o.sample_rate)))] * B if rates is None else [int(r) for r in rates]
-        channels = [1] * B if channels is None else [int(c) for c in channels]
-        views = [np.ascontiguousarray(v, dtype="<i2") for v in views]
-        offs, total = hip.gather_offsets([v.nbytes for v in views], 16)
-        if total >= 2 ** 31:
-            raise ValueError("Fbank.packed: a batch of %d bytes (the offsets are int32)" % total)
-        meta = torch.empty(RESAMPLE_META * B, dtype=torch.int32, pin_memory=True)
-        plan = plan_resample(meta.numpy(), B, self.o, offs, [v.shape[0] for v in views], rates, channels, self.channel, utts)
-        frames = [self.num_frames(n) for n in plan["counts"]]
-        for b, n in enumerate(frames):
-            if n < 1:
-                raise ValueError("utterance %s: %d samples at %d Hz are shorter than one analysis window"
-                                 % (utts[b] if utts is not None else "#%d" % b, plan["counts"][b], plan["out_rate"]))
-        host = torch.empty(total, dtype=torch.uint8, pin_memory=True)
-        hip.host_gather(host.data_ptr(), views, 1, align=16)
-        feats = torch.empty(B, max(frames), self.o.num_mel, dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            staged = host.to(self.device, non_blocking=True)
-            meta_d = meta.to(self.device, non_blocking=True)
-            wave = torch.empty(plan["wave_floats"], dtype=torch.float32, device=self.device)
-            run_resampled(self.o, plan, staged, total, meta.numpy(), meta_d, B, wave, feats, self.pad_value, self.mean64, self.std64)
-            self.resampled_passes += 1
-            return self._spliced(feats, frames)
 
     def __call__(self, waves):
         """waves: list of 1-D arrays / tensors on the int16 scale (what Kaldi reads from a wav file)."""

@@ -31,6 +31,7 @@ import torch
 
 from . import dist as cdist
 from . import hip as _hip
+from .staging import PackedBatch, PackedStaging, _form  # noqa: F401 (PackedBatch is imported from here by the tools and the tests)
 
 
 def subsampled(T):
@@ -49,186 +50,6 @@ class _NoStream:
 
     def synchronize(self):
         pass
-
-
-class PackedBatch:
-    """A batch the reader has NOT collated: the utterances' archive rows as they lie in the .ark - read-only float32 views (n_b, F)
-    into the memory map of the archive (``data.kaldi_io.load_mat_view``) - in the batch's order.  It stands where the padded
-    (B, T, F) tensor of ``SuperviseLoader.collate_fn`` (src/data/speech_loader.py:327-356) would: ``shape`` is that tensor's shape,
-    ``ratios()`` its float32 length ratios.  The decode pipelines copy the rows of a whole engine pass back to back into page-locked
-    memory (one straight memcpy per utterance, no padding), send them with one DMA and spread them over the padded batch on the
-    device (``hip.unpack_rows``: padding and, when asked for, the global CMVN in float64 happen there).
-
-    The COMPRESSED form (``from_payloads`` on Kaldi `CM` / `CM2` / `CM3` entries; ``kinds`` is then a list, otherwise None) keeps
-    per utterance the payload as the archive holds it - a read-only uint8 view from min_value on (``data.kaldi_io.mat_payload``) -
-    its kind (1 / 2 / 3) and its rows; shape, lengths and ratios come from the headers.  The pipelines stage the payloads as they
-    are, a quarter of the float32 bytes, and ``hip.unpack_compressed`` decompresses on the device; ``padded()`` - host
-    decompression with ``kaldi_io.decompress`` - is the definition of what it must produce.
-
-    The WAVE form (``from_waves``; ``kinds`` is the string "wave") keeps per utterance a read-only '<i2' view of the samples inside the
-    memory map of its sound file (``data.wave_io.pcm_view``); ``lens`` are the frame counts of the fbank front-end and ``shape`` the
-    padded FEATURE shape.  The pipelines stage the samples as they are and ``hip.fbank_packed`` computes the features on the
-    device; there is no host fbank in the product, so ``padded()`` and ``matrices()`` raise.  With ``formats`` - per utterance the
-    file's (rate, channels) - the views hold the INTERLEAVED data chunks of files at other rates or of several channels, ``channel``
-    is the one that is read, and ``lens`` count the frames of the wave at the front-end's rate: ``hip.wave_resample`` writes that
-    wave on the device, ``hip.fbank_packed_f32`` reads it.
-
-    SPLICING (``splice`` = (left, right, skip), every form): the set splices and / or skips frames (the recipes' decode YAMLs:
-    0 / 2 / 1).  ``lens`` stay the SOURCE rows and ``source_shape`` the unspliced (B, longest source count, F0); ``shape`` is what the
-    dataset's general host path collates - (B, longest n_out, (left + right + 1) * F0) with n_out = ``out_lens`` = ceil(rows / skip) -
-    and ``ratios()`` are n_out / longest n_out.  ``padded()`` applies the dataset's steps on the host (``speech_loader.splice_host``:
-    CMVN in float64, zero rows up to a multiple of skip, ``feat_op.context_feat``, ``feat_op.skip_feat``, then padding): the
-    definition ``hip.splice_rows`` is held to."""
-
-    __slots__ = ("views", "lens", "shape", "dtype", "is_cuda", "kinds", "utts", "splice", "source_shape", "out_lens", "formats", "channel")
-
-    def __init__(self, views, utts=None, splice=None):
-        self.views = views
-        self.kinds = None
-        self.formats, self.channel = None, -1
-        self.utts = utts
-        self.lens = [int(v.shape[0]) for v in views]
-        self.shape = (len(views), max(self.lens), int(views[0].shape[1]))
-        self.dtype = torch.float32
-        self.is_cuda = False
-        self._set_splice(splice)
-
-    def _set_splice(self, splice):
-        """``shape`` holds the unspliced shape when this is called: keep it as ``source_shape`` and derive the spliced one."""
-        from .data.speech_loader import splice_triple, spliced_frames
-
-        self.splice = splice_triple(*splice) if splice else None
-        self.source_shape = self.shape
-        self.out_lens = [spliced_frames(n, self.splice) for n in self.lens]
-        if self.splice is not None:
-            self.shape = (self.shape[0], max(self.out_lens), (self.splice[0] + self.splice[1] + 1) * self.shape[2])
-
-    @classmethod
-    def from_payloads(cls, entries, utts=None, compressed=None, cols=None, splice=None):
-        """``entries``: one ``kaldi_io.mat_payload`` tuple (kind, rows, cols, payload) per utterance - all `FM` (the float32 form,
-        as ``PackedBatch(views)``) or all of the compressed kinds, which may mix.  Every header is checked: an entry of the other
-        family (``compressed`` = True / False: the family the caller expects; None: the first entry's), of another column count
-        (``cols``; None: the first entry's) or whose payload is not the size its header gives raises a ValueError that names the
-        utterance - nothing is strided on a guess."""
-        from .data.kaldi_io import COMPRESSED_KINDS
-
-        def name(b):
-            return "utterance %s" % (utts[b] if utts is not None else "#%d of the batch" % b)
-
-        if not entries:
-            raise ValueError("PackedBatch: an empty batch")
-        want_c = (entries[0][0] in COMPRESSED_KINDS) if compressed is None else bool(compressed)
-        want_cols = int(entries[0][2]) if cols is None else int(cols)
-        views, kinds, lens = [], [], []
-        for b, (kind, rows, ncols, payload) in enumerate(entries):
-            is_c = kind in COMPRESSED_KINDS
-            if kind != "FM" and not is_c:
-                raise ValueError("PackedBatch: %s holds a %r matrix, which the packed reader does not take" % (name(b), kind))
-            if is_c != want_c:
-                raise ValueError("PackedBatch: %s holds a %r matrix in a batch of %s ones" % (name(b), kind, "compressed" if want_c else "float32"))
-            if int(ncols) != want_cols:
-                raise ValueError("PackedBatch: %s has %d columns, the batch %d" % (name(b), ncols, want_cols))
-            rows, ncols = int(rows), int(ncols)
-            if not is_c:
-                if rows < 0 or payload.nbytes != 4 * rows * ncols:
-                    raise ValueError("PackedBatch: %s: payload of %d bytes for %d x %d float32" % (name(b), payload.nbytes, rows, ncols))
-                views.append(payload.view("<f4").reshape(rows, ncols))
-                continue
-            need = 16 + {"CM": 8 * ncols + rows * ncols, "CM2": 2 * rows * ncols, "CM3": rows * ncols}[kind]
-            if rows < 0 or payload.dtype != np.uint8 or payload.ndim != 1 or payload.nbytes != need:
-                raise ValueError("PackedBatch: %s: payload of %d bytes for a %d x %d %s matrix (%d)" % (name(b), payload.nbytes, rows, ncols, kind, need))
-            if tuple(np.frombuffer(payload[8:16].tobytes(), "<i4")) != (rows, ncols):  # (the device strides by the payload's own header)
-                raise ValueError("PackedBatch: %s: the payload's header does not say %d x %d" % (name(b), rows, ncols))
-            views.append(payload)
-            kinds.append(COMPRESSED_KINDS[kind])
-            lens.append(rows)
-        if not want_c:
-            return cls(views, utts, splice=splice)
-        self = cls.__new__(cls)
-        self.views, self.kinds, self.lens, self.utts = views, kinds, lens, utts
-        self.formats, self.channel = None, -1
-        self.shape = (len(views), max(lens), want_cols)
-        self.dtype = torch.float32
-        self.is_cuda = False
-        self._set_splice(splice)
-        return self
-
-    @classmethod
-    def from_waves(cls, views, frames, num_mel, utts=None, splice=None, formats=None, channel=-1):
-        """``views``: one '<i2', one-dimensional, C-contiguous array of samples per utterance; ``frames``: their frame counts under
-        the front-end's options (``Fbank.num_frames``).  Anything else - and an utterance of zero frames - raises a ValueError that
-        names the utterance.  ``formats``: per utterance (rate, channels) of its file - the view is then the interleaved data chunk
-        (``wave_io.pcm_frames``), ``frames`` count the wave at the front-end's rate and ``channel`` (the front-end's `--channel`)
-        must name a channel of every file that has more than one; None: mono files at the front-end's rate."""
-        def name(b):
-            return "utterance %s" % (utts[b] if utts is not None else "#%d of the batch" % b)
-
-        if not views:
-            raise ValueError("PackedBatch: an empty batch")
-        if len(frames) != len(views):
-            raise ValueError("PackedBatch: %d frame counts for %d utterances" % (len(frames), len(views)))
-        if formats is not None and len(formats) != len(views):
-            raise ValueError("PackedBatch: %d (rate, channels) pairs for %d utterances" % (len(formats), len(views)))
-        for b, v in enumerate(views):
-            if not isinstance(v, np.ndarray) or v.dtype != np.dtype("<i2") or v.ndim != 1 or not v.flags.c_contiguous:
-                raise ValueError("PackedBatch: %s: the samples must be a one-dimensional C-contiguous '<i2' array (got %s)"
-                                 % (name(b), "%s %s" % (getattr(v, "dtype", type(v).__name__), getattr(v, "shape", ""))))
-            if int(frames[b]) < 1:
-                raise ValueError("PackedBatch: %s: %d samples give no frame" % (name(b), v.shape[0]))
-            if formats is not None:
-                rate, chans = int(formats[b][0]), int(formats[b][1])
-                if rate < 1 or chans < 1 or v.shape[0] % chans:
-                    raise ValueError("PackedBatch: %s: %d int16 values at (rate, channels) = (%d, %d)" % (name(b), v.shape[0], rate, chans))
-                if chans > 1 and not 0 <= int(channel) < chans:
-                    raise ValueError("PackedBatch: %s: %d channels, channel %d is not one of them" % (name(b), chans, int(channel)))
-        self = cls.__new__(cls)
-        self.views, self.kinds, self.utts = list(views), "wave", utts
-        self.formats = None if formats is None else [(int(r), int(c)) for r, c in formats]
-        self.channel = int(channel)
-        self.lens = [int(n) for n in frames]
-        self.shape = (len(views), max(self.lens), int(num_mel))
-        self.dtype = torch.float32
-        self.is_cuda = False
-        self._set_splice(splice)
-        return self
-
-    def ratios(self):
-        """collate's ``ratios[b] = feat.shape[0] / t_max``: the Python (double) quotient rounded to float32 (of the rows the dataset
-        hands out: the spliced counts when the batch splices)"""
-        t_max = self.shape[1]
-        return torch.tensor([n / t_max for n in self.out_lens], dtype=torch.float32)
-
-    def matrices(self):
-        """The utterances' float32 matrices on the host (the compressed form decompressed by ``kaldi_io.decompress``)."""
-        if self.kinds is None:
-            return self.views
-        if self.kinds == "wave":
-            raise NotImplementedError("PackedBatch: the wave form holds samples - the features exist on the device only (hip.fbank_packed)")
-        from .data.kaldi_io import decompress
-
-        names = {1: "CM", 2: "CM2", 3: "CM3"}
-        return [decompress(names[k], n, self.source_shape[2], v) for k, n, v in zip(self.kinds, self.lens, self.views)]
-
-    def padded(self, pad=0.0, cmvn=None):
-        """The collated tensor itself (host): what the packed path must reproduce; used by the CPU rehearsal and the tests."""
-        if self.kinds == "wave":
-            raise NotImplementedError("PackedBatch: the wave form holds samples - the features exist on the device only (hip.fbank_packed)")
-        out = np.full(self.shape, float(pad), np.float32)
-        if self.splice is not None:
-            from .data.speech_loader import splice_host
-
-            for b, v in enumerate(self.matrices()):  # (the assignment rounds to float32 once, as collate does)
-                out[b, : self.out_lens[b]] = splice_host(v, self.splice, cmvn)
-            return torch.from_numpy(out)
-        for b, v in enumerate(self.matrices()):
-            out[b, : v.shape[0]] = v if cmvn is None else ((v.astype(np.float64) - cmvn[0]) / cmvn[1]).astype(np.float32)
-        return torch.from_numpy(out)
-
-
-def _form(f):
-    """The staging form of a batch: None (a tensor, or float32 archive rows), "compressed" or "wave"."""
-    kinds = getattr(f, "kinds", None)
-    return None if kinds is None else ("wave" if isinstance(kinds, str) else "compressed")
 
 
 class _Job:
@@ -267,7 +88,7 @@ class _Pass:
     __slots__ = ("items", "first", "feats", "ratio", "rows", "frames", "ticket", "u_hint", "rec", "recs", "ev", "tp")
 
 
-class DecodePipelines:
+class DecodePipelines(PackedStaging):
     def __init__(self, model, n_pipelines, batch, frames, with_weights=True, after_engine=None, coalesce=1, share_from=None,
                  ragged=0.75, predict_rows=True, area_frames=None, cmvn=None, copy_threads=0, fbank=None):
         """``model``: a CassNAT holding the parameters; ``batch`` x ``frames``: the largest single batch a pipeline must take.
@@ -298,7 +119,7 @@ class DecodePipelines:
         self._fp16 = getattr(model, "hip_precision", "") == "fp16"  # (its scores are checked for the half range: hip.check_fp16_range)
         self._guarded = getattr(model, "hip_precision", "") in ("fp16", "bf16x3")  # (engines with a feature-range guard: Engine.check_range)
         self.copy_threads = max(0, int(copy_threads))
-        self._packed = [{} for _ in range(max(1, int(n_pipelines)))]  # per pipeline: packed-pass staging buffers by slot
+        self._packed = [{} for _ in range(max(1, int(n_pipelines)))]  # per pipeline: packed-pass staging buffers by (form, slot)
         self.cmvn = None if cmvn is None else (np.ascontiguousarray(cmvn[0], dtype=np.float64), np.ascontiguousarray(cmvn[1], dtype=np.float64))
         self._cmvn_dev = {}
         self.n = max(1, int(n_pipelines))
@@ -478,252 +299,6 @@ class DecodePipelines:
         state["next"] += len(items)
         return i, items
 
-    def _stage_packed(self, k, slot, items, pad):
-        """A pass of ``PackedBatch``es: every utterance's archive rows go back to back into this slot's page-locked buffer (a
-        straight copy out of the memory map; with ``copy_threads`` the utterances are dealt over helper threads), ONE DMA takes them
-        to the device, and ``hip.unpack_rows`` spreads them over the padded merged batch - frames past an utterance's length get
-        the padding value, and the global CMVN (float64, the dataset's arithmetic) is applied on the way when the pipelines have
-        the statistics.  No padded batch ever exists on the host."""
-        on_gpu, device = self._on_gpu, self._device
-        batches = [x[0] for x in items]
-        rows = sum(b.shape[0] for b in batches)
-        tmax = max(b.shape[1] for b in batches)
-        F = batches[0].shape[2]
-        forms = set(_form(b) for b in batches)
-        if len(set(b.splice for b in batches)) > 1:
-            raise ValueError("DecodePipelines: a pass mixes packed batches of different splice triples")
-        if "wave" in forms:
-            if len(forms) > 1:
-                raise ValueError("DecodePipelines: a pass mixes wave batches with another form of packed batch")
-            if not on_gpu:
-                raise NotImplementedError("DecodePipelines: the wave form has no CPU rehearsal (the fbank front-end runs on the device only)")
-            return self._stage_wave(k, slot, items, pad, rows, tmax, F, torch.device("cuda", device))
-        if not on_gpu:  # CPU rehearsal of the host logic: the collated tensors themselves
-            feats = torch.full((rows, tmax, F), float(pad))
-            o = 0
-            for b in batches:
-                feats[o:o + b.shape[0], : b.shape[1]] = b.padded(pad, self.cmvn)
-                o += b.shape[0]
-            return feats, torch.cat([x[1] for x in items], 0)
-        dev_ = torch.device("cuda", device)
-        if batches[0].kinds is not None:
-            return self._stage_compressed(k, slot, items, pad, rows, tmax, F, dev_)
-        views = [v for b in batches for v in b.views]
-        lens = [n for b in batches for n in b.lens]
-        total = sum(lens)
-        # a spliced pass: the staging buffers hold SOURCE rows of F0 values (skip times the output frames), `out` the spliced batch
-        splice = batches[0].splice
-        F0 = batches[0].source_shape[2]
-        bufs = self._packed[k].get(slot)
-        cap = max(total, self.max_batch * self.frames_cap * (splice[2] if splice else 1))
-        if bufs is None or bufs["cap"] < total or bufs["F"] != F or bufs["F0"] != F0 or bufs["utts"] < rows:
-            utts = max(rows, self.max_utts)
-            bufs = {"cap": cap, "F": F, "F0": F0, "utts": utts,
-                    "host": torch.empty(cap * F0, dtype=torch.float32, pin_memory=True),
-                    "dev": torch.empty(cap * F0, dtype=torch.float32, device=dev_),
-                    # per utterance: row offset, frames, float32 ratio (as int32 bits) - one small DMA
-                    "meta_h": torch.empty(3 * utts, dtype=torch.int32, pin_memory=True),
-                    "meta_d": torch.empty(3 * utts, dtype=torch.int32, device=dev_),
-                    "out": torch.empty(max(rows * tmax, self.max_batch * self.frames_cap) * F, dtype=torch.float32, device=dev_)}
-            self._packed[k][slot] = bufs
-        if bufs["out"].numel() < rows * tmax * F:
-            bufs["out"] = torch.empty(rows * tmax * F, dtype=torch.float32, device=dev_)
-        offs = np.zeros(rows, np.int64)
-        np.cumsum(lens[:-1], out=offs[1:])
-        from . import hip
-
-        # one GIL-free call copies the pass's rows out of the page cache (numpy's slice assignment holds the GIL: the two pipelines'
-        # threads took turns); copy_threads > 1 deals the utterances over that many host threads inside the call
-        hip.host_gather(bufs["host"].data_ptr(), views, max(1, self.copy_threads))
-        meta = bufs["meta_h"].numpy()
-        utts = bufs["utts"]
-        meta[:rows] = offs
-        meta[utts:utts + rows] = lens
-        meta[2 * utts:2 * utts + rows] = torch.cat([x[1] for x in items], 0).numpy().view(np.int32)
-        bufs["dev"][: total * F0].copy_(bufs["host"][: total * F0], non_blocking=True)
-        bufs["meta_d"].copy_(bufs["meta_h"], non_blocking=True)
-        feats = bufs["out"][: rows * tmax * F].view(rows, tmax, F)
-        stats = (None, None)
-        if self.cmvn is not None:
-            stats = self._cmvn_dev.get(device)
-            if stats is None:
-                stats = self._cmvn_dev[device] = (torch.from_numpy(self.cmvn[0]).to(dev_), torch.from_numpy(self.cmvn[1]).to(dev_))
-        if splice is not None:  # ONE launch from the staging buffer: padding, CMVN, zero rows, splice and skip
-            hip.splice_rows(bufs["dev"], bufs["meta_d"][:utts], bufs["meta_d"][utts:2 * utts], feats, splice[0], splice[1], splice[2], pad,
-                            stats[0], stats[1])
-            self._bump("spliced_passes", 1)
-        else:
-            hip.unpack_rows(bufs["dev"], bufs["meta_d"][:utts], bufs["meta_d"][utts:2 * utts], feats, pad, stats[0], stats[1])
-        return feats, bufs["meta_d"][2 * utts:2 * utts + rows].view(torch.float32)
-
-    def _stage_compressed(self, k, slot, items, pad, rows, tmax, F, dev_):
-        """A pass of compressed ``PackedBatch``es (Kaldi `CM` / `CM2` / `CM3`, mixed as they come): the payloads go into the slot's
-        page-locked buffer as the archive holds them, each at a 16-byte-aligned offset (one ``cn_host_gather`` call), ONE DMA of
-        those bytes - about a quarter of the float32 rows - takes them to the device, the per-utterance (byte offset, frames,
-        ratio, kind) follow in the small DMA, and ``hip.unpack_compressed`` decompresses, normalises and pads.  The buffers are
-        sized in bytes (area x F values of one byte plus the headers; grown for a pass that needs more, e.g. all `CM2`)."""
-        from . import hip
-
-        batches = [x[0] for x in items]
-        if any(b.kinds is None or b.shape[2] != F for b in batches):
-            raise ValueError("DecodePipelines: a pass mixes compressed and float32 packed batches, or feature dimensions")
-        splice = batches[0].splice
-        F0 = batches[0].source_shape[2]
-        views = [v for b in batches for v in b.views]
-        lens = [n for b in batches for n in b.lens]
-        kinds = [c for b in batches for c in b.kinds]
-        offs, total = hip.gather_offsets([v.nbytes for v in views], 16)
-        if total >= 2 ** 31:
-            raise ValueError("DecodePipelines: a pass of %d compressed bytes (the offsets are int32)" % total)
-        key = ("compressed", slot)
-        bufs = self._packed[k].get(key)
-        if bufs is None or bufs["cap"] < total or bufs["F"] != F or bufs["F0"] != F0 or bufs["utts"] < rows:
-            utts = max(rows, self.max_utts)
-            cap = max(total, self.max_batch * self.frames_cap * (splice[2] if splice else 1) * F0 + utts * (32 + 8 * F0))
-            bufs = {"cap": cap, "F": F, "F0": F0, "utts": utts,
-                    "host": torch.empty(cap, dtype=torch.uint8, pin_memory=True),
-                    "dev": torch.empty(cap, dtype=torch.uint8, device=dev_),
-                    # per utterance: byte offset, frames, float32 ratio (as int32 bits), kind - one small DMA
-                    "meta_h": torch.empty(4 * utts, dtype=torch.int32, pin_memory=True),
-                    "meta_d": torch.empty(4 * utts, dtype=torch.int32, device=dev_),
-                    "out": torch.empty(max(rows * tmax, self.max_batch * self.frames_cap) * F, dtype=torch.float32, device=dev_)}
-            self._packed[k][key] = bufs
-        if bufs["out"].numel() < rows * tmax * F:
-            bufs["out"] = torch.empty(rows * tmax * F, dtype=torch.float32, device=dev_)
-        hip.host_gather(bufs["host"].data_ptr(), views, max(1, self.copy_threads), align=16)
-        meta = bufs["meta_h"].numpy()
-        utts = bufs["utts"]
-        meta[:rows] = offs
-        meta[utts:utts + rows] = lens
-        meta[2 * utts:2 * utts + rows] = torch.cat([x[1] for x in items], 0).numpy().view(np.int32)
-        meta[3 * utts:3 * utts + rows] = kinds
-        bufs["dev"][:total].copy_(bufs["host"][:total], non_blocking=True)
-        bufs["meta_d"].copy_(bufs["meta_h"], non_blocking=True)
-        feats = bufs["out"][: rows * tmax * F].view(rows, tmax, F)
-        stats = (None, None)
-        if self.cmvn is not None:
-            stats = self._cmvn_dev.get(self._device)
-            if stats is None:
-                stats = self._cmvn_dev[self._device] = (torch.from_numpy(self.cmvn[0]).to(dev_), torch.from_numpy(self.cmvn[1]).to(dev_))
-        if splice is not None:  # two launches: decompress + CMVN into the slot's scratch, then splice and skip out of it
-            mid, sp = self._splice_scratch(bufs, batches, rows, F0, splice, dev_)
-            hip.unpack_compressed(bufs["dev"], bufs["meta_d"][:utts], bufs["meta_d"][utts:2 * utts], bufs["meta_d"][3 * utts:4 * utts], mid, pad,
-                                  stats[0], stats[1])
-            hip.splice_rows(mid, sp[0], sp[1], feats, splice[0], splice[1], splice[2], pad)
-            self._bump("spliced_passes", 1)
-        else:
-            hip.unpack_compressed(bufs["dev"], bufs["meta_d"][:utts], bufs["meta_d"][utts:2 * utts], bufs["meta_d"][3 * utts:4 * utts], feats, pad,
-                                  stats[0], stats[1])
-        self._bump("compressed_passes", 1)
-        return feats, bufs["meta_d"][2 * utts:2 * utts + rows].view(torch.float32)
-
-    def _splice_scratch(self, bufs, batches, rows, F0, splice, dev_):
-        """The two-launch forms (compressed, wave) of a spliced pass: the slot's scratch for the UNSPLICED normalised batch - a
-        (rows, T0, F0) view, T0 the pass's longest source count; allocated with the slot's other staging buffers at the size of the
-        engines' area, grown only for a pass that needs more - and the per-utterance (row offset r * T0, source rows) that
-        ``hip.splice_rows`` reads it by, sent in one small DMA.  Rows at or behind an utterance's count are never read there."""
-        t0 = max(b.source_shape[1] for b in batches)
-        need = rows * t0 * F0
-        if bufs.get("mid") is None or bufs["mid"].numel() < need:
-            bufs["mid"] = torch.empty(max(need, self.max_batch * self.frames_cap * splice[2] * F0), dtype=torch.float32, device=dev_)
-        utts = bufs["utts"]
-        if bufs.get("sp_h") is None:
-            bufs["sp_h"] = torch.empty(2 * utts, dtype=torch.int32, pin_memory=True)
-            bufs["sp_d"] = torch.empty(2 * utts, dtype=torch.int32, device=dev_)
-        sp = bufs["sp_h"].numpy()
-        sp[:rows] = np.arange(rows, dtype=np.int64) * t0
-        sp[utts:utts + rows] = [n for b in batches for n in b.lens]
-        bufs["sp_d"].copy_(bufs["sp_h"], non_blocking=True)
-        return bufs["mid"][:need].view(rows, t0, F0), (bufs["sp_d"][:utts], bufs["sp_d"][utts:2 * utts])
-
-    def _stage_wave(self, k, slot, items, pad, rows, tmax, F, dev_):
-        """A pass of wave-form ``PackedBatch``es: every utterance's int16 samples go into the slot's page-locked buffer as its sound
-        file holds them, each at a 16-byte-aligned offset (one ``cn_host_gather`` call), ONE DMA takes those bytes to the device, the
-        per-utterance (byte offset, samples, ratio) follow in the small DMA, and ``hip.fbank_packed`` computes the padded
-        (rows, tmax, F) features, normalised with the pipelines' statistics when they have them.  The buffers are sized in bytes: a
-        frame shift of samples is 320 bytes at the default options, what 80 float32 features take.
-
-        A pass that holds files at other rates or of several channels (``PackedBatch.formats``) stages the interleaved data chunks
-        in the same buffers - sized in the bytes the files hold -, and on the pass's stream one ``hip.wave_resample`` per distinct
-        rate writes the chosen channel at the front-end's rate into the slot's float32 wave scratch, which ``hip.fbank_packed_f32``
-        reads (``data.fbank.plan_resample`` / ``run_resampled``).  A pass that needs neither is the pass above, launch for launch."""
-        from . import hip
-        from .data.fbank import RESAMPLE_META, plain_formats, plan_resample, run_resampled
-
-        if self.fbank is None:
-            raise ValueError("DecodePipelines: a wave batch, but the pipelines were built without fbank options")
-        batches = [x[0] for x in items]
-        splice = batches[0].splice
-        F0 = batches[0].source_shape[2]
-        if F0 != int(self.fbank.num_mel) or any(b.shape[2] != F or b.source_shape[2] != F0 for b in batches):
-            raise ValueError("DecodePipelines: wave batches of %d features, the front-end computes %d" % (F0, int(self.fbank.num_mel)))
-        views = [v for b in batches for v in b.views]
-        own = int(round(float(self.fbank.sample_rate)))
-        formats = [f for b in batches for f in (b.formats if b.formats is not None else [(own, 1)] * len(b.views))]
-        resample = not plain_formats(self.fbank.sample_rate, [r for r, _ in formats], [c for _, c in formats])
-        if resample and len(set(b.channel for b in batches if b.formats is not None)) > 1:
-            raise ValueError("DecodePipelines: a pass mixes wave batches that read different channels")
-        offs, total = hip.gather_offsets([v.nbytes for v in views], 16)
-        if total >= 2 ** 31:
-            raise ValueError("DecodePipelines: a pass of %d sample bytes (the offsets are int32)" % total)
-        shift = max(1, int(self.fbank.sample_rate * 0.001 * self.fbank.frame_shift_ms))
-        flen = int(self.fbank.sample_rate * 0.001 * self.fbank.frame_length_ms)
-        key = ("wave", slot)
-        bufs = self._packed[k].get(key)
-        if bufs is None or bufs["cap"] < total or bufs["F"] != F or bufs["utts"] < rows:
-            utts = max(rows, self.max_utts)
-            cap = max(total, 2 * self.max_batch * self.frames_cap * (splice[2] if splice else 1) * shift + utts * (2 * flen + 16))
-            bufs = {"cap": cap, "F": F, "utts": utts,
-                    "host": torch.empty(cap, dtype=torch.uint8, pin_memory=True),
-                    "dev": torch.empty(cap, dtype=torch.uint8, device=dev_),
-                    # per utterance: byte offset, samples, float32 ratio (as int32 bits) - one small DMA
-                    "meta_h": torch.empty(3 * utts, dtype=torch.int32, pin_memory=True),
-                    "meta_d": torch.empty(3 * utts, dtype=torch.int32, device=dev_),
-                    "out": torch.empty(max(rows * tmax, self.max_batch * self.frames_cap) * F, dtype=torch.float32, device=dev_)}
-            self._packed[k][key] = bufs
-        if bufs["out"].numel() < rows * tmax * F:
-            bufs["out"] = torch.empty(rows * tmax * F, dtype=torch.float32, device=dev_)
-        hip.host_gather(bufs["host"].data_ptr(), views, max(1, self.copy_threads), align=16)
-        meta = bufs["meta_h"].numpy()
-        utts = bufs["utts"]
-        plan = None
-        if resample:  # the resampler's own small DMA (per utterance: offsets, samples, channels, where its wave goes; the rates' row lists)
-            if bufs.get("rs_h") is None:
-                bufs["rs_h"] = torch.empty(RESAMPLE_META * utts, dtype=torch.int32, pin_memory=True)
-                bufs["rs_d"] = torch.empty(RESAMPLE_META * utts, dtype=torch.int32, device=dev_)
-            channel = next(b.channel for b in batches if b.formats is not None)
-            plan = plan_resample(bufs["rs_h"].numpy(), utts, self.fbank, offs, [v.shape[0] for v in views], [r for r, _ in formats],
-                                 [c for _, c in formats], channel, [u for b in batches for u in (b.utts or [None] * len(b.views))])
-            if bufs.get("wave") is None or bufs["wave"].numel() < plan["wave_floats"]:
-                bufs["wave"] = torch.empty(max(plan["wave_floats"], bufs["cap"] // 2), dtype=torch.float32, device=dev_)
-            bufs["rs_d"].copy_(bufs["rs_h"], non_blocking=True)
-        meta[:rows] = offs
-        meta[utts:utts + rows] = [v.shape[0] for v in views]
-        meta[2 * utts:2 * utts + rows] = torch.cat([x[1] for x in items], 0).numpy().view(np.int32)
-        bufs["dev"][:total].copy_(bufs["host"][:total], non_blocking=True)
-        bufs["meta_d"].copy_(bufs["meta_h"], non_blocking=True)
-        feats = bufs["out"][: rows * tmax * F].view(rows, tmax, F)
-        stats = (None, None)
-        if self.cmvn is not None:
-            stats = self._cmvn_dev.get(self._device)
-            if stats is None:
-                stats = self._cmvn_dev[self._device] = (torch.from_numpy(self.cmvn[0]).to(dev_), torch.from_numpy(self.cmvn[1]).to(dev_))
-        def fbank(out):
-            if plan is None:
-                return hip.fbank_packed(self.fbank, bufs["dev"], total, bufs["meta_d"][:utts], bufs["meta_d"][utts:2 * utts], out, pad, stats[0], stats[1])
-            run_resampled(self.fbank, plan, bufs["dev"], total, bufs["rs_h"].numpy(), bufs["rs_d"], utts, bufs["wave"], out, pad, stats[0], stats[1])
-            self._bump("resampled_passes", 1)
-
-        if splice is not None:  # two launches: fbank + CMVN into the slot's scratch, then splice and skip out of it
-            mid, sp = self._splice_scratch(bufs, batches, rows, F0, splice, dev_)
-            fbank(mid)
-            hip.splice_rows(mid, sp[0], sp[1], feats, splice[0], splice[1], splice[2], pad)
-            self._bump("spliced_passes", 1)
-        else:
-            fbank(feats)
-        self._bump("wave_passes", 1)
-        return feats, bufs["meta_d"][2 * utts:2 * utts + rows].view(torch.float32)
-
     def _stage_inputs(self, k, slot, items, pad):
         """The merged input of a pass: the batches one after the other, padded to the longest with padding frames, in a buffer
         of the pipeline's full capacity (two of them: two passes in flight), allocated at the first merged pass."""
@@ -762,12 +337,7 @@ class DecodePipelines:
             # an utterance's frame count from collate's float32 ratio len / t (exact after rounding: t is a few thousand at most)
             lens = torch.cat([(x[1].double().cpu() * int(x[0].shape[1])).round().to(torch.int32) for x in items])
             if on_gpu:
-                stats = self._cmvn_dev.get(device)
-                if stats is None:
-                    stats = self._cmvn_dev[device] = (torch.from_numpy(self.cmvn[0]).to(dev_), torch.from_numpy(self.cmvn[1]).to(dev_))
-                from . import hip
-
-                hip.cmvn_(feats, lens.pin_memory().to(dev_, non_blocking=True), stats[0], stats[1])
+                _hip.cmvn_(feats, lens.pin_memory().to(dev_, non_blocking=True), *self._cmvn_stats(dev_))
             else:  # CPU rehearsal of the host logic: the same arithmetic in numpy
                 fv = feats.numpy()
                 for b, n in enumerate(lens.tolist()):

@@ -293,24 +293,21 @@ class CassNATTask(BaseTask):
         meta, frames, i, end = {}, 0, -1, time.time()
 
         def batches():
-            if wave:  # the loader's batches as views into the memory maps of the sound files (a map lives as long as its pass)
-                for j, idx in enumerate(self.test_loader.batch_sampler):
-                    got = [ds[i] for i in idx]
-                    pb = PackedBatch.from_waves([v for _, v, _ in got], [ds.wave_frames[i] for i in idx], feat_dim, utts=[u for u, _, _ in got],
-                                                splice=splice, formats=None if ds.wave_plain else [ds.wave_formats[i] for i in idx],
-                                                channel=ds.wave_admit["channel"])
-                    meta[j] = ([u for u, _, _ in got], [None] * len(got), pb.shape[0] * pb.shape[1], max(len(t) for _, _, t in got))
-                    yield pb, pb.ratios(), j
-                return
-            if packed:  # the loader's batches (same utterances, same order) as views into the archives' memory maps
-                for j, idx in enumerate(self.test_loader.batch_sampler):
-                    items = [ds._items[i] for i in idx]
-                    # (every header is checked against the path chosen above and the set's feature dimension: a contradiction
-                    # raises, naming the utterance)
-                    pb = PackedBatch.from_payloads([kaldi_io.mat_payload(spec) for _, spec, _ in items], utts=[u for u, _, _ in items],
-                                                   compressed=compressed, cols=feat_dim, splice=splice)
+            if wave or packed:  # the loader's batches (same utterances, same order) as views into the memory maps of the sound files
+                for j, idx in enumerate(self.test_loader.batch_sampler):  # / of the archives (a map lives as long as its pass)
+                    if wave:
+                        got = [ds[i] for i in idx]
+                        pb = PackedBatch.from_waves([v for _, v, _ in got], [ds.wave_frames[i] for i in idx], feat_dim, utts=[u for u, _, _ in got],
+                                                    splice=splice, formats=None if ds.wave_plain else [ds.wave_formats[i] for i in idx],
+                                                    channel=ds.wave_admit["channel"])
+                    else:
+                        got = [ds._items[i] for i in idx]
+                        # (every header is checked against the path chosen above and the set's feature dimension: a contradiction
+                        # raises, naming the utterance)
+                        pb = PackedBatch.from_payloads([kaldi_io.mat_payload(spec) for _, spec, _ in got], utts=[u for u, _, _ in got],
+                                                       compressed=compressed, cols=feat_dim, splice=splice)
                     # (utt2diff reads the width of the PADDED label row, src/tasks/cassnat_task.py:358-360)
-                    meta[j] = ([u for u, _, _ in items], [None] * len(items), pb.shape[0] * pb.shape[1], max(len(t) for _, _, t in items))
+                    meta[j] = ([u for u, _, _ in got], [None] * len(got), pb.shape[0] * pb.shape[1], max(len(t) for _, _, t in got))
                     yield pb, pb.ratios(), j
                 return
             for j, (utt_list, feats, labels, feat_sizes, label_sizes) in enumerate(self.test_loader):
