@@ -79,6 +79,15 @@ class CnAttnDesc(C.Structure):
                 ("rel_pos", C.c_void_p), ("rel_u", C.c_void_p), ("rel_v", C.c_void_p), ("rel_R", C.c_int32), ("ld_pos", C.c_int32)]
 
 
+class CnNgramDesc(C.Structure):
+    """cn_ngram_desc: the tables of an ARPA n-gram model (models.ngram.NgramLM owns them; cn_op_ngram_score / cn_ngram_score_host)."""
+    _fields_ = [("word_keys", C.c_void_p), ("word_ids", C.c_void_p), ("word_slots", C.c_int64),
+                ("gram_keys", C.c_void_p), ("gram_prob", C.c_void_p), ("gram_bo", C.c_void_p), ("gram_slots", C.c_int64),
+                ("piece_hash", C.c_void_p), ("piece_pow", C.c_void_p), ("piece_starts", C.c_void_p)] + \
+               [(n, C.c_int32) for n in ("vocab", "order", "bos", "eos", "unk", "reserved0")] + \
+               [("key_mask", C.c_uint64), ("reserved", C.c_int64 * 6)]
+
+
 class HipError(RuntimeError):
     pass
 
@@ -248,6 +257,13 @@ def lib(flavour=None):
                                        C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     L.cn_ast_ctc_correct.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(CnDecodeOpts), C.c_int32,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]
+    L.cn_ngram_desc_size.argtypes = []
+    L.cn_ngram_counts.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
+    L.cn_ngram_parse.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_int64, C.c_void_p]
+    L.cn_ngram_hash.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    L.cn_ngram_score_host.argtypes = [C.POINTER(CnNgramDesc), C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+    L.cn_op_ngram_score.argtypes = [C.POINTER(CnNgramDesc), C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     L.cn_profile_begin.argtypes = [C.c_void_p, C.c_char_p]
     L.cn_profile_end.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
     want = "fp16" if flavour == "f16" else "bf16"

@@ -542,7 +542,12 @@ class CassNAT(nn.Module):
         tokf, ylf = tok.reshape(S * B, stride), ylen.reshape(S * B)
         ylen_h = ylen.transpose(0, 1).cpu().long()                                                # (B, S)
         rank = getattr(args, "rank_model", "lm")
-        if rank == "n-gram":
+        if rank == "n-gram" and hasattr(lm_model, "score_tokens") and getattr(lm_model, "device_ok", False):
+            # models.ngram.NgramLM: the same numbers from the token rows where they are - the pieces are glued into words and every
+            # word is scored on the device; only the (S, B) sentence scores come back
+            sc = lm_model.score_tokens(tokf.contiguous(), ylf.contiguous(), drop_id=2)
+            prob_sum = (sc.reshape(S, B).transpose(0, 1).cpu().double() / ylen_h.double()).float()
+        elif rank == "n-gram":
             # cassnat.py:523-535: the n-gram model (kenlm) scores the predicted word pieces as text, per sample: score / tgt_len
             tok_c = tok.cpu().numpy()
             prob_sum = torch.zeros(B, S)

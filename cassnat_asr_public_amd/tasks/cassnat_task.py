@@ -64,6 +64,17 @@ def hyps_to_words_batch(toks, lens, vocab, padding_idx, table=None):
     return out
 
 
+def _is_arpa(path):
+    """True when the first non-blank line of the file is ``\\data\\`` (an ARPA text; kenlm's binary files begin otherwise)."""
+    with open(path, "rb") as f:
+        for raw in f:
+            if raw.strip():
+                return raw.strip() == b"\\data\\"
+            if f.tell() > 65536:
+                break
+    return False
+
+
 class CassNATTask(BaseTask):
     def __init__(self, mode, args):
         for k, v in _DEFAULTS.items():
@@ -126,8 +137,9 @@ class CassNATTask(BaseTask):
 
     def load_lm_model(self, args):
         """src/tasks/cassnat_task.py:85-125: the model that ranks ESA samples - a TransformerLM (rank_model 'lm'), the
-        autoregressive baseline (rank_model 'at_baseline': models.transformer, scoring teacher-forced) or a kenlm n-gram model
-        (rank_model 'n-gram', scored on the host as the reference does).  ``lm_weight > 0`` loads the same way (:86): the
+        autoregressive baseline (rank_model 'at_baseline': models.transformer, scoring teacher-forced) or an n-gram model
+        (rank_model 'n-gram': an ARPA text in ``rnnlm`` is read by models.ngram.NgramLM and scored on the device; anything else
+        goes to kenlm and is scored on the host as the reference does).  ``lm_weight > 0`` loads the same way (:86): the
         TransformerLM that the finish loop fuses (models.cassnat.CassNAT._lm_finish), which needs rank_model 'lm' - the reference
         calls lm_model(ys, mask) on whatever it loaded and fails on the other two."""
         self.lm_model = None
@@ -137,7 +149,13 @@ class CassNATTask(BaseTask):
                                       "fails on rank_model '%s' there)" % rank)
         if args.lm_weight > 0 or getattr(args, "ctc_lm_weight", 0) > 0:
             if rank == "n-gram":
-                import kenlm  # (not a dependency of this package: needed for this ranker only, as in the reference)
+                if _is_arpa(args.rnnlm):  # an ARPA text: the package's own model, scored on the device (models.ngram)
+                    from ..models.ngram import NgramLM
+
+                    lm_model = NgramLM.load(args.rnnlm, self.vocab)  # (every rank reads the file itself, as it would with kenlm)
+                    self.lm_model = lm_model.cuda(getattr(self, "local_rank", None)) if torch.cuda.is_available() else lm_model
+                    return
+                import kenlm  # (binary kenlm files: not a dependency of this package, needed for them only, as in the reference)
 
                 self.lm_model = kenlm.Model(args.rnnlm)
                 return

@@ -718,6 +718,58 @@ int cn_op_ctc_lm_frame(double* pb, double* pnb, double* sctc, double* slm, int32
                        int32_t iter, int32_t Lt, int32_t hist_stride, double lp, double lm_weight, void* stream);
 int cn_op_ctc_lm_rows(const float* fresh, const float* prv, float* nxt, const int32_t* parent, const int32_t* stay, const int32_t* count,
                       int32_t iter, int32_t slots, int32_t W, int32_t V, void* stream);
+
+/* ---- ARPA n-gram model: the ESA ranker `rank_model: n-gram` (ngram.hip; models/ngram.py owns the tables) ---------------------
+ * The score of a row of word-piece ids is log10 P(w_1 .. w_m </s> | <s>) of the words its pieces spell, with textbook ARPA back-off:
+ * the history of a word is the last c = min(order - 1, words so far + 1) ids, starting with <s>; p is the probability of the longest
+ * k-gram (k = c + 1 .. 1) of the model that ends in the word, and the back-off weights of the j-grams made of the last j history ids
+ * are added for j = k .. c in that order (an absent n-gram or weight adds nothing).  float32 throughout: a word's score is summed in
+ * that order, the row's score is the sum of the word scores in word order, </s> last.
+ * Hashing.  A word's key is H(bytes) = sum (byte_i + 1) * P^(n - 1 - i) mod 2^64 with P = 0x9E3779B97F4A7C15, so that
+ * H(ab) = H(a) * P^len(b) + H(b): a piece of the vocabulary contributes the pair (H(body), P^len(body)) and a flag "begins with a
+ * separator" (U+2581 or ASCII white space, a leading run only; the body may be empty).  An n-gram's key mixes its order and ids.
+ * Look-ups compare the 64-bit key alone (key_mask keeps the low hash_bits of every key: a test's way to make keys collide).
+ * Tables: open addressing with linear probing, power-of-two slot counts, at most half full.  word_ids < 0 and gram_prob = +infinity
+ * mark an empty slot.  Every pointer of a desc is a device pointer for cn_op_ngram_score and a host pointer for the host entries. */
+typedef struct cn_ngram_desc {
+    const uint64_t* word_keys; /* [word_slots] */
+    const int32_t* word_ids;   /* [word_slots] */
+    int64_t word_slots;
+    const uint64_t* gram_keys; /* [gram_slots] */
+    const float* gram_prob;    /* [gram_slots] */
+    const float* gram_bo;      /* [gram_slots] */
+    int64_t gram_slots;
+    const uint64_t* piece_hash; /* [vocab] H(body) */
+    const uint64_t* piece_pow;  /* [vocab] P^len(body) */
+    const uint8_t* piece_starts; /* [vocab] 1: the piece begins with a separator */
+    int32_t vocab;
+    int32_t order;             /* 1 .. 8 */
+    int32_t bos, eos, unk;     /* word ids of <s>, </s>, <unk> */
+    int32_t reserved0;
+    uint64_t key_mask;
+    int64_t reserved[6];
+} cn_ngram_desc;
+int32_t cn_ngram_desc_size(void);
+/* Host only, no GPU involved.  cn_ngram_counts reads the \data\ header of an ARPA text: counts[0] = order (1 .. 8, else refused),
+ * counts[k] = the `ngram k=` value.  cn_ngram_parse reads the whole text into tables the caller allocated (word_slots / gram_slots:
+ * powers of two, at least 2 * (counts[1] + 1) and 2 * (sum of the counts + 1)); word ids are the positions in the 1-gram section, a
+ * file without <unk> gets one more id with probability -100.  info[0..8) = order, ids, entries, entries whose prefix or suffix
+ * (n - 1)-gram is not in the file, the ids of <s>, </s>, <unk>, and 1 when the file has <unk>.  Refused with the line's number
+ * in the message: a section whose line count differs from its `ngram k=` line, a malformed line, a missing <s> or </s>, two entries
+ * with the same key.  cn_ngram_hash: H and P^len of n byte strings, string i = bytes[off[i], off[i + 1]). */
+int cn_ngram_counts(const void* text, int64_t bytes, int64_t* counts);
+int cn_ngram_parse(const void* text, int64_t bytes, int32_t hash_bits, uint64_t* word_keys, int32_t* word_ids, int64_t word_slots,
+                   uint64_t* gram_keys, float* gram_prob, float* gram_bo, int64_t gram_slots, int64_t* info);
+int cn_ngram_hash(const void* bytes, const int64_t* off, int32_t n, uint64_t* h, uint64_t* pw);
+/* Scores of `rows` rows of tok [rows][stride] (row r: its first len[r] ids, clamped to [0, stride]); ids equal to drop_id are left
+ * out, an id outside [0, vocab) is never used as an index: it stands for a piece that begins a word no model holds.  score [rows]
+ * float32; nothing else is written.  cn_ngram_score_host runs on the host with host pointers; cn_op_ngram_score is one wave per row
+ * on the device, stateless, ordered on `stream`; the two share one scoring core and agree bit for bit.  Refused without a launch
+ * (-1): a null pointer, rows or stride < 1, vocab < 0, an order outside 1 .. 8, a slot count that is no power of two. */
+int cn_ngram_score_host(const cn_ngram_desc* desc, const int32_t* tok, int32_t stride, const int32_t* len, int32_t rows,
+                        int32_t drop_id, float* score);
+int cn_op_ngram_score(const cn_ngram_desc* desc, const int32_t* tok_dev, int32_t stride, const int32_t* len_dev, int32_t rows,
+                      int32_t drop_id, float* score_dev, void* stream);
 #ifdef __cplusplus
 }
 #endif
