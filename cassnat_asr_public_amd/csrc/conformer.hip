@@ -98,6 +98,7 @@ int launch_glu(int prec, const void* in, void* out, int M, int d, hipStream_t s)
 // Tiled form for the kernel sizes the recipes use: a thread owns one channel and TT consecutive frames; the K taps sit in
 // registers and every input frame of the window is loaded once (TT + K - 1 loads per TT outputs instead of K per output).
 // Each output still accumulates bias, tap 0, tap 1, ... in that order, so the result equals dwconv_kernel's bit for bit.
+// (tests/test_gpu_convmodule.py holds both forms to that, through cn_op_dwconv's form argument.)
 template <typename T, int K, int TT>
 __global__ __launch_bounds__(256) void dwconv_tiled_kernel(const T* __restrict__ x, const float* __restrict__ w,
                                                            const float* __restrict__ bias, float* __restrict__ y, int L, int d) {
@@ -137,9 +138,12 @@ static void launch_dwconv_tiled(const void* x, const float* w, const float* bias
     hipLaunchKernelGGL((dwconv_tiled_kernel<T, K, TT>), grid, dim3(256), 0, s, (const T*)x, w, bias, y, L, d);
 }
 
-int launch_dwconv(int prec, const void* x, const float* w, const float* bias, float* y, int B, int L, int d, int k, hipStream_t s) {
+// form 0: the tiled kernel for the kernel sizes it is built for (3, 7, 15, 31), dwconv_kernel for every other; 1: dwconv_kernel
+int launch_dwconv(int prec, const void* x, const float* w, const float* bias, float* y, int B, int L, int d, int k, int form,
+                  hipStream_t s) {
     if (B * L <= 0) return 0;
-    static const bool naive = cn_exp_env("CASSNAT_DWCONV_NAIVE") != nullptr;
+    static const bool naive_env = cn_exp_env("CASSNAT_DWCONV_NAIVE") != nullptr;
+    const bool naive = naive_env || form == 1;
 #define DW_CASE(KK)                                                                                   \
     case KK:                                                                                          \
         if (prec == CN_PREC_F32) launch_dwconv_tiled<float, KK>(x, w, bias, y, B, L, d, s);           \

@@ -170,7 +170,8 @@ int attention_print_stamps();  // CASSNAT_ATTN_STAMPS: phase timestamps of the l
 
 // ---- conformer convolution module pieces (conformer.hip)
 int launch_glu(int prec, const void* in, void* out, int M, int d, hipStream_t s);
-int launch_dwconv(int prec, const void* x, const float* w, const float* bias, float* y, int B, int L, int d, int k, hipStream_t s);
+int launch_dwconv(int prec, const void* x, const float* w, const float* bias, float* y, int B, int L, int d, int k, int form,
+                  hipStream_t s);
 int launch_groupnorm_swish(int prec, const float* x, double* stats, const float* gw, const float* gb, void* out, int B, int L,
                            int d, float eps, hipStream_t s);
 

@@ -1752,7 +1752,7 @@ int run_conv_module(cn_model* m, const Layer& L, const Norm& n, float* x, int B,
     {
         ProfScope ps(m, "conv_glu_depthwise_norm", 2.0 * M * d * L.conv.k, (double)M * d * (4 * m->es + 12), s);
         CN_TRY(launch_glu(m->prec, m->cv_a, m->xn, M, d, s));
-        CN_TRY(launch_dwconv(m->prec, m->xn, L.conv.dw_w, L.conv.dw_b, m->cv_f, B, Lseq, d, L.conv.k, s));
+        CN_TRY(launch_dwconv(m->prec, m->xn, L.conv.dw_w, L.conv.dw_b, m->cv_f, B, Lseq, d, L.conv.k, 0, s));
         CN_TRY(launch_groupnorm_swish(m->prec, m->cv_f, m->gn_stats, L.conv.gn_w, L.conv.gn_b, m->xn, B, Lseq, d, 1e-5f, s));
     }
     return run_linear(m, "conv_pointwise2_resid", L.conv.pw2, m->xn, d, x, d, 1, M, CN_EPI_RESID, x, d, s);
@@ -1788,7 +1788,7 @@ int run_conformer_layer_chain(cn_model* m, const Layer& L, float* x, int B, int 
     {
         ProfScope ps(m, "conv_glu_depthwise_norm", 2.0 * M * d * L.conv.k, (double)M * d * (4 * m->es + 12), s);
         CN_TRY(launch_glu(m->prec, m->cv_a, m->xn, M, d, s));
-        CN_TRY(launch_dwconv(m->prec, m->xn, L.conv.dw_w, L.conv.dw_b, m->cv_f, B, Lseq, d, L.conv.k, s));
+        CN_TRY(launch_dwconv(m->prec, m->xn, L.conv.dw_w, L.conv.dw_b, m->cv_f, B, Lseq, d, L.conv.k, 0, s));
         // (the module's output goes to m->ctx: the next chain's output projection is pointwise conv 2)
         CN_TRY(launch_groupnorm_swish(m->prec, m->cv_f, m->gn_stats, L.conv.gn_w, L.conv.gn_b, m->ctx, B, Lseq, d, 1e-5f, s));
         m->ctx_blocked = false;  // (row-major)
@@ -2428,6 +2428,15 @@ extern "C" int cn_model_create(const cn_config* cfg, cn_model** out) {
         cn_set_error(c.ast == 1 ? "cn_model_create: the autoregressive model (ast = 1) has no conformer decoder (conf_dec = 1): the reference "
                                   "defines none (models/conformer.py keeps transformer decoder layers)"
                                 : "cn_model_create: the TransformerLM (ast = 2) has no conformer blocks");
+        return -1;
+    }
+    // the reference's Conv1d(padding = (k - 1) // 2) yields L - 1 frames for an even k and its residual add fails
+    if (c.conf_enc && (c.enc_kernel < 1 || c.enc_kernel % 2 == 0)) {
+        cn_set_error("cn_model_create: enc_kernel must be odd and >= 1 for a conformer encoder (conf_enc = 1), got " + std::to_string(c.enc_kernel));
+        return -1;
+    }
+    if (c.conf_dec && (c.dec_kernel < 1 || c.dec_kernel % 2 == 0)) {
+        cn_set_error("cn_model_create: dec_kernel must be odd and >= 1 for a conformer decoder (conf_dec = 1), got " + std::to_string(c.dec_kernel));
         return -1;
     }
     if (c.input_size < 4 || c.vocab_size < 4 || c.max_batch < 1 || c.max_frames < 4 || c.n_enc < 0 || c.n_extra < 0 ||

@@ -382,6 +382,77 @@ extern "C" int cn_op_layernorm(int32_t precision, const float* x, const float* a
     return launch_layernorm(precision, x, a2, b2, y, 0, M, d, eps, (hipStream_t)stream);
 }
 
+// ---- the conformer convolution module's kernels (conformer.hip), one at a time
+// the kernels index rows of d elements and an utterance's L x d image with int: refuse what would not fit
+static int conv_module_dims(const char* who, int precision, long long rows, long long row_len, int d, const char* what) {
+    if (precision != CN_PREC_F32 && precision != CN_PREC_BF16 && precision != CN_PREC_X3) {
+        cn_set_error(std::string(who) + ": precision must be F32, BF16 (F16 in the half-precision build) or BF16X3");
+        return -1;
+    }
+    if (precision == CN_PREC_X3 && d % 32 != 0) {
+        cn_set_error(std::string(who) + ": split-bf16 (bf16x3) rows are groups of 32 elements: d % 32 != 0 has no layout");
+        return -1;
+    }
+    if (row_len * d > 0x7fffffffLL || rows * row_len > 0x7fffffffLL || rows * row_len * d >= (1LL << 39)) {
+        cn_set_error(std::string(who) + ": " + what + " exceeds the kernels' int arithmetic (2^31 - 1; all elements together: 2^39)");
+        return -1;
+    }
+    return 0;
+}
+
+extern "C" int cn_op_glu(int32_t precision, const void* in, void* out, int32_t M, int32_t d, void* stream) {
+    if ((precision = cn_own_precision(precision, "cn_op_glu")) < 0) return -1;
+    if (!in || !out) {
+        cn_set_error("cn_op_glu: null pointer (in, out)");
+        return -1;
+    }
+    if (M < 1 || d < 1) {
+        cn_set_error("cn_op_glu: M and d must be >= 1");
+        return -1;
+    }
+    // (the input row holds 2 d elements)
+    CN_TRY(conv_module_dims("cn_op_glu", precision, 1, 2LL * M, d, "M * 2d"));
+    return launch_glu(precision, in, out, M, d, (hipStream_t)stream);
+}
+
+extern "C" int cn_op_dwconv(int32_t precision, const void* x, const float* w, const float* bias, float* y, int32_t B, int32_t L,
+                            int32_t d, int32_t k, int32_t form, void* stream) {
+    if ((precision = cn_own_precision(precision, "cn_op_dwconv")) < 0) return -1;
+    if (!x || !w || !bias || !y) {
+        cn_set_error("cn_op_dwconv: null pointer (x, w, bias, y)");
+        return -1;
+    }
+    if (B < 1 || L < 1 || d < 1 || k < 1) {
+        cn_set_error("cn_op_dwconv: B, L, d and k must be >= 1");
+        return -1;
+    }
+    if (form != 0 && form != 1) {
+        cn_set_error("cn_op_dwconv: form must be 0 (the launcher's choice) or 1 (the naive kernel)");
+        return -1;
+    }
+    CN_TRY(conv_module_dims("cn_op_dwconv", precision, B, L, d, "L * d (or B * L)"));
+    if ((long long)d * k > 0x7fffffffLL || (long long)L + k > 0x7fffffffLL) {
+        cn_set_error("cn_op_dwconv: d * k and L + k exceed the kernels' int arithmetic (<= 2^31 - 1)");
+        return -1;
+    }
+    return launch_dwconv(precision, x, w, bias, y, B, L, d, k, form, (hipStream_t)stream);
+}
+
+extern "C" int cn_op_groupnorm_swish(int32_t precision, const float* x, double* stats, const float* gw, const float* gb, void* out,
+                                     int32_t B, int32_t L, int32_t d, float eps, void* stream) {
+    if ((precision = cn_own_precision(precision, "cn_op_groupnorm_swish")) < 0) return -1;
+    if (!x || !stats || !gw || !gb || !out) {
+        cn_set_error("cn_op_groupnorm_swish: null pointer (x, stats, gw, gb, out)");
+        return -1;
+    }
+    if (B < 1 || L < 1 || d < 1) {
+        cn_set_error("cn_op_groupnorm_swish: B, L and d must be >= 1");
+        return -1;
+    }
+    CN_TRY(conv_module_dims("cn_op_groupnorm_swish", precision, B, L, d, "L * d (or B * L)"));
+    return launch_groupnorm_swish(precision, x, stats, gw, gb, out, B, L, d, eps, (hipStream_t)stream);
+}
+
 extern "C" int cn_op_attention(int32_t precision, const void* Q, int32_t ldq, const void* K, int32_t ldk, const void* V,
                                int32_t ldv, void* O, int32_t ldo, int32_t B, int32_t H, int32_t Lq, int32_t Lk,
                                const uint8_t* keymask, const int32_t* klen, const int32_t* intervals, int32_t iv_stride,

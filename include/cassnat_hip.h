@@ -56,7 +56,7 @@ typedef struct cn_config {
      * attention, convolution module.  conf_enc / conf_dec = args.use_conv_enc / use_conv_dec. */
     int32_t conf_enc, conf_dec;
     int32_t enc_max_rel, dec_max_rel; /* args.enc_max_relative_len / dec_max_relative_len (<= 31) */
-    int32_t enc_kernel, dec_kernel;   /* args.enc_kernel_size / dec_kernel_size (odd) */
+    int32_t enc_kernel, dec_kernel;   /* args.enc_kernel_size / dec_kernel_size (odd, >= 1: cn_model_create refuses others) */
     int32_t d_ff;                     /* args.d_ff: width of the conformer extractor's FFN */
     int32_t esa_group;                /* ESA: sampled alignments per utterance one cn_esa_sample pass may take (0/1: one);
                                          sizes the decoder-side workspace (max_batch x esa_group query sets) */
@@ -478,6 +478,23 @@ int cn_op_conv2(int32_t precision, const void* conv1_out, const void* w_khwc, co
                 int32_t T1, int32_t F1, int32_t C, void* stream);
 int cn_op_layernorm(int32_t precision, const float* x, const float* a2, const float* b2, void* y, int32_t M, int32_t d,
                     float eps, void* stream);
+/* The conformer convolution module's kernels one at a time (csrc/conformer.hip; src/models/modules/conformer_related.py:15-44).
+ * "The precision's layout": fp32, the library's 16-bit operand, or split-bf16 rows (per group of 32 columns 32 hi then 32 lo
+ * halves; d % 32 == 0).  Each entry refuses, before any launch: null pointers; M, B, L, d or k < 1; M * d (L * d) beyond the
+ * kernels' int arithmetic; split-bf16 with d % 32 != 0.
+ * cn_op_glu: in [M][2d] -> out [M][d] = in[:, :d] * sigmoid(in[:, d:]), both in the precision's layout. */
+int cn_op_glu(int32_t precision, const void* in, void* out, int32_t M, int32_t d, void* stream);
+/* Depthwise convolution over time: y[b][t][c] = bias[c] + sum_j w[c][j] x[b][t + j - (k - 1) / 2][c], zero outside [0, L) of the
+ * same utterance.  x [B*L][d] in the precision's layout; w [d][k], bias [d], y [B*L][d] fp32.  Any k >= 1 (an even k has the
+ * longer side of its window behind t; cn_model_create refuses it for a model).  form 0: the launcher's choice (the tiled kernel for
+ * k = 3, 7, 15, 31, the naive one otherwise), 1: the naive kernel. */
+int cn_op_dwconv(int32_t precision, const void* x, const float* w, const float* bias, float* y, int32_t B, int32_t L, int32_t d,
+                 int32_t k, int32_t form, void* stream);
+/* GroupNorm(1, d) over the whole L x d image of each utterance (biased variance), affine per channel, Swish.  x [B*L][d] fp32;
+ * stats [B][2] float64, written by the call: (sum, sum of squares) of each utterance; gw, gb [d] fp32; out [B*L][d] in the
+ * precision's layout. */
+int cn_op_groupnorm_swish(int32_t precision, const float* x, double* stats, const float* gw, const float* gb, void* out, int32_t B,
+                          int32_t L, int32_t d, float eps, void* stream);
 int cn_op_attention(int32_t precision, const void* Q, int32_t ldq, const void* K, int32_t ldk, const void* V,
                     int32_t ldv, void* O, int32_t ldo, int32_t B, int32_t H, int32_t Lq, int32_t Lk,
                     const uint8_t* keymask, const int32_t* klen, const int32_t* intervals, int32_t iv_stride,
