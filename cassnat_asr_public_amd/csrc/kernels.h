@@ -339,6 +339,12 @@ int launch_wave_resample(int in_rate, int out_rate, const unsigned char* staged,
                          const int* channels, const int* channel, int utts, const int* rows, int n_rows, long long max_out, float* out,
                          const int* out_off, hipStream_t s);
 
+// ---- FLAC frames -> interleaved int16 PCM as a WAV data chunk holds it (flac.hip; the per-frame routines: flac_decode.h)
+long long flac_scratch_bytes(int frames, long long frame_words);
+int launch_flac_decode(const unsigned char* staged, long long staged_bytes, const int* table, int frames, const int* utt, int utts,
+                       int max_channels, long long frame_words, unsigned char* pcm, long long pcm_bytes, int* status, int* scratch,
+                       hipStream_t s);
+
 // ---- conv2 as an LDS-DMA implicit GEMM, bf16 / 256 -> 256 channels (conv2.hip); launch_gemm dispatches to it
 bool conv2_dma_applies(int prec, int C, int N);
 // split-bf16 form of the same kernel: image and weights as hi / lo bf16 planes, three K steps per K step of the bf16 loop

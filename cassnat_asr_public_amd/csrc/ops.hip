@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/cassnat_hip.h"
+#include "flac_decode.h"
 #include "kernels.h"
 
 namespace {
@@ -741,6 +742,70 @@ extern "C" int cn_host_gather(void* dst, const uint64_t* src_ptrs, const uint64_
     }
     for (auto& th : pool) th.join();
     return 0;
+}
+
+// Host side of the FLAC reader: the exact frame index of a stream's audio bytes (flac_format.h: one linear pass, every frame's CRC-16
+// checked); GIL-free like the gather, the loader's workers and the pipelines' threads run it side by side.
+extern "C" int cn_host_flac_index(const void* audio, int64_t nbytes, int32_t rate, int32_t channels, int32_t bits, int32_t* out,
+                                  int64_t capacity, int64_t* frames, int64_t* samples, int64_t* bad_offset) {
+    if (!audio || nbytes < 0 || !frames || !samples || !bad_offset || capacity < 0) {
+        cn_set_error("cn_host_flac_index: null argument");
+        return -1;
+    }
+    const int rc = flac_index(static_cast<const uint8_t*>(audio), nbytes, rate, channels, bits, out, capacity, frames, samples, bad_offset);
+    if (rc == FLAC_INDEX_NO_CHAIN)
+        cn_set_error("cn_host_flac_index: no chain of frames with matching CRCs reaches the end: it breaks at byte offset " +
+                     std::to_string(*bad_offset));
+    else if (rc == FLAC_INDEX_FORMAT)
+        cn_set_error("cn_host_flac_index: the frame at byte offset " + std::to_string(*bad_offset) +
+                     " has another sample rate, channel count or sample size than STREAMINFO");
+    else if (rc == FLAC_INDEX_CAPACITY)
+        cn_set_error("cn_host_flac_index: more frames than the output holds");
+    else if (rc == FLAC_INDEX_RANGE)
+        cn_set_error("cn_host_flac_index: offsets or sample counts beyond 2^31 - 1");
+    return rc;
+}
+
+extern "C" int32_t cn_host_flac_crc16(const void* data, int64_t nbytes) {
+    return data && nbytes > 0 ? (int32_t)flac_crc16(static_cast<const uint8_t*>(data), nbytes) : 0;
+}
+
+extern "C" int64_t cn_flac_frame_words(int32_t channels, int32_t block_size) { return flac_frame_words(channels, block_size); }
+
+extern "C" int64_t cn_flac_scratch_bytes(int32_t frames, int64_t frame_words) { return flac_scratch_bytes(frames, frame_words); }
+
+extern "C" int cn_op_flac_decode(const void* staged_dev, int64_t staged_bytes, const int32_t* table_dev, int32_t frames, const int32_t* utt_dev,
+                                 int32_t utts, int32_t max_channels, int64_t frame_words, void* pcm_dev, int64_t pcm_bytes,
+                                 int32_t* status_dev, void* scratch_dev, int64_t scratch_bytes, void* stream) {
+    if (!staged_dev || !table_dev || !utt_dev || !pcm_dev || !status_dev) {
+        cn_set_error("cn_op_flac_decode: null argument");
+        return -1;
+    }
+    if (frames < 1 || utts < 1 || max_channels < 1 || max_channels > 8 || staged_bytes < 0 || pcm_bytes < 0 ||
+        frame_words < flac_frame_words(1, 1) || frame_words > flac_frame_words(8, 65536)) {
+        cn_set_error("cn_op_flac_decode: need frames, utts >= 1, 1 <= max_channels <= 8 and frame_words of at least one sample");
+        return -1;
+    }
+    if (((size_t)pcm_dev & 1) || ((size_t)scratch_dev & 3)) {
+        cn_set_error("cn_op_flac_decode: the PCM buffer must be 2-byte, the scratch 4-byte aligned");
+        return -1;
+    }
+    const int64_t need = flac_scratch_bytes(frames, frame_words);
+    if (scratch_dev) {  // the caller's scratch (the packed reader keeps one per slot): nothing is allocated, nothing waited for
+        if (scratch_bytes < need) {
+            cn_set_error("cn_op_flac_decode: the scratch holds " + std::to_string(scratch_bytes) + " bytes, the pass needs " + std::to_string(need));
+            return -1;
+        }
+        return launch_flac_decode(static_cast<const unsigned char*>(staged_dev), staged_bytes, table_dev, frames, utt_dev, utts, max_channels,
+                                  frame_words, static_cast<unsigned char*>(pcm_dev), pcm_bytes, status_dev, static_cast<int*>(scratch_dev),
+                                  (hipStream_t)stream);
+    }
+    Scratch sc("cn_op_flac_decode", (hipStream_t)stream);
+    int* scratch = static_cast<int*>(sc.alloc((size_t)need));
+    if (!sc.ok()) return -2;
+    return sc.finish(launch_flac_decode(static_cast<const unsigned char*>(staged_dev), staged_bytes, table_dev, frames, utt_dev, utts,
+                                        max_channels, frame_words, static_cast<unsigned char*>(pcm_dev), pcm_bytes, status_dev, scratch,
+                                        (hipStream_t)stream));
 }
 
 extern "C" int cn_op_unpack_rows(const float* packed_dev, const int32_t* off_dev, const int32_t* len_dev, float* out_dev, int32_t rows,

@@ -151,6 +151,49 @@ def run_resampled(opts, plan, staged, total, mv, meta_d, U, wave, feats, pad, me
     hip.fbank_packed_f32(opts, wave, 4 * plan["wave_floats"], meta_d[5 * U:6 * U], meta_d[6 * U:7 * U], feats, pad, mean, std)
 
 
+def plan_flac(index, offs, channels):
+    """Host side of a FLAC pass.  ``index``: per utterance its ``flac_io.FlacIndex``; ``offs``: the byte offset of its frames in the
+    staging buffer; ``channels``: its channel count.  -> dict: ``table`` int32 (frames, 4) - byte offset in the staging buffer, byte
+    length, utterance, first sample -, ``utt`` int32 (3, B) - channels, samples per channel, byte offset of the PCM -, ``pcm_offs`` /
+    ``pcm_bytes`` (every utterance's PCM at a 16-byte-aligned offset: the layout of staged WAV data chunks), ``lengths`` (int16
+    values per utterance, all channels), ``frame_words`` and ``max_channels`` (what ``hip.flac_decode`` sizes its scratch by),
+    ``starts`` (the first table row of every utterance)."""
+    B = len(index)
+    tabs, words, starts, at = [], 0, [], 0
+    for b, ix in enumerate(index):
+        fr = np.asarray(ix.frames, np.int32).reshape(-1, 3)
+        if fr.shape[0] == 0:
+            raise ValueError("utterance #%d: a FLAC index without frames" % b)
+        t = np.empty((fr.shape[0], 4), np.int32)
+        t[:, 0], t[:, 1], t[:, 2], t[:, 3] = fr[:, 0].astype(np.int64) + int(offs[b]), fr[:, 1], b, fr[:, 2]
+        tabs.append(t)
+        starts.append(at)
+        at += fr.shape[0]
+        longest = int(np.diff(np.append(fr[:, 2].astype(np.int64), int(ix.samples))).max())
+        words = max(words, hip.flac_frame_words(int(channels[b]), max(1, longest)))
+    lengths = [int(ix.samples) * int(c) for ix, c in zip(index, channels)]
+    pcm_offs, pcm_bytes = hip.gather_offsets([2 * n for n in lengths], 16)
+    if pcm_bytes >= 2 ** 31:
+        raise ValueError("a pass of %d decoded PCM bytes (the offsets are int32)" % pcm_bytes)
+    utt = np.empty((3, B), np.int32)
+    utt[0], utt[1], utt[2] = channels, [int(ix.samples) for ix in index], pcm_offs
+    return {"table": np.concatenate(tabs), "utt": utt, "pcm_offs": pcm_offs, "pcm_bytes": int(pcm_bytes), "lengths": lengths,
+            "frame_words": words, "max_channels": int(max(channels)), "starts": starts}
+
+
+def flac_status_error(status, plan, utts=None):
+    """The status word of ``hip.flac_decode`` after a pass -> None (0: every frame decoded) or the ValueError that names the
+    utterance and the frame.  With an index whose CRC-16s matched this does not happen; it is what keeps a wrong table from
+    becoming a wild write."""
+    if not status:
+        return None
+    f = int(status) - 1
+    b = int(plan["table"][f, 2]) if 0 <= f < plan["table"].shape[0] else -1
+    name = utts[b] if utts is not None and 0 <= b < len(utts) and utts[b] is not None else "#%d" % b
+    return ValueError("utterance %s: FLAC frame %d (row %d of the pass's frame table) did not decode on the device: its bitstream does "
+                      "not end on the frame's footer, or its block does not fit the utterance" % (name, f - plan["starts"][b] if b >= 0 else -1, f))
+
+
 class Fbank:
     def __init__(self, cmvn_mean=None, cmvn_std=None, pad_value=0.0, device=None, splice=None, **opts):
         """opts: sample_rate, frame_length_ms, frame_shift_ms, preemph, low_freq, high_freq, num_mel, window, remove_dc, ...
@@ -162,7 +205,7 @@ class Fbank:
         self.allow_downsample = bool(opts.pop("allow_downsample", ADMIT_OPTIONS["allow_downsample"]))
         self.allow_upsample = bool(opts.pop("allow_upsample", ADMIT_OPTIONS["allow_upsample"]))
         self.channel = int(opts.pop("channel", ADMIT_OPTIONS["channel"]))
-        self.resampled_passes = 0
+        self.resampled_passes = self.flac_passes = 0
         self.splice = splice_triple(*splice) if splice else None
         self.L = hip.lib()
         self.o = hip.CnFbankOpts()
@@ -204,7 +247,7 @@ class Fbank:
         """The keyword options of ``wave_io`` that say which files this front-end takes."""
         return {"allow_downsample": self.allow_downsample, "allow_upsample": self.allow_upsample, "channel": self.channel}
 
-    def packed(self, views, utts=None, rates=None, channels=None):
+    def packed(self, views, utts=None, rates=None, channels=None, flac=None):
         """``views``: one-dimensional int16 arrays (``wave_io.pcm_view``) -> (feats (B, T, num_mel) float32 cuda, ratios (B,) float32
         host) on the current stream.  The samples travel as they are - gathered at 16-byte-aligned offsets into page-locked memory,
         one copy - and ``hip.fbank_packed`` computes the padded batch on the device; no padded float matrix exists on the host.
@@ -212,14 +255,26 @@ class Fbank:
         the interleaved data chunks).  None, or every rate equal to ``sample_rate`` and every file mono: exactly the path above.
         Otherwise the interleaved int16 is staged as it is (same gather, same single copy), one ``hip.wave_resample`` per distinct
         rate writes channel ``self.channel`` at ``sample_rate`` into a float32 wave buffer and ``hip.fbank_packed_f32`` reads that.
-        The splice follows either way."""
+        The splice follows either way.
+        ``flac``: per utterance the ``flac_io.FlacIndex`` of its file - ``views`` are then the files' uint8 frame bytes (``rates`` /
+        ``channels`` from STREAMINFO are required): they are staged as they are, about half the bytes of the PCM, the pass's frame
+        table follows in a DMA of its own and ``hip.flac_decode`` writes the interleaved int16 PCM into a device buffer laid out as
+        the staged data chunks of WAV files would be - everything behind it is the path above, launch for launch."""
         resample = not plain_formats(self.o.sample_rate, rates, channels)
         B = len(views)
-        views = [np.ascontiguousarray(v, dtype="<i2") for v in views]
+        if flac is not None:
+            if rates is None or channels is None or len(flac) != B:
+                raise ValueError("Fbank.packed: a FLAC batch needs one index, rate and channel count per utterance")
+            views = [np.ascontiguousarray(v, dtype=np.uint8) for v in views]
+        else:
+            views = [np.ascontiguousarray(v, dtype="<i2") for v in views]
         offs, total = hip.gather_offsets([v.nbytes for v in views], 16)
         if total >= 2 ** 31:
             raise ValueError("Fbank.packed: a batch of %d bytes (the offsets are int32)" % total)
         counts, at = [v.shape[0] for v in views], ""  # (the samples the front-end sees, per utterance)
+        if flac is not None:  # the front-end reads the decoded PCM: its offsets, its int16 counts
+            fplan = plan_flac(flac, offs, [int(c) for c in channels])
+            flac_offs, flac_total, offs, total, counts = offs, total, fplan["pcm_offs"], fplan["pcm_bytes"], fplan["lengths"]
         meta = torch.empty((RESAMPLE_META if resample else 2) * B, dtype=torch.int32, pin_memory=True)
         if resample:
             rates = [int(round(float(self.o.sample_rate)))] * B if rates is None else [int(r) for r in rates]
@@ -232,12 +287,25 @@ class Fbank:
         for b, n in enumerate(frames):
             if n < 1:
                 raise ValueError("utterance %s: %d samples%s are shorter than one analysis window" % (utts[b] if utts is not None else "#%d" % b, counts[b], at))
-        host = torch.empty(total, dtype=torch.uint8, pin_memory=True)
+        host = torch.empty(total if flac is None else flac_total, dtype=torch.uint8, pin_memory=True)
         hip.host_gather(host.data_ptr(), views, 1, align=16)
         feats = torch.empty(B, max(frames), self.o.num_mel, dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
             staged = host.to(self.device, non_blocking=True)
             meta_d = meta.to(self.device, non_blocking=True)
+            if flac is not None:
+                nf = fplan["table"].shape[0]
+                fmeta = torch.empty(4 * nf + 3 * B + 1, dtype=torch.int32, pin_memory=True)
+                fmeta.numpy()[:4 * nf], fmeta.numpy()[4 * nf:4 * nf + 3 * B], fmeta.numpy()[-1] = fplan["table"].ravel(), fplan["utt"].ravel(), 0
+                fmeta_d = fmeta.to(self.device, non_blocking=True)
+                pcm = torch.empty(max(16, total), dtype=torch.uint8, device=self.device)
+                hip.flac_decode(staged, flac_total, fmeta_d[:4 * nf], nf, fmeta_d[4 * nf:4 * nf + 3 * B], B, fplan["max_channels"],
+                                fplan["frame_words"], pcm, total, fmeta_d[-1:])
+                err = flac_status_error(int(fmeta_d[-1].item()), fplan, utts)
+                if err is not None:
+                    raise err
+                staged = pcm
+                self.flac_passes += 1
             if resample:
                 wave = torch.empty(plan["wave_floats"], dtype=torch.float32, device=self.device)
                 run_resampled(self.o, plan, staged, total, meta.numpy(), meta_d, B, wave, feats, self.pad_value, self.mean64, self.std64)

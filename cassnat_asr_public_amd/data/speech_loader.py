@@ -10,7 +10,7 @@ import numpy as np
 import torch
 from torch.utils.data import DataLoader, Dataset
 
-from . import kaldi_io, wave_io
+from . import flac_io, kaldi_io, wave_io
 from .feat_op import context_feat, skip_feat
 
 
@@ -70,18 +70,30 @@ class WaveBatch(object):
     progress printing and ``first.shape[1]`` work as for a tensor; the features themselves are computed on the device, in the task's
     own process (``Fbank.packed`` / the packed reader's wave form).  ``formats``: per utterance the file's (rate, channels) - the
     views then hold the interleaved data chunks and ``frames`` count the RESAMPLED wave's frames; None: mono files at the
-    front-end's rate."""
+    front-end's rate.  ``index``: per utterance the ``flac_io.FlacIndex`` of a FLAC set - the views are then the files' uint8 frame
+    bytes, decoded on the device, and ``formats`` is always given."""
 
-    __slots__ = ("views", "frames", "utts", "shape", "dtype", "is_cuda", "splice", "formats")
+    __slots__ = ("views", "frames", "utts", "shape", "dtype", "is_cuda", "splice", "formats", "index")
 
-    def __init__(self, views, frames, num_mel, utts=None, splice=None, formats=None):
+    def __init__(self, views, frames, num_mel, utts=None, splice=None, formats=None, index=None):
         self.views, self.frames, self.utts = list(views), [int(n) for n in frames], utts
+        self.index = None if index is None else list(index)
         self.formats = None if formats is None else [(int(r), int(c)) for r, c in formats]
         self.splice = splice_triple(*splice) if splice else None
         blocks = (self.splice[0] + self.splice[1] + 1) if self.splice else 1
         self.shape = (len(self.views), max(spliced_frames(n, self.splice) for n in self.frames), blocks * int(num_mel))
         self.dtype = torch.float32
         self.is_cuda = False
+
+
+class FlacFrames(object):
+    """What a FLAC set hands out per utterance where a wave set hands out samples: ``view`` - a read-only uint8 view of the
+    memory-mapped file from its first audio frame to the end - and ``index``, the file's ``flac_io.FlacIndex``."""
+
+    __slots__ = ("view", "index")
+
+    def __init__(self, view, index):
+        self.view, self.index = view, index
 
 
 def front_end(args):
@@ -106,7 +118,7 @@ def frames_of(opts, samples):
 
 def sniff_wave_set(items, mode="auto"):
     """Is the list of (utt, spec, ...) a wave set?  Decided from EVERY entry (``wave_io.entry_kind``): all RIFF/WAVE files - True;
-    none - False (``mode`` "1": an error); a command, a WAV with a `:offset`, or WAV files mixed with anything else raise a
+    all FLAC entries (``flac_io.is_flac``) - "flac" (FLAC entries mixed with WAV files or feature matrices raise); none - False (``mode`` "1": an error); a command, a WAV with a `:offset`, or WAV files mixed with anything else raise a
     ValueError that names the utterance.  ``mode`` "0": never look."""
     mode = str(mode)
     if mode == "0":
@@ -116,14 +128,14 @@ def sniff_wave_set(items, mode="auto"):
     def kind(spec):
         spec = spec.strip()
         if spec.endswith("|"):
-            return "pipe"
+            return "flac" if flac_io.is_flac(spec) else "pipe"
         path, _, off = spec.rpartition(":")
         has_off = bool(path) and off.isdigit()
         name = path if has_off else spec
         if name not in seen:
-            seen[name] = wave_io.is_wav(name)
-        if not seen[name]:
-            return None
+            seen[name] = "wav" if wave_io.is_wav(name) else ("flac" if not has_off and flac_io.is_flac(name) else None)
+        if seen[name] != "wav":
+            return seen[name]
         return "wav_offset" if has_off else "wav"
 
     kinds = [kind(it[1]) for it in items]
@@ -131,6 +143,14 @@ def sniff_wave_set(items, mode="auto"):
         if k in ("pipe", "wav_offset"):
             wave_io.check_spec(it[1], it[0])
     n_wav = sum(1 for k in kinds if k == "wav")
+    n_flac = sum(1 for k in kinds if k == "flac")
+    if n_flac:  # a FLAC set: every entry a FLAC stream (a plain path, or the recipe's `flac -c -d -s FILE |`)
+        if n_flac != len(items):
+            odd, odd_kind = next((it, k) for it, k in zip(items, kinds) if k != "flac")
+            raise ValueError("the set mixes FLAC entries and %s: utterance %s (%s) is not a FLAC stream, utterance %s is"
+                             % ("WAV files" if odd_kind == "wav" else "feature matrices", odd[0], odd[1],
+                                next(it for it, k in zip(items, kinds) if k == "flac")[0]))
+        return "flac"
     if n_wav == 0:
         if mode == "1":
             raise ValueError("--hip_audio 1: utterance %s (%s) is not a RIFF/WAVE file" % (items[0][0], items[0][1]) if items
@@ -154,10 +174,12 @@ class SpeechDataset(Dataset):
         self.device_cmvn = False
         self.data_streams = [SingleSet(vocab, p, getattr(args, "rank", 0)) for p in data_paths]
         self._items = [it for s in self.data_streams for it in s.items]
-        if sniff_wave_set(self._items, getattr(args, "hip_audio", "auto")):
-            self._init_wave_set(args)
+        self.is_flac = False
+        found = sniff_wave_set(self._items, getattr(args, "hip_audio", "auto"))
+        if found:
+            self._init_wave_set(args, flac=found == "flac")
 
-    def _init_wave_set(self, args):
+    def _init_wave_set(self, args, flac=False):
         """A wave set: the entries are sound files, the dataset hands out (utt, int16 view, text) and the features are computed on
         the device by the consumer.  Every header is read once and checked here - format, rate and channels against what the
         front-end admits, at least one frame of the wave at the front-end's rate (``cn_resample_num_samples`` of the file's samples)
@@ -172,8 +194,16 @@ class SpeechDataset(Dataset):
         self.sample_rate, self.num_mel = float(self.fbank_opts.sample_rate), int(self.fbank_opts.num_mel)
         self.wave_frames, self.wave_formats = [], []
         own = int(round(self.sample_rate))
+        self.flac_infos = [] if flac else None  # a FLAC set: per file its path and metadata (``flac_io.Info``), read once here
         for utt, spec, _ in self._items:
-            n, rate, channels = wave_io.wave_format(spec, self.sample_rate, utt, **self.wave_admit)
+            if flac:
+                path = flac_io.flac_path(spec)
+                info = flac_io.checked(path, self.sample_rate, utt, **self.wave_admit)
+                # (a STREAMINFO total of 0 means unknown: the index says how many samples the frames hold)
+                n, rate, channels = info.total or flac_io.frame_index(path, info, utt).samples, info.rate, info.channels
+                self.flac_infos.append((path, info, n))
+            else:
+                n, rate, channels = wave_io.wave_format(spec, self.sample_rate, utt, **self.wave_admit)
             if rate != own:
                 if self.sample_rate != own:
                     raise ValueError("utterance %s (%s): %d Hz, and resampling needs an integer --sample-frequency (it is %r)"
@@ -190,7 +220,8 @@ class SpeechDataset(Dataset):
         # (a set of mono files at the front-end's rate - every set there was before the options - hands out plain sample views)
         self.wave_plain = all(f == (own, 1) for f in self.wave_formats)
         self.is_wave = True
-        self._kinds = frozenset(["WAV"])
+        self.is_flac = bool(flac)
+        self._kinds = frozenset(["FLAC" if flac else "WAV"])
 
     def _load_cmvn(self, cmvn_file):
         """Kaldi global CMVN stats: row 0 = sums (last column = frame count), row 1 = sums of squares."""
@@ -206,6 +237,10 @@ class SpeechDataset(Dataset):
 
     def __getitem__(self, idx):
         utt, spec, text = self._items[idx]
+        if self.is_flac:  # (the frames as the file holds them, with their exact index; decoded on the device)
+            path, info, _ = self.flac_infos[idx]
+            view = flac_io.audio_view(path, info)
+            return utt, FlacFrames(view, flac_io.frame_index(path, info, utt, view)), text
         if self.is_wave:  # (the samples as the file holds them; normalisation happens with the features, on the device)
             if self.wave_plain:
                 return utt, wave_io.pcm_view(spec, self.sample_rate, utt), text
@@ -268,7 +303,8 @@ class SpeechDataset(Dataset):
 
     def matrix_kinds(self):
         """The kinds of matrix this set holds (``kaldi_io.mat_kind``), from EVERY utterance's header: Kaldi mixes `CM` and `CM2`
-        inside one archive, and a table may point into archives of different kinds.  A wave set (sound files) is {"WAV"}."""
+        inside one archive, and a table may point into archives of different kinds.  A wave set (sound files) is {"WAV"}, a FLAC
+        set {"FLAC"}."""
         if getattr(self, "_kinds", None) is None:
             self._kinds = frozenset(kaldi_io.mat_kind(spec) for _, spec, _ in self._items)
         return self._kinds
@@ -316,6 +352,7 @@ def collate_waves(batch, padding_idx=0, opts=None, splice=None, formats=None):
     features would stand (no GPU is touched here: a loader worker process may run it).  With a ``splice`` triple the ratios are the
     spliced frame counts' (``spliced_frames``).  ``formats``: {utt: (rate, channels)} of a set that holds other files than mono ones
     at the front-end's rate (their samples are the interleaved data chunks; the frames are those of the resampled wave)."""
+    index = None
     if formats is None:
         frames, fmts = [frames_of(opts, int(x[1].shape[0])) for x in batch], None
     else:
@@ -323,7 +360,13 @@ def collate_waves(batch, padding_idx=0, opts=None, splice=None, formats=None):
 
         own = int(round(float(opts.sample_rate)))
         fmts = [formats[x[0]] for x in batch]
-        frames = [frames_of(opts, hip.resample_num_samples(r, own, int(x[1].shape[0]) // c)) for x, (r, c) in zip(batch, fmts)]
+        if isinstance(batch[0][1], FlacFrames):  # a FLAC set: the index rides beside the formats, the sample counts come from it
+            index = [x[1].index for x in batch]
+            batch = [(x[0], x[1].view, x[2]) for x in batch]
+            per = [ix.samples for ix in index]
+        else:
+            per = [int(x[1].shape[0]) // c for x, (r, c) in zip(batch, fmts)]
+        frames = [frames_of(opts, hip.resample_num_samples(r, own, n)) for n, (r, c) in zip(per, fmts)]
     n_out = [spliced_frames(n, splice) for n in frames]
     t_max = max(n_out)
     l_max = max(len(x[2]) for x in batch)
@@ -336,7 +379,7 @@ def collate_waves(batch, padding_idx=0, opts=None, splice=None, formats=None):
         ratios[b] = n_out[b] / t_max
         sizes[b] = len(text) - 2
         utts.append(utt)
-    return utts, WaveBatch([x[1] for x in batch], frames, opts.num_mel, utts, splice=splice, formats=fmts), texts, ratios, sizes
+    return utts, WaveBatch([x[1] for x in batch], frames, opts.num_mel, utts, splice=splice, formats=fmts, index=index), texts, ratios, sizes
 
 
 def _one_thread_worker(_worker_id):
@@ -358,7 +401,7 @@ class SpeechDataLoader(DataLoader):
         # (83 ms per 9-MB batch measured): the loader's pinning thread moves them into page-locked memory first
         super().__init__(dataset, batch_sampler=batches, num_workers=num_workers,
                          collate_fn=(functools.partial(collate_waves, padding_idx=padding_idx, opts=dataset.fbank_opts, splice=dataset.splice(),
-                                                       formats=None if dataset.wave_plain else
+                                                       formats=None if dataset.wave_plain and not getattr(dataset, "is_flac", False) else
                                                        {it[0]: f for it, f in zip(dataset._items, dataset.wave_formats)})
                                      if getattr(dataset, "is_wave", False) else functools.partial(collate, padding_idx=padding_idx)),
                          pin_memory=bool(num_workers > 0 and torch.cuda.is_available()),

@@ -7,7 +7,8 @@ interleaved channels, of which one is read.  The chunks of
 the file are walked (anything may sit before `data`: `LIST`, `fact`, ...; an odd-sized chunk is followed by a pad byte),
 `WAVE_FORMAT_EXTENSIBLE` is accepted with the PCM sub-format, and a `data` size of 0 or 0xFFFFFFFF means "to the end of the file", as
 Kaldi reads streamed files.  Everything else raises a ValueError that names the utterance and the reason; an `.scp` entry that is a
-command (`... |`) or carries a `:offset` is refused too - no subprocess is ever started.
+command (`... |`) or carries a `:offset` is refused too - no subprocess is ever started (the one command form that is taken,
+`flac -c -d -s FILE |` on a FLAC stream, is read directly: ``data.flac_io``).
 
 ``pcm_view`` hands out a read-only '<i2' view of the samples inside a memory map of the file.  The map lives exactly as long as
 the view: nothing is cached here (a test set is thousands of files), the reader drops the views of a pass once it is staged.
@@ -30,8 +31,12 @@ def check_spec(spec, utt=None):
     """An `.scp` entry of a wave set must be a plain path: a command or a `:offset` raises."""
     spec = spec.strip()
     if spec.endswith("|"):
-        raise ValueError("%s: the entry is a command (ends in '|'): piped wav.scp entries are not read, no subprocess is started"
-                         % _who(spec, utt))
+        from . import flac_io
+
+        if flac_io.is_flac(spec):  # (the recipe's `flac -c -d -s FILE |` on a FLAC stream: the file is read directly)
+            return spec
+        raise ValueError("%s: the entry is a command (ends in '|'): piped wav.scp entries are not read, no subprocess is started "
+                         "(only `flac -c -d -s FILE |` is taken, by reading FILE directly, when FILE is a FLAC stream)" % _who(spec, utt))
     path, _, off = spec.rpartition(":")
     if path and off.isdigit():
         raise ValueError("%s: the entry carries a :offset, a wave set names whole files" % _who(spec, utt))

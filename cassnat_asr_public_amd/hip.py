@@ -242,6 +242,14 @@ def lib(flavour=None):
     L.cn_resample_table.argtypes = [C.c_int32, C.c_int32] + [C.POINTER(C.c_int32)] * 3 + [C.c_void_p] * 3 + [C.c_int64]
     L.cn_op_wave_resample.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_int64] + [C.c_void_p] * 6 + [C.c_int32, C.c_void_p, C.c_int32,
                                                                                                       C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.cn_host_flac_index.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64] + [C.POINTER(C.c_int64)] * 3
+    L.cn_host_flac_crc16.argtypes = [C.c_char_p, C.c_int64]
+    L.cn_flac_frame_words.argtypes = [C.c_int32, C.c_int32]
+    L.cn_flac_frame_words.restype = C.c_int64
+    L.cn_flac_scratch_bytes.argtypes = [C.c_int32, C.c_int64]
+    L.cn_flac_scratch_bytes.restype = C.c_int64
+    L.cn_op_flac_decode.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p,
+                                    C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     L.cn_esa_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(CnDecodeOpts), C.c_void_p]
     L.cn_esa_sample.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.POINTER(CnDecodeOpts), C.c_void_p,
                                 C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_void_p]
@@ -444,6 +452,67 @@ def wave_resample(in_rate, out_rate, staged, staged_bytes, off, samples, channel
                                     _ptr(channel), channels_host.ctypes.data_as(C.c_void_p), channel_host.ctypes.data_as(C.c_void_p), utts,
                                     _ptr(rows), n, int(max_out), _ptr(wave), _ptr(out_off), current_stream()), "cn_op_wave_resample")
     return wave
+
+
+class FlacIndexError(ValueError):
+    """``flac_index`` refused a stream: ``code`` is cn_host_flac_index's (-2 no chain of frames, -3 a frame unlike STREAMINFO, -6 out of
+    range), ``offset`` the byte offset it names."""
+
+    def __init__(self, msg, code, offset):
+        super().__init__(msg)
+        self.code, self.offset = code, offset
+
+
+def flac_index(audio, rate, channels, bits=16, frames_hint=0):
+    """The exact frame index of a FLAC stream's audio bytes (cn_host_flac_index; host only, GIL-free): ``audio`` a C-contiguous uint8
+    array from the first frame to the end of the file -> (int32 (frames, 3): byte offset, byte length, first sample; total samples).
+    A stream in which no chain of frames with matching CRC-16s reaches the end, or a frame of which differs from (rate, channels,
+    bits), raises ``FlacIndexError``."""
+    assert audio.dtype == np.uint8 and audio.ndim == 1 and audio.flags.c_contiguous
+    L = lib()
+    nf, ns, bad = C.c_int64(), C.c_int64(), C.c_int64()
+    cap = int(frames_hint) + 16 if frames_hint else audio.shape[0] // 256 + 16
+    while True:
+        out = np.empty((cap, 3), np.int32)
+        rc = L.cn_host_flac_index(C.c_void_p(audio.ctypes.data), audio.shape[0], int(rate), int(channels), int(bits), C.c_void_p(out.ctypes.data), cap,
+                                  C.byref(nf), C.byref(ns), C.byref(bad))
+        if rc != -5:
+            break
+        cap = max(2 * cap, audio.shape[0] // 9 + 1) if cap < audio.shape[0] // 9 + 1 else cap * 2  # (a frame takes at least 9 bytes)
+    if rc != 0:
+        raise FlacIndexError(L.cn_last_error().decode(errors="replace").replace("cn_host_flac_index: ", ""), rc, bad.value)
+    return out[:nf.value].copy(), int(ns.value)
+
+
+def flac_crc16(data):
+    """CRC-16 of a FLAC frame's bytes (cn_host_flac_crc16; host only)."""
+    data = bytes(data)
+    return int(lib().cn_host_flac_crc16(data, len(data)))
+
+
+def flac_frame_words(channels, block_size):
+    """Scratch words of one frame in ``flac_decode`` (cn_flac_frame_words)."""
+    return int(lib().cn_flac_frame_words(int(channels), int(block_size)))
+
+
+def flac_scratch_bytes(frames, frame_words):
+    return int(lib().cn_flac_scratch_bytes(int(frames), int(frame_words)))
+
+
+def flac_decode(staged, staged_bytes, table, frames, utt, utts, max_channels, frame_words, pcm, pcm_bytes, status, scratch=None):
+    """FLAC frames -> interleaved int16 PCM on the device (cn_op_flac_decode), on the current stream: ``staged`` uint8 CUDA bytes of
+    the files, ``table`` int32 CUDA (frames, 4) - byte offset, byte length, utterance, first sample -, ``utt`` int32 CUDA (3, utts) -
+    channels, samples per channel, byte offset of the PCM in ``pcm`` (uint8 CUDA) -, ``status`` one int32 CUDA word: 0 after a clean
+    pass, else a failed frame's index + 1.  ``scratch``: a CUDA buffer of ``flac_scratch_bytes`` bytes - None: the call allocates
+    one and waits for the stream."""
+    assert staged.is_contiguous() and staged.element_size() == 1 and 0 <= int(staged_bytes) <= staged.numel()
+    assert table.is_contiguous() and table.element_size() == 4 and table.numel() >= 4 * int(frames)
+    assert utt.is_contiguous() and utt.element_size() == 4 and utt.numel() >= 3 * int(utts)
+    assert pcm.is_contiguous() and 0 <= int(pcm_bytes) <= pcm.numel() * pcm.element_size() and status.element_size() == 4
+    check(lib().cn_op_flac_decode(_ptr(staged), int(staged_bytes), _ptr(table), int(frames), _ptr(utt), int(utts), int(max_channels),
+                                  int(frame_words), _ptr(pcm), int(pcm_bytes), _ptr(status), _ptr(scratch),
+                                  0 if scratch is None else scratch.numel() * scratch.element_size(), current_stream()), "cn_op_flac_decode")
+    return pcm
 
 
 class Engine:

@@ -85,7 +85,7 @@ class _Pass:
     """One engine pass in flight: what is needed to hand its results out - or to decode it again when the predicted row
     count turns out too small."""
 
-    __slots__ = ("items", "first", "feats", "ratio", "rows", "frames", "ticket", "u_hint", "rec", "recs", "ev", "tp")
+    __slots__ = ("items", "first", "feats", "ratio", "rows", "frames", "ticket", "u_hint", "rec", "recs", "ev", "tp", "slot")
 
 
 class DecodePipelines(PackedStaging):
@@ -120,6 +120,7 @@ class DecodePipelines(PackedStaging):
         self._guarded = getattr(model, "hip_precision", "") in ("fp16", "bf16x3")  # (engines with a feature-range guard: Engine.check_range)
         self.copy_threads = max(0, int(copy_threads))
         self._packed = [{} for _ in range(max(1, int(n_pipelines)))]  # per pipeline: packed-pass staging buffers by (form, slot)
+        self._flac_checks = [{} for _ in range(max(1, int(n_pipelines)))]  # per pipeline and slot: the status check of a FLAC pass in flight
         self.cmvn = None if cmvn is None else (np.ascontiguousarray(cmvn[0], dtype=np.float64), np.ascontiguousarray(cmvn[1], dtype=np.float64))
         self._cmvn_dev = {}
         self.n = max(1, int(n_pipelines))
@@ -157,7 +158,7 @@ class DecodePipelines(PackedStaging):
         self._rows_lock = threading.Lock()
         self._stats_lock = threading.Lock()
         self.timeline = None  # a list: the workers and the consumer append (label, pipeline, perf_counter) - bench.py --host-timeline
-        self.stats = {"passes": 0, "batches": 0, "predicted": 0, "missed": 0, "merged_ragged": 0, "compressed_passes": 0, "wave_passes": 0, "resampled_passes": 0, "spliced_passes": 0,
+        self.stats = {"passes": 0, "batches": 0, "predicted": 0, "missed": 0, "merged_ragged": 0, "compressed_passes": 0, "wave_passes": 0, "flac_passes": 0, "resampled_passes": 0, "spliced_passes": 0,
                       # host seconds of the worker threads, by what they were doing (summed over the pipelines)
                       "s_take": 0.0, "s_stage": 0.0, "s_launch": 0.0, "s_retire_wait": 0.0}
 
@@ -375,6 +376,9 @@ class DecodePipelines(PackedStaging):
             p.ev.synchronize()
             self._bump("s_retire_wait", time.perf_counter() - t_)
             self._mark("drained", k)
+        flac_check = self._flac_checks[k].pop(getattr(p, "slot", None), None)
+        if flac_check is not None:  # a FLAC pass: a frame that did not decode on the device raises, naming utterance and frame
+            flac_check()
         if self._guarded:
             self.engines[k].check_range("DecodePipelines")  # (features beyond the engine's operand range: the pass is not handed out)
         if p.ticket is not None and p.ticket >= 0:
@@ -421,6 +425,7 @@ class DecodePipelines(PackedStaging):
                 p.rows = [int(x[0].shape[0]) for x in p.items]
                 p.frames = [int(x[0].shape[1]) for x in p.items]
                 p.ticket = None
+                p.slot = n_pass & 1
                 t_ = time.perf_counter()
                 if len(p.items) == 1 and self.cmvn is None and not isinstance(p.items[0][0], PackedBatch):  # (raw / packed batches go through the staging buffer, alone or not)
                     p.feats, p.ratio = p.items[0][0], p.items[0][1]

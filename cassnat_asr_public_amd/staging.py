@@ -38,6 +38,12 @@ class PackedBatch:
     is the one that is read, and ``lens`` count the frames of the wave at the front-end's rate: ``hip.wave_resample`` writes that
     wave on the device, ``hip.fbank_packed_f32`` reads it.
 
+    The FLAC form (``from_waves(..., index=...)``; ``kinds`` is the string "flac") keeps per utterance a read-only uint8 view of its
+    FLAC file from the first audio frame on and, in ``index``, the file's exact frame index (``data.flac_io.FlacIndex``); ``formats``
+    are STREAMINFO's (rate, channels).  The pipelines stage the frames as they are - about half the bytes of the 16-bit PCM - and the
+    pass's frame table; ``hip.flac_decode`` writes the interleaved int16 PCM into a scratch of the slot that is laid out as staged WAV
+    data chunks are, and the wave form's launches read that.
+
     SPLICING (``splice`` = (left, right, skip), every form): the set splices and / or skips frames (the recipes' decode YAMLs:
     0 / 2 / 1).  ``lens`` stay the SOURCE rows and ``source_shape`` the unspliced (B, longest source count, F0); ``shape`` is what the
     dataset's general host path collates - (B, longest n_out, (left + right + 1) * F0) with n_out = ``out_lens`` = ceil(rows / skip) -
@@ -45,18 +51,18 @@ class PackedBatch:
     CMVN in float64, zero rows up to a multiple of skip, ``feat_op.context_feat``, ``feat_op.skip_feat``, then padding): the
     definition ``hip.splice_rows`` is held to."""
 
-    __slots__ = ("views", "lens", "shape", "dtype", "is_cuda", "kinds", "utts", "splice", "source_shape", "out_lens", "formats", "channel")
+    __slots__ = ("views", "lens", "shape", "dtype", "is_cuda", "kinds", "utts", "splice", "source_shape", "out_lens", "formats", "channel", "index")
 
     def __init__(self, views, utts=None, splice=None):
         self._init(views, None, [int(v.shape[0]) for v in views], None, utts, splice)
 
-    def _init(self, views, kinds, lens, cols, utts, splice, formats=None, channel=-1):
+    def _init(self, views, kinds, lens, cols, utts, splice, formats=None, channel=-1, index=None):
         """Every slot, for the three constructors: ``lens`` are the source rows (frames), ``cols`` the unspliced feature width (None:
         the width of the views)."""
         from .data.speech_loader import splice_triple, spliced_frames
 
         self.views, self.kinds, self.lens, self.utts = views, kinds, lens, utts
-        self.formats, self.channel = formats, channel
+        self.formats, self.channel, self.index = formats, channel, index
         self.dtype = torch.float32
         self.is_cuda = False
         self.splice = splice_triple(*splice) if splice else None
@@ -107,19 +113,36 @@ class PackedBatch:
         return cls.__new__(cls)._init(views, kinds, lens, want_cols, utts, splice)
 
     @classmethod
-    def from_waves(cls, views, frames, num_mel, utts=None, splice=None, formats=None, channel=-1):
+    def from_waves(cls, views, frames, num_mel, utts=None, splice=None, formats=None, channel=-1, index=None):
         """``views``: one '<i2', one-dimensional, C-contiguous array of samples per utterance; ``frames``: their frame counts under
         the front-end's options (``Fbank.num_frames``).  Anything else - and an utterance of zero frames - raises a ValueError that
         names the utterance.  ``formats``: per utterance (rate, channels) of its file - the view is then the interleaved data chunk
         (``wave_io.pcm_frames``), ``frames`` count the wave at the front-end's rate and ``channel`` (the front-end's `--channel`)
-        must name a channel of every file that has more than one; None: mono files at the front-end's rate."""
+        must name a channel of every file that has more than one; None: mono files at the front-end's rate.
+        ``index``: per utterance the ``flac_io.FlacIndex`` of a FLAC file - the views are then one-dimensional C-contiguous uint8
+        arrays, the file's frames, ``formats`` (required) what STREAMINFO says, and every frame of the index must lie inside its view."""
         if not views:
             raise ValueError("PackedBatch: an empty batch")
         if len(frames) != len(views):
             raise ValueError("PackedBatch: %d frame counts for %d utterances" % (len(frames), len(views)))
         if formats is not None and len(formats) != len(views):
             raise ValueError("PackedBatch: %d (rate, channels) pairs for %d utterances" % (len(formats), len(views)))
+        if index is not None and (formats is None or len(index) != len(views)):
+            raise ValueError("PackedBatch: a FLAC batch needs one frame index and one (rate, channels) pair per utterance")
         for b, v in enumerate(views):
+            if index is not None:
+                fr = np.asarray(index[b].frames)
+                if not isinstance(v, np.ndarray) or v.dtype != np.uint8 or v.ndim != 1 or not v.flags.c_contiguous:
+                    raise ValueError("PackedBatch: %s: the FLAC frames must be a one-dimensional C-contiguous uint8 array" % _name(utts, b))
+                if (fr.ndim != 2 or fr.shape[1] != 3 or fr.shape[0] < 1 or fr.dtype != np.int32 or int(fr[:, 0].min()) < 0 or int(fr[:, 1].min()) < 1
+                        or int((fr[:, 0].astype(np.int64) + fr[:, 1]).max()) > v.shape[0] or int(index[b].samples) < 1):
+                    raise ValueError("PackedBatch: %s: the frame index does not lie inside the %d bytes of the file's frames" % (_name(utts, b), v.shape[0]))
+                if int(frames[b]) < 1:
+                    raise ValueError("PackedBatch: %s: %d samples give no frame" % (_name(utts, b), int(index[b].samples)))
+                rate, chans = int(formats[b][0]), int(formats[b][1])
+                if rate < 1 or not 1 <= chans <= 8 or (chans > 1 and not 0 <= int(channel) < chans):
+                    raise ValueError("PackedBatch: %s: (rate, channels) = (%d, %d), channel %d" % (_name(utts, b), rate, chans, int(channel)))
+                continue
             if not isinstance(v, np.ndarray) or v.dtype != np.dtype("<i2") or v.ndim != 1 or not v.flags.c_contiguous:
                 raise ValueError("PackedBatch: %s: the samples must be a one-dimensional C-contiguous '<i2' array (got %s)"
                                  % (_name(utts, b), "%s %s" % (getattr(v, "dtype", type(v).__name__), getattr(v, "shape", ""))))
@@ -131,8 +154,9 @@ class PackedBatch:
                     raise ValueError("PackedBatch: %s: %d int16 values at (rate, channels) = (%d, %d)" % (_name(utts, b), v.shape[0], rate, chans))
                 if chans > 1 and not 0 <= int(channel) < chans:
                     raise ValueError("PackedBatch: %s: %d channels, channel %d is not one of them" % (_name(utts, b), chans, int(channel)))
-        return cls.__new__(cls)._init(list(views), "wave", [int(n) for n in frames], num_mel, utts, splice,
-                                      None if formats is None else [(int(r), int(c)) for r, c in formats], int(channel))
+        return cls.__new__(cls)._init(list(views), "wave" if index is None else "flac", [int(n) for n in frames], num_mel, utts, splice,
+                                      None if formats is None else [(int(r), int(c)) for r, c in formats], int(channel),
+                                      None if index is None else list(index))
 
     def ratios(self):
         """collate's ``ratios[b] = feat.shape[0] / t_max``: the Python (double) quotient rounded to float32 (of the rows the dataset
@@ -144,7 +168,7 @@ class PackedBatch:
         """The utterances' float32 matrices on the host (the compressed form decompressed by ``kaldi_io.decompress``)."""
         if self.kinds is None:
             return self.views
-        if self.kinds == "wave":
+        if self.kinds in ("wave", "flac"):
             raise NotImplementedError("PackedBatch: the wave form holds samples - the features exist on the device only (hip.fbank_packed)")
         from .data.kaldi_io import decompress
 
@@ -153,7 +177,7 @@ class PackedBatch:
 
     def padded(self, pad=0.0, cmvn=None):
         """The collated tensor itself (host): what the packed path must reproduce; used by the CPU rehearsal and the tests."""
-        if self.kinds == "wave":
+        if self.kinds in ("wave", "flac"):
             raise NotImplementedError("PackedBatch: the wave form holds samples - the features exist on the device only (hip.fbank_packed)")
         out = np.full(self.shape, float(pad), np.float32)
         if self.splice is not None:
@@ -168,9 +192,9 @@ class PackedBatch:
 
 
 def _form(f):
-    """The staging form of a batch: None (a tensor, or float32 archive rows), "compressed" or "wave"."""
+    """The staging form of a batch: None (a tensor, or float32 archive rows), "compressed", "wave" or "flac"."""
     kinds = getattr(f, "kinds", None)
-    return None if kinds is None else ("wave" if isinstance(kinds, str) else "compressed")
+    return None if kinds is None else (kinds if isinstance(kinds, str) else "compressed")
 
 
 def _byte_layout(views, what, **rest):
@@ -225,7 +249,7 @@ class PackedStaging:
         lay.cap = max(lay.total, area * F0 + utts * (32 + 8 * F0))
         return lay
 
-    def _wave_form(self, batches, views, lens, area, utts, pad):
+    def _wave_form(self, batches, views, lens, area, utts, pad, pcm=None):
         """int16 samples as the sound files hold them; the second column holds SAMPLES and ``hip.fbank_packed`` computes the padded
         features, normalised with the pipelines' statistics.  Sized in bytes: a frame shift of samples is 320 bytes at the default
         options, what 80 float32 features take.
@@ -234,7 +258,11 @@ class PackedStaging:
         in the same buffers - sized in the bytes the files hold -, and one ``hip.wave_resample`` per distinct rate writes the chosen
         channel at the front-end's rate into the slot's float32 wave scratch, which ``hip.fbank_packed_f32`` reads
         (``data.fbank.plan_resample`` / ``run_resampled``; the resampler's per-utterance arrays travel in a small DMA of their own).
-        A pass that needs neither is the int16 pass, launch for launch."""
+        A pass that needs neither is the int16 pass, launch for launch.
+
+        ``pcm`` (the FLAC form): the samples are not the staged bytes but what ``hip.flac_decode`` wrote - a dict with the buffer's
+        key in the slot (``src``), the utterances' byte ``offs`` and int16 counts (``lengths``) in it, its ``total`` bytes and
+        ``cols`` (bufs -> the two device columns): the same launches then read that buffer."""
         from .data.fbank import RESAMPLE_META, plain_formats, plan_resample, run_resampled
 
         fb = self.fbank
@@ -249,28 +277,94 @@ class PackedStaging:
         resample = not plain_formats(fb.sample_rate, rates, chans)
         if resample and len(set(b.channel for b in batches if b.formats is not None)) > 1:
             raise ValueError("DecodePipelines: a pass mixes wave batches that read different channels")
-        samples = [v.shape[0] for v in views]
+        samples = [v.shape[0] for v in views] if pcm is None else pcm["lengths"]
 
         def produce(bufs, m, out, stats):
+            src, total, offs = (bufs["dev"], lay.total, lay.offs) if pcm is None else (bufs[pcm["src"]], pcm["total"], pcm["offs"])
+            if pcm is not None:
+                m = pcm["cols"](bufs)
             if not resample:
-                return hip.fbank_packed(fb, bufs["dev"], lay.total, m[0], m[1], out, pad, *stats)
+                return hip.fbank_packed(fb, src, total, m[0], m[1], out, pad, *stats)
             U, dev_ = bufs["utts"], bufs["dev"].device
             if bufs.get("rs_h") is None:
                 bufs["rs_h"] = torch.empty(RESAMPLE_META * U, dtype=torch.int32, pin_memory=True)
                 bufs["rs_d"] = torch.empty(RESAMPLE_META * U, dtype=torch.int32, device=dev_)
             channel = next(b.channel for b in batches if b.formats is not None)
-            plan = plan_resample(bufs["rs_h"].numpy(), U, fb, lay.offs, samples, rates, chans, channel,
+            plan = plan_resample(bufs["rs_h"].numpy(), U, fb, offs, samples, rates, chans, channel,
                                  [u for b in batches for u in (b.utts or [None] * len(b.views))])
             if bufs.get("wave") is None or bufs["wave"].numel() < plan["wave_floats"]:
                 bufs["wave"] = torch.empty(max(plan["wave_floats"], bufs["cap"] // 2), dtype=torch.float32, device=dev_)
             bufs["rs_d"].copy_(bufs["rs_h"], non_blocking=True)
-            run_resampled(fb, plan, bufs["dev"], lay.total, bufs["rs_h"].numpy(), bufs["rs_d"], U, bufs["wave"], out, pad, *stats)
+            run_resampled(fb, plan, src, total, bufs["rs_h"].numpy(), bufs["rs_d"], U, bufs["wave"], out, pad, *stats)
             self._bump("resampled_passes", 1)
 
         lay = _byte_layout(views, "sample", count="wave_passes", col1=samples, col3=None, produce=produce)
         shift = max(1, int(fb.sample_rate * 0.001 * fb.frame_shift_ms))
         flen = int(fb.sample_rate * 0.001 * fb.frame_length_ms)
         lay.cap = max(lay.total, 2 * area * shift + utts * (2 * flen + 16))
+        return lay
+
+    def _flac_form(self, batches, views, lens, area, utts, pad):
+        """FLAC frames as the files hold them - about half the bytes of the 16-bit PCM - staged by the same gather and single DMA.
+        The pass's frame table (``data.fbank.plan_flac``: per frame its byte offset, length, utterance and first sample - about 16
+        bytes per 4096 samples - then per utterance channels, samples and the byte offset of its PCM, then the status word) follows
+        in a DMA of its own; ``hip.flac_decode`` writes the interleaved int16 PCM into the slot's ``pcm`` scratch - sized from the
+        headers, grown as ``bufs["wave"]`` is - at 16-byte-aligned offsets, exactly the staged data chunks of WAV files holding the
+        same samples, and the wave form's ``produce`` (the resampled branch included) runs on that buffer.  The status word comes
+        back with the results: ``_flac_checks`` holds, per slot, the check the pipelines make when the pass has drained."""
+        from .data.fbank import flac_status_error, plan_flac
+
+        if any(b.index is None for b in batches):
+            raise ValueError("DecodePipelines: a pass mixes FLAC batches with another form of packed batch")
+        chans = [c for b in batches for _, c in b.formats]
+        names = [u for b in batches for u in (b.utts or [None] * len(b.views))]
+        state = {}
+
+        def cols(bufs):
+            U, nf = bufs["utts"], state["nf"]
+            return bufs["fl_d"][4 * nf + 2 * U:4 * nf + 3 * U], bufs["fl_d"][4 * nf + 3 * U + 1:4 * nf + 4 * U + 1]  # (PCM offsets, int16 counts)
+
+        def produce(bufs, m, out, stats):
+            U, dev_, B = bufs["utts"], bufs["dev"].device, len(views)
+            nf = state["nf"] = plan["table"].shape[0]
+            need = 4 * nf + 4 * U + 1  # the table; channels, samples, PCM offsets; the status word; the int16 counts
+            if bufs.get("fl_h") is None or bufs["fl_h"].numel() < need:
+                bufs["fl_h"] = torch.empty(2 * need, dtype=torch.int32, pin_memory=True)
+                bufs["fl_d"] = torch.empty(2 * need, dtype=torch.int32, device=dev_)
+                bufs["fl_back"] = torch.empty(1, dtype=torch.int32, pin_memory=True)
+            fv = bufs["fl_h"].numpy()
+            fv[:4 * nf] = plan["table"].ravel()
+            for c in range(3):
+                fv[4 * nf + c * U:4 * nf + c * U + B] = plan["utt"][c]
+            fv[4 * nf + 3 * U] = 0
+            fv[4 * nf + 3 * U + 1:4 * nf + 3 * U + 1 + B] = plan["lengths"]
+            bufs["fl_d"][:need].copy_(bufs["fl_h"][:need], non_blocking=True)
+            if bufs.get("pcm") is None or bufs["pcm"].numel() < plan["pcm_bytes"]:
+                bufs["pcm"] = torch.empty(max(plan["pcm_bytes"], 2 * bufs["cap"]), dtype=torch.uint8, device=dev_)
+            scratch = hip.flac_scratch_bytes(nf, plan["frame_words"])
+            if bufs.get("fl_scratch") is None or bufs["fl_scratch"].numel() < scratch:
+                bufs["fl_scratch"] = torch.empty(scratch + scratch // 4, dtype=torch.uint8, device=dev_)
+            status = bufs["fl_d"][4 * nf + 3 * U:4 * nf + 3 * U + 1]
+            hip.flac_decode(bufs["dev"], lay.total, bufs["fl_d"][:4 * nf], nf, bufs["fl_d"][4 * nf:4 * nf + 3 * U], U, plan["max_channels"],
+                            plan["frame_words"], bufs["pcm"], plan["pcm_bytes"], status, bufs["fl_scratch"])
+            bufs["fl_back"].copy_(status, non_blocking=True)
+            back = bufs["fl_back"]
+
+            def check():
+                err = flac_status_error(int(back[0]), plan, names)
+                if err is not None:
+                    raise err
+
+            state["check"] = check
+            wave.produce(bufs, m, out, stats)
+            self._bump("wave_passes", 1)
+
+        lay = _byte_layout(views, "FLAC", count="flac_passes", col1=[v.shape[0] for v in views], col3=None, produce=produce)
+        plan = plan_flac([ix for b in batches for ix in b.index], lay.offs, chans)
+        wave = self._wave_form(batches, views, lens, area, utts, pad,
+                               pcm={"src": "pcm", "offs": plan["pcm_offs"], "lengths": plan["lengths"], "total": plan["pcm_bytes"], "cols": cols})
+        lay.cap = max(lay.total, wave.cap // 2)
+        lay.state = state
         return lay
 
     def _stage_packed(self, k, slot, items, pad):
@@ -289,9 +383,9 @@ class PackedStaging:
         forms = set(_form(b) for b in batches)
         if len(set(b.splice for b in batches)) > 1:
             raise ValueError("DecodePipelines: a pass mixes packed batches of different splice triples")
-        if "wave" in forms:
+        if "wave" in forms or "flac" in forms:
             if len(forms) > 1:
-                raise ValueError("DecodePipelines: a pass mixes wave batches with another form of packed batch")
+                raise ValueError("DecodePipelines: a pass mixes %s batches with another form of packed batch" % ("wave" if "flac" not in forms else "FLAC"))
             if not on_gpu:
                 raise NotImplementedError("DecodePipelines: the wave form has no CPU rehearsal (the fbank front-end runs on the device only)")
         if not on_gpu:  # CPU rehearsal of the host logic: the collated tensors themselves
@@ -307,7 +401,7 @@ class PackedStaging:
         lens = [n for b in batches for n in b.lens]
         area = self.max_batch * self.frames_cap
         want_utts = max(rows, self.max_utts)
-        lay = {None: self._rows_form, "compressed": self._compressed_form, "wave": self._wave_form}[form](
+        lay = {None: self._rows_form, "compressed": self._compressed_form, "wave": self._wave_form, "flac": self._flac_form}[form](
             batches, views, lens, area * (splice[2] if splice else 1), want_utts, pad)
         ncols = 3 + (lay.col3 is not None)
         # the slot's buffers, per form: allocated at the engines' area, again only for a pass that does not fit or another width
@@ -345,6 +439,8 @@ class PackedStaging:
             self._bump("spliced_passes", 1)
         if lay.count:
             self._bump(lay.count, 1)
+        if form == "flac":  # (the decoder's status word travels back behind the pass: checked when it has drained)
+            self._flac_checks[k][slot] = lay.state["check"]
         return feats, m[2][:rows].view(torch.float32)
 
     def _splice_scratch(self, bufs, batches, rows, F0, splice, dev_):

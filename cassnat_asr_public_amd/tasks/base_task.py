@@ -78,4 +78,5 @@ class BaseTask(object):
             self._fbank = fb
         if feats.formats is None:
             return fb.packed(feats.views, utts=feats.utts)
-        return fb.packed(feats.views, utts=feats.utts, rates=[r for r, _ in feats.formats], channels=[c for _, c in feats.formats])
+        return fb.packed(feats.views, utts=feats.utts, rates=[r for r, _ in feats.formats], channels=[c for _, c in feats.formats],
+                         flac=feats.index)

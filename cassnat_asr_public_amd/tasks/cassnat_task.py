@@ -114,9 +114,13 @@ class CassNATTask(BaseTask):
             if all(utt in table for utt, _ in entries):
                 return np.array([table[utt] for utt, _ in entries])
         if need:
-            from ..data import speech_loader, wave_io
+            from ..data import flac_io, speech_loader, wave_io
 
-            if speech_loader.sniff_wave_set(entries, getattr(args, "hip_audio", "auto")):  # audio input: from the WAV headers
+            found = speech_loader.sniff_wave_set(entries, getattr(args, "hip_audio", "auto"))
+            if found == "flac":  # FLAC input: the sample counts of STREAMINFO (at the file's own rate: the lengths only order the list)
+                opts = speech_loader.front_end_options(args)
+                return np.array([speech_loader.frames_of(opts, flac_io.num_samples(flac_io.flac_path(spec), None, utt)) for utt, spec in entries])
+            if found:  # audio input: from the WAV headers
                 opts = speech_loader.front_end_options(args)
                 return np.array([speech_loader.frames_of(opts, wave_io.num_samples(spec, opts.sample_rate, utt)) for utt, spec in entries])
             return np.array([kaldi_io.mat_rows(spec) for _, spec in entries])
@@ -310,14 +314,23 @@ class CassNATTask(BaseTask):
         stats0 = dict(pipes.stats)
         meta, frames, i, end = {}, 0, -1, time.time()
 
+        flac_pool = None
+        if getattr(ds, "is_flac", False):
+            from concurrent.futures import ThreadPoolExecutor
+
+            flac_pool = ThreadPoolExecutor(max_workers=4, thread_name_prefix="flac-index")
+
         def batches():
             if wave or packed:  # the loader's batches (same utterances, same order) as views into the memory maps of the sound files
                 for j, idx in enumerate(self.test_loader.batch_sampler):  # / of the archives (a map lives as long as its pass)
                     if wave:
-                        got = [ds[i] for i in idx]
-                        pb = PackedBatch.from_waves([v for _, v, _ in got], [ds.wave_frames[i] for i in idx], feat_dim, utts=[u for u, _, _ in got],
-                                                    splice=splice, formats=None if ds.wave_plain else [ds.wave_formats[i] for i in idx],
-                                                    channel=ds.wave_admit["channel"])
+                        flac = getattr(ds, "is_flac", False)  # (a FLAC set hands out the files' frames and their index)
+                        # (indexing a FLAC file is one CRC-16 pass over its bytes inside a GIL-free call: the batch's files side by side)
+                        got = list(flac_pool.map(ds.__getitem__, idx)) if flac else [ds[i] for i in idx]
+                        pb = PackedBatch.from_waves([v.view if flac else v for _, v, _ in got], [ds.wave_frames[i] for i in idx], feat_dim,
+                                                    utts=[u for u, _, _ in got], splice=splice,
+                                                    formats=None if ds.wave_plain and not flac else [ds.wave_formats[i] for i in idx],
+                                                    channel=ds.wave_admit["channel"], index=[v.index for _, v, _ in got] if flac else None)
                     else:
                         got = [ds._items[i] for i in idx]
                         # (every header is checked against the path chosen above and the set's feature dimension: a contradiction
@@ -333,16 +346,20 @@ class CassNATTask(BaseTask):
                 yield feats, feat_sizes, j
 
         table = np.array([self.vocab.index2word[k] for k in range(self.vocab.n_words)], dtype=object)
-        for i, (toks, lens), _scores in pipes.decode(batches(), args, sos=sos, as_lists=False):
-            utt_list, labels, nfr, lab_width = meta.pop(i)
-            frames += nfr
-            words = hyps_to_words_batch(toks, lens, self.vocab, args.padding_idx, table)
-            for utt, w, n in zip(utt_list, words, lens.tolist()):
-                results[utt] = (w, n - lab_width)
-            batch_time.update(time.time() - end)
-            end = time.time()
-            if i % args.print_freq == 0 and self.rank == 0:
-                progress.print(i)
+        try:
+            for i, (toks, lens), _scores in pipes.decode(batches(), args, sos=sos, as_lists=False):
+                utt_list, labels, nfr, lab_width = meta.pop(i)
+                frames += nfr
+                words = hyps_to_words_batch(toks, lens, self.vocab, args.padding_idx, table)
+                for utt, w, n in zip(utt_list, words, lens.tolist()):
+                    results[utt] = (w, n - lab_width)
+                batch_time.update(time.time() - end)
+                end = time.time()
+                if i % args.print_freq == 0 and self.rank == 0:
+                    progress.print(i)
+        finally:
+            if flac_pool is not None:
+                flac_pool.shutdown(wait=True)
         self.pipeline_stats = {k: pipes.stats[k] - stats0[k] for k in stats0}
         return frames, i
 

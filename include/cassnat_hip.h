@@ -660,6 +660,38 @@ int cn_op_splice_rows(const float* src_dev, const int32_t* off_dev, const int32_
 /* host side of the same reader: n byte ranges (an utterance's rows in the memory map of its archive) copied back to back into a
  * staging buffer (dst + dst_offsets[i]) by one GIL-free call; threads > 1 deals them over that many host threads */
 int cn_host_gather(void* dst, const uint64_t* src_ptrs, const uint64_t* dst_offsets, const uint64_t* nbytes, int32_t n, int32_t threads);
+/* ---- FLAC input (RFC 9639, 16-bit streams): frames indexed on the host, decoded on the device --------------------
+ * cn_host_flac_index: the exact frame index of the audio bytes of a stream (from its first frame to the end of the file) whose
+ * STREAMINFO says (rate, channels, bits) - one linear, GIL-free pass.  From the start of the current frame a running CRC-16
+ * (0x8005, initial 0, MSB first) is kept; a later position becomes the next frame start only when a complete header stands there -
+ * sync, valid codes, reserved bits 0, the expected next frame number (variable block size: sample number), explicit block size /
+ * rate, a matching CRC-8 (0x07), the stream's blocking strategy - AND the two bytes in front of it equal the running CRC-16 of
+ * everything before them.  A sync pattern inside a payload is stepped over.  The last frame ends at nbytes, where its own CRC-16
+ * is checked.  out: `capacity` rows of three int32 - byte offset, byte length, first sample - or NULL to count; *frames, *samples:
+ * what was found.  0, or (error set, *bad_offset: where) -2 no chain of frames with matching CRCs reaches the end (the offset of
+ * the frame whose end was not found), -3 a frame whose rate, channels or sample size differ from STREAMINFO's, -5 more than
+ * `capacity` frames, -6 offsets or samples beyond 2^31 - 1.
+ * cn_op_flac_decode: the frames of a pass -> interleaved little-endian int16 PCM, on the device.  staged_dev: the files' bytes,
+ * utterance r's at a 16-byte-aligned offset (cn_host_gather's layout); table_dev [frames][4] int32: per frame its byte offset in
+ * staged_dev, byte length, utterance and first sample, in any order; utt_dev [3][utts] int32: channels, samples per channel, byte
+ * offset of the utterance's PCM in pcm_dev (even; the packed reader uses multiples of 16).  Sample j of channel c of utterance r is
+ * written to pcm_dev + offset[r] + 2 * (j * channels + c): the data chunk of a WAV file holding the same samples, which
+ * cn_op_fbank_packed and cn_op_wave_resample read as they are.  Nothing else of pcm_dev is written.  frame_words: the largest
+ * cn_flac_frame_words(channels, block size) of the pass (it sizes the scratch); max_channels: the largest channel count.
+ * scratch_dev: cn_flac_scratch_bytes(frames, frame_words) bytes of the caller's, or NULL - the call then allocates them and
+ * returns when the stream has drained.  status_dev: one int32, 0 after a pass whose frames all decoded; a frame that fails - a
+ * table entry outside the buffers, a header that does not parse, a block that does not fit the utterance or frame_words, a
+ * bitstream that leaves the frame's bytes or does not end on the footer - writes no PCM and leaves its index + 1 there (the
+ * largest).  Every read is bounded by the frame's byte span, every write by the utterance's samples. */
+int cn_host_flac_index(const void* audio, int64_t nbytes, int32_t rate, int32_t channels, int32_t bits, int32_t* out, int64_t capacity,
+                       int64_t* frames, int64_t* samples, int64_t* bad_offset);
+/* the frames' CRC-16 (polynomial 0x8005, initial value 0, MSB first) of nbytes bytes; host only (tools that write FLAC) */
+int32_t cn_host_flac_crc16(const void* data, int64_t nbytes);
+int64_t cn_flac_frame_words(int32_t channels, int32_t block_size);
+int64_t cn_flac_scratch_bytes(int32_t frames, int64_t frame_words);
+int cn_op_flac_decode(const void* staged_dev, int64_t staged_bytes, const int32_t* table_dev, int32_t frames, const int32_t* utt_dev,
+                      int32_t utts, int32_t max_channels, int64_t frame_words, void* pcm_dev, int64_t pcm_bytes, int32_t* status_dev,
+                      void* scratch_dev, int64_t scratch_bytes, void* stream);
 int cn_op_quantize_fp8(const void* src_bf16_dev, int32_t ld, void* dst_dev, int32_t M, int32_t K, float scale, void* stream);
 /* generator tail of the autoregressive step (src/models/transformer.py:48-51, 199-200): log_softmax(logits / T) and its per-row
  * top-k (sorted descending, ties: lower index) in one pass; the logits [M][V] are left untouched */
