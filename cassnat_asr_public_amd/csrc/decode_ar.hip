@@ -1,0 +1,716 @@
+// The autoregressive decoder (cfg.ast = 1) and the TransformerLM step (cfg.ast = 2): their step caches, one decoding step of
+// either, and the entries cn_ast_*, cn_lm_step* and cn_decode_ast (the beam search on the device).
+#include <algorithm>
+#include <cmath>
+
+#include "model.h"
+
+using namespace cn_host;
+
+// ESA ranking with rank_model == 'at_baseline' (src/models/cassnat.py:514-520; Transformer.forward_decoder,
+// src/models/transformer.py:113-116): the autoregressive model (cfg.ast = 1) scores the NAT predictions teacher-forced.
+// Its own encoder runs on the B utterances; the decoder then takes N = B * n_per_utt token rows (row e belongs to utterance
+// e % B: the sample-major order of cn_esa_sample) under the causal + length mask, with cross attention to its utterance's
+// encoder output under the padding mask: score[e][u] = log softmax(att_generator(dec_h))[e][u][tgt[e][u]] (the reference
+// takes the probability itself: exp on the caller's side).  tok / tgt / score are [N][ld], ld >= U; cfg.esa_group >= n_per_utt.
+extern "C" int cn_ast_teacher_score(cn_model* m, const float* feats_dev, int32_t B, int32_t T, int32_t F, const cn_decode_opts* opts,
+                                    const int32_t* tok_dev, const int32_t* tgt_dev, const int32_t* len_dev, int32_t n_per_utt,
+                                    int32_t U, int32_t ld, float* score_dev, void* stream) {
+    CN_TRY(check_call(m, B, T, F));
+    if (!opts || m->cfg.ast != 1 || !m->tgt_lut || n_per_utt < 1 || n_per_utt > std::max(1, m->cfg.esa_group) || U < 1 || ld < U ||
+        U > m->pe_rows) {
+        cn_set_error("cn_ast_teacher_score: needs an autoregressive model (cfg.ast = 1) whose cfg.esa_group covers the samples per utterance");
+        return -1;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    CN_HIP_CHECK(hipSetDevice(m->cfg.device));
+    CN_TRY(stage_encode(m, feats_dev, B, T, F, opts, s));
+    const int d = m->cfg.d_model, V = m->cfg.vocab_size, Tp = m->Tp, N = B * n_per_utt, M = N * U;
+    if ((size_t)M > (size_t)m->maxB * (m->maxTp + 1) * std::max(1, m->cfg.esa_group)) {
+        cn_set_error("cn_ast_teacher_score: token rows exceed the workspace");
+        return -1;
+    }
+    m->dec_group = n_per_utt;  // N query sets over the B utterances' encoder outputs
+    float* x = m->xd;
+    CN_TRY(launch_lm_embed(tok_dev, ld, m->tgt_lut, m->pe, x, N, U, d, sqrtf((float)d), s));
+    for (size_t i = 0; i < m->mad.size(); ++i) {  // DecoderLayer: self attention, source attention, feed-forward
+        const Layer& L = m->mad[i];
+        CN_TRY(run_self_attn(m, L, &L.n[0], x, N, U, nullptr, len_dev, 1, s));
+        CN_TRY(run_src_attn(m, L, &L.n[1], x, N, U, Tp, nullptr, s));
+        CN_TRY(run_ffn(m, L, L.n[2], x, M, nullptr, nullptr, s));
+    }
+    CN_TRY(run_ln(m, m->dec_norm, x, m->dec_h, M, s));
+    // generator in chunks of whole token rows that fit the logits buffer (B * (T' + 1) rows)
+    const int cap_rows = m->maxB * (m->maxTp + 1);
+    const int seq_per = std::max(1, cap_rows / U);
+    for (int e0 = 0; e0 < N; e0 += seq_per) {
+        const int ne = std::min(seq_per, N - e0), rows = ne * U;
+        const void* h = (const unsigned char*)m->dec_h + (size_t)e0 * U * d * m->es;
+        CN_TRY(run_linear(m, "generator_proj", m->att_gen, h, d, m->logits, V, 1, rows, 0, nullptr, 0, s));
+        CN_TRY(launch_logsoftmax_argmax(m->logits, rows, V, V, m->tok, m->val, 1, s));
+        CN_TRY(launch_gather_logp(m->logits, V, tgt_dev + (size_t)e0 * ld, ld, score_dev + (size_t)e0 * ld, ne, U, s));
+    }
+    m->dec_group = 1;
+    return 0;
+}
+
+// ArtTask decode_type 'ctc_correct' (Transformer.fast_decode_with_ctc, src/models/transformer.py:243-342): the CTC greedy hypothesis
+// of every utterance, behind sos, is the decoder's teacher-forced input under the causal + padding mask; the finish loop then reads
+// the k best labels of row i while i <= length[b].  Device part: encoder, CTC arg-max + collapse, decoder, generator + log-softmax +
+// top-k.  Outputs: len_out_dev [B] (CTC labels per utterance), tok_out_dev / val_out_dev [B][U][k] (U = longest + 1 rows, returned
+// in *rows_host; the buffers hold B * (T' + 1) * k entries).  One host sync on the longest hypothesis (the reference's max(length)).
+extern "C" int cn_ast_ctc_correct(cn_model* m, const float* feats_dev, int32_t B, int32_t T, int32_t F, const cn_decode_opts* opts,
+                                  int32_t k, int32_t* tok_out_dev, float* val_out_dev, int32_t* len_out_dev, int32_t* rows_host,
+                                  void* stream) {
+    CN_TRY(check_call(m, B, T, F));
+    if (!opts || m->cfg.ast != 1 || !m->tgt_lut || !m->ctc_gen.W || k < 1 || k > 16 || !tok_out_dev || !val_out_dev || !len_out_dev ||
+        !rows_host) {
+        cn_set_error("cn_ast_ctc_correct: needs an autoregressive model (cfg.ast = 1) with a CTC head, 1 <= k <= 16 and all output buffers");
+        return -1;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    CN_HIP_CHECK(hipSetDevice(m->cfg.device));
+    CN_TRY(stage_encode_ctc_rows(m, feats_dev, B, T, F, opts, s));
+    const int d = m->cfg.d_model, V = m->cfg.vocab_size, Tp = m->Tp, ld = Tp + 1;
+    if (ld > m->pe_rows) {
+        cn_set_error("cn_ast_ctc_correct: more subsampled frames than rows of the positional table");
+        return -1;
+    }
+    void *tgt = nullptr, *keylen = nullptr;
+    CN_TRY(scratch_buf(m, "cc_tgt", (size_t)B * ld * 4, &tgt));
+    CN_TRY(scratch_buf(m, "cc_keylen", (size_t)B * 4, &keylen));
+    CN_TRY(launch_ctc_collapse(m->best, m->keymask, B, Tp, opts->sos, opts->padding_idx, ld, (int*)tgt, len_out_dev, (int*)keylen, m->ymax, s));
+    CN_HIP_CHECK(hipMemcpyAsync(m->ymax_pinned, m->ymax, sizeof(int), hipMemcpyDeviceToHost, s));
+    CN_HIP_CHECK(hipStreamSynchronize(s));  // the decoder's row count is data dependent (max_length + 1, transformer.py:266)
+    const int U = *m->ymax_pinned + 1, M = B * U;
+    if (U < 1 || U > ld) {
+        cn_set_error("cn_ast_ctc_correct: impossible CTC hypothesis length");
+        return -3;
+    }
+    m->dec_group = 1;
+    float* x = m->xd;
+    CN_TRY(launch_lm_embed((const int*)tgt, ld, m->tgt_lut, m->pe, x, B, U, d, sqrtf((float)d), s));
+    for (size_t i = 0; i < m->mad.size(); ++i) {  // DecoderLayer: self attention (causal + padding mask), source attention, feed-forward
+        const Layer& L = m->mad[i];
+        CN_TRY(run_self_attn(m, L, &L.n[0], x, B, U, nullptr, (const int*)keylen, 1, s));
+        CN_TRY(run_src_attn(m, L, &L.n[1], x, B, U, Tp, nullptr, s));
+        CN_TRY(run_ffn(m, L, L.n[2], x, M, nullptr, nullptr, s));
+    }
+    CN_TRY(run_ln(m, m->dec_norm, x, m->dec_h, M, s));
+    CN_TRY(run_linear(m, "generator_proj", m->att_gen, m->dec_h, d, m->logits, V, 1, M, 0, nullptr, 0, s));
+    CN_TRY(launch_logsoftmax_argmax(m->logits, M, V, V, m->tok, m->val, 1, s));
+    CN_TRY(launch_topk(m->logits, M, V, V, k, tok_out_dev, val_out_dev, s));
+    *rows_host = U;
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// AST (autoregressive) path: BASELINE config 4
+// ---------------------------------------------------------------------------------------------------------------------
+namespace cn_host {
+namespace {
+int ast_alloc(cn_model* m, void** p, size_t bytes) {
+    CN_HIP_CHECK(hipMalloc(p, bytes ? bytes : 256));
+    m->ast_allocs.push_back(*p);
+    return 0;
+}
+
+int ast_prepare_buffers(cn_model* m, int max_len, int max_slots, int ctc_beam) {
+    if (m->ast_max_len >= max_len && m->ast_slots >= max_slots && m->ast_ctc_beam >= ctc_beam && m->ast_Tp_cap >= m->maxTp)
+        return 0;
+    for (void* q : m->ast_allocs) (void)hipFree(q);
+    m->ast_allocs.clear();
+    m->beam_S = m->beam_L = m->beam_K = 0;  // the beam-search state lives in the same allocation list
+    m->ast_kvx.clear();
+    m->ast_ck.clear();
+    m->ast_cv.clear();
+    const size_t d = m->cfg.d_model, V = m->cfg.vocab_size, es = m->es;
+    const size_t Mmem = (size_t)m->maxB * m->maxTp;
+    for (size_t l = 0; l < m->mad.size(); ++l) {
+        void *kvx = nullptr, *ck = nullptr, *cv = nullptr;
+        CN_TRY(ast_alloc(m, &kvx, Mmem * 2 * d * es));
+        CN_TRY(ast_alloc(m, &ck, (size_t)max_len * max_slots * d * es));
+        CN_TRY(ast_alloc(m, &cv, (size_t)max_len * max_slots * d * es));
+        m->ast_kvx.push_back(kvx);
+        m->ast_ck.push_back(ck);
+        m->ast_cv.push_back(cv);
+    }
+    CN_TRY(ast_alloc(m, (void**)&m->ast_logits, (size_t)max_slots * V * 4));
+    CN_TRY(ast_alloc(m, (void**)&m->ast_arg, (size_t)max_slots * 4));
+    CN_TRY(ast_alloc(m, (void**)&m->ast_maxlp, (size_t)max_slots * 4));
+    CN_TRY(ast_alloc(m, (void**)&m->ast_r0, Mmem * 2 * 4));
+    const int kb = ctc_beam > 0 ? ctc_beam : 1;
+    for (int i = 0; i < 2; ++i) CN_TRY(ast_alloc(m, (void**)&m->ast_r[i], (size_t)max_slots * kb * m->maxTp * 2 * 4));
+    m->ast_max_len = max_len;
+    m->ast_slots = max_slots;
+    m->ast_ctc_beam = ctc_beam;
+    m->ast_Tp_cap = m->maxTp;
+    return 0;
+}
+}  // namespace
+
+// the TransformerLM's step cache [layer][pos][slot][d] (K and V) and its logits [slot][V], on the LM handle
+int lm_prepare_buffers(cn_model* lm, int max_len, int max_slots) {
+    CN_TRY(build_workspace(lm));
+    if (lm->ast_max_len >= max_len && lm->ast_slots >= max_slots) return 0;
+    for (void* q : lm->ast_allocs) (void)hipFree(q);
+    lm->ast_allocs.clear();
+    lm->ast_ck.clear();
+    lm->ast_cv.clear();
+    const size_t d = lm->cfg.d_model, V = lm->cfg.vocab_size, es = lm->es;
+    for (size_t l = 0; l < lm->enc.size(); ++l) {
+        void *ck = nullptr, *cv = nullptr;
+        CN_TRY(ast_alloc(lm, &ck, (size_t)max_len * max_slots * d * es));
+        CN_TRY(ast_alloc(lm, &cv, (size_t)max_len * max_slots * d * es));
+        lm->ast_ck.push_back(ck);
+        lm->ast_cv.push_back(cv);
+    }
+    CN_TRY(ast_alloc(lm, (void**)&lm->ast_logits, (size_t)max_slots * V * 4));
+    lm->ast_max_len = max_len;
+    lm->ast_slots = max_slots;
+    return 0;
+}
+
+int lm_check_step(const cn_model* lm, int max_len, int max_slots, const char* who) {
+    if (!lm || lm->cfg.ast != 2 || !lm->finalized || !lm->tgt_lut) {
+        cn_set_error(std::string(who) + ": the LM must be a finalized TransformerLM handle (cfg.ast = 2)");
+        return -1;
+    }
+    if ((size_t)max_slots > (size_t)lm->maxB * (lm->maxTp + 1) || max_len > lm->pe_rows) {
+        cn_set_error(std::string(who) + ": the LM handle's workspace (max_batch x max_frames) or position table is too small for "
+                     "the beam's slots / max_len");
+        return -1;
+    }
+    return 0;
+}
+
+// TransformerLM (src/models/lm.py:52-56) on the newest position of n hypotheses -> logits [n][V] fp32 in lm->ast_logits.  The
+// reference runs lm_model(ys, tgt_mask) on the whole prefix under the decoder's mask (ys != padding_idx) & subsequent_mask
+// (transformer.py:186-191); here the keys / values of earlier positions come from the LM's own cache through the SAME ancestor
+// and key-mask tables as the decoder's.  Per layer (pre-norm encoder layer): LN, fused QKV, cached self-attention (appends this
+// position), out-proj + residual, FFN sublayer; then encoder.norm and out_generator.proj.
+// With row_pos / row_stay (the CTC prefix beam search, whose hypotheses differ in length): row h sits at position row_pos[h] <= pos,
+// anc_dev holds its cache ROW ids (one per prefix position, any row of the cache), every key is allowed (keyok_dev unused), and a
+// row with row_stay[h] != 0 appends nothing - its logits are garbage the caller discards.
+int lm_step_run(cn_model* lm, int n, int pos, const int32_t* tok_dev, const int32_t* anc_dev, const uint8_t* keyok_dev,
+                int table_stride, hipStream_t s, const int32_t* row_pos, const int32_t* row_stay) {
+    const cn_config& c = lm->cfg;
+    const int d = c.d_model, V = c.vocab_size, H = c.n_head;
+    const float scale = 1.0f / sqrtf((float)(d / H));
+    float* x = lm->x;
+    if (row_pos)
+        CN_TRY(launch_ast_embed_rows(tok_dev, lm->tgt_lut, lm->pe, row_pos, x, n, d, sqrtf((float)d), pos, s));
+    else
+        CN_TRY(launch_ast_embed(tok_dev, lm->tgt_lut, lm->pe + (size_t)pos * d, x, n, d, sqrtf((float)d), s));
+    // bf16 / d_model 256 (lm_small): the decode step's d_ff split of the fused FFN kernel, as in ast_step_run
+    static const bool no_split = cn_exp_env("CASSNAT_AST_NO_FFN_SPLIT") != nullptr;
+    const int dff = c.d_encff;
+    const int ffn_slices = (lm->enc.empty() || !lm->enc[0].w1p || no_split) ? 1 : (dff % (128 * 8) == 0 ? 8 : (dff % (128 * 4) == 0 ? 4 : 1));
+    const size_t hbuf_bytes = (size_t)lm->maxB * (lm->maxTp + 1) * std::max(1, c.esa_group) *
+                              (size_t)std::max(std::max(c.d_encff, c.d_decff), c.d_ff) * lm->es;
+    const bool split_now = ffn_slices > 1 && n <= 2048 && (size_t)ffn_slices * n * d * 4 <= hbuf_bytes;
+    bool have_ln = false;
+    for (size_t l = 0; l < lm->enc.size(); ++l) {
+        const Layer& L = lm->enc[l];
+        if (!have_ln) CN_TRY(run_ln(lm, L.n[0], x, lm->xn, n, s));
+        have_ln = false;
+        CN_TRY(run_linear(lm, "lm_qkv_proj", L.qkv, lm->xn, d, lm->qkv, 3 * d, 0, n, 0, nullptr, 0, s));
+        GatherAttnArgs a;
+        a.append_pos = pos;
+        a.q = lm->qkv;
+        a.ldq = 3 * d;
+        a.k = lm->ast_ck[l];
+        a.v = lm->ast_cv[l];
+        a.o = lm->ctx;
+        a.ldo = d;
+        a.n = n;
+        a.H = H;
+        a.nkeys = pos + 1;
+        a.slots = lm->ast_slots;
+        a.d = d;
+        a.table_stride = table_stride;
+        a.anc = anc_dev;
+        a.keyok = keyok_dev;
+        a.scale = scale;
+        if (row_pos) {
+            GatherRowsArgs r;
+            r.q = lm->qkv;
+            r.ldq = 3 * d;
+            r.k = lm->ast_ck[l];
+            r.v = lm->ast_cv[l];
+            r.o = lm->ctx;
+            r.ldo = d;
+            r.n = n;
+            r.H = H;
+            r.d = d;
+            r.table_stride = table_stride;
+            r.max_keys = pos + 1;
+            r.rowid = anc_dev;
+            r.pos = row_pos;
+            r.stay = row_stay;
+            r.scale = scale;
+            ProfScope ps(lm, "lm_cache_attention_rows", 4.0 * n * H * (pos + 1) * 64, 2.0 * n * (pos + 1) * d * lm->es, s);
+            CN_TRY(launch_ast_gather_attn_rows(lm->prec, r, s));
+        } else {
+            ProfScope ps(lm, "lm_cache_attention", 4.0 * n * H * (pos + 1) * 64, 2.0 * n * (pos + 1) * d * lm->es, s);
+            CN_TRY(launch_ast_gather_attn(lm->prec, 0, a, s));
+        }
+        CN_TRY(run_linear(lm, "lm_out_proj_resid", L.self_o, lm->ctx, d, x, d, 1, n, CN_EPI_RESID, x, d, s));
+        if (split_now) {
+            const bool last = l + 1 == lm->enc.size();
+            const Norm& nx = last ? lm->enc_norm : lm->enc[l + 1].n[0];
+            ProfScope ps(lm, "lm_ffn_split", 4.0 * n * (double)L.w1.N * d, 2.0 * L.w1.N * d * 2 + (double)n * d * (8 + 4 * ffn_slices), s);
+            FfnFusedArgs f;
+            f.x = x;
+            f.ln_a = L.n[1].a;
+            f.ln_b = L.n[1].b;
+            f.w1p = L.w1p;
+            f.b1 = L.w1.b;
+            f.w2p = L.w2p;
+            f.b2 = L.w2.b;
+            f.M = n;
+            f.d = d;
+            f.dff = L.w1.N;
+            f.nslice = ffn_slices;
+            f.partial = reinterpret_cast<float*>(lm->hbuf);
+            f.act = FF_ACT_RELU;
+            CN_TRY(launch_ffn_fused(f, s));
+            CN_TRY(launch_ffn_reduce(x, f.partial, ffn_slices, L.w2.b, nx.a, nx.b, last ? lm->enc_h : lm->xn, n, 1e-6f, s));
+            have_ln = true;
+        } else {
+            CN_TRY(run_ffn(lm, L, L.n[1], x, n, nullptr, nullptr, s));
+        }
+    }
+    if (!have_ln) CN_TRY(run_ln(lm, lm->enc_norm, x, lm->enc_h, n, s));
+    return run_linear(lm, "lm_generator_proj", lm->att_gen, lm->enc_h, d, lm->ast_logits, V, 1, n, 0, nullptr, 0, s);
+}
+}  // namespace cn_host
+
+// src/tasks/art_task.py:67-90 + transformer.py:186-209: the LM whose step ast_step fuses when lm_weight > 0 (NULL detaches).
+extern "C" int cn_ast_attach_lm(cn_model* m, cn_model* lm) {
+    if (!m || m->cfg.ast != 1) {
+        cn_set_error("cn_ast_attach_lm: the first handle must be an autoregressive model (cfg.ast = 1)");
+        return -1;
+    }
+    if (!lm) {
+        m->ast_lm = nullptr;
+        return 0;
+    }
+    if (lm->lib_tag != m->lib_tag) {
+        cn_set_error("cn_ast_attach_lm: the two handles come from different libraries");
+        return -1;
+    }
+    if (lm->cfg.ast != 2 || !lm->finalized) {
+        cn_set_error("cn_ast_attach_lm: the LM handle must be a finalized TransformerLM (cfg.ast = 2)");
+        return -1;
+    }
+    if (lm->cfg.vocab_size != m->cfg.vocab_size || lm->cfg.device != m->cfg.device) {
+        cn_set_error("cn_ast_attach_lm: the LM must have the decoder's vocabulary and device");
+        return -1;
+    }
+    m->ast_lm = lm;
+    return 0;
+}
+
+extern "C" int cn_ast_begin(cn_model* m, const float* feats_dev, int32_t B, int32_t T, int32_t F, const cn_decode_opts* opts,
+                            int32_t want_ctc, int32_t max_len, int32_t max_slots, int32_t ctc_beam, void* stream) {
+    CN_TRY(check_call(m, B, T, F));
+    if (m->cfg.ast != 1 || !m->tgt_lut) {
+        cn_set_error("cn_ast_begin: the model was not created with cfg.ast = 1");
+        return -1;
+    }
+    if (max_len < 2 || max_slots < 1 || (size_t)max_slots > (size_t)m->maxB * (m->maxTp + 1) || ctc_beam < 0 || ctc_beam > 32) {
+        cn_set_error("cn_ast_begin: bad max_len / max_slots / ctc_beam");
+        return -1;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    CN_HIP_CHECK(hipSetDevice(m->cfg.device));
+    CN_TRY(ast_prepare_buffers(m, max_len, max_slots, ctc_beam));
+    if (m->ast_lm) {  // the attached LM's step cache, sized like the decoder's
+        CN_TRY(lm_check_step(m->ast_lm, max_len, max_slots, "cn_ast_begin"));
+        CN_TRY(lm_prepare_buffers(m->ast_lm, max_len, max_slots));
+    }
+    m->ast_blank = opts->padding_idx;
+    CN_TRY(stage_encode(m, feats_dev, B, T, F, opts, s));
+    const int d = m->cfg.d_model, Mmem = B * m->Tp, V = m->cfg.vocab_size;
+    for (size_t l = 0; l < m->mad.size(); ++l)  // cross-attention K|V of the memory, once per utterance batch
+        CN_TRY(run_linear(m, "src_kv_proj", m->mad[l].src_kv, m->enc_h, d, m->ast_kvx[l], 2 * d, 0, Mmem, 0, nullptr, 0, s));
+    if (want_ctc) {
+        CN_TRY(run_linear(m, "generator_proj", m->ctc_gen, m->enc_h, d, m->logits, V, 1, Mmem, 0, nullptr, 0, s));
+        CN_TRY(launch_logsoftmax_argmax(m->logits, Mmem, V, V, m->best, m->ctc_maxlp, 1, s));
+    m->ctc_maxlp_valid = true;
+        CN_TRY(launch_ast_ctc_prepare(m->logits, m->keymask, m->ast_r0, B, m->Tp, V, opts->padding_idx, s));
+    }
+    return 0;
+}
+
+namespace cn_host {
+namespace {
+// decoder layers on the newest position of n hypotheses -> top-K (token, temperature log-softmax value) per hypothesis
+// dense_bw > 0: the rows are the dense slots b * dense_bw + j of the device beam (utt[row] = row / dense_bw)
+int ast_step_run(cn_model* m, int n, int pos, const int32_t* tok_dev, const int32_t* utt_dev, const int32_t* anc_dev,
+                 const uint8_t* keyok_dev, int table_stride, float temperature, int K, int32_t* topk_idx_dev,
+                 float* topk_val_dev, int dense_bw, hipStream_t s, float lm_weight = 0.f, float* lm_val_dev = nullptr) {
+    const cn_config& c = m->cfg;
+    const int d = c.d_model, V = c.vocab_size, H = c.n_head;
+    const float scale = 1.0f / sqrtf((float)(d / H));
+    float* x = m->xd;
+    CN_TRY(launch_ast_embed(tok_dev, m->tgt_lut, m->pe + (size_t)pos * d, x, n, d, sqrtf((float)d), s));
+    // A decode step has few rows (live hypotheses, <= batch x beam): the fused feed-forward kernel would put them on
+    // ceil(n / 64) workgroups that each stream the whole 2 MB of W1|W2.  Its d_ff split spreads the hidden units over 8
+    // workgroups per row tile; the reduce kernel that adds the slices also writes the LayerNorm the next sublayer starts
+    // with (the next layer's self-attention pre-norm, or decoder.norm after the last layer).
+    static const bool no_split = cn_exp_env("CASSNAT_AST_NO_FFN_SPLIT") != nullptr;
+    const int ffn_slices = (m->mad.empty() || !m->mad[0].w1p || no_split) ? 1 : (c.d_decff % (128 * 8) == 0 ? 8 : (c.d_decff % (128 * 4) == 0 ? 4 : 1));
+    bool have_ln = false;  // m->xn already holds LN(x) for the sublayer about to start
+    // (only while the rows are few, and the slices fit the hidden-activation buffer they borrow)
+    const size_t hbuf_bytes = (size_t)m->maxB * (m->maxTp + 1) * std::max(1, c.esa_group) *
+                              (size_t)std::max(std::max(c.d_encff, c.d_decff), c.d_ff) * m->es;
+    const bool split_now = ffn_slices > 1 && n <= 2048 && (size_t)ffn_slices * n * d * 4 <= hbuf_bytes;
+    for (size_t l = 0; l < m->mad.size(); ++l) {
+        const Layer& L = m->mad[l];
+        // x += O(SelfAttn(LN x)) over the cached prefix
+        if (!have_ln) CN_TRY(run_ln(m, L.n[0], x, m->xn, n, s));
+        have_ln = false;
+        CN_TRY(run_linear(m, "qkv_proj", L.qkv, m->xn, d, m->qkv, 3 * d, 0, n, 0, nullptr, 0, s));
+        GatherAttnArgs a;
+        a.append_pos = pos;  // the cache attention appends this position's K | V itself (it is the only reader of that row now)
+        a.q = m->qkv;
+        a.ldq = 3 * d;
+        a.k = m->ast_ck[l];
+        a.v = m->ast_cv[l];
+        a.o = m->ctx;
+        a.ldo = d;
+        a.n = n;
+        a.H = H;
+        a.nkeys = pos + 1;
+        a.slots = m->ast_slots;
+        a.d = d;
+        a.table_stride = table_stride;
+        a.anc = anc_dev;
+        a.keyok = keyok_dev;
+        a.scale = scale;
+        {
+            ProfScope ps(m, "ast_cache_attention", 4.0 * n * H * (pos + 1) * 64, 2.0 * n * (pos + 1) * d * m->es, s);
+            CN_TRY(launch_ast_gather_attn(m->prec, 0, a, s));
+        }
+        CN_TRY(run_linear(m, "out_proj_resid", L.self_o, m->ctx, d, x, d, 1, n, CN_EPI_RESID, x, d, s));
+        // x += O(SrcAttn(LN x, memory))
+        CN_TRY(run_ln(m, L.n[1], x, m->xn, n, s));
+        CN_TRY(run_linear(m, "src_q_proj", L.src_q, m->xn, d, m->qd, d, 0, n, 0, nullptr, 0, s));
+        GatherAttnArgs b;
+        b.q = m->qd;
+        b.ldq = d;
+        b.k = m->ast_kvx[l];
+        b.v = (const unsigned char*)m->ast_kvx[l] + (size_t)d * m->es;
+        b.o = m->ctx;
+        b.ldo = d;
+        b.n = n;
+        b.H = H;
+        b.nkeys = m->Tp;
+        b.d = d;
+        b.utt = utt_dev;
+        b.keymask = m->keymask;
+        b.scale = scale;
+        static const bool no_fast_src = cn_exp_env("CASSNAT_AST_GATHER_SRC") != nullptr;
+        if (m->prec == CN_PREC_BF16 && m->Tp <= 256 && !no_fast_src) {
+            // every hypothesis row is a batch entry of one query whose keys / values are its utterance's: the LDS-resident
+            // attention kernel (K|V of a (row, head) by LDS-DMA, MFMA products) instead of the scalar gather kernel
+            ProfScope ps(m, "ast_src_attention", 4.0 * n * H * m->Tp * 64, 2.0 * n * m->Tp * d * m->es, s);
+            AttnArgs a2;
+            a2.Q = m->qd;
+            a2.K = m->ast_kvx[l];
+            a2.V = (const unsigned char*)m->ast_kvx[l] + (size_t)d * m->es;
+            a2.O = m->ctx;
+            a2.ldq = d;
+            a2.ldk = a2.ldv = 2 * d;
+            a2.ldo = d;
+            a2.H = H;
+            a2.Lk = m->Tp;
+            a2.keymask = m->keymask;
+            if (dense_bw > 0 && n % dense_bw == 0) {  // device beam: utterance b owns rows b * bw .. + bw - 1
+                a2.B = n / dense_bw;
+                a2.Lq = dense_bw;
+            } else {  // caller-managed rows: every row is a batch entry of one query that names its utterance
+                a2.B = n;
+                a2.Lq = 1;
+                a2.kv_index = utt_dev;
+            }
+            a2.scale = scale;
+            CN_TRY(launch_attention(m->prec, a2, s));
+        } else {
+            ProfScope ps(m, "ast_src_attention", 4.0 * n * H * m->Tp * 64, 2.0 * n * m->Tp * d * m->es, s);
+            CN_TRY(launch_ast_gather_attn(m->prec, 1, b, s));
+        }
+        CN_TRY(run_linear(m, "out_proj_resid", L.src_o, m->ctx, d, x, d, 1, n, CN_EPI_RESID, x, d, s));
+        if (split_now) {
+            const bool last = l + 1 == m->mad.size();
+            const Norm& nx = last ? m->dec_norm : m->mad[l + 1].n[0];
+            ProfScope ps(m, "ffn_split", 4.0 * n * (double)L.w1.N * d, 2.0 * L.w1.N * d * 2 + (double)n * d * (8 + 4 * ffn_slices), s);
+            FfnFusedArgs a;
+            a.x = x;
+            a.ln_a = L.n[2].a;
+            a.ln_b = L.n[2].b;
+            a.w1p = L.w1p;
+            a.b1 = L.w1.b;
+            a.w2p = L.w2p;
+            a.b2 = L.w2.b;
+            a.M = n;
+            a.d = d;
+            a.dff = L.w1.N;
+            a.nslice = ffn_slices;
+            a.partial = reinterpret_cast<float*>(m->hbuf);  // [slices][n][256] fp32 <= the [rows][d_ff] hidden buffer
+            a.act = L.ff_swish ? FF_ACT_SWISH : FF_ACT_RELU;
+            CN_TRY(launch_ffn_fused(a, s));
+            CN_TRY(launch_ffn_reduce(x, a.partial, ffn_slices, L.w2.b, nx.a, nx.b, last ? m->dec_h : m->xn, n, 1e-6f, s));
+            have_ln = true;
+        } else {
+            CN_TRY(run_ffn(m, L, L.n[2], x, n, nullptr, nullptr, s));
+        }
+    }
+    if (!have_ln) CN_TRY(run_ln(m, m->dec_norm, x, m->dec_h, n, s));
+    CN_TRY(run_linear(m, "generator_proj", m->att_gen, m->dec_h, d, m->ast_logits, V, 1, n, 0, nullptr, 0, s));
+    if (lm_weight > 0.f) {  // shallow fusion (transformer.py:186-209): the LM step on the same rows, tables and position
+        cn_model* lm = m->ast_lm;
+        CN_TRY(lm_step_run(lm, n, pos, tok_dev, anc_dev, keyok_dev, table_stride, s));
+        ProfScope ps(m, "lm_fusion", 0, 2.0 * n * V * 4, s);
+        if (!lm_val_dev)  // no CTC: top-K of att + lm_weight * lm over the vocabulary
+            return launch_logsoftmax_fuse_topk(m->ast_logits, lm->ast_logits, n, V, V, temperature, lm_weight, K, topk_idx_dev,
+                                               topk_val_dev, s);
+        CN_TRY(launch_logsoftmax_topk(m->ast_logits, n, V, V, temperature, K, topk_idx_dev, topk_val_dev, s));
+        return launch_logsoftmax_gather(lm->ast_logits, n, V, V, topk_idx_dev, K, lm_val_dev, s);
+    }
+    CN_TRY(launch_logsoftmax_topk(m->ast_logits, n, V, V, temperature, K, topk_idx_dev, topk_val_dev, s));
+    return 0;
+}
+}  // namespace
+}  // namespace cn_host
+
+extern "C" int cn_ast_step(cn_model* m, int32_t n, int32_t pos, const int32_t* tok_dev, const int32_t* utt_dev,
+                           const int32_t* anc_dev, const uint8_t* keyok_dev, int32_t table_stride, float temperature,
+                           int32_t K, int32_t* topk_idx_dev, float* topk_val_dev, void* stream) {
+    if (!m || !m->cfg.ast || m->ast_slots == 0) {
+        cn_set_error("cn_ast_step: call cn_ast_begin first");
+        return -1;
+    }
+    if (n < 1 || n > m->ast_slots || pos < 0 || pos >= m->ast_max_len || pos >= m->pe_rows || K < 1 || K > 32 ||
+        K > m->cfg.vocab_size || table_stride <= pos) {
+        cn_set_error("cn_ast_step: live rows / position / K outside the configured cache (K <= 32 and <= the vocabulary)");
+        return -1;
+    }
+    CN_HIP_CHECK(hipSetDevice(m->cfg.device));
+    return ast_step_run(m, n, pos, tok_dev, utt_dev, anc_dev, keyok_dev, table_stride, temperature, K, topk_idx_dev, topk_val_dev, 0,
+                        (hipStream_t)stream);
+}
+
+extern "C" int cn_ast_step_lm(cn_model* m, int32_t n, int32_t pos, const int32_t* tok_dev, const int32_t* utt_dev,
+                              const int32_t* anc_dev, const uint8_t* keyok_dev, int32_t table_stride, float temperature, int32_t K,
+                              float lm_weight, int32_t use_ctc, int32_t* topk_idx_dev, float* topk_val_dev, float* lm_val_dev,
+                              void* stream) {
+    if (!m || m->cfg.ast != 1 || m->ast_slots == 0) {
+        cn_set_error("cn_ast_step_lm: call cn_ast_begin first");
+        return -1;
+    }
+    if (!(lm_weight > 0.f) || !m->ast_lm || m->ast_lm->ast_slots < m->ast_slots || m->ast_lm->ast_max_len < m->ast_max_len) {
+        cn_set_error("cn_ast_step_lm: needs lm_weight > 0 and an LM attached (cn_ast_attach_lm) before cn_ast_begin");
+        return -1;
+    }
+    if (n < 1 || n > m->ast_slots || pos < 0 || pos >= m->ast_max_len || pos >= m->pe_rows || K < 1 || K > 32 ||
+        K > m->cfg.vocab_size || table_stride <= pos || (use_ctc && !lm_val_dev)) {
+        cn_set_error("cn_ast_step_lm: live rows / position / K outside the configured cache (K <= 32 and <= the vocabulary; or use_ctc "
+                     "without lm_val_dev)");
+        return -1;
+    }
+    CN_HIP_CHECK(hipSetDevice(m->cfg.device));
+    return ast_step_run(m, n, pos, tok_dev, utt_dev, anc_dev, keyok_dev, table_stride, temperature, K, topk_idx_dev, topk_val_dev, 0,
+                        (hipStream_t)stream, lm_weight, use_ctc ? lm_val_dev : nullptr);
+}
+
+// kernel-test entry of the LM step: log_softmax of the LM's logits at position pos of n rows -> logp_dev [n][V]
+extern "C" int cn_lm_step_begin(cn_model* lm, int32_t max_len, int32_t max_slots) {
+    CN_TRY(lm_check_step(lm, max_len, max_slots, "cn_lm_step_begin"));
+    if (max_len < 1 || max_slots < 1) {
+        cn_set_error("cn_lm_step_begin: bad max_len / max_slots");
+        return -1;
+    }
+    CN_HIP_CHECK(hipSetDevice(lm->cfg.device));
+    return lm_prepare_buffers(lm, max_len, max_slots);
+}
+
+extern "C" int cn_lm_step(cn_model* lm, int32_t n, int32_t pos, const int32_t* tok_dev, const int32_t* anc_dev,
+                          const uint8_t* keyok_dev, int32_t table_stride, float* logp_dev, void* stream) {
+    if (!lm || lm->cfg.ast != 2 || lm->ast_slots == 0) {
+        cn_set_error("cn_lm_step: call cn_lm_step_begin first");
+        return -1;
+    }
+    if (n < 1 || n > lm->ast_slots || pos < 0 || pos >= lm->ast_max_len || pos >= lm->pe_rows || table_stride <= pos) {
+        cn_set_error("cn_lm_step: rows / position outside the configured cache");
+        return -1;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    CN_HIP_CHECK(hipSetDevice(lm->cfg.device));
+    const int V = lm->cfg.vocab_size;
+    CN_TRY(lm_step_run(lm, n, pos, tok_dev, anc_dev, keyok_dev, table_stride, s));
+    CN_TRY(launch_logsoftmax_argmax(lm->ast_logits, n, V, V, lm->best, lm->ctc_maxlp, 1, s));
+    CN_HIP_CHECK(hipMemcpyAsync(logp_dev, lm->ast_logits, (size_t)n * V * 4, hipMemcpyDeviceToDevice, s));
+    return 0;
+}
+
+// kernel-test entry of the LM step with a position per row (cn_ctc_beam_lm's): row h holds token tok_dev[h] at position
+// pos_dev[h] <= max_pos; rowid_dev [n][table_stride] names the cache row of every prefix position (any row below the
+// max_len * max_slots of cn_lm_step_begin; the caller keeps them in range - they are not read back here); rows with stay_dev[h]
+// != 0 append nothing and their output is unspecified.  logp_dev [n][V]: log_softmax of the logits, as cn_lm_step's.
+extern "C" int cn_lm_step_rows(cn_model* lm, int32_t n, int32_t max_pos, const int32_t* tok_dev, const int32_t* pos_dev,
+                               const int32_t* stay_dev, const int32_t* rowid_dev, int32_t table_stride, float* logp_dev, void* stream) {
+    if (!lm || lm->cfg.ast != 2 || lm->ast_slots == 0) {
+        cn_set_error("cn_lm_step_rows: call cn_lm_step_begin first");
+        return -1;
+    }
+    if (!tok_dev || !pos_dev || !stay_dev || !rowid_dev || !logp_dev) {
+        cn_set_error("cn_lm_step_rows: null array");
+        return -1;
+    }
+    if (n < 1 || n > lm->ast_slots || max_pos < 0 || max_pos >= lm->ast_max_len || max_pos >= lm->pe_rows || table_stride <= max_pos) {
+        cn_set_error("cn_lm_step_rows: rows / position outside the configured cache");
+        return -1;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    CN_HIP_CHECK(hipSetDevice(lm->cfg.device));
+    const int V = lm->cfg.vocab_size;
+    CN_TRY(lm_step_run(lm, n, max_pos, tok_dev, rowid_dev, nullptr, table_stride, s, pos_dev, stay_dev));
+    CN_TRY(launch_logsoftmax_argmax(lm->ast_logits, n, V, V, lm->best, lm->ctc_maxlp, 1, s));
+    CN_HIP_CHECK(hipMemcpyAsync(logp_dev, lm->ast_logits, (size_t)n * V * 4, hipMemcpyDeviceToDevice, s));
+    return 0;
+}
+
+extern "C" int cn_ast_ctc_score(cn_model* m, int32_t n, int32_t out_len, const int32_t* utt_dev, const int32_t* last_tok_dev,
+                                const int32_t* cand_dev, int32_t K, const int32_t* prev_ref_dev, int32_t parity, int32_t eos,
+                                float* score_dev, void* stream) {
+    if (!m || !m->cfg.ast || !m->ast_r0 || K < 1 || K > m->ast_ctc_beam || n < 1 || n > m->ast_slots) {
+        cn_set_error("cn_ast_ctc_score: call cn_ast_begin with want_ctc and a ctc_beam >= K first");
+        return -1;
+    }
+    CN_HIP_CHECK(hipSetDevice(m->cfg.device));
+    CtcPrefixArgs a;
+    a.logp = m->logits;
+    a.r0 = m->ast_r0;
+    a.r_prev = m->ast_r[(parity & 1) ^ 1];
+    a.r_new = m->ast_r[parity & 1];
+    a.utt = utt_dev;
+    a.last_tok = last_tok_dev;
+    a.cand = cand_dev;
+    a.prev_ref = prev_ref_dev;
+    a.score = score_dev;
+    a.n = n;
+    a.K = K;
+    a.Tp = m->Tp;
+    a.V = m->cfg.vocab_size;
+    a.blank = m->ast_blank;
+    a.eos = eos;
+    a.out_len = out_len;
+    return launch_ast_ctc_prefix(a, (hipStream_t)stream);
+}
+
+// Whole joint CTC/attention beam search on the device (transformer.py:122-241): encoder, then max_step iterations of
+// [decoder step on every slot -> CTC prefix scores -> beam update kernel]; the host only polls the live-hypothesis
+// counter every 8 steps to stop early.  Outputs (device pointers): hyp_out [B][beam_width][max_len] (sos first, padded
+// with padding_idx), hyp_len [B][beam_width], score [B][beam_width] as double; beams best first.
+extern "C" int cn_decode_ast(cn_model* m, const float* feats_dev, int32_t B, int32_t T, int32_t F, const cn_decode_opts* opts,
+                             const cn_ast_opts* ao, int32_t* hyp_out_dev, int32_t max_len, int32_t* hyp_len_dev,
+                             double* score_dev, void* stream) {
+    if (!m || !opts || !ao || !hyp_out_dev || !hyp_len_dev || !score_dev) {
+        cn_set_error("cn_decode_ast: null argument");
+        return -1;
+    }
+    const int bw = ao->beam_width, want_ctc = ao->ctc_weight > 0.f ? 1 : 0;
+    const int K = want_ctc ? ao->ctc_beam : bw;
+    if (bw < 1 || bw > 32 || K < bw || K > 32 || ao->max_step < 1 || max_len < ao->max_step + 1) {
+        cn_set_error("cn_decode_ast: need 1 <= beam_width <= ctc_beam <= 32 and max_len > max_step");
+        return -1;
+    }
+    if (K > m->cfg.vocab_size) {
+        cn_set_error("cn_decode_ast: the candidate count (ctc_beam, or beam_width without CTC) exceeds the vocabulary");
+        return -1;
+    }
+    // step pos scores prefixes of pos tokens: the CTC prefix scorer is defined up to out_len == T' (the reference raises
+    // IndexError beyond it), so the last step, max_step - 1, must not pass the subsampled frame count
+    const int Tp = ((T - 1) / 2 + 1 - 1) / 2 + 1;
+    if (want_ctc && ao->max_step > Tp + 1) {
+        cn_set_error("cn_decode_ast: with CTC, max_step may not exceed the subsampled frame count + 1 (max_decode_ratio too large: "
+                     "the CTC prefix score of a hypothesis longer than the frames is undefined)");
+        return -1;
+    }
+    const bool use_lm = ao->lm_weight > 0.f;
+    if (use_lm && !m->ast_lm) {
+        cn_set_error("cn_decode_ast: lm_weight > 0 needs an LM attached with cn_ast_attach_lm");
+        return -1;
+    }
+    const int S = B * bw, L = max_len;
+    CN_TRY(cn_ast_begin(m, feats_dev, B, T, F, opts, want_ctc, L, S, want_ctc ? K : 0, stream));
+    hipStream_t s = (hipStream_t)stream;
+    if (m->beam_S < S || m->beam_L < L || m->beam_K < K) {
+        AstBeamState& st = m->beam;
+        for (int i = 0; i < 2; ++i) {
+            CN_TRY(ast_alloc(m, (void**)&st.tok[i], (size_t)S * L * 4));
+            CN_TRY(ast_alloc(m, (void**)&st.anc[i], (size_t)S * L * 4));
+            CN_TRY(ast_alloc(m, (void**)&st.keyok[i], (size_t)S * L));
+            CN_TRY(ast_alloc(m, (void**)&st.len[i], (size_t)S * 4));
+            CN_TRY(ast_alloc(m, (void**)&st.score[i], (size_t)S * 8));
+            CN_TRY(ast_alloc(m, (void**)&st.valid[i], (size_t)S * 4));
+            CN_TRY(ast_alloc(m, (void**)&st.ctc_ref[i], (size_t)S * 4));
+            CN_TRY(ast_alloc(m, (void**)&st.ctc_prev[i], (size_t)S * 4));
+        }
+        CN_TRY(ast_alloc(m, (void**)&st.cur_tok, (size_t)S * 4));
+        CN_TRY(ast_alloc(m, (void**)&st.utt, (size_t)S * 4));
+        CN_TRY(ast_alloc(m, (void**)&st.live, 64));
+        CN_TRY(ast_alloc(m, (void**)&m->beam_idx, (size_t)S * K * 4));
+        CN_TRY(ast_alloc(m, (void**)&m->beam_val, (size_t)S * K * 4));
+        CN_TRY(ast_alloc(m, (void**)&m->beam_ctc, (size_t)S * K * 4));
+        CN_TRY(ast_alloc(m, (void**)&m->beam_lm, (size_t)S * K * 4));
+        m->beam_S = S;
+        m->beam_L = L;
+        m->beam_K = K;
+    }
+    const AstBeamState& st = m->beam;
+    int cur = 0;
+    CN_TRY(launch_ast_beam_init(st, cur, B, bw, L, opts->sos, opts->padding_idx, s));
+    for (int pos = 0; pos < ao->max_step; ++pos) {
+        CN_TRY(ast_step_run(m, S, pos, st.cur_tok, st.utt, st.anc[cur], st.keyok[cur], L, ao->temperature, K, m->beam_idx,
+                            m->beam_val, bw, s, use_lm ? ao->lm_weight : 0.f, use_lm && want_ctc ? m->beam_lm : nullptr));
+        if (want_ctc)
+            CN_TRY(cn_ast_ctc_score(m, S, pos, st.utt, st.cur_tok, m->beam_idx, K, st.ctc_ref[cur], pos & 1, ao->eos, m->beam_ctc,
+                                    stream));
+        AstBeamStep q;
+        q.idx = m->beam_idx;
+        q.att = m->beam_val;
+        q.ctc = m->beam_ctc;
+        q.cur = cur;
+        q.pos = pos;
+        q.bw = bw;
+        q.K = K;
+        q.L = L;
+        q.eos = ao->eos;
+        q.sos = opts->sos;
+        q.pad = opts->padding_idx;
+        q.use_ctc = want_ctc;
+        q.use_lp = ao->use_length_penalty;
+        q.use_lm = use_lm;
+        q.lm = m->beam_lm;
+        q.lw = ao->lm_weight;
+        q.w = ao->ctc_weight;
+        q.u = ao->one_minus_ctc_weight;
+        q.lp = ao->length_penalty;
+        CN_TRY(launch_ast_beam_update(st, q, B, s));
+        cur ^= 1;
+        if ((pos & 7) == 7 && pos + 1 < ao->max_step) {  // every 8 steps: anything still alive?
+            CN_HIP_CHECK(hipMemcpyAsync(m->ymax_pinned + 8, st.live, sizeof(int), hipMemcpyDeviceToHost, s));
+            CN_HIP_CHECK(hipStreamSynchronize(s));
+            if (m->ymax_pinned[8] == 0) break;
+        }
+    }
+    CN_HIP_CHECK(hipMemcpyAsync(hyp_out_dev, st.tok[cur], (size_t)S * L * 4, hipMemcpyDeviceToDevice, s));
+    CN_HIP_CHECK(hipMemcpyAsync(hyp_len_dev, st.len[cur], (size_t)S * 4, hipMemcpyDeviceToDevice, s));
+    CN_HIP_CHECK(hipMemcpyAsync(score_dev, st.score[cur], (size_t)S * 8, hipMemcpyDeviceToDevice, s));
+    return 0;
+}
+

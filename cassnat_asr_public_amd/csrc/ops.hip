@@ -1,6 +1,7 @@
 // C-ABI entry points of libcassnat_hip.so that take no model handle: the Kaldi fbank front end and the resampler in front of it, the host gather of the packed
 // reader and the single-kernel entries (cn_op_*) through which the tests drive every hand-written kernel.  See
-// include/cassnat_hip.h for the contract; the handle, weight packing and decode paths are model.hip.
+// include/cassnat_hip.h for the contract; the handle is handle.hip, weight packing weights.hip, the decode paths
+// model.hip / decode_ar.hip.
 #include <algorithm>
 #include <cmath>
 #include <cstring>

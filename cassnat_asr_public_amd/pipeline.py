@@ -175,7 +175,7 @@ class DecodePipelines(PackedStaging):
     # ------------------------------------------------------------------------------------------ capacity
     def fits(self, rows, T):
         """Does a pass of ``rows`` utterances x ``T`` frames fit the engines' workspace?  (The library's own check, ws_check in
-        csrc/model.hip, restated: every buffer scales with one of these products.)"""
+        csrc/workspace.hip, restated: every buffer scales with one of these products.)"""
         T1 = (T - 1) // 2 + 1
         Tp = (T1 - 1) // 2 + 1
         mT1 = (self.frames_cap - 1) // 2 + 1

@@ -723,7 +723,7 @@ def test_merged_pass_without_trigger_rows_equals_separate_passes(prec):
 def test_fp16_engine_fails_loudly_outside_the_half_range():
     """The fp16 engine's MFMA operands have a range (+-65504) and do not saturate.  What drives magnitudes from outside is the scale
     of the features, so every pass checks them against the bound under which neither subsampling convolution's output can pass
-    65504 / 2 (from the convolutions' weight row sums; csrc/model.hip op16_feat_limit): `beam_decode` and the decode pipelines
+    65504 / 2 (from the convolutions' weight row sums; csrc/weights.hip op16_feat_limit): `beam_decode` and the decode pipelines
     raise instead of returning hypotheses of such a pass; inside the bound the engine decodes, and the same features decode on the
     bf16 engine (range of fp32)."""
     from cassnat_asr_public_amd.pipeline import DecodePipelines
