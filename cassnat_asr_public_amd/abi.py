@@ -1,0 +1,109 @@
+"""The C ABI read from include/cassnat_hip.h, the only place that declares it: ``FUNCTIONS`` name -> (restype, argtypes),
+``STRUCTS`` C name -> ctypes.Structure, ``CONSTANTS`` enum / #define name -> int.  It reads this project's header, not C in general:
+what it does not recognise raises ``AbiError`` naming the declaration.  Standard library only (no torch, numpy, library or GPU)."""
+import ctypes as C
+import os
+import re
+
+HEADER_PATH = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "cassnat_hip.h")
+SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint64_t": C.c_uint64, "float": C.c_float, "double": C.c_double}
+_BASE = re.compile(r"(?:const\s+)?(\w+)\s*")
+_DECL = re.compile(r"((?:\*\s*)*)(\w*)\s*(?:\[(\d+)\])?")
+
+
+class AbiError(ValueError):
+    pass
+
+
+class Abi:
+    def __init__(self):
+        self.functions, self.structs, self.constants, self.opaque = {}, {}, {}, set()
+
+    def ctype(self, base, stars, where):
+        """``base`` behind ``stars`` asterisks: a scalar by value, c_char_p, POINTER(struct), or c_void_p for every other pointer."""
+        if not stars and base in SCALARS:
+            return SCALARS[base]
+        if stars == 1 and base == "char":
+            return C.c_char_p
+        if stars == 1 and base in self.structs:
+            return C.POINTER(self.structs[base])
+        if stars and (base in SCALARS or base in self.structs or base in self.opaque or base in ("void", "char", "uint8_t")):
+            return C.c_void_p
+        raise AbiError(f"{where}: unknown type {base + '*' * stars!r}")
+
+    def declarators(self, text, where):
+        """``const T *a, b[3]`` -> [(name, ctypes type)]; an empty name is a bare type (``void`` alone gives None)."""
+        text = " ".join(text.split())
+        m = _BASE.match(text)
+        out = []
+        for part in text[m.end():].split(",") if m else ():
+            d = _DECL.fullmatch(part.strip())
+            if not d:
+                raise AbiError(f"{where}: cannot read {text!r}")
+            if m.group(1) == "void" and not d.group(1) and not d.group(2):
+                out.append(("", None))
+                continue
+            t = self.ctype(m.group(1), d.group(1).count("*"), f"{where}: {text!r}")
+            out.append((d.group(2), t * int(d.group(3)) if d.group(3) else t))
+        if not out:
+            raise AbiError(f"{where}: cannot read {text!r}")
+        return out
+
+
+def parse(text):
+    abi = Abi()
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    for name, value in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(CN_\w+)[ \t]+(-?\w+)[ \t]*$", text, re.M):
+        abi.constants[name] = int(value, 0)
+    text = re.sub(r'^[ \t]*#[^\n]*|extern\s+"C"\s*\{', " ", text, flags=re.M)
+
+    def enum(m):
+        for item in filter(None, (s.strip() for s in m.group(1).split(","))):
+            name, eq, value = (s.strip() for s in item.partition("="))
+            if not eq or not re.fullmatch(r"\w+", name):
+                raise AbiError(f"enum: cannot read {item!r}")
+            abi.constants[name] = int(value, 0)
+        return " "
+
+    def struct(m):
+        fields = []
+        for line in filter(None, (s.strip() for s in m.group(2).split(";"))):
+            got = abi.declarators(line, f"struct {m.group(1)}")
+            if any(not name or t is None for name, t in got):
+                raise AbiError(f"struct {m.group(1)}: cannot read {line!r}")
+            fields += got
+        cls = "".join(p.title() for p in m.group(1).split("_"))
+        abi.structs[m.group(1)] = type(cls, (C.Structure,), {"_fields_": fields, "__doc__": f"{m.group(1)} of include/cassnat_hip.h"})
+        return " "
+
+    text = re.sub(r"\benum\s*\{(.*?)\}\s*;", enum, text, flags=re.S)
+    abi.opaque.update(re.findall(r"\btypedef\s+struct\s+(\w+)\s+\1\s*;", text))
+    text = re.sub(r"\btypedef\s+struct\s+(\w+)\s+\1\s*;", " ", text)
+    text = re.sub(r"\btypedef\s+struct\s+(\w+)\s*\{(.*?)\}\s*\1\s*;", struct, text, flags=re.S)
+    for stmt in filter(None, (s.strip() for s in text.split(";"))):
+        m = re.fullmatch(r"(.*?)\b(cn_\w+)\s*\((.*)\)", stmt, re.S)
+        if not m:
+            if stmt == "}":  # (closes extern "C")
+                continue
+            raise AbiError(f"cannot split the declaration {' '.join(stmt.split())!r}")
+        name, params = m.group(2), m.group(3).strip()
+        ret = abi.declarators(m.group(1), f"{name}: return type")
+        args = [] if params == "void" else [d for p in params.split(",") for d in abi.declarators(p, name)]
+        if len(ret) != 1 or ret[0][0] or any(not n or t is None for n, t in args):
+            raise AbiError(f"cannot split the declaration of {name}: {' '.join(stmt.split())!r}")
+        abi.functions[name] = (ret[0][1], [t for _, t in args])
+    return abi
+
+
+with open(HEADER_PATH) as _f:
+    HEADER = parse(_f.read())
+FUNCTIONS, STRUCTS, CONSTANTS = HEADER.functions, HEADER.structs, HEADER.constants
+
+
+def bind(L):
+    """Set ``restype`` / ``argtypes`` of every declared function on the loaded library ``L``; a function the header declares and the
+    library lacks raises AttributeError."""
+    for name, (restype, argtypes) in FUNCTIONS.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
+    return L

@@ -4,9 +4,10 @@ The product path has no CPU fallback: if the library is missing or a call fails,
 """
 import ctypes as C
 import os
-import re
 
 import numpy as np
+
+from . import abi
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # (CASSNAT_HIP_LIB: another build of the same library - A/B measurements of kernel variants, tools/scripts/ab_bench.sh)
@@ -14,11 +15,15 @@ LIB_PATH = os.environ.get("CASSNAT_HIP_LIB") or os.path.join(_HERE, "libcassnat_
 # the second build of the same sources (csrc/common.h: -DCN_OP16_F16): the fast engine with IEEE half-precision MFMA operands -
 # --hip_precision fp16.  Same C ABI; an engine keeps the library it was created in.
 LIB_PATH_F16 = os.path.join(_HERE, "libcassnat_hip_f16.so")
-HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "cassnat_hip.h")
+HEADER_PATH = abi.HEADER_PATH
 
-PRECISION = {"fp32": 0, "f32": 0, "float32": 0, "bf16": 1, "bfloat16": 1, "fp8": 2, "bf16x3": 3, "fp16": 4, "float16": 4}
-DTYPES = {0: np.float32, 1: np.int32, 2: np.uint8, 3: np.float64}
-FP8_SCOPE_BITS = {"conv2": 1, "linear": 2, "ffn": 4}
+# the header's enums and #defines under the names the options use
+_K = abi.CONSTANTS
+_F32, _BF16, _FP8, _BF16X3, _F16 = (_K["CN_PRECISION_" + n] for n in ("F32", "BF16", "FP8", "BF16X3", "F16"))
+PRECISION = {"fp32": _F32, "f32": _F32, "float32": _F32, "bf16": _BF16, "bfloat16": _BF16, "fp8": _FP8, "bf16x3": _BF16X3, "fp16": _F16,
+             "float16": _F16}
+DTYPES = {_K["CN_DTYPE_F32"]: np.float32, _K["CN_DTYPE_I32"]: np.int32, _K["CN_DTYPE_U8"]: np.uint8, _K["CN_DTYPE_F64"]: np.float64}
+FP8_SCOPE_BITS = {"conv2": _K["CN_FP8_CONV2"], "linear": _K["CN_FP8_LINEAR"], "ffn": _K["CN_FP8_FFN"]}
 
 
 def parse_fp8_scope(text):
@@ -43,49 +48,9 @@ def parse_fp8_scope(text):
     return scope, first
 
 
-class CnConfig(C.Structure):
-    _fields_ = [(n, C.c_int32) for n in (
-        "input_size", "d_model", "n_head", "d_encff", "d_decff", "n_enc", "n_extra", "n_self_dec", "n_mix_dec",
-        "vocab_size", "precision", "max_batch", "max_frames", "device", "ast", "conf_enc", "conf_dec", "enc_max_rel", "dec_max_rel",
-        "enc_kernel", "dec_kernel", "d_ff", "esa_group", "fp8_scope", "fp8_ffn_first_layer")]
-
-
-class CnDecodeOpts(C.Structure):
-    _fields_ = [(n, C.c_int32) for n in (
-        "padding_idx", "sos", "left_trigger", "right_trigger", "src_trigger", "use_unimask", "beam_width",
-        "capture", "sub_batch", "no_trigger")] + [("reserved", C.c_int32 * 6)]
-
-
-class CnAstOpts(C.Structure):
-    _fields_ = [("ctc_weight", C.c_float), ("temperature", C.c_float), ("ctc_beam", C.c_int32), ("beam_width", C.c_int32),
-                ("max_step", C.c_int32), ("eos", C.c_int32), ("use_length_penalty", C.c_int32), ("one_minus_ctc_weight", C.c_float),
-                ("length_penalty", C.c_double), ("lm_weight", C.c_float), ("reserved", C.c_int32 * 3)]
-
-
-class CnFbankOpts(C.Structure):
-    _fields_ = [(n, C.c_float) for n in ("sample_rate", "frame_length_ms", "frame_shift_ms", "preemph", "low_freq", "high_freq")] + \
-               [(n, C.c_int32) for n in ("num_mel", "window_type", "remove_dc", "use_power", "use_log")] + \
-               [("reserved", C.c_int32 * 5)]
-
-
-class CnAttnDesc(C.Structure):
-    """cn_attn_desc: every option of the fused attention kernel (cn_op_attention_desc)."""
-    _fields_ = [("Q", C.c_void_p), ("K", C.c_void_p), ("V", C.c_void_p), ("O", C.c_void_p)] + \
-               [(n, C.c_int32) for n in ("ldq", "ldk", "ldv", "ldo", "B", "H", "Lq", "Lk")] + \
-               [("keymask", C.c_void_p), ("kv_mod", C.c_int32), ("kv_index", C.c_void_p), ("klen", C.c_void_p), ("kcap", C.c_void_p),
-                ("kcap_stride", C.c_int32)] + \
-               [(n, C.c_int32) for n in ("q_blocked", "kv_blocked", "q_col", "k_col", "v_col", "q_n", "kv_n", "o_blocked")] + \
-               [("intervals", C.c_void_p), ("iv_stride", C.c_int32), ("causal", C.c_int32), ("scale", C.c_float),
-                ("rel_pos", C.c_void_p), ("rel_u", C.c_void_p), ("rel_v", C.c_void_p), ("rel_R", C.c_int32), ("ld_pos", C.c_int32)]
-
-
-class CnNgramDesc(C.Structure):
-    """cn_ngram_desc: the tables of an ARPA n-gram model (models.ngram.NgramLM owns them; cn_op_ngram_score / cn_ngram_score_host)."""
-    _fields_ = [("word_keys", C.c_void_p), ("word_ids", C.c_void_p), ("word_slots", C.c_int64),
-                ("gram_keys", C.c_void_p), ("gram_prob", C.c_void_p), ("gram_bo", C.c_void_p), ("gram_slots", C.c_int64),
-                ("piece_hash", C.c_void_p), ("piece_pow", C.c_void_p), ("piece_starts", C.c_void_p)] + \
-               [(n, C.c_int32) for n in ("vocab", "order", "bos", "eos", "unk", "reserved0")] + \
-               [("key_mask", C.c_uint64), ("reserved", C.c_int64 * 6)]
+# the six structs of the header, derived from it field for field (abi.py)
+CnConfig, CnDecodeOpts, CnAstOpts, CnFbankOpts, CnAttnDesc, CnNgramDesc = (abi.STRUCTS[n] for n in (
+    "cn_config", "cn_decode_opts", "cn_ast_opts", "cn_fbank_opts", "cn_attn_desc", "cn_ngram_desc"))
 
 
 class HipError(RuntimeError):
@@ -97,9 +62,7 @@ _libs = {}
 
 def declared_symbols():
     """Every function name include/cassnat_hip.h declares."""
-    with open(HEADER_PATH) as f:
-        text = f.read()
-    return sorted(set(re.findall(r"\b(cn_[a-z0-9_]+)\s*\(", text)) - {"cn_model", "cn_config", "cn_decode_opts"})
+    return sorted(abi.FUNCTIONS)
 
 
 def lib_for(precision):
@@ -118,165 +81,7 @@ def lib(flavour=None):
         raise HipError(f"{path} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                        "(there is no CPU fallback for the CASS-NAT hot path)")
     L = C.CDLL(path)
-    L.cn_last_error.restype = C.c_char_p
-    L.cn_version.restype = C.c_char_p
-    L.cn_operand16.restype = C.c_char_p
-    L.cn_model_destroy.restype = None
-    for name in declared_symbols():
-        fn = getattr(L, name)  # AttributeError here = header and library disagree
-        if name not in ("cn_last_error", "cn_version", "cn_operand16", "cn_model_destroy"):
-            fn.restype = C.c_int
-    L.cn_op_gemm.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
-                             C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
-                             C.c_float, C.c_void_p]
-    L.cn_op_convert.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
-    L.cn_op_conv1.argtypes = [C.c_int32] + [C.c_void_p] * 4 + [C.c_int32] * 4 + [C.c_void_p]
-    L.cn_op_conv1_bordered.argtypes = [C.c_void_p] * 4 + [C.c_int32] * 4 + [C.c_void_p]
-    L.cn_op_conv2.argtypes = [C.c_int32] + [C.c_void_p] * 4 + [C.c_int32] * 4 + [C.c_void_p]
-    L.cn_op_conv_frontend_fp8.argtypes = [C.c_void_p] * 7 + [C.c_int32] * 4 + [C.c_float, C.c_float, C.c_void_p, C.c_void_p]
-    L.cn_op_conv_frontend_mix.argtypes = [C.c_void_p] * 7 + [C.c_int32] * 4 + [C.c_void_p]
-    L.cn_op_linear256_fp8.argtypes = [C.c_void_p] * 4 + [C.c_int32] * 2 + [C.c_float, C.c_float, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
-    L.cn_op_layernorm.argtypes = [C.c_int32] + [C.c_void_p] * 4 + [C.c_int32, C.c_int32, C.c_float, C.c_void_p]
-    L.cn_op_glu.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
-    L.cn_op_dwconv.argtypes = [C.c_int32] + [C.c_void_p] * 4 + [C.c_int32] * 5 + [C.c_void_p]
-    L.cn_op_groupnorm_swish.argtypes = [C.c_int32] + [C.c_void_p] * 5 + [C.c_int32] * 3 + [C.c_float, C.c_void_p]
-    L.cn_op_attention.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
-                                  C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
-                                  C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_void_p]
-    L.cn_op_attention_desc.argtypes = [C.c_int32, C.POINTER(CnAttnDesc), C.c_void_p]
-    L.cn_attn_desc_size.argtypes = []
-    L.cn_op_attention_packed.argtypes = [C.c_int32, C.POINTER(CnAttnDesc), C.c_void_p, C.c_int32, C.c_void_p]
-    L.cn_op_row_plan.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.cn_op_logsoftmax_argmax.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
-    L.cn_op_ctc_align.argtypes = [C.c_void_p] * 3 + [C.c_int32] * 5 + [C.c_void_p] * 6
-    L.cn_op_greedy_pack.argtypes = [C.c_void_p] * 3 + [C.c_int32] * 4 + [C.c_void_p] * 4
-    L.cn_op_ctc_prefix_beam.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double,
-                                        C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                        C.c_void_p]
-    L.cn_op_ctc_viterbi.argtypes = [C.c_void_p] * 5 + [C.c_int32] * 6 + [C.c_void_p, C.c_void_p]
-    L.cn_op_topk.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.cn_op_gemm_fp8.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float,
-                                 C.c_int32, C.POINTER(C.c_float), C.c_void_p]
-    L.cn_op_cmvn.argtypes = [C.c_void_p] * 4 + [C.c_int32] * 3 + [C.c_void_p]
-    L.cn_host_gather.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]
-    L.cn_op_unpack_rows.argtypes = [C.c_void_p] * 4 + [C.c_int32] * 3 + [C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.cn_op_unpack_compressed.argtypes = [C.c_void_p] * 5 + [C.c_int32] * 3 + [C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.cn_op_splice_rows.argtypes = [C.c_void_p] * 4 + [C.c_int32] * 6 + [C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.cn_op_quantize_fp8.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_void_p]
-    L.cn_op_logsoftmax_topk.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.cn_op_logsoftmax_fuse_topk.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_int32, C.c_void_p,
-                                             C.c_void_p, C.c_void_p]
-    L.cn_op_logsoftmax_gather.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
-    L.cn_op_ast_gather_attn.argtypes = ([C.c_int32, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 3 + [C.c_int32] * 7 +
-                                        [C.c_void_p] * 4 + [C.c_float, C.c_int32, C.c_void_p])
-    L.cn_op_ast_ctc_prepare.argtypes = [C.c_void_p] * 3 + [C.c_int32] * 4 + [C.c_void_p]
-    L.cn_op_ast_ctc_prefix.argtypes = [C.c_void_p] * 9 + [C.c_int32] * 7 + [C.c_void_p]
-    L.cn_op_ast_beam_init.argtypes = [C.c_void_p] * 19 + [C.c_int32] * 6 + [C.c_void_p]
-    L.cn_op_ast_beam_update.argtypes = ([C.c_void_p] * 23 + [C.c_int32] * 11 + [C.c_float] * 3 + [C.c_double, C.c_int32, C.c_void_p])
-    L.cn_model_create.argtypes = [C.POINTER(CnConfig), C.POINTER(C.c_void_p)]
-    L.cn_model_create_shared.argtypes = [C.POINTER(CnConfig), C.c_void_p, C.POINTER(C.c_void_p)]
-    L.cn_model_destroy.argtypes = [C.c_void_p]
-    L.cn_model_load_weights.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int32]
-    L.cn_model_load_pe.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
-    L.cn_model_finalize.argtypes = [C.c_void_p]
-    L.cn_model_weight_blob.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
-    L.cn_decode_nast.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
-                                 C.POINTER(CnDecodeOpts), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.cn_decode_nast_merged.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(CnDecodeOpts),
-                                        C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.c_int32,
-                                        C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
-    L.cn_decode_ticket.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-    L.cn_take_range_fault.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_float)]
-    L.cn_encode_align.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
-                                  C.POINTER(CnDecodeOpts), C.POINTER(C.c_int32), C.c_void_p]
-    L.cn_fetch.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32),
-                           C.POINTER(C.c_int32)]
-    L.cn_op_ffn_fused.argtypes = [C.c_void_p] * 10 + [C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_void_p]
-    L.cn_op_ffn_x3.argtypes = [C.c_void_p] * 10 + [C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_void_p]
-    L.cn_op_ffn_fused_act.argtypes = [C.c_void_p] * 10 + [C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_void_p]
-    L.cn_op_ffn_x3_act.argtypes = [C.c_void_p] * 10 + [C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_void_p]
-    L.cn_op_x3_chain.argtypes = [C.c_void_p] * 16 + [C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_void_p]
-    L.cn_op_chain.argtypes = ([C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 13 +
-                              [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_void_p])
-    L.cn_op_chain_rows.argtypes = ([C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 13 +
-                                   [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_void_p, C.c_void_p])
-    L.cn_op_genmax.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.cn_op_genmax_gather.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
-                                      C.c_void_p, C.c_void_p]
-    L.cn_op_genmax_x3.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
-                                  C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
-    L.cn_op_proj_x3.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
-                                C.c_void_p]
-    L.cn_ast_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(CnDecodeOpts), C.c_int32,
-                               C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
-    L.cn_ast_step.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
-                              C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.cn_ast_attach_lm.argtypes = [C.c_void_p, C.c_void_p]
-    L.cn_ast_step_lm.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
-                                 C.c_float, C.c_int32, C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.cn_nat_attach_lm.argtypes = [C.c_void_p, C.c_void_p]
-    L.cn_nat_lm_finish.argtypes = [C.c_void_p, C.POINTER(CnDecodeOpts), C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_double, C.c_int32,
-                                   C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.cn_op_nat_lm_fuse_topk.argtypes = [C.c_void_p] * 4 + [C.c_int32] * 5 + [C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.cn_op_nat_beam_update.argtypes = [C.c_void_p] * 12 + [C.c_int32] * 6 + [C.c_double, C.c_int32, C.c_void_p]
-    L.cn_lm_step_begin.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
-    L.cn_lm_step.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
-    L.cn_lm_step_rows.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
-                                  C.c_void_p]
-    L.cn_ctc_beam_lm.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(CnDecodeOpts),
-                                 C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_void_p, C.c_int32] + [C.c_void_p] * 6 + \
-                                [C.POINTER(C.c_int32), C.c_void_p]
-    L.cn_op_ctc_lm_frame.argtypes = [C.c_void_p] * 20 + [C.c_int32] * 10 + [C.c_double, C.c_double, C.c_void_p]
-    L.cn_op_ctc_lm_rows.argtypes = [C.c_void_p] * 6 + [C.c_int32] * 4 + [C.c_void_p]
-    L.cn_fbank_default_opts.argtypes = [C.POINTER(CnFbankOpts)]
-    L.cn_fbank_default_opts.restype = None
-    L.cn_fbank_num_frames.argtypes = [C.POINTER(CnFbankOpts), C.c_int32]
-    L.cn_fbank_num_frames.restype = C.c_int32
-    L.cn_fbank.argtypes = [C.POINTER(CnFbankOpts), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
-                           C.c_int32, C.c_float, C.c_void_p]
-    L.cn_op_fbank_packed.argtypes = [C.POINTER(CnFbankOpts), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
-                                     C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.cn_op_fbank_packed_f32.argtypes = L.cn_op_fbank_packed.argtypes
-    L.cn_resample_num_samples.argtypes = [C.c_int32, C.c_int32, C.c_int64]
-    L.cn_resample_num_samples.restype = C.c_int64
-    L.cn_resample_table.argtypes = [C.c_int32, C.c_int32] + [C.POINTER(C.c_int32)] * 3 + [C.c_void_p] * 3 + [C.c_int64]
-    L.cn_op_wave_resample.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_int64] + [C.c_void_p] * 6 + [C.c_int32, C.c_void_p, C.c_int32,
-                                                                                                      C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.cn_host_flac_index.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64] + [C.POINTER(C.c_int64)] * 3
-    L.cn_host_flac_crc16.argtypes = [C.c_char_p, C.c_int64]
-    L.cn_flac_frame_words.argtypes = [C.c_int32, C.c_int32]
-    L.cn_flac_frame_words.restype = C.c_int64
-    L.cn_flac_scratch_bytes.argtypes = [C.c_int32, C.c_int64]
-    L.cn_flac_scratch_bytes.restype = C.c_int64
-    L.cn_op_flac_decode.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p,
-                                    C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
-    L.cn_esa_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(CnDecodeOpts), C.c_void_p]
-    L.cn_esa_sample.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.POINTER(CnDecodeOpts), C.c_void_p,
-                                C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_void_p]
-    L.cn_lm_score.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
-    L.cn_decode_ast.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(CnDecodeOpts),
-                                C.POINTER(CnAstOpts), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.cn_ast_ctc_score.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
-                                   C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
-    L.cn_ctc_beam.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(CnDecodeOpts), C.c_int32,
-                              C.c_int32, C.c_double, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                              C.c_void_p]
-    L.cn_decode_nast_forced.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(CnDecodeOpts),
-                                        C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
-                                        C.c_void_p]
-    L.cn_ast_teacher_score.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(CnDecodeOpts), C.c_void_p,
-                                       C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
-    L.cn_ast_ctc_correct.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(CnDecodeOpts), C.c_int32,
-                                     C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]
-    L.cn_ngram_desc_size.argtypes = []
-    L.cn_ngram_counts.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
-    L.cn_ngram_parse.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
-                                 C.c_int64, C.c_void_p]
-    L.cn_ngram_hash.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
-    L.cn_ngram_score_host.argtypes = [C.POINTER(CnNgramDesc), C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
-    L.cn_op_ngram_score.argtypes = [C.POINTER(CnNgramDesc), C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
-    L.cn_profile_begin.argtypes = [C.c_void_p, C.c_char_p]
-    L.cn_profile_end.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
+    abi.bind(L)  # argtypes / restype of every declared function; AttributeError here = header and library disagree
     want = "fp16" if flavour == "f16" else "bf16"
     if L.cn_operand16().decode() != want:
         raise HipError(f"{path}: the library's 16-bit operand is {L.cn_operand16().decode()}, expected {want}")
@@ -299,6 +104,11 @@ def check_fp16_range(scores, what="decode"):
     if not np.isfinite(np.asarray(scores, dtype=np.float64)).all():
         raise HipError(f"{what}: non-finite hypothesis score from the fp16 engine - an MFMA operand left the half-precision range "
                        "(+-65504); use --hip_precision bf16 / bf16x3 for this model or these features")
+
+
+def subsampled(T):
+    """T' of T frames after the two stride-2 convolutions (embedding.py:102-108)."""
+    return ((T - 1) // 2 + 1 - 1) // 2 + 1
 
 
 def _ptr(t):
@@ -729,7 +539,7 @@ class Engine:
         import torch
 
         B, T, F = feats.shape
-        cap = ((T - 1) // 2 + 1 - 1) // 2 + 1 + 1
+        cap = subsampled(T) + 1
         dev = feats.device
         hyp = torch.empty(B, beam, cap, dtype=torch.int32, device=dev)
         hlen = torch.empty(B, beam, dtype=torch.int32, device=dev)
@@ -748,7 +558,7 @@ class Engine:
         if lm is None or lm.L is not self.L:
             raise HipError("cn_ctc_beam_lm: the LM engine comes from the other library")
         B, T, F = feats.shape
-        cap = ((T - 1) // 2 + 1 - 1) // 2 + 1 + 1
+        cap = subsampled(T) + 1
         dev = feats.device
         hyp = torch.empty(B, beam, cap, dtype=torch.int32, device=dev)
         hlen = torch.empty(B, beam, dtype=torch.int32, device=dev)
@@ -780,7 +590,7 @@ class Engine:
         import torch
 
         B, T, F = feats.shape
-        Tp = ((T - 1) // 2 + 1 - 1) // 2 + 1
+        Tp = subsampled(T)
         tok = torch.empty(B * (Tp + 1) * k, dtype=torch.int32, device=feats.device)
         val = torch.empty(B * (Tp + 1) * k, dtype=torch.float32, device=feats.device)
         length = torch.empty(B, dtype=torch.int32, device=feats.device)

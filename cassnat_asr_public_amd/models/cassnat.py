@@ -415,7 +415,7 @@ class CassNAT(nn.Module):
         if getattr(args, "lm_weight", 0) > 0:  # the fused finish reads the pass's full rows; the per-row top-k tables are not its input
             opts.reserved[0], opts.beam_width = 1, 1
         opts.sub_batch = int(sub_batch)  # coalesced batches of that size each (pipeline.DecodePipelines): per-batch hypotheses
-        stride = ((T - 1) // 2 + 1 - 1) // 2 + 1 + 2
+        stride = hip.subsampled(T) + 2
         hyp = torch.empty(B, stride, dtype=torch.int32, device=dev)
         hyp_len = torch.empty(B, dtype=torch.int32, device=dev)
         score = torch.empty(B, dtype=torch.float64, device=dev)
@@ -478,7 +478,7 @@ class CassNAT(nn.Module):
         feats = src.to(dev, torch.float32).contiguous()
         ratio = src_size.to(dev, torch.float32).contiguous()
         B, T, _ = feats.shape
-        Tp = ((T - 1) // 2 + 1 - 1) // 2 + 1
+        Tp = hip.subsampled(T)
         lab = [list(ctc_top_seqs[b][0]["hyp"]) for b in range(B)]
         ymax = max(len(x) for x in lab)
         labels = np.zeros((B, max(ymax, 1)), np.int32)
@@ -510,7 +510,7 @@ class CassNAT(nn.Module):
         ratio = src_size.to(dev, torch.float32).contiguous()
         B, T, _ = feats.shape
         S = int(args.sample_num)
-        Tp = ((T - 1) // 2 + 1 - 1) // 2 + 1
+        Tp = hip.subsampled(T)
         # samples per decoder pass: the decoder side runs B * group query sets over the B utterances' encoder outputs
         group = max(1, min(S, int(getattr(args, "hip_esa_group", 16))))
         eng = self.engine(B, T, esa_group=group)

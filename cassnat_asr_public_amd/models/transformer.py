@@ -140,7 +140,7 @@ class Transformer(nn.Module):
         dev = torch.device("cuda", getattr(self, "_device", torch.cuda.current_device()))
         feats = src.to(dev, torch.float32).contiguous()
         B, T, _ = feats.shape
-        Tp = ((T - 1) // 2 + 1 - 1) // 2 + 1
+        Tp = hip.subsampled(T)
         eng = engine if engine is not None else self.engine(B, T)
         use_ctc = args.ctc_weight > 0
         bw = int(args.beam_width)

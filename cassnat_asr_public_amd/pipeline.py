@@ -34,9 +34,7 @@ from . import hip as _hip
 from .staging import PackedBatch, PackedStaging, _form  # noqa: F401 (PackedBatch is imported from here by the tools and the tests)
 
 
-def subsampled(T):
-    """T' of T frames after the two stride-2 convolutions (embedding.py:102-108)."""
-    return ((T - 1) // 2 + 1 - 1) // 2 + 1
+subsampled = _hip.subsampled
 
 
 class _NoStream:

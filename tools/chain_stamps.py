@@ -10,7 +10,7 @@ os.environ.setdefault("CASSNAT_CHAIN_STAMPS", "1")  # 2: also skip the tail's st
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from cassnat_asr_public_amd import build as B  # noqa: E402
+from cassnat_asr_public_amd import abi, build as B  # noqa: E402
 
 
 def main():
@@ -21,9 +21,7 @@ def main():
     # the stamps are an experiment switch (csrc/common.h: cn_exp_env): an experiments build of the library, with the extra flags if
     # any (CASSNAT_CHAIN_STAMP_BLOCK chooses the workgroup that writes the stamps)
     lib = os.environ.get("CASSNAT_HIP_LIB") or B.experiments_lib(extra, tag="chain" + tag)
-    L = C.CDLL(lib)
-    L.cn_op_chain.argtypes = [C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 12 + [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
-                                                                                       C.c_float, C.c_int32, C.c_void_p]
+    L = abi.bind(C.CDLL(lib))
     d, dff, tail = 256, 2048, 768
     g = torch.Generator().manual_seed(1)
     rn = lambda *s: torch.randn(*s, generator=g)

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from cassnat_asr_public_amd import build as B  # noqa: E402
+from cassnat_asr_public_amd import abi, build as B  # noqa: E402
 
 
 def main():
@@ -26,8 +26,7 @@ def main():
     extra = sys.argv[3:]  # e.g. -DFX_EXP_NO_WLOAD / -DFX_EXP_NO_XREAD: timing experiments (wrong results)
     tag = "".join(c for c in "".join(extra) if c.isalnum())
     lib = B.build(extra_flags=["-DFX_STAMPS"] + extra, lib=os.path.join(out, "libcassnat_hip_stamps%s.so" % tag), objdir=os.path.join(out, "cn_stamps_obj" + tag))
-    L = C.CDLL(lib)
-    L.cn_op_ffn_x3.argtypes = [C.c_void_p] * 10 + [C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_void_p]
+    L = abi.bind(C.CDLL(lib))
     L.cn_debug_ffn_x3_stamps.argtypes = [C.c_void_p, C.c_int32]
     g = torch.Generator().manual_seed(0)
     x = (torch.randn(M, 256, generator=g) * 2).cuda()
