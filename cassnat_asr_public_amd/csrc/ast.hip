@@ -53,78 +53,67 @@ int launch_ast_kv_append(int prec, const void* qkv, void* ck, void* cv, int n, i
 }
 
 // ---------------------------------------------------------------------------------------------
-// Single-query multi-head attention with gathered key/value rows (d_k = 64).  One workgroup per hypothesis, one wave per
+// Single-query multi-head attention with gathered key/value rows (d_k = 64).  One workgroup per row of queries, one wave per
 // head.  Phase 1: a lane owns a key (64-dim dot product with the query held in registers); masked keys get float-min
 // exactly like MultiHeadedAttention (attention.py:19-21).  Phase 2: a lane owns an output dimension.
-//   MODE 0 (self, cache):  key j in [0, nkeys): row (j*slots + anc[h][j]) of ck / cv (row length d), allowed iff keyok[h][j]
-//   MODE 1 (source):       key j in [0, nkeys): row (utt[h]*nkeys + j) of the fused K|V matrix (row length 2d), allowed iff
-//                          keymask[utt[h]][j]
+// One body, ga_head, does the work of a (row, head) wave.  The forms differ in the keys of a row, which a key set describes:
+//   n           keys of the row: j in [0, n)
+//   ld          row length of k / v, in elements
+//   row(j)      the row of k / v that holds key j
+//   allowed(j)  false: the key scores float-min
+//   own         the key whose K | V are still in the projection buffer (columns d.. and 2d.. of q's row), or < 0 for none: the
+//               wave writes its 64 columns of them to row own_row of k / v for the steps to come and reads key `own` from the
+//               projection buffer itself (no separate append launch, no read-after-write through the cache)
 // ---------------------------------------------------------------------------------------------
-struct GatherAttnParams {
-    const void* q;  // [n][ldq], head hd at column hd*64
-    int ldq;
-    const void* k;
-    const void* v;
-    void* o;  // [n][ldo]
-    int ldo;
-    int n, H, nkeys, slots, d, table_stride;
-    const int* anc;              // MODE 0: [n][table_stride]
-    const unsigned char* keyok;  // MODE 0: [n][table_stride]
-    const int* utt;              // MODE 1: [n]
-    const unsigned char* keymask;  // MODE 1: [B][nkeys]
-    float scale;
-    // MODE 0, append_pos >= 0: this step's K and V of hypothesis h are still in the projection buffer (columns d.. and 2d.. of
-    // q's row): the workgroup writes them to cache row (append_pos, slot h) for the steps to come and reads key append_pos
-    // from the projection buffer itself (no separate append launch, no read-after-write through the cache)
-    int append_pos;
+// decoder self-attention over the KV cache [pos][slots][d]: key j is cache row (j, anc[j]), allowed iff keyok[j]
+struct GaCacheKeys {
+    const int* anc;              // the row's [table_stride] entries
+    const unsigned char* keyok;  // the row's [table_stride] entries
+    int slots, n, ld, own;
+    long long own_row;
+    __device__ long long row(int j) const { return (long long)j * slots + anc[j]; }
+    __device__ bool allowed(int j) const { return keyok[j] != 0; }
+};
+// source attention over the fused K | V matrix [B * n][2d]: key j is row first + j, allowed iff the utterance's keymask[j]
+struct GaSourceKeys {
+    const unsigned char* keymask;  // the utterance's [n] entries
+    long long first;
+    int n, ld;
+    static constexpr int own = -1;
+    static constexpr long long own_row = 0;
+    __device__ long long row(int j) const { return first + j; }
+    __device__ bool allowed(int j) const { return keymask[j] != 0; }
+};
+// a position per row (ctc_lm.hip): key j is the absolute cache row ids[j], every key allowed (a CTC hypothesis holds no padding)
+struct GaRowKeys {
+    const int* ids;  // the row's [table_stride] entries
+    int n, ld, own;
+    long long own_row;
+    __device__ long long row(int j) const { return ids[j]; }
+    __device__ bool allowed(int) const { return true; }
 };
 
-// element c of a row that starts at byte pointer `row` (c counted from the row's first column; for split-bf16 rows the start
-// must be a multiple of 32 columns): fp32 / bf16 elements are contiguous, a split-bf16 element is a bf16 hi half at
-// cn_split_off(c) and its lo half 64 bytes further
-template <typename T> __device__ __forceinline__ float ga_load(const unsigned char* row, int c) {
-    if constexpr (__is_same(T, split_t)) {
-        const unsigned char* e = row + cn_split_off((size_t)c);
-        return (float)*reinterpret_cast<const bf16*>(e) + (float)*reinterpret_cast<const bf16*>(e + 64);
-    } else {
-        return to_f32(reinterpret_cast<const T*>(row)[c]);
-    }
-}
-template <typename T> __device__ __forceinline__ void ga_store(unsigned char* row, int c, float v) {
-    if constexpr (__is_same(T, split_t)) {
-        unsigned char* e = row + cn_split_off((size_t)c);
-        const bf16 hi = (bf16)v;
-        *reinterpret_cast<bf16*>(e) = hi;
-        *reinterpret_cast<bf16*>(e + 64) = (bf16)(v - (float)hi);
-    } else {
-        reinterpret_cast<T*>(row)[c] = from_f32<T>(v);
-    }
-}
+// bytes per element of a row of T (a split-bf16 pair is 4); head hd of a row is 64 consecutive columns = 64 * ES contiguous bytes
+// in every layout
+template <typename T> constexpr int ga_elem_bytes = __is_same(T, split_t) ? 4 : (int)sizeof(T);
 
-template <typename T, int MODE>
-__global__ void ast_gather_attn_kernel(GatherAttnParams p) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+// sc: the wave's n scores in LDS
+template <typename T, typename Keys>
+__device__ __forceinline__ void ga_head(const Keys& ks, const void* q_base, int ldq, int d, const void* k_base, const void* v_base,
+                                        void* o_base, int ldo, float scale, float* sc) {
     const int h = blockIdx.x, lane = threadIdx.x & 63, hd = threadIdx.x >> 6;
-    float* sc = reinterpret_cast<float*>(smem) + (long long)hd * p.nkeys;
-    constexpr int ES = __is_same(T, split_t) ? 4 : (int)sizeof(T);  // bytes per element (a split-bf16 pair is 4)
-    // rows as byte pointers: head hd of a row is 64 consecutive columns = 64 * ES contiguous bytes in every layout
-    const unsigned char* qrow = reinterpret_cast<const unsigned char*>(p.q) + ((long long)h * p.ldq + hd * 64) * ES;
+    constexpr int ES = ga_elem_bytes<T>;
+    const unsigned char* qrow = reinterpret_cast<const unsigned char*>(q_base) + ((long long)h * ldq + hd * 64) * ES;
     float q[64];
 #pragma unroll
-    for (int i = 0; i < 64; ++i) q[i] = ga_load<T>(qrow, i);
-    const int u = MODE == 1 ? p.utt[h] : 0;
-    auto row_of = [&](int j) -> long long {
-        if (MODE == 0) return (long long)j * p.slots + p.anc[(long long)h * p.table_stride + j];
-        return (long long)u * p.nkeys + j;
-    };
-    const int kstride = MODE == 0 ? p.d : 2 * p.d;
-    const bool append = MODE == 0 && p.append_pos >= 0;
-    const unsigned char* new_k = qrow + (long long)p.d * ES;      // (head hd of this row's K | V in the fused projection)
-    const unsigned char* new_v = qrow + (long long)2 * p.d * ES;
-    const unsigned char* kb = reinterpret_cast<const unsigned char*>(p.k);
-    const unsigned char* vb = reinterpret_cast<const unsigned char*>(p.v);
+    for (int i = 0; i < 64; ++i) q[i] = cn_ld_row_elem<T>(qrow, i);
+    const bool append = ks.own >= 0;
+    const unsigned char* new_k = qrow + (long long)d * ES;  // (head hd of this row's K | V in the fused projection)
+    const unsigned char* new_v = qrow + (long long)2 * d * ES;
+    const unsigned char* kb = reinterpret_cast<const unsigned char*>(k_base);
+    const unsigned char* vb = reinterpret_cast<const unsigned char*>(v_base);
     if (append) {  // the head's 64 * ES bytes of K and of V, ES bytes per lane (a byte copy: any element layout)
-        const long long crow = (((long long)p.append_pos * p.slots + h) * p.d + hd * 64) * ES + lane * ES;
+        const long long crow = (ks.own_row * ks.ld + hd * 64) * ES + lane * ES;
         if constexpr (ES == 4) {
             *reinterpret_cast<unsigned*>(const_cast<unsigned char*>(kb) + crow) = *reinterpret_cast<const unsigned*>(new_k + lane * 4);
             *reinterpret_cast<unsigned*>(const_cast<unsigned char*>(vb) + crow) = *reinterpret_cast<const unsigned*>(new_v + lane * 4);
@@ -134,19 +123,18 @@ __global__ void ast_gather_attn_kernel(GatherAttnParams p) {
         }
     }
     float lmax = -INFINITY;
-    for (int j = lane; j < p.nkeys; j += 64) {
-        const unsigned char* kr = (append && j == p.append_pos) ? new_k : kb + (row_of(j) * kstride + hd * 64) * ES;
+    for (int j = lane; j < ks.n; j += 64) {
+        const unsigned char* kr = (append && j == ks.own) ? new_k : kb + (ks.row(j) * ks.ld + hd * 64) * ES;
         float dot = 0.f;
 #pragma unroll
-        for (int i = 0; i < 64; ++i) dot = fmaf(q[i], ga_load<T>(kr, i), dot);
-        const bool ok = MODE == 0 ? p.keyok[(long long)h * p.table_stride + j] != 0 : p.keymask[(long long)u * p.nkeys + j] != 0;
-        const float s = ok ? dot * p.scale : CN_NEG_FILL;
+        for (int i = 0; i < 64; ++i) dot = fmaf(q[i], cn_ld_row_elem<T>(kr, i), dot);
+        const float s = ks.allowed(j) ? dot * scale : CN_NEG_FILL;
         sc[j] = s;
         lmax = fmaxf(lmax, s);
     }
     lmax = wave_max(lmax);
     float lsum = 0.f;
-    for (int j = lane; j < p.nkeys; j += 64) {
+    for (int j = lane; j < ks.n; j += 64) {
         const float e = expf(sc[j] - lmax);
         sc[j] = e;
         lsum += e;
@@ -156,11 +144,49 @@ __global__ void ast_gather_attn_kernel(GatherAttnParams p) {
     // phase 2: lane = output dimension; LDS writes above are visible to the whole wave (same wave, program order)
     const float inv = 1.f / lsum;
     float acc = 0.f;
-    for (int j = 0; j < p.nkeys; ++j) {
-        const unsigned char* vr = (append && j == p.append_pos) ? new_v : vb + (row_of(j) * kstride + hd * 64) * ES;
-        acc = fmaf(sc[j], ga_load<T>(vr, lane), acc);
+    for (int j = 0; j < ks.n; ++j) {
+        const unsigned char* vr = (append && j == ks.own) ? new_v : vb + (ks.row(j) * ks.ld + hd * 64) * ES;
+        acc = fmaf(sc[j], cn_ld_row_elem<T>(vr, lane), acc);
     }
-    ga_store<T>(reinterpret_cast<unsigned char*>(p.o) + ((long long)h * p.ldo + hd * 64) * ES, lane, acc * inv);
+    cn_st_row_elem<T>(reinterpret_cast<unsigned char*>(o_base) + ((long long)h * ldo + hd * 64) * ES, lane, acc * inv);
+}
+
+//   MODE 0 (self, cache):  key j in [0, nkeys): row (j*slots + anc[h][j]) of ck / cv (row length d), allowed iff keyok[h][j];
+//                          append_pos >= 0: the row's own key, appended to cache row (append_pos, slot h)
+//   MODE 1 (source):       key j in [0, nkeys): row (utt[h]*nkeys + j) of the fused K|V matrix (row length 2d), allowed iff
+//                          keymask[utt[h]][j]
+template <typename T, int MODE>
+__global__ void ast_gather_attn_kernel(GatherAttnArgs p) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int h = blockIdx.x, hd = threadIdx.x >> 6;
+    float* sc = reinterpret_cast<float*>(smem) + (long long)hd * p.nkeys;
+    if constexpr (MODE == 0) {
+        const long long t = (long long)h * p.table_stride;
+        const GaCacheKeys ks{p.anc + t, p.keyok + t, p.slots, p.nkeys, p.d, p.append_pos, (long long)p.append_pos * p.slots + h};
+        ga_head<T>(ks, p.q, p.ldq, p.d, p.k, p.v, p.o, p.ldo, p.scale, sc);
+    } else {
+        const long long first = (long long)p.utt[h] * p.nkeys;
+        const GaSourceKeys ks{p.keymask + first, first, p.nkeys, 2 * p.d};
+        ga_head<T>(ks, p.q, p.ldq, p.d, p.k, p.v, p.o, p.ldo, p.scale, sc);
+    }
+}
+
+// launch(element type tag) for the rows of a precision: fp32, split-bf16 (strides in whole groups of 32 elements) or the 16-bit type
+template <typename Launch>
+static int ga_for_precision(int prec, const char* who, int ldq, int ldo, int d, Launch launch) {
+    if (prec == CN_PREC_F32) {
+        launch(float{});
+    } else if (prec == CN_PREC_X3) {
+        if (ldq % 32 || ldo % 32 || d % 32) {
+            cn_set_error(std::string(who) + ": split-bf16 rows need strides that are multiples of 32 elements");
+            return -1;
+        }
+        launch(split_t{});
+    } else {
+        launch(bf16{});
+    }
+    CN_HIP_CHECK(hipGetLastError());
+    return 0;
 }
 
 int launch_ast_gather_attn(int prec, int mode, const GatherAttnArgs& a, hipStream_t s) {
@@ -169,56 +195,27 @@ int launch_ast_gather_attn(int prec, int mode, const GatherAttnArgs& a, hipStrea
         cn_set_error("ast_gather_attn: need 1 <= heads <= 16 and at least one key");
         return -1;
     }
-    GatherAttnParams p;
-    p.q = a.q;
-    p.ldq = a.ldq;
-    p.k = a.k;
-    p.v = a.v;
-    p.o = a.o;
-    p.ldo = a.ldo;
-    p.n = a.n;
-    p.H = a.H;
-    p.nkeys = a.nkeys;
-    p.slots = a.slots;
-    p.d = a.d;
-    p.table_stride = a.table_stride;
-    p.anc = a.anc;
-    p.keyok = a.keyok;
-    p.utt = a.utt;
-    p.keymask = a.keymask;
-    p.scale = a.scale;
-    p.append_pos = mode == 0 ? a.append_pos : -1;
+    GatherAttnArgs p = a;
+    if (mode != 0) p.append_pos = -1;
     const size_t lds = (size_t)a.H * a.nkeys * sizeof(float);
     if (lds > 64 * 1024) {
         cn_set_error("ast_gather_attn: too many keys for the score buffer");
         return -1;
     }
     const dim3 grid(a.n), block(64 * a.H);
-    if (prec == CN_PREC_F32) {
-        if (mode == 0) hipLaunchKernelGGL((ast_gather_attn_kernel<float, 0>), grid, block, lds, s, p);
-        else hipLaunchKernelGGL((ast_gather_attn_kernel<float, 1>), grid, block, lds, s, p);
-    } else if (prec == CN_PREC_X3) {
-        if (a.ldq % 32 || a.ldo % 32 || a.d % 32) {
-            cn_set_error("ast_gather_attn: split-bf16 rows need strides that are multiples of 32 elements");
-            return -1;
-        }
-        if (mode == 0) hipLaunchKernelGGL((ast_gather_attn_kernel<split_t, 0>), grid, block, lds, s, p);
-        else hipLaunchKernelGGL((ast_gather_attn_kernel<split_t, 1>), grid, block, lds, s, p);
-    } else {
-        if (mode == 0) hipLaunchKernelGGL((ast_gather_attn_kernel<bf16, 0>), grid, block, lds, s, p);
-        else hipLaunchKernelGGL((ast_gather_attn_kernel<bf16, 1>), grid, block, lds, s, p);
-    }
-    CN_HIP_CHECK(hipGetLastError());
-    return 0;
+    return ga_for_precision(prec, "ast_gather_attn", a.ldq, a.ldo, a.d, [&](auto tag) {
+        using T = decltype(tag);
+        if (mode == 0) hipLaunchKernelGGL((ast_gather_attn_kernel<T, 0>), grid, block, lds, s, p);
+        else hipLaunchKernelGGL((ast_gather_attn_kernel<T, 1>), grid, block, lds, s, p);
+    });
 }
 
 // ---------------------------------------------------------------------------------------------
 // The same two kernels with a position PER ROW (ctc_lm.hip: the hypotheses of a CTC prefix beam have different lengths).
 //   embed:     x[h][:] = lut[tok[h]][:] * sqrt(d) + pe[pos[h]][:]
 //   attention: row h has pos[h] + 1 keys; key j is cache row rowid[h][j] (an absolute row of ck / cv, row length d), every key
-//              allowed (a CTC hypothesis holds no padding token).  stay[h] == 0: the row's own K | V (still in the projection
-//              buffer) are written to cache row rowid[h][pos[h]] and key pos[h] is read from the projection buffer, as MODE 0
-//              does with append_pos.  stay[h] != 0: the hypothesis did not change - its LM row is carried by the caller - so the
+//              allowed.  stay[h] == 0: the row's own key is pos[h], appended to cache row rowid[h][pos[h]], as MODE 0 does with
+//              append_pos.  stay[h] != 0: the hypothesis did not change - its LM row is carried by the caller - so the
 //              workgroup appends nothing and writes a zero context row (rows are independent in everything downstream).
 // ---------------------------------------------------------------------------------------------
 __global__ void ast_embed_rows_kernel(const int* __restrict__ tok, const float* __restrict__ lut, const float* __restrict__ pe,
@@ -238,77 +235,18 @@ int launch_ast_embed_rows(const int* tok, const float* lut, const float* pe, con
     return 0;
 }
 
-struct GatherRowsParams {
-    const void* q;  // [n][ldq]: Q | K | V of the fused projection
-    int ldq;
-    void* k;
-    void* v;
-    void* o;
-    int ldo;
-    int d, table_stride, max_keys;
-    const int* rowid;  // [n][table_stride]
-    const int* pos;    // [n]
-    const int* stay;   // [n]
-    float scale;
-};
-
 template <typename T>
-__global__ void ast_gather_attn_rows_kernel(GatherRowsParams p) {
+__global__ void ast_gather_attn_rows_kernel(GatherRowsArgs p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int h = blockIdx.x, lane = threadIdx.x & 63, hd = threadIdx.x >> 6;
-    constexpr int ES = __is_same(T, split_t) ? 4 : (int)sizeof(T);
-    unsigned char* orow = reinterpret_cast<unsigned char*>(p.o) + ((long long)h * p.ldo + hd * 64) * ES;
-    const int apos = p.pos[h], nkeys = apos + 1;
+    const int apos = p.pos[h];
     if (p.stay[h] || apos < 0 || apos >= p.max_keys) {  // (a position outside the score buffer: nothing is read or written through it)
-        ga_store<T>(orow, lane, 0.f);
+        cn_st_row_elem<T>(reinterpret_cast<unsigned char*>(p.o) + ((long long)h * p.ldo + hd * 64) * ga_elem_bytes<T>, lane, 0.f);
         return;
     }
-    float* sc = reinterpret_cast<float*>(smem) + (long long)hd * p.max_keys;
-    const unsigned char* qrow = reinterpret_cast<const unsigned char*>(p.q) + ((long long)h * p.ldq + hd * 64) * ES;
-    float q[64];
-#pragma unroll
-    for (int i = 0; i < 64; ++i) q[i] = ga_load<T>(qrow, i);
     const int* ids = p.rowid + (long long)h * p.table_stride;
-    const unsigned char* new_k = qrow + (long long)p.d * ES;
-    const unsigned char* new_v = qrow + (long long)2 * p.d * ES;
-    unsigned char* kb = reinterpret_cast<unsigned char*>(p.k);
-    unsigned char* vb = reinterpret_cast<unsigned char*>(p.v);
-    {
-        const long long crow = ((long long)ids[apos] * p.d + hd * 64) * ES + lane * ES;
-        if constexpr (ES == 4) {
-            *reinterpret_cast<unsigned*>(kb + crow) = *reinterpret_cast<const unsigned*>(new_k + lane * 4);
-            *reinterpret_cast<unsigned*>(vb + crow) = *reinterpret_cast<const unsigned*>(new_v + lane * 4);
-        } else {
-            *reinterpret_cast<unsigned short*>(kb + crow) = *reinterpret_cast<const unsigned short*>(new_k + lane * 2);
-            *reinterpret_cast<unsigned short*>(vb + crow) = *reinterpret_cast<const unsigned short*>(new_v + lane * 2);
-        }
-    }
-    float lmax = -INFINITY;
-    for (int j = lane; j < nkeys; j += 64) {
-        const unsigned char* kr = j == apos ? new_k : kb + ((long long)ids[j] * p.d + hd * 64) * ES;
-        float dot = 0.f;
-#pragma unroll
-        for (int i = 0; i < 64; ++i) dot = fmaf(q[i], ga_load<T>(kr, i), dot);
-        const float s = dot * p.scale;
-        sc[j] = s;
-        lmax = fmaxf(lmax, s);
-    }
-    lmax = wave_max(lmax);
-    float lsum = 0.f;
-    for (int j = lane; j < nkeys; j += 64) {
-        const float e = expf(sc[j] - lmax);
-        sc[j] = e;
-        lsum += e;
-    }
-    lsum = wave_sum(lsum);
-    __builtin_amdgcn_wave_barrier();
-    const float inv = 1.f / lsum;
-    float acc = 0.f;
-    for (int j = 0; j < nkeys; ++j) {
-        const unsigned char* vr = j == apos ? new_v : vb + ((long long)ids[j] * p.d + hd * 64) * ES;
-        acc = fmaf(sc[j], ga_load<T>(vr, lane), acc);
-    }
-    ga_store<T>(orow, lane, acc * inv);
+    const GaRowKeys ks{ids, apos + 1, p.d, apos, ids[apos]};
+    ga_head<T>(ks, p.q, p.ldq, p.d, p.k, p.v, p.o, p.ldo, p.scale, reinterpret_cast<float*>(smem) + (long long)hd * p.max_keys);
 }
 
 int launch_ast_gather_attn_rows(int prec, const GatherRowsArgs& a, hipStream_t s) {
@@ -317,39 +255,15 @@ int launch_ast_gather_attn_rows(int prec, const GatherRowsArgs& a, hipStream_t s
         cn_set_error("ast_gather_attn_rows: need 1 <= heads <= 16, 1 <= max_keys <= table_stride and the row tables");
         return -1;
     }
-    GatherRowsParams p;
-    p.q = a.q;
-    p.ldq = a.ldq;
-    p.k = a.k;
-    p.v = a.v;
-    p.o = a.o;
-    p.ldo = a.ldo;
-    p.d = a.d;
-    p.table_stride = a.table_stride;
-    p.max_keys = a.max_keys;
-    p.rowid = a.rowid;
-    p.pos = a.pos;
-    p.stay = a.stay;
-    p.scale = a.scale;
     const size_t lds = (size_t)a.H * a.max_keys * sizeof(float);
     if (lds > 64 * 1024) {
         cn_set_error("ast_gather_attn_rows: too many keys for the score buffer");
         return -1;
     }
     const dim3 grid(a.n), block(64 * a.H);
-    if (prec == CN_PREC_F32) {
-        hipLaunchKernelGGL((ast_gather_attn_rows_kernel<float>), grid, block, lds, s, p);
-    } else if (prec == CN_PREC_X3) {
-        if (a.ldq % 32 || a.ldo % 32 || a.d % 32) {
-            cn_set_error("ast_gather_attn_rows: split-bf16 rows need strides that are multiples of 32 elements");
-            return -1;
-        }
-        hipLaunchKernelGGL((ast_gather_attn_rows_kernel<split_t>), grid, block, lds, s, p);
-    } else {
-        hipLaunchKernelGGL((ast_gather_attn_rows_kernel<bf16>), grid, block, lds, s, p);
-    }
-    CN_HIP_CHECK(hipGetLastError());
-    return 0;
+    return ga_for_precision(prec, "ast_gather_attn_rows", a.ldq, a.ldo, a.d, [&](auto tag) {
+        hipLaunchKernelGGL((ast_gather_attn_rows_kernel<decltype(tag)>), grid, block, lds, s, a);
+    });
 }
 
 // ---------------------------------------------------------------------------------------------

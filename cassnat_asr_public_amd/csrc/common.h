@@ -201,6 +201,9 @@ template <typename T> __device__ __forceinline__ void cn_st_elem(void* base, lon
         reinterpret_cast<T*>(base)[row * ld + c] = from_f32<T>(v);
     }
 }
+// the same for a row given by the byte pointer of its first column (split-bf16: a multiple of 32 columns into its matrix row)
+template <typename T> __device__ __forceinline__ float cn_ld_row_elem(const void* row, int c) { return cn_ld_elem<T>(row, 0, 0, c); }
+template <typename T> __device__ __forceinline__ void cn_st_row_elem(void* row, int c, float v) { cn_st_elem<T>(row, 0, 0, c, v); }
 
 // 16-byte global load / LDS store helpers on raw bytes.
 __device__ __forceinline__ uint4 ld16(const void* p) { return *reinterpret_cast<const uint4*>(p); }
@@ -283,7 +286,7 @@ __device__ __forceinline__ float wave_max(float v) {
 #include <string>
 void cn_set_error(const std::string& msg);
 // The internal precision of a public CN_PRECISION_* request, or -1 (error set, prefixed with `who`) when it belongs to the
-// other build of the library (model.hip)
+// other build of the library (handle.hip)
 int cn_own_precision(int32_t precision, const char* who);
 #define CN_HIP_CHECK(expr)                                                                        \
     do {                                                                                          \

@@ -6,65 +6,25 @@
 // the next beam with the ancestor / key-mask tables the next LM step gathers through.  Nothing returns to the host inside
 // the loop: utterance b consumes steps 0 .. last[b] = min(ylen[b], ymax - 1), which the host knows before it starts.
 #include "kernels.h"
-
-namespace {
-// (value, index) maximum, ties to the lower index: over the entries a thread owns, then over the workgroup (4 waves).  A NaN
-// entry is never chosen (both comparisons are false): that is how a selected entry is retired, so a row with fewer than k
-// entries above -inf (an -inf LM logit of an overflowing half-precision engine) yields its -inf entries one by one, lower index
-// first, as torch.topk would - never an index twice.  No entry left (NaNs only): index 0x7fffffff, value -inf.
-__device__ __forceinline__ void nl_local_best(const float* row, int V, int tid, float& best, int& bidx) {
-    best = -INFINITY;
-    bidx = 0x7fffffff;
-    for (int i = tid; i < V; i += 256) {
-        const float v = row[i];
-        if (v > best || (v == best && i < bidx)) {
-            best = v;
-            bidx = i;
-        }
-    }
-}
-__device__ __forceinline__ void nl_block_best(float* s_val, int* s_idx, int lane, int wave, float& best, int& bidx) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(best, o);
-        const int oi = __shfl_xor(bidx, o);
-        if (ov > best || (ov == best && oi < bidx)) {
-            best = ov;
-            bidx = oi;
-        }
-    }
-    if (lane == 0) {
-        s_val[wave] = best;
-        s_idx[wave] = bidx;
-    }
-    __syncthreads();
-    best = s_val[0];
-    bidx = s_idx[0];
-#pragma unroll
-    for (int w = 1; w < 4; ++w)
-        if (s_val[w] > best || (s_val[w] == best && s_idx[w] < bidx)) {
-            best = s_val[w];
-            bidx = s_idx[w];
-        }
-    __syncthreads();  // s_val / s_idx are rewritten by the next round
-}
-}  // namespace
+#include "rowreduce.h"
 
 // local_prob = att_prob + lm_weight * lm_prob; torch.topk(local_prob, beam_width) (cassnat.py:606-611).  One workgroup per
 // slot.  The attention operand is row (b, step) of the engine's LOG-PROBABILITY rows - it is not normalised again (what
 // logsoftmax_topk_kernel<true> does to its first operand) - or an all-zero row for a step at or past zlen[b] (ESA: att_out
 // masked by the selected sample's own length, cassnat.py:536).  The LM operand is the slot's row of raw logits: its maximum
-// and log-sum-exp in the same partition and order as logsoftmax_topk_kernel / logsoftmax_gather_kernel, then every entry
-// becomes att + fl32(w * ((x - max) - lse)), float32 with one rounding per operation (no FMA contraction), and k rounds
-// select on that sum (sorted descending, ties: lower index first).
+// and log-sum-exp by rowreduce.h, as in logsoftmax_topk_kernel / logsoftmax_gather_kernel, then every entry becomes
+// att + fl32(w * ((x - max) - lse)), float32 with one rounding per operation (no FMA contraction), and k rounds select on that
+// sum (sorted descending, ties: lower index first).  A selected entry is retired with a NaN, which is never chosen again: a row
+// with fewer than k entries above -inf (an -inf LM logit of an overflowing half-precision engine) yields its -inf entries one
+// by one, lower index first, as torch.topk would - never an index twice.
 __global__ __launch_bounds__(256) void nat_lm_fuse_topk_kernel(NatFuseArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float* row = reinterpret_cast<float*>(smem);
-    __shared__ float s_val[4], s_sum[4];
-    __shared__ int s_idx[4];
+    __shared__ RowReduceLds red;
     const int slot = blockIdx.x, b = slot / a.bw;
-    if (a.last && a.step > a.last[b]) return;  // the utterance has ended: its beams are carried, nothing reads this slot's row
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, V = a.V;
+    // the utterance has ended: its beams are carried, nothing reads this slot's row (the whole workgroup leaves, before any barrier)
+    if (a.last && a.step > a.last[b]) return;
+    const int tid = threadIdx.x, V = a.V;
     const float* pl = a.lm + (long long)slot * V;
     const bool zero = a.zlen && a.step >= a.zlen[b];
     const float* pa = a.att + ((long long)b * a.U + a.step) * V;
@@ -74,36 +34,15 @@ __global__ __launch_bounds__(256) void nat_lm_fuse_topk_kernel(NatFuseArgs a) {
         row[i] = v;
         lbest = fmaxf(lbest, v);
     }
-    lbest = wave_max(lbest);
-    if (lane == 0) s_val[wave] = lbest;
-    __syncthreads();
-    const float lmax = fmaxf(fmaxf(s_val[0], s_val[1]), fmaxf(s_val[2], s_val[3]));
-    float lsum = 0.f;
-    for (int i = tid; i < V; i += 256) lsum += expf(row[i] - lmax);
-    lsum = wave_sum(lsum);
-    if (lane == 0) s_sum[wave] = lsum;
-    __syncthreads();  // (also: s_val has been read by every thread before the selection rounds rewrite it)
-    const float llse = logf((s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]));
-    // (a thread only reads the entries it wrote until the first nl_block_best: no barrier needed before it)
+    const float lmax = rr_block_max(red, tid, lbest);
+    const float llse = rr_block_lse(red, row, V, tid, lmax);
     for (int i = tid; i < V; i += 256)
         row[i] = __fadd_rn(zero ? 0.f : pa[i], cn_mul_rn(a.w, __fsub_rn(__fsub_rn(row[i], lmax), llse)));
-    float mybest, best;
-    int myidx, bidx;
-    nl_local_best(row, V, tid, mybest, myidx);
-    for (int r = 0; r < a.k; ++r) {
-        best = mybest;
-        bidx = myidx;
-        nl_block_best(s_val, s_idx, lane, wave, best, bidx);
-        if (tid == 0) {
-            // (a row of NaNs has no winner: token 0 then, never an index outside the vocabulary - it becomes an embedding row)
-            a.idx[(long long)slot * a.k + r] = bidx < V ? bidx : 0;
-            a.val[(long long)slot * a.k + r] = best;
-        }
-        if (bidx < V && (bidx & 255) == tid) {  // the owner retires the winner and finds its next candidate
-            row[bidx] = __builtin_nanf("");
-            nl_local_best(row, V, tid, mybest, myidx);
-        }
-    }
+    rr_select_rounds(red, row, V, tid, a.k, __builtin_nanf(""), [&](int r, int bidx, float best) {
+        // (a row of NaNs has no winner: token 0 then, never an index outside the vocabulary - it becomes an embedding row)
+        a.idx[(long long)slot * a.k + r] = bidx < V ? bidx : 0;
+        a.val[(long long)slot * a.k + r] = best;
+    });
 }
 
 int launch_nat_lm_fuse_topk(const NatFuseArgs& a, int slots, hipStream_t s) {

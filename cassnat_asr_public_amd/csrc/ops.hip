@@ -921,6 +921,41 @@ extern "C" int cn_op_ast_gather_attn(int32_t precision, int32_t mode, const void
     return launch_ast_gather_attn(precision, mode, a, (hipStream_t)stream);
 }
 
+extern "C" int cn_op_ast_gather_attn_rows(int32_t precision, const void* q, int32_t ldq, void* k, void* v, void* o, int32_t ldo, int32_t n,
+                                          int32_t H, int32_t d, int32_t table_stride, int32_t max_keys, const int32_t* rowid,
+                                          const int32_t* pos, const int32_t* stay, float scale, void* stream) {
+    if ((precision = cn_own_precision(precision, "cn_op_ast_gather_attn_rows")) < 0) return -1;
+    if (precision != CN_PREC_F32 && precision != CN_PREC_BF16 && precision != CN_PREC_X3) {
+        cn_set_error("cn_op_ast_gather_attn_rows: precision must be F32, BF16 (F16 in the half-precision build) or BF16X3");
+        return -1;
+    }
+    if (n < 0 || H < 1 || H > 16 || d != 64 * H || max_keys < 1 || ldo < d || ldq < 3 * d || !q || !k || !v || (n > 0 && !o)) {
+        cn_set_error("cn_op_ast_gather_attn_rows: need 1 <= H <= 16, d = 64 * H, max_keys >= 1, ldo >= d and ldq >= 3d");
+        return -1;
+    }
+    if (table_stride < max_keys || !rowid || !pos || !stay) {
+        cn_set_error("cn_op_ast_gather_attn_rows: need table_stride >= max_keys and the rowid, pos and stay tables");
+        return -1;
+    }
+    GatherRowsArgs a;
+    a.q = q;
+    a.ldq = ldq;
+    a.k = k;
+    a.v = v;
+    a.o = o;
+    a.ldo = ldo;
+    a.n = n;
+    a.H = H;
+    a.d = d;
+    a.table_stride = table_stride;
+    a.max_keys = max_keys;
+    a.rowid = rowid;
+    a.pos = pos;
+    a.stay = stay;
+    a.scale = scale;
+    return launch_ast_gather_attn_rows(precision, a, (hipStream_t)stream);
+}
+
 extern "C" int cn_op_ast_ctc_prepare(float* logp, const uint8_t* keymask, float* r0, int32_t B, int32_t Tp, int32_t V, int32_t blank,
                                      void* stream) {
     if (B < 1 || Tp < 1 || V < 1 || blank < 0 || blank >= V || !logp || !keymask || !r0) {

@@ -1,6 +1,7 @@
 // Row-wise, HBM-bound kernels of the hot path: the reference's custom LayerNorm, the generator's
 // log-softmax + argmax, the padding mask, query-table broadcast and precision converts.
 #include "kernels.h"
+#include "rowreduce.h"
 
 // ---------------------------------------------------------------------------------------------
 // LayerNorm exactly as src/models/modules/norm.py:15-18: unbiased std (divide by d-1), eps added to
@@ -140,59 +141,25 @@ int launch_quantize_fp8(const void* src_bf16, int ld, void* dst, int M, int K, f
 // ---------------------------------------------------------------------------------------------
 // Generator tail (src/models/cassnat.py:113 log_softmax, :378 argmax, :611 topk(1)): per row of
 // fp32 logits the first-index argmax and its log-probability (x - max) - log(sum exp(x - max));
-// optionally the row is rewritten in place as log-probabilities.  One workgroup per row.
+// optionally the row is rewritten in place as log-probabilities.  One workgroup per row.  The
+// reductions of this and the three kernels below are rowreduce.h's: one partition, one order.
 // ---------------------------------------------------------------------------------------------
 // temperature: Generator.forward(x, T) = log_softmax(proj(x) / T) (src/models/transformer.py:48-51); 1.0 = no division
 __global__ __launch_bounds__(256) void logsoftmax_argmax_kernel(float* __restrict__ logits, int V, int ldl,
                                                                 int* __restrict__ arg, float* __restrict__ maxlp,
                                                                 int write_logp, float temperature) {
-    __shared__ float s_val[4];
-    __shared__ int s_idx[4];
-    __shared__ float s_sum[4];
+    __shared__ RowReduceLds red;
     float* p = logits + (long long)blockIdx.x * ldl;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     if (temperature != 1.0f) {
         for (int i = tid; i < V; i += 256) p[i] = p[i] / temperature;
         __syncthreads();
     }
-    float best = -INFINITY;
-    int bidx = 0x7fffffff;
-    for (int i = tid; i < V; i += 256) {
-        const float v = p[i];
-        if (v > best || (v == best && i < bidx)) {
-            best = v;
-            bidx = i;
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(best, o);
-        const int oi = __shfl_xor(bidx, o);
-        if (ov > best || (ov == best && oi < bidx)) {
-            best = ov;
-            bidx = oi;
-        }
-    }
-    if (lane == 0) {
-        s_val[wave] = best;
-        s_idx[wave] = bidx;
-    }
-    __syncthreads();
-    best = s_val[0];
-    bidx = s_idx[0];
-#pragma unroll
-    for (int w = 1; w < 4; ++w) {
-        if (s_val[w] > best || (s_val[w] == best && s_idx[w] < bidx)) {
-            best = s_val[w];
-            bidx = s_idx[w];
-        }
-    }
-    float sum = 0.f;
-    for (int i = tid; i < V; i += 256) sum += expf(p[i] - best);
-    sum = wave_sum(sum);
-    if (lane == 0) s_sum[wave] = sum;
-    __syncthreads();
-    const float lse = logf((s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]));
+    float best;
+    int bidx;
+    rr_local_best(p, V, tid, best, bidx);
+    rr_block_argmax(red, tid, best, bidx);
+    const float lse = rr_block_lse(red, p, V, tid, best);
     if (tid == 0) {
         arg[blockIdx.x] = bidx;
         maxlp[blockIdx.x] = -lse;
@@ -216,57 +183,19 @@ int launch_logsoftmax_temp(float* logits, int M, int V, int ldl, float temperatu
     return 0;
 }
 
-// per-row top-k of log-probs (beam_width > 1, src/models/cassnat.py:611). Row staged in LDS, k rounds.
+// per-row top-k of log-probs (beam_width > 1, src/models/cassnat.py:611). Row staged in LDS (every thread its own entries), k rounds.
 __global__ __launch_bounds__(256) void topk_kernel(const float* __restrict__ logp, int V, int ldl, int k,
                                                    int* __restrict__ idx, float* __restrict__ val) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float* row = reinterpret_cast<float*>(smem);
-    __shared__ float s_val[4];
-    __shared__ int s_idx[4];
+    __shared__ RowReduceLds red;
     const float* p = logp + (long long)blockIdx.x * ldl;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     for (int i = tid; i < V; i += 256) row[i] = p[i];
-    __syncthreads();
-    for (int r = 0; r < k; ++r) {
-        float best = -INFINITY;
-        int bidx = 0x7fffffff;
-        for (int i = tid; i < V; i += 256) {
-            const float v = row[i];
-            if (v > best || (v == best && i < bidx)) {
-                best = v;
-                bidx = i;
-            }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ov = __shfl_xor(best, o);
-            const int oi = __shfl_xor(bidx, o);
-            if (ov > best || (ov == best && oi < bidx)) {
-                best = ov;
-                bidx = oi;
-            }
-        }
-        if (lane == 0) {
-            s_val[wave] = best;
-            s_idx[wave] = bidx;
-        }
-        __syncthreads();
-        best = s_val[0];
-        bidx = s_idx[0];
-#pragma unroll
-        for (int w = 1; w < 4; ++w) {
-            if (s_val[w] > best || (s_val[w] == best && s_idx[w] < bidx)) {
-                best = s_val[w];
-                bidx = s_idx[w];
-            }
-        }
-        if (tid == 0) {
-            idx[(long long)blockIdx.x * k + r] = bidx;
-            val[(long long)blockIdx.x * k + r] = best;
-            if (bidx < V) row[bidx] = -INFINITY;
-        }
-        __syncthreads();
-    }
+    rr_select_rounds(red, row, V, tid, k, -INFINITY, [&](int r, int bidx, float best) {
+        idx[(long long)blockIdx.x * k + r] = bidx;
+        val[(long long)blockIdx.x * k + r] = best;
+    });
 }
 
 int launch_topk(const float* logp, int M, int V, int ldl, int k, int* idx, float* val, hipStream_t s) {
@@ -296,64 +225,18 @@ __global__ __launch_bounds__(256) void logsoftmax_topk_kernel(const float* __res
                                                               const float* __restrict__ lm, float w) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float* row = reinterpret_cast<float*>(smem);
-    __shared__ float s_val[4], s_sum[4];
-    __shared__ int s_idx[4];
+    __shared__ RowReduceLds red;
     const float* p = logits + (long long)blockIdx.x * ldl;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    auto local_best = [&](float& best, int& bidx) {
-        best = -INFINITY;
-        bidx = 0x7fffffff;
-        for (int i = tid; i < V; i += 256) {
-            const float v = row[i];
-            if (v > best || (v == best && i < bidx)) {
-                best = v;
-                bidx = i;
-            }
-        }
-    };
-    auto block_best = [&](float& best, int& bidx) {  // all threads return the winner
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ov = __shfl_xor(best, o);
-            const int oi = __shfl_xor(bidx, o);
-            if (ov > best || (ov == best && oi < bidx)) {
-                best = ov;
-                bidx = oi;
-            }
-        }
-        if (lane == 0) {
-            s_val[wave] = best;
-            s_idx[wave] = bidx;
-        }
-        __syncthreads();
-        best = s_val[0];
-        bidx = s_idx[0];
-#pragma unroll
-        for (int w = 1; w < 4; ++w)
-            if (s_val[w] > best || (s_val[w] == best && s_idx[w] < bidx)) {
-                best = s_val[w];
-                bidx = s_idx[w];
-            }
-        __syncthreads();  // s_val / s_idx are rewritten by the next round
-    };
+    const int tid = threadIdx.x;
     if (temperature != 1.0f)
         for (int i = tid; i < V; i += 256) row[i] = p[i] / temperature;
     else
         for (int i = tid; i < V; i += 256) row[i] = p[i];
-    // (a thread only ever reads the entries it wrote until the first block_best: no barrier needed before it)
-    float mybest;
-    int myidx;
-    local_best(mybest, myidx);
-    float best = mybest;
-    int bidx = myidx;
-    block_best(best, bidx);
-    const float rmax = best;
-    float sum = 0.f;
-    for (int i = tid; i < V; i += 256) sum += expf(row[i] - rmax);
-    sum = wave_sum(sum);
-    if (lane == 0) s_sum[wave] = sum;
-    __syncthreads();
-    const float lse = logf((s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]));
+    float rmax;
+    int rarg;
+    rr_local_best(row, V, tid, rmax, rarg);
+    rr_block_argmax(red, tid, rmax, rarg);
+    const float lse = rr_block_lse(red, row, V, tid, rmax);
     // the selection ranks the LOG-PROBABILITIES, as the two-kernel form and the reference do: two logits one ulp apart can
     // round to the same log-probability, and the tie then goes to the lower index
     if constexpr (FUSE) {
@@ -365,37 +248,17 @@ __global__ __launch_bounds__(256) void logsoftmax_topk_kernel(const float* __res
             lrow[i] = v;
             lbest = fmaxf(lbest, v);
         }
-        lbest = wave_max(lbest);
-        __syncthreads();  // s_sum of the attention row has been read by every thread
-        if (lane == 0) s_val[wave] = lbest;
-        __syncthreads();
-        const float lmax = fmaxf(fmaxf(s_val[0], s_val[1]), fmaxf(s_val[2], s_val[3]));
-        float lsum = 0.f;
-        for (int i = tid; i < V; i += 256) lsum += expf(lrow[i] - lmax);
-        lsum = wave_sum(lsum);
-        if (lane == 0) s_sum[wave] = lsum;
-        __syncthreads();
-        const float llse = logf((s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]));
-        __syncthreads();  // s_val is rewritten by the selection rounds
+        const float lmax = rr_block_max(red, tid, lbest);
+        const float llse = rr_block_lse(red, lrow, V, tid, lmax);
         for (int i = tid; i < V; i += 256)
             row[i] = __fadd_rn(__fsub_rn(__fsub_rn(row[i], rmax), lse), cn_mul_rn(w, __fsub_rn(__fsub_rn(lrow[i], lmax), llse)));
     } else {
         for (int i = tid; i < V; i += 256) row[i] = (row[i] - rmax) - lse;
     }
-    local_best(mybest, myidx);
-    for (int r = 0; r < k; ++r) {
-        best = mybest;
-        bidx = myidx;
-        block_best(best, bidx);
-        if (tid == 0) {
-            idx[(long long)blockIdx.x * k + r] = bidx;
-            val[(long long)blockIdx.x * k + r] = best;
-        }
-        if (bidx < V && (bidx & 255) == tid) {  // the owner retires the winner and finds its next candidate
-            row[bidx] = -INFINITY;
-            local_best(mybest, myidx);
-        }
-    }
+    rr_select_rounds(red, row, V, tid, k, -INFINITY, [&](int r, int bidx, float best) {
+        idx[(long long)blockIdx.x * k + r] = bidx;
+        val[(long long)blockIdx.x * k + r] = best;
+    });
 }
 
 int launch_logsoftmax_topk(const float* logits, int M, int V, int ldl, float temperature, int k, int* idx, float* val,
@@ -425,31 +288,23 @@ int launch_logsoftmax_fuse_topk(const float* att, const float* lm, int M, int V,
 }
 
 // LM shallow fusion with CTC (src/models/transformer.py:208-209, lm_prob.gather(1, indices)): per row the log-sum-exp of the LM
-// logits (temperature 1; same partition and order as logsoftmax_topk_kernel), then out[r][c] = (x[cand[r][c]] - max) - lse for
+// logits (temperature 1; rowreduce.h, as in logsoftmax_topk_kernel), then out[r][c] = (x[cand[r][c]] - max) - lse for
 // the k attention candidates.  One workgroup per row; the row is read once, into LDS.
 __global__ __launch_bounds__(256) void logsoftmax_gather_kernel(const float* __restrict__ logits, int V, int ldl,
                                                                 const int* __restrict__ cand, int k, float* __restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float* row = reinterpret_cast<float*>(smem);
-    __shared__ float s_val[4], s_sum[4];
+    __shared__ RowReduceLds red;
     const float* p = logits + (long long)blockIdx.x * ldl;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     float best = -INFINITY;
     for (int i = tid; i < V; i += 256) {
         const float v = p[i];
         row[i] = v;
         best = fmaxf(best, v);
     }
-    best = wave_max(best);
-    if (lane == 0) s_val[wave] = best;
-    __syncthreads();
-    const float rmax = fmaxf(fmaxf(s_val[0], s_val[1]), fmaxf(s_val[2], s_val[3]));
-    float sum = 0.f;
-    for (int i = tid; i < V; i += 256) sum += expf(row[i] - rmax);
-    sum = wave_sum(sum);
-    if (lane == 0) s_sum[wave] = sum;
-    __syncthreads();
-    const float lse = logf((s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]));
+    const float rmax = rr_block_max(red, tid, best);
+    const float lse = rr_block_lse(red, row, V, tid, rmax);
     if (tid < k) {
         const int c = cand[(long long)blockIdx.x * k + tid];
         out[(long long)blockIdx.x * k + tid] = (c >= 0 && c < V) ? (row[c] - rmax) - lse : -INFINITY;

@@ -714,6 +714,13 @@ int cn_op_logsoftmax_gather(const float* logits, int32_t M, int32_t V, const int
 int cn_op_ast_gather_attn(int32_t precision, int32_t mode, const void* q, int32_t ldq, void* k, void* v, void* o, int32_t ldo, int32_t n,
                           int32_t H, int32_t nkeys, int32_t slots, int32_t d, int32_t table_stride, const int32_t* anc, const uint8_t* keyok,
                           const int32_t* utt, const uint8_t* keymask, float scale, int32_t append_pos, void* stream);
+/* cn_op_ast_gather_attn_rows: mode 0 with a position per row (the LM step of the CTC prefix beam): row r has pos[r] + 1 keys, key j
+ *   is cache row rowid[r][j] of k / v [rows][d] (table [n][table_stride], table_stride >= max_keys), every key allowed; the row's own
+ *   K | V are written to cache row rowid[r][pos[r]] and key pos[r] is read from q's row.  A row with stay[r] != 0 or a position
+ *   outside [0, max_keys) reads and appends nothing and gets a zero output row. */
+int cn_op_ast_gather_attn_rows(int32_t precision, const void* q, int32_t ldq, void* k, void* v, void* o, int32_t ldo, int32_t n, int32_t H,
+                               int32_t d, int32_t table_stride, int32_t max_keys, const int32_t* rowid, const int32_t* pos,
+                               const int32_t* stay, float scale, void* stream);
 /* CTC side (src/utils/ctc_prefix.py): prepare masks logp [B][Tp][V] in place (frames with keymask 0: logzero, blank 0) and writes
  * the initial states r0 [B][Tp][2]; prefix scores the K candidates cand [n][K] of n prefixes of out_len tokens (0 <= out_len <= Tp)
  * -> score [n][K] and states r_new [n * K][Tp][2]; prev_ref[h] >= 0 takes row prev_ref[h] of r_prev, < 0 the initial state of

@@ -89,3 +89,24 @@ def test_gather_attention_refuses_bad_geometry(flavour):
     refused(L, gather_attn(L, own16, 0, 384, 128, table_stride=9), "table_stride >= nkeys")
     # 64 KB of scores per workgroup: H * nkeys <= 16384
     refused(L, gather_attn(L, own16, 1, 128, 128, nkeys=8193, slots=4, table_stride=8193), "score buffer")
+
+
+def gather_attn_rows(L, prec, H=2, d=128, ldq=384, ldo=128, table_stride=10, max_keys=10, rowid=P, pos=P, stay=P, n=4):
+    return L.cn_op_ast_gather_attn_rows(prec, P, ldq, P, P, P, ldo, n, H, d, table_stride, max_keys, rowid, pos, stay, 0.125, None)
+
+
+@pytest.mark.parametrize("flavour", FLAVOURS)
+def test_gather_attention_rows_refuses_bad_geometry(flavour):
+    L = hip.lib(flavour)
+    own16 = hip.PRECISION["fp16" if flavour == "f16" else "bf16"]
+    refused(L, gather_attn_rows(L, hip.PRECISION["bf16" if flavour == "f16" else "fp16"]), "F16")
+    refused(L, gather_attn_rows(L, own16, table_stride=9), "table_stride >= max_keys")
+    for missing in ("rowid", "pos", "stay"):
+        refused(L, gather_attn_rows(L, own16, **{missing: None}), "tables")
+    refused(L, gather_attn_rows(L, own16, H=17, d=17 * 64, ldq=3 * 17 * 64, ldo=17 * 64), "H <= 16")
+    refused(L, gather_attn_rows(L, own16, d=96), "d = 64 * H")
+    refused(L, gather_attn_rows(L, own16, max_keys=0), "max_keys >= 1")
+    refused(L, gather_attn_rows(L, own16, ldq=256), "ldq >= 3d")
+    refused(L, gather_attn_rows(L, own16, max_keys=8193, table_stride=8193), "score buffer")
+    if flavour != "f16":
+        refused(L, gather_attn_rows(L, hip.PRECISION["bf16x3"], ldq=384 + 16), "multiples of 32")

@@ -246,6 +246,111 @@ def test_gather_attention_against_float64(layout, mode):
     print(f"gather_attn {layout} mode {mode}: worst |out - fp64| {worst_abs:.2e} ({worst_ratio:.2f} of the fp32 bound)")
 
 
+def gather_rows_attn(L, prec, q_d, ldq, k_d, v_d, o, ldo, H, ts, max_keys, rowid, pos, stay, scale):
+    n, d = pos.numel(), 64 * H
+    tables = [t.to(torch.int32).cuda() for t in (rowid, pos, stay)]
+    hip.check(L.cn_op_ast_gather_attn_rows(prec, p(q_d), ldq, p(k_d), p(v_d), p(o), ldo, n, H, d, ts, max_keys, *[p(t) for t in tables],
+                                           scale, stream()), "cn_op_ast_gather_attn_rows", L)
+    torch.cuda.synchronize()
+
+
+def row_bytes(t):
+    return t.view(torch.uint8).reshape(t.shape[0], -1)
+
+
+@pytest.mark.parametrize("H", [1, 4])
+@pytest.mark.parametrize("layout", list(LAYOUTS))
+def test_gather_attention_rows_against_float64(layout, H):
+    """The form with a position per row (ast_gather_attn_rows_kernel): key counts on both sides of the 64-lane stride, cache rows
+    through a shuffled table whose stride is not max_keys, a "stay" row and a position outside the score buffer (both: a zero row,
+    nothing read or written).  Every cache row the launch has no business reading holds NaN."""
+    flavour, prec, operand = LAYOUTS[layout]
+    L = hip.lib(flavour)
+    assert L.cn_operand16().decode() == operand
+    g = torch.Generator().manual_seed(23 + H)
+    d, max_keys, ts, scale = 64 * H, 66, 70, 0.125
+    pos = torch.tensor([0, 1, 63, 64, 65, 2, max_keys], dtype=torch.int32)
+    stay = torch.tensor([0, 0, 0, 0, 0, 1, 0], dtype=torch.int32)
+    n = pos.numel()
+    live = [h for h in range(n) if not stay[h] and pos[h] < max_keys]
+    pad = 32 if layout == "bf16x3" else 16
+    ldq, ldo = 3 * d + pad, d + pad
+    rows = n * ts + 37
+    rowid = torch.randperm(rows, generator=g)[: n * ts].reshape(n, ts).to(torch.int32)  # distinct, in no order
+    held = torch.zeros(rows, dtype=torch.bool)  # cache rows that hold an earlier position of a live row
+    for h in live:
+        held[rowid[h, : pos[h]].long()] = True
+    kc, vc = torch.randn(rows, d, generator=g), torch.randn(rows, d, generator=g)
+    kc[~held], vc[~held] = float("nan"), float("nan")
+    q_d, q64 = to_layout(torch.randn(n, ldq, generator=g) * 2, layout)
+    k_d, k64 = to_layout(kc, layout)
+    v_d, v64 = to_layout(vc, layout)
+    k0, v0 = k_d.clone(), v_d.clone()
+    o = torch.ones(n, 2 * ldo if layout == "bf16x3" else ldo, dtype=q_d.dtype, device="cuda")
+    o0 = from_layout(o, layout)
+    gather_rows_attn(L, prec, q_d, ldq, k_d, v_d, o, ldo, H, ts, max_keys, rowid, pos, stay, scale)
+    got = from_layout(o, layout)
+    es = q_d.element_size() * (2 if layout == "bf16x3" else 1)
+    qb = row_bytes(q_d)
+    worst_ratio = 0.0
+    for h in range(n):
+        if h not in live:
+            assert torch.equal(got[h, :d], torch.zeros(d, dtype=torch.float64)), (layout, H, h)
+            continue
+        nk = int(pos[h]) + 1
+        ids = rowid[h, :nk].long()
+        Kg, Vg = k64[ids][None].clone(), v64[ids][None].clone()
+        Kg[0, nk - 1], Vg[0, nk - 1] = q64[h, d:2 * d], q64[h, 2 * d:3 * d]  # the row's own key comes from its projection row ...
+        row_bytes(k0)[int(ids[-1])] = qb[h, d * es:2 * d * es]  # ... and is written to its cache row byte for byte
+        row_bytes(v0)[int(ids[-1])] = qb[h, 2 * d * es:3 * d * es]
+        ref, bound = attn_model(q64[h:h + 1, :d], Kg, Vg, torch.ones(1, nk, dtype=torch.bool), H, scale)
+        err = (got[h:h + 1, :d] - ref).abs()
+        tol = bound + out_ulp(ref, layout)
+        assert (err <= tol).all(), (layout, H, h, nk, float(err.max()), float((err - tol).max()))
+        worst_ratio = max(worst_ratio, float((err / tol).max()))
+    assert torch.equal(got[:, d:], o0[:, d:])  # nothing past d
+    assert torch.equal(row_bytes(k_d), row_bytes(k0)) and torch.equal(row_bytes(v_d), row_bytes(v0))  # nothing else in the cache changes
+    print(f"gather_attn_rows {layout} H={H}: worst error {worst_ratio:.2f} of the fp32 bound")
+
+
+@pytest.mark.parametrize("nkeys", [1, 65])
+@pytest.mark.parametrize("layout", list(LAYOUTS))
+def test_gather_attention_rows_equal_the_cache_form_bitwise(layout, nkeys):
+    """With one position for every row, rowid[h][j] = j * slots + anc[h][j] and every key allowed, the rows form is MODE 0 with
+    append_pos: the same output bits and the same cache bytes."""
+    flavour, prec, _ = LAYOUTS[layout]
+    L = hip.lib(flavour)
+    g = torch.Generator().manual_seed(31 + nkeys)
+    H, n, scale = 2, 5, 0.125
+    d, slots, ts, append_pos = 64 * H, n + 3, nkeys + 5, nkeys - 1
+    pad = 32 if layout == "bf16x3" else 16
+    ldq, ldo = 3 * d + pad, d + pad
+    q_d, _ = to_layout(torch.randn(n, ldq, generator=g) * 2, layout)
+    k_d, _ = to_layout(torch.randn(nkeys * slots, d, generator=g), layout)
+    v_d, _ = to_layout(torch.randn(nkeys * slots, d, generator=g), layout)
+    anc = torch.randint(0, slots, (n, ts), generator=g, dtype=torch.int32)
+    anc[:, append_pos] = torch.arange(n, dtype=torch.int32)  # (append_pos, slot h) is where MODE 0 writes row h's K | V
+    rowid = torch.arange(ts, dtype=torch.int32)[None, :] * slots + anc
+    rowid[:, nkeys:] = 0  # (table entries past the keys: never read, and inside the cache if they were)
+    keyok = torch.ones(n, ts, dtype=torch.uint8)
+    outs = []
+    for form in ("cache", "rows"):
+        kk, vv = k_d.clone(), v_d.clone()
+        o = torch.zeros(n, 2 * ldo if layout == "bf16x3" else ldo, dtype=q_d.dtype, device="cuda")
+        if form == "cache":
+            anc_d, keyok_d = anc.cuda(), keyok.cuda()
+            hip.check(L.cn_op_ast_gather_attn(prec, 0, p(q_d), ldq, p(kk), p(vv), p(o), ldo, n, H, nkeys, slots, d, ts, p(anc_d),
+                                              p(keyok_d), None, None, scale, append_pos, stream()), "cn_op_ast_gather_attn", L)
+            torch.cuda.synchronize()
+        else:
+            gather_rows_attn(L, prec, q_d, ldq, kk, vv, o, ldo, H, ts, nkeys, rowid, torch.full((n,), append_pos, dtype=torch.int32),
+                             torch.zeros(n, dtype=torch.int32), scale)
+        outs.append([row_bytes(t).cpu().numpy() for t in (o, kk, vv)])
+    for a, b, what in zip(outs[0], outs[1], ("output", "K cache", "V cache")):
+        assert np.array_equal(a, b), (layout, nkeys, what)
+    assert not np.array_equal(outs[0][1], row_bytes(k_d).cpu().numpy())  # (the append happened)
+
+
 # ============================================================================================ CTC prefix scorer (ast.hip)
 def ctc_inputs(B, Tp, V, seed, blank=0):
     g = np.random.default_rng(seed)
