@@ -1,4 +1,5 @@
-"""The C ABI read from include/cassnat_hip.h, the only place that declares it: ``FUNCTIONS`` name -> (restype, argtypes),
+"""The C ABI read from include/cassnat_hip.h, the place that declares it (``EXTRA_FUNCTIONS``: the entry points of its companion
+include/cassnat_hip_ctc_ngram.h, read the same way): ``FUNCTIONS`` name -> (restype, argtypes),
 ``STRUCTS`` C name -> ctypes.Structure, ``CONSTANTS`` enum / #define name -> int.  It reads this project's header, not C in general:
 what it does not recognise raises ``AbiError`` naming the declaration.  Standard library only (no torch, numpy, library or GPU)."""
 import ctypes as C
@@ -50,8 +51,12 @@ class Abi:
         return out
 
 
-def parse(text):
+def parse(text, base=None):
+    """``base``: the Abi of a header this one includes; its structs and opaque types are known here, its functions are not repeated."""
     abi = Abi()
+    if base is not None:
+        abi.structs.update(base.structs)
+        abi.opaque.update(base.opaque)
     text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
     for name, value in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(CN_\w+)[ \t]+(-?\w+)[ \t]*$", text, re.M):
         abi.constants[name] = int(value, 0)
@@ -98,12 +103,16 @@ def parse(text):
 with open(HEADER_PATH) as _f:
     HEADER = parse(_f.read())
 FUNCTIONS, STRUCTS, CONSTANTS = HEADER.functions, HEADER.structs, HEADER.constants
+# the companion header of the CTC prefix beam search with word n-gram fusion: functions only, over cassnat_hip.h's types
+EXTRA_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "cassnat_hip_ctc_ngram.h")
+with open(EXTRA_HEADER_PATH) as _f:
+    EXTRA_FUNCTIONS = parse(_f.read(), base=HEADER).functions
 
 
 def bind(L):
-    """Set ``restype`` / ``argtypes`` of every declared function on the loaded library ``L``; a function the header declares and the
+    """Set ``restype`` / ``argtypes`` of every declared function on the loaded library ``L``; a function a header declares and the
     library lacks raises AttributeError."""
-    for name, (restype, argtypes) in FUNCTIONS.items():
+    for name, (restype, argtypes) in list(FUNCTIONS.items()) + list(EXTRA_FUNCTIONS.items()):
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     return L

@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <cmath>
 
+#include "ctc_ngram_search.h"
 #include "model.h"
 
 using namespace cn_host;
@@ -695,6 +696,71 @@ extern "C" int cn_ctc_beam(cn_model* m, const float* feats_dev, const float* siz
     a.n_out = nbeam_dev;
     ProfScope ps(m, "ctc_prefix_beam", 0, (double)M * (pruning + 1) * 4, s);
     return launch_ctc_prefix_beam(a, s);
+}
+
+// The same search with a word n-gram model fused (ctc_ngram.hip; not in the reference): encoder, CTC generator and pruning as
+// cn_ctc_beam, then one launch of the n-gram kernel.  Outputs as cn_ctc_beam_lm.
+extern "C" int cn_ctc_beam_ngram(cn_model* m, const cn_ngram_desc* desc, const float* feats_dev, const float* size_ratio_dev, int32_t B,
+                                 int32_t T, int32_t F, const cn_decode_opts* opts, int32_t beam, int32_t pruning, double length_penalty,
+                                 double lm_scale, int32_t* hyp_out_dev, int32_t hyp_cap, int32_t* hyp_len_dev, double* score_dev,
+                                 double* score_lm_dev, double* p_blk_dev, double* p_nblk_dev, int32_t* nbeam_dev, void* stream) {
+    CN_TRY(check_call(m, B, T, F));
+    if (!opts || !desc || m->cfg.ast == 2 || !m->ctc_gen.W || !size_ratio_dev) {
+        cn_set_error("cn_ctc_beam_ngram: needs a model with a CTC head, a cn_ngram_desc and decode options");
+        return -1;
+    }
+    // (the limits are looked at before anything is launched; launch_ctc_ngram_beam checks the rest of the desc before the search)
+    if (beam < 1 || beam > CG_MAX_BEAM || pruning < 0 || pruning > CG_MAX_PRUNE || desc->order < 1 || desc->order > NG_MAX_ORDER ||
+        !(lm_scale == lm_scale) || !hyp_out_dev || !hyp_len_dev || !score_dev || !score_lm_dev || !p_blk_dev || !p_nblk_dev || !nbeam_dev) {
+        cn_set_error("cn_ctc_beam_ngram: need 1 <= ctc_beam <= 32, 0 <= ctc_pruning <= 32, an order in 1 .. 8, lm_scale a number and all "
+                     "output buffers");
+        return -1;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    CN_HIP_CHECK(hipSetDevice(m->cfg.device));
+    CN_TRY(stage_encode_ctc_rows(m, feats_dev, B, T, F, opts, s));
+    const int Tp = m->Tp, M = B * Tp, V = m->cfg.vocab_size;
+    if (hyp_cap < Tp + 1) {
+        cn_set_error("cn_ctc_beam_ngram: hyp_cap must be at least T' + 1");
+        return -1;
+    }
+    CtcNgramArgs a;
+    a.d = *desc;
+    a.size_ratio = size_ratio_dev;
+    a.B = B;
+    a.Tp = Tp;
+    a.V = V;
+    a.P = pruning;
+    a.W = beam;
+    a.blank = opts->padding_idx;
+    a.Lmax = hyp_cap;
+    a.lp = length_penalty;
+    a.lm_scale = lm_scale;
+    a.hyp = hyp_out_dev;
+    a.hyp_len = hyp_len_dev;
+    a.score = score_dev;
+    a.score_lm = score_lm_dev;
+    a.p_blk = p_blk_dev;
+    a.p_nblk = p_nblk_dev;
+    a.n_out = nbeam_dev;
+    // (a capture run keeps the log-posteriors the search ran on: cn_fetch "ctc_out", as after cn_ctc_beam_lm)
+    if (opts->capture) CN_TRY(capture(m, "ctc_out", m->logits, false, CN_DTYPE_F32, {B, Tp, V}, s));
+    void *top_idx = nullptr, *top_val = nullptr, *hpar = nullptr, *htok = nullptr;
+    const int P = pruning > 0 ? pruning : 1;
+    CN_TRY(scratch_buf(m, "cb_top_idx", (size_t)M * P * 4, &top_idx));
+    CN_TRY(scratch_buf(m, "cb_top_val", (size_t)M * P * 4, &top_val));
+    CN_TRY(scratch_buf(m, "cb_hist_par", (size_t)M * beam, &hpar));
+    CN_TRY(scratch_buf(m, "cb_hist_tok", (size_t)M * beam * 4, &htok));
+    if (pruning > 0) {
+        ProfScope ps(m, "ctc_topk", 0, (double)M * V * 4, s);
+        CN_TRY(launch_topk(m->logits, M, V, V, pruning, (int*)top_idx, (float*)top_val, s));
+    }
+    a.logp = m->logits;
+    a.top_idx = (const int*)top_idx;
+    a.hist_parent = (unsigned char*)hpar;
+    a.hist_tok = (int*)htok;
+    ProfScope ps(m, "ctc_ngram_beam", 0, (double)M * (pruning + 1) * 4, s);
+    return launch_ctc_ngram_beam(a, s);
 }
 
 // CassNAT.beam_decode with decode_type 'ctc_att' and sample_num 1 (src/models/cassnat.py:446-448, 391-414): the trigger mask

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/cassnat_hip.h"
+#include "ctc_ngram_search.h"
 #include "flac_decode.h"
 #include "kernels.h"
 
@@ -1197,6 +1198,34 @@ extern "C" int cn_op_ctc_lm_rows(const float* fresh, const float* prv, float* nx
         return -1;
     }
     return launch_ctc_lm_rows(fresh, prv, nxt, parent, stay, count, iter, slots, W, V, (hipStream_t)stream);
+}
+
+// ctc_ngram.hip's kernel alone on given log-posteriors and given pruned labels (cn_ctc_beam_ngram runs it behind the encoder)
+extern "C" int cn_op_ctc_ngram_beam(const cn_ngram_desc* desc, const float* logp, const int32_t* top_idx, const float* size_ratio, int32_t B,
+                                    int32_t Tp, int32_t V, int32_t beam, int32_t pruning, double length_penalty, double lm_scale,
+                                    int32_t blank, int32_t* hyp, int32_t hyp_cap, int32_t* hyp_len, double* score, double* score_lm,
+                                    double* p_blk, double* p_nblk, int32_t* nbeam, void* stream) {
+    if (!desc) {
+        cn_set_error("cn_op_ctc_ngram_beam: null argument");
+        return -1;
+    }
+    CtcNgramArgs a;
+    a.d = *desc;
+    a.logp = logp, a.top_idx = top_idx, a.size_ratio = size_ratio;
+    a.B = B, a.Tp = Tp, a.V = V, a.P = pruning, a.W = beam, a.blank = blank, a.Lmax = hyp_cap;
+    a.lp = length_penalty, a.lm_scale = lm_scale;
+    a.hyp = hyp, a.hyp_len = hyp_len, a.score = score, a.score_lm = score_lm, a.p_blk = p_blk, a.p_nblk = p_nblk, a.n_out = nbeam;
+    const std::string bad = cg_check(a, false);
+    if (!bad.empty()) {
+        cn_set_error("cn_op_ctc_ngram_beam: " + bad);
+        return -1;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    Scratch sc("cn_op_ctc_ngram_beam", s);
+    a.hist_parent = (unsigned char*)sc.alloc((size_t)B * Tp * beam);
+    a.hist_tok = (int*)sc.alloc((size_t)B * Tp * beam * 4);
+    if (!sc.ok()) return -2;
+    return sc.finish(launch_ctc_ngram_beam(a, s));
 }
 
 extern "C" int cn_op_ffn_fused(float* x_dev, const float* ln_a_dev, const float* ln_b_dev, const float* w1_host,

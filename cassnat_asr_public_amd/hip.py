@@ -1,4 +1,4 @@
-"""ctypes binding of libcassnat_hip.so (the C ABI declared in include/cassnat_hip.h).
+"""ctypes binding of libcassnat_hip.so (the C ABI declared in include/cassnat_hip.h and its companion cassnat_hip_ctc_ngram.h).
 
 The product path has no CPU fallback: if the library is missing or a call fails, this raises.
 """
@@ -569,6 +569,24 @@ class Engine:
                                         int(pruning), float(length_penalty), float(lm_weight), _ptr(hyp), cap, _ptr(hlen), _ptr(sc),
                                         _ptr(slm), _ptr(pb), _ptr(pnb), _ptr(nb), C.byref(iters), current_stream()), "cn_ctc_beam_lm")
         return hyp, hlen, sc, slm, pb, pnb, nb, iters.value
+
+    def ctc_beam_ngram(self, desc, feats, size_ratio, opts, beam, pruning, length_penalty, lm_scale):
+        """CTC prefix beam search with a word n-gram model in the frame loop (``cn_ctc_beam_ngram``): ``desc`` a ``CnNgramDesc`` over
+        tables on the feats' device, ``lm_scale`` = ctc_lm_weight * ln(10) -> ``ctc_beam``'s tuple with score_lm (B, beam) float64
+        behind score_ctc."""
+        import torch
+
+        B, T, F = feats.shape
+        cap = subsampled(T) + 1
+        dev = feats.device
+        hyp = torch.empty(B, beam, cap, dtype=torch.int32, device=dev)
+        hlen = torch.empty(B, beam, dtype=torch.int32, device=dev)
+        sc, slm, pb, pnb = (torch.empty(B, beam, dtype=torch.float64, device=dev) for _ in range(4))
+        nb = torch.empty(B, dtype=torch.int32, device=dev)
+        self._chk(self.L.cn_ctc_beam_ngram(self.handle, C.byref(desc), _ptr(feats), _ptr(size_ratio), B, T, F, C.byref(opts), int(beam),
+                                           int(pruning), float(length_penalty), float(lm_scale), _ptr(hyp), cap, _ptr(hlen), _ptr(sc),
+                                           _ptr(slm), _ptr(pb), _ptr(pnb), _ptr(nb), current_stream()), "cn_ctc_beam_ngram")
+        return hyp, hlen, sc, slm, pb, pnb, nb
 
     def lm_step_rows(self, max_pos, tok, pos, stay, rowid, logp):
         self._chk(self.L.cn_lm_step_rows(self.handle, tok.shape[0], int(max_pos), _ptr(tok), _ptr(pos), _ptr(stay), _ptr(rowid),

@@ -9,11 +9,20 @@ the device (``cn_ctc_beam``; csrc/ctc_beam.hip).
 With ``lm_model`` a ``models.lm.TransformerLM`` and ``args.ctc_lm_weight > 0`` the reference's in-loop LM fusion runs on the
 device too (``cn_ctc_beam_lm``; csrc/ctc_lm.hip): one LM step per processed frame over all kept hypotheses, ``score_lm`` the
 reference's running sum over the pruned labels (it is not reset between the candidates of a hypothesis).  ``ctc_lm_weight == 0``
-with an LM at hand is the LM-free search (the reference runs the LM and adds zeros).  Any other ``lm_model`` object is refused.
+with an LM at hand is the LM-free search (the reference runs the LM and adds zeros).
+
+With ``lm_model`` a ``models.ngram.NgramLM`` (``rank_model: n-gram`` with an ARPA file) the search fuses the word n-gram model
+(``cn_ctc_beam_ngram``; csrc/ctc_ngram.hip; not in the reference): a candidate whose label begins a new word adds
+``ctc_lm_weight * ln(10)`` times the ARPA score of the word its parent had open, given the parent's word history; after the last
+frame every hypothesis adds its open word and ``</s>``.  The whole frame loop is one launch.  Any other ``lm_model`` object - a
+``kenlm.Model`` included - is refused.
 """
+import math
+
 import torch
 
 from .. import hip
+from ..models.ngram import NgramLM
 
 logzero, logone = -1e10, 0  # src/utils/ctc_prefix.py:11-12
 
@@ -21,9 +30,14 @@ logzero, logone = -1e10, 0  # src/utils/ctc_prefix.py:11-12
 def ctc_beam_decode(model, src, src_mask, src_size, vocab, args, lm_model=None, engine=None):
     """``model``: a CassNAT (src/tasks/cassnat_task.py:335-341) or the autoregressive Transformer with its CTC head
     (src/tasks/art_task.py:252-253).  ``engine``: run on this handle (a decode pipeline's) instead of the model's own."""
-    if lm_model is not None and not hasattr(lm_model, "step_engine"):
-        raise NotImplementedError("CTC beam search with in-loop LM fusion needs a models.lm.TransformerLM as lm_model (rank_model 'lm'); "
-                                  "%s is outside the accelerated path" % type(lm_model).__name__)
+    ngram = isinstance(lm_model, NgramLM)
+    if lm_model is not None and not ngram and not hasattr(lm_model, "step_engine"):
+        raise NotImplementedError("CTC beam search with in-loop LM fusion needs a models.lm.TransformerLM (rank_model 'lm') or a "
+                                  "models.ngram.NgramLM (rank_model 'n-gram' with an ARPA file) as lm_model; %s is outside the "
+                                  "accelerated path" % type(lm_model).__name__)
+    if ngram and float(getattr(args, "ctc_lm_weight", 0) or 0) != 0 and not lm_model.device_ok:
+        raise ValueError("a piece of the vocabulary has a separator behind its leading run: its hypotheses cannot be glued into words, "
+                         "so the CTC beam search cannot fuse the n-gram model")
     if args.ctc_lp is None:
         raise TypeError("ctc_lp must be a number (with None the reference's sort key is a lambda and sorted() fails)")
     sos = vocab.word2index["sos"]
@@ -39,7 +53,14 @@ def ctc_beam_decode(model, src, src_mask, src_size, vocab, args, lm_model=None, 
     opts.sos = sos
     lm_weight = float(getattr(args, "ctc_lm_weight", 0) or 0)
     slm = None
-    if lm_model is not None and lm_weight != 0:
+    if ngram and lm_weight != 0:
+        if dev not in lm_model._dev:
+            lm_model.cuda(dev)
+        # (ARPA scores are log10, the CTC scores natural logarithms)
+        hyp, hlen, sc, slm, pb, pnb, nb = eng.ctc_beam_ngram(lm_model.desc(dev), feats, ratio, opts, int(args.ctc_beam), int(args.ctc_pruning),
+                                                             float(args.ctc_lp), lm_weight * math.log(10.0))
+        slm = slm.cpu().numpy()
+    elif lm_model is not None and lm_weight != 0:
         lm_eng = lm_model.step_engine(B * int(args.ctc_beam))  # (one LM engine kept per model, as CassNAT._lm_finish's)
         hyp, hlen, sc, slm, pb, pnb, nb, _ = eng.ctc_beam_lm(lm_eng, feats, ratio, opts, int(args.ctc_beam), int(args.ctc_pruning),
                                                              float(args.ctc_lp), lm_weight)
