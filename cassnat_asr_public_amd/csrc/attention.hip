@@ -51,6 +51,11 @@ struct AttnParams {
     int rel_R, ld_pos;
     const int* row_off;  // (last: the other fields keep their offsets) packed query and, kv_packed, key rows: AttnArgs.row_off
     int kv_packed;
+    // PROJ form (behind the others, which keep their offsets): LNn(x) in the chain kernel's B-operand order, the 24 tail units of
+    // the Q|K|V projection and its 768 biases (AttnArgs.proj_y / proj_w / proj_b)
+    const unsigned char* Y;
+    const unsigned char* W;
+    const float* bt;
 };
 
 template <typename T> struct AttnCfg;
@@ -92,12 +97,18 @@ __device__ long long attn_stamps[8];
 // = one wave per SIMD = ONE 256-thread workgroup per CU, with two barriers and a global load round trip per key tile and nothing to
 // overlap them with; bounded to 256 registers two workgroups share a CU)
 // PK: packed rows (AttnArgs.row_off) - a form of its own, so that the launches without them keep their code
-template <typename T, int NW, bool RES, bool REL = false, bool PK = false>
+// PROJ (the resident 8-wave 16-bit form, self attention of at most 256 rows): Q, K and V do not come from memory - the workgroup
+// projects them itself from LNn(x) (p.Y, the chain kernel's blocked `ln_out`), with the tail units of the chain's own weight stream
+// (p.W) and the tail biases (p.bt), tile by tile in the instruction sequence of the chain kernel's tail (chain.hip, S5): the bits
+// are the ones that kernel would have written, and the 6 x d bytes per row of the Q|K|V round trip become 2 x d of LNn(x).  Each
+// wave projects its own 32 rows - as queries into `qf`, as keys / values into the LDS images the LDS-DMA path produces.
+template <typename T, int NW, bool RES, bool REL = false, bool PK = false, bool PROJ = false>
 __global__ __launch_bounds__(64 * NW, (RES && NW == 8) ? 4 : ((__is_same(T, split_t) && NW == 4 && !REL) ? 2 : 1)) void attention_kernel(AttnParams p) {
     typedef AttnCfg<T> Cfg;
     typedef typename Frag<T>::type frag_t;
     constexpr bool SPLIT = __is_same(T, split_t);
     static_assert(!SPLIT || !RES, "split-bf16 attention: the staged forms only");
+    static_assert(!PROJ || (RES && NW == 8 && !REL && !PK && sizeof(T) == 2), "the projecting form: resident, 8 waves, 16-bit operands");
     constexpr int KROW = Cfg::KROW, CPR = Cfg::CPR;
     constexpr int VROW = RES ? 128 : Cfg::VROW;  // RES: unpadded rows, 64-byte halves swapped on rows with (row>>1)&1
     constexpr int KT_BYTES = 64 * KROW, VT_BYTES = (SPLIT ? 2 : 1) * 64 * VROW, NRES = RES ? 4 : 1;
@@ -114,7 +125,17 @@ __global__ __launch_bounds__(64 * NW, (RES && NW == 8) ? 4 : ((__is_same(T, spli
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int half = lane >> 5, l31 = lane & 31;
-    const int b = blockIdx.z, h = blockIdx.y;
+    int b = blockIdx.z, h = blockIdx.y;
+    if constexpr (PROJ) {
+        // The four heads of an entry read the same rows of LNn(x): deal them to ONE XCD (workgroups go round-robin over the eight
+        // XCDs in launch order, id = h + 4 b), so that one L2 fetches the rows and three hit - among 32 consecutive ids, id % 8
+        // picks the entry of a group of eight and id / 8 the head.  (Entries behind the last whole group keep their ids.)
+        const int id = blockIdx.y + 4 * blockIdx.z, grp = id >> 5, r = id & 31;
+        if (grp < ((int)gridDim.z >> 3)) {
+            b = grp * 8 + (r & 7);
+            h = r >> 3;
+        }
+    }
     AT_STAMP(0)
     // the entry's query rows: Lq of them from row b * Lq on, or (packed) its own count from row_off[b] on - a workgroup past the
     // count leaves before anything is requested (uniform over the workgroup)
@@ -131,7 +152,9 @@ __global__ __launch_bounds__(64 * NW, (RES && NW == 8) ? 4 : ((__is_same(T, spli
     frag_t qf[NF];
     {
         const unsigned char* qp = p.Q + (q0 + qc) * p.ldq_b + (long long)h * KROW;
-        if constexpr (SPLIT) {
+        if constexpr (PROJ) {
+            (void)qp;  // (projected below, once V is in place)
+        } else if constexpr (SPLIT) {
 #pragma unroll
             for (int s = 0; s < NF; ++s) {  // k-step s: group s >> 1, chunk 2 (s & 1) + half of its hi quarter; lo 64 B further
                 const unsigned char* c = qp + (s >> 1) * 128 + (2 * (s & 1) + half) * 16;
@@ -155,6 +178,105 @@ __global__ __launch_bounds__(64 * NW, (RES && NW == 8) ? 4 : ((__is_same(T, spli
 #pragma unroll
             for (int s = 0; s < NF; ++s) qf[s] = as_frag<T>(ld16(qp + (2 * s + half) * 16));
         }
+    }
+    // (in front of everything the key loop keeps in registers: the prologue wants all of them)
+    if constexpr (PROJ) {
+        // Row 32 wave + l31 of the entry (a row at or past its count: its last row - finite filler, as the DMA path's clamp) is
+        // query row and key row alike.  LNn(x) is blocked by the ROW OF THE LAUNCH: k-step ks of row m is the 16 bytes at
+        // ((m >> 5) * 16 + ks) * 1024 + (32 half + (m & 31)) * 16 - exactly the chain kernel's bop[ks] of that row and half.
+        typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+        const long long ym = q0 + qc;
+        // (the lane offset is made opaque: shared with the output address behind the key loop, its common part stayed live across
+        // the loop - one register more than the loop's 128, i.e. a spill)
+        int y_half = half;
+        asm volatile("" : "+v"(y_half));
+        const int y_lane = ((y_half << 5) + (int)(ym & 31)) * 16;
+        const unsigned char* yb = p.Y + (ym >> 5) * 16384 + y_lane;
+        const int key = wave * 32 + l31;
+        // The row's 16 B operands are loaded ONCE and stay in registers through the three products (64 VGPRs; nothing of the key
+        // loop is live yet): every row is needed by four heads' workgroups as it is, and the L2 -> CU traffic, not the matrix
+        // pipe, is what the prologue costs (loading them per product made the launch 65 us longer than the Q|K|V read it replaces)
+        bf16x8 yf[16];
+#pragma unroll
+        for (int ks = 0; ks < 16; ++ks) yf[ks] = as_frag<bf16>(ld16(yb + ks * 1024));
+        // a pair of tail units (tiles `tile`, `tile + 1`: the 64 columns of one head's Q, K or V; 32 KiB contiguous in the stream)
+        // goes into the K region through registers: [2 tiles][16 k-steps][64 lanes][16 B], read back lane-linear.  (Fetching the
+        // next pair in front of the current product does not fit: with the row's operands resident the four registers spill.)
+        uint4 wr[4];
+        auto fetch = [&](int tile) {
+            const uint4* src = reinterpret_cast<const uint4*>(p.W) + (long long)tile * 1024 + tid;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) wr[i] = src[NT * i];
+        };
+        auto put = [&]() {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) st16(Ks_all + (tid + NT * i) * 16, wr[i]);
+        };
+        // tile `tile` (the second of the staged pair when d): o[gp] = channels 32 d + 16 gp + 8 half .. + 7 of the lane's row - the
+        // bias as the accumulator's initial value, k-steps 0 .. 15 in order, the 16-bit conversion, the half-wave exchange: CH_S5N /
+        // CH_EPI_CVT / CH_EPI_OUT of the chain kernel, instruction for instruction
+        auto project = [&](int tile, int d, u32x4& o_0, u32x4& o_1) {
+            f32x16 a;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const f32x4 v = *reinterpret_cast<const f32x4*>(p.bt + 32 * tile + 8 * g + 4 * half);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) a[4 * g + e] = v[e];
+            }
+            // (left to the compiler's schedule: a hand-scheduled form - fragment reads three MFMAs ahead, biases through scalar
+            // loads - measured the same launch time and cost a spill; the prologue waits for memory, not for the matrix pipe)
+#pragma unroll
+            for (int ks = 0; ks < 16; ++ks)
+                a = CN_MFMA16(as_frag<bf16>(ld16(Ks_all + d * 16384 + ks * 1024 + lane * 16)), yf[ks], a, 0, 0, 0);
+#pragma unroll
+            for (int gp = 0; gp < 2; ++gp) {
+                bf16x4 o0, o1;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    o0[e] = (bf16)a[8 * gp + e];
+                    o1[e] = (bf16)a[8 * gp + 4 + e];
+                }
+                const uint2 lo_ = __builtin_bit_cast(uint2, o0), hi_ = __builtin_bit_cast(uint2, o1);
+                const auto s0_ = __builtin_amdgcn_permlane32_swap(lo_.x, hi_.x, false, false);
+                const auto s1_ = __builtin_amdgcn_permlane32_swap(lo_.y, hi_.y, false, false);
+                (gp ? o_1 : o_0) = u32x4{s0_[0], s1_[0], s0_[1], s1_[1]};
+            }
+        };
+        u32x4 pk[4];
+        fetch(16 + 2 * h);
+        put();
+        __syncthreads();
+        // V: 128-byte rows, the 64-byte halves swapped on rows with (row >> 1) & 1; chunk 2 c + half of the row
+#pragma unroll
+        for (int d = 0; d < 2; ++d) {
+            project(16 + 2 * h + d, d, pk[0], pk[1]);
+#pragma unroll
+            for (int c = 0; c < 2; ++c)
+                *reinterpret_cast<u32x4*>(Vs_all + key * 128 + (((2 * (2 * d + c) + half) ^ (((key >> 1) & 1) << 2)) << 4)) = pk[c];
+        }
+        __syncthreads();  // every wave is done with V's units
+        fetch(2 * h);
+        put();
+        __syncthreads();
+        // Q: chunk 2 s + half of the row = fragment s
+#pragma unroll
+        for (int d = 0; d < 2; ++d) {
+            project(2 * h + d, d, pk[0], pk[1]);
+            qf[2 * d] = __builtin_bit_cast(bf16x8, pk[0]);
+            qf[2 * d + 1] = __builtin_bit_cast(bf16x8, pk[1]);
+        }
+        __syncthreads();
+        fetch(8 + 2 * h);
+        put();
+        __syncthreads();
+        // K: held in registers until nobody reads the units it is about to overwrite
+        project(8 + 2 * h, 0, pk[0], pk[1]);
+        project(8 + 2 * h + 1, 1, pk[2], pk[3]);
+        __syncthreads();
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+            *reinterpret_cast<u32x4*>(Ks_all + key * KROW + (((2 * c + half) ^ Cfg::swz(key)) << 4)) = pk[c];
+        AT_STAMP(1)
     }
     constexpr int REL_N = REL ? 64 : 1;
     __shared__ float rel_tab[REL ? 64 * 64 : 1];        // P rows of this head: [2R+1][64]
@@ -285,7 +407,7 @@ __global__ __launch_bounds__(64 * NW, (RES && NW == 8) ? 4 : ((__is_same(T, spli
     if constexpr (RES) {
         const int wave_u = __builtin_amdgcn_readfirstlane(wave);
         const int r8 = lane >> 3, cp = lane & 7;
-        for (int piece = wave_u; piece < nkt * 16; piece += NW) {  // 1-KiB pieces: 8 rows x 128 B of K or V
+        for (int piece = wave_u; !PROJ && piece < nkt * 16; piece += NW) {  // 1-KiB pieces: 8 rows x 128 B of K or V
             const int kt2 = piece >> 4, is_v = (piece >> 3) & 1, j = piece & 7;
             const int row = 8 * j + r8;
             int key = kt2 * 64 + row;
@@ -300,7 +422,7 @@ __global__ __launch_bounds__(64 * NW, (RES && NW == 8) ? 4 : ((__is_same(T, spli
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
                                              (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
         }
-        AT_STAMP(1)
+        if constexpr (!PROJ) AT_STAMP(1)
         if (tid < NRES) Mplain[tid] = 1;
         __syncthreads();
         for (int i = tid; i < nkt * 64; i += NT) {
@@ -633,6 +755,9 @@ template <typename T> static int run_attention(const AttnArgs& a, hipStream_t s)
     }
     p.row_off = a.row_off;
     p.kv_packed = a.kv_packed;
+    p.Y = (const unsigned char*)a.proj_y;
+    p.W = (const unsigned char*)a.proj_w;
+    p.bt = a.proj_b;
     if ((a.row_off && (a.rel_pos || sizeof(T) != 2 || __is_same(T, split_t))) ||
         (a.kv_packed && (!a.row_off || a.kv_mod > 0 || a.kv_index || a.keymask || a.Lq != a.Lk))) {
         cn_set_error("attention: packed rows exist for the 16-bit kernels without relative positions; packed keys are the entry's own "
@@ -657,6 +782,22 @@ template <typename T> static int run_attention(const AttnArgs& a, hipStream_t s)
             hipLaunchKernelGGL((attention_kernel<T, 2, false, true>), dim3(cn_ceil_div(a.Lq, 64), a.H, a.B), dim3(128), 0, s, p);
             CN_HIP_CHECK(hipGetLastError());
             return 0;
+        }
+    }
+    // (every field of p is set by here)
+    if (a.proj_y) {
+        if constexpr (sizeof(T) == 2) {
+            if (!a.proj_w || !a.proj_b || a.H != 4 || a.Lq != a.Lk || a.Lk > 256 || a.row_off || a.rel_pos || a.kv_mod > 0 || a.kv_index) {
+                cn_set_error("attention: the projecting form is self attention of at most 256 rows per entry, 4 heads (d_model 256), "
+                             "without packed rows, relative positions, kv_mod or kv_index");
+                return -1;
+            }
+            hipLaunchKernelGGL((attention_kernel<T, 8, true, false, false, true>), dim3(1, a.H, a.B), dim3(512), 0, s, p);
+            CN_HIP_CHECK(hipGetLastError());
+            return 0;
+        } else {
+            cn_set_error("attention: the projecting form exists for the 16-bit kernels");
+            return -1;
         }
     }
     const long long big_grid = (long long)cn_ceil_div(a.Lq, 128) * a.H * a.B;
@@ -713,7 +854,8 @@ int launch_attention(int prec, const AttnArgs& a, hipStream_t s) {
     // head h reads / writes columns 64 h .. 64 h + 63 of a row: narrower rows would overlap the next row's heads, a blocked
     // window past its matrix the next 32-row block
     const long long w = 64LL * a.H;
-    if ((!a.q_blocked && a.ldq < w) || (!a.kv_blocked && (a.ldk < w || a.ldv < w)) || a.ldo < w) {
+    const bool qkv_used = a.proj_y == nullptr;  // (the projecting form reads neither Q nor K / V)
+    if ((qkv_used && ((!a.q_blocked && a.ldq < w) || (!a.kv_blocked && (a.ldk < w || a.ldv < w)))) || a.ldo < w) {
         cn_set_error("attention: row strides ldq / ldk / ldv / ldo must be >= 64 * H");
         return -1;
     }

@@ -50,6 +50,7 @@ static_assert(CH_LDS <= 160 * 1024, "LDS budget");
 constexpr int CT_BO = 0, CT_LN1A = 256, CT_LN1B = 512, CT_B2 = 768, CT_NLNA = 1024, CT_NLNB = 1280, CT_BT = 1536,
               CT_B1 = 3072;  // tail biases: up to 1536; b1: up to 2048 -> 5120 = the whole table
 constexpr int CH_MAX_TAIL = 48, CH_MAX_FFN_TILES = 64;
+static_assert(CT_BT == CHAIN_TAB_BT && CH_TAB_FLOATS == CHAIN_TAB_FLOATS && CH_UNIT_BYTES == CHAIN_UNIT_BYTES, "kernels.h names the same layout");
 
 __device__ long long ch_stamps[16];  // phase timestamps of workgroup 0 / wave 0 (investigation aid: CASSNAT_CHAIN_STAMPS)
 
@@ -78,6 +79,7 @@ struct ChainParams {
     // multiplied by 2^(qa - 127) 2^(qb - 127)) - W1 . LN1(x) and W2 . hidden
     const int* f8_q;  // [4]: qa1, qb1, qa2, qb2
     const int* m_dev;  // (last: the other fields keep their offsets) null, or the device word that holds the true row count <= M (ChainArgs.m_dev)
+    int ln_blk;  // ln_out as the B operands themselves: per 32-row block [16 k-steps][64 lanes][16 B] (ChainArgs.ln_blocked)
 };
 
 #define CH_STR2(x) #x
@@ -996,7 +998,17 @@ __global__ __launch_bounds__(256) void chain_kernel(ChainParams p) {
         ch_layernorm_pack<false>(acc, tab_lane, CT_NLNA, CT_NLNB, 0, p.eps, bop);
         CH_STAMP(7)
         if (p.ln_out) {
-            // y = LNn(x) itself, row-major bf16.  bop[2 nt + s][j] is channel 32 nt + 16 s + 8 (j >> 2) + 4 half + (j & 3)
+            // y = LNn(x) itself.  Blocked: the packed operands exactly as they are - k-step k of this wave's row block is 1 KiB
+            // contiguous, [lane][16 B], the layout ctx_blk reads on the way in (whole blocks: rows past M land in the buffer's
+            // padding) - for a reader that multiplies them itself (the attention kernel's projecting form)
+            if (p.ln_blk) {
+                if (rb < nrb) {
+                    bf16x8* op = reinterpret_cast<bf16x8*>(p.ln_out) + ((long long)rb * 16 * 64 + lane);
+#pragma unroll
+                    for (int k = 0; k < 16; ++k) op[k * 64] = bop[k];
+                }
+            } else
+            // row-major bf16.  bop[2 nt + s][j] is channel 32 nt + 16 s + 8 (j >> 2) + 4 half + (j & 3)
             if (live) {
                 bf16* op = p.ln_out + (long long)m * p.ld_ln + 4 * half;
 #pragma unroll
@@ -1182,6 +1194,11 @@ int launch_chain(const ChainArgs& a, hipStream_t s) {
     p.out_blk = a.out_blocked && a.tail_n > 0;
     p.ctx_blk = a.ctx && a.ctx_blocked;
     p.f8_q = a.f8_q;
+    p.ln_blk = a.ln_blocked && p.ln_out && a.has_next;
+    if (p.ln_blk && p.ld_ln != CH_D) {
+        cn_set_error("chain: a blocked LNn(x) has 256 columns");
+        return -1;
+    }
     if (p.ctx_blk && a.ldctx != CH_D) {
         cn_set_error("chain: a blocked ctx has 256 columns");
         return -1;

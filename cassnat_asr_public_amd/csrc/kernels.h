@@ -164,6 +164,14 @@ struct AttnArgs {
     const float* rel_pos = nullptr;
     const float *rel_u = nullptr, *rel_v = nullptr;
     int rel_R = 0, ld_pos = 0;
+    // 16-bit kernels, self attention with Lq == Lk <= 256, H == 4 (d_model 256): proj_y != null - the kernel projects Q | K | V
+    // itself.  proj_y: LNn(x) of the launch's B * Lq rows as the row-chain kernel's blocked `ln_out` writes it (ChainArgs.
+    // ln_blocked); proj_w: the 24 tail units of a pack_chain stream whose tail is the [768][256] Q|K|V projection; proj_b: its
+    // 768 biases (the stream's table + 1536 floats).  Q / K / V and their strides are then unused; O as always.  The context rows
+    // are bit for bit those of the chain launch with the tail followed by this kernel on the Q|K|V it wrote.
+    const void* proj_y = nullptr;
+    const void* proj_w = nullptr;
+    const float* proj_b = nullptr;
 };
 int launch_attention(int prec, const AttnArgs& a, hipStream_t s);
 int attention_print_stamps();  // CASSNAT_ATTN_STAMPS: phase timestamps of the last launch's workgroup 0
@@ -380,6 +388,7 @@ int launch_conv2_dma(const void* in, const void* w, const float* bias, void* out
 // ---- row-chain kernel, bf16 / d_model == 256: out-projection + residual, FFN sublayer + residual, next pre-norm and the
 // next attention's input projection for 128-row blocks, activations in registers, weights streamed once per block (chain.hip)
 constexpr int CHAIN_TAB_FLOATS = 5120;
+constexpr int CHAIN_TAB_BT = 1536;  // the tail biases' place in the table (floats)
 constexpr int CHAIN_UNIT_BYTES = 16384;
 struct ChainArgs {
     float* x = nullptr;          // [M][256] fp32 residual stream, in place
@@ -401,6 +410,10 @@ struct ChainArgs {
     // (buffer must hold ceil(M / 32) * 32 rows).  store_x = 0: x is not written back (nothing reads it afterwards)
     int x_in_blocked = 0, x_out_blocked = 0, store_x = 1;
     int out_blocked = 0;  // the tail projection `out` is written as a blocked bf16 matrix of ldo columns (common.h: cn_blk16_off)
+    // LNn(x) (ln_out, or `out` of a launch without tail) is written as the kernel's own B operands: per 32-row block [16 k-steps of
+    // 16 channels][lane = 32 * half + row % 32][8 bf16], the channels of (k-step, half, j) in the accumulator order the tail units
+    // are packed for - the layout of AttnArgs.o_blocked.  256 columns; the buffer holds ceil(M / 32) * 32 rows
+    int ln_blocked = 0;
     int swish = 0;  // feed-forward activation: x * sigmoid(x) instead of ReLU (conformer)
     int f8 = 0;     // the stream's feed-forward units are e4m3 (pack_chain with f8_q)
     const int* f8_q = nullptr;  // device: the four scale bytes pack_chain returned

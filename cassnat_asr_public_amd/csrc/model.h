@@ -282,14 +282,14 @@ bool x3_chain_applies(const cn_model* m, const Layer& L, const Linear* tail);
 int run_x3_chain(cn_model* m, const Layer& L, const Norm& n1, float* x, int M, const Norm& next, void* next_out, const Linear* tail,
                  void* tail_out, int ld_tail, const char* tag, hipStream_t s);
 int run_self_attn_core(cn_model* m, int B, int Lseq, const unsigned char* keymask, const int* klen, int causal, hipStream_t s,
-                       bool blocked = false, const int* row_off = nullptr);
+                       bool blocked = false, const int* row_off = nullptr, const ChainRef* proj = nullptr);
 int run_self_attn(cn_model* m, const Layer& L, const Norm* pre, float* x, int B, int Lseq, const unsigned char* keymask,
                   const int* klen, int causal, hipStream_t s);
 // x_mode of run_chain: the fp32 stream is read / written row-major or in the kernel's blocked tile layout, or not written
 enum { CHX_IN_BLK = 1, CHX_OUT_BLK = 2, CHX_NO_STORE = 4 };
 int run_chain(cn_model* m, const ChainRef& r, float* x, int M, void* out, int ldo, bool with_next, int x_mode, hipStream_t s,
               void* ln_out = nullptr, int ld_ln = 0, bool out_blocked = false, const char* tag = "row_chain",
-              const int* m_dev = nullptr);
+              const int* m_dev = nullptr, bool ln_only = false);
 int run_enc_layer_fp8(cn_model* m, const Layer& L, float* x, int B, int Tp, hipStream_t s);
 int run_ffn_swish(cn_model* m, const Linear& w1, const Linear& w2, const Norm& n, float* x, int M, float scale, hipStream_t s);
 int run_rel_self_attn(cn_model* m, const Layer& L, const Norm& n, float* x, int B, int Lseq, const unsigned char* keymask,

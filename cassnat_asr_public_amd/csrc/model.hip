@@ -216,9 +216,20 @@ int stage_encode(cn_model* m, const float* feats, int B, int T, int F, const cn_
     // layout: 1-KiB store instructions instead of thirty-two 32-byte row segments (the tail phase was store-bound)
     static const bool blk = cn_exp_env("CASSNAT_NO_BLOCKED_QKV") == nullptr;
     m->kv_blocked = false;
+    // Q | K | V projected inside the attention kernel (attention.hip, PROJ): where the self-attention launch is the resident
+    // 8-wave form (128 < T' <= 256, 4 heads) the chain launches in front of it end with LNn(x) - the entry launch is the
+    // LayerNorm alone, layers 0 .. N - 2 run without their tail - and the attention workgroups multiply it by the tail units of
+    // the same stream: the same bits, without the 3d-wide round trip.  The last launch keeps its tail (enc_h and the decoder
+    // side's K|V); capture runs and cn_decode_opts.reserved[2] keep the two-launch form.
+    static const bool no_attn_proj = cn_exp_env("CASSNAT_NO_ATTN_PROJ") != nullptr;
+    bool proj = chain && !cap && blk && !no_attn_proj && o->reserved[2] == 0 && m->enc_entry.w && m->prec == CN_PREC_BF16 &&
+                c.n_head == 4 && Tp > 128 && Tp <= 256 && m->enc_entry.tail_n == 3 * d;
+    for (size_t n = 0; proj && n + 1 < m->enc_chain.size(); ++n) proj = m->enc_chain[n].tail_n == 3 * d && m->enc_chain[n].has_next;
     if (chain) {  // bf16 / d_model 256: LN + QKV of layer 0 (an entry chain launch: no FFN, x left alone), then per layer
                   // attention -> row-chain kernel
-        if (m->enc_entry.w) {
+        if (m->enc_entry.w && proj) {
+            CN_TRY(run_chain(m, m->enc_entry, m->x, M, m->xn, d, true, CHX_NO_STORE, s, nullptr, 0, false, "row_chain", nullptr, true));
+        } else if (m->enc_entry.w) {
             CN_TRY(run_chain(m, m->enc_entry, m->x, M, m->qkv, 3 * d, true, CHX_NO_STORE, s, nullptr, 0, blk));
         } else {
             CN_TRY(run_ln(m, m->enc[0].n[0], m->x, m->xn, M, s));
@@ -234,7 +245,10 @@ int stage_encode(cn_model* m, const float* feats, int B, int T, int F, const cn_
         const Layer& L = m->enc[n];
         const bool last = n + 1 == m->enc.size();
         if (chain) {
-            CN_TRY(run_self_attn_core(m, B, Tp, m->keymask, nullptr, 0, s, (n > 0 || m->enc_entry.w) && blk));
+            if (proj)  // (the tail that projects layer n's Q|K|V: the entry stream's, then layer n - 1's)
+                CN_TRY(run_self_attn_core(m, B, Tp, m->keymask, nullptr, 0, s, false, nullptr, n > 0 ? &m->enc_chain[n - 1] : &m->enc_entry));
+            else
+                CN_TRY(run_self_attn_core(m, B, Tp, m->keymask, nullptr, 0, s, (n > 0 || m->enc_entry.w) && blk));
             // between chain launches the residual stream lives in the kernel's blocked layout; the last layer's x is
             // consumed by nobody (enc_h is the output).  Captures read x row-major.
             const int xm = cap ? 0 : ((n > 0 ? CHX_IN_BLK : 0) | (last ? CHX_NO_STORE : CHX_OUT_BLK));
@@ -242,6 +256,8 @@ int stage_encode(cn_model* m, const float* feats, int B, int T, int F, const cn_
                 CN_TRY(run_chain(m, m->enc_chain[n], m->x, M, m->kv_all, m->kv_cols, true, xm, s, m->enc_h, d, blk));
                 m->kv_ready = true;
                 m->kv_blocked = blk;
+            } else if (proj && !last) {
+                CN_TRY(run_chain(m, m->enc_chain[n], m->x, M, m->xn, d, true, xm, s, nullptr, 0, false, "row_chain", nullptr, true));
             } else {
                 CN_TRY(run_chain(m, m->enc_chain[n], m->x, M, last ? m->enc_h : m->qkv, last ? d : 3 * d, true, xm, s, nullptr, 0,
                                  blk && !last));

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/cassnat_hip.h"
+#include "../../include/cassnat_hip_attention_proj.h"
 #include "ctc_ngram_search.h"
 #include "flac_decode.h"
 #include "kernels.h"
@@ -538,6 +539,55 @@ static int op_attention_desc(const char* who, int32_t precision, const cn_attn_d
 
 extern "C" int cn_op_attention_desc(int32_t precision, const cn_attn_desc* d, void* stream) {
     return op_attention_desc("cn_op_attention_desc", precision, d, nullptr, 0, stream);
+}
+
+// The projecting form (attention.hip, PROJ) on a caller's LNn(x): the Q|K|V projection is packed as the tail of a chain stream
+// (pack_chain, as cn_op_chain packs it on every call) and the kernel reads its units and biases from there
+extern "C" int cn_op_attention_proj(int32_t precision, const cn_attn_desc* d, const void* y_dev, const float* wt_host,
+                                    const float* bt_host, void* stream) {
+    if ((precision = cn_own_precision(precision, "cn_op_attention_proj")) < 0) return -1;
+    if (!d || !y_dev || !wt_host || !bt_host) {
+        cn_set_error("cn_op_attention_proj: null argument");
+        return -1;
+    }
+    if (precision != CN_PREC_BF16) {
+        cn_set_error("cn_op_attention_proj: the projecting form exists for the 16-bit kernels");
+        return -1;
+    }
+    ChainWeights w;
+    w.wt = wt_host;
+    w.bt = bt_host;
+    w.tail_n = 768;
+    std::vector<uint16_t> hs(chain_stream_units(0, 0, 768) * (CHAIN_UNIT_BYTES / 2));
+    std::vector<float> ht(CHAIN_TAB_FLOATS);
+    pack_chain(w, hs.data(), ht.data());
+    Scratch sc("cn_op_attention_proj", (hipStream_t)stream);
+    const void* ds = sc.upload(hs.data(), hs.size() * 2);
+    const float* dt = (const float*)sc.upload(ht.data(), ht.size() * 4);
+    if (!sc.ok()) return -2;
+    AttnArgs a;
+    a.O = d->O;
+    a.ldo = d->ldo;
+    a.B = d->B;
+    a.H = d->H;
+    a.Lq = d->Lq;
+    a.Lk = d->Lk;
+    a.keymask = d->keymask;
+    a.kv_mod = d->kv_mod;
+    a.kv_index = d->kv_index;
+    a.klen = d->klen;
+    a.kcap = d->kcap;
+    a.kcap_stride = d->kcap_stride;
+    a.o_blocked = d->o_blocked;
+    a.intervals = d->intervals;
+    a.iv_stride = d->iv_stride;
+    a.causal = d->causal;
+    a.scale = d->scale;
+    a.rel_pos = d->rel_pos;
+    a.proj_y = y_dev;
+    a.proj_w = ds;
+    a.proj_b = dt + CHAIN_TAB_BT;
+    return sc.finish(launch_attention(precision, a, (hipStream_t)stream));
 }
 
 extern "C" int cn_op_attention_packed(int32_t precision, const cn_attn_desc* d, const int32_t* row_off_dev, int32_t kv_packed,
@@ -1435,6 +1485,7 @@ static int op_chain(float* x_dev, const void* ctx_dev, int32_t ldctx, const floa
     a.store_x = (x_mode & 4) == 0;
     a.swish = (x_mode & 8) != 0;
     a.out_blocked = (x_mode & 16) != 0;
+    a.ln_blocked = (x_mode & 64) != 0;
     a.f8 = f8;
     a.f8_q = f8 ? reinterpret_cast<const int*>(dt + CHAIN_TAB_FLOATS) : nullptr;
     int rc = launch_chain(a, (hipStream_t)stream);

@@ -151,8 +151,10 @@ int run_x3_chain(cn_model* m, const Layer& L, const Norm& n1, float* x, int M, c
 
 // ctx <- Attn(q, k, v) on the fused [M][3d] projection buffer m->qkv
 // row_off: packed rows (AttnArgs.row_off; queries AND keys are the entry's own rows) - the decoder side of a packed pass
+// proj: the kernel projects Q | K | V itself (AttnArgs.proj_y) from LNn(x) in m->xn (the blocked ln_out of a run_chain launch
+// with `ln_only`) and the tail units / biases of that launch's stream - m->qkv is neither written nor read
 int run_self_attn_core(cn_model* m, int B, int Lseq, const unsigned char* keymask, const int* klen, int causal,
-                       hipStream_t s, bool blocked, const int* row_off) {
+                       hipStream_t s, bool blocked, const int* row_off, const ChainRef* proj) {
     const int d = m->cfg.d_model, M = B * Lseq;
     AttnArgs a;
     const size_t es = m->es;
@@ -167,6 +169,13 @@ int run_self_attn_core(cn_model* m, int B, int Lseq, const unsigned char* keymas
         a.v_col = 2 * d;
         a.q_n = a.kv_n = 3 * d;
         a.o_blocked = 1;  // (blocked in = the row-chain path: its next launch reads ctx as B operands)
+    }
+    if (proj) {
+        a.proj_y = m->xn;
+        a.proj_w = (const unsigned char*)proj->w +
+                   chain_stream_units(proj->has_wo, proj->dff, 0, proj->f8q != nullptr) * (size_t)CHAIN_UNIT_BYTES;
+        a.proj_b = proj->tab + CHAIN_TAB_BT;
+        a.o_blocked = 1;
     }
     m->ctx_blocked = a.o_blocked != 0;
     a.O = m->ctx;
@@ -185,7 +194,9 @@ int run_self_attn_core(cn_model* m, int B, int Lseq, const unsigned char* keymas
     }
     a.causal = causal;
     a.scale = 1.0f / sqrtf((float)(d / m->cfg.n_head));
-    ProfScope ps(m, "self_attention", 4.0 * B * a.H * (double)Lseq * Lseq * 64, (double)M * 4 * d * m->es, s);
+    // (projecting form: + the Q|K|V product; LNn(x) in and ctx out, and every (entry, head) workgroup its 6 tail units)
+    ProfScope ps(m, "self_attention", 4.0 * B * a.H * (double)Lseq * Lseq * 64 + (proj ? 2.0 * M * d * 3.0 * d : 0.0),
+                 proj ? (double)M * 2 * d * m->es + (double)B * 3 * d * d * m->es : (double)M * 4 * d * m->es, s);
     return launch_attention(m->prec, a, s);
 }
 
@@ -206,10 +217,12 @@ int run_self_attn(cn_model* m, const Layer& L, const Norm* pre, float* x, int B,
 // x_mode: CHX_* bits (model.h)
 // tag: the profile row of the launch ("row_chain": encoder-side, full-width launches; "row_chain_dec": the decoder side's - a
 // tenth of the rows, a quarter of the CUs: bench.py prices the two apart)
+// ln_only: the stream's tail projection is left to its reader (run_self_attn_core with `proj`) - the launch ends with LNn(x),
+// written to `out` ([ceil(M / 32) * 32][d]) as the kernel's own B operands (ChainArgs.ln_blocked)
 int run_chain(cn_model* m, const ChainRef& r, float* x, int M, void* out, int ldo, bool with_next, int x_mode,
-              hipStream_t s, void* ln_out, int ld_ln, bool out_blocked, const char* tag, const int* m_dev) {
+              hipStream_t s, void* ln_out, int ld_ln, bool out_blocked, const char* tag, const int* m_dev, bool ln_only) {
     const int d = m->cfg.d_model;
-    const int tail_n = with_next ? r.tail_n : 0;
+    const int tail_n = with_next && !ln_only ? r.tail_n : 0;
     const double macs = (r.has_wo ? (double)d * d : 0.0) + 2.0 * d * r.dff + (double)d * tail_n;
     ProfScope ps(m, tag, 2.0 * M * macs, (double)M * d * (8 + 2) + (double)M * ldo * 2 + 2.0 * macs, s);
     ChainArgs a;
@@ -234,6 +247,7 @@ int run_chain(cn_model* m, const ChainRef& r, float* x, int M, void* out, int ld
     a.store_x = (x_mode & CHX_NO_STORE) == 0;
     a.swish = r.swish ? 1 : 0;
     a.out_blocked = out_blocked ? 1 : 0;
+    a.ln_blocked = ln_only ? 1 : 0;
     a.f8 = r.f8q ? 1 : 0;
     a.f8_q = r.f8q;
     return launch_chain(a, s);

@@ -46,7 +46,7 @@ std::vector<WsRow> ws_table(const cn_model* m, const WsDims& v) {
         WS_ROW(c2, B * Tp * F2 * d * es);
     }
     WS_ROW(x, (M + 32) * d * 4);  // + one 32-row block: the chain kernel's blocked layout rounds up
-    WS_ROW(xn, M * d * es);
+    WS_ROW(xn, (M + 32) * d * es);  // (+ 32 rows: whole 32-row blocks of the chain kernel's blocked LNn(x))
     WS_ROW(qkv, (M + 32) * 3 * d * es);  // (+ 32 rows: the chain kernel writes whole 32-row blocks of its blocked output)
     WS_ROW(ctx, (M + 32) * d * es);  // (+ 32 rows: whole 32-row blocks of the blocked form)
     WS_ROW(hbuf, M * dff * es);

@@ -400,6 +400,9 @@ class Engine:
                             use_unimask=int(bool(getattr(args, "use_unimask", False))), beam_width=int(args.beam_width),
                             capture=int(bool(capture)), no_trigger=int(not getattr(args, "use_trigger", True)))
         opts.reserved[1] = int(bool(getattr(args, "hip_padded_rows", False)))
+        # args.hip_chain_qkv: cn_decode_opts.reserved[2] - the encoder's Q|K|V written by the row-chain launches where the
+        # self-attention kernel would project them itself (same results bit for bit; the A/B switch of the two forms)
+        opts.reserved[2] = int(bool(getattr(args, "hip_chain_qkv", False)))
         return opts
 
     def decode(self, feats, size_ratio, opts, hyp, hyp_len, score):

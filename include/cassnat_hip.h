@@ -94,7 +94,11 @@ typedef struct cn_decode_opts {
                             PACKS its decoder side: utterance b owns only the rows its hypothesis reads - min(ylen[b] + 1, row
                             count of its own batch) - one utterance behind the other, instead of U rows each.  Hypotheses,
                             lengths and scores are the same bit for bit either way; the switch is there to compare the two
-                            layouts in one library.  The others must be 0 */
+                            layouts in one library.
+                            reserved[2] != 0: the encoder's Q|K|V come from the row-chain launches.  A pass of a 16-bit engine
+                            with the row-chain encoder and 128 < T' <= 256 (4 heads, no capture) otherwise projects them inside
+                            the self-attention kernel from the LayerNorm rows the chain launches then end with; the results are
+                            the same bit for bit, the switch compares the two forms in one library.  The others must be 0 */
 } cn_decode_opts;
 
 const char* cn_last_error(void);
@@ -352,7 +356,9 @@ int cn_profile_end(cn_model* m, char* json_out, int64_t cap);
  * the buffer then holds ceil(M / 32) * 32 rows.  32 = the two feed-forward products take e4m3fn operands (BASELINE config 5,
  * CN_PRECISION_FP8 engines; d_ff % 256 == 0, ReLU only): LN1(x) at x16 and the ReLU output at x8, both saturating at +-448,
  * W1 and W2 each at the largest power-of-two scale that keeps its largest magnitude <= 448; accumulation, bias, residual and
- * everything else of the launch as without the bit. */
+ * everything else of the launch as without the bit.  64 (with tail_n == 0, ldo == 256) = LNn(x) goes to out_dev as the kernel's
+ * own B operands: per 32-row block [16 k-steps][lane = row % 32 + 32 h][8 values], value j of (k-step ks, h) being channel
+ * 32 (ks / 2) + 16 (ks % 2) + 8 (j / 4) + 4 h + j % 4; ceil(M / 32) * 32 rows - what cn_op_attention_proj (cassnat_hip_attention_proj.h) reads as y_dev. */
 int cn_op_chain(float* x_dev, const void* ctx_dev, int32_t ldctx, const float* wo_host, const float* bo_host,
                 const float* ln1_a_host, const float* ln1_b_host, const float* w1_host, const float* b1_host,
                 const float* w2_host, const float* b2_host, const float* nln_a_host, const float* nln_b_host,
