@@ -1,5 +1,6 @@
-"""The C ABI read from include/cassnat_hip.h, the place that declares it (``EXTRA_FUNCTIONS`` / ``PROJ_FUNCTIONS``: the entry points of
-its companions include/cassnat_hip_ctc_ngram.h and include/cassnat_hip_attention_proj.h, read the same way): ``FUNCTIONS`` name -> (restype, argtypes),
+"""The C ABI read from include/cassnat_hip.h, the place that declares it (``EXTRA_FUNCTIONS`` / ``PROJ_FUNCTIONS`` / ``AST_NGRAM_FUNCTIONS``:
+the entry points of its companions include/cassnat_hip_ctc_ngram.h, include/cassnat_hip_attention_proj.h and
+include/cassnat_hip_ast_ngram.h, read the same way): ``FUNCTIONS`` name -> (restype, argtypes),
 ``STRUCTS`` C name -> ctypes.Structure, ``CONSTANTS`` enum / #define name -> int.  It reads this project's header, not C in general:
 what it does not recognise raises ``AbiError`` naming the declaration.  Standard library only (no torch, numpy, library or GPU)."""
 import ctypes as C
@@ -111,12 +112,16 @@ with open(EXTRA_HEADER_PATH) as _f:
 PROJ_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "cassnat_hip_attention_proj.h")
 with open(PROJ_HEADER_PATH) as _f:
     PROJ_FUNCTIONS = parse(_f.read(), base=HEADER).functions
+# the companion header of the AST beam search with word n-gram fusion, likewise
+AST_NGRAM_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "cassnat_hip_ast_ngram.h")
+with open(AST_NGRAM_HEADER_PATH) as _f:
+    AST_NGRAM_FUNCTIONS = parse(_f.read(), base=HEADER).functions
 
 
 def bind(L):
     """Set ``restype`` / ``argtypes`` of every declared function on the loaded library ``L``; a function a header declares and the
     library lacks raises AttributeError."""
-    for name, (restype, argtypes) in list(FUNCTIONS.items()) + list(EXTRA_FUNCTIONS.items()) + list(PROJ_FUNCTIONS.items()):
+    for name, (restype, argtypes) in list(FUNCTIONS.items()) + list(EXTRA_FUNCTIONS.items()) + list(PROJ_FUNCTIONS.items()) + list(AST_NGRAM_FUNCTIONS.items()):
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     return L

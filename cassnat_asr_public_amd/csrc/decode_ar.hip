@@ -3,6 +3,7 @@
 #include <algorithm>
 #include <cmath>
 
+#include "ast_ngram_search.h"
 #include "model.h"
 
 using namespace cn_host;
@@ -350,7 +351,8 @@ namespace {
 // dense_bw > 0: the rows are the dense slots b * dense_bw + j of the device beam (utt[row] = row / dense_bw)
 int ast_step_run(cn_model* m, int n, int pos, const int32_t* tok_dev, const int32_t* utt_dev, const int32_t* anc_dev,
                  const uint8_t* keyok_dev, int table_stride, float temperature, int K, int32_t* topk_idx_dev,
-                 float* topk_val_dev, int dense_bw, hipStream_t s, float lm_weight = 0.f, float* lm_val_dev = nullptr) {
+                 float* topk_val_dev, int dense_bw, hipStream_t s, float lm_weight = 0.f, float* lm_val_dev = nullptr,
+                 const float* ng_adds_dev = nullptr, int ng_eos = -1) {
     const cn_config& c = m->cfg;
     const int d = c.d_model, V = c.vocab_size, H = c.n_head;
     const float scale = 1.0f / sqrtf((float)(d / H));
@@ -480,6 +482,11 @@ int ast_step_run(cn_model* m, int n, int pos, const int32_t* tok_dev, const int3
         CN_TRY(launch_logsoftmax_topk(m->ast_logits, n, V, V, temperature, K, topk_idx_dev, topk_val_dev, s));
         return launch_logsoftmax_gather(lm->ast_logits, n, V, V, topk_idx_dev, K, lm_val_dev, s);
     }
+    if (ng_adds_dev) {  // word n-gram fusion without CTC: top-K of att + scale * term(class of the token) over the vocabulary
+        ProfScope ps(m, "ngram_fusion", 0, 1.0 * n * V * 4, s);
+        return launch_logsoftmax_class_topk(m->ast_logits, n, V, V, temperature, m->ast_ng.piece_starts, ng_adds_dev, ng_eos,
+                                            m->ast_ng_scale, K, topk_idx_dev, topk_val_dev, s);
+    }
     CN_TRY(launch_logsoftmax_topk(m->ast_logits, n, V, V, temperature, K, topk_idx_dev, topk_val_dev, s));
     return 0;
 }
@@ -511,6 +518,10 @@ extern "C" int cn_ast_step_lm(cn_model* m, int32_t n, int32_t pos, const int32_t
         cn_set_error("cn_ast_step_lm: call cn_ast_begin first");
         return -1;
     }
+    if (m->ast_ng_on) {
+        cn_set_error("cn_ast_step_lm: an n-gram model is attached (cn_ast_attach_ngram); it and a TransformerLM cannot be fused together");
+        return -1;
+    }
     if (!(lm_weight > 0.f) || !m->ast_lm || m->ast_lm->ast_slots < m->ast_slots || m->ast_lm->ast_max_len < m->ast_max_len) {
         cn_set_error("cn_ast_step_lm: needs lm_weight > 0 and an LM attached (cn_ast_attach_lm) before cn_ast_begin");
         return -1;
@@ -524,6 +535,68 @@ extern "C" int cn_ast_step_lm(cn_model* m, int32_t n, int32_t pos, const int32_t
     CN_HIP_CHECK(hipSetDevice(m->cfg.device));
     return ast_step_run(m, n, pos, tok_dev, utt_dev, anc_dev, keyok_dev, table_stride, temperature, K, topk_idx_dev, topk_val_dev, 0,
                         (hipStream_t)stream, lm_weight, use_ctc ? lm_val_dev : nullptr);
+}
+
+// include/cassnat_hip_ast_ngram.h: the word n-gram model whose class terms the step fuses (NULL detaches)
+extern "C" int cn_ast_attach_ngram(cn_model* m, const cn_ngram_desc* desc, float lm_scale) {
+    if (!m || m->cfg.ast != 1) {
+        cn_set_error("cn_ast_attach_ngram: the handle must be an autoregressive model (cfg.ast = 1)");
+        return -1;
+    }
+    if (!desc) {
+        m->ast_ng_on = false;
+        m->ast_ng = cn_ngram_desc{};
+        m->ast_ng_scale = 0.f;
+        return 0;
+    }
+    const std::string bad = an_check_desc(*desc);
+    if (!bad.empty()) {
+        cn_set_error("cn_ast_attach_ngram: " + bad);
+        return -1;
+    }
+    if (desc->vocab != m->cfg.vocab_size) {
+        cn_set_error("cn_ast_attach_ngram: the model's pieces must be the decoder's vocabulary (desc->vocab " + std::to_string(desc->vocab) +
+                     ", vocab_size " + std::to_string(m->cfg.vocab_size) + ")");
+        return -1;
+    }
+    if (!(lm_scale == lm_scale)) {
+        cn_set_error("cn_ast_attach_ngram: lm_scale must be a number");
+        return -1;
+    }
+    m->ast_ng = *desc;
+    m->ast_ng_scale = lm_scale;
+    m->ast_ng_on = true;
+    return 0;
+}
+
+extern "C" int cn_ast_step_ngram(cn_model* m, int32_t n, int32_t pos, const int32_t* tok_dev, const int32_t* utt_dev,
+                                 const int32_t* anc_dev, const uint8_t* keyok_dev, int32_t table_stride, float temperature, int32_t K,
+                                 int32_t use_ctc, int32_t eos, const float* adds_dev, int32_t* topk_idx_dev, float* topk_val_dev,
+                                 float* term_dev, void* stream) {
+    if (!m || m->cfg.ast != 1 || m->ast_slots == 0) {
+        cn_set_error("cn_ast_step_ngram: call cn_ast_begin first");
+        return -1;
+    }
+    if (!m->ast_ng_on) {
+        cn_set_error("cn_ast_step_ngram: needs an n-gram model attached with cn_ast_attach_ngram");
+        return -1;
+    }
+    if (m->ast_lm) {
+        cn_set_error("cn_ast_step_ngram: an n-gram model and a TransformerLM are attached together; detach one");
+        return -1;
+    }
+    if (n < 1 || n > m->ast_slots || pos < 0 || pos >= m->ast_max_len || pos >= m->pe_rows || K < 1 || K > 32 ||
+        K > m->cfg.vocab_size || table_stride <= pos || !adds_dev || (use_ctc && !term_dev)) {
+        cn_set_error("cn_ast_step_ngram: live rows / position / K outside the configured cache (K <= 32 and <= the vocabulary; or no "
+                     "adds_dev; or use_ctc without term_dev)");
+        return -1;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    CN_HIP_CHECK(hipSetDevice(m->cfg.device));
+    CN_TRY(ast_step_run(m, n, pos, tok_dev, utt_dev, anc_dev, keyok_dev, table_stride, temperature, K, topk_idx_dev, topk_val_dev, 0, s,
+                        0.f, nullptr, use_ctc ? nullptr : adds_dev, eos));
+    if (use_ctc) return launch_ast_ngram_terms(m->ast_ng.piece_starts, adds_dev, eos, topk_idx_dev, n, K, term_dev, s);
+    return 0;
 }
 
 // kernel-test entry of the LM step: log_softmax of the LM's logits at position pos of n rows -> logp_dev [n][V]
@@ -645,6 +718,11 @@ extern "C" int cn_decode_ast(cn_model* m, const float* feats_dev, int32_t B, int
         cn_set_error("cn_decode_ast: lm_weight > 0 needs an LM attached with cn_ast_attach_lm");
         return -1;
     }
+    const bool use_ng = m->ast_ng_on;
+    if (use_ng && use_lm) {
+        cn_set_error("cn_decode_ast: an n-gram model is attached and lm_weight > 0 asks for the TransformerLM; the two cannot be fused together");
+        return -1;
+    }
     const int S = B * bw, L = max_len;
     CN_TRY(cn_ast_begin(m, feats_dev, B, T, F, opts, want_ctc, L, S, want_ctc ? K : 0, stream));
     hipStream_t s = (hipStream_t)stream;
@@ -667,6 +745,7 @@ extern "C" int cn_decode_ast(cn_model* m, const float* feats_dev, int32_t B, int
         CN_TRY(ast_alloc(m, (void**)&m->beam_val, (size_t)S * K * 4));
         CN_TRY(ast_alloc(m, (void**)&m->beam_ctc, (size_t)S * K * 4));
         CN_TRY(ast_alloc(m, (void**)&m->beam_lm, (size_t)S * K * 4));
+        CN_TRY(ast_alloc(m, (void**)&m->beam_adds, (size_t)S * 2 * 4));
         m->beam_S = S;
         m->beam_L = L;
         m->beam_K = K;
@@ -675,8 +754,16 @@ extern "C" int cn_decode_ast(cn_model* m, const float* feats_dev, int32_t B, int
     int cur = 0;
     CN_TRY(launch_ast_beam_init(st, cur, B, bw, L, opts->sos, opts->padding_idx, s));
     for (int pos = 0; pos < ao->max_step; ++pos) {
+        // word n-gram fusion: every slot's (a_word, a_eos) from its own tokens behind sos.  Without CTC they enter the top-K over the
+        // vocabulary; with CTC the same launch runs behind the attention top-K and writes the terms at its candidates
+        if (use_ng && !want_ctc)
+            CN_TRY(launch_ast_ngram_adds(m->ast_ng, st.tok[cur], L, 1, st.len[cur], -1, S, ao->eos, m->beam_adds, nullptr, 0, nullptr, s));
         CN_TRY(ast_step_run(m, S, pos, st.cur_tok, st.utt, st.anc[cur], st.keyok[cur], L, ao->temperature, K, m->beam_idx,
-                            m->beam_val, bw, s, use_lm ? ao->lm_weight : 0.f, use_lm && want_ctc ? m->beam_lm : nullptr));
+                            m->beam_val, bw, s, use_lm ? ao->lm_weight : 0.f, use_lm && want_ctc ? m->beam_lm : nullptr,
+                            use_ng && !want_ctc ? m->beam_adds : nullptr, ao->eos));
+        if (use_ng && want_ctc)
+            CN_TRY(launch_ast_ngram_adds(m->ast_ng, st.tok[cur], L, 1, st.len[cur], -1, S, ao->eos, m->beam_adds, m->beam_idx, K,
+                                         m->beam_lm, s));
         if (want_ctc)
             CN_TRY(cn_ast_ctc_score(m, S, pos, st.utt, st.cur_tok, m->beam_idx, K, st.ctc_ref[cur], pos & 1, ao->eos, m->beam_ctc,
                                     stream));
@@ -694,9 +781,9 @@ extern "C" int cn_decode_ast(cn_model* m, const float* feats_dev, int32_t B, int
         q.pad = opts->padding_idx;
         q.use_ctc = want_ctc;
         q.use_lp = ao->use_length_penalty;
-        q.use_lm = use_lm;
+        q.use_lm = use_lm || use_ng;
         q.lm = m->beam_lm;
-        q.lw = ao->lm_weight;
+        q.lw = use_ng ? m->ast_ng_scale : ao->lm_weight;
         q.w = ao->ctc_weight;
         q.u = ao->one_minus_ctc_weight;
         q.lp = ao->length_penalty;

@@ -261,6 +261,17 @@ int launch_logsoftmax_topk(const float* logits, int M, int V, int ldl, float tem
 // log_softmax(att / T) + fl(w * log_softmax(lm)) (no CTC), and the LM's log-probability at k given candidates (with CTC)
 int launch_logsoftmax_fuse_topk(const float* att, const float* lm, int M, int V, int ldl, float temperature, float w, int k,
                                 int* idx, float* val, hipStream_t s);
+// launch_logsoftmax_fuse_topk's sibling for a word n-gram model (AST beam search without CTC): the second addend of entry c is
+// fl32(w * term(c)) with term(c) = adds[row][1] if c == eos, adds[row][0] if starts[c], else 0
+int launch_logsoftmax_class_topk(const float* att, int M, int V, int ldl, float temperature, const unsigned char* starts,
+                                 const float* adds, int eos, float w, int k, int* idx, float* val, hipStream_t s);
+// ast_ngram.hip: adds [n][2] of token rows tok [n][ld] (row r: its first len[r] + len_bias ids from column col0 on) and, when term is
+// given, the terms at the candidates idx [n][K]
+struct cn_ngram_desc;
+int launch_ast_ngram_adds(const cn_ngram_desc& d, const int* tok, int ld, int col0, const int* len, int len_bias, int n, int eos,
+                          float* adds, const int* idx, int K, float* term, hipStream_t s);
+int launch_ast_ngram_terms(const unsigned char* starts, const float* adds, int eos, const int* idx, int n, int K, float* term,
+                           hipStream_t s);
 int launch_logsoftmax_gather(const float* logits, int M, int V, int ldl, const int* cand, int k, float* out, hipStream_t s);
 
 // ---- fused FFN sublayer, bf16 / d_model == 256                                     (fused.hip)

@@ -214,6 +214,12 @@ struct cn_model {
     // handle whose step runs beside this decoder's.  On an LM handle
     // (cfg.ast = 2) the ast_ck / ast_cv / ast_logits fields above hold ITS step cache [layer][pos][slot][d] and logits.
     cn_model* ast_lm = nullptr;
+    // word n-gram shallow fusion (cn_ast_attach_ngram): the desc by value (device tables the caller keeps alive), lm_weight * ln 10
+    // as float32, and the per-slot (a_word, a_eos) pairs of cn_decode_ast's step loop
+    cn_ngram_desc ast_ng = {};
+    bool ast_ng_on = false;
+    float ast_ng_scale = 0.f;
+    float* beam_adds = nullptr;  // [S][2]
     const void* lib_tag = nullptr;  // which of the two libraries created the handle (an attach never crosses them)
 
     // last call

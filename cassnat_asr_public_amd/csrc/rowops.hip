@@ -287,6 +287,51 @@ int launch_logsoftmax_fuse_topk(const float* att, const float* lm, int M, int V,
     return 0;
 }
 
+// Word n-gram shallow fusion without CTC (include/cassnat_hip_ast_ngram.h): logsoftmax_topk_kernel<true>'s sibling.  The second
+// addend of entry c is no LM row but fl32(w * term(c)), term(c) one of three numbers: adds[row][1] for eos, adds[row][0] for a piece
+// that begins with a separator (starts[c]), 0 for every other.  The row arithmetic before it - x / T, maximum, log-sum-exp,
+// (x - max) - lse - and the selection after it are logsoftmax_topk_kernel's, so zero adds give its output bit for bit.
+__global__ __launch_bounds__(256) void logsoftmax_class_topk_kernel(const float* __restrict__ logits, int V, int ldl, float temperature,
+                                                                    int k, int* __restrict__ idx, float* __restrict__ val,
+                                                                    const unsigned char* __restrict__ starts,
+                                                                    const float* __restrict__ adds, int eos, float w) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    float* row = reinterpret_cast<float*>(smem);
+    __shared__ RowReduceLds red;
+    const float* p = logits + (long long)blockIdx.x * ldl;
+    const int tid = threadIdx.x;
+    if (temperature != 1.0f)
+        for (int i = tid; i < V; i += 256) row[i] = p[i] / temperature;
+    else
+        for (int i = tid; i < V; i += 256) row[i] = p[i];
+    float rmax;
+    int rarg;
+    rr_local_best(row, V, tid, rmax, rarg);
+    rr_block_argmax(red, tid, rmax, rarg);
+    const float lse = rr_block_lse(red, row, V, tid, rmax);
+    const float a_word = cn_mul_rn(w, adds[2 * (long long)blockIdx.x]), a_eos = cn_mul_rn(w, adds[2 * (long long)blockIdx.x + 1]);
+    const float a_none = cn_mul_rn(w, 0.f);
+    for (int i = tid; i < V; i += 256)
+        row[i] = __fadd_rn(__fsub_rn(__fsub_rn(row[i], rmax), lse), i == eos ? a_eos : (starts[i] ? a_word : a_none));
+    rr_select_rounds(red, row, V, tid, k, -INFINITY, [&](int r, int bidx, float best) {
+        idx[(long long)blockIdx.x * k + r] = bidx;
+        val[(long long)blockIdx.x * k + r] = best;
+    });
+}
+
+int launch_logsoftmax_class_topk(const float* att, int M, int V, int ldl, float temperature, const unsigned char* starts,
+                                 const float* adds, int eos, float w, int k, int* idx, float* val, hipStream_t s) {
+    if (k < 1 || k > 32 || k > V || V > 8192) {
+        cn_set_error("logsoftmax_class_topk: need 1 <= k <= min(32, V) and V <= 8192");
+        return -1;
+    }
+    if (M <= 0) return 0;
+    hipLaunchKernelGGL(logsoftmax_class_topk_kernel, dim3(M), dim3(256), (size_t)V * sizeof(float), s, att, V, ldl, temperature, k, idx,
+                       val, starts, adds, eos, w);
+    CN_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
 // LM shallow fusion with CTC (src/models/transformer.py:208-209, lm_prob.gather(1, indices)): per row the log-sum-exp of the LM
 // logits (temperature 1; rowreduce.h, as in logsoftmax_topk_kernel), then out[r][c] = (x[cand[r][c]] - max) - lse for
 // the k attention candidates.  One workgroup per row; the row is read once, into LDS.

@@ -1,4 +1,4 @@
-"""ctypes binding of libcassnat_hip.so (the C ABI declared in include/cassnat_hip.h and its companion cassnat_hip_ctc_ngram.h).
+"""ctypes binding of libcassnat_hip.so (the C ABI declared in include/cassnat_hip.h and its companions, abi.py lists them).
 
 The product path has no CPU fallback: if the library is missing or a call fails, this raises.
 """
@@ -477,6 +477,19 @@ class Engine:
         self._chk(self.L.cn_ast_step_lm(self.handle, tok.shape[0], pos, _ptr(tok), _ptr(utt), _ptr(anc), _ptr(keyok), anc.shape[1],
                                     float(temperature), K, float(lm_weight), int(use_ctc), _ptr(topk_idx), _ptr(topk_val),
                                     _ptr(lm_val) if lm_val is not None else None, current_stream()), "cn_ast_step_lm")
+
+    def ast_attach_ngram(self, desc, lm_scale=0.0):
+        """Word n-gram shallow fusion (include/cassnat_hip_ast_ngram.h): ``desc`` a ``CnNgramDesc`` over tables on this engine's
+        device (copied; the caller keeps the tables alive while attached), ``lm_scale`` = float32(lm_weight * ln 10); None detaches."""
+        self._chk(self.L.cn_ast_attach_ngram(self.handle, C.byref(desc) if desc is not None else None, float(lm_scale)),
+                  "cn_ast_attach_ngram")
+
+    def ast_step_ngram(self, pos, tok, utt, anc, keyok, temperature, K, use_ctc, eos, adds, topk_idx, topk_val, term=None):
+        """``ast_step`` with the attached n-gram model: ``adds`` float32 (n, 2) cuda.  Without CTC topk_idx / topk_val are the fused
+        top-K; with CTC they are the attention top-K and ``term`` (n, K) receives the terms at it."""
+        self._chk(self.L.cn_ast_step_ngram(self.handle, tok.shape[0], pos, _ptr(tok), _ptr(utt), _ptr(anc), _ptr(keyok), anc.shape[1],
+                                           float(temperature), K, int(use_ctc), int(eos), _ptr(adds), _ptr(topk_idx), _ptr(topk_val),
+                                           _ptr(term) if term is not None else None, current_stream()), "cn_ast_step_ngram")
 
     # ---- CASS-NAT + LM: the finish loop with LM shallow fusion
     def nat_attach_lm(self, lm):

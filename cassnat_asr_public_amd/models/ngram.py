@@ -161,6 +161,18 @@ class NgramLM(object):
                   "cn_ngram_score_host")
         return out
 
+    def ast_adds_host(self, rows, lens, eos):
+        """rows int32 (n, ld), lens int32 (n,), numpy -> float32 (n, 2): per hypothesis (tokens behind sos) what a token that begins
+        a word and what eos add in the AST beam search (include/cassnat_hip_ast_ngram.h), on the host."""
+        self._need_pieces()
+        rows, lens = np.ascontiguousarray(rows, np.int32), np.ascontiguousarray(lens, np.int32)
+        n, ld = rows.shape
+        assert lens.shape == (n,)
+        out = np.zeros((n, 2), np.float32)
+        hip.check(hip.lib().cn_ast_ngram_adds_host(C.byref(self.desc()), _ptr(rows), ld, _ptr(lens), n, int(eos), _ptr(out)),
+                  "cn_ast_ngram_adds_host")
+        return out
+
     def score_tokens(self, tok, ylen, drop_id=2):
         """The same on the device: CUDA int32 tensors (rows, stride) and (rows,) -> CUDA float32 (rows,), on the current stream."""
         self._need_pieces()

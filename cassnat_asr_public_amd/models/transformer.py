@@ -11,6 +11,7 @@ Python over ``cn_ast_begin / cn_ast_step / cn_ast_ctc_score`` (same results; use
 With ``args.lm_weight > 0`` the TransformerLM ``lm_model`` (models.lm) is fused (transformer.py:186-209): its incremental
 step runs beside the decoder's on the same ancestor / key-mask tables (``cn_ast_attach_lm``, ``cn_ast_step_lm``).
 """
+import math
 from types import SimpleNamespace
 
 import numpy as np
@@ -123,18 +124,29 @@ class Transformer(nn.Module):
         """Same contract as the reference's Transformer.beam_decode (src/models/transformer.py:122-241), LM shallow fusion
         included (``args.lm_weight > 0`` with ``lm_model`` a models.lm.TransformerLM).  ``engine``: run on this handle (a decode
         pipeline's, see ``new_engine``) instead of the model's own; ``lm_engine``: the pipeline's LM handle
-        (TransformerLM.new_engine) instead of the LM's own."""
+        (TransformerLM.new_engine) instead of the LM's own.
+
+        ``lm_model`` a models.ngram.NgramLM (``rank_model: n-gram`` with an ARPA file): word n-gram shallow fusion
+        (include/cassnat_hip_ast_ngram.h) - the model's device tables are attached with float32(lm_weight * ln 10) for the call.
+        The ``hip_host_beam`` loop takes its per-hypothesis adds from ``lm_model.ast_adds_host``; any object that offers that
+        method beside ``desc`` / ``cuda`` / ``device_ok`` serves there."""
         lm_weight = float(getattr(args, "lm_weight", 0) or 0)
         if lm_weight <= 0:
             return self._beam_decode(src, args, vocab, engine, None, 0.0)
         if lm_model is None:
             raise ValueError("beam_decode: lm_weight > 0 needs lm_model")
+        if hasattr(lm_model, "ast_adds_host"):
+            if not lm_model.device_ok:
+                raise ValueError("a piece of the vocabulary has a separator behind its leading run: its hypotheses cannot be glued into "
+                                 "words, so the AST beam search cannot fuse the n-gram model")
+            # (ARPA scores are log10, the attention and CTC scores natural logarithms)
+            return self._beam_decode(src, args, vocab, engine, None, 0.0, ngram=lm_model, ngram_scale=float(np.float32(lm_weight * math.log(10.0))))
         bw = int(args.beam_width)
         B = src.shape[0]
         lm_eng = lm_engine if lm_engine is not None else lm_model.step_engine(B * bw)
         return self._beam_decode(src, args, vocab, engine, lm_eng, lm_weight)
 
-    def _beam_decode(self, src, args, vocab, engine, lm_eng, lm_weight):
+    def _beam_decode(self, src, args, vocab, engine, lm_eng, lm_weight, ngram=None, ngram_scale=0.0):
         sos, eos = vocab.word2index["sos"], vocab.word2index["eos"]
         assert vocab.word2index["blank"] == args.padding_idx
         dev = torch.device("cuda", getattr(self, "_device", torch.cuda.current_device()))
@@ -149,13 +161,19 @@ class Transformer(nn.Module):
         max_len = max_step + 1
         opts = hip.CnDecodeOpts(padding_idx=int(args.padding_idx), sos=sos, beam_width=1)
         eng.ast_attach_lm(lm_eng)  # (None detaches: a handle never keeps an LM from an earlier call)
+        eng.ast_attach_ngram(None)
         try:
-            return self._beam_search(eng, feats, opts, args, sos, eos, bw, K, use_ctc, max_step, lm_weight, dev)
+            if ngram is not None:
+                ngram.cuda(dev)
+                eng.ast_attach_ngram(ngram.desc(dev), ngram_scale)
+            return self._beam_search(eng, feats, opts, args, sos, eos, bw, K, use_ctc, max_step, lm_weight, dev, ngram, ngram_scale)
         finally:
             if lm_eng is not None:
                 eng.ast_attach_lm(None)
+            if ngram is not None:
+                eng.ast_attach_ngram(None)
 
-    def _beam_search(self, eng, feats, opts, args, sos, eos, bw, K, use_ctc, max_step, lm_weight, dev):
+    def _beam_search(self, eng, feats, opts, args, sos, eos, bw, K, use_ctc, max_step, lm_weight, dev, ngram=None, ngram_scale=0.0):
         B = feats.shape[0]
         max_len = max_step + 1
         use_lm = lm_weight > 0
@@ -182,7 +200,7 @@ class Transformer(nn.Module):
         eng.ast_begin(feats, opts, use_ctc, max_len, B * bw, K if use_ctc else 0)
         w32 = np.float32(args.ctc_weight)
         u32 = np.float32(1 - args.ctc_weight)
-        lw32 = np.float32(lm_weight)
+        lw32 = np.float32(ngram_scale if ngram is not None else lm_weight)
 
         beams = [[{"score": 0.0, "hyp": [sos], "anc": [], "ctc_ref": -1 - b, "ctc_prev": np.float32(0.0)}] for b in range(B)]
         idx_d = torch.empty(B * bw, K, dtype=torch.int32, device=dev)
@@ -204,7 +222,14 @@ class Transformer(nn.Module):
                 keyok[k, : i + 1] = [t != args.padding_idx for t in s["hyp"]]
             tok_d, utt_d = torch.from_numpy(tok).to(dev), torch.from_numpy(utt).to(dev)
             anc_d, keyok_d = torch.from_numpy(anc).to(dev), torch.from_numpy(keyok).to(dev)
-            if use_lm:  # no CTC: val = top-K of att + lm_weight * lm; with CTC: attention top-K and the LM at those candidates
+            if ngram is not None:  # as use_lm, the LM row being the n-gram terms of the hypotheses' own tokens (behind sos)
+                rows = np.zeros((n, max(1, i)), np.int32)
+                for k, (_, s) in enumerate(live):
+                    rows[k, :i] = s["hyp"][1:]
+                adds = np.ascontiguousarray(ngram.ast_adds_host(rows, np.full(n, i, np.int32), eos), np.float32).reshape(n, 2)
+                eng.ast_step_ngram(i, tok_d, utt_d, anc_d, keyok_d, args.T, K, use_ctc, eos, torch.from_numpy(adds).to(dev), idx_d[:n],
+                                   val_d[:n], lm_d[:n])
+            elif use_lm:  # no CTC: val = top-K of att + lm_weight * lm; with CTC: attention top-K and the LM at those candidates
                 eng.ast_step_lm(i, tok_d, utt_d, anc_d, keyok_d, args.T, K, lm_weight, use_ctc, idx_d[:n], val_d[:n], lm_d[:n])
             else:
                 eng.ast_step(i, tok_d, utt_d, anc_d, keyok_d, args.T, K, idx_d[:n], val_d[:n])
@@ -216,7 +241,7 @@ class Transformer(nn.Module):
             if use_ctc:
                 prev = np.array([s["ctc_prev"] for _, s in live], np.float32)[:, None]
                 local = w32 * (ctc - prev) + u32 * att  # float32, same op order as transformer.py:205-206
-                if use_lm:
+                if use_lm or ngram is not None:
                     local = local + lw32 * lm_d[:n].cpu().numpy()  # transformer.py:208-209
                 local_idx = np.argsort(-local, axis=1, kind="stable")[:, :bw]
                 local_scores = np.take_along_axis(local, local_idx, 1)

@@ -5,7 +5,8 @@ Same constructor / decode surface and result-file lines ("<utt> tok tok ...").  
 (art_task.py:252-259): ``ctc_att`` (joint CTC/attention beam search, src/models/transformer.py:122-241), ``ctc_only`` (CTC prefix
 beam search on the encoder, utils.beam_decode.ctc_beam_decode) and ``ctc_correct`` (the decoder as a correction model over the CTC
 greedy hypothesis, transformer.py:243-342).  ``ctc_att`` with ``--lm_weight > 0`` fuses the TransformerLM of ``--lm_config`` /
-``--rnnlm`` (art_task.py:67-90, transformer.py:186-209) on the device; LM fusion in ``ctc_only`` / ``ctc_correct`` raises.
+``--rnnlm`` (art_task.py:67-90, transformer.py:186-209) on the device, or - with ``--rank_model n-gram`` and an ARPA text in
+``--rnnlm`` - a word n-gram model (models.ngram.NgramLM); LM fusion in ``ctc_only`` / ``ctc_correct`` raises.
 A decode step keeps a handful of CUs busy, so a test set goes through
 ``args.hip_pipelines`` (default 4) engine handles (own workspace + KV cache, ONE shared device copy of the weights) on their
 own HIP streams and host threads - batches pulled from the loader by the workers, result lines written in input order.
@@ -28,7 +29,7 @@ from ..models import make_conformer, make_transformer
 from ..utils import util
 from ..utils.beam_decode import ctc_beam_decode
 from .base_task import BaseTask
-from .cassnat_task import hyp_to_words
+from .cassnat_task import _is_arpa, hyp_to_words
 
 _DEFAULTS = dict(use_gpu=True, decode_type="ctc_att", use_cmvn=False, dataset_type="SpeechDataset", beam_width=10, ctc_beam=15,
                  ctc_pruning=0, ctc_lp=0, ctc_lm_weight=0, ctc_weight=0.3, max_decode_ratio=0, T=1.0, length_penalty=None, lm_weight=0, left_ctx=0, right_ctx=0,
@@ -91,6 +92,18 @@ class ArtTask(BaseTask):
         if getattr(args, "decode_type", "ctc_att") != "ctc_att":
             raise NotImplementedError("LM fusion with decode_type '%s' is outside the accelerated path (ctc_att fuses the LM)"
                                       % args.decode_type)
+        if getattr(args, "rank_model", "lm") == "n-gram":
+            # an ARPA text: the package's own word n-gram model, fused in the step loop on the device (every rank reads the file
+            # itself); binary kenlm files stay out
+            if not _is_arpa(args.rnnlm):
+                raise NotImplementedError("rank_model 'n-gram' needs an ARPA text in --rnnlm (a binary kenlm file is not read)")
+            from ..models.ngram import NgramLM
+
+            print("Loading n-gram language model from {}".format(args.rnnlm))
+            self.lm_model = NgramLM.load(args.rnnlm, self.vocab)
+            if torch.cuda.is_available():  # (the tables go up once, before the decode workers start)
+                self.lm_model.cuda(getattr(self.model, "_device", None))
+            return
         import yaml
         from types import SimpleNamespace
 
@@ -111,7 +124,7 @@ class ArtTask(BaseTask):
 
     def _lm_engines(self, n, args):
         """One LM handle per pipeline (own step cache), all on the LM's one device copy of the weights."""
-        if self.lm_model is None:
+        if self.lm_model is None or not hasattr(self.lm_model, "step_engine"):  # (an NgramLM: the workers share its read-only tables)
             return [None] * n
         slots = int(args.batch_size) * int(args.beam_width)
         lm0 = self.lm_model.step_engine(slots)

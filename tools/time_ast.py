@@ -8,14 +8,22 @@ preparation) apart from the decoder steps: ``decoder_ms_per_step`` = (search - e
 ``--lm lm_small|lm_recipe``: LM shallow fusion (transformer.py:186-209) with a seeded TransformerLM of that synth preset
 (lm_recipe = conf/lm.yaml: 16 layers, d 512); ``lm_ms_per_step`` times the LM step alone (cn_lm_step over the same slots and
 positions).  ``--beam`` / ``--ctc-beam``: run_art.sh stage 3 uses 20 / 30.
+``--lm ngram``: word n-gram shallow fusion (include/cassnat_hip_ast_ngram.h) with a synthetic order-3 ARPA model of about
+``--ngram-entries`` entries (time_esa.write_synthetic_arpa) over a vocabulary of one-piece words and continuation pieces.
+``--alternate none,ngram,lm_recipe --rounds 5``: the legs named take turns in one process, ``--rounds`` timed decodes each (after
+one warm-up each); one JSON line per leg with the median and the range of ms per step and utt/s, and nothing else is measured.
 
     python tools/time_ast.py [--model transformer|conformer] [--batch 32] [--frames 1000] [--precision bf16] [--ctc-weight 0.3] [--ratio 0.3]
-                             [--lm none|lm_small|lm_recipe] [--lm-weight 0.6] [--beam 10] [--ctc-beam 15]
+                             [--lm none|lm_small|lm_recipe|ngram] [--lm-weight 0.6] [--beam 10] [--ctc-beam 15] [--ngram-entries N]
+                             [--alternate none,ngram,lm_recipe --rounds 5]
 """
 import argparse
+import copy
 import json
 import os
+import statistics
 import sys
+import tempfile
 import time
 
 import torch
@@ -31,6 +39,71 @@ class Vocab:
     word2index = {"blank": 0, "sos": 1, "eos": 2, "unk": 3}
 
 
+def piece_vocab(n):
+    """A vocabulary of n pieces for the n-gram legs: the four specials, then three one-piece words for every continuation piece."""
+    pieces = ["blank", "sos", "eos", "unk"] + [("c%d" if i % 4 == 3 else "\u2581w%d") % i for i in range(n - 4)]
+    v = Vocab()
+    v.index2word, v.n_words = dict(enumerate(pieces)), n
+    return v
+
+
+def make_ngram(vocab, entries):
+    from cassnat_asr_public_amd.models.ngram import NgramLM
+    from time_esa import write_synthetic_arpa
+
+    with tempfile.TemporaryDirectory() as d:
+        path = os.path.join(d, "synthetic.arpa")
+        n = write_synthetic_arpa(path, [vocab.index2word[i] for i in range(4, vocab.n_words)], entries=entries)
+        lm = NgramLM.load(path, vocab).cuda()
+    return lm, n
+
+
+def make_transformer_lm(preset, vocab_size, precision):
+    lm_args = synth.make_args_lm(preset, vocab_size=vocab_size)
+    lm_args.hip_precision = precision
+    lm = make_lm(lm_args).cuda()
+    lm_state = synth.make_state(lm_args, seed=9)
+    with torch.no_grad():
+        for k, p in lm.named_parameters():
+            p.copy_(torch.from_numpy(lm_state[k]))
+    return lm
+
+
+def alternate(a, args, model, src, mask):
+    """The legs of --alternate in turn, --rounds times: per leg the median and range of ms per decode step and utt/s."""
+    vocab = piece_vocab(args.vocab_size)
+    legs = {}
+    for name in a.alternate.split(","):
+        largs = copy.copy(args)
+        largs.lm_weight = 0 if name == "none" else a.lm_weight
+        entries = None
+        if name == "none":
+            lm = None
+        elif name == "ngram":
+            lm, entries = make_ngram(vocab, a.ngram_entries)
+        else:
+            lm = make_transformer_lm(name, args.vocab_size, a.precision)
+        legs[name] = dict(args=largs, lm=lm, entries=entries, sec=[], steps=0)
+    for r in range(a.rounds + 1):  # (round 0 warms every leg up)
+        for name, leg in legs.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            beams = model.beam_decode(src, mask, vocab, leg["args"], leg["lm"])
+            torch.cuda.synchronize()
+            if r:
+                leg["sec"].append(time.perf_counter() - t0)
+            leg["steps"] = max(len(b[0]["hyp"]) for b in beams) - 1
+    for name, leg in legs.items():
+        ms = [1e3 * t / max(leg["steps"], 1) for t in leg["sec"]]
+        ups = [a.batch / t for t in leg["sec"]]
+        print(json.dumps({"leg": name, "model": a.model, "precision": a.precision, "batch": a.batch, "frames": a.frames, "beam": a.beam,
+                          "ctc_beam": a.ctc_beam, "ctc_weight": a.ctc_weight, "lm_weight": leg["args"].lm_weight, "ngram_entries": leg["entries"],
+                          "rounds": a.rounds, "decode_steps": leg["steps"],
+                          "ms_per_decode_step": {"median": round(statistics.median(ms), 3), "min": round(min(ms), 3), "max": round(max(ms), 3)},
+                          "utt_per_sec": {"median": round(statistics.median(ups), 2), "min": round(min(ups), 2), "max": round(max(ups), 2)},
+                          "all_runs_sec": [round(t, 4) for t in leg["sec"]]}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", choices=("transformer", "conformer"), default="transformer")
@@ -43,7 +116,10 @@ def main():
     ap.add_argument("--streams", type=int, default=1,
                     help="decode pipelines (engine handle + HIP stream + host thread each) working on independent batches: a decode "
                          "step occupies a handful of CUs, so throughput - not latency - scales with pipelines")
-    ap.add_argument("--lm", choices=("none", "lm_small", "lm_recipe"), default="none")
+    ap.add_argument("--lm", choices=("none", "lm_small", "lm_recipe", "ngram"), default="none")
+    ap.add_argument("--ngram-entries", type=int, default=1000000)
+    ap.add_argument("--alternate", default="", help="comma-separated legs (none, ngram, lm_small, lm_recipe) that take turns in one process")
+    ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--lm-weight", type=float, default=0.6)
     ap.add_argument("--beam", type=int, default=10)
     ap.add_argument("--ctc-beam", type=int, default=15)
@@ -61,22 +137,21 @@ def main():
     with torch.no_grad():
         for k, p in model.named_parameters():
             p.copy_(torch.from_numpy(state[k]))
-    lm = None
-    if a.lm != "none":
-        lm_args = synth.make_args_lm(a.lm, vocab_size=args.vocab_size)
-        lm_args.hip_precision = a.precision
-        lm = make_lm(lm_args).cuda()
-        lm_state = synth.make_state(lm_args, seed=9)
-        with torch.no_grad():
-            for k, p in lm.named_parameters():
-                p.copy_(torch.from_numpy(lm_state[k]))
     src = torch.from_numpy(feats).cuda()
     mask = (src[:, :, 0] != args.padding_idx).unsqueeze(1)
+    if a.alternate:
+        return alternate(a, args, model, src, mask)
+    lm, vocab, ngram_entries = None, Vocab, None
+    if a.lm == "ngram":
+        vocab = piece_vocab(args.vocab_size)
+        lm, ngram_entries = make_ngram(vocab, a.ngram_entries)
+    elif a.lm != "none":
+        lm = make_transformer_lm(a.lm, args.vocab_size, a.precision)
     times = []
     for r in range(a.reps + 1):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        beams = model.beam_decode(src, mask, Vocab, args, lm)
+        beams = model.beam_decode(src, mask, vocab, args, lm)
         torch.cuda.synchronize()
         times.append(time.perf_counter() - t0)
     best = min(times[1:])
@@ -94,7 +169,7 @@ def main():
         enc.append(time.perf_counter() - t0)
     enc_best = min(enc[1:])
     lm_ms = None
-    if lm is not None:  # the LM step alone on the beam's slots, position after position (identity ancestor table)
+    if lm is not None and a.lm != "ngram":  # the LM step alone on the beam's slots, position after position (identity ancestor table)
         S = a.batch * int(args.beam_width)
         leng = lm.step_engine(S)
         leng.lm_step_begin(steps + 1, S)
@@ -112,7 +187,7 @@ def main():
             lt.append(time.perf_counter() - t0)
         lm_ms = round(1e3 * min(lt[1:]) / max(steps, 1), 3)
     out = {"workload": "BASELINE configs[3]: AST beam search, 12L enc / 6L dec, beam %d, ctc_beam %d" % (args.beam_width, args.ctc_beam),
-           "lm": a.lm, "lm_weight": args.lm_weight, "lm_ms_per_step": lm_ms,
+           "lm": a.lm, "lm_weight": args.lm_weight, "lm_ms_per_step": lm_ms, "ngram_entries": ngram_entries,
            "model": a.model, "encoder": "conformer (d_encff 1024, kernel 31, max_rel 20)" if a.model == "conformer" else "transformer",
            "decoder_ffn": "swish" if a.model == "conformer" else "relu",
            "encoder_ms": round(1e3 * enc_best, 3), "decoder_ms_per_step": round(1e3 * (best - enc_best) / max(steps, 1), 3),
@@ -131,14 +206,14 @@ def main():
                     p.copy_(torch.from_numpy(state[k]))
             models.append(m2)
         S = a.batch * int(args.beam_width)  # one LM handle (own step cache) per pipeline, one copy of the LM weights
-        lm_engs = [None] * a.streams if lm is None else [lm.step_engine(S)] + [lm.new_engine(S, share=lm.step_engine(S))
+        lm_engs = [None] * a.streams if lm is None or a.lm == "ngram" else [lm.step_engine(S)] + [lm.new_engine(S, share=lm.step_engine(S))
                                                                                  for _ in range(a.streams - 1)]
 
         def worker(i, n):
             st = torch.cuda.Stream()
             with torch.cuda.stream(st):
                 for _ in range(n):
-                    models[i].beam_decode(src, mask, Vocab, args, lm, lm_engine=lm_engs[i])
+                    models[i].beam_decode(src, mask, vocab, args, lm, lm_engine=lm_engs[i])
                 st.synchronize()
 
         for n in (1, a.reps):  # warm-up round (engine builds), then the timed one
