@@ -1,5 +1,5 @@
 // AST beam search with word n-gram shallow fusion for gfx950: `--task art`, `decode_type: ctc_att`, `rank_model: n-gram`, an ARPA
-// model and lm_weight > 0.  The reference fuses only a TransformerLM there; this is the word-level fusion of ctc_ngram.hip in
+// model and lm_weight > 0.  The reference fuses only a TransformerLM there; this is the word-level fusion of ctc_ngram_search.h in
 // Transformer.beam_decode's step loop.  ast_ngram_search.h holds the step functions, include/cassnat_hip_ast_ngram.h the contract.
 //
 // What a candidate token adds depends on its class alone - eos, a piece that begins a word, any other - so a step needs two floats
@@ -35,7 +35,7 @@ __global__ __launch_bounds__(64) void ast_ngram_adds_kernel(cn_ngram_desc d, con
                                                             float* __restrict__ term) {
     __shared__ int32_t ids[NG_HIST + 64];  // the last NG_HIST ids of the chunks before, then this chunk's closed words in order
     __shared__ AnState st;
-    __shared__ NgProbe pr[2 * CG_TASKS];
+    __shared__ NgProbe pr[2 * NG_TASKS];
     __shared__ float out[2];
     const int row = blockIdx.x, lane = threadIdx.x;
     int n = len[row] + len_bias;
@@ -79,7 +79,7 @@ __global__ __launch_bounds__(64) void ast_ngram_adds_kernel(cn_ngram_desc d, con
         st.hist[NG_HIST + 1] = d.bos;
     }
     __syncthreads();
-    if (lane < 2 * CG_TASKS) an_probe(d, st, lane, &pr[lane]);
+    if (lane < 2 * NG_TASKS) an_probe(d, st, lane, &pr[lane]);
     __syncthreads();
     if (lane == 0) {
         an_adds(d, st, pr, out);
@@ -102,7 +102,7 @@ __global__ __launch_bounds__(256) void ast_ngram_terms_kernel(const unsigned cha
 
 int launch_ast_ngram_adds(const cn_ngram_desc& d, const int* tok, int ld, int col0, const int* len, int len_bias, int n, int eos,
                           float* adds, const int* idx, int K, float* term, hipStream_t s) {
-    const std::string bad = an_check_desc(d);
+    const std::string bad = ng_check_desc(d);
     if (!bad.empty()) {
         cn_set_error("ast_ngram_adds: " + bad);
         return -1;
@@ -145,7 +145,7 @@ extern "C" int cn_ast_ngram_adds_host(const cn_ngram_desc* desc, const int32_t* 
         cn_set_error("cn_ast_ngram_adds_host: null argument, or rows / stride < 1");
         return -1;
     }
-    const std::string bad = an_check_desc(*desc);
+    const std::string bad = ng_check_desc(*desc);
     if (!bad.empty()) {
         cn_set_error("cn_ast_ngram_adds_host: " + bad);
         return -1;

@@ -5,16 +5,16 @@
 // A hypothesis is a row of word-piece ids (no sos).  Ids equal to eos and ids outside [0, vocab) contribute no piece; the others are
 // glued with the ranker's piece monoid (ngram_core.h), a piece that begins with a separator closing the word before it.  What the
 // walk leaves behind is an AnState: the carry of the open word (pw == 1: none), the last NG_HIST closed word ids (<s> in front) and
-// their count.  From it the two numbers a step needs derive with at most 15 + 15 independent table probes (cg_probe), summed in
-// ng_word_score's order (cg_word_score):
+// their count.  From it the two numbers a step needs derive with at most 15 + 15 independent table probes (ng_probe), summed in
+// ng_word_score's order (ng_probe_score):
 //   close32 = score(open word | history), end32 = score(</s> | history [+ open word])
 //   a_word  = open ? close32 : 0,          a_eos = open ? fl32(close32 + end32) : end32
 // and the term of a candidate token c is a_eos if c == eos, a_word if the piece c begins with a separator, else 0.
 #pragma once
 #include "../../include/cassnat_hip_ast_ngram.h"
-#include "ctc_ngram_search.h"
+#include "ngram_core.h"
 
-constexpr int AN_CLOSE = 0, AN_END = CG_TASKS;  // first probe of the open word's score / of </s>'s in an NgProbe[2 * CG_TASKS]
+constexpr int AN_CLOSE = 0, AN_END = NG_TASKS;  // first probe of the open word's score / of </s>'s in an NgProbe[2 * NG_TASKS]
 
 struct AnState {
     NgPiece carry;              // the open word
@@ -46,26 +46,26 @@ NG_HD void an_advance(const cn_ngram_desc& d, AnState* s, int32_t t, int32_t eos
     s->carry = ng_combine(s->carry, pc);
 }
 
-// What probe `task` of 0 .. 2 * CG_TASKS - 1 looks up, given the walked state with hist[NG_HIST] = id of the open word (if any):
+// What probe `task` of 0 .. 2 * NG_TASKS - 1 looks up, given the walked state with hist[NG_HIST] = id of the open word (if any):
 // tasks AN_CLOSE + t score the open word behind the history, tasks AN_END + t score </s> behind the history plus the open word.
 NG_HD void an_probe(const cn_ngram_desc& d, const AnState& s, int task, NgProbe* out) {
     const bool open = s.carry.pw != 1;
     out->prob = 0.f, out->bo = 0.f, out->found = 0;
     if (task < AN_END) {
-        if (open && task < CG_TASKS - 1) cg_probe(d, s.hist + NG_HIST, an_context(d, s.nwords), s.hist[NG_HIST], task, out);
-    } else if (task - AN_END < CG_TASKS - 1) {
+        if (open && task < NG_TASKS - 1) ng_probe(d, s.hist + NG_HIST, an_context(d, s.nwords), s.hist[NG_HIST], task, out);
+    } else if (task - AN_END < NG_TASKS - 1) {
         const int shift = open ? 1 : 0;
-        cg_probe(d, s.hist + NG_HIST + shift, an_context(d, s.nwords + shift), d.eos, task - AN_END, out);
+        ng_probe(d, s.hist + NG_HIST + shift, an_context(d, s.nwords + shift), d.eos, task - AN_END, out);
     }
 }
 
-// adds = (a_word, a_eos) from the 2 * CG_TASKS probes
+// adds = (a_word, a_eos) from the 2 * NG_TASKS probes
 NG_HD void an_adds(const cn_ngram_desc& d, const AnState& s, const NgProbe* pr, float* adds) {
     const bool open = s.carry.pw != 1;
     const int shift = open ? 1 : 0;
-    const float end32 = cg_word_score(pr + AN_END, an_context(d, s.nwords + shift));
+    const float end32 = ng_probe_score(pr + AN_END, an_context(d, s.nwords + shift));
     if (open) {
-        const float close32 = cg_word_score(pr + AN_CLOSE, an_context(d, s.nwords));
+        const float close32 = ng_probe_score(pr + AN_CLOSE, an_context(d, s.nwords));
         adds[0] = close32;
         adds[1] = close32 + end32;
     } else {
@@ -80,24 +80,13 @@ NG_HD float an_term(const unsigned char* starts, const float* adds, int32_t eos,
 }
 
 // ---- host only -------------------------------------------------------------------------------------------------------------------
-// "" when the desc can be walked (pointers of the caller's side: not dereferenced here), else what is wrong
-inline std::string an_check_desc(const cn_ngram_desc& d) {
-    if (!d.word_keys || !d.word_ids || !d.gram_keys || !d.gram_prob || !d.gram_bo || !d.piece_hash || !d.piece_pow || !d.piece_starts)
-        return "null table in the desc";
-    if (d.order < 1 || d.order > NG_MAX_ORDER) return "order " + std::to_string(d.order) + " is outside 1 .. 8";
-    if (d.word_slots < 1 || (d.word_slots & (d.word_slots - 1)) || d.gram_slots < 1 || (d.gram_slots & (d.gram_slots - 1)))
-        return "the slot counts must be powers of two";
-    if (d.vocab < 0) return "vocab must not be negative";
-    return "";
-}
-
 // adds of one row of n ids, every pointer a host pointer
 inline void an_adds_row_host(const cn_ngram_desc& d, const int32_t* tok, int n, int32_t eos, float* adds) {
     AnState s;
     an_init(d, &s);
     for (int i = 0; i < n; ++i) an_advance(d, &s, tok[i], eos);
     if (s.carry.pw != 1) s.hist[NG_HIST] = ng_word_id(d, s.carry.h);
-    NgProbe pr[2 * CG_TASKS];
-    for (int t = 0; t < 2 * CG_TASKS; ++t) an_probe(d, s, t, &pr[t]);
+    NgProbe pr[2 * NG_TASKS];
+    for (int t = 0; t < 2 * NG_TASKS; ++t) an_probe(d, s, t, &pr[t]);
     an_adds(d, s, pr, adds);
 }

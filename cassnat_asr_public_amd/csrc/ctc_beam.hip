@@ -1,33 +1,57 @@
-// CTC prefix beam search and CTC forced (Viterbi) alignment for gfx950: the device half of `decode_type: ctc_only / ctc_att`.
+// CTC prefix beam search - without a language model, and with a word n-gram model fused - and CTC forced (Viterbi) alignment for
+// gfx950: the device half of `decode_type: ctc_only / ctc_att`.
 //
-// Reference: ctc_beam_decode (src/utils/beam_decode.py:8-93, called from src/tasks/cassnat_task.py:335-341) and
-// CassNAT.beam_path_align -> viterbi_align (src/models/cassnat.py:391-414, 272-353).
+// The search is ctc_search.h's (ctc_beam_decode, src/utils/beam_decode.py:8-93, called from src/tasks/cassnat_task.py:335-341): one
+// workgroup of 256 per utterance, the frame loop inside the kernel, one candidate per thread (in rounds when there are more than
+// 256), the stable top-W by counting rank, (parent, label) back-pointers per processed frame, unrolled at the end.  One kernel
+// body, two instantiations:
+//   ctc_beam_kernel<false>  score_lm = 0: `ctc_lm_weight: 0`.
+//   ctc_beam_kernel<true>   score_lm = lm_scale * (the word scores of the words a hypothesis has closed): `rank_model: n-gram` with an
+//                           ARPA model and ctc_lm_weight > 0 (ctc_ngram_search.h; the reference has no such search).  On top of the
+//                           body above:
+//     * the n-gram state of the kept hypotheses (CgHyp: carry, history, word count, score_lm and the cached value of closing the open
+//       word) lives in LDS in two buffers: a winner writes slot `rank` of the other buffer from its parent's slot of this one;
+//     * what closing a word adds depends on the parent alone, so table look-ups are per kept hypothesis whose open word changed (at
+//       most W a frame), not per candidate: the winner's thread finds the word's id, then the up to 2 * order - 1 probes of the word's
+//       score are spread over (hypothesis, task) threads and one thread per hypothesis adds them up in ng_word_score's float32 order;
+//     * after the last frame every kept hypothesis adds its open word and </s>, and the beam is sorted once more by the same key.
+//   Every probe loop is bounded by its table's slot count.
 //
-// ctc_beam_decode is a per-frame loop over a Python list of hypotheses: every kept hypothesis yields one "stay" candidate
-// (blank or a repetition of its last label) and one candidate per pruned label of the frame; the candidates are NOT merged
-// by prefix; a stable descending sort by score_ctc + score_lm + ctc_lp * len(hyp) keeps `ctc_beam` of them.  Frames past
-// src_size and frames whose blank probability exceeds 0.95 are skipped.  All scores are Python floats (float64) made of
-// float32 log-posteriors.  Here: one workgroup per utterance, the frame loop inside the kernel, candidates one per thread
-// in float64 with numpy's logaddexp formula, the stable top-W by counting rank (key descending, list position ascending),
-// hypotheses kept as (parent, label) back-pointers per processed frame and unrolled at the end.  Integer / ordering work:
-// the hypotheses are those of the reference wherever two candidate scores are not within an ulp of each other.
-//
-// viterbi_align is the max-product CTC forward pass over the blank-augmented label sequence in float32 followed by a
-// sequential back-trace; here one workgroup per utterance with the two live alpha rows in LDS and the back-pointers in
-// global memory; same float32 operation order, first-maximum-wins among the three predecessors (torch.max).
+// viterbi_align (CassNAT.beam_path_align, src/models/cassnat.py:391-414, 272-353) is the max-product CTC forward pass over the
+// blank-augmented label sequence in float32 followed by a sequential back-trace; here one workgroup per utterance with the two live
+// alpha rows in LDS and the back-pointers in global memory; same float32 operation order, first-maximum-wins among the three
+// predecessors (torch.max).
+#include <type_traits>
+
+#include "ctc_ngram_search.h"
 #include "kernels.h"
 
-#define CB_LOGZERO (-1e10)
+// what the n-gram instantiation keeps in static LDS (the other one: nothing)
+template <bool NGRAM>
+struct CgLds {};
+template <>
+struct CgLds<true> {
+    CgHyp hyps[2][CS_MAX_BEAM];  // n-gram state, double buffered
+    NgProbe probes[CS_MAX_BEAM * NG_TASKS];
+    int wflag[CS_MAX_BEAM], wid[CS_MAX_BEAM];
+};
 
-__device__ __forceinline__ double cb_logaddexp(double x, double y) {  // numpy's npy_logaddexp
-    if (x == y) return x + 0.693147180559945309417232121458176568;
-    const double tmp = x - y;
-    if (tmp > 0) return x + log1p(exp(-tmp));
-    if (tmp <= 0) return y + log1p(exp(tmp));
-    return tmp;
+// the word scores of hypotheses r < n with flag[r] set, word wid[r] behind hy[r]'s history: probes by (hypothesis, task) threads, then
+// thread r returns double(score) * lm_scale (0 for the others).  All 256 threads call it; the caller puts a barrier behind its use.
+__device__ __forceinline__ double cg_score_words(const cn_ngram_desc& d, const CgHyp* hy, const int* flag, const int* wid, int n,
+                                                 NgProbe* probes, double lm_scale) {
+    const int tid = threadIdx.x;
+    for (int i = tid; i < n * NG_TASKS; i += 256) {
+        const int r = i / NG_TASKS, t = i - r * NG_TASKS;
+        if (t < NG_TASKS - 1 && flag[r]) ng_probe(d, hy[r].hist + NG_HIST, cg_context(d, hy[r]), wid[r], t, &probes[i]);
+    }
+    __syncthreads();
+    if (tid < n && flag[tid]) return (double)ng_probe_score(probes + tid * NG_TASKS, cg_context(d, hy[tid])) * lm_scale;
+    return 0.0;
 }
 
-__global__ __launch_bounds__(256) void ctc_prefix_beam_kernel(CtcBeamArgs a) {
+template <bool NGRAM>
+__global__ __launch_bounds__(256) void ctc_beam_kernel(std::conditional_t<NGRAM, CtcNgramArgs, CtcBeamArgs> a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int b = blockIdx.x, tid = threadIdx.x;
     const int W = a.W, P = a.P, NC = W * (P + 1);
@@ -38,88 +62,66 @@ __global__ __launch_bounds__(256) void ctc_prefix_beam_kernel(CtcBeamArgs a) {
     double* cpb = ckey + NC;
     double* cpnb = cpb + NC;
     double* ctot = cpnb + NC;
-    double* ptot = ctot + NC;                      // [W] score_ctc of the kept hypotheses
+    double* cslm = ctot + NC;                      // (n-gram only)
+    double* ptot = cslm + (NGRAM ? NC : 0);        // [W] score_ctc of the kept hypotheses
     int* blen = reinterpret_cast<int*>(ptot + W);  // [W]
     int* blast = blen + W;                         // [W] last label (-1: empty hypothesis)
     int* cpar = blast + W;                         // [NC] parent slot (-1: not a candidate)
     int* ctok = cpar + NC;                         // [NC] appended label (-1: stay)
     int* clen = ctok + NC;
     int* clast = clen + NC;
+    __shared__ CgLds<NGRAM> ng;
     __shared__ int s_nb, s_steps;
 
     const float* logp = a.logp + (long long)b * a.Tp * a.V;
     const int* top = a.top_idx + (long long)b * a.Tp * P;
-    unsigned char* hpar = a.hist_parent + (long long)b * a.Tp * W;
-    int* htok = a.hist_tok + (long long)b * a.Tp * W;
-    // src_size = (ratio * T').long(): fp32 product, truncation (beam_decode.py:22)
-    const int ssz = (int)(long long)(a.size_ratio[b] * (float)a.Tp);
+    const long long hist = (long long)b * a.Tp * W;
+    unsigned char* hpar = a.hist_parent + hist;
+    int* htok = a.hist_tok + hist;
+    const int ssz = cs_src_size(a.size_ratio[b], a.Tp);
     if (tid == 0) {
         pb[0] = 0.0;  // logone
-        pnb[0] = CB_LOGZERO;
+        pnb[0] = CS_LOGZERO;
         ptot[0] = 0.0;
         blen[0] = 0;
         blast[0] = -1;
+        if constexpr (NGRAM) cg_init(a.d, &ng.hyps[0][0]);
         s_nb = 1;
         s_steps = 0;
     }
+    int cur = 0;
     __syncthreads();
     for (int t = 0; t < a.Tp; ++t) {
-        if (t > ssz) continue;  // (the reference does process frame t == src_size)
+        if (t > ssz) continue;
         const float* row = logp + (long long)t * a.V;
-        const float pblank = row[a.blank];
-        // torch.exp of a float32, compared with the double 0.95
-        if ((double)(float)exp((double)pblank) > 0.95) continue;
+        if (cs_skip_frame(row[a.blank])) continue;
         const int nb = s_nb, step = s_steps;
-        for (int i = tid; i < NC; i += 256) {
-            const int k = i / (P + 1), j = i - k * (P + 1);
-            int par = -1, tok = -1, nlen = 0, nlast = -1;
-            double npb = CB_LOGZERO, npnb = CB_LOGZERO, tot = CB_LOGZERO;
-            if (k < nb) {
-                const double p_b = pb[k], p_nb = pnb[k];
-                const int last = blast[k], len = blen[k];
-                if (j == 0) {  // blank or repetition
-                    npnb = len > 0 ? p_nb + (double)row[last] : CB_LOGZERO;
-                    const double pt = (double)pblank;
-                    npb = cb_logaddexp(p_b + pt, p_nb + pt);
-                    tot = cb_logaddexp(npb, npnb);
-                    par = k;
-                    nlen = len;
-                    nlast = last;
-                } else {
-                    const int c = top[(long long)t * P + (j - 1)];
-                    if (c != a.blank) {
-                        const double pt = (double)row[c];
-                        npnb = (c != last) ? cb_logaddexp(p_b + pt, p_nb + pt) : p_b + pt;
-                        npb = CB_LOGZERO;
-                        tot = cb_logaddexp(npb, npnb);
-                        par = k;
-                        tok = c;
-                        nlen = len + 1;
-                        nlast = c;
-                    }
-                }
-            }
-            cpar[i] = par;
-            ctok[i] = tok;
-            clen[i] = nlen;
-            clast[i] = nlast;
-            cpb[i] = npb;
-            cpnb[i] = npnb;
-            ctot[i] = tot;
-            ckey[i] = (tot + 0.0) + a.lp * (double)nlen;  // score_ctc + score_lm + ctc_lp * len(hyp)
-        }
-        __syncthreads();
-        // stable descending order: rank = candidates that sort before this one
         const int ncand = nb * (P + 1);
         for (int i = tid; i < ncand; i += 256) {
-            if (cpar[i] < 0) continue;
-            const double key = ckey[i];
-            int rank = 0;
-            for (int j = 0; j < ncand; ++j) {
-                if (cpar[j] < 0) continue;
-                const double kj = ckey[j];
-                rank += (kj > key || (kj == key && j < i)) ? 1 : 0;
+            const int k = i / (P + 1), j = i - k * (P + 1);
+            const int c = j == 0 ? -1 : top[(long long)t * P + (j - 1)];
+            const CsCand r = cs_candidate(row, a.V, a.blank, k, j == 0, c, pb[k], pnb[k], blast[k], blen[k]);
+            double slm = 0.0;
+            if constexpr (NGRAM) {
+                if (r.par >= 0) slm = cg_candidate_slm(a.d, ng.hyps[cur][k], r.tok);
+                cslm[i] = slm;
             }
+            cpar[i] = r.par;
+            ctok[i] = r.tok;
+            clen[i] = r.len;
+            clast[i] = r.last;
+            cpb[i] = r.pb;
+            cpnb[i] = r.pnb;
+            ctot[i] = r.tot;
+            ckey[i] = cs_key(r.tot, slm, a.lp, r.len);
+        }
+        if constexpr (NGRAM) {
+            if (tid < W) ng.wflag[tid] = 0;
+        }
+        __syncthreads();
+        for (int i = tid; i < ncand; i += 256) {
+            if (cpar[i] < 0) continue;
+            const int rank = cs_rank(ckey, cpar, ncand, i);
             if (rank < W) {
                 pb[rank] = cpb[i];
                 pnb[rank] = cpnb[i];
@@ -128,64 +130,111 @@ __global__ __launch_bounds__(256) void ctc_prefix_beam_kernel(CtcBeamArgs a) {
                 blast[rank] = clast[i];
                 hpar[(long long)step * W + rank] = (unsigned char)cpar[i];
                 htok[(long long)step * W + rank] = ctok[i];
+                if constexpr (NGRAM) {
+                    CgHyp* h = &ng.hyps[cur ^ 1][rank];
+                    if (cg_advance(a.d, ng.hyps[cur][cpar[i]], ctok[i], h) && h->carry.pw != 1) {
+                        ng.wid[rank] = h->close_wid = ng_word_id(a.d, h->carry.h);
+                        ng.wflag[rank] = 1;
+                    }
+                }
             }
         }
         // (pb / pnb / blen / blast were only read in the candidate phase above, behind the barrier: safe to overwrite)
         if (tid == 0) {
-            int valid = 0;
-            for (int j = 0; j < ncand; ++j) valid += cpar[j] >= 0 ? 1 : 0;
-            s_nb = valid < W ? valid : W;
+            s_nb = cs_count_valid(cpar, ncand, W);
             s_steps = step + 1;
         }
         __syncthreads();
-    }
-    // unroll the back-pointers: one thread per kept hypothesis
-    const int nb = s_nb, steps = s_steps;
-    if (tid == 0) a.n_out[b] = nb;
-    if (tid < W) {
-        int* h = a.hyp + ((long long)b * W + tid) * a.Lmax;
-        if (tid < nb) {
-            const int len = blen[tid];
-            int pos = len - 1, cur = tid;
-            for (int st = steps - 1; st >= 0; --st) {
-                const int tok = htok[(long long)st * W + cur];
-                if (tok >= 0) {
-                    if (pos >= 0 && pos < a.Lmax) h[pos] = tok;
-                    --pos;
-                }
-                cur = hpar[(long long)st * W + cur];
-            }
-            for (int i = len; i < a.Lmax; ++i) h[i] = 0;
-            a.hyp_len[b * W + tid] = len;
-            a.score[b * W + tid] = ptot[tid];
-            a.p_blk[b * W + tid] = pb[tid];
-            a.p_nblk[b * W + tid] = pnb[tid];
-        } else {
-            for (int i = 0; i < a.Lmax; ++i) h[i] = 0;
-            a.hyp_len[b * W + tid] = 0;
-            a.score[b * W + tid] = CB_LOGZERO;
-            a.p_blk[b * W + tid] = CB_LOGZERO;
-            a.p_nblk[b * W + tid] = CB_LOGZERO;
+        if constexpr (NGRAM) {
+            cur ^= 1;
+            const int kept = s_nb;
+            const double add = cg_score_words(a.d, ng.hyps[cur], ng.wflag, ng.wid, kept, ng.probes, a.lm_scale);
+            if (tid < kept && ng.wflag[tid]) ng.hyps[cur][tid].close_add = add;
+            __syncthreads();
         }
     }
+    const int nb = s_nb, steps = s_steps;
+    int out = tid;  // the slot a kept hypothesis is written at
+    if constexpr (NGRAM) {
+        // the open word, then </s>, and one more stable sort by the same key
+        if (tid < nb) {
+            CgHyp* h = &ng.hyps[cur][tid];
+            if (h->carry.pw != 1) cg_push_word(h, h->close_wid, h->close_add);
+            ng.wflag[tid] = 1;
+            ng.wid[tid] = a.d.eos;
+        }
+        __syncthreads();
+        const double add = cg_score_words(a.d, ng.hyps[cur], ng.wflag, ng.wid, nb, ng.probes, a.lm_scale);
+        if (tid < nb) {
+            ng.hyps[cur][tid].slm += add;
+            ckey[tid] = cs_key(ptot[tid], ng.hyps[cur][tid].slm, a.lp, blen[tid]);
+            cpar[tid] = tid;
+        }
+        __syncthreads();
+        if (tid < nb) out = cs_rank(ckey, cpar, nb, tid);
+    }
+    // one thread per slot: a kept hypothesis unrolls its back-pointers
+    if (tid == 0) a.out.n_out[b] = nb;
+    if (tid < W) {
+        CsKept kept = {};
+        if (tid < nb) {
+            kept.score = ptot[tid], kept.p_blk = pb[tid], kept.p_nblk = pnb[tid], kept.len = blen[tid];
+            if constexpr (NGRAM) kept.score_lm = ng.hyps[cur][tid].slm;
+        }
+        cs_write_row(a.out, (long long)b * W + out, a.hist_parent, a.hist_tok, hist, W, steps, tid < nb ? tid : -1, kept);
+    }
+}
+
+template <bool NGRAM, class Args>
+static int launch_beam(const Args& a, hipStream_t s) {
+    static CnAttrOnce attr_once;  // (one per instantiation)
+    int attr_dev;
+    if (attr_once.need(&attr_dev)) {
+        CN_HIP_CHECK(hipFuncSetAttribute((const void*)ctc_beam_kernel<NGRAM>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
+        attr_once.mark(attr_dev);
+    }
+    hipLaunchKernelGGL(ctc_beam_kernel<NGRAM>, dim3(a.B), dim3(256), cs_lds_bytes(a.W, a.P, NGRAM), s, a);
+    CN_HIP_CHECK(hipGetLastError());
+    return 0;
 }
 
 int launch_ctc_prefix_beam(const CtcBeamArgs& a, hipStream_t s) {
     if (a.B <= 0) return 0;
-    if (a.W < 1 || a.W > 32 || a.P < 0 || a.P > 32 || a.Lmax < 1) {
-        cn_set_error("ctc_beam: need 1 <= ctc_beam <= 32 and 0 <= ctc_pruning <= 32");
+    const char* bad = cs_check_limits(a.W, a.P, 0, 0);
+    if (bad || a.out.Lmax < 1) {
+        cn_set_error(std::string("ctc_beam: ") + (bad ? bad : "hyp_cap must be at least 1"));
         return -1;
     }
-    const int NC = a.W * (a.P + 1);
-    const size_t lds = (size_t)(3 * a.W + 4 * NC) * 8 + (size_t)(2 * a.W + 4 * NC) * 4 + 64;
-    static CnAttrOnce attr_once;
-    int attr_dev;
-    if (attr_once.need(&attr_dev)) {
-        CN_HIP_CHECK(hipFuncSetAttribute((const void*)ctc_prefix_beam_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-        attr_once.mark(attr_dev);
+    return launch_beam<false>(a, s);
+}
+
+int launch_ctc_ngram_beam(const CtcNgramArgs& a, hipStream_t s) {
+    const std::string bad = cg_check(a, true);
+    if (!bad.empty()) {
+        cn_set_error("ctc_ngram_beam: " + bad);
+        return -1;
     }
-    hipLaunchKernelGGL(ctc_prefix_beam_kernel, dim3(a.B), dim3(256), lds, s, a);
-    CN_HIP_CHECK(hipGetLastError());
+    return launch_beam<true>(a, s);
+}
+
+// the n-gram search on the host: every pointer a host pointer, no GPU call
+extern "C" int cn_ctc_ngram_beam_host(const cn_ngram_desc* desc, const float* logp, const int32_t* top_idx, const float* size_ratio, int32_t B,
+                                      int32_t Tp, int32_t V, int32_t beam, int32_t pruning, double length_penalty, double lm_scale,
+                                      int32_t blank, int32_t* hyp, int32_t hyp_cap, int32_t* hyp_len, double* score, double* score_lm,
+                                      double* p_blk, double* p_nblk, int32_t* nbeam) {
+    if (!desc) {
+        cn_set_error("cn_ctc_ngram_beam_host: null argument");
+        return -1;
+    }
+    const CtcNgramArgs a = ctc_ngram_args(*desc, lm_scale,
+                                          ctc_beam_args(logp, top_idx, size_ratio, B, Tp, V, beam, pruning, blank, length_penalty,
+                                                        ctc_beam_out(hyp, hyp_cap, hyp_len, score, score_lm, p_blk, p_nblk, nbeam)));
+    const std::string bad = cg_check(a, false);
+    if (!bad.empty()) {
+        cn_set_error("cn_ctc_ngram_beam_host: " + bad);
+        return -1;
+    }
+    for (int32_t b = 0; b < B; ++b) cg_search_host(a, b);
     return 0;
 }
 

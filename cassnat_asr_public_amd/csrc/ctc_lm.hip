@@ -10,8 +10,8 @@
 //   LM step    over all S = B * beam slots with a position per row (ast.hip: launch_ast_embed_rows / launch_ast_gather_attn_rows)
 //   rows       the LM's next-token log-probability row of every slot, double buffered: a hypothesis that did not change ("stay")
 //              copies its parent's row, an extended one takes the fresh log-softmax of this iteration's LM step
-//   frame      one workgroup per utterance, one thread per candidate, as ctc_prefix_beam_kernel, plus score_lm
-//   finish     unrolls the back-pointers
+//   frame      one workgroup per utterance, one thread per candidate: one frame of the shared search (ctc_search.h) with score_lm
+//   finish     unrolls the back-pointers (ctc_search.h)
 //
 // score_lm is the reference's: a Python float that is NOT reset between the candidates of a hypothesis - the j-th non-blank
 // candidate carries the parent's score_lm plus double(lm_prob[c_i]) * double(lm_weight) summed over the non-blank labels
@@ -25,29 +25,15 @@
 // what they always read.  Cost: iterations x S rows per layer.
 #include "kernels.h"
 
-#define CL_LOGZERO (-1e10)
-
-namespace {
-__device__ __forceinline__ double cl_logaddexp(double x, double y) {  // numpy's npy_logaddexp
-    if (x == y) return x + 0.693147180559945309417232121458176568;
-    const double tmp = x - y;
-    if (tmp > 0) return x + log1p(exp(-tmp));
-    if (tmp <= 0) return y + log1p(exp(tmp));
-    return tmp;
-}
-}  // namespace
-
-// one thread per utterance: the predicate of ctc_prefix_beam_kernel, frame by frame
+// one thread per utterance: the search's frame predicate, frame by frame
 __global__ void ctc_lm_schedule_kernel(const float* __restrict__ logp, const float* __restrict__ size_ratio, int B, int Tp, int V,
                                        int blank, int* __restrict__ frames, int* __restrict__ count) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
-    const int ssz = (int)(long long)(size_ratio[b] * (float)Tp);
+    const int ssz = cs_src_size(size_ratio[b], Tp);
     int n = 0;
-    for (int t = 0; t < Tp; ++t) {
-        if (t > ssz) break;
-        const float pblank = logp[((long long)b * Tp + t) * V + blank];
-        if ((double)(float)exp((double)pblank) > 0.95) continue;
+    for (int t = 0; t < Tp && t <= ssz; ++t) {
+        if (cs_skip_frame(logp[((long long)b * Tp + t) * V + blank])) continue;
         frames[(long long)b * Tp + n++] = t;
     }
     count[b] = n;
@@ -59,9 +45,9 @@ __global__ void ctc_lm_init_kernel(CtcLmState st, int B, int W, int Lt, int sos)
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= B * W) return;
     const int j = s % W;
-    st.pb[s] = j == 0 ? 0.0 : CL_LOGZERO;
-    st.pnb[s] = CL_LOGZERO;
-    st.sctc[s] = j == 0 ? 0.0 : CL_LOGZERO;
+    st.pb[s] = j == 0 ? 0.0 : CS_LOGZERO;
+    st.pnb[s] = CS_LOGZERO;
+    st.sctc[s] = j == 0 ? 0.0 : CS_LOGZERO;
     st.slm[s] = 0.0;
     st.len[s] = 0;
     st.last[s] = -1;
@@ -115,7 +101,7 @@ __global__ __launch_bounds__(256) void ctc_lm_frame_kernel(CtcLmState st, CtcLmF
     int* ctok = cpar + NC;  // [NC] appended label (-1: stay)
     __shared__ int s_valid;
 
-    const int nb = st.nb[b], t = a.frames[(long long)b * a.Tp + a.iter];
+    const int nb = min(st.nb[b], W), t = a.frames[(long long)b * a.Tp + a.iter];  // (never more candidates than the LDS holds)
     if (t < 0 || t >= a.Tp) return;
     const float* row = a.logp + ((long long)b * a.Tp + t) * a.V;
     const int* top = a.top_idx + ((long long)b * a.Tp + t) * P;
@@ -130,63 +116,33 @@ __global__ __launch_bounds__(256) void ctc_lm_frame_kernel(CtcLmState st, CtcLmF
         next[tid] = 0;
     }
     __syncthreads();
-    const float pblank = row[a.blank];
-    for (int i = tid; i < NC; i += 256) {
-        const int k = i / (P + 1), j = i - k * (P + 1);
-        int par = -1, tok = -1;
-        double npb = CL_LOGZERO, npnb = CL_LOGZERO, tot = CL_LOGZERO, slm = 0.0;
-        int nlen = 0;
-        if (k < nb) {
-            const double p_b = pb[k], p_nb = pnb[k];
-            const int last = blast[k], len = blen[k];
-            if (j == 0) {  // blank or repetition: the parent's score_lm
-                npnb = len > 0 ? p_nb + (double)row[last] : CL_LOGZERO;
-                const double pt = (double)pblank;
-                npb = cl_logaddexp(p_b + pt, p_nb + pt);
-                tot = cl_logaddexp(npb, npnb);
-                par = k;
-                nlen = len;
-                slm = pslm[k];
-            } else {
-                const int c = top[j - 1];
-                if (c != a.blank && c >= 0 && c < a.V) {  // (an id outside the vocabulary is no candidate: nothing is read through it)
-                    const double pt = (double)row[c];
-                    npnb = (c != last) ? cl_logaddexp(p_b + pt, p_nb + pt) : p_b + pt;
-                    tot = cl_logaddexp(CL_LOGZERO, npnb);
-                    par = k;
-                    tok = c;
-                    nlen = len + 1;
-                    // score_lm += lm_prob[s_idx, c].item() * lm_weight over the non-blank labels up to this one, in list order
-                    const float* lm = a.lmrow + (long long)(s0 + k) * a.V;
-                    slm = pslm[k];
-                    for (int jj = 0; jj < j; ++jj) {
-                        const int cc = top[jj];
-                        if (cc != a.blank && cc >= 0 && cc < a.V) slm += cn_mul_rn((double)lm[cc], a.lm_weight);
-                    }
-                }
-            }
-        }
-        cpar[i] = par;
-        ctok[i] = tok;
-        cpb[i] = npb;
-        cpnb[i] = npnb;
-        ctot[i] = tot;
-        cslm[i] = slm;
-        ckey[i] = (tot + slm) + cn_mul_rn(a.lp, (double)nlen);  // x['score_ctc'] + x['score_lm'] + length_penalty * len(x['hyp'])
-    }
-    __syncthreads();
-    // stable descending order: rank = candidates that sort before this one.  The state of the kept hypotheses is in LDS, so the
-    // winners write the new state over it in global memory
     const int ncand = nb * (P + 1);
     for (int i = tid; i < ncand; i += 256) {
-        if (cpar[i] < 0) continue;
-        const double key = ckey[i];
-        int rank = 0;
-        for (int j = 0; j < ncand; ++j) {
-            if (cpar[j] < 0) continue;
-            const double kj = ckey[j];
-            rank += (kj > key || (kj == key && j < i)) ? 1 : 0;
+        const int k = i / (P + 1), j = i - k * (P + 1);
+        // (an id outside the vocabulary is no candidate: nothing is read through it)
+        const CsCand r = cs_candidate(row, a.V, a.blank, k, j == 0, j == 0 ? -1 : top[j - 1], pb[k], pnb[k], blast[k], blen[k]);
+        double slm = pslm[k];  // blank or repetition: the parent's score_lm
+        if (r.tok >= 0) {
+            // score_lm += lm_prob[s_idx, c].item() * lm_weight over the non-blank labels up to this one, in list order
+            const float* lm = a.lmrow + (long long)(s0 + k) * a.V;
+            for (int jj = 0; jj < j; ++jj) {
+                const int cc = top[jj];
+                if (cc != a.blank && cc >= 0 && cc < a.V) slm += cn_mul_rn((double)lm[cc], a.lm_weight);
+            }
         }
+        cpar[i] = r.par;
+        ctok[i] = r.tok;
+        cpb[i] = r.pb;
+        cpnb[i] = r.pnb;
+        ctot[i] = r.tot;
+        cslm[i] = slm;
+        ckey[i] = cs_key(r.tot, slm, a.lp, r.len);
+    }
+    __syncthreads();
+    // The state of the kept hypotheses is in LDS, so the winners write the new state over it in global memory
+    for (int i = tid; i < ncand; i += 256) {
+        if (cpar[i] < 0) continue;
+        const int rank = cs_rank(ckey, cpar, ncand, i);
         if (rank < W) {
             const int k = cpar[i], tok = ctok[i], sn = s0 + rank;
             const int nlen = blen[k] + (tok >= 0 ? 1 : 0), nlast = tok >= 0 ? tok : blast[k];
@@ -206,11 +162,7 @@ __global__ __launch_bounds__(256) void ctc_lm_frame_kernel(CtcLmState st, CtcLmF
             next[rank] = tok >= 0;
         }
     }
-    if (tid == 0) {
-        int valid = 0;
-        for (int j = 0; j < ncand; ++j) valid += cpar[j] >= 0 ? 1 : 0;
-        s_valid = valid < W ? valid : W;
-    }
+    if (tid == 0) s_valid = cs_count_valid(cpar, ncand, W);
     __syncthreads();
     const int nbn = s_valid;
     if (tid == 0) st.nb[b] = nbn;
@@ -231,40 +183,16 @@ __global__ __launch_bounds__(256) void ctc_lm_frame_kernel(CtcLmState st, CtcLmF
     }
 }
 
-// unroll the back-pointers: one thread per kept hypothesis
-__global__ void ctc_lm_finish_kernel(CtcLmState st, CtcLmOut o, const int* __restrict__ count, const unsigned char* __restrict__ hist_parent,
+// one thread per slot: a kept hypothesis unrolls its back-pointers
+__global__ void ctc_lm_finish_kernel(CtcLmState st, CtcBeamOut o, const int* __restrict__ count, const unsigned char* __restrict__ hist_parent,
                                      const int* __restrict__ hist_tok, int hist_stride, int W) {
     const int b = blockIdx.x, tid = threadIdx.x;
     if (tid >= W) return;
-    const int nb = st.nb[b], steps = count[b], s = b * W + tid;
+    const int nb = st.nb[b], s = b * W + tid;
     if (tid == 0) o.n_out[b] = nb;
-    int* h = o.hyp + (long long)s * o.Lmax;
-    if (tid < nb) {
-        const int len = st.len[s];
-        int pos = len - 1, cur = tid;
-        for (int k = steps - 1; k >= 0; --k) {
-            const long long e = ((long long)b * hist_stride + k) * W + cur;
-            const int tok = hist_tok[e];
-            if (tok >= 0) {
-                if (pos >= 0 && pos < o.Lmax) h[pos] = tok;
-                --pos;
-            }
-            cur = hist_parent[e];
-        }
-        for (int i = len; i < o.Lmax; ++i) h[i] = 0;
-        o.hyp_len[s] = len;
-        o.score[s] = st.sctc[s];
-        o.score_lm[s] = st.slm[s];
-        o.p_blk[s] = st.pb[s];
-        o.p_nblk[s] = st.pnb[s];
-    } else {
-        for (int i = 0; i < o.Lmax; ++i) h[i] = 0;
-        o.hyp_len[s] = 0;
-        o.score[s] = CL_LOGZERO;
-        o.score_lm[s] = 0.0;
-        o.p_blk[s] = CL_LOGZERO;
-        o.p_nblk[s] = CL_LOGZERO;
-    }
+    CsKept kept = {};
+    if (tid < nb) kept = CsKept{st.sctc[s], st.slm[s], st.pb[s], st.pnb[s], st.len[s]};
+    cs_write_row(o, s, hist_parent, hist_tok, (long long)b * hist_stride * W, W, count[b], tid < nb ? tid : -1, kept);
 }
 
 int launch_ctc_lm_schedule(const float* logp, const float* size_ratio, int B, int Tp, int V, int blank, int* frames, int* count,
@@ -301,8 +229,8 @@ int launch_ctc_lm_rows(const float* fresh, const float* prv, float* nxt, const i
 
 int launch_ctc_lm_frame(const CtcLmState& st, const CtcLmFrame& a, hipStream_t s) {
     if (a.B <= 0) return 0;
-    if (a.W < 1 || a.W > 32 || a.P < 0 || a.P > 32) {
-        cn_set_error("ctc_lm_frame: need 1 <= ctc_beam <= 32 and 0 <= ctc_pruning <= 32");
+    if (const char* bad = cs_check_limits(a.W, a.P, 0, 0)) {
+        cn_set_error(std::string("ctc_lm_frame: ") + bad);
         return -1;
     }
     // (a hypothesis has at most iter labels before this step: ids 0 .. iter + 1 are written)
@@ -310,14 +238,12 @@ int launch_ctc_lm_frame(const CtcLmState& st, const CtcLmFrame& a, hipStream_t s
         cn_set_error("ctc_lm_frame: iteration outside the history / row-id tables, or the blank outside the vocabulary");
         return -1;
     }
-    const int NC = a.W * (a.P + 1);
-    const size_t lds = (size_t)(3 * a.W + 5 * NC) * 8 + (size_t)(4 * a.W + 2 * NC) * 4 + 64;
-    hipLaunchKernelGGL(ctc_lm_frame_kernel, dim3(a.B), dim3(256), lds, s, st, a);
+    hipLaunchKernelGGL(ctc_lm_frame_kernel, dim3(a.B), dim3(256), cs_lds_bytes(a.W, a.P, true, 4, 2), s, st, a);
     CN_HIP_CHECK(hipGetLastError());
     return 0;
 }
 
-int launch_ctc_lm_finish(const CtcLmState& st, const CtcLmOut& o, const int* count, const unsigned char* hist_parent, const int* hist_tok,
+int launch_ctc_lm_finish(const CtcLmState& st, const CtcBeamOut& o, const int* count, const unsigned char* hist_parent, const int* hist_tok,
                          int hist_stride, int B, int W, hipStream_t s) {
     if (B < 1 || W < 1 || W > 32 || o.Lmax < 1) {
         cn_set_error("ctc_lm_finish: need B >= 1, 1 <= ctc_beam <= 32 and room for a label");

@@ -549,7 +549,7 @@ extern "C" int cn_ast_attach_ngram(cn_model* m, const cn_ngram_desc* desc, float
         m->ast_ng_scale = 0.f;
         return 0;
     }
-    const std::string bad = an_check_desc(*desc);
+    const std::string bad = ng_check_desc(*desc);
     if (!bad.empty()) {
         cn_set_error("cn_ast_attach_ngram: " + bad);
         return -1;

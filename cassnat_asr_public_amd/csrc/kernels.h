@@ -2,6 +2,7 @@
 // Every launcher is stream-ordered, allocates nothing and returns 0 / negative error code.
 #pragma once
 #include "common.h"
+#include "ctc_search.h"
 
 // model precisions of the kernels (the public CN_PRECISION_FP8 = 2 is a CN_PREC_BF16 engine with fp8 encoder products)
 enum { CN_PREC_F32 = 0, CN_PREC_BF16 = 1, CN_PREC_X3 = 3 };  // X3: split-bf16 elements (common.h split_t), 3 bf16 MFMAs per product
@@ -218,21 +219,7 @@ int launch_ctc_collapse(const int* best, const unsigned char* km, int B, int Tp,
                         int* maxlen, hipStream_t s);
 
 // ---- CTC prefix beam search + forced alignment (decode_type ctc_only / ctc_att)              (ctc_beam.hip)
-struct CtcBeamArgs {
-    const float* logp = nullptr;        // [B][Tp][V] CTC log-posteriors of ALL frames
-    const int* top_idx = nullptr;       // [B][Tp][P] the P best labels per frame, best first
-    const float* size_ratio = nullptr;  // [B]
-    int B = 0, Tp = 0, V = 0, P = 0, W = 0, blank = 0, Lmax = 0;
-    double lp = 0.0;                    // args.ctc_lp
-    unsigned char* hist_parent = nullptr;  // [B][Tp][W] scratch
-    int* hist_tok = nullptr;               // [B][Tp][W] scratch
-    int* hyp = nullptr;       // [B][W][Lmax]
-    int* hyp_len = nullptr;   // [B][W]
-    double* score = nullptr;  // [B][W] score_ctc
-    double* p_blk = nullptr;  // [B][W]
-    double* p_nblk = nullptr;
-    int* n_out = nullptr;     // [B] hypotheses kept
-};
+// (CtcBeamArgs / CtcBeamOut: ctc_search.h, the search every CTC beam variant shares)
 int launch_ctc_prefix_beam(const CtcBeamArgs& a, hipStream_t s);
 struct ViterbiArgs {
     const float* logp = nullptr;             // [B][Tp][V]
@@ -615,26 +602,12 @@ struct CtcLmState {
     int* stay;      // [S] 1: the hypothesis did not change (or the slot is unused): no LM step needed
     int* rowid[2];  // [S][Lt] LM cache row of every prefix position; iteration k reads [k & 1], the frame step writes [(k + 1) & 1]
 };
-struct CtcLmFrame {
-    const float* logp;    // [B][Tp][V] CTC log-posteriors
-    const int* top_idx;   // [B][Tp][P] pruned labels per frame, best first
+struct CtcLmFrame : CtcBeamArgs {  // (hist_parent / hist_tok: [B][hist_stride][W]; size_ratio and out are not used)
     const float* lmrow;   // [S][V] LM log-probability row of every kept hypothesis
     const int* frames;    // [B][Tp] processed frames
     const int* count;     // [B] their number
-    unsigned char* hist_parent;  // [B][hist_stride][W]
-    int* hist_tok;               // [B][hist_stride][W]
-    int B, Tp, V, P, W, blank, sos, iter, Lt, hist_stride;
-    double lp, lm_weight;
-};
-struct CtcLmOut {
-    int* hyp;       // [S][Lmax]
-    int* hyp_len;   // [S]
-    double* score;  // [S] score_ctc
-    double* score_lm;
-    double* p_blk;
-    double* p_nblk;
-    int* n_out;     // [B]
-    int Lmax;
+    int sos, iter, Lt, hist_stride;
+    double lm_weight;
 };
 int launch_ctc_lm_schedule(const float* logp, const float* size_ratio, int B, int Tp, int V, int blank, int* frames, int* count,
                            hipStream_t s);
@@ -642,6 +615,6 @@ int launch_ctc_lm_init(const CtcLmState& st, int B, int W, int Lt, int sos, hipS
 int launch_ctc_lm_rows(const float* fresh, const float* prv, float* nxt, const int* parent, const int* stay, const int* count, int iter,
                        int slots, int W, int V, hipStream_t s);
 int launch_ctc_lm_frame(const CtcLmState& st, const CtcLmFrame& a, hipStream_t s);
-int launch_ctc_lm_finish(const CtcLmState& st, const CtcLmOut& o, const int* count, const unsigned char* hist_parent, const int* hist_tok,
+int launch_ctc_lm_finish(const CtcLmState& st, const CtcBeamOut& o, const int* count, const unsigned char* hist_parent, const int* hist_tok,
                          int hist_stride, int B, int W, hipStream_t s);
 int launch_logsoftmax_temp(float* logits, int M, int V, int ldl, float temperature, int* arg, float* maxlp, hipStream_t s);

@@ -659,6 +659,50 @@ int stage_encode_ctc_rows(cn_model* m, const float* feats, int B, int T, int F, 
 }
 }  // namespace cn_host
 
+namespace {
+// The common opening of cn_ctc_beam / cn_ctc_beam_ngram / cn_ctc_beam_lm (`who` in the messages): the refusals they share, encoder
+// and CTC generator, the pruned labels of every frame, and the search's arguments filled.  capture_out: a capture run keeps the
+// log-posteriors the search ran on (cn_fetch "ctc_out").  with_hist: the back-pointers get [B][T'][beam] scratch (the LM variant
+// sizes its own once it knows its iteration count).
+int ctc_search_open(cn_model* m, const std::string& who, const float* feats_dev, const float* size_ratio_dev, int B, int T, int F,
+                    const cn_decode_opts* opts, int beam, int pruning, double length_penalty, const CtcBeamOut& out, bool capture_out,
+                    bool with_hist, CtcBeamArgs* a, hipStream_t s) {
+    // (a NAT model, or the autoregressive model with its CTC head: ArtTask decode_type 'ctc_only', src/tasks/art_task.py:252-253)
+    if (!opts || m->cfg.ast == 2 || !m->ctc_gen.W || !out.hyp || !out.hyp_len || !out.score || !out.p_blk || !out.p_nblk || !out.n_out) {
+        cn_set_error(who + ": needs a model with a CTC head, decode options and all output buffers");
+        return -1;
+    }
+    if (const char* bad = cs_check_limits(beam, pruning, 0, 0)) {
+        cn_set_error(who + ": " + bad);
+        return -1;
+    }
+    CN_HIP_CHECK(hipSetDevice(m->cfg.device));
+    CN_TRY(stage_encode_ctc_rows(m, feats_dev, B, T, F, opts, s));
+    const int Tp = m->Tp, M = B * Tp, V = m->cfg.vocab_size;
+    if (const char* bad = cs_check_limits(beam, pruning, Tp, out.Lmax)) {
+        cn_set_error(who + ": " + bad);
+        return -1;
+    }
+    if (capture_out && opts->capture) CN_TRY(capture(m, "ctc_out", m->logits, false, CN_DTYPE_F32, {B, Tp, V}, s));
+    void *top_idx = nullptr, *top_val = nullptr, *hpar = nullptr, *htok = nullptr;
+    const int P = pruning > 0 ? pruning : 1;  // (a zero-width pruning still needs a buffer; the kernel then sees P = 0)
+    CN_TRY(scratch_buf(m, "cb_top_idx", (size_t)M * P * 4, &top_idx));
+    CN_TRY(scratch_buf(m, "cb_top_val", (size_t)M * P * 4, &top_val));
+    if (with_hist) {
+        CN_TRY(scratch_buf(m, "cb_hist_par", (size_t)M * beam, &hpar));
+        CN_TRY(scratch_buf(m, "cb_hist_tok", (size_t)M * beam * 4, &htok));
+    }
+    if (pruning > 0) {
+        ProfScope ps(m, "ctc_topk", 0, (double)M * V * 4, s);
+        CN_TRY(launch_topk(m->logits, M, V, V, pruning, (int*)top_idx, (float*)top_val, s));
+    }
+    *a = ctc_beam_args(m->logits, (const int*)top_idx, size_ratio_dev, B, Tp, V, beam, pruning, opts->padding_idx, length_penalty, out);
+    a->hist_parent = (unsigned char*)hpar;
+    a->hist_tok = (int*)htok;
+    return 0;
+}
+}  // namespace
+
 // ctc_beam_decode (src/utils/beam_decode.py:8-93) without a language model: hyp_out_dev [B][beam][hyp_cap] labels (no sos),
 // hyp_len_dev / score_dev (score_ctc, float64) / p_blk_dev / p_nblk_dev [B][beam], nbeam_dev [B] hypotheses kept (best first).
 extern "C" int cn_ctc_beam(cn_model* m, const float* feats_dev, const float* size_ratio_dev, int32_t B, int32_t T, int32_t F,
@@ -666,117 +710,39 @@ extern "C" int cn_ctc_beam(cn_model* m, const float* feats_dev, const float* siz
                            int32_t hyp_cap, int32_t* hyp_len_dev, double* score_dev, double* p_blk_dev, double* p_nblk_dev,
                            int32_t* nbeam_dev, void* stream) {
     CN_TRY(check_call(m, B, T, F));
-    // (a NAT model, or the autoregressive model with its CTC head: ArtTask decode_type 'ctc_only', src/tasks/art_task.py:252-253)
-    if (!opts || m->cfg.ast == 2 || !m->ctc_gen.W || beam < 1 || beam > 32 || pruning < 0 || pruning > 32 || !hyp_out_dev || !hyp_len_dev ||
-        !score_dev || !p_blk_dev || !p_nblk_dev || !nbeam_dev) {
-        cn_set_error("cn_ctc_beam: needs a model with a CTC head, 1 <= ctc_beam <= 32, 0 <= ctc_pruning <= 32 and all output buffers");
-        return -1;
-    }
     hipStream_t s = (hipStream_t)stream;
-    CN_HIP_CHECK(hipSetDevice(m->cfg.device));
-    CN_TRY(stage_encode_ctc_rows(m, feats_dev, B, T, F, opts, s));
-    const int Tp = m->Tp, M = B * Tp, V = m->cfg.vocab_size;
-    if (hyp_cap < Tp + 1) {
-        cn_set_error("cn_ctc_beam: hyp_cap must be at least T' + 1");
-        return -1;
-    }
-    void *top_idx = nullptr, *top_val = nullptr, *hpar = nullptr, *htok = nullptr;
-    const int P = pruning > 0 ? pruning : 1;  // (a zero-width pruning still needs a buffer; the kernel then sees P = 0)
-    CN_TRY(scratch_buf(m, "cb_top_idx", (size_t)M * P * 4, &top_idx));
-    CN_TRY(scratch_buf(m, "cb_top_val", (size_t)M * P * 4, &top_val));
-    CN_TRY(scratch_buf(m, "cb_hist_par", (size_t)M * beam, &hpar));
-    CN_TRY(scratch_buf(m, "cb_hist_tok", (size_t)M * beam * 4, &htok));
-    if (pruning > 0) {
-        ProfScope ps(m, "ctc_topk", 0, (double)M * V * 4, s);
-        CN_TRY(launch_topk(m->logits, M, V, V, pruning, (int*)top_idx, (float*)top_val, s));
-    }
     CtcBeamArgs a;
-    a.logp = m->logits;
-    a.top_idx = (const int*)top_idx;
-    a.size_ratio = size_ratio_dev;
-    a.B = B;
-    a.Tp = Tp;
-    a.V = V;
-    a.P = pruning;
-    a.W = beam;
-    a.blank = opts->padding_idx;
-    a.Lmax = hyp_cap;
-    a.lp = length_penalty;
-    a.hist_parent = (unsigned char*)hpar;
-    a.hist_tok = (int*)htok;
-    a.hyp = hyp_out_dev;
-    a.hyp_len = hyp_len_dev;
-    a.score = score_dev;
-    a.p_blk = p_blk_dev;
-    a.p_nblk = p_nblk_dev;
-    a.n_out = nbeam_dev;
-    ProfScope ps(m, "ctc_prefix_beam", 0, (double)M * (pruning + 1) * 4, s);
+    CN_TRY(ctc_search_open(m, "cn_ctc_beam", feats_dev, size_ratio_dev, B, T, F, opts, beam, pruning, length_penalty,
+                           ctc_beam_out(hyp_out_dev, hyp_cap, hyp_len_dev, score_dev, nullptr, p_blk_dev, p_nblk_dev, nbeam_dev), false, true,
+                           &a, s));
+    ProfScope ps(m, "ctc_prefix_beam", 0, (double)B * a.Tp * (pruning + 1) * 4, s);
     return launch_ctc_prefix_beam(a, s);
 }
 
-// The same search with a word n-gram model fused (ctc_ngram.hip; not in the reference): encoder, CTC generator and pruning as
-// cn_ctc_beam, then one launch of the n-gram kernel.  Outputs as cn_ctc_beam_lm.
+// The same search with a word n-gram model fused (ctc_ngram_search.h; not in the reference): one launch of the n-gram instantiation
+// of the search kernel.  Outputs as cn_ctc_beam_lm.
 extern "C" int cn_ctc_beam_ngram(cn_model* m, const cn_ngram_desc* desc, const float* feats_dev, const float* size_ratio_dev, int32_t B,
                                  int32_t T, int32_t F, const cn_decode_opts* opts, int32_t beam, int32_t pruning, double length_penalty,
                                  double lm_scale, int32_t* hyp_out_dev, int32_t hyp_cap, int32_t* hyp_len_dev, double* score_dev,
                                  double* score_lm_dev, double* p_blk_dev, double* p_nblk_dev, int32_t* nbeam_dev, void* stream) {
     CN_TRY(check_call(m, B, T, F));
-    if (!opts || !desc || m->cfg.ast == 2 || !m->ctc_gen.W || !size_ratio_dev) {
-        cn_set_error("cn_ctc_beam_ngram: needs a model with a CTC head, a cn_ngram_desc and decode options");
+    // (looked at before anything is launched)
+    if (!desc || !size_ratio_dev || !score_lm_dev || !(lm_scale == lm_scale)) {
+        cn_set_error("cn_ctc_beam_ngram: needs a cn_ngram_desc, size ratios, lm_scale a number and all output buffers");
         return -1;
     }
-    // (the limits are looked at before anything is launched; launch_ctc_ngram_beam checks the rest of the desc before the search)
-    if (beam < 1 || beam > CG_MAX_BEAM || pruning < 0 || pruning > CG_MAX_PRUNE || desc->order < 1 || desc->order > NG_MAX_ORDER ||
-        !(lm_scale == lm_scale) || !hyp_out_dev || !hyp_len_dev || !score_dev || !score_lm_dev || !p_blk_dev || !p_nblk_dev || !nbeam_dev) {
-        cn_set_error("cn_ctc_beam_ngram: need 1 <= ctc_beam <= 32, 0 <= ctc_pruning <= 32, an order in 1 .. 8, lm_scale a number and all "
-                     "output buffers");
+    const std::string bad = ng_check_desc(*desc);
+    if (!bad.empty()) {
+        cn_set_error("cn_ctc_beam_ngram: " + bad);
         return -1;
     }
     hipStream_t s = (hipStream_t)stream;
-    CN_HIP_CHECK(hipSetDevice(m->cfg.device));
-    CN_TRY(stage_encode_ctc_rows(m, feats_dev, B, T, F, opts, s));
-    const int Tp = m->Tp, M = B * Tp, V = m->cfg.vocab_size;
-    if (hyp_cap < Tp + 1) {
-        cn_set_error("cn_ctc_beam_ngram: hyp_cap must be at least T' + 1");
-        return -1;
-    }
-    CtcNgramArgs a;
-    a.d = *desc;
-    a.size_ratio = size_ratio_dev;
-    a.B = B;
-    a.Tp = Tp;
-    a.V = V;
-    a.P = pruning;
-    a.W = beam;
-    a.blank = opts->padding_idx;
-    a.Lmax = hyp_cap;
-    a.lp = length_penalty;
-    a.lm_scale = lm_scale;
-    a.hyp = hyp_out_dev;
-    a.hyp_len = hyp_len_dev;
-    a.score = score_dev;
-    a.score_lm = score_lm_dev;
-    a.p_blk = p_blk_dev;
-    a.p_nblk = p_nblk_dev;
-    a.n_out = nbeam_dev;
-    // (a capture run keeps the log-posteriors the search ran on: cn_fetch "ctc_out", as after cn_ctc_beam_lm)
-    if (opts->capture) CN_TRY(capture(m, "ctc_out", m->logits, false, CN_DTYPE_F32, {B, Tp, V}, s));
-    void *top_idx = nullptr, *top_val = nullptr, *hpar = nullptr, *htok = nullptr;
-    const int P = pruning > 0 ? pruning : 1;
-    CN_TRY(scratch_buf(m, "cb_top_idx", (size_t)M * P * 4, &top_idx));
-    CN_TRY(scratch_buf(m, "cb_top_val", (size_t)M * P * 4, &top_val));
-    CN_TRY(scratch_buf(m, "cb_hist_par", (size_t)M * beam, &hpar));
-    CN_TRY(scratch_buf(m, "cb_hist_tok", (size_t)M * beam * 4, &htok));
-    if (pruning > 0) {
-        ProfScope ps(m, "ctc_topk", 0, (double)M * V * 4, s);
-        CN_TRY(launch_topk(m->logits, M, V, V, pruning, (int*)top_idx, (float*)top_val, s));
-    }
-    a.logp = m->logits;
-    a.top_idx = (const int*)top_idx;
-    a.hist_parent = (unsigned char*)hpar;
-    a.hist_tok = (int*)htok;
-    ProfScope ps(m, "ctc_ngram_beam", 0, (double)M * (pruning + 1) * 4, s);
-    return launch_ctc_ngram_beam(a, s);
+    CtcBeamArgs search;
+    CN_TRY(ctc_search_open(m, "cn_ctc_beam_ngram", feats_dev, size_ratio_dev, B, T, F, opts, beam, pruning, length_penalty,
+                           ctc_beam_out(hyp_out_dev, hyp_cap, hyp_len_dev, score_dev, score_lm_dev, p_blk_dev, p_nblk_dev, nbeam_dev), true,
+                           true, &search, s));
+    ProfScope ps(m, "ctc_ngram_beam", 0, (double)B * search.Tp * (pruning + 1) * 4, s);
+    return launch_ctc_ngram_beam(ctc_ngram_args(*desc, lm_scale, search), s);
 }
 
 // CassNAT.beam_decode with decode_type 'ctc_att' and sample_num 1 (src/models/cassnat.py:446-448, 391-414): the trigger mask
@@ -1139,9 +1105,8 @@ extern "C" int cn_ctc_beam_lm(cn_model* m, cn_model* lm, const float* feats_dev,
                               double* score_lm_dev, double* p_blk_dev, double* p_nblk_dev, int32_t* nbeam_dev, int32_t* iterations_host,
                               void* stream) {
     CN_TRY(check_call(m, B, T, F));
-    if (!opts || m->cfg.ast == 2 || !m->ctc_gen.W || beam < 1 || beam > 32 || pruning < 0 || pruning > 32 || !hyp_out_dev || !hyp_len_dev ||
-        !score_dev || !score_lm_dev || !p_blk_dev || !p_nblk_dev || !nbeam_dev) {
-        cn_set_error("cn_ctc_beam_lm: needs a model with a CTC head, 1 <= ctc_beam <= 32, 0 <= ctc_pruning <= 32 and all output buffers");
+    if (!opts || !score_lm_dev) {
+        cn_set_error("cn_ctc_beam_lm: needs decode options and all output buffers");
         return -1;
     }
     if (!lm || lm->cfg.ast != 2 || !lm->finalized) {
@@ -1162,23 +1127,11 @@ extern "C" int cn_ctc_beam_lm(cn_model* m, cn_model* lm, const float* feats_dev,
         return -1;
     }
     hipStream_t s = (hipStream_t)stream;
-    CN_HIP_CHECK(hipSetDevice(m->cfg.device));
-    CN_TRY(stage_encode_ctc_rows(m, feats_dev, B, T, F, opts, s));
-    const int Tp = m->Tp, M = B * Tp, W = beam, S = B * W;
-    if (hyp_cap < Tp + 1) {
-        cn_set_error("cn_ctc_beam_lm: hyp_cap must be at least T' + 1");
-        return -1;
-    }
-    // (a capture run keeps the log-posteriors the search ran on: cn_fetch "ctc_out", as after cn_decode_nast_forced)
-    if (opts->capture) CN_TRY(capture(m, "ctc_out", m->logits, false, CN_DTYPE_F32, {B, Tp, V}, s));
-    void *top_idx = nullptr, *top_val = nullptr, *p = nullptr;
-    const int P = pruning > 0 ? pruning : 1;
-    CN_TRY(scratch_buf(m, "cb_top_idx", (size_t)M * P * 4, &top_idx));
-    CN_TRY(scratch_buf(m, "cb_top_val", (size_t)M * P * 4, &top_val));
-    if (pruning > 0) {
-        ProfScope ps(m, "ctc_topk", 0, (double)M * V * 4, s);
-        CN_TRY(launch_topk(m->logits, M, V, V, pruning, (int*)top_idx, (float*)top_val, s));
-    }
+    const CtcBeamOut o = ctc_beam_out(hyp_out_dev, hyp_cap, hyp_len_dev, score_dev, score_lm_dev, p_blk_dev, p_nblk_dev, nbeam_dev);
+    CtcLmFrame a;
+    CN_TRY(ctc_search_open(m, "cn_ctc_beam_lm", feats_dev, size_ratio_dev, B, T, F, opts, beam, pruning, length_penalty, o, true, false, &a, s));
+    const int Tp = a.Tp, M = B * Tp, W = beam, S = B * W;
+    void* p = nullptr;
     int *frames = nullptr, *count = nullptr;
     CN_TRY(scratch_buf(m, "cl_frames", (size_t)M * 4, (void**)&frames));
     CN_TRY(scratch_buf(m, "cl_count", (size_t)B * 4, (void**)&count));
@@ -1229,6 +1182,8 @@ extern "C" int cn_ctc_beam_lm(cn_model* m, cn_model* lm, const float* feats_dev,
     CN_TRY(scratch_buf(m, "cl_hist_par", (size_t)B * hs * W, &hpar));
     CN_TRY(scratch_buf(m, "cl_hist_tok", (size_t)B * hs * W * 4, &htok));
     CN_TRY(launch_ctc_lm_init(st, B, W, Lt, sos, s));
+    a.frames = frames, a.count = count, a.hist_parent = (unsigned char*)hpar, a.hist_tok = (int*)htok;
+    a.sos = sos, a.Lt = Lt, a.hist_stride = hs, a.lm_weight = lm_weight;
     for (int k = 0; k < K; ++k) {
         CN_TRY(lm_step_run(lm, S, k, st.tok, st.rowid[k & 1], nullptr, Lt, s, st.pos, st.stay));
         CN_TRY(launch_logsoftmax_argmax(lm->ast_logits, S, V, V, lm->best, lm->ctc_maxlp, 1, s));
@@ -1236,38 +1191,11 @@ extern "C" int cn_ctc_beam_lm(cn_model* m, cn_model* lm, const float* feats_dev,
             ProfScope ps(m, "ctc_lm_rows", 0, 2.0 * S * V * 4, s);
             CN_TRY(launch_ctc_lm_rows(lm->ast_logits, lmrow[(k & 1) ^ 1], lmrow[k & 1], st.parent, st.stay, count, k, S, W, V, s));
         }
-        CtcLmFrame a;
-        a.logp = m->logits;
-        a.top_idx = (const int*)top_idx;
         a.lmrow = lmrow[k & 1];
-        a.frames = frames;
-        a.count = count;
-        a.hist_parent = (unsigned char*)hpar;
-        a.hist_tok = (int*)htok;
-        a.B = B;
-        a.Tp = Tp;
-        a.V = V;
-        a.P = pruning;
-        a.W = W;
-        a.blank = blank;
-        a.sos = sos;
         a.iter = k;
-        a.Lt = Lt;
-        a.hist_stride = hs;
-        a.lp = length_penalty;
-        a.lm_weight = lm_weight;
         ProfScope ps(m, "ctc_lm_frame", 0, (double)S * (pruning + 1) * 8, s);
         CN_TRY(launch_ctc_lm_frame(st, a, s));
     }
-    CtcLmOut o;
-    o.hyp = hyp_out_dev;
-    o.hyp_len = hyp_len_dev;
-    o.score = score_dev;
-    o.score_lm = score_lm_dev;
-    o.p_blk = p_blk_dev;
-    o.p_nblk = p_nblk_dev;
-    o.n_out = nbeam_dev;
-    o.Lmax = hyp_cap;
     return launch_ctc_lm_finish(st, o, count, (const unsigned char*)hpar, (const int*)htok, hs, B, W, s);
 }
 

@@ -134,20 +134,9 @@ static int ng_check(const char* who, const cn_ngram_desc* d, const void* tok, in
         cn_set_error(w + ": null argument");
         return -1;
     }
-    if (!d->word_keys || !d->word_ids || !d->gram_keys || !d->gram_prob || !d->gram_bo || !d->piece_hash || !d->piece_pow || !d->piece_starts) {
-        cn_set_error(w + ": null table in the desc");
-        return -1;
-    }
-    if (rows < 1 || stride < 1 || d->vocab < 0) {
-        cn_set_error(w + ": rows and stride must be positive, vocab not negative");
-        return -1;
-    }
-    if (d->order < 1 || d->order > NG_MAX_ORDER) {
-        cn_set_error(w + ": order " + std::to_string(d->order) + " is outside 1 .. 8");
-        return -1;
-    }
-    if (d->word_slots < 1 || (d->word_slots & (d->word_slots - 1)) || d->gram_slots < 1 || (d->gram_slots & (d->gram_slots - 1))) {
-        cn_set_error(w + ": the slot counts must be powers of two");
+    const std::string bad = rows < 1 || stride < 1 ? "rows and stride must be positive" : ng_check_desc(*d);
+    if (!bad.empty()) {
+        cn_set_error(w + ": " + bad);
         return -1;
     }
     return 0;

@@ -1,9 +1,11 @@
 // The scoring core of the ARPA n-gram model (include/cassnat_hip.h has the contract and the hashing): hash probes, the per-word score
-// and the piece monoid, written once as __host__ __device__ code.  ngram.hip (the ESA ranker) and ctc_ngram.hip (the CTC prefix beam
-// search with word n-gram fusion) are built from it; a plain C++ compiler reads it too (tools/ctc_ngram_check.cpp).
+// - serial, and as independent probes for a group of threads - and the piece monoid, written once as __host__ __device__ code; and
+// the validity check of a cn_ngram_desc.  ngram.hip (the ESA ranker), the CTC prefix beam search (ctc_ngram_search.h) and the AST beam
+// search (ast_ngram_search.h) are built from it; a plain C++ compiler reads it too (tools/*_check.cpp).
 #pragma once
 #include <cstdint>
 #include <limits>
+#include <string>
 
 #include "../../include/cassnat_hip.h"
 
@@ -117,4 +119,49 @@ NG_HD float ng_word_score(const cn_ngram_desc& d, const int32_t* h, int c, int32
         }
     }
     return s;
+}
+
+// ---- the same score from independent table probes ---------------------------------------------------------------------------------
+constexpr int NG_TASKS = 2 * NG_MAX_ORDER;  // probes of one word: NG_MAX_ORDER k-grams, NG_MAX_ORDER - 1 back-off weights, one idle
+struct NgProbe {
+    float prob, bo;
+    int found;
+};
+
+// The table probes of ng_word_score(d, h, c, w), one per task, independent of each other: task i < NG_MAX_ORDER is the (i + 1)-gram
+// that ends in w (needs i <= c), task NG_MAX_ORDER + j - 1 the back-off weight of the j-gram h[-j .. -1] (1 <= j <= c).
+NG_HD void ng_probe(const cn_ngram_desc& d, const int32_t* h, int c, int32_t w, int task, NgProbe* out) {
+    out->prob = 0.f, out->bo = 0.f, out->found = 0;
+    const bool gram = task < NG_MAX_ORDER;
+    const int n = gram ? task : task - NG_MAX_ORDER + 1;  // history ids folded
+    if (n > c || (!gram && n < 1) || n >= NG_MAX_ORDER) return;
+    uint64_t f = gram ? ng_fold(NG_SEED, w) : NG_SEED;
+    for (int i = 1; i <= n; ++i) f = ng_fold(f, h[-i]);
+    out->found = ng_gram(d, ng_gram_key(f, gram ? n + 1 : n, d.key_mask), &out->prob, &out->bo) ? 1 : 0;
+}
+
+// ng_word_score's float32 sum from the probes: the longest k-gram's probability, then the back-off weights for j = k .. c
+NG_HD float ng_probe_score(const NgProbe* pr, int c) {
+    int k = 0;
+    float s = NG_UNK_LOGPROB;
+    for (int i = NG_MAX_ORDER; i >= 1; --i) {
+        if (k == 0 && i <= c + 1 && pr[i - 1].found) k = i, s = pr[i - 1].prob;
+    }
+    if (k == 0) k = 1;
+    for (int j = 1; j < NG_MAX_ORDER; ++j) {
+        if (j <= c && j >= k && pr[NG_MAX_ORDER + j - 1].found) s += pr[NG_MAX_ORDER + j - 1].bo;
+    }
+    return s;
+}
+
+// ---- host only -------------------------------------------------------------------------------------------------------------------
+// "" when the desc can be scored with (pointers of the caller's side: not dereferenced here), else what is wrong
+inline std::string ng_check_desc(const cn_ngram_desc& d) {
+    if (!d.word_keys || !d.word_ids || !d.gram_keys || !d.gram_prob || !d.gram_bo || !d.piece_hash || !d.piece_pow || !d.piece_starts)
+        return "null table in the desc";
+    if (d.order < 1 || d.order > NG_MAX_ORDER) return "order " + std::to_string(d.order) + " is outside 1 .. 8";
+    if (d.word_slots < 1 || (d.word_slots & (d.word_slots - 1)) || d.gram_slots < 1 || (d.gram_slots & (d.gram_slots - 1)))
+        return "the slot counts must be powers of two";
+    if (d.vocab < 0) return "vocab must not be negative";
+    return "";
 }

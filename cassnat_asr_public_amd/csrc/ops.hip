@@ -652,26 +652,10 @@ extern "C" int cn_op_ctc_prefix_beam(const float* logp, const float* size_ratio,
     if (!sc.ok()) return -2;
     int rc = pruning > 0 ? launch_topk(logp, (int)M, V, V, pruning, top_idx, top_val, s) : 0;
     if (rc == 0) {
-        CtcBeamArgs a;
-        a.logp = logp;
-        a.top_idx = top_idx;
-        a.size_ratio = size_ratio;
-        a.B = B;
-        a.Tp = Tp;
-        a.V = V;
-        a.P = pruning;
-        a.W = beam;
-        a.blank = blank;
-        a.Lmax = hyp_cap;
-        a.lp = length_penalty;
+        CtcBeamArgs a = ctc_beam_args(logp, top_idx, size_ratio, B, Tp, V, beam, pruning, blank, length_penalty,
+                                      ctc_beam_out(hyp, hyp_cap, hyp_len, score, nullptr, p_blk, p_nblk, nbeam));
         a.hist_parent = hpar;
         a.hist_tok = htok;
-        a.hyp = hyp;
-        a.hyp_len = hyp_len;
-        a.score = score;
-        a.p_blk = p_blk;
-        a.p_nblk = p_nblk;
-        a.n_out = nbeam;
         rc = launch_ctc_prefix_beam(a, s);
     }
     return sc.finish(rc);
@@ -1219,25 +1203,10 @@ extern "C" int cn_op_ctc_lm_frame(double* pb, double* pnb, double* sctc, double*
     st.rowid[iter & 1] = const_cast<int32_t*>(rowid_cur);
     st.rowid[(iter & 1) ^ 1] = rowid_nxt;
     CtcLmFrame a;
-    a.logp = logp;
-    a.top_idx = top_idx;
-    a.lmrow = lmrow;
-    a.frames = frames;
-    a.count = count;
-    a.hist_parent = hist_parent;
-    a.hist_tok = hist_tok;
-    a.B = B;
-    a.Tp = Tp;
-    a.V = V;
-    a.P = P;
-    a.W = W;
-    a.blank = blank;
-    a.sos = sos;
-    a.iter = iter;
-    a.Lt = Lt;
-    a.hist_stride = hist_stride;
-    a.lp = lp;
-    a.lm_weight = lm_weight;
+    static_cast<CtcBeamArgs&>(a) = ctc_beam_args(logp, top_idx, nullptr, B, Tp, V, W, P, blank, lp, CtcBeamOut());
+    a.hist_parent = hist_parent, a.hist_tok = hist_tok;
+    a.lmrow = lmrow, a.frames = frames, a.count = count;
+    a.sos = sos, a.iter = iter, a.Lt = Lt, a.hist_stride = hist_stride, a.lm_weight = lm_weight;
     return launch_ctc_lm_frame(st, a, (hipStream_t)stream);
 }
 
@@ -1250,7 +1219,7 @@ extern "C" int cn_op_ctc_lm_rows(const float* fresh, const float* prv, float* nx
     return launch_ctc_lm_rows(fresh, prv, nxt, parent, stay, count, iter, slots, W, V, (hipStream_t)stream);
 }
 
-// ctc_ngram.hip's kernel alone on given log-posteriors and given pruned labels (cn_ctc_beam_ngram runs it behind the encoder)
+// the n-gram search kernel (ctc_beam.hip) alone on given log-posteriors and given pruned labels (cn_ctc_beam_ngram runs it behind the encoder)
 extern "C" int cn_op_ctc_ngram_beam(const cn_ngram_desc* desc, const float* logp, const int32_t* top_idx, const float* size_ratio, int32_t B,
                                     int32_t Tp, int32_t V, int32_t beam, int32_t pruning, double length_penalty, double lm_scale,
                                     int32_t blank, int32_t* hyp, int32_t hyp_cap, int32_t* hyp_len, double* score, double* score_lm,
@@ -1259,12 +1228,9 @@ extern "C" int cn_op_ctc_ngram_beam(const cn_ngram_desc* desc, const float* logp
         cn_set_error("cn_op_ctc_ngram_beam: null argument");
         return -1;
     }
-    CtcNgramArgs a;
-    a.d = *desc;
-    a.logp = logp, a.top_idx = top_idx, a.size_ratio = size_ratio;
-    a.B = B, a.Tp = Tp, a.V = V, a.P = pruning, a.W = beam, a.blank = blank, a.Lmax = hyp_cap;
-    a.lp = length_penalty, a.lm_scale = lm_scale;
-    a.hyp = hyp, a.hyp_len = hyp_len, a.score = score, a.score_lm = score_lm, a.p_blk = p_blk, a.p_nblk = p_nblk, a.n_out = nbeam;
+    CtcNgramArgs a = ctc_ngram_args(*desc, lm_scale,
+                                    ctc_beam_args(logp, top_idx, size_ratio, B, Tp, V, beam, pruning, blank, length_penalty,
+                                                  ctc_beam_out(hyp, hyp_cap, hyp_len, score, score_lm, p_blk, p_nblk, nbeam)));
     const std::string bad = cg_check(a, false);
     if (!bad.empty()) {
         cn_set_error("cn_op_ctc_ngram_beam: " + bad);

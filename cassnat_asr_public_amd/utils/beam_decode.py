@@ -12,7 +12,7 @@ reference's running sum over the pruned labels (it is not reset between the cand
 with an LM at hand is the LM-free search (the reference runs the LM and adds zeros).
 
 With ``lm_model`` a ``models.ngram.NgramLM`` (``rank_model: n-gram`` with an ARPA file) the search fuses the word n-gram model
-(``cn_ctc_beam_ngram``; csrc/ctc_ngram.hip; not in the reference): a candidate whose label begins a new word adds
+(``cn_ctc_beam_ngram``; csrc/ctc_ngram_search.h; not in the reference): a candidate whose label begins a new word adds
 ``ctc_lm_weight * ln(10)`` times the ARPA score of the word its parent had open, given the parent's word history; after the last
 frame every hypothesis adds its open word and ``</s>``.  The whole frame loop is one launch.  Any other ``lm_model`` object - a
 ``kenlm.Model`` included - is refused.

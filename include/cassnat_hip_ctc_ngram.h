@@ -8,7 +8,7 @@
 extern "C" {
 #endif
 
-/* ---- CTC prefix beam search with word n-gram fusion (ctc_ngram.hip; decode_type ctc_only / ctc_att with rank_model n-gram) ------
+/* ---- CTC prefix beam search with word n-gram fusion (ctc_beam.hip; decode_type ctc_only / ctc_att with rank_model n-gram) --------
  * cn_ctc_beam's search with score_lm from an ARPA model; not in the reference, whose only in-loop fusion is the TransformerLM's.  The
  * words of a hypothesis are the ones the ranker's gluing finds in its labels with drop_id = 2.  A kept hypothesis carries the carry
  * of its open word, its last 7 word ids (<s> in front) and its word count.  A stay candidate has its parent's score_lm; a candidate

@@ -1,4 +1,4 @@
-"""float64 restatement of the CTC prefix beam search with word n-gram fusion (csrc/ctc_ngram.hip; the semantics are in
+"""float64 restatement of the CTC prefix beam search with word n-gram fusion (csrc/ctc_ngram_search.h; the semantics are in
 include/cassnat_hip_ctc_ngram.h).  Nothing here comes from the code under test: the schedule is ctc_lm_model.schedule, the candidate arithmetic
 is ctc_lm_model.frame_step's (stay candidate, one candidate per pruned non-blank label, numpy's logaddexp, stable descending sort by
 (score_ctc + score_lm) + lp * len), the words are the ones ngram_model.text_of finds, the scores are ArpaModel's.

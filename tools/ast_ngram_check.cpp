@@ -118,20 +118,20 @@ void check_rows(const Model& m, std::mt19937& rng, const std::vector<uint8_t>& s
 }
 
 void check_refusals(const Model& m) {
-    CHECK(an_check_desc(m.d).empty(), "%s", an_check_desc(m.d).c_str());
+    CHECK(ng_check_desc(m.d).empty(), "%s", ng_check_desc(m.d).c_str());
     cn_ngram_desc d = m.d;
     d.order = 0;
-    CHECK(!an_check_desc(d).empty(), "order 0 accepted");
+    CHECK(!ng_check_desc(d).empty(), "order 0 accepted");
     d.order = NG_MAX_ORDER + 1;
-    CHECK(!an_check_desc(d).empty(), "order 9 accepted");
+    CHECK(!ng_check_desc(d).empty(), "order 9 accepted");
     d = m.d, d.gram_slots = 48;
-    CHECK(!an_check_desc(d).empty(), "48 slots accepted");
+    CHECK(!ng_check_desc(d).empty(), "48 slots accepted");
     d = m.d, d.word_slots = 0;
-    CHECK(!an_check_desc(d).empty(), "0 slots accepted");
+    CHECK(!ng_check_desc(d).empty(), "0 slots accepted");
     d = m.d, d.piece_pow = nullptr;
-    CHECK(!an_check_desc(d).empty(), "null table accepted");
+    CHECK(!ng_check_desc(d).empty(), "null table accepted");
     d = m.d, d.vocab = -1;
-    CHECK(!an_check_desc(d).empty(), "negative vocab accepted");
+    CHECK(!ng_check_desc(d).empty(), "negative vocab accepted");
 }
 
 }  // namespace

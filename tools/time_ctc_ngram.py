@@ -5,8 +5,8 @@ ctc_beam / ctc_pruning setting three legs, alternating, `--runs` runs each (a ru
 synchronisations, the mean of them), all in this process on this tree's library:
 
   ngram   cn_ctc_beam_ngram: encoder, CTC head, top-k, the n-gram search in one launch
-  nolm    cn_ctc_beam at the same settings: the LM-free search (sources this tree shares unchanged with its parent commit)
-  lm      cn_ctc_beam_lm with the TransformerLM `--lm` (lm_small) at the same settings (unchanged likewise)
+  nolm    cn_ctc_beam at the same settings: the LM-free search
+  lm      cn_ctc_beam_lm with the TransformerLM `--lm` (lm_small) at the same settings
 
 One JSON line per setting: the median and the range of each leg in seconds per batch, the ratios of the medians, and whether the
 ranges of `ngram` and `lm` overlap.  Appended to --out (profiles/ctc_ngram_time.jsonl).
