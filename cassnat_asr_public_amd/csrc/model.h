@@ -214,7 +214,7 @@ struct cn_model {
     // handle whose step runs beside this decoder's.  On an LM handle
     // (cfg.ast = 2) the ast_ck / ast_cv / ast_logits fields above hold ITS step cache [layer][pos][slot][d] and logits.
     cn_model* ast_lm = nullptr;
-    // word n-gram shallow fusion (cn_ast_attach_ngram): the desc by value (device tables the caller keeps alive), lm_weight * ln 10
+    // word n-gram shallow fusion (cn_ast_attach_ngram; cn_nat_attach_ngram on a CASS-NAT handle): the desc by value (device tables the caller keeps alive), lm_weight * ln 10
     // as float32, and the per-slot (a_word, a_eos) pairs of cn_decode_ast's step loop
     cn_ngram_desc ast_ng = {};
     bool ast_ng_on = false;

@@ -991,6 +991,10 @@ extern "C" int cn_nat_attach_lm(cn_model* m, cn_model* lm) {
         m->ast_lm = nullptr;
         return 0;
     }
+    if (m->ast_ng_on) {
+        cn_set_error("cn_nat_attach_lm: an n-gram model is attached (cn_nat_attach_ngram); it and a TransformerLM cannot be fused together");
+        return -1;
+    }
     if (lm->lib_tag != m->lib_tag) {
         cn_set_error("cn_nat_attach_lm: the two handles come from different libraries");
         return -1;

@@ -507,6 +507,20 @@ class Engine:
                                           int(length_penalty is not None), float(length_penalty or 0.0), int(bool(zero_past_len)),
                                           _ptr(hyp), hyp.shape[2], _ptr(hyp_len), _ptr(score), current_stream()), "cn_nat_lm_finish")
 
+    # ---- CASS-NAT + word n-gram model: the finish loop with n-gram shallow fusion (include/cassnat_hip_nat_ngram.h)
+    def nat_attach_ngram(self, desc, lm_scale=0.0):
+        """``desc`` a ``CnNgramDesc`` over tables on this engine's device (copied; the caller keeps the tables alive while attached) is
+        the model of this NAT engine's n-gram finish loop, ``lm_scale`` = float32(lm_weight * ln 10); None detaches."""
+        self._chk(self.L.cn_nat_attach_ngram(self.handle, C.byref(desc) if desc is not None else None, float(lm_scale)),
+                  "cn_nat_attach_ngram")
+
+    def nat_ngram_finish(self, opts, ymax, beam_width, eos, length_penalty, zero_past_len, hyp, hyp_len, score):
+        """The finish loop with the attached n-gram model after a pass that kept its rows (``opts.reserved[0] = 1``); the outputs are
+        ``nat_lm_finish``'s."""
+        self._chk(self.L.cn_nat_ngram_finish(self.handle, C.byref(opts), int(ymax), int(beam_width), int(eos),
+                                             int(length_penalty is not None), float(length_penalty or 0.0), int(bool(zero_past_len)),
+                                             _ptr(hyp), hyp.shape[2], _ptr(hyp_len), _ptr(score), current_stream()), "cn_nat_ngram_finish")
+
     def lm_step_begin(self, max_len, max_slots):
         self._chk(self.L.cn_lm_step_begin(self.handle, int(max_len), int(max_slots)), "cn_lm_step_begin")
 

@@ -371,10 +371,20 @@ class CassNAT(nn.Module):
         if getattr(args, "lm_weight", 0) > 0:
             # LM shallow fusion in the finish loop (src/models/cassnat.py:600-607): the loop runs on the device (_lm_finish)
             if lm_model is None:
-                raise ValueError("beam_decode: lm_weight > 0 needs lm_model (a models.lm.TransformerLM)")
-            if not hasattr(lm_model, "step_engine") or (getattr(args, "sample_num", 0) > 1 and getattr(args, "rank_model", "lm") != "lm"):
-                raise NotImplementedError("lm_weight > 0 fuses a models.lm.TransformerLM; with rank_model 'at_baseline' / 'n-gram' the "
-                                          "reference calls lm_model(ys, mask) on the ranker and fails")
+                raise ValueError("beam_decode: lm_weight > 0 needs lm_model (a models.lm.TransformerLM or a models.ngram.NgramLM)")
+            esa, rank = getattr(args, "sample_num", 0) > 1, getattr(args, "rank_model", "lm")
+            if self._is_ngram(lm_model):
+                # a word n-gram model (models.ngram.NgramLM): its class terms are fused on the device (_ngram_finish); with ESA it
+                # is also the ranker
+                if not lm_model.device_ok:
+                    raise NotImplementedError("lm_weight > 0 with an n-gram model: a piece of the vocabulary has a separator behind "
+                                              "its leading run, token rows cannot be scored")
+                if esa and rank != "n-gram":
+                    raise NotImplementedError("lm_weight > 0 with a models.ngram.NgramLM and sample_num > 1 needs rank_model 'n-gram'")
+            elif not hasattr(lm_model, "step_engine") or (esa and rank != "lm"):
+                raise NotImplementedError("lm_weight > 0 fuses a models.lm.TransformerLM or a models.ngram.NgramLM (an ARPA file); with "
+                                          "rank_model 'at_baseline' / 'n-gram' (kenlm) the reference calls lm_model(ys, mask) on the "
+                                          "ranker and fails")
             if not 1 <= int(args.beam_width) <= 16:
                 raise NotImplementedError("lm_weight > 0: beam_width must be in [1, 16]")
         if getattr(args, "sample_num", 0) > 1:
@@ -392,6 +402,12 @@ class CassNAT(nn.Module):
         if self._conf_dec and getattr(args, "use_unimask", False):
             raise NotImplementedError("use_unimask with the conformer decoder: the reference itself cannot run it "
                                       "(cassnat.py:486-488 indexes the (x, pos_embed) tuple)")
+
+    @staticmethod
+    def _is_ngram(lm_model):
+        from .ngram import NgramLM
+
+        return isinstance(lm_model, NgramLM)
 
     def _range_ok(self):
         """fp16 engine: the features of the call just finished were inside the range its half-precision operands hold."""
@@ -429,8 +445,8 @@ class CassNAT(nn.Module):
                     label_sizes=None):
         """Same contract as the reference's CassNAT.beam_decode (src/models/cassnat.py:420-637) for
         ``decode_type`` 'att_only' / 'ctc_att', ``sample_num`` > 1 (ESA) and ``use_trigger=False``; ``lm_weight > 0`` with a
-        ``models.lm.TransformerLM`` as ``lm_model`` runs the finish loop with LM shallow fusion on the device (``_lm_finish``).
-        Anything else raises.
+        ``models.lm.TransformerLM`` as ``lm_model`` runs the finish loop with LM shallow fusion on the device (``_lm_finish``), with
+        a ``models.ngram.NgramLM`` the finish loop with word n-gram fusion (``_ngram_finish``).  Anything else raises.
 
         ``x_mask`` is accepted for signature compatibility; like the reference's caller
         (src/tasks/cassnat_task.py:328) the padding mask is ``src[:,:,0] != padding_idx`` and is re-derived on
@@ -452,7 +468,8 @@ class CassNAT(nn.Module):
             eng = self._engine
             opts = hip.Engine.make_opts(args)
             opts.sos = sos
-            out = self._lm_finish(eng, opts, args, lm_model, src.shape[0], eng.shape("tok")[1], False)
+            finish = self._ngram_finish if self._is_ngram(lm_model) else self._lm_finish
+            out = finish(eng, opts, args, lm_model, src.shape[0], eng.shape("tok")[1], False, vocab)
             return out, args
         if args.beam_width > 1:
             out = self._host_beam(self._engine, args, sos)
@@ -576,10 +593,12 @@ class CassNAT(nn.Module):
             # selected alignments keeps their rows (as _esa_beam_finish), rows at or past a sample's own count read as zero (:536)
             sel = select.gather(0, pick.reshape(1, B, 1).expand(1, B, select.shape[2]).to(select.device)).contiguous()
             opts.reserved[0] = 1  # (beam_width stays 1: the rows are what the finish reads, not a top-k table)
+            opts.capture = int(bool(getattr(args, "hip_capture", False)))  # (this pass's rows are the ones a caller would fetch)
             one = [torch.zeros(1, B, stride, dtype=t, device=dev) for t in (torch.int32, torch.float32)]
             eng.esa_sample(sel, args.threshold, ratio, opts, one[0], one[1], torch.zeros(1, B, dtype=torch.int32, device=dev), force_U=force)
-            opts.reserved[0] = 0
-            return self._lm_finish(eng, opts, args, lm_model, B, ymax, True)
+            opts.reserved[0], opts.capture = 0, 0
+            finish = self._ngram_finish if self._is_ngram(lm_model) else self._lm_finish
+            return finish(eng, opts, args, lm_model, B, ymax, True, vocab)
         if bw > 1:
             return self._esa_beam_finish(eng, select, pick, args, ratio, opts, bw, force, ylen_sel, ymax, sos)
         out = []
@@ -626,7 +645,7 @@ class CassNAT(nn.Module):
             out.append(beams)
         return out
 
-    def _lm_finish(self, eng, opts, args, lm_model, B, ymax, zero_past_len):
+    def _lm_finish(self, eng, opts, args, lm_model, B, ymax, zero_past_len, vocab=None):
         """The finish loop with LM shallow fusion (src/models/cassnat.py:574-637, lm_weight > 0) on the device, after a pass of
         ``eng`` that kept its log-probability rows: per step the TransformerLM's incremental step on every beam slot, the fused
         row top-k and the beam update (``cn_nat_lm_finish``).  Returns the reference's records, ``'ys'`` grown with the hypothesis."""
@@ -645,6 +664,37 @@ class CassNAT(nn.Module):
             eng.nat_attach_lm(None)  # (the LM model may rebuild its engine before the next call)
         self._range_ok()
         if "fp16" in (self.hip_precision, lm_model.hip_precision):
+            hip.check_fp16_range(score_h, "beam_decode")
+        out = []
+        for b in range(B):
+            beams = []
+            for j in range(bw):
+                h = hyp_h[b, j, : len_h[b, j]].tolist()
+                beams.append({"ys": torch.tensor([h], dtype=torch.long), "score": float(score_h[b, j]), "hyp": h})
+            out.append(beams)
+        return out
+
+    def _ngram_finish(self, eng, opts, args, lm_model, B, ymax, zero_past_len, vocab):
+        """The finish loop with word n-gram shallow fusion (include/cassnat_hip_nat_ngram.h; not in the reference) on the device, after
+        a pass of ``eng`` that kept its log-probability rows: the class tables of every row, then all steps of every utterance
+        (``cn_nat_ngram_finish``, two launches).  ``lm_model`` is a models.ngram.NgramLM; its tables are attached with
+        float32(lm_weight * ln 10) for the call.  Returns ``_lm_finish``'s records."""
+        bw = int(args.beam_width)
+        dev = torch.device("cuda", getattr(self, "_device", torch.cuda.current_device()))
+        eos = vocab.word2index["eos"]
+        hyp = torch.empty(B, bw, ymax + 1, dtype=torch.int32, device=dev)
+        hyp_len = torch.empty(B, bw, dtype=torch.int32, device=dev)
+        score = torch.empty(B, bw, dtype=torch.float64, device=dev)
+        lm_model.cuda(dev)
+        eng.nat_attach_lm(None)
+        eng.nat_attach_ngram(lm_model.desc(dev), float(np.float32(float(args.lm_weight) * math.log(10.0))))
+        try:
+            eng.nat_ngram_finish(opts, ymax, bw, eos, args.length_penalty, zero_past_len, hyp, hyp_len, score)
+            hyp_h, len_h, score_h = hyp.cpu().numpy(), hyp_len.cpu().numpy(), score.cpu().numpy()
+        finally:
+            eng.nat_attach_ngram(None)
+        self._range_ok()
+        if self.hip_precision == "fp16":
             hip.check_fp16_range(score_h, "beam_decode")
         out = []
         for b in range(B):

@@ -145,12 +145,14 @@ class CassNATTask(BaseTask):
         (rank_model 'n-gram': an ARPA text in ``rnnlm`` is read by models.ngram.NgramLM and scored on the device; anything else
         goes to kenlm and is scored on the host as the reference does).  ``lm_weight > 0`` loads the same way (:86): the
         TransformerLM that the finish loop fuses (models.cassnat.CassNAT._lm_finish), which needs rank_model 'lm' - the reference
-        calls lm_model(ys, mask) on whatever it loaded and fails on the other two."""
+        calls lm_model(ys, mask) on whatever it loaded and fails on the other two - or, with rank_model 'n-gram' and an ARPA text,
+        the NgramLM whose class terms the finish loop fuses (CassNAT._ngram_finish; not in the reference)."""
         self.lm_model = None
         rank = getattr(args, "rank_model", "lm")
-        if args.lm_weight > 0 and rank != "lm":
-            raise NotImplementedError("lm_weight > 0 needs rank_model 'lm': the finish loop fuses a TransformerLM (the reference "
-                                      "fails on rank_model '%s' there)" % rank)
+        if args.lm_weight > 0 and rank != "lm" and not (rank == "n-gram" and args.rnnlm and _is_arpa(args.rnnlm)):
+            raise NotImplementedError("lm_weight > 0 needs rank_model 'lm' (the finish loop fuses a TransformerLM; the reference "
+                                      "fails on rank_model '%s' there) or rank_model 'n-gram' with an ARPA text in --rnnlm, whose "
+                                      "word n-gram model the finish loop fuses on the device" % rank)
         if args.lm_weight > 0 or getattr(args, "ctc_lm_weight", 0) > 0:
             if rank == "n-gram":
                 if _is_arpa(args.rnnlm):  # an ARPA text: the package's own model, scored on the device (models.ngram)
