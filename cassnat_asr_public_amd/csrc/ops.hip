@@ -1392,66 +1392,98 @@ extern "C" int cn_op_x3_chain(float* x_dev, const void* ctx_dev, const float* wo
     return sc.finish(launch_ffn_x3(a, (hipStream_t)stream));
 }
 
-static int op_chain(float* x_dev, const void* ctx_dev, int32_t ldctx, const float* wo_host, const float* bo_host,
-                    const float* ln1_a_host, const float* ln1_b_host, const float* w1_host, const float* b1_host,
-                    const float* w2_host, const float* b2_host, const float* nln_a_host, const float* nln_b_host,
-                    const float* wt_host, const float* bt_host, void* out_dev, int32_t ldo, int32_t M, int32_t dff,
-                    int32_t tail_n, float eps, int32_t x_mode, const int32_t* m_dev, void* stream) {
-    if (dff < 0 || dff % 32 != 0 || dff > 2048 || tail_n < 0 || tail_n % 32 != 0 || tail_n > 1536) {
-        cn_set_error("cn_op_chain: d_ff and the tail width must be multiples of 32 (<= 2048 / <= 1536)");
+// Every ChainArgs field from the descriptor.  `who`: the entry's name for messages.  Everything the launcher would refuse is refused
+// here, before the weights are packed and anything touches the device.
+static int op_chain_desc(const char* who, const cn_chain_desc* d, void* stream) {
+    auto refuse = [&](const char* why) {
+        cn_set_error((std::string(who) + ": " + why).c_str());
         return -1;
+    };
+    if (!d) return refuse("null descriptor");
+    const int32_t dff = d->dff, tail_n = d->tail_n;
+    if (dff < 0 || dff % 128 != 0 || dff > 2048 || tail_n < 0 || tail_n % 256 != 0 || tail_n > 1536)
+        return refuse("d_ff must be a multiple of 128 (<= 2048) and the tail width a multiple of 256 (<= 1536)");
+    if (!d->x) return refuse("null x");
+    if (d->ctx && (!d->wo || !d->bo)) return refuse("ctx needs wo and bo");
+    if (dff > 0 && (!d->ln1_a || !d->ln1_b || !d->w1 || !d->b1 || !d->w2 || !d->b2))
+        return refuse("d_ff > 0 needs ln1_a, ln1_b, w1, b1, w2 and b2");
+    const bool has_next = d->nln_a != nullptr;
+    if (has_next && !d->nln_b) return refuse("nln_a needs nln_b");
+    if (tail_n > 0 && (!has_next || !d->out || !d->wt || !d->bt)) return refuse("a tail needs nln_a, nln_b, wt, bt and out");
+    if (has_next && !d->out && !d->ln_out) return refuse("LNn(x) needs out or ln_out");
+    if (d->ln_out && !has_next) return refuse("ln_out needs nln_a and nln_b");
+    const int f8 = d->f8 != 0;
+    if (f8 && (dff <= 0 || dff % 256 != 0 || d->swish))
+        return refuse("the e4m3 feed-forward form (x_mode bit 32) needs d_ff % 256 == 0 and the ReLU activation");
+    if (d->rows_dev && d->swish) return refuse("a device-side row count exists for the ReLU forms (the transformer decoder side)");
+    if (d->ctx && d->ctx_blocked && d->ldctx != 256) return refuse("a blocked ctx has 256 columns (ldctx == 256)");
+    if (d->ctx && !d->ctx_blocked && (d->ldctx < 256 || d->ldctx % 8 != 0))
+        return refuse("row-major ctx rows hold 256 columns and are 16-byte aligned (ldctx >= 256, % 8 == 0)");
+    // where LNn(x) goes and with which row stride (launch_chain): ln_out, else `out` of a launch without tail
+    const bool ln_to_out = has_next && !d->ln_out && tail_n == 0;
+    const int32_t ld_ln = d->ln_out ? d->ld_ln : d->ldo;
+    if (has_next && (d->ln_out || ln_to_out)) {
+        if (d->ln_blocked && ld_ln != 256)
+            return refuse("a blocked LNn(x) has 256 columns (ld_ln == 256, or ldo == 256 where out takes it)");
+        if (!d->ln_blocked && (ld_ln < 256 || ld_ln % 4 != 0))
+            return refuse("row-major LNn(x) rows hold 256 columns and are 8-byte aligned (ld >= 256, % 4 == 0)");
     }
+    if (tail_n > 0) {
+        if (d->out_blocked && (d->ldo < tail_n || d->ldo % 32 != 0))
+            return refuse("a blocked tail output needs ldo % 32 == 0 and ldo >= tail_n");
+        if (!d->out_blocked && (d->ldo < tail_n || d->ldo % 8 != 0))
+            return refuse("row-major tail rows hold tail_n columns and are 16-byte aligned (ldo >= tail_n, % 8 == 0)");
+    }
+    if (d->M < 0) return refuse("M < 0");
     ChainWeights w;
-    w.wo = ctx_dev ? wo_host : nullptr;
-    w.bo = bo_host;
-    w.ln1_a = ln1_a_host;
-    w.ln1_b = ln1_b_host;
-    w.w1 = w1_host;
-    w.b1 = b1_host;
-    w.w2 = w2_host;
-    w.b2 = b2_host;
-    w.nln_a = nln_a_host;
-    w.nln_b = nln_b_host;
-    w.wt = wt_host;
-    w.bt = bt_host;
+    w.wo = d->ctx ? d->wo : nullptr;
+    w.bo = d->bo;
+    w.ln1_a = d->ln1_a;
+    w.ln1_b = d->ln1_b;
+    w.w1 = d->w1;
+    w.b1 = d->b1;
+    w.w2 = d->w2;
+    w.b2 = d->b2;
+    w.nln_a = d->nln_a;
+    w.nln_b = d->nln_b;
+    w.wt = d->wt;
+    w.bt = d->bt;
     w.dff = dff;
     w.tail_n = tail_n;
-    const int f8 = (x_mode & 32) != 0;
-    if (f8 && (dff <= 0 || dff % 256 != 0 || (x_mode & 8))) {
-        cn_set_error("cn_op_chain: the e4m3 feed-forward form (x_mode bit 32) needs d_ff % 256 == 0 and the ReLU activation");
-        return -1;
-    }
-    const size_t units = chain_stream_units(ctx_dev != nullptr, dff, tail_n, f8);
+    const size_t units = chain_stream_units(d->ctx != nullptr, dff, tail_n, f8);
     std::vector<uint16_t> hs((units + 7) * (CHAIN_UNIT_BYTES / 2));  // (seven spare units: the kernel's dummy refills read them)
     std::vector<float> ht(CHAIN_TAB_FLOATS + 4);  // the table, then the four scale bytes of the e4m3 form
     int hq[4] = {127, 127, 127, 127};
     pack_chain(w, hs.data(), ht.data(), f8 ? hq : nullptr);
     std::memcpy(&ht[CHAIN_TAB_FLOATS], hq, 16);
-    Scratch sc("cn_op_chain", (hipStream_t)stream);
+    Scratch sc(who, (hipStream_t)stream);
     void* ds = sc.upload(hs.data(), hs.size() * 2);
     const float* dt = (const float*)sc.upload(ht.data(), ht.size() * 4);
     if (!sc.ok()) return -2;
     ChainArgs a;
-    a.x = x_dev;
-    a.ctx = ctx_dev;
-    a.ldctx = ldctx;
+    a.x = d->x;
+    a.ctx = d->ctx;
+    a.ldctx = d->ldctx;
+    a.ctx_blocked = d->ctx_blocked != 0;
     a.wstream = ds;
     a.tab = dt;
-    a.out = out_dev;
-    a.ldo = ldo;
-    a.M = M;
-    a.m_dev = m_dev;
+    a.out = d->out;
+    a.ldo = d->ldo;
+    a.ln_out = d->ln_out;
+    a.ld_ln = d->ld_ln;
+    a.M = d->M;
+    a.m_dev = d->rows_dev;
     a.d = 256;
     a.dff = dff;
     a.tail_n = tail_n;
-    a.has_next = nln_a_host != nullptr;
-    a.eps = eps;
-    a.x_in_blocked = (x_mode & 1) != 0;
-    a.x_out_blocked = (x_mode & 2) != 0;
-    a.store_x = (x_mode & 4) == 0;
-    a.swish = (x_mode & 8) != 0;
-    a.out_blocked = (x_mode & 16) != 0;
-    a.ln_blocked = (x_mode & 64) != 0;
+    a.has_next = has_next;
+    a.eps = d->eps;
+    a.x_in_blocked = d->x_in_blocked != 0;
+    a.x_out_blocked = d->x_out_blocked != 0;
+    a.store_x = d->store_x != 0;
+    a.swish = d->swish != 0;
+    a.out_blocked = d->out_blocked != 0;
+    a.ln_blocked = d->ln_blocked != 0;
     a.f8 = f8;
     a.f8_q = f8 ? reinterpret_cast<const int*>(dt + CHAIN_TAB_FLOATS) : nullptr;
     int rc = launch_chain(a, (hipStream_t)stream);
@@ -1473,13 +1505,54 @@ static int op_chain(float* x_dev, const void* ctx_dev, int32_t ldctx, const floa
     return rc;
 }
 
+// cn_op_chain / cn_op_chain_rows: the descriptor with the x_mode bits spelled out
+static cn_chain_desc chain_desc_of(float* x_dev, const void* ctx_dev, int32_t ldctx, const float* wo_host, const float* bo_host,
+                                   const float* ln1_a_host, const float* ln1_b_host, const float* w1_host, const float* b1_host,
+                                   const float* w2_host, const float* b2_host, const float* nln_a_host, const float* nln_b_host,
+                                   const float* wt_host, const float* bt_host, void* out_dev, int32_t ldo, int32_t M, int32_t dff,
+                                   int32_t tail_n, float eps, int32_t x_mode, const int32_t* rows_dev) {
+    cn_chain_desc d = {};
+    d.x = x_dev;
+    d.ctx = ctx_dev;
+    d.ldctx = ldctx;
+    d.wo = wo_host;
+    d.bo = bo_host;
+    d.ln1_a = ln1_a_host;
+    d.ln1_b = ln1_b_host;
+    d.w1 = w1_host;
+    d.b1 = b1_host;
+    d.w2 = w2_host;
+    d.b2 = b2_host;
+    d.nln_a = nln_a_host;
+    d.nln_b = nln_b_host;
+    d.wt = wt_host;
+    d.bt = bt_host;
+    d.out = out_dev;
+    d.ldo = ldo;
+    d.M = M;
+    d.dff = dff;
+    d.tail_n = tail_n;
+    d.eps = eps;
+    d.x_in_blocked = (x_mode & 1) != 0;
+    d.x_out_blocked = (x_mode & 2) != 0;
+    d.store_x = (x_mode & 4) == 0;
+    d.swish = (x_mode & 8) != 0;
+    d.out_blocked = (x_mode & 16) != 0;
+    d.f8 = (x_mode & 32) != 0;
+    d.ln_blocked = (x_mode & 64) != 0;
+    d.rows_dev = rows_dev;
+    return d;
+}
+
 extern "C" int cn_op_chain(float* x_dev, const void* ctx_dev, int32_t ldctx, const float* wo_host, const float* bo_host,
                            const float* ln1_a_host, const float* ln1_b_host, const float* w1_host, const float* b1_host,
                            const float* w2_host, const float* b2_host, const float* nln_a_host, const float* nln_b_host,
                            const float* wt_host, const float* bt_host, void* out_dev, int32_t ldo, int32_t M, int32_t dff,
                            int32_t tail_n, float eps, int32_t x_mode, void* stream) {
-    return op_chain(x_dev, ctx_dev, ldctx, wo_host, bo_host, ln1_a_host, ln1_b_host, w1_host, b1_host, w2_host, b2_host, nln_a_host,
-                    nln_b_host, wt_host, bt_host, out_dev, ldo, M, dff, tail_n, eps, x_mode, nullptr, stream);
+    const cn_chain_desc d = chain_desc_of(x_dev, ctx_dev, ldctx, wo_host, bo_host, ln1_a_host, ln1_b_host, w1_host, b1_host, w2_host,
+                                          b2_host, nln_a_host, nln_b_host, wt_host, bt_host, out_dev, ldo, M, dff, tail_n, eps, x_mode,
+                                          nullptr);
+    return op_chain_desc("cn_op_chain", &d, stream);
 }
 
 extern "C" int cn_op_chain_rows(float* x_dev, const void* ctx_dev, int32_t ldctx, const float* wo_host, const float* bo_host,
@@ -1491,9 +1564,14 @@ extern "C" int cn_op_chain_rows(float* x_dev, const void* ctx_dev, int32_t ldctx
         cn_set_error("cn_op_chain_rows: null row count");
         return -1;
     }
-    return op_chain(x_dev, ctx_dev, ldctx, wo_host, bo_host, ln1_a_host, ln1_b_host, w1_host, b1_host, w2_host, b2_host, nln_a_host,
-                    nln_b_host, wt_host, bt_host, out_dev, ldo, M, dff, tail_n, eps, x_mode, rows_dev, stream);
+    const cn_chain_desc d = chain_desc_of(x_dev, ctx_dev, ldctx, wo_host, bo_host, ln1_a_host, ln1_b_host, w1_host, b1_host, w2_host,
+                                          b2_host, nln_a_host, nln_b_host, wt_host, bt_host, out_dev, ldo, M, dff, tail_n, eps, x_mode,
+                                          rows_dev);
+    return op_chain_desc("cn_op_chain_rows", &d, stream);
 }
+
+extern "C" int cn_op_chain_desc(const cn_chain_desc* d, void* stream) { return op_chain_desc("cn_op_chain_desc", d, stream); }
+extern "C" int32_t cn_chain_desc_size(void) { return (int32_t)sizeof(cn_chain_desc); }
 
 static int op_genmax_impl(const void* h_dev, const float* w_host, const float* b_host, int32_t M, int32_t V,
                           int32_t* arg_dev, float* maxlp_dev, const int32_t* tgt_dev, float* tgt_lp_dev, int32_t U, int32_t ld,

@@ -348,7 +348,8 @@ int cn_profile_end(cn_model* m, char* json_out, int64_t cap);
  * Replaces linears[3] + SublayerConnection + PositionwiseFeedForward + LayerNorm + linears[0..2]
  * (src/models/modules/attention.py:44-66, utils.py:23-32, positionff.py:15-16, norm.py:15-18).  Weights are host fp32
  * in nn.Linear layout and are packed on every call: a test entry point, the model keeps its packed copies.
- * x_mode bits: 1 = x_dev is read in the kernel's blocked layout, 2 = written in it, 4 = not written back, 8 = the feed-forward
+ * x_mode bits (each a field of cn_chain_desc below, which states every layout in one place): 1 = x_dev is read in the kernel's
+ * blocked layout, 2 = written in it, 4 = not written back, 8 = the feed-forward
  * activation is Swish (x * sigmoid(x), the conformer's macaron halves) instead of ReLU, 16 = the tail projection out_dev is
  * written as a blocked bf16 matrix of ldo columns (ceil(M / 32) * 32 rows; 32 x 32 tiles of 2 KiB, each [16-column half][lane =
  * 32 * (bit 3 of the column) + row % 32][8 bf16]: what the attention kernel reads as `blocked` Q / K / V).  Blocked x: 32-row
@@ -371,6 +372,60 @@ int cn_op_chain_rows(float* x_dev, const void* ctx_dev, int32_t ldctx, const flo
                      const float* w2_host, const float* b2_host, const float* nln_a_host, const float* nln_b_host,
                      const float* wt_host, const float* bt_host, void* out_dev, int32_t ldo, int32_t M, int32_t dff,
                      int32_t tail_n, float eps, int32_t x_mode, const int32_t* rows_dev, void* stream);
+/* Every option of the row-chain kernel (the internal ChainArgs), the one place that states its fields and layouts; cn_op_chain
+ * and cn_op_chain_rows are this entry with the x_mode bits spelled out.  One launch, on the library's 16-bit operand type (bf16,
+ * or IEEE half in libcassnat_hip_f16):
+ *   x += Wo.ctx + bo                      if ctx != NULL
+ *   x += W2.act(W1.LN1(x) + b1) + b2      if dff > 0 (act: ReLU, or Swish = v * sigmoid(v) with `swish`)
+ *   y = LNn(x)                            if nln_a != NULL; LayerNorm of the reference: unbiased std, eps added to the std
+ *   out = Wt.y + bt (tail_n > 0) or out = y (tail_n == 0); ln_out = y as well where it is given.
+ * Weights (wo [256][256], w1 [dff][256], w2 [256][dff], wt [tail_n][256], the biases and LayerNorm vectors) are HOST fp32 in
+ * nn.Linear layout, packed on every call: a test entry.  dff % 128 == 0 <= 2048, tail_n % 256 == 0 <= 1536.  M rows; with
+ * rows_dev (a device word, ReLU forms only) M sizes the grid and the buffers, *rows_dev <= M rows exist and workgroups past them
+ * write nothing.  store_x == 0: x is read and not written back.  f8: the two feed-forward products on e4m3fn operands as x_mode
+ * bit 32 of cn_op_chain describes (dff % 256 == 0, ReLU only).
+ * Layouts (device buffers; a blocked buffer holds ceil(M / 32) * 32 rows, and the rows of the last 32-row block past M may be
+ * written with values of no meaning):
+ *   x       row-major fp32 [M][256]; x_in_blocked / x_out_blocked: read / written as 32-row blocks of [32 pieces i][64 lanes]
+ *           [4 floats], lane = row % 32 + 32 h holding channels 32 (i / 4) + 8 (i % 4) + 4 h + (0..3)
+ *   ctx     row-major [M][ldctx] of 16-bit values (the first 256 columns are read); ctx_blocked (ldctx == 256): the attention
+ *           kernel's o_blocked output - per 32-row block [16 k-steps][lane = row % 32 + 32 h][8 values], value j of (k-step ks, h)
+ *           being channel 16 ks + 8 h + j
+ *   out     row-major [M][ldo] of 16-bit values; out_blocked (tail_n > 0, ldo % 32 == 0): a blocked matrix of ldo columns -
+ *           32 x 32 tiles of 2 KiB, each [16-column half][lane = 32 * (bit 3 of the column) + row % 32][8 values], what the
+ *           attention kernel reads as `blocked` Q / K / V
+ *   ln_out  row-major [M][ld_ln] of 16-bit values, written IN ADDITION to a tail (the last encoder layer: enc_h beside the
+ *           decoder side's K|V); NULL: none.  ln_blocked (256 columns: ld_ln == 256, or ldo == 256 where `out` takes y): y goes
+ *           out - to ln_out, or to `out` of a launch without tail - as the kernel's own B operands: per 32-row block
+ *           [16 k-steps][lane = row % 32 + 32 h][8 values], value j of (k-step ks, h) being channel
+ *           32 (ks / 2) + 16 (ks % 2) + 8 (j / 4) + 4 h + j % 4 - what cn_op_attention_proj reads as y_dev.
+ * cn_chain_desc_size() is sizeof(cn_chain_desc). */
+typedef struct cn_chain_desc {
+    float* x;
+    const void* ctx;
+    int32_t ldctx, ctx_blocked;
+    const float* wo;
+    const float* bo;
+    const float* ln1_a;
+    const float* ln1_b;
+    const float* w1;
+    const float* b1;
+    const float* w2;
+    const float* b2;
+    const float* nln_a;
+    const float* nln_b;
+    const float* wt;
+    const float* bt;
+    void* out;
+    void* ln_out;
+    int32_t ldo, ld_ln;
+    int32_t M, dff, tail_n;
+    float eps;
+    int32_t ln_blocked, out_blocked, store_x, x_in_blocked, x_out_blocked, swish, f8;
+    const int32_t* rows_dev;
+} cn_chain_desc;
+int cn_op_chain_desc(const cn_chain_desc* d, void* stream);
+int32_t cn_chain_desc_size(void);
 
 /* ---- front-end: waveform -> log-mel filterbank features (+ global CMVN), padded batch out ----------------------
  * What the reference leaves to Kaldi's compute-fbank-feats (egs/librispeech/conf/fbank.conf:1-6: hamming window, 16 kHz,
