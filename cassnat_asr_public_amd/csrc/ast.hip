@@ -7,7 +7,7 @@
 // list at step j:  cache[l][j][s][d].  Every (j, s) cell is written exactly once (at step j), so a hypothesis never copies
 // its parent's cache: it carries an ancestor table anc[j] = slot that wrote position j of its prefix, and the attention
 // kernel gathers through it.  HBM-bound gather work - no MFMA (one query row per hypothesis).
-#include "kernels.h"
+#include "beam_core.h"
 
 // x[h][:] = lut[tok[h]][:] * sqrt(d) + pe[pos][:]        (TextEmbedding + PositionalEncoding, embedding.py:71-78, 29-31)
 __global__ void ast_embed_kernel(const int* __restrict__ tok, const float* __restrict__ lut, const float* __restrict__ pe_row,
@@ -22,32 +22,6 @@ int launch_ast_embed(const int* tok, const float* lut, const float* pe_row, floa
                      hipStream_t s) {
     if (n <= 0) return 0;
     hipLaunchKernelGGL(ast_embed_kernel, dim3(cn_ceil_div(n * d, 256)), dim3(256), 0, s, tok, lut, pe_row, x, n, d, scale);
-    CN_HIP_CHECK(hipGetLastError());
-    return 0;
-}
-
-// append the new position's K|V (columns d..3d of the fused projection) to the cache cell (pos, slot = row)
-template <typename T>
-__global__ void ast_kv_append_kernel(const T* __restrict__ qkv, T* __restrict__ ck, T* __restrict__ cv, int n, int d,
-                                     int slots, int pos) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;  // 16-byte chunks
-    const int per = d * (int)sizeof(T) / 16;
-    if (i >= n * per) return;
-    const int h = i / per, c = i - h * per;
-    const uint4* src = reinterpret_cast<const uint4*>(qkv + (long long)h * 3 * d);
-    const long long cell = ((long long)pos * slots + h) * per + c;
-    reinterpret_cast<uint4*>(ck)[cell] = src[per + c];
-    reinterpret_cast<uint4*>(cv)[cell] = src[2 * per + c];
-}
-
-int launch_ast_kv_append(int prec, const void* qkv, void* ck, void* cv, int n, int d, int slots, int pos, hipStream_t s) {
-    if (n <= 0) return 0;
-    const int per = d * (int)cn_elem_size(prec) / 16;
-    const dim3 grid(cn_ceil_div(n * per, 256));
-    if (prec == CN_PREC_F32 || prec == CN_PREC_X3)  // (split-bf16: d columns are d * 4 contiguous bytes of a row, whole 128-byte groups)
-        hipLaunchKernelGGL(ast_kv_append_kernel<float>, grid, dim3(256), 0, s, (const float*)qkv, (float*)ck, (float*)cv, n, d, slots, pos);
-    else
-        hipLaunchKernelGGL(ast_kv_append_kernel<bf16>, grid, dim3(256), 0, s, (const bf16*)qkv, (bf16*)ck, (bf16*)cv, n, d, slots, pos);
     CN_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -394,13 +368,8 @@ __global__ void ast_beam_init_kernel(AstBeamState st, int cur, int B, int bw, in
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= B * bw) return;
     const int b = s / bw, j = s - b * bw;
-    for (int t = 0; t < L; ++t) {
-        st.tok[cur][(long long)s * L + t] = t == 0 ? sos : pad;
-        st.anc[cur][(long long)s * L + t] = s;
-        st.keyok[cur][(long long)s * L + t] = (t == 0 && sos != pad) ? 1 : 0;
-    }
+    beam_init_row(st, cur, s, L, sos, pad);
     st.len[cur][s] = 1;
-    st.score[cur][s] = 0.0;
     st.valid[cur][s] = j == 0;
     st.ctc_ref[cur][s] = -1 - b;
     st.ctc_prev[cur][s] = 0.f;
@@ -438,7 +407,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void ast_beam_update_kernel(AstBeamSt
         const int s = b * bw + fin_idx[tid];
         const double sc = st.score[cur][s];
         cscore[tid] = sc;
-        ckey[tid] = q.use_lp ? sc + cn_mul_rn((double)(st.len[cur][s] - 1), q.lp) : sc;
+        ckey[tid] = beam_key(sc, st.len[cur][s] - 1, q.lp, q.use_lp);
         cpar[tid] = fin_idx[tid];
         ccand[tid] = -1;
     }
@@ -464,7 +433,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void ast_beam_update_kernel(AstBeamSt
             const int j = live_idx[li], s = b * bw + j, e = nf + li * bw + r;
             const double sc = st.score[cur][s] + (double)v;
             cscore[e] = sc;
-            ckey[e] = q.use_lp ? sc + cn_mul_rn((double)st.len[cur][s], q.lp) : sc;  // new length - 1 = old length
+            ckey[e] = beam_key(sc, st.len[cur][s], q.lp, q.use_lp);  // new length - 1 = old length
             cpar[e] = j;
             ccand[e] = c;
             ctok[e] = q.idx[(long long)s * K + c];
@@ -474,9 +443,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void ast_beam_update_kernel(AstBeamSt
     __syncthreads();
     const int ncand = nf + nl * (K < bw ? K : bw);
     for (int e = tid; e < ncand; e += BEAM_THREADS) {
-        const double k = ckey[e];
-        int r = 0;
-        for (int e2 = 0; e2 < ncand; ++e2) r += (ckey[e2] > k) || (ckey[e2] == k && e2 < e);
+        const int r = beam_rank(ckey, ncand, e);
         if (r < bw) newslot[r] = e;
     }
     __syncthreads();
@@ -499,21 +466,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void ast_beam_update_kernel(AstBeamSt
         const int so = b * bw + cpar[e];
         const int len_o = st.len[cur][so];
         const bool grown = ccand[e] >= 0;
-        for (int t = tid; t < L; t += BEAM_THREADS) {
-            int tk = st.tok[cur][(long long)so * L + t], an = st.anc[cur][(long long)so * L + t];
-            unsigned char ko = st.keyok[cur][(long long)so * L + t];
-            if (grown) {
-                if (t == len_o) {
-                    tk = ctok[e];
-                    ko = ctok[e] != q.pad;
-                }
-                if (t == q.pos) an = so;       // position pos was computed in the parent's slot this step
-                if (t == q.pos + 1) an = sn;   // the next position will be computed in this slot
-            }
-            st.tok[nxt][(long long)sn * L + t] = tk;
-            st.anc[nxt][(long long)sn * L + t] = an;
-            st.keyok[nxt][(long long)sn * L + t] = ko;
-        }
+        beam_write_row(st, cur, L, so, sn, grown, len_o, q.pos, grown ? ctok[e] : 0, q.pad, tid, BEAM_THREADS);
         if (tid == 0) {
             st.valid[nxt][sn] = 1;
             st.len[nxt][sn] = len_o + (grown ? 1 : 0);

@@ -150,6 +150,34 @@ int ast_prepare_buffers(cn_model* m, int max_len, int max_slots, int ctc_beam) {
 }
 }  // namespace
 
+// is this LM handle usable beside model m (an attach, or a call that takes both handles)?
+int lm_check_pair(const cn_model* m, const cn_model* lm, const char* who) {
+    if (!lm || lm->cfg.ast != 2 || !lm->finalized) {
+        cn_set_error(std::string(who) + ": the LM handle must be a finalized TransformerLM (cfg.ast = 2)");
+        return -1;
+    }
+    if (lm->lib_tag != m->lib_tag) {
+        cn_set_error(std::string(who) + ": the two handles come from different libraries");
+        return -1;
+    }
+    if (lm->cfg.vocab_size != m->cfg.vocab_size || lm->cfg.device != m->cfg.device) {
+        cn_set_error(std::string(who) + ": the LM must have the model's vocabulary and device");
+        return -1;
+    }
+    return 0;
+}
+
+// the range of one step of handle m (decoder or LM) against its step cache and tables; K = 0: the entry takes no top-K
+int step_check(const cn_model* m, const char* who, int n, int pos, int table_stride, int K) {
+    if (n < 1 || n > m->ast_slots || pos < 0 || pos >= m->ast_max_len || pos >= m->pe_rows || table_stride <= pos ||
+        (K != 0 && (K < 1 || K > 32 || K > m->cfg.vocab_size))) {
+        cn_set_error(std::string(who) + ": rows / position / K outside the configured cache (1 <= rows <= slots, 0 <= position < max_len, "
+                     "the position table and table_stride; 1 <= K <= 32 and <= the vocabulary)");
+        return -1;
+    }
+    return 0;
+}
+
 // the TransformerLM's step cache [layer][pos][slot][d] (K and V) and its logits [slot][V], on the LM handle
 int lm_prepare_buffers(cn_model* lm, int max_len, int max_slots) {
     CN_TRY(build_workspace(lm));
@@ -185,104 +213,193 @@ int lm_check_step(const cn_model* lm, int max_len, int max_slots, const char* wh
     return 0;
 }
 
+namespace {
+// The rows of one decoding step: the newest position of n hypotheses (already embedded into the stack's stream), each with the
+// tables its cache attention gathers through.
+struct StepRows {
+    int n = 0, pos = 0;                // rows; the step's position (with row_pos: the largest of them)
+    const int32_t* anc = nullptr;      // [n][table_stride] cache slot that wrote every prefix position (with row_pos: cache ROW ids)
+    const uint8_t* keyok = nullptr;    // [n][table_stride] key allowed (unused with row_pos: every key is)
+    int table_stride = 0;
+    const int32_t* row_pos = nullptr;  // a position per row (the CTC prefix beam, whose hypotheses differ in length) ...
+    const int32_t* row_stay = nullptr; // ... and the rows that append nothing (their output is garbage the caller discards)
+    const int32_t* utt = nullptr;      // [n] utterance of the row: whose memory a layer's source attention reads
+    int dense_bw = 0;                  // > 0: the rows are the dense slots b * dense_bw + j of the device beam (utt[row] = row / dense_bw)
+};
+// A stack of pre-norm layers whose self-attention reads the step cache m->ast_ck / ast_cv: the decoder's (m->mad, with source
+// attention over m->ast_kvx) or the TransformerLM's (m->enc).
+struct StepStack {
+    const std::vector<Layer>& layers;
+    int ffn_norm;            // the Layer::n[] that precedes the feed-forward sublayer
+    const Norm& final_norm;  // behind the last layer, into ...
+    void* final_out;
+    float* x;                // the residual stream [n][d]
+    const char *tag_qkv, *tag_attn, *tag_attn_rows, *tag_out, *tag_ffn_split;  // ProfScope tags
+};
+
+// x += FFN(LN x) on the n rows of a step.  A decode step has few rows (live hypotheses, <= batch x beam): the fused feed-forward
+// kernel would put them on ceil(n / 64) workgroups that each stream the whole 2 MB of W1|W2.  Its d_ff split spreads the hidden
+// units over 8 workgroups per row tile; the reduce kernel that adds the slices also writes the LayerNorm the next sublayer
+// starts with into next_out, and *have_next says so (otherwise: the plain sublayer, nothing behind it).  Only where the layer
+// has the fused kernel's streams, while the rows are few, and the slices fit the hidden-activation buffer they borrow.
+// (L.w1.N is the stack's d_encff / d_decff in every layer: weights.hip packs each layer of a stack with that one width.)
+int run_ffn_step(cn_model* m, const Layer& L, const Norm& norm, float* x, int n, const Norm& next_norm, void* next_out,
+                 const char* tag, hipStream_t s, bool* have_next) {
+    static const bool no_split = cn_exp_env("CASSNAT_AST_NO_FFN_SPLIT") != nullptr;
+    const cn_config& c = m->cfg;
+    const int d = c.d_model, dff = L.w1.N;
+    const int ffn_slices = (!L.w1p || no_split) ? 1 : (dff % (128 * 8) == 0 ? 8 : (dff % (128 * 4) == 0 ? 4 : 1));
+    const size_t hbuf_bytes = (size_t)m->maxB * (m->maxTp + 1) * std::max(1, c.esa_group) *
+                              (size_t)std::max(std::max(c.d_encff, c.d_decff), c.d_ff) * m->es;
+    const bool split_now = ffn_slices > 1 && n <= 2048 && (size_t)ffn_slices * n * d * 4 <= hbuf_bytes;
+    *have_next = split_now;
+    if (!split_now) return run_ffn(m, L, norm, x, n, nullptr, nullptr, s);
+    ProfScope ps(m, tag, 4.0 * n * (double)dff * d, 2.0 * dff * d * 2 + (double)n * d * (8 + 4 * ffn_slices), s);
+    FfnFusedArgs f;
+    f.x = x;
+    f.ln_a = norm.a;
+    f.ln_b = norm.b;
+    f.w1p = L.w1p;
+    f.b1 = L.w1.b;
+    f.w2p = L.w2p;
+    f.b2 = L.w2.b;
+    f.M = n;
+    f.d = d;
+    f.dff = dff;
+    f.nslice = ffn_slices;
+    f.partial = reinterpret_cast<float*>(m->hbuf);  // [slices][n][256] fp32 <= the [rows][d_ff] hidden buffer
+    f.act = L.ff_swish ? FF_ACT_SWISH : FF_ACT_RELU;
+    CN_TRY(launch_ffn_fused(f, s));
+    return launch_ffn_reduce(x, f.partial, ffn_slices, L.w2.b, next_norm.a, next_norm.b, next_out, n, 1e-6f, s);
+}
+
+// x += O(SrcAttn(LN x, memory)) of decoder layer l on the rows of a step: the memory's K | V are m->ast_kvx[l] (cn_ast_begin)
+int run_src_attn_step(cn_model* m, const Layer& L, size_t l, float* x, const StepRows& r, float scale, hipStream_t s) {
+    const int d = m->cfg.d_model, H = m->cfg.n_head, n = r.n;
+    CN_TRY(run_ln(m, L.n[1], x, m->xn, n, s));
+    CN_TRY(run_linear(m, "src_q_proj", L.src_q, m->xn, d, m->qd, d, 0, n, 0, nullptr, 0, s));
+    static const bool no_fast_src = cn_exp_env("CASSNAT_AST_GATHER_SRC") != nullptr;
+    if (m->prec == CN_PREC_BF16 && m->Tp <= 256 && !no_fast_src) {
+        // every hypothesis row is a batch entry of one query whose keys / values are its utterance's: the LDS-resident
+        // attention kernel (K|V of a (row, head) by LDS-DMA, MFMA products) instead of the scalar gather kernel
+        ProfScope ps(m, "ast_src_attention", 4.0 * n * H * m->Tp * 64, 2.0 * n * m->Tp * d * m->es, s);
+        AttnArgs a2;
+        a2.Q = m->qd;
+        a2.K = m->ast_kvx[l];
+        a2.V = (const unsigned char*)m->ast_kvx[l] + (size_t)d * m->es;
+        a2.O = m->ctx;
+        a2.ldq = d;
+        a2.ldk = a2.ldv = 2 * d;
+        a2.ldo = d;
+        a2.H = H;
+        a2.Lk = m->Tp;
+        a2.keymask = m->keymask;
+        if (r.dense_bw > 0 && n % r.dense_bw == 0) {  // device beam: utterance b owns rows b * bw .. + bw - 1
+            a2.B = n / r.dense_bw;
+            a2.Lq = r.dense_bw;
+        } else {  // caller-managed rows: every row is a batch entry of one query that names its utterance
+            a2.B = n;
+            a2.Lq = 1;
+            a2.kv_index = r.utt;
+        }
+        a2.scale = scale;
+        CN_TRY(launch_attention(m->prec, a2, s));
+    } else {
+        GatherAttnArgs b;
+        b.q = m->qd;
+        b.ldq = d;
+        b.k = m->ast_kvx[l];
+        b.v = (const unsigned char*)m->ast_kvx[l] + (size_t)d * m->es;
+        b.o = m->ctx;
+        b.ldo = d;
+        b.n = n;
+        b.H = H;
+        b.nkeys = m->Tp;
+        b.d = d;
+        b.utt = r.utt;
+        b.keymask = m->keymask;
+        b.scale = scale;
+        ProfScope ps(m, "ast_src_attention", 4.0 * n * H * m->Tp * 64, 2.0 * n * m->Tp * d * m->es, s);
+        CN_TRY(launch_ast_gather_attn(m->prec, 1, b, s));
+    }
+    return run_linear(m, "out_proj_resid", L.src_o, m->ctx, d, x, d, 1, n, CN_EPI_RESID, x, d, s);
+}
+
+// The newest position of the rows through the stack: st.x (the embedded tokens) -> final_norm of the stack's output in
+// st.final_out.  Per layer: LN, fused QKV, cache attention over the earlier positions (it appends this position's K | V itself:
+// it is the only reader of that row now), out-projection + residual, the source-attention sublayer of a layer that has one, the
+// feed-forward sublayer.
+int run_step_stack(cn_model* m, const StepStack& st, const StepRows& r, hipStream_t s) {
+    const int d = m->cfg.d_model, H = m->cfg.n_head, n = r.n;
+    const float scale = 1.0f / sqrtf((float)(d / H));
+    float* x = st.x;
+    bool have_ln = false;  // m->xn already holds LN(x) for the sublayer about to start
+    for (size_t l = 0; l < st.layers.size(); ++l) {
+        const Layer& L = st.layers[l];
+        if (!have_ln) CN_TRY(run_ln(m, L.n[0], x, m->xn, n, s));
+        CN_TRY(run_linear(m, st.tag_qkv, L.qkv, m->xn, d, m->qkv, 3 * d, 0, n, 0, nullptr, 0, s));
+        GatherArgs g;
+        g.q = m->qkv;
+        g.ldq = 3 * d;
+        g.k = m->ast_ck[l];
+        g.v = m->ast_cv[l];
+        g.o = m->ctx;
+        g.ldo = d;
+        g.n = n;
+        g.H = H;
+        g.d = d;
+        g.table_stride = r.table_stride;
+        g.scale = scale;
+        {
+            ProfScope ps(m, r.row_pos ? st.tag_attn_rows : st.tag_attn, 4.0 * n * H * (r.pos + 1) * 64, 2.0 * n * (r.pos + 1) * d * m->es, s);
+            if (r.row_pos) {
+                GatherRowsArgs a;
+                static_cast<GatherArgs&>(a) = g;
+                a.max_keys = r.pos + 1;
+                a.rowid = r.anc;
+                a.pos = r.row_pos;
+                a.stay = r.row_stay;
+                CN_TRY(launch_ast_gather_attn_rows(m->prec, a, s));
+            } else {
+                GatherAttnArgs a;
+                static_cast<GatherArgs&>(a) = g;
+                a.append_pos = r.pos;
+                a.nkeys = r.pos + 1;
+                a.slots = m->ast_slots;
+                a.anc = r.anc;
+                a.keyok = r.keyok;
+                CN_TRY(launch_ast_gather_attn(m->prec, 0, a, s));
+            }
+        }
+        CN_TRY(run_linear(m, st.tag_out, L.self_o, m->ctx, d, x, d, 1, n, CN_EPI_RESID, x, d, s));
+        if (L.has_src) CN_TRY(run_src_attn_step(m, L, l, x, r, scale, s));
+        const bool last = l + 1 == st.layers.size();
+        CN_TRY(run_ffn_step(m, L, L.n[st.ffn_norm], x, n, last ? st.final_norm : st.layers[l + 1].n[0], last ? st.final_out : m->xn,
+                            st.tag_ffn_split, s, &have_ln));
+    }
+    if (!have_ln) CN_TRY(run_ln(m, st.final_norm, x, st.final_out, n, s));
+    return 0;
+}
+}  // namespace
+
 // TransformerLM (src/models/lm.py:52-56) on the newest position of n hypotheses -> logits [n][V] fp32 in lm->ast_logits.  The
 // reference runs lm_model(ys, tgt_mask) on the whole prefix under the decoder's mask (ys != padding_idx) & subsequent_mask
 // (transformer.py:186-191); here the keys / values of earlier positions come from the LM's own cache through the SAME ancestor
-// and key-mask tables as the decoder's.  Per layer (pre-norm encoder layer): LN, fused QKV, cached self-attention (appends this
-// position), out-proj + residual, FFN sublayer; then encoder.norm and out_generator.proj.
+// and key-mask tables as the decoder's.  The embedding, its pre-norm encoder layers as a step stack, then encoder.norm and
+// out_generator.proj.
 // With row_pos / row_stay (the CTC prefix beam search, whose hypotheses differ in length): row h sits at position row_pos[h] <= pos,
 // anc_dev holds its cache ROW ids (one per prefix position, any row of the cache), every key is allowed (keyok_dev unused), and a
 // row with row_stay[h] != 0 appends nothing - its logits are garbage the caller discards.
 int lm_step_run(cn_model* lm, int n, int pos, const int32_t* tok_dev, const int32_t* anc_dev, const uint8_t* keyok_dev,
                 int table_stride, hipStream_t s, const int32_t* row_pos, const int32_t* row_stay) {
-    const cn_config& c = lm->cfg;
-    const int d = c.d_model, V = c.vocab_size, H = c.n_head;
-    const float scale = 1.0f / sqrtf((float)(d / H));
-    float* x = lm->x;
+    const int d = lm->cfg.d_model, V = lm->cfg.vocab_size;
     if (row_pos)
-        CN_TRY(launch_ast_embed_rows(tok_dev, lm->tgt_lut, lm->pe, row_pos, x, n, d, sqrtf((float)d), pos, s));
+        CN_TRY(launch_ast_embed_rows(tok_dev, lm->tgt_lut, lm->pe, row_pos, lm->x, n, d, sqrtf((float)d), pos, s));
     else
-        CN_TRY(launch_ast_embed(tok_dev, lm->tgt_lut, lm->pe + (size_t)pos * d, x, n, d, sqrtf((float)d), s));
-    // bf16 / d_model 256 (lm_small): the decode step's d_ff split of the fused FFN kernel, as in ast_step_run
-    static const bool no_split = cn_exp_env("CASSNAT_AST_NO_FFN_SPLIT") != nullptr;
-    const int dff = c.d_encff;
-    const int ffn_slices = (lm->enc.empty() || !lm->enc[0].w1p || no_split) ? 1 : (dff % (128 * 8) == 0 ? 8 : (dff % (128 * 4) == 0 ? 4 : 1));
-    const size_t hbuf_bytes = (size_t)lm->maxB * (lm->maxTp + 1) * std::max(1, c.esa_group) *
-                              (size_t)std::max(std::max(c.d_encff, c.d_decff), c.d_ff) * lm->es;
-    const bool split_now = ffn_slices > 1 && n <= 2048 && (size_t)ffn_slices * n * d * 4 <= hbuf_bytes;
-    bool have_ln = false;
-    for (size_t l = 0; l < lm->enc.size(); ++l) {
-        const Layer& L = lm->enc[l];
-        if (!have_ln) CN_TRY(run_ln(lm, L.n[0], x, lm->xn, n, s));
-        have_ln = false;
-        CN_TRY(run_linear(lm, "lm_qkv_proj", L.qkv, lm->xn, d, lm->qkv, 3 * d, 0, n, 0, nullptr, 0, s));
-        GatherAttnArgs a;
-        a.append_pos = pos;
-        a.q = lm->qkv;
-        a.ldq = 3 * d;
-        a.k = lm->ast_ck[l];
-        a.v = lm->ast_cv[l];
-        a.o = lm->ctx;
-        a.ldo = d;
-        a.n = n;
-        a.H = H;
-        a.nkeys = pos + 1;
-        a.slots = lm->ast_slots;
-        a.d = d;
-        a.table_stride = table_stride;
-        a.anc = anc_dev;
-        a.keyok = keyok_dev;
-        a.scale = scale;
-        if (row_pos) {
-            GatherRowsArgs r;
-            r.q = lm->qkv;
-            r.ldq = 3 * d;
-            r.k = lm->ast_ck[l];
-            r.v = lm->ast_cv[l];
-            r.o = lm->ctx;
-            r.ldo = d;
-            r.n = n;
-            r.H = H;
-            r.d = d;
-            r.table_stride = table_stride;
-            r.max_keys = pos + 1;
-            r.rowid = anc_dev;
-            r.pos = row_pos;
-            r.stay = row_stay;
-            r.scale = scale;
-            ProfScope ps(lm, "lm_cache_attention_rows", 4.0 * n * H * (pos + 1) * 64, 2.0 * n * (pos + 1) * d * lm->es, s);
-            CN_TRY(launch_ast_gather_attn_rows(lm->prec, r, s));
-        } else {
-            ProfScope ps(lm, "lm_cache_attention", 4.0 * n * H * (pos + 1) * 64, 2.0 * n * (pos + 1) * d * lm->es, s);
-            CN_TRY(launch_ast_gather_attn(lm->prec, 0, a, s));
-        }
-        CN_TRY(run_linear(lm, "lm_out_proj_resid", L.self_o, lm->ctx, d, x, d, 1, n, CN_EPI_RESID, x, d, s));
-        if (split_now) {
-            const bool last = l + 1 == lm->enc.size();
-            const Norm& nx = last ? lm->enc_norm : lm->enc[l + 1].n[0];
-            ProfScope ps(lm, "lm_ffn_split", 4.0 * n * (double)L.w1.N * d, 2.0 * L.w1.N * d * 2 + (double)n * d * (8 + 4 * ffn_slices), s);
-            FfnFusedArgs f;
-            f.x = x;
-            f.ln_a = L.n[1].a;
-            f.ln_b = L.n[1].b;
-            f.w1p = L.w1p;
-            f.b1 = L.w1.b;
-            f.w2p = L.w2p;
-            f.b2 = L.w2.b;
-            f.M = n;
-            f.d = d;
-            f.dff = L.w1.N;
-            f.nslice = ffn_slices;
-            f.partial = reinterpret_cast<float*>(lm->hbuf);
-            f.act = FF_ACT_RELU;
-            CN_TRY(launch_ffn_fused(f, s));
-            CN_TRY(launch_ffn_reduce(x, f.partial, ffn_slices, L.w2.b, nx.a, nx.b, last ? lm->enc_h : lm->xn, n, 1e-6f, s));
-            have_ln = true;
-        } else {
-            CN_TRY(run_ffn(lm, L, L.n[1], x, n, nullptr, nullptr, s));
-        }
-    }
-    if (!have_ln) CN_TRY(run_ln(lm, lm->enc_norm, x, lm->enc_h, n, s));
+        CN_TRY(launch_ast_embed(tok_dev, lm->tgt_lut, lm->pe + (size_t)pos * d, lm->x, n, d, sqrtf((float)d), s));
+    const StepStack st{lm->enc, 1, lm->enc_norm, lm->enc_h, lm->x, "lm_qkv_proj", "lm_cache_attention", "lm_cache_attention_rows",
+                       "lm_out_proj_resid", "lm_ffn_split"};
+    CN_TRY(run_step_stack(lm, st, StepRows{n, pos, anc_dev, keyok_dev, table_stride, row_pos, row_stay}, s));
     return run_linear(lm, "lm_generator_proj", lm->att_gen, lm->enc_h, d, lm->ast_logits, V, 1, n, 0, nullptr, 0, s);
 }
 }  // namespace cn_host
@@ -297,18 +414,7 @@ extern "C" int cn_ast_attach_lm(cn_model* m, cn_model* lm) {
         m->ast_lm = nullptr;
         return 0;
     }
-    if (lm->lib_tag != m->lib_tag) {
-        cn_set_error("cn_ast_attach_lm: the two handles come from different libraries");
-        return -1;
-    }
-    if (lm->cfg.ast != 2 || !lm->finalized) {
-        cn_set_error("cn_ast_attach_lm: the LM handle must be a finalized TransformerLM (cfg.ast = 2)");
-        return -1;
-    }
-    if (lm->cfg.vocab_size != m->cfg.vocab_size || lm->cfg.device != m->cfg.device) {
-        cn_set_error("cn_ast_attach_lm: the LM must have the decoder's vocabulary and device");
-        return -1;
-    }
+    CN_TRY(lm_check_pair(m, lm, "cn_ast_attach_lm"));
     m->ast_lm = lm;
     return 0;
 }
@@ -339,7 +445,7 @@ extern "C" int cn_ast_begin(cn_model* m, const float* feats_dev, int32_t B, int3
     if (want_ctc) {
         CN_TRY(run_linear(m, "generator_proj", m->ctc_gen, m->enc_h, d, m->logits, V, 1, Mmem, 0, nullptr, 0, s));
         CN_TRY(launch_logsoftmax_argmax(m->logits, Mmem, V, V, m->best, m->ctc_maxlp, 1, s));
-    m->ctc_maxlp_valid = true;
+        m->ctc_maxlp_valid = true;
         CN_TRY(launch_ast_ctc_prepare(m->logits, m->keymask, m->ast_r0, B, m->Tp, V, opts->padding_idx, s));
     }
     return 0;
@@ -353,124 +459,12 @@ int ast_step_run(cn_model* m, int n, int pos, const int32_t* tok_dev, const int3
                  const uint8_t* keyok_dev, int table_stride, float temperature, int K, int32_t* topk_idx_dev,
                  float* topk_val_dev, int dense_bw, hipStream_t s, float lm_weight = 0.f, float* lm_val_dev = nullptr,
                  const float* ng_adds_dev = nullptr, int ng_eos = -1) {
-    const cn_config& c = m->cfg;
-    const int d = c.d_model, V = c.vocab_size, H = c.n_head;
-    const float scale = 1.0f / sqrtf((float)(d / H));
-    float* x = m->xd;
-    CN_TRY(launch_ast_embed(tok_dev, m->tgt_lut, m->pe + (size_t)pos * d, x, n, d, sqrtf((float)d), s));
-    // A decode step has few rows (live hypotheses, <= batch x beam): the fused feed-forward kernel would put them on
-    // ceil(n / 64) workgroups that each stream the whole 2 MB of W1|W2.  Its d_ff split spreads the hidden units over 8
-    // workgroups per row tile; the reduce kernel that adds the slices also writes the LayerNorm the next sublayer starts
-    // with (the next layer's self-attention pre-norm, or decoder.norm after the last layer).
-    static const bool no_split = cn_exp_env("CASSNAT_AST_NO_FFN_SPLIT") != nullptr;
-    const int ffn_slices = (m->mad.empty() || !m->mad[0].w1p || no_split) ? 1 : (c.d_decff % (128 * 8) == 0 ? 8 : (c.d_decff % (128 * 4) == 0 ? 4 : 1));
-    bool have_ln = false;  // m->xn already holds LN(x) for the sublayer about to start
-    // (only while the rows are few, and the slices fit the hidden-activation buffer they borrow)
-    const size_t hbuf_bytes = (size_t)m->maxB * (m->maxTp + 1) * std::max(1, c.esa_group) *
-                              (size_t)std::max(std::max(c.d_encff, c.d_decff), c.d_ff) * m->es;
-    const bool split_now = ffn_slices > 1 && n <= 2048 && (size_t)ffn_slices * n * d * 4 <= hbuf_bytes;
-    for (size_t l = 0; l < m->mad.size(); ++l) {
-        const Layer& L = m->mad[l];
-        // x += O(SelfAttn(LN x)) over the cached prefix
-        if (!have_ln) CN_TRY(run_ln(m, L.n[0], x, m->xn, n, s));
-        have_ln = false;
-        CN_TRY(run_linear(m, "qkv_proj", L.qkv, m->xn, d, m->qkv, 3 * d, 0, n, 0, nullptr, 0, s));
-        GatherAttnArgs a;
-        a.append_pos = pos;  // the cache attention appends this position's K | V itself (it is the only reader of that row now)
-        a.q = m->qkv;
-        a.ldq = 3 * d;
-        a.k = m->ast_ck[l];
-        a.v = m->ast_cv[l];
-        a.o = m->ctx;
-        a.ldo = d;
-        a.n = n;
-        a.H = H;
-        a.nkeys = pos + 1;
-        a.slots = m->ast_slots;
-        a.d = d;
-        a.table_stride = table_stride;
-        a.anc = anc_dev;
-        a.keyok = keyok_dev;
-        a.scale = scale;
-        {
-            ProfScope ps(m, "ast_cache_attention", 4.0 * n * H * (pos + 1) * 64, 2.0 * n * (pos + 1) * d * m->es, s);
-            CN_TRY(launch_ast_gather_attn(m->prec, 0, a, s));
-        }
-        CN_TRY(run_linear(m, "out_proj_resid", L.self_o, m->ctx, d, x, d, 1, n, CN_EPI_RESID, x, d, s));
-        // x += O(SrcAttn(LN x, memory))
-        CN_TRY(run_ln(m, L.n[1], x, m->xn, n, s));
-        CN_TRY(run_linear(m, "src_q_proj", L.src_q, m->xn, d, m->qd, d, 0, n, 0, nullptr, 0, s));
-        GatherAttnArgs b;
-        b.q = m->qd;
-        b.ldq = d;
-        b.k = m->ast_kvx[l];
-        b.v = (const unsigned char*)m->ast_kvx[l] + (size_t)d * m->es;
-        b.o = m->ctx;
-        b.ldo = d;
-        b.n = n;
-        b.H = H;
-        b.nkeys = m->Tp;
-        b.d = d;
-        b.utt = utt_dev;
-        b.keymask = m->keymask;
-        b.scale = scale;
-        static const bool no_fast_src = cn_exp_env("CASSNAT_AST_GATHER_SRC") != nullptr;
-        if (m->prec == CN_PREC_BF16 && m->Tp <= 256 && !no_fast_src) {
-            // every hypothesis row is a batch entry of one query whose keys / values are its utterance's: the LDS-resident
-            // attention kernel (K|V of a (row, head) by LDS-DMA, MFMA products) instead of the scalar gather kernel
-            ProfScope ps(m, "ast_src_attention", 4.0 * n * H * m->Tp * 64, 2.0 * n * m->Tp * d * m->es, s);
-            AttnArgs a2;
-            a2.Q = m->qd;
-            a2.K = m->ast_kvx[l];
-            a2.V = (const unsigned char*)m->ast_kvx[l] + (size_t)d * m->es;
-            a2.O = m->ctx;
-            a2.ldq = d;
-            a2.ldk = a2.ldv = 2 * d;
-            a2.ldo = d;
-            a2.H = H;
-            a2.Lk = m->Tp;
-            a2.keymask = m->keymask;
-            if (dense_bw > 0 && n % dense_bw == 0) {  // device beam: utterance b owns rows b * bw .. + bw - 1
-                a2.B = n / dense_bw;
-                a2.Lq = dense_bw;
-            } else {  // caller-managed rows: every row is a batch entry of one query that names its utterance
-                a2.B = n;
-                a2.Lq = 1;
-                a2.kv_index = utt_dev;
-            }
-            a2.scale = scale;
-            CN_TRY(launch_attention(m->prec, a2, s));
-        } else {
-            ProfScope ps(m, "ast_src_attention", 4.0 * n * H * m->Tp * 64, 2.0 * n * m->Tp * d * m->es, s);
-            CN_TRY(launch_ast_gather_attn(m->prec, 1, b, s));
-        }
-        CN_TRY(run_linear(m, "out_proj_resid", L.src_o, m->ctx, d, x, d, 1, n, CN_EPI_RESID, x, d, s));
-        if (split_now) {
-            const bool last = l + 1 == m->mad.size();
-            const Norm& nx = last ? m->dec_norm : m->mad[l + 1].n[0];
-            ProfScope ps(m, "ffn_split", 4.0 * n * (double)L.w1.N * d, 2.0 * L.w1.N * d * 2 + (double)n * d * (8 + 4 * ffn_slices), s);
-            FfnFusedArgs a;
-            a.x = x;
-            a.ln_a = L.n[2].a;
-            a.ln_b = L.n[2].b;
-            a.w1p = L.w1p;
-            a.b1 = L.w1.b;
-            a.w2p = L.w2p;
-            a.b2 = L.w2.b;
-            a.M = n;
-            a.d = d;
-            a.dff = L.w1.N;
-            a.nslice = ffn_slices;
-            a.partial = reinterpret_cast<float*>(m->hbuf);  // [slices][n][256] fp32 <= the [rows][d_ff] hidden buffer
-            a.act = L.ff_swish ? FF_ACT_SWISH : FF_ACT_RELU;
-            CN_TRY(launch_ffn_fused(a, s));
-            CN_TRY(launch_ffn_reduce(x, a.partial, ffn_slices, L.w2.b, nx.a, nx.b, last ? m->dec_h : m->xn, n, 1e-6f, s));
-            have_ln = true;
-        } else {
-            CN_TRY(run_ffn(m, L, L.n[2], x, n, nullptr, nullptr, s));
-        }
-    }
-    if (!have_ln) CN_TRY(run_ln(m, m->dec_norm, x, m->dec_h, n, s));
+    const int d = m->cfg.d_model, V = m->cfg.vocab_size;
+    CN_TRY(launch_ast_embed(tok_dev, m->tgt_lut, m->pe + (size_t)pos * d, m->xd, n, d, sqrtf((float)d), s));
+    // DecoderLayer: self attention over the cached prefix, source attention over the memory, feed-forward
+    const StepStack st{m->mad, 2, m->dec_norm, m->dec_h, m->xd, "qkv_proj", "ast_cache_attention", "ast_cache_attention",
+                       "out_proj_resid", "ffn_split"};
+    CN_TRY(run_step_stack(m, st, StepRows{n, pos, anc_dev, keyok_dev, table_stride, nullptr, nullptr, utt_dev, dense_bw}, s));
     CN_TRY(run_linear(m, "generator_proj", m->att_gen, m->dec_h, d, m->ast_logits, V, 1, n, 0, nullptr, 0, s));
     if (lm_weight > 0.f) {  // shallow fusion (transformer.py:186-209): the LM step on the same rows, tables and position
         cn_model* lm = m->ast_lm;
@@ -500,11 +494,7 @@ extern "C" int cn_ast_step(cn_model* m, int32_t n, int32_t pos, const int32_t* t
         cn_set_error("cn_ast_step: call cn_ast_begin first");
         return -1;
     }
-    if (n < 1 || n > m->ast_slots || pos < 0 || pos >= m->ast_max_len || pos >= m->pe_rows || K < 1 || K > 32 ||
-        K > m->cfg.vocab_size || table_stride <= pos) {
-        cn_set_error("cn_ast_step: live rows / position / K outside the configured cache (K <= 32 and <= the vocabulary)");
-        return -1;
-    }
+    CN_TRY(step_check(m, "cn_ast_step", n, pos, table_stride, K < 1 ? -1 : K));  // (a K of 0 is not "no top-K" here)
     CN_HIP_CHECK(hipSetDevice(m->cfg.device));
     return ast_step_run(m, n, pos, tok_dev, utt_dev, anc_dev, keyok_dev, table_stride, temperature, K, topk_idx_dev, topk_val_dev, 0,
                         (hipStream_t)stream);
@@ -526,10 +516,9 @@ extern "C" int cn_ast_step_lm(cn_model* m, int32_t n, int32_t pos, const int32_t
         cn_set_error("cn_ast_step_lm: needs lm_weight > 0 and an LM attached (cn_ast_attach_lm) before cn_ast_begin");
         return -1;
     }
-    if (n < 1 || n > m->ast_slots || pos < 0 || pos >= m->ast_max_len || pos >= m->pe_rows || K < 1 || K > 32 ||
-        K > m->cfg.vocab_size || table_stride <= pos || (use_ctc && !lm_val_dev)) {
-        cn_set_error("cn_ast_step_lm: live rows / position / K outside the configured cache (K <= 32 and <= the vocabulary; or use_ctc "
-                     "without lm_val_dev)");
+    CN_TRY(step_check(m, "cn_ast_step_lm", n, pos, table_stride, K < 1 ? -1 : K));
+    if (use_ctc && !lm_val_dev) {
+        cn_set_error("cn_ast_step_lm: use_ctc without lm_val_dev");
         return -1;
     }
     CN_HIP_CHECK(hipSetDevice(m->cfg.device));
@@ -585,10 +574,9 @@ extern "C" int cn_ast_step_ngram(cn_model* m, int32_t n, int32_t pos, const int3
         cn_set_error("cn_ast_step_ngram: an n-gram model and a TransformerLM are attached together; detach one");
         return -1;
     }
-    if (n < 1 || n > m->ast_slots || pos < 0 || pos >= m->ast_max_len || pos >= m->pe_rows || K < 1 || K > 32 ||
-        K > m->cfg.vocab_size || table_stride <= pos || !adds_dev || (use_ctc && !term_dev)) {
-        cn_set_error("cn_ast_step_ngram: live rows / position / K outside the configured cache (K <= 32 and <= the vocabulary; or no "
-                     "adds_dev; or use_ctc without term_dev)");
+    CN_TRY(step_check(m, "cn_ast_step_ngram", n, pos, table_stride, K < 1 ? -1 : K));
+    if (!adds_dev || (use_ctc && !term_dev)) {
+        cn_set_error("cn_ast_step_ngram: no adds_dev, or use_ctc without term_dev");
         return -1;
     }
     hipStream_t s = (hipStream_t)stream;
@@ -616,10 +604,7 @@ extern "C" int cn_lm_step(cn_model* lm, int32_t n, int32_t pos, const int32_t* t
         cn_set_error("cn_lm_step: call cn_lm_step_begin first");
         return -1;
     }
-    if (n < 1 || n > lm->ast_slots || pos < 0 || pos >= lm->ast_max_len || pos >= lm->pe_rows || table_stride <= pos) {
-        cn_set_error("cn_lm_step: rows / position outside the configured cache");
-        return -1;
-    }
+    CN_TRY(step_check(lm, "cn_lm_step", n, pos, table_stride, 0));
     hipStream_t s = (hipStream_t)stream;
     CN_HIP_CHECK(hipSetDevice(lm->cfg.device));
     const int V = lm->cfg.vocab_size;
@@ -643,10 +628,7 @@ extern "C" int cn_lm_step_rows(cn_model* lm, int32_t n, int32_t max_pos, const i
         cn_set_error("cn_lm_step_rows: null array");
         return -1;
     }
-    if (n < 1 || n > lm->ast_slots || max_pos < 0 || max_pos >= lm->ast_max_len || max_pos >= lm->pe_rows || table_stride <= max_pos) {
-        cn_set_error("cn_lm_step_rows: rows / position outside the configured cache");
-        return -1;
-    }
+    CN_TRY(step_check(lm, "cn_lm_step_rows", n, max_pos, table_stride, 0));
     hipStream_t s = (hipStream_t)stream;
     CN_HIP_CHECK(hipSetDevice(lm->cfg.device));
     const int V = lm->cfg.vocab_size;

@@ -480,20 +480,22 @@ bool genmax_applies(int prec, int d, int V);
 
 // ---- autoregressive decoder step with KV cache + CTC prefix scorer (BASELINE config 4)             (ast.hip)
 int launch_ast_embed(const int* tok, const float* lut, const float* pe_row, float* x, int n, int d, float scale, hipStream_t s);
-int launch_ast_kv_append(int prec, const void* qkv, void* ck, void* cv, int n, int d, int slots, int pos, hipStream_t s);
-struct GatherAttnArgs {
-    const void* q = nullptr;
-    int ldq = 0;
-    const void* k = nullptr;
+// what every form of the gather attention reads: n query rows (one workgroup each), H heads of 64 columns
+struct GatherArgs {
+    const void* q = nullptr;  // [n][ldq] queries (mode 0 / rows: the fused Q | K | V projection)
+    const void* k = nullptr;  // cache rows [rows][d], or the fused K | V matrix of the source memory
     const void* v = nullptr;
-    void* o = nullptr;
-    int ldo = 0;
-    int n = 0, H = 0, nkeys = 0, slots = 0, d = 0, table_stride = 0;
+    void* o = nullptr;        // [n][ldo]
+    int ldq = 0, ldo = 0;
+    int n = 0, H = 0, d = 0, table_stride = 0;
+    float scale = 0.125f;
+};
+struct GatherAttnArgs : GatherArgs {
+    int nkeys = 0, slots = 0;
     const int* anc = nullptr;
     const unsigned char* keyok = nullptr;
     const int* utt = nullptr;
     const unsigned char* keymask = nullptr;
-    float scale = 0.125f;
     int append_pos = -1;  // mode 0: >= 0 appends this step's K | V (columns d.. / 2d.. of q's rows) to the cache at that position
 };
 int launch_ast_gather_attn(int prec, int mode, const GatherAttnArgs& a, hipStream_t s);  // mode 0: cache, 1: source memory
@@ -501,18 +503,11 @@ int launch_ast_gather_attn(int prec, int mode, const GatherAttnArgs& a, hipStrea
 // append nothing and give a zero context row
 int launch_ast_embed_rows(const int* tok, const float* lut, const float* pe, const int* pos, float* x, int n, int d, float scale,
                           int max_pos, hipStream_t s);
-struct GatherRowsArgs {
-    const void* q = nullptr;  // [n][ldq] fused Q | K | V projection
-    int ldq = 0;
-    void* k = nullptr;        // cache rows [rows][d]
-    void* v = nullptr;
-    void* o = nullptr;
-    int ldo = 0;
-    int n = 0, H = 0, d = 0, table_stride = 0, max_keys = 0;  // max_keys: bound of pos[h] + 1 (sizes the score buffer)
+struct GatherRowsArgs : GatherArgs {
+    int max_keys = 0;            // bound of pos[h] + 1 (sizes the score buffer)
     const int* rowid = nullptr;  // [n][table_stride]
     const int* pos = nullptr;    // [n]
     const int* stay = nullptr;   // [n]
-    float scale = 0.125f;
 };
 int launch_ast_gather_attn_rows(int prec, const GatherRowsArgs& a, hipStream_t s);
 int launch_ast_ctc_prepare(float* logp, const unsigned char* keymask, float* r0, int B, int Tp, int V, int blank, hipStream_t s);
@@ -529,17 +524,21 @@ struct CtcPrefixArgs {
     int n, K, Tp, V, blank, eos, out_len;
 };
 int launch_ast_ctc_prefix(const CtcPrefixArgs& a, hipStream_t s);
-// device-side beam state of the autoregressive search (double buffered: [cur], [cur ^ 1]); S = B * beam_width slots, L = max length
-struct AstBeamState {
+// device-side state every token-level beam keeps (double buffered: [cur], [cur ^ 1]); S = B * beam_width slots, L = max length.
+// (beam_core.h: the device functions of the two update kernels that work on it)
+struct BeamTables {
     int* tok[2];              // [S][L] hypothesis tokens (sos first)
-    int* anc[2];              // [S][L] KV-cache slot that produced each position
+    int* anc[2];              // [S][L] cache slot that produced each position
     unsigned char* keyok[2];  // [S][L] token != padding_idx
-    int* len[2];              // [S]
     double* score[2];         // [S]
+    int* cur_tok;             // [S] newest token = the next step's input
+};
+// ... and what the autoregressive search adds
+struct AstBeamState : BeamTables {  // (anc: the KV-cache slot)
+    int* len[2];              // [S]
     int* valid[2];            // [S]
     int* ctc_ref[2];          // [S] row of the previous step's CTC states (< 0: initial state of utterance -1-ref)
     float* ctc_prev[2];       // [S] CTC prefix score of the hypothesis
-    int* cur_tok;             // [S] newest token = the next step's input
     int* utt;                 // [S] utterance of the slot
     int* live;                // [1] live hypotheses after the last update
 };
@@ -568,14 +567,7 @@ struct NatFuseArgs {
     float w;
 };
 int launch_nat_lm_fuse_topk(const NatFuseArgs& a, int slots, hipStream_t s);
-// device-side beam state of that loop (double buffered); S = B * beam_width slots of L tokens
-struct NatBeamState {
-    int* tok[2];              // [S][L] hypothesis tokens (sos first)
-    int* anc[2];              // [S][L] LM cache slot that produced each position
-    unsigned char* keyok[2];  // [S][L] token != padding_idx
-    double* score[2];         // [S]
-    int* cur_tok;             // [S] newest token = the next LM step's input
-};
+using NatBeamState = BeamTables;  // the beam state of that loop (anc: the LM cache slot)
 struct NatBeamStep {
     const int* idx;    // [S][bw] candidate tokens of this step (best first)
     const float* val;  // [S][bw] their fused values

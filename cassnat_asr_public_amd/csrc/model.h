@@ -320,6 +320,7 @@ int stage_encode_ctc_rows(cn_model* m, const float* feats, int B, int T, int F, 
 // ---- decode_ar.hip: the TransformerLM's step, also run by the NAT finish loop and the CTC + LM beam ----
 int lm_prepare_buffers(cn_model* lm, int max_len, int max_slots);
 int lm_check_step(const cn_model* lm, int max_len, int max_slots, const char* who);
+int lm_check_pair(const cn_model* m, const cn_model* lm, const char* who);
 int lm_step_run(cn_model* lm, int n, int pos, const int32_t* tok_dev, const int32_t* anc_dev, const uint8_t* keyok_dev,
                 int table_stride, hipStream_t s, const int32_t* row_pos = nullptr, const int32_t* row_stay = nullptr);
 

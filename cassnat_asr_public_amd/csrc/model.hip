@@ -995,18 +995,7 @@ extern "C" int cn_nat_attach_lm(cn_model* m, cn_model* lm) {
         cn_set_error("cn_nat_attach_lm: an n-gram model is attached (cn_nat_attach_ngram); it and a TransformerLM cannot be fused together");
         return -1;
     }
-    if (lm->lib_tag != m->lib_tag) {
-        cn_set_error("cn_nat_attach_lm: the two handles come from different libraries");
-        return -1;
-    }
-    if (lm->cfg.ast != 2 || !lm->finalized) {
-        cn_set_error("cn_nat_attach_lm: the LM handle must be a finalized TransformerLM (cfg.ast = 2)");
-        return -1;
-    }
-    if (lm->cfg.vocab_size != m->cfg.vocab_size || lm->cfg.device != m->cfg.device) {
-        cn_set_error("cn_nat_attach_lm: the LM must have the decoder's vocabulary and device");
-        return -1;
-    }
+    CN_TRY(lm_check_pair(m, lm, "cn_nat_attach_lm"));
     m->ast_lm = lm;
     return 0;
 }
@@ -1113,18 +1102,7 @@ extern "C" int cn_ctc_beam_lm(cn_model* m, cn_model* lm, const float* feats_dev,
         cn_set_error("cn_ctc_beam_lm: needs decode options and all output buffers");
         return -1;
     }
-    if (!lm || lm->cfg.ast != 2 || !lm->finalized) {
-        cn_set_error("cn_ctc_beam_lm: the LM handle must be a finalized TransformerLM (cfg.ast = 2)");
-        return -1;
-    }
-    if (lm->lib_tag != m->lib_tag) {
-        cn_set_error("cn_ctc_beam_lm: the two handles come from different libraries");
-        return -1;
-    }
-    if (lm->cfg.vocab_size != m->cfg.vocab_size || lm->cfg.device != m->cfg.device) {
-        cn_set_error("cn_ctc_beam_lm: the LM must have the model's vocabulary and device");
-        return -1;
-    }
+    CN_TRY(lm_check_pair(m, lm, "cn_ctc_beam_lm"));
     const int V = m->cfg.vocab_size, blank = opts->padding_idx, sos = opts->sos;
     if (!(lm_weight == lm_weight) || blank < 0 || blank >= V || sos < 0 || sos >= V || sos == blank) {
         cn_set_error("cn_ctc_beam_lm: lm_weight must be a number; blank and sos two different ids of the vocabulary");

@@ -5,7 +5,7 @@
 // kernel gives every slot its bw best continuations, and one workgroup per utterance ranks the bw * bw candidates and writes
 // the next beam with the ancestor / key-mask tables the next LM step gathers through.  Nothing returns to the host inside
 // the loop: utterance b consumes steps 0 .. last[b] = min(ylen[b], ymax - 1), which the host knows before it starts.
-#include "kernels.h"
+#include "beam_core.h"
 #include "rowreduce.h"
 
 // local_prob = att_prob + lm_weight * lm_prob; torch.topk(local_prob, beam_width) (cassnat.py:606-611).  One workgroup per
@@ -63,14 +63,7 @@ __global__ void nat_beam_init_kernel(NatBeamState st, const int* __restrict__ yl
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= B * bw) return;
     const int b = s / bw;
-    for (int p = 0; p < 2; ++p) {
-        for (int t = 0; t < L; ++t) {
-            st.tok[p][(long long)s * L + t] = t == 0 ? sos : pad;
-            st.anc[p][(long long)s * L + t] = s;
-            st.keyok[p][(long long)s * L + t] = (t == 0 && sos != pad) ? 1 : 0;
-        }
-        st.score[p][s] = 0.0;
-    }
+    for (int p = 0; p < 2; ++p) beam_init_row(st, p, s, L, sos, pad);
     st.cur_tok[s] = sos;
     const int l = ylen[b] < ymax - 1 ? ylen[b] : ymax - 1;
     if (s == b * bw) last[b] = l;
@@ -106,33 +99,19 @@ __global__ __launch_bounds__(NAT_MAXC) void nat_beam_update_kernel(NatBeamState 
         const long long c = (long long)s * bw + (tid - (tid / bw) * bw);
         const double sc = st.score[cur][s] + (double)q.val[c];
         cscore[tid] = sc;
-        ckey[tid] = q.use_lp ? sc + cn_mul_rn((double)(q.step + 1), q.lp) : sc;
+        ckey[tid] = beam_key(sc, q.step + 1, q.lp, q.use_lp);
         ctok[tid] = q.idx[c];
     }
     __syncthreads();
     if (tid < ncand) {
-        const double k = ckey[tid];
-        int r = 0;
-        for (int e = 0; e < ncand; ++e) r += (ckey[e] > k) || (ckey[e] == k && e < tid);
+        const int r = beam_rank(ckey, ncand, tid);
         if (r < bw) newslot[r] = tid;
     }
     __syncthreads();
     for (int qn = 0; qn < bw; ++qn) {
         const int e = newslot[qn];
         const int so = b * bw + e / bw, sn = b * bw + qn;
-        for (int t = tid; t < L; t += NAT_MAXC) {
-            int tk = st.tok[cur][(long long)so * L + t], an = st.anc[cur][(long long)so * L + t];
-            unsigned char ko = st.keyok[cur][(long long)so * L + t];
-            if (t == q.step + 1) {
-                tk = ctok[e];
-                ko = ctok[e] != q.pad;  // tgt_mask = (ys != padding_idx): a blank inside the prefix is masked for later positions
-                an = sn;                // the next position will be computed in this slot
-            }
-            if (t == q.step) an = so;   // position `step` was computed in the parent's slot this step
-            st.tok[nxt][(long long)sn * L + t] = tk;
-            st.anc[nxt][(long long)sn * L + t] = an;
-            st.keyok[nxt][(long long)sn * L + t] = ko;
-        }
+        beam_write_row(st, cur, L, so, sn, true, q.step + 1, q.step, ctok[e], q.pad, tid, NAT_MAXC);  // (every candidate grows)
         if (tid == 0) {
             st.score[nxt][sn] = cscore[e];
             st.cur_tok[sn] = ctok[e];

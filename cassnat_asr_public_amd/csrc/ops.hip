@@ -908,24 +908,46 @@ extern "C" int cn_op_logsoftmax_gather(const float* logits, int32_t M, int32_t V
 }
 
 // ---- kernel-test entries of the AST beam search's step kernels (ast.hip)
+// what the two gather-attention entries share: the precision, the common shape checks (min_ldq: 3d behind the fused Q | K | V
+// projection, d for plain queries; `keys`: the entry's name of its key count) and the common fields of the arguments
+static int gather_args_of(GatherArgs& a, int32_t& precision, const char* who, const char* keys, int32_t nkeys, int32_t min_ldq,
+                          const void* q, int32_t ldq, void* k, void* v, void* o, int32_t ldo, int32_t n, int32_t H, int32_t d,
+                          int32_t table_stride, float scale) {
+    if ((precision = cn_own_precision(precision, who)) < 0) return -1;
+    if (precision != CN_PREC_F32 && precision != CN_PREC_BF16 && precision != CN_PREC_X3) {
+        cn_set_error(std::string(who) + ": precision must be F32, BF16 (F16 in the half-precision build) or BF16X3");
+        return -1;
+    }
+    if (n < 0 || H < 1 || H > 16 || d != 64 * H || nkeys < 1 || ldo < d || ldq < min_ldq || !q || !k || !v || (n > 0 && !o)) {
+        cn_set_error(std::string(who) + ": need 1 <= H <= 16, d = 64 * H, " + keys + " >= 1, ldo >= d, ldq >= " +
+                     (min_ldq == d ? "d" : "3d") + " and the q / k / v / o arrays");
+        return -1;
+    }
+    a.q = q;
+    a.ldq = ldq;
+    a.k = k;
+    a.v = v;
+    a.o = o;
+    a.ldo = ldo;
+    a.n = n;
+    a.H = H;
+    a.d = d;
+    a.table_stride = table_stride;
+    a.scale = scale;
+    return 0;
+}
+
 extern "C" int cn_op_ast_gather_attn(int32_t precision, int32_t mode, const void* q, int32_t ldq, void* k, void* v, void* o,
                                      int32_t ldo, int32_t n, int32_t H, int32_t nkeys, int32_t slots, int32_t d, int32_t table_stride,
                                      const int32_t* anc, const uint8_t* keyok, const int32_t* utt, const uint8_t* keymask, float scale,
                                      int32_t append_pos, void* stream) {
-    if ((precision = cn_own_precision(precision, "cn_op_ast_gather_attn")) < 0) return -1;
-    if (precision != CN_PREC_F32 && precision != CN_PREC_BF16 && precision != CN_PREC_X3) {
-        cn_set_error("cn_op_ast_gather_attn: precision must be F32, BF16 (F16 in the half-precision build) or BF16X3");
-        return -1;
-    }
     if (mode != 0 && mode != 1) {
         cn_set_error("cn_op_ast_gather_attn: mode must be 0 (cache) or 1 (source memory)");
         return -1;
     }
-    if (n < 0 || H < 1 || H > 16 || d != 64 * H || nkeys < 1 || ldo < d || ldq < (mode == 0 ? 3 * d : d) || !q || !k || !v ||
-        (n > 0 && !o)) {
-        cn_set_error("cn_op_ast_gather_attn: need 1 <= H <= 16, d = 64 * H, nkeys >= 1, ldo >= d and ldq >= 3d (mode 0) / d (mode 1)");
-        return -1;
-    }
+    GatherAttnArgs a;
+    CN_TRY(gather_args_of(a, precision, "cn_op_ast_gather_attn", "nkeys", nkeys, mode == 0 ? 3 * d : d, q, ldq, k, v, o, ldo, n, H, d,
+                          table_stride, scale));
     if (mode == 0 && (slots < n || table_stride < nkeys || append_pos < -1 || append_pos >= nkeys || !anc || !keyok)) {
         cn_set_error("cn_op_ast_gather_attn: mode 0 needs slots >= n, table_stride >= nkeys, -1 <= append_pos < nkeys, anc and keyok");
         return -1;
@@ -934,24 +956,12 @@ extern "C" int cn_op_ast_gather_attn(int32_t precision, int32_t mode, const void
         cn_set_error("cn_op_ast_gather_attn: mode 1 needs utt and keymask");
         return -1;
     }
-    GatherAttnArgs a;
-    a.q = q;
-    a.ldq = ldq;
-    a.k = k;
-    a.v = v;
-    a.o = o;
-    a.ldo = ldo;
-    a.n = n;
-    a.H = H;
     a.nkeys = nkeys;
     a.slots = slots;
-    a.d = d;
-    a.table_stride = table_stride;
     a.anc = anc;
     a.keyok = keyok;
     a.utt = utt;
     a.keymask = keymask;
-    a.scale = scale;
     a.append_pos = mode == 0 ? append_pos : -1;
     return launch_ast_gather_attn(precision, mode, a, (hipStream_t)stream);
 }
@@ -959,35 +969,17 @@ extern "C" int cn_op_ast_gather_attn(int32_t precision, int32_t mode, const void
 extern "C" int cn_op_ast_gather_attn_rows(int32_t precision, const void* q, int32_t ldq, void* k, void* v, void* o, int32_t ldo, int32_t n,
                                           int32_t H, int32_t d, int32_t table_stride, int32_t max_keys, const int32_t* rowid,
                                           const int32_t* pos, const int32_t* stay, float scale, void* stream) {
-    if ((precision = cn_own_precision(precision, "cn_op_ast_gather_attn_rows")) < 0) return -1;
-    if (precision != CN_PREC_F32 && precision != CN_PREC_BF16 && precision != CN_PREC_X3) {
-        cn_set_error("cn_op_ast_gather_attn_rows: precision must be F32, BF16 (F16 in the half-precision build) or BF16X3");
-        return -1;
-    }
-    if (n < 0 || H < 1 || H > 16 || d != 64 * H || max_keys < 1 || ldo < d || ldq < 3 * d || !q || !k || !v || (n > 0 && !o)) {
-        cn_set_error("cn_op_ast_gather_attn_rows: need 1 <= H <= 16, d = 64 * H, max_keys >= 1, ldo >= d and ldq >= 3d");
-        return -1;
-    }
+    GatherRowsArgs a;
+    CN_TRY(gather_args_of(a, precision, "cn_op_ast_gather_attn_rows", "max_keys", max_keys, 3 * d, q, ldq, k, v, o, ldo, n, H, d,
+                          table_stride, scale));
     if (table_stride < max_keys || !rowid || !pos || !stay) {
         cn_set_error("cn_op_ast_gather_attn_rows: need table_stride >= max_keys and the rowid, pos and stay tables");
         return -1;
     }
-    GatherRowsArgs a;
-    a.q = q;
-    a.ldq = ldq;
-    a.k = k;
-    a.v = v;
-    a.o = o;
-    a.ldo = ldo;
-    a.n = n;
-    a.H = H;
-    a.d = d;
-    a.table_stride = table_stride;
     a.max_keys = max_keys;
     a.rowid = rowid;
     a.pos = pos;
     a.stay = stay;
-    a.scale = scale;
     return launch_ast_gather_attn_rows(precision, a, (hipStream_t)stream);
 }
 
@@ -1028,15 +1020,13 @@ extern "C" int cn_op_ast_ctc_prefix(const float* logp, const float* r0, const fl
     return launch_ast_ctc_prefix(a, (hipStream_t)stream);
 }
 
-static int ast_beam_state_of(AstBeamState& st, int32_t* tok0, int32_t* tok1, int32_t* anc0, int32_t* anc1, uint8_t* keyok0,
-                             uint8_t* keyok1, int32_t* len0, int32_t* len1, double* score0, double* score1, int32_t* valid0,
-                             int32_t* valid1, int32_t* ctc_ref0, int32_t* ctc_ref1, float* ctc_prev0, float* ctc_prev1, int32_t* cur_tok,
-                             int32_t* utt, int32_t* live, const char* who) {
-    const void* all[] = {tok0, tok1, anc0, anc1, keyok0, keyok1, len0, len1, score0, score1, valid0, valid1, ctc_ref0, ctc_ref1,
-                         ctc_prev0, ctc_prev1, cur_tok, utt, live};
+// the nine arrays every token-level beam keeps (kernels.h: BeamTables); a null one is refused with the entry's own words
+static int beam_tables_of(BeamTables& st, int32_t* tok0, int32_t* tok1, int32_t* anc0, int32_t* anc1, uint8_t* keyok0, uint8_t* keyok1,
+                          double* score0, double* score1, int32_t* cur_tok, const std::string& null_error) {
+    const void* all[] = {tok0, tok1, anc0, anc1, keyok0, keyok1, score0, score1, cur_tok};
     for (const void* ptr : all)
         if (!ptr) {
-            cn_set_error(std::string(who) + ": null state array");
+            cn_set_error(null_error);
             return -1;
         }
     st.tok[0] = tok0;
@@ -1045,17 +1035,32 @@ static int ast_beam_state_of(AstBeamState& st, int32_t* tok0, int32_t* tok1, int
     st.anc[1] = anc1;
     st.keyok[0] = keyok0;
     st.keyok[1] = keyok1;
-    st.len[0] = len0;
-    st.len[1] = len1;
     st.score[0] = score0;
     st.score[1] = score1;
+    st.cur_tok = cur_tok;
+    return 0;
+}
+
+static int ast_beam_state_of(AstBeamState& st, int32_t* tok0, int32_t* tok1, int32_t* anc0, int32_t* anc1, uint8_t* keyok0,
+                             uint8_t* keyok1, int32_t* len0, int32_t* len1, double* score0, double* score1, int32_t* valid0,
+                             int32_t* valid1, int32_t* ctc_ref0, int32_t* ctc_ref1, float* ctc_prev0, float* ctc_prev1, int32_t* cur_tok,
+                             int32_t* utt, int32_t* live, const char* who) {
+    const std::string null_error = std::string(who) + ": null state array";
+    CN_TRY(beam_tables_of(st, tok0, tok1, anc0, anc1, keyok0, keyok1, score0, score1, cur_tok, null_error));
+    const void* all[] = {len0, len1, valid0, valid1, ctc_ref0, ctc_ref1, ctc_prev0, ctc_prev1, utt, live};
+    for (const void* ptr : all)
+        if (!ptr) {
+            cn_set_error(null_error);
+            return -1;
+        }
+    st.len[0] = len0;
+    st.len[1] = len1;
     st.valid[0] = valid0;
     st.valid[1] = valid1;
     st.ctc_ref[0] = ctc_ref0;
     st.ctc_ref[1] = ctc_ref1;
     st.ctc_prev[0] = ctc_prev0;
     st.ctc_prev[1] = ctc_prev1;
-    st.cur_tok = cur_tok;
     st.utt = utt;
     st.live = live;
     return 0;
@@ -1140,22 +1145,12 @@ extern "C" int cn_op_nat_beam_update(int32_t* tok0, int32_t* tok1, int32_t* anc0
                                      double* score0, double* score1, int32_t* cur_tok, const int32_t* idx, const float* val,
                                      const int32_t* last, int32_t cur, int32_t step, int32_t bw, int32_t L, int32_t pad, int32_t use_lp,
                                      double lp, int32_t B, void* stream) {
-    const void* all[] = {tok0, tok1, anc0, anc1, keyok0, keyok1, score0, score1, cur_tok, idx, val, last};
-    for (const void* ptr : all)
-        if (!ptr) {
-            cn_set_error("cn_op_nat_beam_update: null array");
-            return -1;
-        }
     NatBeamState st;
-    st.tok[0] = tok0;
-    st.tok[1] = tok1;
-    st.anc[0] = anc0;
-    st.anc[1] = anc1;
-    st.keyok[0] = keyok0;
-    st.keyok[1] = keyok1;
-    st.score[0] = score0;
-    st.score[1] = score1;
-    st.cur_tok = cur_tok;
+    CN_TRY(beam_tables_of(st, tok0, tok1, anc0, anc1, keyok0, keyok1, score0, score1, cur_tok, "cn_op_nat_beam_update: null array"));
+    if (!idx || !val || !last) {
+        cn_set_error("cn_op_nat_beam_update: null array");
+        return -1;
+    }
     NatBeamStep q;
     q.idx = idx;
     q.val = val;
