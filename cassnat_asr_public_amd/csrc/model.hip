@@ -713,7 +713,7 @@ extern "C" int cn_ctc_beam(cn_model* m, const float* feats_dev, const float* siz
     hipStream_t s = (hipStream_t)stream;
     CtcBeamArgs a;
     CN_TRY(ctc_search_open(m, "cn_ctc_beam", feats_dev, size_ratio_dev, B, T, F, opts, beam, pruning, length_penalty,
-                           ctc_beam_out(hyp_out_dev, hyp_cap, hyp_len_dev, score_dev, nullptr, p_blk_dev, p_nblk_dev, nbeam_dev), false, true,
+                           ctc_beam_out(hyp_out_dev, hyp_cap, hyp_len_dev, score_dev, nullptr, p_blk_dev, p_nblk_dev, nbeam_dev), true, true,
                            &a, s));
     ProfScope ps(m, "ctc_prefix_beam", 0, (double)B * a.Tp * (pruning + 1) * 4, s);
     return launch_ctc_prefix_beam(a, s);

@@ -12,6 +12,7 @@
 #include "../../include/cassnat_hip.h"
 #include "../../include/cassnat_hip_attention_proj.h"
 #include "ctc_ngram_search.h"
+#include "ctc_times_search.h"
 #include "flac_decode.h"
 #include "kernels.h"
 
@@ -683,6 +684,27 @@ extern "C" int cn_op_ctc_viterbi(const float* logp, const uint8_t* keymask, cons
     v.bp = bp;
     v.out_path = out_path;
     return sc.finish(launch_ctc_viterbi(v, s));
+}
+
+// the forced alignment with spans and confidences on given log-posteriors (include/cassnat_hip_ctc_times.h; all pointers device)
+extern "C" int cn_op_ctc_token_times(const float* logp_dev, const int32_t* frames_dev, const int32_t* labels_dev, int32_t ld,
+                                     const int32_t* label_len_dev, int32_t B, int32_t Tp, int32_t V, int32_t blank, int64_t bp_lds_limit,
+                                     int32_t* start_dev, int32_t* end_dev, float* conf_dev, double* score_dev, int32_t* status_dev,
+                                     void* stream) {
+    CtcTimesArgs a;
+    a.logp = logp_dev, a.frames = frames_dev, a.labels = labels_dev, a.label_len = label_len_dev;
+    a.B = B, a.Tp = Tp, a.V = V, a.ld = ld, a.blank = blank;
+    a.start = start_dev, a.end = end_dev, a.conf = conf_dev, a.score = score_dev, a.status = status_dev;
+    const std::string bad = ct_check(a);  // (before the scratch is sized from these numbers)
+    if (!bad.empty()) {
+        cn_set_error("cn_op_ctc_token_times: " + bad);
+        return -1;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    Scratch sc("cn_op_ctc_token_times", s);
+    if (const size_t need = ct_scratch_bytes(B, Tp, ld, bp_lds_limit)) a.bp = (unsigned long long*)sc.alloc(need);
+    if (!sc.ok()) return -2;
+    return sc.finish(launch_ctc_token_times(a, bp_lds_limit, s));
 }
 
 extern "C" int cn_op_greedy_pack(const int32_t* tok, const float* val, const int32_t* ylen, int32_t B, int32_t U,

@@ -618,6 +618,28 @@ class Engine:
                                            _ptr(slm), _ptr(pb), _ptr(pnb), _ptr(nb), current_stream()), "cn_ctc_beam_ngram")
         return hyp, hlen, sc, slm, pb, pnb, nb
 
+    # ---- word / token time stamps: forced CTC alignment with spans and confidences (include/cassnat_hip_ctc_times.h)
+    def ctc_token_times(self, feats, size_ratio, opts, labels, label_len):
+        """Forced CTC alignment of ``labels`` (B, ld) int32 (no sos / eos / blank; ``label_len`` (B,) int32 of them count) on this
+        engine's own log-posteriors of ``feats`` (``cn_ctc_token_times``: encoder + CTC head, then one launch) -> (start (B, ld) int32,
+        end (B, ld) int32 exclusive, conf_lp (B, ld) float32, score (B,) float64, status (B,) int32) as cuda tensors, in subsampled
+        frames; status 0 aligned, 1 no path, 2 a bad label.  ``size_ratio`` is not read (the valid frames are the key mask's)."""
+        import torch
+
+        B, T, F = feats.shape
+        dev = feats.device
+        labels = labels.to(dev, torch.int32).contiguous()
+        label_len = label_len.to(dev, torch.int32).contiguous()
+        ld = labels.shape[1]
+        start = torch.full((B, ld), -1, dtype=torch.int32, device=dev)
+        end = torch.full((B, ld), -1, dtype=torch.int32, device=dev)
+        conf = torch.zeros(B, ld, dtype=torch.float32, device=dev)
+        score = torch.empty(B, dtype=torch.float64, device=dev)
+        status = torch.empty(B, dtype=torch.int32, device=dev)
+        self._chk(self.L.cn_ctc_token_times(self.handle, _ptr(feats), _ptr(size_ratio), B, T, F, C.byref(opts), _ptr(labels), ld, _ptr(label_len),
+                                            _ptr(start), _ptr(end), _ptr(conf), _ptr(score), _ptr(status), current_stream()), "cn_ctc_token_times")
+        return start, end, conf, score, status
+
     def lm_step_rows(self, max_pos, tok, pos, stay, rowid, logp):
         self._chk(self.L.cn_lm_step_rows(self.handle, tok.shape[0], int(max_pos), _ptr(tok), _ptr(pos), _ptr(stay), _ptr(rowid),
                                          rowid.shape[1], _ptr(logp), current_stream()), "cn_lm_step_rows")

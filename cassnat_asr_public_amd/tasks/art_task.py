@@ -26,7 +26,7 @@ import torch.distributed as dist
 from .. import dist as cdist
 from ..data.vocab import Vocab
 from ..models import make_conformer, make_transformer
-from ..utils import util
+from ..utils import ctm, util
 from ..utils.beam_decode import ctc_beam_decode
 from .base_task import BaseTask
 from .cassnat_task import _is_arpa, hyp_to_words
@@ -178,6 +178,10 @@ class ArtTask(BaseTask):
                                                            lm_engine=lm_engines[k])
                         lines = [utt + " " + " ".join(hyp_to_words(seqs[0]["hyp"], self.vocab, args.padding_idx))
                                  for utt, seqs in zip(utt_list, recog)]
+                        if getattr(args, "hip_ctm", ""):  # (on this worker's engine and stream, a second encoder pass: utils.ctm)
+                            times = ctm.align_batch(self.model, feats, feat_sizes, args, [seqs[0]["hyp"] for seqs in recog], self.vocab,
+                                                    engine=engines[k])
+                            lines = list(zip(lines, times))
                         with cv:
                             done[i] = lines
                             cv.notify_all()
@@ -191,7 +195,7 @@ class ArtTask(BaseTask):
         for t in threads:
             t.start()
         i = -1
-        results = {}
+        results, times = {}, {}
         for i in range(len(self.test_loader)):
             with cv:
                 while i not in done and not err:
@@ -200,6 +204,9 @@ class ArtTask(BaseTask):
                     raise err[0]
                 lines = done.pop(i)
             for line in lines:
+                if isinstance(line, tuple):  # (--hip_ctm: the line and the utterance's time record)
+                    line, rec = line
+                    times[line.split(" ", 1)[0]] = rec
                 results[line.split(" ", 1)[0]] = line
             batch_time.update(time.time() - end)
             end = time.time()
@@ -215,9 +222,16 @@ class ArtTask(BaseTask):
             gathered = [None] * self.world
             dist.all_gather_object(gathered, results)
             results = {k: v for part in gathered for k, v in part.items()}
+            if getattr(args, "hip_ctm", ""):
+                gathered = [None] * self.world
+                dist.all_gather_object(gathered, times)
+                times = {k: v for part in gathered for k, v in part.items()}
         if self.rank == 0:
             order = [line.split()[0] for line in open(args.test_paths[0]["scp_path"]) if line.strip()]
             with open(args.result_file, "w") as out_file:
                 for utt in order:
                     print(results[utt], flush=True, file=out_file)
+            if getattr(args, "hip_ctm", ""):
+                missed = ctm.write(args.hip_ctm, order, times, ctm.seconds_per_frame(args), ctm.unit_of(args, self.vocab))
+                print("CTM: %d of %d utterances could not be aligned (their units share the frames evenly, confidence 0)" % (missed, len(order)))
         return 0

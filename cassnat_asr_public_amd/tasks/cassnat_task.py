@@ -16,7 +16,7 @@ import torch.distributed as dist
 from .. import dist as cdist
 from ..data.vocab import Vocab
 from ..models import make_cassnat_model
-from ..utils import util
+from ..utils import ctm, util
 from ..utils.beam_decode import ctc_beam_decode
 from .base_task import BaseTask
 
@@ -216,9 +216,12 @@ class CassNATTask(BaseTask):
                 else:
                     recog, args = self.model.beam_decode(feats, src_mask, feat_sizes, self.vocab, args, self.lm_model,
                                                          labels=labels, label_sizes=label_sizes)
-                for utt, seqs, lab in zip(utt_list, recog, labels):
+                # --hip_ctm: the best hypotheses force-aligned to the CTC log-posteriors of a second encoder pass (utils.ctm)
+                times = (ctm.align_batch(self.model, feats, feat_sizes, args, [seqs[0]["hyp"] for seqs in recog], self.vocab)
+                         if getattr(args, "hip_ctm", "") else [None] * len(utt_list))
+                for utt, seqs, lab, rec in zip(utt_list, recog, labels, times):
                     # utt2diff as the reference computes it (cassnat_task.py:358-360): against the PADDED label row's width
-                    results[utt] = (hyp_to_words(seqs[0]["hyp"], self.vocab, args.padding_idx), len(seqs[0]["hyp"]) - len(lab))
+                    results[utt] = (hyp_to_words(seqs[0]["hyp"], self.vocab, args.padding_idx), len(seqs[0]["hyp"]) - len(lab), rec)
                 batch_time.update(time.time() - end)
                 end = time.time()
                 if i % args.print_freq == 0 and self.rank == 0:
@@ -387,11 +390,12 @@ class CassNATTask(BaseTask):
         batch_time = util.AverageMeter("Time", ":6.3f")
         progress = util.ProgressMeter(len(self.test_loader), batch_time)
         results = {}
-        # args.hip_pipelines (default 2; 1 = the plain loop): beam search, ESA, LM fusion and capture runs keep the plain loop
+        # args.hip_pipelines (default 2; 1 = the plain loop): beam search, ESA, LM fusion, capture runs and --hip_ctm keep the plain loop
         # (beam_width 1 with lm_weight > 0 is not the greedy finish: every step takes the arg-max of the FUSED row)
         n_pipes = int(getattr(args, "hip_pipelines", 2))
         plain_greedy = (args.beam_width == 1 and getattr(args, "sample_num", 0) <= 1 and not getattr(args, "hip_capture", False)
-                        and args.decode_type == "att_only" and not getattr(args, "lm_weight", 0) > 0)
+                        and args.decode_type == "att_only" and not getattr(args, "lm_weight", 0) > 0
+                        and not getattr(args, "hip_ctm", ""))
         # Both branches issue the same collectives (one weight broadcast; the result gather below), and the choice is made from
         # rank-invariant data: the snake deal can leave ranks with batch counts that differ by one.
         n_batches = len(self.test_loader)
@@ -426,5 +430,9 @@ class CassNATTask(BaseTask):
                 with open(os.path.join(os.path.dirname(args.result_file), "utt2diff"), "w") as f:
                     for utt in order:
                         print(utt + " " + str(max(-3, min(3, results[utt][1]))), file=f)
+            if getattr(args, "hip_ctm", ""):
+                missed = ctm.write(args.hip_ctm, order, {utt: results[utt][2] for utt in order}, ctm.seconds_per_frame(args),
+                                   ctm.unit_of(args, self.vocab))
+                print("CTM: %d of %d utterances could not be aligned (their units share the frames evenly, confidence 0)" % (missed, len(order)))
         self.decoded_frames = frames
         return 0

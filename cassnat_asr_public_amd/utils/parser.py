@@ -62,6 +62,15 @@ class DecodeParser(object):
                             "use-power, use-log-fbank).  Default: the built-in options, which are those of the reference's conf/fbank.conf "
                             "(hamming window, 16 kHz, 80 mel bins, no energy).  Dither is not implemented: an absent --dither means 0 "
                             "(Kaldi's default of 1.0 adds noise that cannot be compared), a non-zero one is refused")
+        p.add_argument("--hip_ctm", default="", type=str,
+                       help="also write a CTM file (UTT 1 START DUR WORD CONF): the best hypothesis of every utterance is force-aligned "
+                            "to the model's own CTC log-posteriors on the device, word times from the pieces' spans, confidence = exp of "
+                            "the smallest piece confidence.  Seconds per subsampled frame = 4 * skip_frame * frame shift (--hip_fbank_conf's, "
+                            "else 10 ms); no receptive-field offset.  --task cassnat then keeps the plain loop (like beam search, ESA, LM "
+                            "fusion and capture runs: the pipelined greedy path writes no time stamps); the result file does not change")
+        p.add_argument("--hip_ctm_unit", default="word", choices=["word", "token"],
+                       help="--hip_ctm: word (default; pieces that begin with the separator start a word, a vocabulary without such "
+                            "pieces is written per token) or token (one line per piece)")
         p.add_argument("--hip_dist_backend", default="nccl", choices=["nccl", "gloo"],
                        help="torch.distributed backend under torch.distributed.run (nccl = RCCL over xGMI; gloo: rehearsal of the "
                             "N-rank path, also with several ranks on one GPU)")
