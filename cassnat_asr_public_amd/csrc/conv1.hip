@@ -67,7 +67,8 @@ __global__ __launch_bounds__(256) void conv1_kernel(const float* __restrict__ x,
             T* dst = orow + (long long)fp * C;
             const bool cell_in = row_in && f1 >= 0 && f1 < F1;
             if (!cell_in) {  // border cell (bordered images only), or a row past the utterance's own batch (written as zeros)
-                if (skip_border && !past_own) continue;
+                // (halo mode 2 leaves every border cell alone, the two at the ends of a row past the own batch included)
+                if (skip_border && !(past_own && f1 >= 0 && f1 < F1)) continue;
                 if constexpr (sizeof(T) == 1) {  // e4m3fn image: 8 channels = 8 bytes
                     *reinterpret_cast<uint2*>(dst) = make_uint2(0, 0);
                 } else if constexpr (sizeof(T) == 2) {
@@ -450,7 +451,20 @@ int launch_conv1_f8(const float* x, const float* w9c, const float* bias, void* o
         return -1;
     }
     static const bool no_mfma = cn_exp_env("CASSNAT_CONV1_F8_VALU") != nullptr;
-    if (conv1_mfma_applies(C, F1) && !no_mfma) return launch_conv1_mfma(true, x, w9c, bias, out8, B, T, F, T1, F1, scale, s, utt_meta);
+    return launch_conv1_f8_form(conv1_mfma_applies(C, F1) && !no_mfma, x, w9c, bias, out8, B, T, F, T1, F1, C, halo, scale, s, utt_meta);
+}
+
+// one of the two kernels behind launch_conv1_f8 by name (mfma: conv1_mfma_shape_ok must hold; it writes its border always)
+bool conv1_mfma_shape_ok(int C, int F1) { return conv1_mfma_applies(C, F1); }
+int launch_conv1_f8_form(bool mfma, const float* x, const float* w9c, const float* bias, void* out8, int B, int T, int F, int T1, int F1,
+                         int C, int halo, float scale, hipStream_t s, const UttMeta* utt_meta) {
+    if (mfma) {
+        if (!conv1_mfma_applies(C, F1)) {
+            cn_set_error("conv1 (matrix-core form): 256 channels and at least 30 feature columns after the stride");
+            return -1;
+        }
+        return launch_conv1_mfma(true, x, w9c, bias, out8, B, T, F, T1, F1, scale, s, utt_meta);
+    }
     long long blocks = (long long)B * (T1 + 2);
     if (blocks > 256 * 8) blocks = 256 * 8;
     if (blocks < 1) blocks = 1;

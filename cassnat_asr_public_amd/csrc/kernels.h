@@ -63,6 +63,11 @@ int launch_conv1_mixplanes(const float* x, const float* w9c, const float* bias, 
                            int halo, float scale_l, float scale_q, hipStream_t s, const UttMeta* utt_meta = nullptr);
 int launch_conv1_f8(const float* x, const float* w9c, const float* bias, void* out8, int B, int T, int F, int T1, int F1, int C,
                     int halo, float scale, hipStream_t s, const UttMeta* utt_meta = nullptr);
+// the two kernels launch_conv1_f8 chooses between, by name (test entry): the VALU kernel, or the matrix-core kernel (256 channels,
+// 32 <= F1 + 2 <= 65: conv1_mfma_shape_ok; it writes its border always)
+bool conv1_mfma_shape_ok(int C, int F1);
+int launch_conv1_f8_form(bool mfma, const float* x, const float* w9c, const float* bias, void* out8, int B, int T, int F, int T1, int F1,
+                         int C, int halo, float scale, hipStream_t s, const UttMeta* utt_meta = nullptr);
 // bf16 engine: the bordered bf16 image on the matrix cores (the e4m3 form's kernel with 512-byte cells); C == 256, F1 + 2 >= 32
 bool conv1_bordered_bf16_applies(int C, int F1);
 int launch_conv1_bordered_bf16(const float* x, const float* w9c, const float* bias, void* out, int B, int T, int F, int T1, int F1,

@@ -381,6 +381,229 @@ extern "C" int cn_op_conv2(int32_t precision, const void* conv1_out, const void*
     return sc.finish(launch_gemm(precision, g, (hipStream_t)stream));
 }
 
+// host fp32 [rows][K] -> the elements of internal precision `prec` as the generic kernels read them (fp32 as it is, the 16-bit
+// operand, or split-bf16 rows: K % 32 == 0)
+static std::vector<unsigned char> host_elems(int prec, const float* w, size_t rows, size_t K) {
+    std::vector<unsigned char> out(rows * K * cn_elem_size(prec));
+    if (prec == CN_PREC_F32) {
+        std::memcpy(out.data(), w, out.size());
+    } else if (prec == CN_PREC_BF16) {
+        for (size_t i = 0; i < rows * K; ++i) {
+            const uint16_t v = cn_host_op16(w[i]);
+            std::memcpy(&out[2 * i], &v, 2);
+        }
+    } else {
+        for (size_t r = 0; r < rows; ++r)
+            for (size_t c = 0; c < K; ++c) {
+                const uint16_t hi = cn_host_op16(w[r * K + c]), lo = cn_host_op16(w[r * K + c] - cn_host_op16_value(hi));
+                std::memcpy(&out[r * K * 4 + cn_split_off(c)], &hi, 2);
+                std::memcpy(&out[r * K * 4 + cn_split_off(c) + 64], &lo, 2);
+            }
+    }
+    return out;
+}
+
+// Every launch form of the subsampling front end from one descriptor (include/cassnat_hip.h, cn_frontend_desc).  Everything that
+// would be refused is refused here, before the weights are packed and anything touches the device.
+extern "C" int cn_op_frontend_desc(const cn_frontend_desc* d, void* stream) {
+    const char* who = "cn_op_frontend_desc";
+    auto refuse = [&](const std::string& why) {
+        cn_set_error(std::string(who) + ": " + why);
+        return -1;
+    };
+    if (!d) return refuse("null descriptor");
+    const int c1 = d->conv1_form, c2 = d->conv2_form, ln = d->linear_form;
+    if (c1 < 0 || c1 > CN_FE_CONV1_BF16_MFMA || c2 < 0 || c2 > CN_FE_CONV2_F8 || ln < 0 || ln > CN_FE_LINEAR_F8) return refuse("unknown form");
+    if (!c1 && !c2 && !ln) return refuse("no stage selected");
+    const int prec = cn_own_precision(d->precision, who);
+    if (prec < 0) return -1;
+    if (prec != CN_PREC_F32 && prec != CN_PREC_BF16 && prec != CN_PREC_X3) return refuse("precision must be CN_PRECISION_F32, BF16, BF16X3 or F16");
+#ifdef CN_OP16_F16
+    if (c1 == CN_FE_CONV1_PLANES || c1 == CN_FE_CONV1_MIXPLANES || c1 == CN_FE_CONV1_F8_VALU || c1 == CN_FE_CONV1_F8_MFMA || c2 == CN_FE_CONV2_X3 ||
+        c2 == CN_FE_CONV2_MIX || c2 == CN_FE_CONV2_F8 || ln == CN_FE_LINEAR_F8)
+        return refuse("the half-precision library has no split-bf16, MIX or e4m3 form");
+#endif
+    const int B = d->B, T = d->T, F = d->F, C = d->C, halo = d->halo;
+    const int T1 = (T - 1) / 2 + 1, F1 = (F - 1) / 2 + 1, T2 = (T1 - 1) / 2 + 1, F2 = (F1 - 1) / 2 + 1;
+    const bool c1_16 = c1 == CN_FE_CONV1_BF16_MFMA || (c1 == CN_FE_CONV1_PLAIN && prec == CN_PREC_BF16);
+    if (c1 || c2) {
+        if (B < 1 || T < 1 || F < 1 || C < 8 || C % 8 != 0 || 256 % (C / 8) != 0)
+            return refuse("B, T, F >= 1 and a channel count that is a multiple of 8 with C / 8 dividing 256");
+        if ((long long)B * (T1 + 2) * (F1 + 2) * C >= (1ll << 31)) return refuse("image beyond 2^31 cells");
+        if (halo < 0 || halo > 2) return refuse("halo is 0, 1 or 2");
+        if (!d->img) return refuse("null img");
+    }
+    if (c1) {
+        if (!d->x || !d->w9c || !d->bias1) return refuse("conv1 needs x, w9c and bias1");
+        const bool mfma = c1 == CN_FE_CONV1_F8_MFMA || c1 == CN_FE_CONV1_BF16_MFMA;
+        if (mfma && !conv1_mfma_shape_ok(C, F1)) return refuse("the matrix-core conv1 forms need C == 256 and 32 <= F1 + 2 <= 65");
+        if (c1 == CN_FE_CONV1_BF16_MFMA && prec != CN_PREC_BF16) return refuse("the 16-bit matrix-core conv1 form needs the 16-bit precision");
+        if (mfma && halo != 1) return refuse("halo 0 / 2 on a matrix-core conv1 form: it writes its border always (halo == 1)");
+        if (c1 != CN_FE_CONV1_PLAIN && halo == 0) return refuse("halo 0 on a conv1 form whose image is always bordered");
+        if (c1 == CN_FE_CONV1_PLAIN && prec == CN_PREC_X3 && (halo || C % 32 != 0))
+            return refuse("the plain split-bf16 image (X3 precision) has no halo form and needs C % 32 == 0");
+        if ((c1 == CN_FE_CONV1_F8_VALU || c1 == CN_FE_CONV1_F8_MFMA || c1 == CN_FE_CONV1_MIXPLANES) && !(d->img_scale > 0.f))
+            return refuse("img_scale must be positive");
+        if (c1 == CN_FE_CONV1_MIXPLANES && !(d->img_scale2 > 0.f)) return refuse("img_scale2 must be positive");
+        if (d->n_sub < 0 || d->n_sub > CN_MAX_SUB) return refuse("a rows list holds at most " + std::to_string(CN_MAX_SUB) + " batches");
+        if (d->n_sub > 0) {
+            if (!d->sub_rows || !d->sub_frames) return refuse("n_sub > 0 needs sub_rows and sub_frames");
+            long long sum = 0;
+            for (int k = 0; k < d->n_sub; ++k) {
+                if (d->sub_rows[k] < 1 || d->sub_frames[k] < 1 || d->sub_frames[k] > T) return refuse("a batch needs rows >= 1 and 1 <= frames <= T");
+                sum += d->sub_rows[k];
+            }
+            if (sum != B) return refuse("the rows list sums to " + std::to_string(sum) + ", not to B = " + std::to_string(B));
+        }
+    }
+    if (c2) {
+        if (!d->w2 || !d->bias2 || !d->c2_out) return refuse("conv2 needs w2, bias2 and c2_out");
+        if (c2 == CN_FE_CONV2_GENERIC && halo && !conv2_dma_applies(prec, C, C))
+            return refuse("a bordered image is read by the 16-bit 256-channel tile kernel only (generic conv2: halo 0)");
+        if (c2 == CN_FE_CONV2_GENERIC && prec == CN_PREC_X3 && C % 32 != 0) return refuse("split-bf16 rows need C % 32 == 0");
+        if (c2 == CN_FE_CONV2_DMA && !conv2_dma_applies(prec, C, C)) return refuse("the LDS-DMA conv2 form needs the 16-bit precision and C == 256");
+        if (c2 == CN_FE_CONV2_X3 && !conv2_x3_applies(CN_PREC_X3, C, C)) return refuse("the X3 conv2 form needs C == 256");
+        if (c2 == CN_FE_CONV2_MIX && !conv2_mix_applies(CN_PREC_X3, C, C)) return refuse("the MIX conv2 form needs C == 256");
+        if (c2 == CN_FE_CONV2_F8 && !conv2_f8_applies(C, C)) return refuse("the e4m3 conv2 form needs C == 256");
+        if (c2 != CN_FE_CONV2_GENERIC && halo == 0) return refuse("halo 0 on a conv2 tile form: it reads a bordered image");
+        if (c2 == CN_FE_CONV2_F8 && (!(d->img_scale > 0.f) || d->out8_scale < 0.f)) return refuse("img_scale must be positive, out8_scale >= 0");
+        if (c1) {  // what conv1 writes is what conv2 reads
+            const bool fits = ((c2 == CN_FE_CONV2_GENERIC && halo == 0) && c1 == CN_FE_CONV1_PLAIN) ||
+                              ((c2 == CN_FE_CONV2_DMA || (c2 == CN_FE_CONV2_GENERIC && halo)) && c1_16) ||
+                              (c2 == CN_FE_CONV2_X3 && c1 == CN_FE_CONV1_PLANES) || (c2 == CN_FE_CONV2_MIX && c1 == CN_FE_CONV1_MIXPLANES) ||
+                              (c2 == CN_FE_CONV2_F8 && (c1 == CN_FE_CONV1_F8_VALU || c1 == CN_FE_CONV1_F8_MFMA));
+            if (!fits) return refuse("this conv2 form does not read the image this conv1 form writes");
+        }
+    }
+    if (ln) {
+        const int M = d->M, K = d->K;
+        if (!d->lin_a || !d->lin_w || !d->lin_bias || !d->lin_out) return refuse("linear needs lin_a, lin_w, lin_bias and lin_out");
+        if (M < 1 || K < 1 || d->lda < K || d->pe_period < 1) return refuse("linear needs M, K >= 1, lda >= K and pe_period >= 1");
+        if (ln == CN_FE_LINEAR_DMA && !linear256_dma_applies(prec, 256, K)) return refuse("the LDS-DMA linear form needs the 16-bit precision, K % 64 == 0 and K >= 128");
+        if (ln == CN_FE_LINEAR_DMA && d->lda % 8 != 0) return refuse("the LDS-DMA linear form needs 16-byte aligned rows (lda % 8 == 0)");
+        if (ln == CN_FE_LINEAR_F8 && (!linear256_f8_applies(256, K) || d->lda != K || !(d->a_scale > 0.f))) return refuse("the e4m3 linear form needs lda == K == 5120 and a positive a_scale");
+        if (ln == CN_FE_LINEAR_GENERIC && ((prec == CN_PREC_X3 && (K % 32 != 0 || d->lda % 32 != 0)) || K % 8 != 0 || d->lda % 8 != 0))
+            return refuse("the generic linear form needs K and lda multiples of 8 (split-bf16: of 32)");
+    }
+    // ---- pack
+    hipStream_t s = (hipStream_t)stream;
+    const size_t wn = (size_t)C * 9 * C;
+    std::vector<unsigned char> w2p, lwp;
+    int q2[4] = {0, 0, 0, 0}, ql[4] = {0, 0, 0, 0};
+    if (c2 == CN_FE_CONV2_GENERIC || c2 == CN_FE_CONV2_DMA) {
+        w2p = host_elems(prec, d->w2, C, (size_t)9 * C);
+    } else if (c2 == CN_FE_CONV2_X3) {  // two [C][9 C] planes: the hi halves, then the lo halves (weights.hip, put_hi_lo)
+        w2p.resize(4 * wn);
+        for (size_t e = 0; e < wn; ++e) {
+            const uint16_t hi = cn_host_op16(d->w2[e]), lo = cn_host_op16(d->w2[e] - cn_host_op16_value(hi));
+            std::memcpy(&w2p[2 * e], &hi, 2);
+            std::memcpy(&w2p[2 * wn + 2 * e], &lo, 2);
+        }
+    } else if (c2 == CN_FE_CONV2_MIX) {
+        w2p.resize(4 * wn);
+        pack_conv2_mix(d->w2, C, 9 * C, C, 1, w2p.data(), q2);
+    } else if (c2 == CN_FE_CONV2_F8) {
+        w2p.resize(wn);
+        const int lg = pack_conv2_f8(d->w2, C, 9 * C, C, 1, w2p.data());
+        q2[0] = 127 - lg;
+        q2[1] = 127 - (int)std::lround(std::log2(d->img_scale));
+    }
+    if (ln == CN_FE_LINEAR_F8) {
+        float mx = 0.f;
+        for (size_t i = 0; i < (size_t)256 * d->K; ++i) mx = std::max(mx, std::fabs(d->lin_w[i]));
+        const int lg = cn_e4m3_exp(mx);
+        lwp.resize((size_t)256 * d->K);
+        for (size_t i = 0; i < lwp.size(); ++i) lwp[i] = cn_f32_to_e4m3_host(d->lin_w[i] * std::ldexp(1.f, lg));
+        ql[0] = 127 - lg;
+        ql[1] = 127 - (int)std::lround(std::log2(d->a_scale));
+    } else if (ln) {
+        lwp = host_elems(prec, d->lin_w, 256, (size_t)d->K);
+    }
+    if (d->q8_out) {
+        std::memcpy(d->q8_out, q2, 16);
+        std::memcpy(d->q8_out + 4, ql, 16);
+    }
+    Scratch sc(who, s);
+    const unsigned char* dw2 = c2 ? (const unsigned char*)sc.upload(w2p.data(), w2p.size()) : nullptr;
+    const void* dlw = ln ? sc.upload(lwp.data(), lwp.size()) : nullptr;
+    const int* dq2 = c2 ? (const int*)sc.upload(q2, 16) : nullptr;
+    const int* dql = ln ? (const int*)sc.upload(ql, 16) : nullptr;
+    UttMeta* meta = (c1 && d->n_sub > 0) ? (UttMeta*)sc.alloc((size_t)B * sizeof(UttMeta)) : nullptr;
+    if (!sc.ok()) return -2;
+    // ---- launch
+    int rc = 0;
+    if (meta) {
+        SubList subs;
+        std::memset(&subs, 0, sizeof(subs));
+        subs.n = d->n_sub;
+        for (int k = 0; k < d->n_sub; ++k) {
+            subs.rows[k] = d->sub_rows[k];
+            subs.frames[k] = d->sub_frames[k];
+        }
+        rc = launch_expand_meta(subs, meta, B, s);
+        if (rc == 0 && d->meta_out) CN_HIP_CHECK(hipMemcpyAsync(d->meta_out, meta, (size_t)B * sizeof(UttMeta), hipMemcpyDeviceToDevice, s));
+    }
+    if (rc == 0 && c1 == CN_FE_CONV1_PLAIN) rc = launch_conv1(prec, d->x, d->w9c, d->bias1, d->img, B, T, F, T1, F1, C, halo, s, meta);
+    if (rc == 0 && c1 == CN_FE_CONV1_PLANES) rc = launch_conv1_planes(d->x, d->w9c, d->bias1, d->img, B, T, F, T1, F1, C, halo, s, meta);
+    if (rc == 0 && c1 == CN_FE_CONV1_MIXPLANES)
+        rc = launch_conv1_mixplanes(d->x, d->w9c, d->bias1, d->img, B, T, F, T1, F1, C, halo, d->img_scale, d->img_scale2, s, meta);
+    if (rc == 0 && (c1 == CN_FE_CONV1_F8_VALU || c1 == CN_FE_CONV1_F8_MFMA))
+        rc = launch_conv1_f8_form(c1 == CN_FE_CONV1_F8_MFMA, d->x, d->w9c, d->bias1, d->img, B, T, F, T1, F1, C, halo, d->img_scale, s, meta);
+    if (rc == 0 && c1 == CN_FE_CONV1_BF16_MFMA) rc = launch_conv1_bordered_bf16(d->x, d->w9c, d->bias1, d->img, B, T, F, T1, F1, C, s, meta);
+    if (rc == 0 && c2 == CN_FE_CONV2_GENERIC) {
+        GemmArgs g;
+        g.A = d->img;
+        g.conv_halo = halo ? 1 : 0;
+        g.W = dw2;
+        g.bias = d->bias2;
+        g.C = d->c2_out;
+        g.ldc = C;
+        g.M = B * T2 * F2;
+        g.N = C;
+        g.K = 9 * C;
+        g.epi = CN_EPI_RELU;
+        g.conv = 1;
+        g.cB = B;
+        g.cT1 = T1;
+        g.cF1 = F1;
+        g.cC = C;
+        g.cT2 = T2;
+        g.cF2 = F2;
+        rc = launch_gemm(prec, g, s);
+    }
+    if (rc == 0 && c2 == CN_FE_CONV2_DMA) rc = launch_conv2_dma(d->img, dw2, d->bias2, d->c2_out, B, T1, F1, T2, F2, s);
+    if (rc == 0 && c2 == CN_FE_CONV2_X3) {
+        const size_t plane = (size_t)B * (T1 + 2) * (F1 + 2) * C * 2;
+        rc = launch_conv2_x3(d->img, (const unsigned char*)d->img + plane, dw2, dw2 + 2 * wn, d->bias2, d->c2_out, B, T1, F1, T2, F2, s);
+    }
+    if (rc == 0 && c2 == CN_FE_CONV2_MIX) rc = launch_conv2_mix(d->img, dw2, dw2 + 2 * wn, dw2 + 3 * wn, dq2, d->bias2, d->c2_out, B, T1, F1, T2, F2, s);
+    if (rc == 0 && c2 == CN_FE_CONV2_F8) rc = launch_conv2_f8(d->img, dw2, dq2, d->bias2, d->c2_out, B, T1, F1, T2, F2, s, d->out8_scale);
+    if (rc == 0 && ln == CN_FE_LINEAR_GENERIC) {
+        GemmArgs g;
+        g.A = d->lin_a;
+        g.lda = d->lda;
+        g.W = dlw;
+        g.bias = d->lin_bias;
+        g.C = d->lin_out;
+        g.ldc = 256;
+        g.c_f32 = 1;
+        g.M = d->M;
+        g.N = 256;
+        g.K = d->K;
+        g.epi = CN_EPI_EMBED;
+        g.pe = d->pe;
+        g.pe_period = d->pe_period;
+        g.scale = d->scale;
+        rc = launch_gemm(prec, g, s);
+    }
+    if (rc == 0 && ln == CN_FE_LINEAR_DMA)
+        rc = launch_linear256_dma(d->lin_a, d->lda, dlw, d->lin_bias, d->lin_out, d->M, d->K, d->scale, d->pe, d->pe_period, s);
+    if (rc == 0 && ln == CN_FE_LINEAR_F8)
+        rc = launch_linear256_f8(d->lin_a, dlw, dql, d->lin_bias, d->lin_out, d->M, d->K, d->scale, d->pe, d->pe_period, s);
+    return sc.finish(rc);
+}
+extern "C" int32_t cn_frontend_desc_size(void) { return (int32_t)sizeof(cn_frontend_desc); }
+
 extern "C" int cn_op_layernorm(int32_t precision, const float* x, const float* a2, const float* b2, void* y, int32_t M,
                                int32_t d, float eps, void* stream) {
     if ((precision = cn_own_precision(precision, "cn_op_layernorm")) < 0) return -1;

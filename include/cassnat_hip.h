@@ -537,6 +537,73 @@ int cn_op_linear256_fp8(const void* a8_dev, const float* w_host, const float* bi
                         float a_scale, float out_scale, const float* pe_dev, int32_t pe_period, float* w_scale_out, void* stream);
 int cn_op_conv2(int32_t precision, const void* conv1_out, const void* w_khwc, const float* bias, void* out, int32_t B,
                 int32_t T1, int32_t F1, int32_t C, void* stream);
+/* Every launch form of the subsampling front end (csrc/conv1.hip, conv2.hip, gemm.hip; src/models/modules/embedding.py:102-119)
+ * from one descriptor - what the entries above cannot reach: per-utterance records of a merged pass, halo modes 1 and 2, each
+ * conv1 kernel by name, conv2's split-bf16 planes form, linear_out with a padded row stride.  A stage runs where its form is not 0;
+ * the stages run in the order conv1, conv2, linear and are independent but for the image.
+ *   precision  CN_PRECISION_F32 / BF16 / BF16X3 (libcassnat_hip.so) or F16 (libcassnat_hip_f16.so): the element type of the plain
+ *              conv1 form, of the generic conv2 and linear forms and of the 16-bit tile forms' operands
+ *   conv1      x [B][T][F] fp32, w9c [9][C] fp32 (tap-major), bias1 [C]: device.  The image `img` (device) is the CALLER's and is
+ *              NOT cleared: [B][T1][F1][C] elements (halo 0) or [B][T1+2][F1+2][C] (halo 1: the border zeros are written; halo 2:
+ *              they are there already - interior cells only, and the rows past an utterance's own batch).
+ *              T1 = (T-1)/2+1, F1 = (F-1)/2+1.  CN_FE_CONV1_PLAIN: the VALU kernel in `precision` (split-bf16: halo 0 only);
+ *              PLANES: bordered bf16 hi plane, then the lo plane; MIXPLANES: bordered half-precision hi values (2 bytes per cell),
+ *              then the bytes e4m3((v - hi) img_scale), then e4m3(v img_scale2); F8_VALU / F8_MFMA: bordered e4m3 bytes at
+ *              img_scale, from the VALU or the matrix-core kernel; BF16_MFMA: the bordered 16-bit image from the matrix-core kernel
+ *              (the two matrix-core forms: C == 256, 32 <= F1 + 2 <= 65; they write their border always: halo == 1).
+ *              n_sub > 0: sub_rows / sub_frames (HOST, n_sub <= 64 entries, rows summing to B, 1 <= frames <= T) are the batches
+ *              of a merged pass; the entry expands them on the device (launch_expand_meta) into B records {frames, tp, sub_lo,
+ *              sub_hi}, hands those to conv1 and copies them to meta_out (device, B x 4 int32; may be NULL).
+ *   conv2      reads `img` ([B][T1(+2)][F1(+2)][C] as above, from the conv1 stage or filled by the caller), w2 HOST fp32
+ *              [C][3][3][C] (k = (kh * 3 + kw) * C + ci) packed per call with the library's own packers, bias2 [C] device ->
+ *              c2_out [B * T2 * F2][C].  CN_FE_CONV2_GENERIC: launch_gemm's implicit GEMM as the engine calls it (halo 0: the
+ *              plain image in `precision`; halo != 0: the engine's bordered call, which the tile kernel takes); DMA: the tile
+ *              kernel on the bordered 16-bit image; X3: on the two bordered planes, split-bf16 rows out; MIX: on the three
+ *              planes, split-bf16 rows out; F8: on the bordered e4m3 image at img_scale, 16-bit rows out, or with out8_scale > 0
+ *              e4m3 bytes at that scale.  The tile forms need C == 256.
+ *   linear     lin_out fp32 [M][256] = (lin_a . lin_w^T + lin_bias) * scale + pe[m % pe_period] (pe may be NULL).  lin_a device
+ *              [M][lda] (CN_FE_LINEAR_F8: e4m3 bytes at a_scale, lda == K == 5120), lin_w HOST fp32 [256][K], lin_bias, pe
+ *              device.  GENERIC: launch_gemm with the embedding epilogue as the engine calls it; DMA: launch_linear256_dma.
+ *   q8_out     (HOST, 8 int32, may be NULL) the E8M0 scale bytes chosen: [0..3] conv2's (F8: {W, image}; MIX: {W_q, A_l, W_l,
+ *              A_q}), [4..7] linear's ({W, A}).
+ * Refused with a message that starts "cn_op_frontend_desc: ", before anything is packed or launched: a null descriptor; no stage;
+ * a form or precision this library does not have; a form whose shape rule fails; a halo the form does not have (0 on an
+ * always-bordered form, 2 on a form that writes its border always, any on the plain split-bf16 image); a conv2 form that does not
+ * read what the conv1 form writes; a rows list that does not sum to B, has more than 64 entries or frames outside 1 .. T.
+ * cn_frontend_desc_size() is sizeof(cn_frontend_desc). */
+enum { CN_FE_CONV1_PLAIN = 1, CN_FE_CONV1_PLANES = 2, CN_FE_CONV1_MIXPLANES = 3, CN_FE_CONV1_F8_VALU = 4, CN_FE_CONV1_F8_MFMA = 5,
+       CN_FE_CONV1_BF16_MFMA = 6 };
+enum { CN_FE_CONV2_GENERIC = 1, CN_FE_CONV2_DMA = 2, CN_FE_CONV2_X3 = 3, CN_FE_CONV2_MIX = 4, CN_FE_CONV2_F8 = 5 };
+enum { CN_FE_LINEAR_GENERIC = 1, CN_FE_LINEAR_DMA = 2, CN_FE_LINEAR_F8 = 3 };
+typedef struct cn_frontend_desc {
+    int32_t precision, conv1_form, conv2_form, linear_form;
+    const float* x;
+    const float* w9c;
+    const float* bias1;
+    int32_t B, T, F, C;
+    int32_t halo, n_sub;
+    float img_scale, img_scale2;
+    const int32_t* sub_rows;
+    const int32_t* sub_frames;
+    void* meta_out;
+    void* img;
+    const float* w2;
+    const float* bias2;
+    void* c2_out;
+    float out8_scale;
+    int32_t lda;
+    const void* lin_a;
+    const float* lin_w;
+    const float* lin_bias;
+    float* lin_out;
+    int32_t M, K;
+    float a_scale, scale;
+    const float* pe;
+    int32_t pe_period, reserved;
+    int32_t* q8_out;
+} cn_frontend_desc;
+int cn_op_frontend_desc(const cn_frontend_desc* d, void* stream);
+int32_t cn_frontend_desc_size(void);
 int cn_op_layernorm(int32_t precision, const float* x, const float* a2, const float* b2, void* y, int32_t M, int32_t d,
                     float eps, void* stream);
 /* The conformer convolution module's kernels one at a time (csrc/conformer.hip; src/models/modules/conformer_related.py:15-44).
