@@ -13,6 +13,7 @@
 #include "../../include/cassnat_hip_attention_proj.h"
 #include "ctc_ngram_search.h"
 #include "ctc_times_search.h"
+#include "edit_align_search.h"
 #include "flac_decode.h"
 #include "kernels.h"
 
@@ -928,6 +929,29 @@ extern "C" int cn_op_ctc_token_times(const float* logp_dev, const int32_t* frame
     if (const size_t need = ct_scratch_bytes(B, Tp, ld, bp_lds_limit)) a.bp = (unsigned long long*)sc.alloc(need);
     if (!sc.ok()) return -2;
     return sc.finish(launch_ctc_token_times(a, bp_lds_limit, s));
+}
+
+// the weighted edit alignment of id sequences (include/cassnat_hip_score.h; all pointers device)
+extern "C" int cn_op_edit_align(const int32_t* ref_dev, int64_t ref_total, const int64_t* ref_begin_dev, const int32_t* ref_len_dev,
+                                const int32_t* hyp_dev, int64_t hyp_total, const int64_t* hyp_begin_dev, const int32_t* hyp_len_dev, int32_t N,
+                                int32_t max_ref, int32_t max_hyp, int32_t c_sub, int32_t c_ins, int32_t c_del, int64_t bp_lds_limit,
+                                int32_t* cost_dev, int32_t* counts_dev, int32_t* path_len_dev, uint8_t* ops_dev, int64_t ops_total,
+                                const int64_t* ops_begin_dev, void* stream) {
+    EditArgs a;
+    a.ref = ref_dev, a.ref_begin = ref_begin_dev, a.ref_len = ref_len_dev, a.hyp = hyp_dev, a.hyp_begin = hyp_begin_dev, a.hyp_len = hyp_len_dev;
+    a.ops_begin = ops_begin_dev, a.ref_total = ref_total, a.hyp_total = hyp_total, a.ops_total = ops_total;
+    a.N = N, a.max_ref = max_ref, a.max_hyp = max_hyp, a.c_sub = c_sub, a.c_ins = c_ins, a.c_del = c_del;
+    a.cost = cost_dev, a.counts = counts_dev, a.path_len = path_len_dev, a.ops = ops_dev;
+    const std::string bad = ea_check(a);  // (before the scratch is sized from these numbers)
+    if (!bad.empty()) {
+        cn_set_error("cn_op_edit_align: " + bad);
+        return -1;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    Scratch sc("cn_op_edit_align", s);
+    if (const size_t need = ea_scratch_bytes(N, max_ref, max_hyp, bp_lds_limit)) a.bp = (unsigned long long*)sc.alloc(need);
+    if (!sc.ok()) return -2;
+    return sc.finish(launch_edit_align(a, bp_lds_limit, s));
 }
 
 extern "C" int cn_op_greedy_pack(const int32_t* tok, const float* val, const int32_t* ylen, int32_t B, int32_t U,

@@ -325,6 +325,67 @@ def flac_decode(staged, staged_bytes, table, frames, utt, utts, max_channels, fr
     return pcm
 
 
+EDIT_OPS = "CSDI"  # the codes of an edit path: 0 correct, 1 substituted, 2 deleted, 3 inserted
+
+
+def edit_align(ref, ref_begin, ref_len, hyp, hyp_begin, hyp_len, costs=(1, 1, 1), max_ref=None, max_hyp=None, bp_lds_limit=-1, flavour=None):
+    """Weighted edit alignment of N pairs of id sequences on the device (cn_op_edit_align; include/cassnat_hip_score.h): ``ref`` /
+    ``hyp`` int32 CUDA id arrays, pair n = ref[ref_begin[n] .. + ref_len[n]) against hyp[hyp_begin[n] .. + hyp_len[n]) (begins int64,
+    lengths int32, CUDA; pairs may share a reference), ``costs`` = (sub, ins, del).  ``max_ref`` / ``max_hyp`` clamp the lengths and
+    size the launch (None: the largest length, which costs a copy to the host).  -> (cost (N,) int32, counts (N, 4) int32 C / S / D / I,
+    path_len (N,) int32, ops uint8, ops_begin (N,) int64) as CUDA tensors: pair n's path is ops[ops_begin[n] .. + path_len[n]), codes
+    as in ``EDIT_OPS``.  On the current stream; returns once it has drained."""
+    import torch
+
+    dev = ref.device
+    ref, hyp = ref.to(dev, torch.int32).contiguous(), hyp.to(dev, torch.int32).contiguous()
+    ref_begin, hyp_begin = ref_begin.to(dev, torch.int64).contiguous(), hyp_begin.to(dev, torch.int64).contiguous()
+    ref_len, hyp_len = ref_len.to(dev, torch.int32).contiguous(), hyp_len.to(dev, torch.int32).contiguous()
+    N = int(ref_len.numel())
+    assert ref_begin.numel() == N and hyp_begin.numel() == N and hyp_len.numel() == N
+    if N and (max_ref is None or max_hyp is None):
+        mr, mh = torch.stack([ref_len.max(), hyp_len.max()]).tolist()
+        max_ref, max_hyp = (max(0, mr) if max_ref is None else max_ref), (max(0, mh) if max_hyp is None else max_hyp)
+    max_ref, max_hyp = int(max_ref or 0), int(max_hyp or 0)
+    span = ref_len.clamp(0, max(0, max_ref)).to(torch.int64) + hyp_len.clamp(0, max(0, max_hyp)).to(torch.int64)
+    ops_begin = torch.cumsum(span, 0) - span
+    ops_total = int(span.sum().item()) if N else 0
+    ops = torch.zeros(max(1, ops_total), dtype=torch.uint8, device=dev)
+    cost = torch.zeros(max(1, N), dtype=torch.int32, device=dev)
+    counts = torch.zeros(max(1, N), 4, dtype=torch.int32, device=dev)
+    plen = torch.zeros(max(1, N), dtype=torch.int32, device=dev)
+    L = lib(flavour)
+    # (an empty id array still needs an address: the op refuses null buffers)
+    refp, hypp = (t if t.numel() else torch.zeros(1, dtype=torch.int32, device=dev) for t in (ref, hyp))
+    check(L.cn_op_edit_align(_ptr(refp), ref.numel(), _ptr(ref_begin), _ptr(ref_len), _ptr(hypp), hyp.numel(), _ptr(hyp_begin), _ptr(hyp_len), N,
+                             max_ref, max_hyp, int(costs[0]), int(costs[1]), int(costs[2]), int(bp_lds_limit), _ptr(cost), _ptr(counts), _ptr(plen),
+                             _ptr(ops), ops_total, _ptr(ops_begin), current_stream()), "cn_op_edit_align", L)
+    return cost[:N], counts[:N], plen[:N], ops[:ops_total], ops_begin
+
+
+def edit_align_host(ref, ref_begin, ref_len, hyp, hyp_begin, hyp_len, costs=(1, 1, 1), max_ref=None, max_hyp=None, flavour=None):
+    """``edit_align`` on numpy arrays through the serial host entry (cn_edit_align_host): no GPU call.  Same outputs, as numpy arrays."""
+    ref, hyp = np.ascontiguousarray(ref, np.int32).reshape(-1), np.ascontiguousarray(hyp, np.int32).reshape(-1)
+    ref_begin, hyp_begin = np.ascontiguousarray(ref_begin, np.int64).reshape(-1), np.ascontiguousarray(hyp_begin, np.int64).reshape(-1)
+    ref_len, hyp_len = np.ascontiguousarray(ref_len, np.int32).reshape(-1), np.ascontiguousarray(hyp_len, np.int32).reshape(-1)
+    N = int(ref_len.size)
+    assert ref_begin.size == N and hyp_begin.size == N and hyp_len.size == N
+    max_ref = int(max(0, ref_len.max(initial=0)) if max_ref is None else max_ref)
+    max_hyp = int(max(0, hyp_len.max(initial=0)) if max_hyp is None else max_hyp)
+    span = np.clip(ref_len, 0, max(0, max_ref)).astype(np.int64) + np.clip(hyp_len, 0, max(0, max_hyp)).astype(np.int64)
+    ops_begin = np.cumsum(span) - span
+    ops_total = int(span.sum())
+    ops = np.zeros(max(1, ops_total), np.uint8)
+    cost, counts, plen = np.zeros(max(1, N), np.int32), np.zeros((max(1, N), 4), np.int32), np.zeros(max(1, N), np.int32)
+    refp, hypp = (a if a.size else np.zeros(1, np.int32) for a in (ref, hyp))
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    L = lib(flavour)
+    check(L.cn_edit_align_host(p(refp), ref.size, p(ref_begin), p(ref_len), p(hypp), hyp.size, p(hyp_begin), p(hyp_len), N, max_ref, max_hyp,
+                               int(costs[0]), int(costs[1]), int(costs[2]), p(cost), p(counts), p(plen), p(ops), ops_total, p(ops_begin)),
+          "cn_edit_align_host", L)
+    return cost[:N], counts[:N], plen[:N], ops[:ops_total], ops_begin
+
+
 class Engine:
     """Owns one ``cn_model`` handle: weights, workspace and the decode pipeline on one GPU."""
 

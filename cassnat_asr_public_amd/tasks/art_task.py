@@ -234,4 +234,8 @@ class ArtTask(BaseTask):
             if getattr(args, "hip_ctm", ""):
                 missed = ctm.write(args.hip_ctm, order, times, ctm.seconds_per_frame(args), ctm.unit_of(args, self.vocab))
                 print("CTM: %d of %d utterances could not be aligned (their units share the frames evenly, confidence 0)" % (missed, len(order)))
+            if getattr(args, "hip_score", ""):  # (a post-pass over the words just printed: utils.score)
+                from ..utils import score
+
+                score.score_run(args, self.vocab, order, {utt: results[utt].split()[1:] for utt in order})
         return 0

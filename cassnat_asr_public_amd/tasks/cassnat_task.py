@@ -434,5 +434,9 @@ class CassNATTask(BaseTask):
                 missed = ctm.write(args.hip_ctm, order, {utt: results[utt][2] for utt in order}, ctm.seconds_per_frame(args),
                                    ctm.unit_of(args, self.vocab))
                 print("CTM: %d of %d utterances could not be aligned (their units share the frames evenly, confidence 0)" % (missed, len(order)))
+            if getattr(args, "hip_score", ""):  # (a post-pass over the words just printed: utils.score)
+                from ..utils import score
+
+                score.score_run(args, self.vocab, order, {utt: " ".join(results[utt][0]).split() for utt in order})
         self.decoded_frames = frames
         return 0

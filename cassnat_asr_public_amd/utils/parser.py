@@ -3,6 +3,22 @@
 import argparse
 
 
+def add_score_arguments(p):
+    """The scorer's options, shared by decode_asr (--hip_score) and bin/score_asr."""
+    p.add_argument("--hip_score_unit", default="word", choices=["word", "token", "char"],
+                   help="what is counted: word (default; pieces merge at the separator, as in the CTM - a vocabulary without separator "
+                        "pieces is scored per token), token (the pieces themselves; needs a reference in pieces) or char (the characters "
+                        "of the words)")
+    p.add_argument("--hip_score_ref_form", default="pieces", choices=["pieces", "words"],
+                   help="the reference file holds pieces (default; what token.scp holds) or words")
+    p.add_argument("--hip_score_costs", default="1,1,1", type=str,
+                   help="S,I,D: the costs of a substitution, an insertion and a deletion, each in 1 .. 255 (default 1,1,1, Kaldi's "
+                        "compute-wer; sclite aligns with 4,3,3).  On equal cost the first of (diagonal, deletion, insertion) wins")
+    p.add_argument("--hip_score_mode", default="present", choices=["present", "all"],
+                   help="present (default): an utterance of the reference file without a hypothesis is skipped and counted as not "
+                        "present; all: its reference counts as deletions")
+
+
 class DecodeParser(object):
     def __init__(self, description="Decode argument parser"):
         p = argparse.ArgumentParser(description=description)
@@ -71,6 +87,14 @@ class DecodeParser(object):
         p.add_argument("--hip_ctm_unit", default="word", choices=["word", "token"],
                        help="--hip_ctm: word (default; pieces that begin with the separator start a word, a vocabulary without such "
                             "pieces is written per token) or token (one line per piece)")
+        add_score_arguments(p)
+        p.add_argument("--hip_score", default="", type=str,
+                       help="also score the run against its references: once the result file is written, rank 0 aligns every hypothesis "
+                            "with its reference on the device (weighted edit distance) and writes DIR/wer (the lines of Kaldi's compute-wer), "
+                            "DIR/per_utt (ref / hyp / op / #csid per utterance), DIR/ref.trn and DIR/hyp.trn; the %%WER line is printed.  A "
+                            "post-pass over the result file's strings: every decode path stays available and its files do not change")
+        p.add_argument("--hip_score_ref", default="", type=str,
+                       help="--hip_score: the reference file, one 'UTT unit unit ...' line per utterance (default: --text_label)")
         p.add_argument("--hip_dist_backend", default="nccl", choices=["nccl", "gloo"],
                        help="torch.distributed backend under torch.distributed.run (nccl = RCCL over xGMI; gloo: rehearsal of the "
                             "N-rank path, also with several ranks on one GPU)")
