@@ -11,6 +11,7 @@
 // chunk c ^ ((r>>1)&7), which makes the ds_read_b128 fragment reads and the ds_write_b128 staging
 // writes bank-conflict free (MI355X LDS: 64 banks x 4 B, b128 reads serviced in 16-lane groups).
 #include "kernels.h"
+#include "../../include/cassnat_hip.h"
 
 struct GemmParams {
     const unsigned char* A;
@@ -301,67 +302,97 @@ static int run_gemm(const GemmArgs& a, hipStream_t s) {
     return 0;
 }
 
-template <typename T> static int dispatch_gemm(const GemmArgs& a, hipStream_t s) {
-    constexpr int BK = 128 / (int)sizeof(T);
-    if (a.M <= 0 || a.N <= 0) return 0;
-    if (a.K <= 0 || a.K % BK != 0) {
-        cn_set_error("gemm: K=" + std::to_string(a.K) + " must be a positive multiple of " + std::to_string(BK));
-        return -1;
-    }
-    if (!a.conv && ((a.lda * sizeof(T)) % 16 != 0)) {
-        cn_set_error("gemm: lda must keep rows 16-byte aligned");
-        return -1;
-    }
-    if (a.conv) {
-        if (a.cC % BK != 0 || a.K != 9 * a.cC || a.M != a.cB * a.cT2 * a.cF2) {
-            cn_set_error("gemm(conv): inconsistent implicit-GEMM shape");
-            return -1;
-        }
-        return run_gemm<T, T, 128, 128, true>(a, s);
-    }
-    // Tile choice: 128x128 when that still yields >= 2 workgroups per CU, else 64x64 to fill 256 CUs.
-    const long long big = (long long)cn_ceil_div(a.M, 128) * cn_ceil_div(a.N, 128);
-    const bool use_big = big >= 512;
-    const bool fullk = a.K == 4 * BK;
-    if (a.c_f32) {
-        if (use_big) return run_gemm<T, float, 128, 128, false>(a, s);
-        return fullk ? run_gemm<T, float, 64, 64, false, true>(a, s) : run_gemm<T, float, 64, 64, false>(a, s);
-    }
-    if (use_big) return run_gemm<T, T, 128, 128, false>(a, s);
-    return fullk ? run_gemm<T, T, 64, 64, false, true>(a, s) : run_gemm<T, T, 64, 64, false>(a, s);
+// ---- the host-only decision: the argument checks and the kernel a call takes (kernels.h: GemmForm).  Nothing here touches
+// the device; launch_gemm launches what it decides, cn_gemm_form (ops.hip) reports it.
+static int gemm_refuse(const char* who, const std::string& what) {
+    cn_set_error(std::string(who) + ": " + what);
+    return -1;
 }
 
-// fp8 operands (the encoder products of config 5): bf16 / fp32 / fp8 output, no implicit-GEMM form
-static int dispatch_gemm_fp8(const GemmArgs& a, hipStream_t s) {
-    if (a.M <= 0 || a.N <= 0) return 0;
-    if (a.conv || a.K <= 0 || a.K % 128 != 0 || a.lda % 16 != 0) {
-        cn_set_error("gemm(fp8): K must be a positive multiple of 128 and rows 16-byte aligned; no convolution form");
-        return -1;
+// rows the kernel can address: the K columns of A and the N of C and resid lie inside their rows (non-convolution forms)
+static int check_gemm_strides(const GemmArgs& a, const char* who) {
+    if (a.lda < a.K) return gemm_refuse(who, "lda=" + std::to_string(a.lda) + " < K=" + std::to_string(a.K));
+    if (a.ldc < a.N) return gemm_refuse(who, "ldc=" + std::to_string(a.ldc) + " < N=" + std::to_string(a.N));
+    if (a.epi & CN_EPI_RESID) {
+        if (!a.resid) return gemm_refuse(who, "the residual epilogue needs resid");
+        if (a.ldr < a.N) return gemm_refuse(who, "ldr=" + std::to_string(a.ldr) + " < N=" + std::to_string(a.N));
     }
+    return 0;
+}
+
+int decide_gemm(int prec, const GemmArgs& a, GemmForm* f, const char* who) {
+    f->elem = a.ab_fp8 ? CN_GEMM_ELEM_E4M3 : prec == CN_PREC_X3 ? CN_GEMM_ELEM_SPLIT : prec == CN_PREC_F32 ? CN_GEMM_ELEM_F32 : CN_GEMM_ELEM_16;
+    f->out = a.c_f32 ? CN_GEMM_OUT_F32 : (a.ab_fp8 && a.c_fp8) ? CN_GEMM_OUT_E4M3 : CN_GEMM_OUT_OWN;
+    f->tile = CN_GEMM_TILE_NONE;
+    // Tile choice: 128x128 when that still yields >= 2 workgroups per CU, else 64x64 to fill 256 CUs.
     const bool use_big = (long long)cn_ceil_div(a.M, 128) * cn_ceil_div(a.N, 128) >= 512;
-    if (a.c_f32) return use_big ? run_gemm<fp8_t, float, 128, 128, false>(a, s) : run_gemm<fp8_t, float, 64, 64, false>(a, s);
-    if (a.c_fp8) return use_big ? run_gemm<fp8_t, fp8_t, 128, 128, false>(a, s) : run_gemm<fp8_t, fp8_t, 64, 64, false>(a, s);
-    return use_big ? run_gemm<fp8_t, bf16, 128, 128, false>(a, s) : run_gemm<fp8_t, bf16, 64, 64, false>(a, s);
+    // fp8 operands (the encoder products of config 5): bf16 / fp32 / fp8 output, no implicit-GEMM form
+    if (a.ab_fp8) {
+        if (a.M <= 0 || a.N <= 0) return 0;
+        if (a.conv || a.K <= 0 || a.K % 128 != 0 || a.lda % 16 != 0)
+            return gemm_refuse(who, "fp8 operands: K must be a positive multiple of 128 and rows 16-byte aligned; no convolution form");
+        if (check_gemm_strides(a, who)) return -1;
+        f->tile = use_big ? CN_GEMM_TILE_128 : CN_GEMM_TILE_64;
+        return 0;
+    }
+    if (a.conv && a.conv_halo) {
+        if (!(a.epi == CN_EPI_RELU && a.ldc == a.N && conv2_dma_applies(prec, a.cC, a.N)))
+            return gemm_refuse(who, "a haloed conv input is only understood by the bf16 256-channel conv2 kernel");
+        f->tile = CN_GEMM_TILE_CONV2_DMA;
+        return 0;
+    }
+    // K-deep products onto all 256 output columns with the embedding epilogue (linear_out): the LDS-DMA tile kernel
+    if (!a.conv && a.epi == CN_EPI_EMBED && a.c_f32 && a.ldc == a.N && a.K >= 1024 && linear256_dma_applies(prec, a.N, a.K)) {
+        f->tile = CN_GEMM_TILE_LINEAR256;
+        return 0;
+    }
+    if (prec == CN_PREC_X3 && (a.lda % 32 != 0 || (!a.c_f32 && a.ldc % 32 != 0)))
+        return gemm_refuse(who, "split-bf16 operands need row strides that are multiples of 32 elements");
+    const int esz = (prec == CN_PREC_F32 || prec == CN_PREC_X3) ? 4 : 2, BK = prec == CN_PREC_X3 ? 32 : 128 / esz;  // (a split element: 4 bytes, a slab 32 of them)
+    if (a.M <= 0 || a.N <= 0) return 0;
+    if (a.K <= 0 || a.K % BK != 0) return gemm_refuse(who, "K=" + std::to_string(a.K) + " must be a positive multiple of " + std::to_string(BK));
+    if (!a.conv && ((size_t)a.lda * esz) % 16 != 0) return gemm_refuse(who, "lda must keep rows 16-byte aligned");
+    if (a.conv) {
+        if (a.cC % BK != 0 || a.K != 9 * a.cC || a.M != a.cB * a.cT2 * a.cF2) return gemm_refuse(who, "(conv) inconsistent implicit-GEMM shape");
+        if (a.ldc < a.N) return gemm_refuse(who, "ldc=" + std::to_string(a.ldc) + " < N=" + std::to_string(a.N));
+        f->out = CN_GEMM_OUT_OWN;
+        f->tile = CN_GEMM_TILE_CONV;
+        return 0;
+    }
+    if (check_gemm_strides(a, who)) return -1;
+    f->tile = use_big ? CN_GEMM_TILE_128 : a.K == 4 * BK ? CN_GEMM_TILE_64_FULLK : CN_GEMM_TILE_64;
+    return 0;
+}
+
+// FULLK exists for the element types whose slab count can be 4 at a latency-bound shape (not for e4m3 operands)
+template <typename T, typename TC> static int run_form(const GemmForm& f, const GemmArgs& a, hipStream_t s) {
+    if (f.tile == CN_GEMM_TILE_128) return run_gemm<T, TC, 128, 128, false>(a, s);
+    if constexpr (sizeof(T) != 1)
+        if (f.tile == CN_GEMM_TILE_64_FULLK) return run_gemm<T, TC, 64, 64, false, true>(a, s);
+    return run_gemm<T, TC, 64, 64, false>(a, s);
+}
+
+template <typename T> static int run_elem(const GemmForm& f, const GemmArgs& a, hipStream_t s) {
+    if (f.tile == CN_GEMM_TILE_CONV) return run_gemm<T, T, 128, 128, true>(a, s);
+    return f.out == CN_GEMM_OUT_F32 ? run_form<T, float>(f, a, s) : run_form<T, T>(f, a, s);
 }
 
 int launch_gemm(int prec, const GemmArgs& a, hipStream_t s) {
-    if (a.ab_fp8) return dispatch_gemm_fp8(a, s);
-    if (a.conv && a.conv_halo) {
-        if (!(a.epi == CN_EPI_RELU && a.ldc == a.N && conv2_dma_applies(prec, a.cC, a.N))) {
-            cn_set_error("gemm: a haloed conv input is only understood by the bf16 256-channel conv2 kernel");
-            return -1;
-        }
-        return launch_conv2_dma(a.A, a.W, a.bias, a.C, a.cB, a.cT1, a.cF1, a.cT2, a.cF2, s);
+    GemmForm f;
+    if (decide_gemm(prec, a, &f) != 0) return -1;
+    switch (f.tile) {
+        case CN_GEMM_TILE_NONE: return 0;
+        case CN_GEMM_TILE_CONV2_DMA: return launch_conv2_dma(a.A, a.W, a.bias, a.C, a.cB, a.cT1, a.cF1, a.cT2, a.cF2, s);
+        case CN_GEMM_TILE_LINEAR256:
+            return launch_linear256_dma(a.A, a.lda, a.W, a.bias, (float*)a.C, a.M, a.K, a.scale, a.pe, a.pe_period, s);
+        default: break;
     }
-    // K-deep products onto all 256 output columns with the embedding epilogue (linear_out): the LDS-DMA tile kernel
-    if (!a.conv && a.epi == CN_EPI_EMBED && a.c_f32 && a.ldc == a.N && a.K >= 1024 && linear256_dma_applies(prec, a.N, a.K))
-        return launch_linear256_dma(a.A, a.lda, a.W, a.bias, (float*)a.C, a.M, a.K, a.scale, a.pe, a.pe_period, s);
-    if (prec == CN_PREC_X3) {
-        if (a.lda % 32 != 0 || (!a.c_f32 && a.ldc % 32 != 0)) {
-            cn_set_error("gemm: split-bf16 operands need row strides that are multiples of 32 elements");
-            return -1;
-        }
-        return dispatch_gemm<split_t>(a, s);
+    switch (f.elem) {
+        case CN_GEMM_ELEM_E4M3:
+            if (f.out == CN_GEMM_OUT_F32) return run_form<fp8_t, float>(f, a, s);
+            return f.out == CN_GEMM_OUT_E4M3 ? run_form<fp8_t, fp8_t>(f, a, s) : run_form<fp8_t, bf16>(f, a, s);
+        case CN_GEMM_ELEM_SPLIT: return run_elem<split_t>(f, a, s);
+        case CN_GEMM_ELEM_F32: return run_elem<float>(f, a, s);
+        default: return run_elem<bf16>(f, a, s);
     }
-    return prec == CN_PREC_F32 ? dispatch_gemm<float>(a, s) : dispatch_gemm<bf16>(a, s);
 }

@@ -40,6 +40,13 @@ struct GemmArgs {
     int cB = 0, cT1 = 0, cF1 = 0, cC = 0, cT2 = 0, cF2 = 0;
 };
 int launch_gemm(int prec, const GemmArgs& a, hipStream_t s);
+// The host-only half of launch_gemm: the argument checks and which kernel the call takes (the CN_GEMM_ELEM_* / OUT_* / TILE_*
+// enumerators of cassnat_hip.h; tile CN_GEMM_TILE_NONE: nothing to launch).  Returns 0, or -1 with the error set, its message
+// starting with `who`.  launch_gemm launches what this decides; cn_gemm_form reports it.
+struct GemmForm {
+    int elem = 0, out = 0, tile = 0;
+};
+int decide_gemm(int prec, const GemmArgs& a, GemmForm* f, const char* who = "gemm");
 
 // ---- first subsampling convolution, 1 -> C channels, 3x3 stride 2 pad 1, + ReLU   (conv1.hip)
 // x (B,T,F) fp32  ->  out (B,T1,F1,C) channels-last in model precision.  w is [9][C] (tap-major).

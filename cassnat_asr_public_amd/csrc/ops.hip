@@ -210,29 +210,100 @@ extern "C" int cn_op_wave_resample(int32_t in_rate, int32_t out_rate, const void
                                 channel_dev, utts, rows_dev, rows, max_out, wave_dev, out_off_dev, (hipStream_t)stream);
 }
 
+// cn_gemm_desc -> (internal precision, GemmArgs): the checks of the descriptor itself (cassnat_hip.h lists them); the shape and
+// stride checks are decide_gemm's, which launch_gemm runs for the engine's calls too.  0, or -1 with the error set.
+static int gemm_args_of(const char* who, const cn_gemm_desc* d, int* prec, GemmArgs* g) {
+    auto refuse = [&](const char* what) {
+        cn_set_error(std::string(who) + ": " + what);
+        return -1;
+    };
+    if (!d) return refuse("null descriptor");
+    if (!d->A || !d->W || !d->C) return refuse("null A, W or C");
+    if (d->precision != CN_PRECISION_F32 && d->precision != CN_PRECISION_BF16 && d->precision != CN_PRECISION_BF16X3 &&
+        d->precision != CN_PRECISION_F16)
+        return refuse("precision must be CN_PRECISION_F32, CN_PRECISION_BF16, CN_PRECISION_BF16X3 or CN_PRECISION_F16");
+    if ((*prec = cn_own_precision(d->precision, who)) < 0) return -1;
+    if (d->reserved != 0) return refuse("the reserved word must be 0");
+    if (d->epi & ~(CN_GEMM_EPI_RELU | CN_GEMM_EPI_RESID | CN_GEMM_EPI_EMBED | CN_GEMM_EPI_SWISH)) return refuse("unknown epilogue bits");
+    if (d->c_kind != CN_GEMM_OUT_OWN && d->c_kind != CN_GEMM_OUT_F32 && d->c_kind != CN_GEMM_OUT_E4M3)
+        return refuse("c_kind must be CN_GEMM_OUT_OWN, CN_GEMM_OUT_F32 or CN_GEMM_OUT_E4M3");
+    if (d->c_kind == CN_GEMM_OUT_E4M3 && !d->ab_fp8) return refuse("an e4m3 output needs e4m3 operands (ab_fp8)");
+    if (d->ab_fp8 && d->precision != CN_PRECISION_BF16)
+        return refuse("e4m3 operands belong to CN_PRECISION_BF16 (the type of their 16-bit output)");
+    if (d->M < 0 || d->N < 0) return refuse("M and N must not be negative");
+    g->A = d->A;
+    g->lda = d->lda;
+    g->W = d->W;
+    g->bias = d->bias;
+    g->C = d->C;
+    g->ldc = d->ldc;
+    g->c_f32 = d->c_kind == CN_GEMM_OUT_F32;
+    g->c_fp8 = d->c_kind == CN_GEMM_OUT_E4M3;
+    g->M = d->M;
+    g->N = d->N;
+    g->K = d->K;
+    g->epi = d->epi;
+    g->resid = d->resid;
+    g->ldr = d->ldr;
+    g->resid_scale = d->resid_scale;
+    g->pe = d->pe;
+    g->pe_period = d->pe_period;
+    g->scale = d->scale;
+    g->ab_fp8 = d->ab_fp8 != 0;
+    g->acc_scale = d->acc_scale;
+    g->w_inv_scale = d->w_inv_scale;
+    g->c_scale = d->c_scale;
+    return 0;
+}
+
+static int op_gemm_desc(const char* who, const cn_gemm_desc* d, void* stream) {
+    int prec;
+    GemmArgs g;
+    GemmForm f;
+    if (gemm_args_of(who, d, &prec, &g) != 0 || decide_gemm(prec, g, &f, who) != 0) return -1;
+    return launch_gemm(prec, g, (hipStream_t)stream);
+}
+
+extern "C" int cn_op_gemm_desc(const cn_gemm_desc* d, void* stream) { return op_gemm_desc("cn_op_gemm_desc", d, stream); }
+extern "C" int32_t cn_gemm_desc_size(void) { return (int32_t)sizeof(cn_gemm_desc); }
+extern "C" int32_t cn_gemm_form(const cn_gemm_desc* d) {
+    int prec;
+    GemmArgs g;
+    GemmForm f;
+    if (gemm_args_of("cn_gemm_form", d, &prec, &g) != 0 || decide_gemm(prec, g, &f, "cn_gemm_form") != 0) return -1;
+    return f.elem | f.out << 4 | f.tile << 8;
+}
+
+static_assert(CN_GEMM_EPI_RELU == CN_EPI_RELU && CN_GEMM_EPI_RESID == CN_EPI_RESID && CN_GEMM_EPI_EMBED == CN_EPI_EMBED &&
+                  CN_GEMM_EPI_SWISH == CN_EPI_SWISH,
+              "the public epilogue bits are the kernel's");
+
+// cn_op_gemm: the descriptor of a product in the model precision with the epilogues its arguments can name
 extern "C" int cn_op_gemm(int32_t precision, const void* A, int32_t lda, const void* W, const float* bias, void* C,
                           int32_t ldc, int32_t c_is_f32, int32_t M, int32_t N, int32_t K, int32_t relu,
                           const float* resid, int32_t ldr, const float* pe, int32_t pe_period, float scale,
                           void* stream) {
-    if ((precision = cn_own_precision(precision, "cn_op_gemm")) < 0) return -1;
-    GemmArgs g;
-    g.A = A;
-    g.lda = lda;
-    g.W = W;
-    g.bias = bias;
-    g.C = C;
-    g.ldc = ldc;
-    g.c_f32 = c_is_f32;
-    g.M = M;
-    g.N = N;
-    g.K = K;
-    g.epi = (relu ? CN_EPI_RELU : 0) | (resid ? CN_EPI_RESID : 0) | (pe ? CN_EPI_EMBED : 0);
-    g.resid = resid;
-    g.ldr = ldr;
-    g.pe = pe;
-    g.pe_period = pe_period;
-    g.scale = scale;
-    return launch_gemm(precision, g, (hipStream_t)stream);
+    cn_gemm_desc d = {};
+    d.precision = precision;
+    d.c_kind = c_is_f32 ? CN_GEMM_OUT_F32 : CN_GEMM_OUT_OWN;
+    d.A = A;
+    d.lda = lda;
+    d.W = W;
+    d.bias = bias;
+    d.C = C;
+    d.ldc = ldc;
+    d.M = M;
+    d.N = N;
+    d.K = K;
+    d.epi = (relu ? CN_GEMM_EPI_RELU : 0) | (resid ? CN_GEMM_EPI_RESID : 0) | (pe ? CN_GEMM_EPI_EMBED : 0);
+    d.resid = resid;
+    d.ldr = ldr;
+    d.resid_scale = 1.f;
+    d.pe = pe;
+    d.pe_period = pe_period;
+    d.scale = scale;
+    d.acc_scale = d.c_scale = 1.f;
+    return op_gemm_desc("cn_op_gemm", &d, stream);
 }
 
 extern "C" int cn_op_convert(int32_t precision, const void* src, void* dst, int64_t n, int32_t to_f32, void* stream) {

@@ -48,9 +48,9 @@ def parse_fp8_scope(text):
     return scope, first
 
 
-# the eight structs of the header, derived from it field for field (abi.py)
-CnConfig, CnDecodeOpts, CnAstOpts, CnFbankOpts, CnAttnDesc, CnNgramDesc, CnChainDesc, CnFrontendDesc = (abi.STRUCTS[n] for n in (
-    "cn_config", "cn_decode_opts", "cn_ast_opts", "cn_fbank_opts", "cn_attn_desc", "cn_ngram_desc", "cn_chain_desc", "cn_frontend_desc"))
+# the nine structs of the header, derived from it field for field (abi.py)
+CnConfig, CnDecodeOpts, CnAstOpts, CnFbankOpts, CnAttnDesc, CnNgramDesc, CnChainDesc, CnFrontendDesc, CnGemmDesc = (abi.STRUCTS[n] for n in (
+    "cn_config", "cn_decode_opts", "cn_ast_opts", "cn_fbank_opts", "cn_attn_desc", "cn_ngram_desc", "cn_chain_desc", "cn_frontend_desc", "cn_gemm_desc"))
 
 
 class HipError(RuntimeError):

@@ -507,6 +507,52 @@ int cn_op_convert(int32_t precision, const void* src, void* dst, int64_t n, int3
 int cn_op_gemm(int32_t precision, const void* A, int32_t lda, const void* W, const float* bias, void* C, int32_t ldc,
                int32_t c_is_f32, int32_t M, int32_t N, int32_t K, int32_t relu, const float* resid, int32_t ldr,
                const float* pe, int32_t pe_period, float scale, void* stream);
+/* The tiled GEMM (csrc/gemm.hip) through a descriptor that reaches every field of its non-convolution product - what cn_op_gemm
+ * cannot express: Swish, resid_scale, e4m3 operands with a 16-bit / fp32 / e4m3 output, the device-side weight scale:
+ *     v = (A . W^T) * deq + bias          deq = 1, or acc_scale * (w_inv_scale ? *w_inv_scale : 1) with e4m3 operands (ab_fp8)
+ *     RELU: v = max(v, 0);  SWISH: v = v * sigmoid(v);  EMBED: v = v * scale + (pe ? pe[m % pe_period][n] : 0)
+ *     RESID: v = resid[m][n] + resid_scale * v;  e4m3 output: v = v * c_scale, saturating at +-448;  C[m][n] = round(v)
+ * in that order, `epi` being a sum of CN_GEMM_EPI_* bits.  All operands are device pointers in the kernel's own storage, nothing is
+ * packed by the call: A [M][lda] and W [N][K] (K contiguous) in the element type of `precision` (CN_PRECISION_F32 / BF16 / BF16X3 /
+ * F16; with ab_fp8: e4m3fn bytes, `precision` CN_PRECISION_BF16 naming the 16-bit output type), bias [N], resid [M][ldr] and pe
+ * [pe_period][N] fp32 (resid may alias an fp32 C), C [M][ldc] of c_kind: CN_GEMM_OUT_OWN (the element type; 16-bit with ab_fp8),
+ * CN_GEMM_OUT_F32 or CN_GEMM_OUT_E4M3 (ab_fp8 only).  Strides in elements.  resid_scale, scale, acc_scale and c_scale are used as
+ * given (a zeroed descriptor has none of them at 1).  Rows >= M and columns >= N (of A: >= K) are neither read nor written.
+ * cn_gemm_form is the host-only decision of which kernel such a call takes, without touching the device: elem | out << 4 | tile << 8
+ * of the CN_GEMM_ELEM_*, CN_GEMM_OUT_*, CN_GEMM_TILE_* enumerators (CN_GEMM_TILE_NONE: M or N is 0, nothing is launched;
+ * CN_GEMM_TILE_LINEAR256: the LDS-DMA linear_out kernel of the front end takes the call), or -1 where cn_op_gemm_desc would refuse.
+ * The engine's own products go through the same decision.
+ * Refused with a message that starts "cn_op_gemm_desc: " (cn_gemm_form: "cn_gemm_form: "), before anything is launched: a null
+ * descriptor, null A, W or C; a precision this library does not own; unknown epilogue bits or output kind, a non-zero reserved
+ * word; an e4m3 output without e4m3 operands; e4m3 operands in another precision than CN_PRECISION_BF16; M or N < 0; a K that is
+ * not a positive multiple of the slab (32 fp32 / 64 sixteen-bit / 32 split / 128 e4m3); an lda that does not keep rows 16-byte
+ * aligned; lda < K, ldc < N; RESID without resid or with ldr < N; split-bf16 strides (lda; ldc of a split output) that are not
+ * multiples of 32.  M == 0 or N == 0: returns 0, launches nothing.  cn_gemm_desc_size() is sizeof(cn_gemm_desc). */
+enum { CN_GEMM_EPI_RELU = 1, CN_GEMM_EPI_RESID = 2, CN_GEMM_EPI_EMBED = 4, CN_GEMM_EPI_SWISH = 8 };
+enum { CN_GEMM_ELEM_F32 = 0, CN_GEMM_ELEM_16 = 1, CN_GEMM_ELEM_SPLIT = 2, CN_GEMM_ELEM_E4M3 = 3 };
+enum { CN_GEMM_OUT_OWN = 0, CN_GEMM_OUT_F32 = 1, CN_GEMM_OUT_E4M3 = 2 };
+enum { CN_GEMM_TILE_NONE = 0, CN_GEMM_TILE_128 = 1, CN_GEMM_TILE_64 = 2, CN_GEMM_TILE_64_FULLK = 3, CN_GEMM_TILE_LINEAR256 = 4,
+       CN_GEMM_TILE_CONV = 5, CN_GEMM_TILE_CONV2_DMA = 6 };
+typedef struct cn_gemm_desc {
+    int32_t precision, c_kind;
+    const void* A;
+    const void* W;
+    const float* bias;
+    void* C;
+    const float* resid;
+    const float* pe;
+    const float* w_inv_scale;
+    int32_t lda, ldc, ldr;
+    int32_t M, N, K;
+    int32_t epi, pe_period;
+    float resid_scale, scale;
+    int32_t ab_fp8;
+    float acc_scale, c_scale;
+    int32_t reserved;
+} cn_gemm_desc;
+int cn_op_gemm_desc(const cn_gemm_desc* d, void* stream);
+int32_t cn_gemm_desc_size(void);
+int32_t cn_gemm_form(const cn_gemm_desc* d);
 int cn_op_conv1(int32_t precision, const float* x, const float* w9c, const float* bias, void* out, int32_t B, int32_t T,
                 int32_t F, int32_t C, void* stream);
 /* the bf16 engine's form of the same layer (src/models/modules/embedding.py:102-104): conv1 + ReLU written as the bordered bf16
