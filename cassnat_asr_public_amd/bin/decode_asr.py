@@ -54,6 +54,13 @@ def main(argv=None):
         raise NotImplementedError("task '%s' is not on the accelerated path (only %s)" % (args.task, sorted(task_dict)))
     task = task_dict[args.task]("test", args)
     task.load_lm_model(args)
+    args.hip_bias_model = None
+    if getattr(args, "hip_bias", ""):  # (read once per process; the tasks refuse the paths that run no CTC prefix beam search)
+        from ..models.bias import BiasList
+
+        args.hip_bias_model = BiasList.load(args.hip_bias, task.vocab, score=args.hip_bias_score)
+        if torch.cuda.is_available():  # (the tables go up once, before any decode worker starts: the workers share them read-only)
+            args.hip_bias_model.cuda(getattr(task.model, "_device", None))
     task.decode(args)
     if hasattr(task, "close"):
         task.close()  # (decode pipelines: engine workspaces and worker threads)

@@ -4,9 +4,9 @@
 // The search is ctc_search.h's (ctc_beam_decode, src/utils/beam_decode.py:8-93, called from src/tasks/cassnat_task.py:335-341): one
 // workgroup of 256 per utterance, the frame loop inside the kernel, one candidate per thread (in rounds when there are more than
 // 256), the stable top-W by counting rank, (parent, label) back-pointers per processed frame, unrolled at the end.  One kernel
-// body, two instantiations:
-//   ctc_beam_kernel<false>  score_lm = 0: `ctc_lm_weight: 0`.
-//   ctc_beam_kernel<true>   score_lm = lm_scale * (the word scores of the words a hypothesis has closed): `rank_model: n-gram` with an
+// body, one instantiation per fusion policy:
+//   ctc_beam_kernel<CS_FUSE_NONE>   score_lm = 0: `ctc_lm_weight: 0`.
+//   ctc_beam_kernel<CS_FUSE_NGRAM>  score_lm = lm_scale * (the word scores of the words a hypothesis has closed): `rank_model: n-gram` with an
 //                           ARPA model and ctc_lm_weight > 0 (ctc_ngram_search.h; the reference has no such search).  On top of the
 //                           body above:
 //     * the n-gram state of the kept hypotheses (CgHyp: carry, history, word count, score_lm and the cached value of closing the open
@@ -15,6 +15,13 @@
 //       most W a frame), not per candidate: the winner's thread finds the word's id, then the up to 2 * order - 1 probes of the word's
 //       score are spread over (hypothesis, task) threads and one thread per hypothesis adds them up in ng_word_score's float32 order;
 //     * after the last frame every kept hypothesis adds its open word and </s>, and the beam is sorted once more by the same key.
+//   ctc_beam_kernel<CS_FUSE_BIAS>   score_lm = the banked bonus of the listed phrases a hypothesis has completed plus the value of its open
+//                           match (ctc_bias_search.h, include/cassnat_hip_ctc_bias.h; `--hip_bias`).  On top of the body above:
+//     * (node, banked) of the kept hypotheses in static LDS, double buffered (2 * 32 * 16 bytes);
+//     * what a label adds depends on the parent's node and on the label, so every candidate thread walks the hashed edges from its
+//       parent's node (tables in global memory, ordinary loads) and leaves the state it arrives at in two more candidate arrays
+//       (node, banked) of dynamic LDS: the winner copies them to slot `rank` of the other buffer and does not walk again;
+//     * after the last frame every kept hypothesis gives up its open match and the beam is sorted once more by the same key.
 //   Every probe loop is bounded by its table's slot count.
 //
 // viterbi_align (CassNAT.beam_path_align, src/models/cassnat.py:391-414, 272-353) is the max-product CTC forward pass over the
@@ -23,14 +30,21 @@
 // predecessors (torch.max).
 #include <type_traits>
 
+#include "ctc_bias_search.h"
 #include "ctc_ngram_search.h"
 #include "kernels.h"
 
-// what the n-gram instantiation keeps in static LDS (the other one: nothing)
-template <bool NGRAM>
+enum { CS_FUSE_NONE = 0, CS_FUSE_NGRAM = 1, CS_FUSE_BIAS = 2 };  // how score_lm is formed
+
+// what an instantiation keeps in static LDS (without fusion: nothing)
+template <int FUSE>
 struct CgLds {};
 template <>
-struct CgLds<true> {
+struct CgLds<CS_FUSE_BIAS> {
+    CbState st[2][CS_MAX_BEAM];  // (node, banked), double buffered
+};
+template <>
+struct CgLds<CS_FUSE_NGRAM> {
     CgHyp hyps[2][CS_MAX_BEAM];  // n-gram state, double buffered
     NgProbe probes[CS_MAX_BEAM * NG_TASKS];
     int wflag[CS_MAX_BEAM], wid[CS_MAX_BEAM];
@@ -50,8 +64,22 @@ __device__ __forceinline__ double cg_score_words(const cn_ngram_desc& d, const C
     return 0.0;
 }
 
-template <bool NGRAM>
-__global__ __launch_bounds__(256) void ctc_beam_kernel(std::conditional_t<NGRAM, CtcNgramArgs, CtcBeamArgs> a) {
+template <int FUSE>
+struct CsFuseArgs {
+    using type = CtcBeamArgs;
+};
+template <>
+struct CsFuseArgs<CS_FUSE_NGRAM> {
+    using type = CtcNgramArgs;
+};
+template <>
+struct CsFuseArgs<CS_FUSE_BIAS> {
+    using type = CtcBiasArgs;
+};
+
+template <int FUSE>
+__global__ __launch_bounds__(256) void ctc_beam_kernel(typename CsFuseArgs<FUSE>::type a) {
+    constexpr bool NGRAM = FUSE == CS_FUSE_NGRAM, BIAS = FUSE == CS_FUSE_BIAS;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int b = blockIdx.x, tid = threadIdx.x;
     const int W = a.W, P = a.P, NC = W * (P + 1);
@@ -62,15 +90,17 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(std::conditional_t<NGRAM,
     double* cpb = ckey + NC;
     double* cpnb = cpb + NC;
     double* ctot = cpnb + NC;
-    double* cslm = ctot + NC;                      // (n-gram only)
-    double* ptot = cslm + (NGRAM ? NC : 0);        // [W] score_ctc of the kept hypotheses
+    double* cslm = ctot + NC;                      // (n-gram and bias only)
+    double* cbank = cslm + (NGRAM || BIAS ? NC : 0);  // (bias only) the candidate's banked bonus
+    double* ptot = cbank + (BIAS ? NC : 0);        // [W] score_ctc of the kept hypotheses
     int* blen = reinterpret_cast<int*>(ptot + W);  // [W]
     int* blast = blen + W;                         // [W] last label (-1: empty hypothesis)
     int* cpar = blast + W;                         // [NC] parent slot (-1: not a candidate)
     int* ctok = cpar + NC;                         // [NC] appended label (-1: stay)
     int* clen = ctok + NC;
     int* clast = clen + NC;
-    __shared__ CgLds<NGRAM> ng;
+    int* cnode = clast + NC;  // (bias only) the candidate's automaton node
+    __shared__ CgLds<FUSE> ng;
     __shared__ int s_nb, s_steps;
 
     const float* logp = a.logp + (long long)b * a.Tp * a.V;
@@ -86,6 +116,7 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(std::conditional_t<NGRAM,
         blen[0] = 0;
         blast[0] = -1;
         if constexpr (NGRAM) cg_init(a.d, &ng.hyps[0][0]);
+        if constexpr (BIAS) ng.st[0][0] = cb_init();
         s_nb = 1;
         s_steps = 0;
     }
@@ -105,6 +136,16 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(std::conditional_t<NGRAM,
             if constexpr (NGRAM) {
                 if (r.par >= 0) slm = cg_candidate_slm(a.d, ng.hyps[cur][k], r.tok);
                 cslm[i] = slm;
+            }
+            if constexpr (BIAS) {
+                CbState st = cb_init();
+                if (r.par >= 0) {
+                    st = cb_step(a.d, ng.st[cur][k], r.tok);
+                    slm = cb_slm(a.d, st);
+                }
+                cslm[i] = slm;
+                cnode[i] = st.node;
+                cbank[i] = st.banked;
             }
             cpar[i] = r.par;
             ctok[i] = r.tok;
@@ -137,6 +178,11 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(std::conditional_t<NGRAM,
                         ng.wflag[rank] = 1;
                     }
                 }
+                if constexpr (BIAS) {
+                    CbState st;
+                    st.node = cnode[i], st.pad = 0, st.banked = cbank[i];
+                    ng.st[cur ^ 1][rank] = st;
+                }
             }
         }
         // (pb / pnb / blen / blast were only read in the candidate phase above, behind the barrier: safe to overwrite)
@@ -152,6 +198,7 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(std::conditional_t<NGRAM,
             if (tid < kept && ng.wflag[tid]) ng.hyps[cur][tid].close_add = add;
             __syncthreads();
         }
+        if constexpr (BIAS) cur ^= 1;
     }
     const int nb = s_nb, steps = s_steps;
     int out = tid;  // the slot a kept hypothesis is written at
@@ -173,6 +220,15 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(std::conditional_t<NGRAM,
         __syncthreads();
         if (tid < nb) out = cs_rank(ckey, cpar, nb, tid);
     }
+    if constexpr (BIAS) {
+        // the open match is given up, and one more stable sort by the same key
+        if (tid < nb) {
+            ckey[tid] = cs_key(ptot[tid], ng.st[cur][tid].banked, a.lp, blen[tid]);
+            cpar[tid] = tid;
+        }
+        __syncthreads();
+        if (tid < nb) out = cs_rank(ckey, cpar, nb, tid);
+    }
     // one thread per slot: a kept hypothesis unrolls its back-pointers
     if (tid == 0) a.out.n_out[b] = nb;
     if (tid < W) {
@@ -180,20 +236,23 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(std::conditional_t<NGRAM,
         if (tid < nb) {
             kept.score = ptot[tid], kept.p_blk = pb[tid], kept.p_nblk = pnb[tid], kept.len = blen[tid];
             if constexpr (NGRAM) kept.score_lm = ng.hyps[cur][tid].slm;
+            if constexpr (BIAS) kept.score_lm = ng.st[cur][tid].banked;
         }
         cs_write_row(a.out, (long long)b * W + out, a.hist_parent, a.hist_tok, hist, W, steps, tid < nb ? tid : -1, kept);
     }
 }
 
-template <bool NGRAM, class Args>
+template <int FUSE, class Args>
 static int launch_beam(const Args& a, hipStream_t s) {
+    constexpr bool BIAS = FUSE == CS_FUSE_BIAS;
     static CnAttrOnce attr_once;  // (one per instantiation)
     int attr_dev;
     if (attr_once.need(&attr_dev)) {
-        CN_HIP_CHECK(hipFuncSetAttribute((const void*)ctc_beam_kernel<NGRAM>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
+        CN_HIP_CHECK(hipFuncSetAttribute((const void*)ctc_beam_kernel<FUSE>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
         attr_once.mark(attr_dev);
     }
-    hipLaunchKernelGGL(ctc_beam_kernel<NGRAM>, dim3(a.B), dim3(256), cs_lds_bytes(a.W, a.P, NGRAM), s, a);
+    const size_t lds = cs_lds_bytes(a.W, a.P, FUSE != CS_FUSE_NONE, 2, BIAS ? 5 : 4, BIAS ? 1 : 0);
+    hipLaunchKernelGGL(ctc_beam_kernel<FUSE>, dim3(a.B), dim3(256), lds, s, a);
     CN_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -205,7 +264,7 @@ int launch_ctc_prefix_beam(const CtcBeamArgs& a, hipStream_t s) {
         cn_set_error(std::string("ctc_beam: ") + (bad ? bad : "hyp_cap must be at least 1"));
         return -1;
     }
-    return launch_beam<false>(a, s);
+    return launch_beam<CS_FUSE_NONE>(a, s);
 }
 
 int launch_ctc_ngram_beam(const CtcNgramArgs& a, hipStream_t s) {
@@ -214,7 +273,7 @@ int launch_ctc_ngram_beam(const CtcNgramArgs& a, hipStream_t s) {
         cn_set_error("ctc_ngram_beam: " + bad);
         return -1;
     }
-    return launch_beam<true>(a, s);
+    return launch_beam<CS_FUSE_NGRAM>(a, s);
 }
 
 // the n-gram search on the host: every pointer a host pointer, no GPU call
@@ -235,6 +294,35 @@ extern "C" int cn_ctc_ngram_beam_host(const cn_ngram_desc* desc, const float* lo
         return -1;
     }
     for (int32_t b = 0; b < B; ++b) cg_search_host(a, b);
+    return 0;
+}
+
+int launch_ctc_bias_beam(const CtcBiasArgs& a, hipStream_t s) {
+    const std::string bad = cb_check(a, true);
+    if (!bad.empty()) {
+        cn_set_error("ctc_bias_beam: " + bad);
+        return -1;
+    }
+    return launch_beam<CS_FUSE_BIAS>(a, s);
+}
+
+// the bias search on the host: every pointer a host pointer, no GPU call
+extern "C" int cn_ctc_bias_beam_host(const cn_bias_desc* desc, const float* logp, const int32_t* top_idx, const float* size_ratio, int32_t B,
+                                     int32_t Tp, int32_t V, int32_t beam, int32_t pruning, double length_penalty, int32_t blank,
+                                     int32_t* hyp, int32_t hyp_cap, int32_t* hyp_len, double* score, double* score_lm, double* p_blk,
+                                     double* p_nblk, int32_t* nbeam) {
+    if (!desc) {
+        cn_set_error("cn_ctc_bias_beam_host: null argument");
+        return -1;
+    }
+    const CtcBiasArgs a = ctc_bias_args(*desc, ctc_beam_args(logp, top_idx, size_ratio, B, Tp, V, beam, pruning, blank, length_penalty,
+                                                             ctc_beam_out(hyp, hyp_cap, hyp_len, score, score_lm, p_blk, p_nblk, nbeam)));
+    const std::string bad = cb_check(a, false);
+    if (!bad.empty()) {
+        cn_set_error("cn_ctc_bias_beam_host: " + bad);
+        return -1;
+    }
+    for (int32_t b = 0; b < B; ++b) cb_search_host(a, b);
     return 0;
 }
 

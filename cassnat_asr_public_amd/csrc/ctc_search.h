@@ -7,7 +7,8 @@
 // probability exceeds 0.95 are skipped.  All scores are Python floats (float64) made of float32 log-posteriors.
 //
 // The variants differ in how score_lm is formed and in where they keep their state, and in nothing else:
-//   ctc_beam.hip    no LM (score_lm = 0) and the word n-gram model: one launch, the frame loop inside, state in LDS
+//   ctc_beam.hip    no LM (score_lm = 0), the word n-gram model and the phrase-biasing automaton (ctc_bias_search.h): one launch, the
+//                   frame loop inside, state in LDS
 //   ctc_lm.hip      the TransformerLM in the loop: one launch per processed frame, state in global memory
 //   cg_search_host  the n-gram search once more, serial, with std::stable_sort (ctc_ngram_search.h)
 // Each forms score_lm itself and takes from here: the frame predicate, the CTC half of a candidate, the sort key, the stable top-W as
@@ -66,10 +67,10 @@ inline const char* cs_check_limits(int W, int P, int Tp, int hyp_cap) {
 
 // dynamic LDS of a frame step over W hypotheses and NC = W * (P + 1) candidates.  Doubles: 3 per hypothesis; key, p_blk, p_nblk,
 // score_ctc (and score_lm) per candidate.  Ints: per hypothesis length and last label, per candidate parent, label, length and last
-// label (ctc_lm_frame_kernel: 4 and 2).
-inline size_t cs_lds_bytes(int W, int P, bool with_lm, int ints_hyp = 2, int ints_cand = 4) {
+// label (ctc_lm_frame_kernel: 4 and 2).  The bias policy adds a double and an int per candidate: the state the candidate arrives at.
+inline size_t cs_lds_bytes(int W, int P, bool with_lm, int ints_hyp = 2, int ints_cand = 4, int more_doubles_cand = 0) {
     const size_t NC = (size_t)W * (P + 1);
-    return (3 * (size_t)W + (with_lm ? 5 : 4) * NC) * 8 + (ints_hyp * (size_t)W + ints_cand * NC) * 4 + 64;
+    return (3 * (size_t)W + ((with_lm ? 5 : 4) + more_doubles_cand) * NC) * 8 + (ints_hyp * (size_t)W + ints_cand * NC) * 4 + 64;
 }
 
 NG_HD double cs_logaddexp(double x, double y) {  // numpy's npy_logaddexp

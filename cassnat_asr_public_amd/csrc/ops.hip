@@ -11,6 +11,7 @@
 
 #include "../../include/cassnat_hip.h"
 #include "../../include/cassnat_hip_attention_proj.h"
+#include "ctc_bias_search.h"
 #include "ctc_ngram_search.h"
 #include "ctc_times_search.h"
 #include "edit_align_search.h"
@@ -1577,6 +1578,30 @@ extern "C" int cn_op_ctc_ngram_beam(const cn_ngram_desc* desc, const float* logp
     a.hist_tok = (int*)sc.alloc((size_t)B * Tp * beam * 4);
     if (!sc.ok()) return -2;
     return sc.finish(launch_ctc_ngram_beam(a, s));
+}
+
+// the bias search kernel (ctc_beam.hip) alone on given log-posteriors and given pruned labels (cn_ctc_beam_bias runs it behind the encoder)
+extern "C" int cn_op_ctc_bias_beam(const cn_bias_desc* desc, const float* logp, const int32_t* top_idx, const float* size_ratio, int32_t B,
+                                   int32_t Tp, int32_t V, int32_t beam, int32_t pruning, double length_penalty, int32_t blank, int32_t* hyp,
+                                   int32_t hyp_cap, int32_t* hyp_len, double* score, double* score_lm, double* p_blk, double* p_nblk,
+                                   int32_t* nbeam, void* stream) {
+    if (!desc) {
+        cn_set_error("cn_op_ctc_bias_beam: null argument");
+        return -1;
+    }
+    CtcBiasArgs a = ctc_bias_args(*desc, ctc_beam_args(logp, top_idx, size_ratio, B, Tp, V, beam, pruning, blank, length_penalty,
+                                                       ctc_beam_out(hyp, hyp_cap, hyp_len, score, score_lm, p_blk, p_nblk, nbeam)));
+    const std::string bad = cb_check(a, false);
+    if (!bad.empty()) {
+        cn_set_error("cn_op_ctc_bias_beam: " + bad);
+        return -1;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    Scratch sc("cn_op_ctc_bias_beam", s);
+    a.hist_parent = (unsigned char*)sc.alloc((size_t)B * Tp * beam);
+    a.hist_tok = (int*)sc.alloc((size_t)B * Tp * beam * 4);
+    if (!sc.ok()) return -2;
+    return sc.finish(launch_ctc_bias_beam(a, s));
 }
 
 extern "C" int cn_op_ffn_fused(float* x_dev, const float* ln_a_dev, const float* ln_b_dev, const float* w1_host,

@@ -51,6 +51,8 @@ def parse_fp8_scope(text):
 # the nine structs of the header, derived from it field for field (abi.py)
 CnConfig, CnDecodeOpts, CnAstOpts, CnFbankOpts, CnAttnDesc, CnNgramDesc, CnChainDesc, CnFrontendDesc, CnGemmDesc = (abi.STRUCTS[n] for n in (
     "cn_config", "cn_decode_opts", "cn_ast_opts", "cn_fbank_opts", "cn_attn_desc", "cn_ngram_desc", "cn_chain_desc", "cn_frontend_desc", "cn_gemm_desc"))
+# the descriptor of the phrase-biasing automaton (include/cassnat_hip_ctc_bias.h declares it beside its entry points)
+CnBiasDesc = abi.CTC_BIAS_STRUCTS["cn_bias_desc"]
 
 
 class HipError(RuntimeError):
@@ -677,6 +679,23 @@ class Engine:
         self._chk(self.L.cn_ctc_beam_ngram(self.handle, C.byref(desc), _ptr(feats), _ptr(size_ratio), B, T, F, C.byref(opts), int(beam),
                                            int(pruning), float(length_penalty), float(lm_scale), _ptr(hyp), cap, _ptr(hlen), _ptr(sc),
                                            _ptr(slm), _ptr(pb), _ptr(pnb), _ptr(nb), current_stream()), "cn_ctc_beam_ngram")
+        return hyp, hlen, sc, slm, pb, pnb, nb
+
+    def ctc_beam_bias(self, desc, feats, size_ratio, opts, beam, pruning, length_penalty):
+        """CTC prefix beam search with contextual phrase biasing in the frame loop (``cn_ctc_beam_bias``): ``desc`` a ``CnBiasDesc``
+        over tables on the feats' device (``models.bias.BiasList.desc``) -> ``ctc_beam_ngram``'s tuple, score_lm the banked bonus."""
+        import torch
+
+        B, T, F = feats.shape
+        cap = subsampled(T) + 1
+        dev = feats.device
+        hyp = torch.empty(B, beam, cap, dtype=torch.int32, device=dev)
+        hlen = torch.empty(B, beam, dtype=torch.int32, device=dev)
+        sc, slm, pb, pnb = (torch.empty(B, beam, dtype=torch.float64, device=dev) for _ in range(4))
+        nb = torch.empty(B, dtype=torch.int32, device=dev)
+        self._chk(self.L.cn_ctc_beam_bias(self.handle, C.byref(desc), _ptr(feats), _ptr(size_ratio), B, T, F, C.byref(opts), int(beam),
+                                          int(pruning), float(length_penalty), _ptr(hyp), cap, _ptr(hlen), _ptr(sc), _ptr(slm), _ptr(pb),
+                                          _ptr(pnb), _ptr(nb), current_stream()), "cn_ctc_beam_bias")
         return hyp, hlen, sc, slm, pb, pnb, nb
 
     # ---- word / token time stamps: forced CTC alignment with spans and confidences (include/cassnat_hip_ctc_times.h)

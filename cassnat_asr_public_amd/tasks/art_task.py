@@ -144,6 +144,9 @@ class ArtTask(BaseTask):
         # correction model over the CTC greedy hypothesis, ctc_att = joint CTC / attention beam search
         if args.decode_type not in ("ctc_att", "ctc_only", "ctc_correct"):
             raise NotImplementedError("decode_type '%s' (ArtTask knows ctc_only, ctc_correct, ctc_att)" % args.decode_type)
+        if (getattr(args, "hip_bias", "") or getattr(args, "hip_bias_model", None) is not None) and args.decode_type != "ctc_only":
+            raise NotImplementedError("--hip_bias biases the CTC prefix beam search (ArtTask: decode_type ctc_only); decode_type '%s' "
+                                      "runs no such search" % args.decode_type)
         self._args = args
         batch_time = util.AverageMeter("Time", ":6.3f")
         progress = util.ProgressMeter(len(self.test_loader), batch_time)

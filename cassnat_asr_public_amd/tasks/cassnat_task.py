@@ -393,6 +393,12 @@ class CassNATTask(BaseTask):
         # args.hip_pipelines (default 2; 1 = the plain loop): beam search, ESA, LM fusion, capture runs and --hip_ctm keep the plain loop
         # (beam_width 1 with lm_weight > 0 is not the greedy finish: every step takes the arg-max of the FUSED row)
         n_pipes = int(getattr(args, "hip_pipelines", 2))
+        if getattr(args, "hip_bias", "") or getattr(args, "hip_bias_model", None) is not None:
+            # (only the CTC prefix beam search is biased: the other paths refuse the flag instead of ignoring it)
+            if args.decode_type not in ("ctc_only", "ctc_att"):
+                path = "ESA (sample_num > 1)" if getattr(args, "sample_num", 0) > 1 else "decode_type '%s'" % args.decode_type
+                raise NotImplementedError("--hip_bias biases the CTC prefix beam search (decode_type ctc_only / ctc_att); %s runs no "
+                                          "such search" % path)
         plain_greedy = (args.beam_width == 1 and getattr(args, "sample_num", 0) <= 1 and not getattr(args, "hip_capture", False)
                         and args.decode_type == "att_only" and not getattr(args, "lm_weight", 0) > 0
                         and not getattr(args, "hip_ctm", ""))

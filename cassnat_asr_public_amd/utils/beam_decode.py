@@ -16,6 +16,11 @@ With ``lm_model`` a ``models.ngram.NgramLM`` (``rank_model: n-gram`` with an ARP
 ``ctc_lm_weight * ln(10)`` times the ARPA score of the word its parent had open, given the parent's word history; after the last
 frame every hypothesis adds its open word and ``</s>``.  The whole frame loop is one launch.  Any other ``lm_model`` object - a
 ``kenlm.Model`` included - is refused.
+
+With ``bias`` a ``models.bias.BiasList`` (``--hip_bias FILE``; the keyword, else ``args.hip_bias_model``) the search rewards the listed
+phrases while they are being spelled (``cn_ctc_beam_bias``; include/cassnat_hip_ctc_bias.h; not in the reference): ``score_lm`` is the
+banked bonus of the completed phrases plus the value of the open match, which is taken back after the last frame.  A bias list together
+with a fused language model is refused.
 """
 import math
 
@@ -27,7 +32,7 @@ from ..models.ngram import NgramLM
 logzero, logone = -1e10, 0  # src/utils/ctc_prefix.py:11-12
 
 
-def ctc_beam_decode(model, src, src_mask, src_size, vocab, args, lm_model=None, engine=None):
+def ctc_beam_decode(model, src, src_mask, src_size, vocab, args, lm_model=None, engine=None, bias=None):
     """``model``: a CassNAT (src/tasks/cassnat_task.py:335-341) or the autoregressive Transformer with its CTC head
     (src/tasks/art_task.py:252-253).  ``engine``: run on this handle (a decode pipeline's) instead of the model's own."""
     ngram = isinstance(lm_model, NgramLM)
@@ -38,6 +43,11 @@ def ctc_beam_decode(model, src, src_mask, src_size, vocab, args, lm_model=None, 
     if ngram and float(getattr(args, "ctc_lm_weight", 0) or 0) != 0 and not lm_model.device_ok:
         raise ValueError("a piece of the vocabulary has a separator behind its leading run: its hypotheses cannot be glued into words, "
                          "so the CTC beam search cannot fuse the n-gram model")
+    if bias is None:
+        bias = getattr(args, "hip_bias_model", None)
+    if bias is not None and lm_model is not None and float(getattr(args, "ctc_lm_weight", 0) or 0) != 0:
+        raise NotImplementedError("--hip_bias together with a language model fused into the CTC beam search (ctc_lm_weight != 0) is not "
+                                  "on the accelerated path: drop one of the two")
     if args.ctc_lp is None:
         raise TypeError("ctc_lp must be a number (with None the reference's sort key is a lambda and sorted() fails)")
     sos = vocab.word2index["sos"]
@@ -53,7 +63,13 @@ def ctc_beam_decode(model, src, src_mask, src_size, vocab, args, lm_model=None, 
     opts.sos = sos
     lm_weight = float(getattr(args, "ctc_lm_weight", 0) or 0)
     slm = None
-    if ngram and lm_weight != 0:
+    if bias is not None:
+        if dev not in bias._dev:
+            bias.cuda(dev)
+        hyp, hlen, sc, slm, pb, pnb, nb = eng.ctc_beam_bias(bias.desc(dev), feats, ratio, opts, int(args.ctc_beam), int(args.ctc_pruning),
+                                                            float(args.ctc_lp))
+        slm = slm.cpu().numpy()
+    elif ngram and lm_weight != 0:
         if dev not in lm_model._dev:
             lm_model.cuda(dev)
         # (ARPA scores are log10, the CTC scores natural logarithms)

@@ -87,6 +87,14 @@ class DecodeParser(object):
         p.add_argument("--hip_ctm_unit", default="word", choices=["word", "token"],
                        help="--hip_ctm: word (default; pieces that begin with the separator start a word, a vocabulary without such "
                             "pieces is written per token) or token (one line per piece)")
+        p.add_argument("--hip_bias", default="", type=str,
+                       help="contextual phrase biasing of the CTC prefix beam search (decode_type ctc_only / ctc_att): a UTF-8 file with "
+                            "one phrase per line as vocabulary pieces separated by blanks (e.g. '▁new ▁york'), optionally a tab and a "
+                            "per-piece score; empty lines and lines starting with # are skipped.  A hypothesis gains the score per piece "
+                            "while it spells a phrase and loses it again when the spelling breaks off")
+        p.add_argument("--hip_bias_score", default=3.0, type=float,
+                       help="--hip_bias: the per-piece score of a phrase without one of its own (default 3.0; natural-log units, the "
+                            "scale of score_ctc)")
         add_score_arguments(p)
         p.add_argument("--hip_score", default="", type=str,
                        help="also score the run against its references: once the result file is written, rank 0 aligns every hypothesis "
