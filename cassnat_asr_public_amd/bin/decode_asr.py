@@ -55,7 +55,7 @@ def main(argv=None):
     task = task_dict[args.task]("test", args)
     task.load_lm_model(args)
     args.hip_bias_model = None
-    if getattr(args, "hip_bias", ""):  # (read once per process; the tasks refuse the paths that run no CTC prefix beam search)
+    if getattr(args, "hip_bias", ""):  # (read once per process; the tasks refuse the paths that run no search --hip_bias_search names)
         from ..models.bias import BiasList
 
         args.hip_bias_model = BiasList.load(args.hip_bias, task.vocab, score=args.hip_bias_score)

@@ -3,6 +3,7 @@
 #include <algorithm>
 #include <cmath>
 
+#include "ast_bias_search.h"
 #include "ast_ngram_search.h"
 #include "model.h"
 
@@ -453,12 +454,18 @@ extern "C" int cn_ast_begin(cn_model* m, const float* feats_dev, int32_t B, int3
 
 namespace cn_host {
 namespace {
+// phrase biasing without CTC: where the rows' nodes come from (the caller's, or carried from the step before) in the fused top-K
+struct AstBiasRows {
+    const int32_t* node = nullptr;
+    AbCarry carry;
+};
+
 // decoder layers on the newest position of n hypotheses -> top-K (token, temperature log-softmax value) per hypothesis
 // dense_bw > 0: the rows are the dense slots b * dense_bw + j of the device beam (utt[row] = row / dense_bw)
 int ast_step_run(cn_model* m, int n, int pos, const int32_t* tok_dev, const int32_t* utt_dev, const int32_t* anc_dev,
                  const uint8_t* keyok_dev, int table_stride, float temperature, int K, int32_t* topk_idx_dev,
                  float* topk_val_dev, int dense_bw, hipStream_t s, float lm_weight = 0.f, float* lm_val_dev = nullptr,
-                 const float* ng_adds_dev = nullptr, int ng_eos = -1) {
+                 const float* ng_adds_dev = nullptr, int ng_eos = -1, const AstBiasRows* bias = nullptr) {
     const int d = m->cfg.d_model, V = m->cfg.vocab_size;
     CN_TRY(launch_ast_embed(tok_dev, m->tgt_lut, m->pe + (size_t)pos * d, m->xd, n, d, sqrtf((float)d), s));
     // DecoderLayer: self attention over the cached prefix, source attention over the memory, feed-forward
@@ -480,6 +487,11 @@ int ast_step_run(cn_model* m, int n, int pos, const int32_t* tok_dev, const int3
         ProfScope ps(m, "ngram_fusion", 0, 1.0 * n * V * 4, s);
         return launch_logsoftmax_class_topk(m->ast_logits, n, V, V, temperature, m->ast_ng.piece_starts, ng_adds_dev, ng_eos,
                                             m->ast_ng_scale, K, topk_idx_dev, topk_val_dev, s);
+    }
+    if (bias) {  // phrase biasing without CTC: top-K of att + term(node of the row, token) over the vocabulary
+        ProfScope ps(m, "bias_fusion", 0, 1.0 * n * V * 4, s);
+        return launch_logsoftmax_bias_topk(m->ast_logits, n, V, V, temperature, m->ast_bias, bias->node, bias->carry, ng_eos, K,
+                                           topk_idx_dev, topk_val_dev, s);
     }
     CN_TRY(launch_logsoftmax_topk(m->ast_logits, n, V, V, temperature, K, topk_idx_dev, topk_val_dev, s));
     return 0;
@@ -510,6 +522,10 @@ extern "C" int cn_ast_step_lm(cn_model* m, int32_t n, int32_t pos, const int32_t
     }
     if (m->ast_ng_on) {
         cn_set_error("cn_ast_step_lm: an n-gram model is attached (cn_ast_attach_ngram); it and a TransformerLM cannot be fused together");
+        return -1;
+    }
+    if (m->ast_bias_on) {
+        cn_set_error("cn_ast_step_lm: a phrase list is attached (cn_ast_attach_bias); it and a TransformerLM cannot be fused together");
         return -1;
     }
     if (!(lm_weight > 0.f) || !m->ast_lm || m->ast_lm->ast_slots < m->ast_slots || m->ast_lm->ast_max_len < m->ast_max_len) {
@@ -552,6 +568,10 @@ extern "C" int cn_ast_attach_ngram(cn_model* m, const cn_ngram_desc* desc, float
         cn_set_error("cn_ast_attach_ngram: lm_scale must be a number");
         return -1;
     }
+    if (m->ast_bias_on) {
+        cn_set_error("cn_ast_attach_ngram: a phrase list is attached (cn_ast_attach_bias); it and an n-gram model cannot be fused together");
+        return -1;
+    }
     m->ast_ng = *desc;
     m->ast_ng_scale = lm_scale;
     m->ast_ng_on = true;
@@ -584,6 +604,62 @@ extern "C" int cn_ast_step_ngram(cn_model* m, int32_t n, int32_t pos, const int3
     CN_TRY(ast_step_run(m, n, pos, tok_dev, utt_dev, anc_dev, keyok_dev, table_stride, temperature, K, topk_idx_dev, topk_val_dev, 0, s,
                         0.f, nullptr, use_ctc ? nullptr : adds_dev, eos));
     if (use_ctc) return launch_ast_ngram_terms(m->ast_ng.piece_starts, adds_dev, eos, topk_idx_dev, n, K, term_dev, s);
+    return 0;
+}
+
+// include/cassnat_hip_ast_bias.h: the phrase list whose terms the step fuses (NULL detaches)
+extern "C" int cn_ast_attach_bias(cn_model* m, const cn_bias_desc* desc) {
+    if (!m || m->cfg.ast != 1) {
+        cn_set_error("cn_ast_attach_bias: the handle must be an autoregressive model (cfg.ast = 1)");
+        return -1;
+    }
+    if (!desc) {
+        m->ast_bias_on = false;
+        m->ast_bias = cn_bias_desc{};
+        return 0;
+    }
+    const std::string bad = cb_check_desc(*desc);
+    if (!bad.empty()) {
+        cn_set_error("cn_ast_attach_bias: " + bad);
+        return -1;
+    }
+    if (m->ast_ng_on) {
+        cn_set_error("cn_ast_attach_bias: an n-gram model is attached (cn_ast_attach_ngram); it and a phrase list cannot be fused together");
+        return -1;
+    }
+    m->ast_bias = *desc;
+    m->ast_bias_on = true;
+    return 0;
+}
+
+extern "C" int cn_ast_step_bias(cn_model* m, int32_t n, int32_t pos, const int32_t* tok_dev, const int32_t* utt_dev,
+                                const int32_t* anc_dev, const uint8_t* keyok_dev, int32_t table_stride, float temperature, int32_t K,
+                                int32_t use_ctc, int32_t eos, const int32_t* node_dev, int32_t* topk_idx_dev, float* topk_val_dev,
+                                float* term_dev, void* stream) {
+    if (!m || m->cfg.ast != 1 || m->ast_slots == 0) {
+        cn_set_error("cn_ast_step_bias: call cn_ast_begin first");
+        return -1;
+    }
+    if (!m->ast_bias_on) {
+        cn_set_error("cn_ast_step_bias: needs a phrase list attached with cn_ast_attach_bias");
+        return -1;
+    }
+    if (m->ast_lm) {
+        cn_set_error("cn_ast_step_bias: a phrase list and a TransformerLM are attached together; detach one");
+        return -1;
+    }
+    CN_TRY(step_check(m, "cn_ast_step_bias", n, pos, table_stride, K < 1 ? -1 : K));
+    if (!node_dev || (use_ctc && !term_dev)) {
+        cn_set_error("cn_ast_step_bias: no node_dev, or use_ctc without term_dev");
+        return -1;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    CN_HIP_CHECK(hipSetDevice(m->cfg.device));
+    AstBiasRows rows;
+    rows.node = node_dev;
+    CN_TRY(ast_step_run(m, n, pos, tok_dev, utt_dev, anc_dev, keyok_dev, table_stride, temperature, K, topk_idx_dev, topk_val_dev, 0, s,
+                        0.f, nullptr, nullptr, eos, use_ctc ? nullptr : &rows));
+    if (use_ctc) return launch_ast_bias_terms(m->ast_bias, node_dev, AbCarry{}, eos, topk_idx_dev, n, K, term_dev, s);
     return 0;
 }
 
@@ -705,6 +781,15 @@ extern "C" int cn_decode_ast(cn_model* m, const float* feats_dev, int32_t B, int
         cn_set_error("cn_decode_ast: an n-gram model is attached and lm_weight > 0 asks for the TransformerLM; the two cannot be fused together");
         return -1;
     }
+    const bool use_bias = m->ast_bias_on;
+    if (use_bias && (use_lm || m->ast_lm)) {
+        cn_set_error("cn_decode_ast: a phrase list is attached (cn_ast_attach_bias) beside a TransformerLM; the two cannot be fused together");
+        return -1;
+    }
+    if (use_bias && use_ng) {
+        cn_set_error("cn_decode_ast: a phrase list and an n-gram model are attached together; detach one");
+        return -1;
+    }
     const int S = B * bw, L = max_len;
     CN_TRY(cn_ast_begin(m, feats_dev, B, T, F, opts, want_ctc, L, S, want_ctc ? K : 0, stream));
     hipStream_t s = (hipStream_t)stream;
@@ -728,6 +813,7 @@ extern "C" int cn_decode_ast(cn_model* m, const float* feats_dev, int32_t B, int
         CN_TRY(ast_alloc(m, (void**)&m->beam_ctc, (size_t)S * K * 4));
         CN_TRY(ast_alloc(m, (void**)&m->beam_lm, (size_t)S * K * 4));
         CN_TRY(ast_alloc(m, (void**)&m->beam_adds, (size_t)S * 2 * 4));
+        for (int i = 0; i < 2; ++i) CN_TRY(ast_alloc(m, (void**)&m->beam_node[i], (size_t)S * 4));
         m->beam_S = S;
         m->beam_L = L;
         m->beam_K = K;
@@ -740,12 +826,26 @@ extern "C" int cn_decode_ast(cn_model* m, const float* feats_dev, int32_t B, int
         // vocabulary; with CTC the same launch runs behind the attention top-K and writes the terms at its candidates
         if (use_ng && !want_ctc)
             CN_TRY(launch_ast_ngram_adds(m->ast_ng, st.tok[cur], L, 1, st.len[cur], -1, S, ao->eos, m->beam_adds, nullptr, 0, nullptr, s));
+        // phrase biasing: a slot's node is one cb_step from the node of the slot that computed the position before (the ancestor table
+        // names it, as it does for the KV cache); the launch that needs it - the fused top-K without CTC, the terms with CTC - computes
+        // it and keeps it for the next step
+        AstBiasRows brows;
+        if (use_bias) {
+            AbCarry& c = brows.carry;
+            c.prev = pos > 0 ? m->beam_node[(pos & 1) ^ 1] : nullptr;
+            c.anc = st.anc[cur];
+            c.tok = st.cur_tok;
+            c.out = m->beam_node[pos & 1];
+            c.ld = L, c.col = pos - 1, c.slots = S;
+        }
         CN_TRY(ast_step_run(m, S, pos, st.cur_tok, st.utt, st.anc[cur], st.keyok[cur], L, ao->temperature, K, m->beam_idx,
                             m->beam_val, bw, s, use_lm ? ao->lm_weight : 0.f, use_lm && want_ctc ? m->beam_lm : nullptr,
-                            use_ng && !want_ctc ? m->beam_adds : nullptr, ao->eos));
+                            use_ng && !want_ctc ? m->beam_adds : nullptr, ao->eos, use_bias && !want_ctc ? &brows : nullptr));
         if (use_ng && want_ctc)
             CN_TRY(launch_ast_ngram_adds(m->ast_ng, st.tok[cur], L, 1, st.len[cur], -1, S, ao->eos, m->beam_adds, m->beam_idx, K,
                                          m->beam_lm, s));
+        if (use_bias && want_ctc)
+            CN_TRY(launch_ast_bias_terms(m->ast_bias, nullptr, brows.carry, ao->eos, m->beam_idx, S, K, m->beam_lm, s));
         if (want_ctc)
             CN_TRY(cn_ast_ctc_score(m, S, pos, st.utt, st.cur_tok, m->beam_idx, K, st.ctc_ref[cur], pos & 1, ao->eos, m->beam_ctc,
                                     stream));
@@ -763,9 +863,9 @@ extern "C" int cn_decode_ast(cn_model* m, const float* feats_dev, int32_t B, int
         q.pad = opts->padding_idx;
         q.use_ctc = want_ctc;
         q.use_lp = ao->use_length_penalty;
-        q.use_lm = use_lm || use_ng;
+        q.use_lm = use_lm || use_ng || use_bias;
         q.lm = m->beam_lm;
-        q.lw = use_ng ? m->ast_ng_scale : ao->lm_weight;
+        q.lw = use_bias ? 1.0f : (use_ng ? m->ast_ng_scale : ao->lm_weight);
         q.w = ao->ctc_weight;
         q.u = ao->one_minus_ctc_weight;
         q.lp = ao->length_penalty;

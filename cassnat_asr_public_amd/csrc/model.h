@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/cassnat_hip.h"
+#include "../../include/cassnat_hip_ctc_bias.h"
 #include "kernels.h"
 
 namespace cn_host {
@@ -220,6 +221,11 @@ struct cn_model {
     bool ast_ng_on = false;
     float ast_ng_scale = 0.f;
     float* beam_adds = nullptr;  // [S][2]
+    // contextual phrase biasing (cn_ast_attach_bias): the desc by value (device tables the caller keeps alive) and the nodes of
+    // cn_decode_ast's beam slots at the last two positions
+    cn_bias_desc ast_bias = {};
+    bool ast_bias_on = false;
+    int32_t* beam_node[2] = {nullptr, nullptr};  // [S] each
     const void* lib_tag = nullptr;  // which of the two libraries created the handle (an attach never crosses them)
 
     // last call

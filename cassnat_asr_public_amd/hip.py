@@ -388,6 +388,42 @@ def edit_align_host(ref, ref_begin, ref_len, hyp, hyp_begin, hyp_len, costs=(1, 
     return cost[:N], counts[:N], plen[:N], ops[:ops_total], ops_begin
 
 
+# ---- AST beam search with phrase biasing: the three kernels alone (include/cassnat_hip_ast_bias.h), on the current stream
+def ast_bias_nodes(desc, tok, lens, flavour=None):
+    """The automaton node of every row of ``tok`` int32 (n, ld) cuda, rows WITHOUT sos, ``lens`` int32 (n,) -> int32 (n,) cuda."""
+    import torch
+
+    out = torch.empty(tok.shape[0], dtype=torch.int32, device=tok.device)
+    L = lib(flavour)
+    check(L.cn_op_ast_bias_nodes(C.byref(desc), _ptr(tok), tok.shape[1], _ptr(lens), tok.shape[0], _ptr(out), current_stream()),
+          "cn_op_ast_bias_nodes", L)
+    return out
+
+
+def ast_bias_terms(desc, node, eos, idx, flavour=None):
+    """The terms of the candidates ``idx`` int32 (n, K) cuda for hypotheses at ``node`` int32 (n,) -> float32 (n, K) cuda."""
+    import torch
+
+    out = torch.empty(idx.shape, dtype=torch.float32, device=idx.device)
+    L = lib(flavour)
+    check(L.cn_op_ast_bias_terms(C.byref(desc), _ptr(node), int(eos), _ptr(idx), idx.shape[0], idx.shape[1], _ptr(out), current_stream()),
+          "cn_op_ast_bias_terms", L)
+    return out
+
+
+def logsoftmax_bias_topk(att, temperature, desc, node, eos, k, flavour=None):
+    """Per row of ``att`` float32 (M, V) cuda the k best of log_softmax(att / T) + term -> (idx int32 (M, k), val float32 (M, k))."""
+    import torch
+
+    M, V = att.shape
+    idx = torch.empty(M, k, dtype=torch.int32, device=att.device)
+    val = torch.empty(M, k, dtype=torch.float32, device=att.device)
+    L = lib(flavour)
+    check(L.cn_op_logsoftmax_bias_topk(_ptr(att), M, V, float(temperature), C.byref(desc), _ptr(node), int(eos), int(k), _ptr(idx), _ptr(val),
+                                       current_stream()), "cn_op_logsoftmax_bias_topk", L)
+    return idx, val
+
+
 class Engine:
     """Owns one ``cn_model`` handle: weights, workspace and the decode pipeline on one GPU."""
 
@@ -553,6 +589,18 @@ class Engine:
         self._chk(self.L.cn_ast_step_ngram(self.handle, tok.shape[0], pos, _ptr(tok), _ptr(utt), _ptr(anc), _ptr(keyok), anc.shape[1],
                                            float(temperature), K, int(use_ctc), int(eos), _ptr(adds), _ptr(topk_idx), _ptr(topk_val),
                                            _ptr(term) if term is not None else None, current_stream()), "cn_ast_step_ngram")
+
+    def ast_attach_bias(self, desc):
+        """Contextual phrase biasing (include/cassnat_hip_ast_bias.h): ``desc`` a ``CnBiasDesc`` over tables on this engine's device
+        (copied; the caller keeps the tables alive while attached); None detaches."""
+        self._chk(self.L.cn_ast_attach_bias(self.handle, C.byref(desc) if desc is not None else None), "cn_ast_attach_bias")
+
+    def ast_step_bias(self, pos, tok, utt, anc, keyok, temperature, K, use_ctc, eos, node, topk_idx, topk_val, term=None):
+        """``ast_step`` with the attached phrase list: ``node`` int32 (n,) cuda.  Without CTC topk_idx / topk_val are the fused
+        top-K; with CTC they are the attention top-K and ``term`` (n, K) receives the terms at it."""
+        self._chk(self.L.cn_ast_step_bias(self.handle, tok.shape[0], pos, _ptr(tok), _ptr(utt), _ptr(anc), _ptr(keyok), anc.shape[1],
+                                          float(temperature), K, int(use_ctc), int(eos), _ptr(node), _ptr(topk_idx), _ptr(topk_val),
+                                          _ptr(term) if term is not None else None, current_stream()), "cn_ast_step_bias")
 
     # ---- CASS-NAT + LM: the finish loop with LM shallow fusion
     def nat_attach_lm(self, lm):

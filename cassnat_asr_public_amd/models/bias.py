@@ -1,5 +1,6 @@
 """Contextual phrase biasing ("hot words") for the CTC prefix beam search (``--hip_bias FILE``; include/cassnat_hip_ctc_bias.h holds
-the semantics; csrc/ctc_bias_search.h walks the tables).  ``BiasList.load`` reads a phrase list written in vocabulary pieces into an
+the semantics; csrc/ctc_bias_search.h walks the tables) and, with ``--hip_bias_search att``, for the AST beam search
+(include/cassnat_hip_ast_bias.h; csrc/ast_bias_search.h).  ``BiasList.load`` reads a phrase list written in vocabulary pieces into an
 Aho-Corasick automaton, ``cuda(dev)`` places its tables on a device and ``desc(dev)`` gives the ``cn_bias_desc`` over them - the manner
 of models.ngram.NgramLM.  The automaton is built on the host in plain Python and numpy (the tables travel as torch tensors, the
 descriptor is hip.CnBiasDesc); no tokenizer is involved.
@@ -7,6 +8,7 @@ descriptor is hip.CnBiasDesc); no tokenizer is involved.
 One ``BiasList`` serves all decode workers of a process: ``cuda`` and ``desc`` take a lock, a device's tables are placed once and
 never replaced, so a descriptor handed out stays valid as long as the object lives.
 """
+import ctypes as C
 import math
 import threading
 
@@ -179,6 +181,40 @@ class BiasList(object):
         """The cn_bias_desc over the host tables, or over those of a device ``cuda`` placed."""
         with self._lock:
             return self._desc_locked(where)
+
+    # ---- the AST beam search's share (include/cassnat_hip_ast_bias.h), on the host: what Transformer.beam_decode's hip_host_beam loop asks
+    def ast_nodes_host(self, rows, lens):
+        """The node of every hypothesis ``rows`` int32 (n, ld), row r its first ``lens[r]`` ids WITHOUT sos -> int32 (n,)
+        (cn_ast_bias_nodes_host: the device's step function on the host tables)."""
+        rows = np.ascontiguousarray(rows, np.int32)
+        rows = rows.reshape(len(rows), -1)
+        lens = np.ascontiguousarray(lens, np.int32).reshape(-1)
+        assert lens.size == rows.shape[0]
+        out = np.zeros(rows.shape[0], np.int32)
+        if rows.shape[0] == 0:
+            return out
+        if rows.shape[1] == 0:  # (the entry wants a stride; rows without a column are empty hypotheses)
+            rows, lens = np.zeros((rows.shape[0], 1), np.int32), np.zeros_like(lens)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        L = hip.lib()
+        hip.check(L.cn_ast_bias_nodes_host(C.byref(self.desc()), p(rows), rows.shape[1], p(lens), rows.shape[0], p(out)),
+                  "cn_ast_bias_nodes_host", L)
+        return out
+
+    def ast_terms_host(self, nodes, idx, eos):
+        """The terms float32 (n, K) of the candidates ``idx`` int32 (n, K) for hypotheses at ``nodes`` int32 (n,)
+        (cn_ast_bias_terms_host)."""
+        nodes = np.ascontiguousarray(nodes, np.int32).reshape(-1)
+        idx = np.ascontiguousarray(idx, np.int32)
+        idx = idx.reshape(nodes.size, -1)
+        out = np.zeros(idx.shape, np.float32)
+        if idx.size == 0:
+            return out
+        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        L = hip.lib()
+        hip.check(L.cn_ast_bias_terms_host(C.byref(self.desc()), p(nodes), int(eos), p(idx), idx.shape[0], idx.shape[1], p(out)),
+                  "cn_ast_bias_terms_host", L)
+        return out
 
     def _desc_locked(self, where):
         if where not in self._desc:

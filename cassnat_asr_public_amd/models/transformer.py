@@ -120,7 +120,7 @@ class Transformer(nn.Module):
             self.build_engine(batch, frames)
         return self._engine
 
-    def beam_decode(self, src, src_mask, vocab, args, lm_model=None, engine=None, lm_engine=None):
+    def beam_decode(self, src, src_mask, vocab, args, lm_model=None, engine=None, lm_engine=None, bias=None):
         """Same contract as the reference's Transformer.beam_decode (src/models/transformer.py:122-241), LM shallow fusion
         included (``args.lm_weight > 0`` with ``lm_model`` a models.lm.TransformerLM).  ``engine``: run on this handle (a decode
         pipeline's, see ``new_engine``) instead of the model's own; ``lm_engine``: the pipeline's LM handle
@@ -129,10 +129,21 @@ class Transformer(nn.Module):
         ``lm_model`` a models.ngram.NgramLM (``rank_model: n-gram`` with an ARPA file): word n-gram shallow fusion
         (include/cassnat_hip_ast_ngram.h) - the model's device tables are attached with float32(lm_weight * ln 10) for the call.
         The ``hip_host_beam`` loop takes its per-hypothesis adds from ``lm_model.ast_adds_host``; any object that offers that
-        method beside ``desc`` / ``cuda`` / ``device_ok`` serves there."""
+        method beside ``desc`` / ``cuda`` / ``device_ok`` serves there.
+
+        ``bias`` a models.bias.BiasList (the keyword, else ``args.hip_bias_model`` when ``args.hip_bias_search == "att"``):
+        contextual phrase biasing (include/cassnat_hip_ast_bias.h) - the list's device tables are attached for the call.  The
+        ``hip_host_beam`` loop takes the hypotheses' nodes from ``bias.ast_nodes_host`` and, with CTC, the terms of its update from
+        ``bias.ast_terms_host``; any object that offers those two methods beside ``desc`` / ``cuda`` serves there.  A list together
+        with a fused language model is refused."""
         lm_weight = float(getattr(args, "lm_weight", 0) or 0)
+        if bias is None and getattr(args, "hip_bias_search", "ctc") == "att":
+            bias = getattr(args, "hip_bias_model", None)
+        if bias is not None and lm_weight > 0:
+            raise NotImplementedError("--hip_bias (hip_bias_search att) together with a language model fused into the AST beam search "
+                                      "(lm_weight > 0) is not on the accelerated path: drop one of the two")
         if lm_weight <= 0:
-            return self._beam_decode(src, args, vocab, engine, None, 0.0)
+            return self._beam_decode(src, args, vocab, engine, None, 0.0, bias=bias)
         if lm_model is None:
             raise ValueError("beam_decode: lm_weight > 0 needs lm_model")
         if hasattr(lm_model, "ast_adds_host"):
@@ -146,7 +157,7 @@ class Transformer(nn.Module):
         lm_eng = lm_engine if lm_engine is not None else lm_model.step_engine(B * bw)
         return self._beam_decode(src, args, vocab, engine, lm_eng, lm_weight)
 
-    def _beam_decode(self, src, args, vocab, engine, lm_eng, lm_weight, ngram=None, ngram_scale=0.0):
+    def _beam_decode(self, src, args, vocab, engine, lm_eng, lm_weight, ngram=None, ngram_scale=0.0, bias=None):
         sos, eos = vocab.word2index["sos"], vocab.word2index["eos"]
         assert vocab.word2index["blank"] == args.padding_idx
         dev = torch.device("cuda", getattr(self, "_device", torch.cuda.current_device()))
@@ -162,18 +173,24 @@ class Transformer(nn.Module):
         opts = hip.CnDecodeOpts(padding_idx=int(args.padding_idx), sos=sos, beam_width=1)
         eng.ast_attach_lm(lm_eng)  # (None detaches: a handle never keeps an LM from an earlier call)
         eng.ast_attach_ngram(None)
+        eng.ast_attach_bias(None)
         try:
             if ngram is not None:
                 ngram.cuda(dev)
                 eng.ast_attach_ngram(ngram.desc(dev), ngram_scale)
-            return self._beam_search(eng, feats, opts, args, sos, eos, bw, K, use_ctc, max_step, lm_weight, dev, ngram, ngram_scale)
+            if bias is not None:
+                bias.cuda(dev)
+                eng.ast_attach_bias(bias.desc(dev))
+            return self._beam_search(eng, feats, opts, args, sos, eos, bw, K, use_ctc, max_step, lm_weight, dev, ngram, ngram_scale, bias)
         finally:
             if lm_eng is not None:
                 eng.ast_attach_lm(None)
             if ngram is not None:
                 eng.ast_attach_ngram(None)
+            if bias is not None:
+                eng.ast_attach_bias(None)
 
-    def _beam_search(self, eng, feats, opts, args, sos, eos, bw, K, use_ctc, max_step, lm_weight, dev, ngram=None, ngram_scale=0.0):
+    def _beam_search(self, eng, feats, opts, args, sos, eos, bw, K, use_ctc, max_step, lm_weight, dev, ngram=None, ngram_scale=0.0, bias=None):
         B = feats.shape[0]
         max_len = max_step + 1
         use_lm = lm_weight > 0
@@ -200,7 +217,7 @@ class Transformer(nn.Module):
         eng.ast_begin(feats, opts, use_ctc, max_len, B * bw, K if use_ctc else 0)
         w32 = np.float32(args.ctc_weight)
         u32 = np.float32(1 - args.ctc_weight)
-        lw32 = np.float32(ngram_scale if ngram is not None else lm_weight)
+        lw32 = np.float32(1.0 if bias is not None else (ngram_scale if ngram is not None else lm_weight))
 
         beams = [[{"score": 0.0, "hyp": [sos], "anc": [], "ctc_ref": -1 - b, "ctc_prev": np.float32(0.0)}] for b in range(B)]
         idx_d = torch.empty(B * bw, K, dtype=torch.int32, device=dev)
@@ -229,6 +246,13 @@ class Transformer(nn.Module):
                 adds = np.ascontiguousarray(ngram.ast_adds_host(rows, np.full(n, i, np.int32), eos), np.float32).reshape(n, 2)
                 eng.ast_step_ngram(i, tok_d, utt_d, anc_d, keyok_d, args.T, K, use_ctc, eos, torch.from_numpy(adds).to(dev), idx_d[:n],
                                    val_d[:n], lm_d[:n])
+            elif bias is not None:  # as use_lm, the LM row being the phrase terms for the hypotheses' nodes, the weight 1
+                rows = np.zeros((n, max(1, i)), np.int32)
+                for k, (_, s) in enumerate(live):
+                    rows[k, :i] = s["hyp"][1:]
+                nodes = np.ascontiguousarray(bias.ast_nodes_host(rows, np.full(n, i, np.int32)), np.int32).reshape(n)
+                eng.ast_step_bias(i, tok_d, utt_d, anc_d, keyok_d, args.T, K, use_ctc, eos, torch.from_numpy(nodes).to(dev), idx_d[:n],
+                                  val_d[:n], lm_d[:n])
             elif use_lm:  # no CTC: val = top-K of att + lm_weight * lm; with CTC: attention top-K and the LM at those candidates
                 eng.ast_step_lm(i, tok_d, utt_d, anc_d, keyok_d, args.T, K, lm_weight, use_ctc, idx_d[:n], val_d[:n], lm_d[:n])
             else:
@@ -241,7 +265,9 @@ class Transformer(nn.Module):
             if use_ctc:
                 prev = np.array([s["ctc_prev"] for _, s in live], np.float32)[:, None]
                 local = w32 * (ctc - prev) + u32 * att  # float32, same op order as transformer.py:205-206
-                if use_lm or ngram is not None:
+                if bias is not None:  # (the terms of this update are the host's, not the device's)
+                    local = local + lw32 * np.ascontiguousarray(bias.ast_terms_host(nodes, indices, eos), np.float32).reshape(n, K)
+                elif use_lm or ngram is not None:
                     local = local + lw32 * lm_d[:n].cpu().numpy()  # transformer.py:208-209
                 local_idx = np.argsort(-local, axis=1, kind="stable")[:, :bw]
                 local_scores = np.take_along_axis(local, local_idx, 1)

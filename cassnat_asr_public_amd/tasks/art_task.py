@@ -144,9 +144,18 @@ class ArtTask(BaseTask):
         # correction model over the CTC greedy hypothesis, ctc_att = joint CTC / attention beam search
         if args.decode_type not in ("ctc_att", "ctc_only", "ctc_correct"):
             raise NotImplementedError("decode_type '%s' (ArtTask knows ctc_only, ctc_correct, ctc_att)" % args.decode_type)
-        if (getattr(args, "hip_bias", "") or getattr(args, "hip_bias_model", None) is not None) and args.decode_type != "ctc_only":
-            raise NotImplementedError("--hip_bias biases the CTC prefix beam search (ArtTask: decode_type ctc_only); decode_type '%s' "
-                                      "runs no such search" % args.decode_type)
+        bias_att = False
+        if getattr(args, "hip_bias", "") or getattr(args, "hip_bias_model", None) is not None:
+            bias_att = getattr(args, "hip_bias_search", "ctc") == "att"
+            if bias_att and args.decode_type != "ctc_att":
+                raise NotImplementedError("--hip_bias_search att biases the attention beam search (ArtTask: decode_type ctc_att); "
+                                          "decode_type '%s' runs no such search" % args.decode_type)
+            if not bias_att and args.decode_type != "ctc_only":
+                raise NotImplementedError("--hip_bias biases the CTC prefix beam search (ArtTask: decode_type ctc_only); decode_type '%s' "
+                                          "runs no such search (--hip_bias_search att biases the attention beam search of ctc_att)"
+                                          % args.decode_type)
+        # (--hip_bias_search att: every pipeline's engine attaches the one list; its tables are shared read-only)
+        bias = getattr(args, "hip_bias_model", None) if bias_att else None
         self._args = args
         batch_time = util.AverageMeter("Time", ":6.3f")
         progress = util.ProgressMeter(len(self.test_loader), batch_time)
@@ -178,7 +187,7 @@ class ArtTask(BaseTask):
                             recog = self.model.fast_decode_with_ctc(feats, src_mask, self.vocab, args, self.lm_model, engine=engines[k])
                         else:
                             recog = self.model.beam_decode(feats, src_mask, self.vocab, args, self.lm_model, engine=engines[k],
-                                                           lm_engine=lm_engines[k])
+                                                           lm_engine=lm_engines[k], bias=bias)
                         lines = [utt + " " + " ".join(hyp_to_words(seqs[0]["hyp"], self.vocab, args.padding_idx))
                                  for utt, seqs in zip(utt_list, recog)]
                         if getattr(args, "hip_ctm", ""):  # (on this worker's engine and stream, a second encoder pass: utils.ctm)

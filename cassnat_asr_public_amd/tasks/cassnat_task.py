@@ -395,6 +395,10 @@ class CassNATTask(BaseTask):
         n_pipes = int(getattr(args, "hip_pipelines", 2))
         if getattr(args, "hip_bias", "") or getattr(args, "hip_bias_model", None) is not None:
             # (only the CTC prefix beam search is biased: the other paths refuse the flag instead of ignoring it)
+            if getattr(args, "hip_bias_search", "ctc") == "att":
+                raise NotImplementedError("--hip_bias_search att biases the attention beam search of --task art (decode_type ctc_att); "
+                                          "CassNATTask runs no such search (its --hip_bias serves decode_type ctc_only / ctc_att with "
+                                          "--hip_bias_search ctc)")
             if args.decode_type not in ("ctc_only", "ctc_att"):
                 path = "ESA (sample_num > 1)" if getattr(args, "sample_num", 0) > 1 else "decode_type '%s'" % args.decode_type
                 raise NotImplementedError("--hip_bias biases the CTC prefix beam search (decode_type ctc_only / ctc_att); %s runs no "

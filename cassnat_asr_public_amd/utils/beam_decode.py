@@ -43,7 +43,7 @@ def ctc_beam_decode(model, src, src_mask, src_size, vocab, args, lm_model=None, 
     if ngram and float(getattr(args, "ctc_lm_weight", 0) or 0) != 0 and not lm_model.device_ok:
         raise ValueError("a piece of the vocabulary has a separator behind its leading run: its hypotheses cannot be glued into words, "
                          "so the CTC beam search cannot fuse the n-gram model")
-    if bias is None:
+    if bias is None and getattr(args, "hip_bias_search", "ctc") != "att":  # (att: the list is the attention beam search's)
         bias = getattr(args, "hip_bias_model", None)
     if bias is not None and lm_model is not None and float(getattr(args, "ctc_lm_weight", 0) or 0) != 0:
         raise NotImplementedError("--hip_bias together with a language model fused into the CTC beam search (ctc_lm_weight != 0) is not "

@@ -95,6 +95,10 @@ class DecodeParser(object):
         p.add_argument("--hip_bias_score", default=3.0, type=float,
                        help="--hip_bias: the per-piece score of a phrase without one of its own (default 3.0; natural-log units, the "
                             "scale of score_ctc)")
+        p.add_argument("--hip_bias_search", default="ctc", choices=["ctc", "att"],
+                       help="--hip_bias: which search the list biases.  ctc (default): the CTC prefix beam search.  att: the attention "
+                            "beam search of --task art, decode_type: ctc_att (the joint CTC / attention search), where a candidate token "
+                            "adds what it changes in the open match and eos gives the open match up; every other path refuses att")
         add_score_arguments(p)
         p.add_argument("--hip_score", default="", type=str,
                        help="also score the run against its references: once the result file is written, rank 0 aligns every hypothesis "

@@ -12,6 +12,8 @@ positions).  ``--beam`` / ``--ctc-beam``: run_art.sh stage 3 uses 20 / 30.
 ``--ngram-entries`` entries (time_esa.write_synthetic_arpa) over a vocabulary of one-piece words and continuation pieces.
 ``--alternate none,ngram,lm_recipe --rounds 5``: the legs named take turns in one process, ``--rounds`` timed decodes each (after
 one warm-up each); one JSON line per leg with the median and the range of ms per step and utt/s, and nothing else is measured.
+A leg ``biasN`` (``bias10``, ``bias5000``) decodes with a synthetic phrase list of N phrases (include/cassnat_hip_ast_bias.h; its
+``ngram_entries`` field holds N); with ``--ctc-weight 0`` its fused top-K kernel runs in place of the terms kernel.
 
     python tools/time_ast.py [--model transformer|conformer] [--batch 32] [--frames 1000] [--precision bf16] [--ctc-weight 0.3] [--ratio 0.3]
                              [--lm none|lm_small|lm_recipe|ngram] [--lm-weight 0.6] [--beam 10] [--ctc-beam 15] [--ngram-entries N]
@@ -58,6 +60,19 @@ def make_ngram(vocab, entries):
     return lm, n
 
 
+def make_bias(vocab_size, phrases, seed=5):
+    """A synthetic phrase list for the ``biasN`` legs: N phrases of 1 to 4 random pieces (no special id), scores 0.5 .. 3."""
+    import numpy as np
+
+    from cassnat_asr_public_amd.models.bias import BiasList
+
+    rng = np.random.RandomState(seed)
+    out = {}
+    while len(out) < phrases:
+        out[tuple(int(t) for t in rng.randint(4, vocab_size, rng.randint(1, 5)))] = float(rng.choice([0.5, 1.0, 2.0, 3.0]))
+    return BiasList.from_phrases(out).cuda()
+
+
 def make_transformer_lm(preset, vocab_size, precision):
     lm_args = synth.make_args_lm(preset, vocab_size=vocab_size)
     lm_args.hip_precision = precision
@@ -75,20 +90,23 @@ def alternate(a, args, model, src, mask):
     legs = {}
     for name in a.alternate.split(","):
         largs = copy.copy(args)
-        largs.lm_weight = 0 if name == "none" else a.lm_weight
-        entries = None
+        largs.lm_weight = 0 if name == "none" or name.startswith("bias") else a.lm_weight
+        entries, bias = None, None
         if name == "none":
             lm = None
+        elif name.startswith("bias"):  # (biasN: a list of N phrases, include/cassnat_hip_ast_bias.h)
+            lm, entries = None, int(name[4:])
+            bias = make_bias(args.vocab_size, entries)
         elif name == "ngram":
             lm, entries = make_ngram(vocab, a.ngram_entries)
         else:
             lm = make_transformer_lm(name, args.vocab_size, a.precision)
-        legs[name] = dict(args=largs, lm=lm, entries=entries, sec=[], steps=0)
+        legs[name] = dict(args=largs, lm=lm, bias=bias, entries=entries, sec=[], steps=0)
     for r in range(a.rounds + 1):  # (round 0 warms every leg up)
         for name, leg in legs.items():
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            beams = model.beam_decode(src, mask, vocab, leg["args"], leg["lm"])
+            beams = model.beam_decode(src, mask, vocab, leg["args"], leg["lm"], bias=leg["bias"])
             torch.cuda.synchronize()
             if r:
                 leg["sec"].append(time.perf_counter() - t0)
@@ -118,7 +136,7 @@ def main():
                          "step occupies a handful of CUs, so throughput - not latency - scales with pipelines")
     ap.add_argument("--lm", choices=("none", "lm_small", "lm_recipe", "ngram"), default="none")
     ap.add_argument("--ngram-entries", type=int, default=1000000)
-    ap.add_argument("--alternate", default="", help="comma-separated legs (none, ngram, lm_small, lm_recipe) that take turns in one process")
+    ap.add_argument("--alternate", default="", help="comma-separated legs (none, ngram, biasN, lm_small, lm_recipe) that take turns in one process")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--lm-weight", type=float, default=0.6)
     ap.add_argument("--beam", type=int, default=10)
