@@ -20,6 +20,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <string>
 
 #include "proj_x3_phase.h"
 
@@ -601,6 +602,24 @@ extern "C" int cn_debug_ffn_x3_stamps(unsigned long long* out, int n_wg) {
 
 bool ffn_x3_applies(int d, int dff) { return d == FX_D && dff % 128 == 0 && dff >= 128 && dff <= 2048 && !cn_exp_env("CASSNAT_NO_FFN_X3"); }
 
+// which of the nine instantiations a launch is (kernels.h): decided on the host alone, cn_ffn_x3_form reports it
+int ffn_x3_form(const char* who, bool has_ctx, bool has_tail, int tail_n, bool mix, int act) {
+    const std::string w = std::string(who) + ": ";
+    if (act != FF_ACT_RELU && act != FF_ACT_SWISH) {
+        cn_set_error(w + "unknown activation");
+        return -1;
+    }
+    if (has_tail && (tail_n < 128 || tail_n % 128 != 0 || tail_n > 1024)) {
+        cn_set_error(w + "tail_n=" + std::to_string(tail_n) + " must be a multiple of 128 in [128, 1024]");
+        return -1;
+    }
+    if (act == FF_ACT_SWISH && (mix || has_ctx || has_tail)) {
+        cn_set_error(w + "the Swish activation runs in the plain split form only (no mixed arithmetic, no row-chain form)");
+        return -1;
+    }
+    return (has_ctx ? FFN_X3_PRO : 0) | (has_tail ? FFN_X3_TAIL : 0) | (mix ? FFN_X3_MIX : 0) | (act == FF_ACT_SWISH ? FFN_X3_SWISH : 0);
+}
+
 int launch_ffn_x3(const FfnX3Args& a, hipStream_t s) {
     if (!ffn_x3_applies(a.d, a.dff)) {
         cn_set_error("ffn_x3: needs d_model == 256 and d_ff % 128 == 0, d_ff <= 2048");
@@ -643,6 +662,8 @@ int launch_ffn_x3(const FfnX3Args& a, hipStream_t s) {
         cn_set_error("ffn_x3: residual stream beyond 2 GiB");
         return -1;
     }
+    const int form = ffn_x3_form("ffn_x3", pro, tail, a.tail_n, a.mix, a.act);
+    if (form < 0) return -1;
     p.ctx = reinterpret_cast<const unsigned char*>(a.ctx);
     p.ldctx_bytes = (long long)a.ldctx * 4;
     p.pro = PxPhase{reinterpret_cast<const unsigned char*>(a.wo_p), a.bo, a.x, FX_D, a.x, FX_D, 1.f, a.M, FX_D};
@@ -659,25 +680,17 @@ int launch_ffn_x3(const FfnX3Args& a, hipStream_t s) {
         }                                                                                                                  \
         hipLaunchKernelGGL((ffn_x3_kernel<PRO_, TAIL_, MIX_, SW_>), grid, dim3(256), LDS_, s, p);                    \
     }
-    if (a.act == FF_ACT_SWISH) {
-        if (a.mix || pro || tail) {
-            cn_set_error("ffn_x3: the Swish activation runs in the plain split form only (no mixed arithmetic, no row-chain form)");
-            return -1;
-        }
-        FX_LAUNCH(false, false, false, true, FX_LDS)
-    } else if (a.act != FF_ACT_RELU) {
-        cn_set_error("ffn_x3: unknown activation");
-        return -1;
-    } else if (a.mix) {
-        if (pro && tail) FX_LAUNCH(true, true, true, false, FX_LDS_TAIL)
-        else if (pro) FX_LAUNCH(true, false, true, false, FX_LDS)
-        else if (tail) FX_LAUNCH(false, true, true, false, FX_LDS_TAIL)
-        else FX_LAUNCH(false, false, true, false, FX_LDS)
-    } else {
-        if (pro && tail) FX_LAUNCH(true, true, false, false, FX_LDS_TAIL)
-        else if (pro) FX_LAUNCH(true, false, false, false, FX_LDS)
-        else if (tail) FX_LAUNCH(false, true, false, false, FX_LDS_TAIL)
-        else FX_LAUNCH(false, false, false, false, FX_LDS)
+    switch (form) {
+        case FFN_X3_SWISH: FX_LAUNCH(false, false, false, true, FX_LDS) break;
+        case FFN_X3_PRO | FFN_X3_TAIL | FFN_X3_MIX: FX_LAUNCH(true, true, true, false, FX_LDS_TAIL) break;
+        case FFN_X3_PRO | FFN_X3_MIX: FX_LAUNCH(true, false, true, false, FX_LDS) break;
+        case FFN_X3_TAIL | FFN_X3_MIX: FX_LAUNCH(false, true, true, false, FX_LDS_TAIL) break;
+        case FFN_X3_MIX: FX_LAUNCH(false, false, true, false, FX_LDS) break;
+        case FFN_X3_PRO | FFN_X3_TAIL: FX_LAUNCH(true, true, false, false, FX_LDS_TAIL) break;
+        case FFN_X3_PRO: FX_LAUNCH(true, false, false, false, FX_LDS) break;
+        case FFN_X3_TAIL: FX_LAUNCH(false, true, false, false, FX_LDS_TAIL) break;
+        case 0: FX_LAUNCH(false, false, false, false, FX_LDS) break;
+        default: cn_set_error("ffn_x3: no such instantiation"); return -1;
     }
 #undef FX_LAUNCH
     CN_HIP_CHECK(hipGetLastError());

@@ -329,6 +329,10 @@ struct FfnX3Args {
     int act = FF_ACT_RELU;
 };
 bool ffn_x3_applies(int d, int dff);
+// the instantiation launch_ffn_x3 picks, as bits FFN_X3_PRO | TAIL | MIX | SWISH, or -1 (error set, starting with `who`) where it
+// refuses: a tail (has_tail) whose tail_n is no multiple of 128 in [128, 1024], Swish with mix, ctx or a tail, an unknown act
+enum { FFN_X3_PRO = 1, FFN_X3_TAIL = 2, FFN_X3_MIX = 4, FFN_X3_SWISH = 8 };
+int ffn_x3_form(const char* who, bool has_ctx, bool has_tail, int tail_n, bool mix, int act);
 int launch_ffn_x3(const FfnX3Args& a, hipStream_t s);
 size_t ffn_x3_stream_bytes(int dff);
 void pack_ffn_x3(const float* w1, const float* w2, int dff, uint16_t* out, bool mix = false);
@@ -462,6 +466,10 @@ struct ProjX3Args {
     int M = 0, N = 0;
 };
 bool proj_x3_applies(int N, int K);
+// why launch_proj_x3 refuses these arguments (a static message), or null; wp and bias are not looked at when `pointers` is false
+const char* proj_x3_refusal(const ProjX3Args& a, bool pointers = true);
+// what launch_proj_x3 launches for M rows and N columns: 32 mt rows per workgroup, `chunks` column chunks (gridDim.y)
+void proj_x3_form(int M, int N, int* mt, int* chunks);
 int launch_proj_x3(const ProjX3Args& a, hipStream_t s);
 size_t proj_x3_off(int n, int k);  // byte offset of W[n][k]'s hi half in the packed stream; the lo half 1024 bytes further
 void pack_proj_x3(const float* w, int N, unsigned char* out);

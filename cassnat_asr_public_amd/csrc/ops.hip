@@ -1708,8 +1708,22 @@ extern "C" int cn_op_x3_chain(float* x_dev, const void* ctx_dev, const float* wo
                               const float* b2_dev, const float* nln_a_dev, const float* nln_b_dev, void* xn_out_dev,
                               const float* wt_host, const float* bt_dev, void* tail_out_dev, int32_t tail_n, int32_t M, int32_t dff,
                               float eps, int32_t mix, void* stream) {
-    if (!ffn_x3_applies(256, dff) || (wt_host && !proj_x3_applies(tail_n, 256))) {
-        cn_set_error("cn_op_x3_chain: d_ff a multiple of 128 (<= 2048), tail_n a multiple of 32 (<= 1024)");
+    // everything launch_ffn_x3 would refuse is refused here, before the weights are packed and anything touches the device
+    if (!ffn_x3_applies(256, dff)) {
+        cn_set_error("cn_op_x3_chain: d_ff=" + std::to_string(dff) + " must be a multiple of 128 in [128, 2048]");
+        return -1;
+    }
+    if (ffn_x3_form("cn_op_x3_chain", ctx_dev != nullptr, wt_host != nullptr, tail_n, mix != 0, FF_ACT_RELU) < 0) return -1;
+    if (wt_host && (!nln_a_dev || !nln_b_dev)) {
+        cn_set_error("cn_op_x3_chain: a tail projection needs the next LayerNorm (nln_a_dev, nln_b_dev): it projects LN_next(x)");
+        return -1;
+    }
+    if (wt_host && (!bt_dev || !tail_out_dev)) {
+        cn_set_error("cn_op_x3_chain: a tail projection needs its bias and its output (bt_dev, tail_out_dev)");
+        return -1;
+    }
+    if (ctx_dev && (!wo_host || !bo_dev)) {
+        cn_set_error("cn_op_x3_chain: ctx_dev needs the output projection's weights and bias (wo_host, bo_dev)");
         return -1;
     }
     Scratch sc("cn_op_x3_chain", (hipStream_t)stream);
@@ -2020,23 +2034,89 @@ extern "C" int cn_op_proj_x3(const float* a_host, const float* w_host, const flo
         cn_set_error("cn_op_proj_x3: N must be a multiple of 32, at most 1024");
         return -1;
     }
-    std::vector<unsigned char> hw((size_t)N * 1024);
-    pack_proj_x3(w_host, N, hw.data());
     const std::vector<unsigned char> hx = split_rows256(a_host, M);
     Scratch sc("cn_op_proj_x3", (hipStream_t)stream);
-    ProjX3Args a;
-    a.A = sc.upload(hx.data(), hx.size());
-    a.lda = 256;
-    a.wp = sc.upload(hw.data(), hw.size());
-    a.bias = (const float*)sc.upload(bias_host, (size_t)N * 4);
+    cn_proj_x3_desc d = {};
+    d.a_dev = sc.upload(hx.data(), hx.size());
     if (!sc.ok()) return -2;
-    a.C = c_dev;
-    a.ldc = N;
-    a.c_f32 = split_out ? 0 : 1;
-    a.resid = resid_dev;
-    a.ldr = N;
-    a.resid_scale = resid_scale;
-    a.M = M;
-    a.N = N;
+    d.w_host = w_host;
+    d.bias_host = bias_host;
+    d.c_dev = c_dev;
+    d.resid_dev = resid_dev;
+    d.lda = 256;
+    d.ldc = d.ldr = N;
+    d.M = M;
+    d.N = N;
+    d.split_out = split_out;
+    d.resid_scale = resid_scale;
+    return cn_op_proj_x3_desc(&d, stream);
+}
+
+// The same projection through a descriptor that reaches every field of ProjX3Args: A is on the device already (split-bf16 rows of
+// lda elements), every stride is the caller's.  Everything launch_proj_x3 would refuse is refused here, before the weights are
+// packed and anything touches the device.
+extern "C" int cn_op_proj_x3_desc(const cn_proj_x3_desc* d, void* stream) {
+    auto refuse = [](const std::string& why) {
+        cn_set_error("cn_op_proj_x3_desc: " + why);
+        return -1;
+    };
+    if (!d) return refuse("null descriptor");
+    if (!d->a_dev || !d->w_host || !d->bias_host || !d->c_dev) return refuse("null a_dev, w_host, bias_host or c_dev");
+    if (d->reserved != 0) return refuse("the reserved word must be 0");
+    if (d->M < 0) return refuse("M=" + std::to_string(d->M) + " is negative");
+    if (d->split_out != 0 && d->split_out != 1) return refuse("split_out must be 0 or 1");
+    ProjX3Args a;
+    a.A = d->a_dev;
+    a.lda = d->lda;
+    a.C = d->c_dev;
+    a.ldc = d->ldc;
+    a.c_f32 = d->split_out ? 0 : 1;
+    a.resid = d->resid_dev;
+    a.ldr = d->ldr;
+    a.resid_scale = d->resid_scale;
+    a.M = d->M;
+    a.N = d->N;
+    if (const char* why = proj_x3_refusal(a, false))
+        return refuse(std::string(why) + " (lda=" + std::to_string(d->lda) + " ldc=" + std::to_string(d->ldc) + " ldr=" +
+                      std::to_string(d->ldr) + " M=" + std::to_string(d->M) + " N=" + std::to_string(d->N) + ")");
+    if (d->M == 0) return 0;
+    std::vector<unsigned char> hw((size_t)d->N * 1024);
+    pack_proj_x3(d->w_host, d->N, hw.data());
+    Scratch sc("cn_op_proj_x3_desc", (hipStream_t)stream);
+    a.wp = sc.upload(hw.data(), hw.size());
+    a.bias = (const float*)sc.upload(d->bias_host, (size_t)d->N * 4);
+    if (!sc.ok()) return -2;
     return sc.finish(launch_proj_x3(a, (hipStream_t)stream));
 }
+extern "C" int32_t cn_proj_x3_desc_size(void) { return (int32_t)sizeof(cn_proj_x3_desc); }
+
+// what launch_proj_x3 launches for (M, N): *mt = 32-row tiles per workgroup (1 or 2), *chunks = column chunks (gridDim.y)
+extern "C" int cn_proj_x3_form(int32_t M, int32_t N, int32_t split_out, int32_t* mt, int32_t* chunks) {
+    if (!mt || !chunks || M < 1 || !proj_x3_applies(N, 256) || (split_out != 0 && split_out != 1)) {
+        cn_set_error("cn_proj_x3_form: needs M >= 1, N a multiple of 32 in [32, 1024], split_out 0 or 1 and both result pointers");
+        return -1;
+    }
+    int mt_, chunks_;
+    proj_x3_form(M, N, &mt_, &chunks_);
+    *mt = mt_;
+    *chunks = chunks_;
+    return 0;
+}
+
+// the instantiation launch_ffn_x3 picks: *form = a sum of CN_FFN_X3_PRO / TAIL / MIX / SWISH; tail_n == 0: no tail
+extern "C" int cn_ffn_x3_form(int32_t has_ctx, int32_t tail_n, int32_t mix, int32_t act, int32_t* form) {
+    if (!form) {
+        cn_set_error("cn_ffn_x3_form: null result pointer");
+        return -1;
+    }
+    if (act != CN_ACT_RELU && act != CN_ACT_SWISH) {
+        cn_set_error("cn_ffn_x3_form: unknown activation");
+        return -1;
+    }
+    const int f = ffn_x3_form("cn_ffn_x3_form", has_ctx != 0, tail_n != 0, tail_n, mix != 0, act == CN_ACT_SWISH ? FF_ACT_SWISH : FF_ACT_RELU);
+    if (f < 0) return -1;
+    *form = f;
+    return 0;
+}
+static_assert(CN_FFN_X3_PRO == FFN_X3_PRO && CN_FFN_X3_TAIL == FFN_X3_TAIL && CN_FFN_X3_MIX == FFN_X3_MIX && CN_FFN_X3_SWISH == FFN_X3_SWISH,
+              "cassnat_hip.h and kernels.h name the same bits");

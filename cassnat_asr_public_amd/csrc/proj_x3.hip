@@ -14,6 +14,7 @@
 //     row, the half-waves trade groups (v_permlane32_swap) and every store is 16 bytes of hi or lo halves.
 #include <cstdlib>
 #include <cstring>
+#include <string>
 
 #include "proj_x3_phase.h"
 
@@ -40,7 +41,7 @@ __global__ __launch_bounds__(256, MT == 1 ? 4 : 2) void proj_x3_kernel(ProjX3Par
     px_tiles<MT, SPLIT_OUT>(p.ph, smem, smem + 32768, m0, tile_lo, tile_hi, wave_u, lane);
 }
 
-template <int MT, bool SPLIT_OUT> static int launch_proj_x3_variant(const ProjX3Params& p, hipStream_t s) {
+template <int MT, bool SPLIT_OUT> static int launch_proj_x3_variant(const ProjX3Params& p, int chunks, hipStream_t s) {
     constexpr int lds = MT * 32768;
     static CnAttrOnce attr_once;
     int attr_dev;
@@ -48,32 +49,52 @@ template <int MT, bool SPLIT_OUT> static int launch_proj_x3_variant(const ProjX3
         CN_HIP_CHECK(hipFuncSetAttribute((const void*)proj_x3_kernel<MT, SPLIT_OUT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         attr_once.mark(attr_dev);
     }
-    // column chunks (blockIdx.y): the fewest that put a workgroup on every CU, among those that deal every wave the same number
-    // of tiles (each chunk stages the row tile again: 32 MT KiB beside 32 KiB per column tile)
-    const int row_tiles = cn_ceil_div(p.ph.M, 32 * MT), ntiles = p.ph.N / 32;
-    int chunks = 1;
-    for (int c = 1; c <= ntiles / 4; ++c) {
-        if (ntiles % (4 * c) != 0) continue;
-        chunks = c;
-        if (row_tiles * c >= 256) break;
-    }
-    hipLaunchKernelGGL((proj_x3_kernel<MT, SPLIT_OUT>), dim3(row_tiles, chunks), dim3(256), lds, s, p);
+    hipLaunchKernelGGL((proj_x3_kernel<MT, SPLIT_OUT>), dim3(cn_ceil_div(p.ph.M, 32 * MT), chunks), dim3(256), lds, s, p);
     CN_HIP_CHECK(hipGetLastError());
     return 0;
 }
 
 bool proj_x3_applies(int N, int K) { return K == 256 && N >= 32 && N % 32 == 0 && N <= 1024; }
 
+// The launch form, decided on the host alone (cn_proj_x3_form reports it):
+//   * 64-row workgroups (mt = 2) from 4096 rows on: what bounds these launches is the chip's L2 -> CU traffic (about 9 TB/s for
+//     this pattern, whatever the tiling: the 64 x 64 GEMM tiles moved the same bytes in the same time), and a wider row tile halves
+//     the weight stream per row; below that the launch needs the workgroups more;
+//   * column chunks (blockIdx.y): the fewest that put a workgroup on every CU, among those that deal every wave the same number
+//     of tiles (each chunk stages the row tile again: 32 mt KiB beside 32 KiB per column tile)
+void proj_x3_form(int M, int N, int* mt, int* chunks) {
+    *mt = M >= 4096 ? 2 : 1;
+    const int row_tiles = cn_ceil_div(M, 32 * *mt), ntiles = N / 32;
+    *chunks = 1;
+    for (int c = 1; c <= ntiles / 4; ++c) {
+        if (ntiles % (4 * c) != 0) continue;
+        *chunks = c;
+        if (row_tiles * c >= 256) break;
+    }
+}
+
+// The fp32 output and the residual go through buffer descriptors of ((M - 1) * ld + N) * 4 bytes and the rows of A are read 1 KiB
+// at a time: a stride shorter than the row would read and write across rows without a fault.
+const char* proj_x3_refusal(const ProjX3Args& a, bool pointers) {
+    if (!proj_x3_applies(a.N, 256)) return "needs K == 256 and N a multiple of 32 in [32, 1024]";
+    if (pointers && (!a.bias || !a.wp)) return "needs its packed weights and a bias";
+    if (a.M > 0 && (!a.A || !a.C)) return "null A or C";
+    if (a.lda % 32 != 0) return "lda must be a multiple of 32 (split-bf16 rows are groups of 32 elements)";
+    if (a.lda < 256) return "lda < K = 256";
+    if (a.ldc < a.N) return "ldc < N";
+    if (!a.c_f32 && a.ldc % 32 != 0) return "ldc of a split-bf16 output must be a multiple of 32";
+    if (a.resid && !a.c_f32) return "a residual needs the fp32 output";
+    if (a.resid && a.ldr < a.N) return "ldr < N";
+    if (a.M > 0 && a.c_f32 && (long long)a.M * (a.ldc > a.ldr ? a.ldc : a.ldr) * 4 >= (1ll << 31)) return "fp32 output beyond 2 GiB";
+    return nullptr;
+}
+
 int launch_proj_x3(const ProjX3Args& a, hipStream_t s) {
-    if (!proj_x3_applies(a.N, 256) || !a.bias || !a.wp || a.lda % 32 != 0 || (!a.c_f32 && a.ldc % 32 != 0) || (a.resid && !a.c_f32)) {
-        cn_set_error("proj_x3: needs K == 256, N a multiple of 32 (<= 1024), 32-element row strides, a residual only with fp32 output");
+    if (const char* why = proj_x3_refusal(a)) {
+        cn_set_error(std::string("proj_x3: ") + why);
         return -1;
     }
     if (a.M <= 0) return 0;
-    if (a.c_f32 && (long long)a.M * (a.ldc > a.ldr ? a.ldc : a.ldr) * 4 >= (1ll << 31)) {
-        cn_set_error("proj_x3: fp32 output beyond 2 GiB");
-        return -1;
-    }
     ProjX3Params p;
     p.A = reinterpret_cast<const unsigned char*>(a.A);
     p.lda_bytes = (long long)a.lda * 4;
@@ -86,12 +107,10 @@ int launch_proj_x3(const ProjX3Args& a, hipStream_t s) {
     p.ph.resid_scale = a.resid_scale;
     p.ph.M = a.M;
     p.ph.N = a.N;
-    // 64-row workgroups from 4096 rows on: what bounds these launches is the chip's L2 -> CU traffic (about 9 TB/s for this
-    // pattern, whatever the tiling: the 64 x 64 GEMM tiles moved the same bytes in the same time), and a wider row tile halves
-    // the weight stream per row; below that the launch needs the workgroups more
-    const bool wide = a.M >= 4096;
-    if (a.c_f32) return wide ? launch_proj_x3_variant<2, false>(p, s) : launch_proj_x3_variant<1, false>(p, s);
-    return wide ? launch_proj_x3_variant<2, true>(p, s) : launch_proj_x3_variant<1, true>(p, s);
+    int mt, chunks;
+    proj_x3_form(a.M, a.N, &mt, &chunks);
+    if (a.c_f32) return mt == 2 ? launch_proj_x3_variant<2, false>(p, chunks, s) : launch_proj_x3_variant<1, false>(p, chunks, s);
+    return mt == 2 ? launch_proj_x3_variant<2, true>(p, chunks, s) : launch_proj_x3_variant<1, true>(p, chunks, s);
 }
 
 static inline uint16_t px_bf16_bits(float f) {

@@ -48,9 +48,10 @@ def parse_fp8_scope(text):
     return scope, first
 
 
-# the nine structs of the header, derived from it field for field (abi.py)
-CnConfig, CnDecodeOpts, CnAstOpts, CnFbankOpts, CnAttnDesc, CnNgramDesc, CnChainDesc, CnFrontendDesc, CnGemmDesc = (abi.STRUCTS[n] for n in (
-    "cn_config", "cn_decode_opts", "cn_ast_opts", "cn_fbank_opts", "cn_attn_desc", "cn_ngram_desc", "cn_chain_desc", "cn_frontend_desc", "cn_gemm_desc"))
+# the ten structs of the header, derived from it field for field (abi.py)
+CnConfig, CnDecodeOpts, CnAstOpts, CnFbankOpts, CnAttnDesc, CnNgramDesc, CnChainDesc, CnFrontendDesc, CnGemmDesc, CnProjX3Desc = (abi.STRUCTS[n] for n in (
+    "cn_config", "cn_decode_opts", "cn_ast_opts", "cn_fbank_opts", "cn_attn_desc", "cn_ngram_desc", "cn_chain_desc", "cn_frontend_desc", "cn_gemm_desc",
+    "cn_proj_x3_desc"))
 # the descriptor of the phrase-biasing automaton (include/cassnat_hip_ctc_bias.h declares it beside its entry points)
 CnBiasDesc = abi.CTC_BIAS_STRUCTS["cn_bias_desc"]
 

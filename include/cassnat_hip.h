@@ -762,7 +762,9 @@ int cn_op_ffn_x3_act(float* x_dev, const float* ln_a_dev, const float* ln_b_dev,
                      int32_t M, int32_t dff, float eps, int32_t mix, int32_t act, void* stream);
 /* the row-chain form of the split-bf16 engine (fused_x3.hip): attention output projection + residual, feed-forward sublayer, next
  * LayerNorm and (wt_host != null) the next attention's projection of it, in one launch; ctx_dev split-bf16 [M][256] or null;
- * weight matrices on the host, vectors on the device (positionff.py:15-16, attention.py:57-66, norm.py:15-18) */
+ * weight matrices on the host, vectors on the device (positionff.py:15-16, attention.py:57-66, norm.py:15-18).  Refused before
+ * anything is packed or uploaded: d_ff not a multiple of 128 in [128, 2048]; with wt_host a tail_n that is not a multiple of 128
+ * in [128, 1024], no next LayerNorm (the tail projects LN_next(x)), no bt_dev or tail_out_dev; ctx_dev without wo_host / bo_dev */
 int cn_op_x3_chain(float* x_dev, const void* ctx_dev, const float* wo_host, const float* bo_dev, const float* ln_a_dev,
                    const float* ln_b_dev, const float* w1_host, const float* b1_dev, const float* w2_host, const float* b2_dev,
                    const float* nln_a_dev, const float* nln_b_dev, void* xn_out_dev, const float* wt_host, const float* bt_dev,
@@ -788,6 +790,41 @@ int cn_op_genmax_x3(const float* h_host, const float* w_host, const float* b_hos
  * rows (M * N * 4 bytes: per 32 columns 64 bytes of bf16 hi halves, then 64 bytes of lo halves) */
 int cn_op_proj_x3(const float* a_host, const float* w_host, const float* bias_host, const float* resid_dev, float resid_scale,
                   void* c_dev, int32_t M, int32_t N, int32_t split_out, void* stream);
+/* The same projection through a descriptor that reaches every field of the launch (cn_op_proj_x3 is a caller of it): a_dev is on
+ * the DEVICE already, M rows of 256 split-bf16 elements at a row stride of lda elements (4 bytes each: per 32 elements 64 bytes of
+ * hi halves, then 64 bytes of lo halves); w_host fp32 [N][256] and bias_host [N] are packed and uploaded by the call; c_dev fp32
+ * [M][ldc] (split_out == 0) or split-bf16 rows of ldc elements (split_out == 1); resid_dev fp32 [M][ldr] or null, fp32 output
+ * only, may alias c_dev: C = resid + resid_scale * (A . W^T + bias).  Strides in elements.  Rows >= M, columns >= 256 of A and
+ * >= N of C and resid are neither read nor written.
+ * Refused with a message that starts "cn_op_proj_x3_desc: ", before anything is packed or touches the device: a null descriptor,
+ * null a_dev, w_host, bias_host or c_dev; a non-zero reserved word; M < 0; split_out other than 0 / 1; N not a multiple of 32 in
+ * [32, 1024]; lda not a multiple of 32; lda < 256; ldc < N; a split output whose ldc is not a multiple of 32; a residual with a
+ * split output or with ldr < N; an fp32 output beyond 2 GiB.  The three stride bounds are the launcher's own (launch_proj_x3), so
+ * the engine's calls are held to them as well.  M == 0: returns 0, launches nothing.
+ * cn_proj_x3_form: what such a call launches, decided on the host alone - *mt = 32-row tiles per workgroup (2 from M = 4096 on),
+ * *chunks = column chunks (gridDim.y: the fewest c with N / 32 divisible by 4 c that reach 256 workgroups, else the most); -1 for
+ * M < 1 or an N the kernel does not take. */
+typedef struct cn_proj_x3_desc {
+    const void* a_dev;
+    const float* w_host;
+    const float* bias_host;
+    void* c_dev;
+    const float* resid_dev;
+    int32_t lda, ldc, ldr;
+    int32_t M, N;
+    int32_t split_out;
+    float resid_scale;
+    int32_t reserved;
+} cn_proj_x3_desc;
+int cn_op_proj_x3_desc(const cn_proj_x3_desc* d, void* stream);
+int32_t cn_proj_x3_desc_size(void);
+int cn_proj_x3_form(int32_t M, int32_t N, int32_t split_out, int32_t* mt, int32_t* chunks);
+/* Which of its nine instantiations the split-bf16 feed-forward kernel (fused_x3.hip) runs for a call of cn_op_ffn_x3_act /
+ * cn_op_x3_chain, decided on the host alone: *form = a sum of CN_FFN_X3_PRO (ctx: the output projection in front), CN_FFN_X3_TAIL
+ * (tail_n != 0: the next projection behind), CN_FFN_X3_MIX and CN_FFN_X3_SWISH.  -1 with a message where the launch is refused: a
+ * tail_n that is not a multiple of 128 in [128, 1024], Swish with mix, ctx or a tail, an unknown act. */
+enum { CN_FFN_X3_PRO = 1, CN_FFN_X3_TAIL = 2, CN_FFN_X3_MIX = 4, CN_FFN_X3_SWISH = 8 };
+int cn_ffn_x3_form(int32_t has_ctx, int32_t tail_n, int32_t mix, int32_t act, int32_t* form);
 int cn_op_topk(const float* logp, int32_t M, int32_t V, int32_t k, int32_t* idx, float* val, void* stream);
 /* e4m3fn product (BASELINE config 5): A bf16 [M][lda] on the device is quantised at a_scale (saturating at 448 / a_scale),
  * W = HOST fp32 [N][K] at the largest power-of-two scale that fits (returned in *w_scale_out), as cn_model_finalize does for

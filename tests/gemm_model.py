@@ -368,6 +368,13 @@ def operands(c, layout, b, lda=None, ldr=None, pe_unwrapped=False):
 
 
 # ================================================================================================ the float64 model
+def split_product_bound(S, K):
+    """|hi.hi + hi.lo + lo.hi in fp32 - a . w| of split-bf16 operands a = hi + lo, given S = sum |a| |w| over K: three products per
+    element pair (2 gamma(3 K), the factor 2 as for every MFMA sum) and the dropped lo . lo (|lo| <= 2^-9 |value|).  Shared with
+    x3_model.py."""
+    return 2 * gamma(3 * K) * S + 2.0 ** -18 * S
+
+
 def gemm_model(c, layout, o, mistakes=()):
     """One launch in float64 from the operand values ``o`` (operands()) -> dict(ref, dv, half, emu_v, acc, S): the fp64 result (an
     e4m3 output: saturated), the bound of the kernel's fp32 v in front of the output's rounding, half an output step, the
@@ -389,7 +396,7 @@ def gemm_model(c, layout, o, mistakes=()):
         f8_term = torch.minimum(E4M3_ACC * S, E4M3_RANGE_CAP * rng)
         dv = f8_term + 2 * EPS * P.abs()                      # ... and the two multiplications by the scales
     elif layout == "bf16x3":
-        dv = 2 * gamma(3 * K) * S + 2.0 ** -18 * S            # three products per element pair, the dropped lo . lo
+        dv = split_product_bound(S, K)
     else:
         dv = 2 * gamma(K + 1) * S                             # (fp32 operands: the product's own rounding)
     # ---- the emulation's product

@@ -84,16 +84,16 @@ def test_parser_refuses_what_it_does_not_recognise(text, names):
 
 
 STRUCT_SIZES = {"cn_config": 100, "cn_decode_opts": 64, "cn_ast_opts": 56, "cn_fbank_opts": 64, "cn_attn_desc": 200, "cn_ngram_desc": 160, "cn_chain_desc": 200,
-                "cn_frontend_desc": 208, "cn_gemm_desc": 120}
+                "cn_frontend_desc": 208, "cn_gemm_desc": 120, "cn_proj_x3_desc": 72}
 
 
 def test_the_real_header():
-    assert len(abi.FUNCTIONS) == 117
+    assert len(abi.FUNCTIONS) == 121
     assert {n: C.sizeof(s) for n, s in abi.STRUCTS.items()} == STRUCT_SIZES
     for cls, name in ((hip.CnConfig, "cn_config"), (hip.CnDecodeOpts, "cn_decode_opts"), (hip.CnAstOpts, "cn_ast_opts"),
                       (hip.CnFbankOpts, "cn_fbank_opts"), (hip.CnAttnDesc, "cn_attn_desc"), (hip.CnNgramDesc, "cn_ngram_desc"),
                       (hip.CnChainDesc, "cn_chain_desc"), (hip.CnFrontendDesc, "cn_frontend_desc"),
-                      (hip.CnGemmDesc, "cn_gemm_desc")):
+                      (hip.CnGemmDesc, "cn_gemm_desc"), (hip.CnProjX3Desc, "cn_proj_x3_desc")):
         assert cls is abi.STRUCTS[name]
     K = abi.CONSTANTS
     assert [K["CN_PRECISION_" + n] for n in ("F32", "BF16", "FP8", "BF16X3", "F16")] == [0, 1, 2, 3, 4]
@@ -101,10 +101,12 @@ def test_the_real_header():
     assert [K["CN_FP8_" + n] for n in ("CONV2", "LINEAR", "FFN")] == [1, 2, 4]
     assert [K["CN_GEMM_EPI_" + n] for n in ("RELU", "RESID", "EMBED", "SWISH")] == [1, 2, 4, 8]
     assert {"cn_op_gemm_desc", "cn_gemm_desc_size", "cn_gemm_form"} <= set(abi.FUNCTIONS)
+    assert {"cn_op_proj_x3_desc", "cn_proj_x3_desc_size", "cn_proj_x3_form", "cn_ffn_x3_form"} <= set(abi.FUNCTIONS)
+    assert [K["CN_FFN_X3_" + n] for n in ("PRO", "TAIL", "MIX", "SWISH")] == [1, 2, 4, 8]
     assert hip.PRECISION["fp32"] == hip.PRECISION["float32"] == 0 and hip.PRECISION["bf16x3"] == 3 and hip.PRECISION["float16"] == 4
     assert sorted(hip.DTYPES) == [0, 1, 2, 3] and hip.FP8_SCOPE_BITS == {"conv2": 1, "linear": 2, "ffn": 4}
     names = hip.declared_symbols()
-    assert names == sorted(set(names)) and len(names) == 117 and all(n.startswith("cn_") for n in names)
+    assert names == sorted(set(names)) and len(names) == 121 and all(n.startswith("cn_") for n in names)
     assert not set(names) & set(abi.STRUCTS) and "cn_model" not in names
 
 
@@ -122,4 +124,4 @@ def test_every_declared_function_is_bound(flavour):
         assert len(fn.argtypes) == count == len(abi.FUNCTIONS[name][1]), name
         assert fn.restype is returns[ret.strip()], name
         seen += 1
-    assert seen == len(abi.FUNCTIONS) == 117
+    assert seen == len(abi.FUNCTIONS) == 121

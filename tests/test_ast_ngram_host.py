@@ -34,7 +34,7 @@ def test_entry_points_are_declared_in_the_new_header_only_and_exported_by_both_l
             assert ret.strip() == "int" and fn.restype is C.c_int, name
             assert len(fn.argtypes) == params.count(",") + 1 == len(abi.AST_NGRAM_FUNCTIONS[name][1]), name
     # the two older headers keep their lists, cn_ast_opts its size
-    assert len(abi.FUNCTIONS) == 117 and len(abi.EXTRA_FUNCTIONS) == 3 and C.sizeof(hip.CnAstOpts) == 56
+    assert len(abi.FUNCTIONS) == 121 and len(abi.EXTRA_FUNCTIONS) == 3 and C.sizeof(hip.CnAstOpts) == 56
 
 
 @pytest.mark.parametrize("order", cases.ORDERS)
