@@ -1,5 +1,6 @@
 // Row-wise, HBM-bound kernels of the hot path: the reference's custom LayerNorm, the generator's
 // log-softmax + argmax, the padding mask, query-table broadcast and precision converts.
+#include "feats_compress.h"
 #include "kernels.h"
 #include "rowreduce.h"
 
@@ -703,22 +704,9 @@ int launch_unpack_rows(const float* packed, const int* off, const int* len, floa
 // the kind's data) at a 16-byte-aligned byte offset off[r] of the staging buffer - and are decompressed, normalised and padded here:
 //   out[r][t][:] = t < len[r] ? norm(decompress(payload_r)[t][:]) : pad          (norm as in unpack_rows_kernel)
 // Decompression is Kaldi's float32 arithmetic, every operation rounded on its own (its x86 builds have no fused multiply-add): the
-// helpers below switch contraction off, since hipcc would otherwise fuse `a + b * c` and change the last bit of about one value in
-// eleven of format 1's third segment.
-__device__ __forceinline__ float uc_scale(float range, float k) {
-#pragma clang fp contract(off)
-    return range * k;
-}
-__device__ __forceinline__ float uc_linear(float mn, float inc, unsigned v) {  // uint16 (formats 1 headers, 2) / uint8 (format 3) -> float
-#pragma clang fp contract(off)
-    return mn + inc * (float)v;
-}
-__device__ __forceinline__ float uc_byte(float p0, float p25, float p75, float p100, unsigned b) {  // format 1: CharToFloat
-#pragma clang fp contract(off)
-    if (b <= 64) return p0 + ((p25 - p0) * (float)b) * (1 / 64.0f);
-    if (b <= 192) return p25 + ((p75 - p25) * (float)(b - 64)) * (1 / 128.0f);
-    return p75 + ((p100 - p75) * (float)(b - 192)) * (1 / 63.0f);
-}
+// helpers uc_scale / uc_linear / uc_byte (feats_compress.h: the writer of these archives computes its quartiles with them) switch
+// contraction off, since hipcc would otherwise fuse `a + b * c` and change the last bit of about one value in eleven of format 1's
+// third segment.
 
 // One workgroup per (utterance, 64-frame tile); the kind is uniform per workgroup.
 // Format 1 (kind 1) is column-major - byte[c * num_rows + t] behind num_cols headers of four uint16 - with an arbitrary column

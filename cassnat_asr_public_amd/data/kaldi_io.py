@@ -36,7 +36,9 @@ multiply-add):
 
 `decompress` below is that in numpy float32 - the definition the device kernel (csrc/rowops.hip: unpack_compressed_kernel) is held
 to bit for bit.  `write_ark_scp(compress=k)` writes valid, tight archives of the three kinds for tests and tools; it does not
-reproduce the bytes of Kaldi's own encoder.
+reproduce the bytes of Kaldi's own encoder (its quartile indices and its rounding differ).  The writer that follows
+`copy-feats --compress=true` - DESIGN.md 7n - is bin/make_fbank: the device kernel cn_op_compress_feats and its host twin;
+``matrix_entry`` and ``cmvn_stats_bytes`` below write its archive entries and its statistics file.
 """
 import mmap
 import os
@@ -319,3 +321,30 @@ def write_ark_scp(ark_path, scp_path, items, compress=None):
                 mat = mat.astype("<f4", copy=False)
             ark.write(b"\0B" + tag + b"\x04" + struct.pack("<i", mat.shape[0]) + b"\x04" + struct.pack("<i", mat.shape[1]))
             ark.write(mat.tobytes())
+
+
+def matrix_entry(utt, mat=None, payload=None):
+    """The bytes of one archive entry and the offset of its `\\0B` inside them: ``UTT `` then, for ``mat`` (float32 / float64), the
+    `FM ` / `DM ` matrix as ``write_ark_scp`` writes it, or, for ``payload`` (a compressed matrix from min_value on, as
+    ``mat_payload`` hands it out and bin/make_fbank's compression writes it), `CM ` / `CM2 ` + the payload - the kind is the one
+    `copy-feats --compress=true` chooses: format 1 for more than 8 rows, format 2 otherwise."""
+    key = utt.encode() + b" "
+    if payload is not None:
+        payload = bytes(payload)
+        rows, cols = struct.unpack("<ii", payload[8:16])
+        token = b"CM " if rows > 8 else b"CM2 "
+        if len(payload) != 16 + (8 * cols + rows * cols if rows > 8 else 2 * rows * cols):
+            raise ValueError("matrix_entry: %s: a payload of %d bytes for a %d x %d compressed matrix" % (utt, len(payload), rows, cols))
+        return key + b"\0B" + token + payload, len(key)
+    mat = np.ascontiguousarray(mat)
+    tag = b"DM " if mat.dtype == np.float64 else b"FM "
+    mat = mat.astype("<f8" if tag == b"DM " else "<f4", copy=False)
+    return (key + b"\0B" + tag + b"\x04" + struct.pack("<i", mat.shape[0]) + b"\x04" + struct.pack("<i", mat.shape[1]) + mat.tobytes(), len(key))
+
+
+def cmvn_stats_bytes(sums, sumsq, count):
+    """Kaldi's global CMVN statistics as ``SpeechDataset._load_cmvn`` reads them: a bare `\\0BDM ` matrix of 2 x (F + 1) - the sums and
+    the frame count, then the sums of squares and 0."""
+    stats = np.zeros((2, len(sums) + 1), "<f8")
+    stats[0, :-1], stats[0, -1], stats[1, :-1] = sums, count, sumsq
+    return matrix_entry("", stats)[0][1:]

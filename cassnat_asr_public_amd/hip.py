@@ -184,6 +184,79 @@ def unpack_compressed(staged, off, lens, kinds, out, pad, mean=None, std=None):
     return out
 
 
+FEATS_STATUS = {1: "no rows", 2: "a non-finite value among its rows", 3: "its payload does not lie inside the output buffer"}
+
+
+def compress_feats_bytes(T, F):
+    """Bytes of the compressed payload of a T x F matrix (cn_compress_feats_bytes): `CM` for T > 8, `CM2` otherwise."""
+    return int(lib().cn_compress_feats_bytes(int(T), int(F)))
+
+
+def compress_feats_layout(lens, F, tmax=None):
+    """Where ``compress_feats`` puts the payloads of utterances of ``lens`` rows (clamped to ``tmax``): (int32 byte offsets, multiples
+    of 16; the payloads' sizes; the end of the last one)."""
+    lens = np.asarray(lens, dtype=np.int64)
+    T = np.maximum(lens if tmax is None else np.minimum(lens, int(tmax)), 0)
+    sizes = np.where(T > 8, 16 + 8 * F + T * F, 16 + 2 * T * F)
+    offs, total = gather_offsets(sizes, 16)
+    if total >= 2 ** 31:
+        raise ValueError("compress_feats_layout: %d payload bytes (the offsets are int32)" % total)
+    return offs.astype(np.int32), sizes, total
+
+
+def compress_feats(feats, lens, out_off, out, status, flavour=None):
+    """Kaldi matrix compression on the device (cn_op_compress_feats; include/cassnat_hip_feats.h), the inverse of
+    ``unpack_compressed``: ``feats`` float32 CUDA (rows, Tmax, F), ``lens`` int32 CUDA rows per utterance, ``out_off`` int32 CUDA byte
+    offsets (``compress_feats_layout``) -> utterance r's payload at out[out_off[r]:] (``out`` uint8 CUDA, 16-byte aligned) and its
+    status word in ``status`` (int32 CUDA; 0 fine, else ``FEATS_STATUS``), on the current stream.  Nothing else of ``out`` is written."""
+    rows, T, F = feats.shape
+    assert feats.is_contiguous() and feats.element_size() == 4 and out.is_contiguous() and out.element_size() == 1
+    assert lens.numel() >= rows and out_off.numel() >= rows and status.numel() >= rows and status.element_size() == 4
+    L = lib(flavour)
+    check(L.cn_op_compress_feats(_ptr(feats), _ptr(lens), _ptr(out_off), rows, T, F, _ptr(out), out.numel(), _ptr(status), current_stream()),
+          "cn_op_compress_feats", L)
+    return out
+
+
+def compress_feats_host(feats, lens, out_off, out, status, flavour=None):
+    """``compress_feats`` on numpy arrays through the serial host entry (cn_compress_feats_host): no GPU call.  ``out`` (uint8) and
+    ``status`` (int32) are written in place."""
+    rows, T, F = feats.shape
+    assert feats.dtype == np.float32 and feats.flags.c_contiguous and out.dtype == np.uint8 and out.flags.c_contiguous
+    assert lens.dtype == np.int32 and out_off.dtype == np.int32 and status.dtype == np.int32 and min(lens.size, out_off.size, status.size) >= rows
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    L = lib(flavour)
+    check(L.cn_compress_feats_host(p(feats), p(lens), p(out_off), rows, T, F, p(out), out.size, p(status)), "cn_compress_feats_host", L)
+    return out
+
+
+def feats_stats(feats, lens, stats, payload=None, out_off=None, status=None, flavour=None):
+    """Per utterance and column the float64 sum and sum of squares of what an archive holds (cn_op_feats_stats) -> ``stats`` float64
+    CUDA (rows, 2, F), on the current stream: with ``payload`` / ``out_off`` (what ``compress_feats`` wrote) the dequantised values,
+    without them the float32 rows of ``feats`` (rows, Tmax, F).  An utterance whose ``status`` word is not 0 gives zeros.  No atomics:
+    two runs give the same bits."""
+    rows, T, F = feats.shape
+    assert feats.is_contiguous() and feats.element_size() == 4 and stats.is_contiguous() and stats.element_size() == 8
+    assert stats.numel() >= rows * 2 * F and lens.numel() >= rows and (payload is None or out_off is not None)
+    L = lib(flavour)
+    check(L.cn_op_feats_stats(_ptr(feats), _ptr(payload), _ptr(out_off), _ptr(lens), _ptr(status), rows, T, F, _ptr(stats), current_stream()),
+          "cn_op_feats_stats", L)
+    return stats
+
+
+def feats_stats_host(feats, lens, payload=None, out_off=None, status=None, flavour=None):
+    """``feats_stats`` on numpy arrays through the serial host entry (cn_feats_stats_host) -> float64 (rows, 2, F)."""
+    rows, T, F = feats.shape
+    assert feats.dtype == np.float32 and feats.flags.c_contiguous and lens.dtype == np.int32 and lens.size >= rows
+    assert payload is None or (payload.dtype == np.uint8 and payload.flags.c_contiguous and out_off is not None and out_off.dtype == np.int32)
+    assert status is None or status.dtype == np.int32
+    stats = np.zeros((rows, 2, F), np.float64)
+    p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+    L = lib(flavour)
+    check(L.cn_feats_stats_host(p(feats), p(payload), p(out_off), p(lens), p(status), rows, T, F, p(stats)), "cn_feats_stats_host", L)
+    return stats
+
+
 def splice_rows(src, off, lens, out, left, right, skip, pad, mean=None, std=None):
     """Frame splicing and skipping on the device (cn_op_splice_rows): ``src`` float32 CUDA rows of F0 features, utterance r at row
     off[r] with lens[r] rows -> ``out`` (rows, T_out, (left + right + 1) * F0) on the current stream: the dataset's order - CMVN
