@@ -23,6 +23,13 @@
 //       (node, banked) of dynamic LDS: the winner copies them to slot `rank` of the other buffer and does not walk again;
 //     * after the last frame every kept hypothesis gives up its open match and the beam is sorted once more by the same key.
 //   Every probe loop is bounded by its table's slot count.
+//   ctc_beam_kernel<FUSE, true>  any of the three policies, merging candidates that spell the same label sequence
+//                           (ctc_merge_search.h, include/cassnat_hip_ctc_merge.h; `--hip_ctc_merge 1`; the reference does not merge).
+//                           One more phase between the candidate phase and the rank phase, behind a barrier: every extension's thread
+//                           looks for a kept hypothesis with its labels - (length, last label) and a 32-bit hash filter, an id link
+//                           proves identity where there is one, else both back-pointer chains are walked - and folds its p_nblk into
+//                           that hypothesis' stay candidate.  (id, prefix id, hash) per kept hypothesis in static LDS, double
+//                           buffered; no scratch beyond the back-pointers.  The <FUSE, false> instantiations are the kernels above.
 //
 // viterbi_align (CassNAT.beam_path_align, src/models/cassnat.py:391-414, 272-353) is the max-product CTC forward pass over the
 // blank-augmented label sequence in float32 followed by a sequential back-trace; here one workgroup per utterance with the two live
@@ -31,6 +38,7 @@
 #include <type_traits>
 
 #include "ctc_bias_search.h"
+#include "ctc_merge_search.h"
 #include "ctc_ngram_search.h"
 #include "kernels.h"
 
@@ -64,6 +72,16 @@ __device__ __forceinline__ double cg_score_words(const cn_ngram_desc& d, const C
     return 0.0;
 }
 
+// what the merging instantiations keep per kept hypothesis in static LDS, double buffered: the id given when an extension was kept
+// (stays inherit it), the id of the hypothesis it extended, the hash of its labels (include/cassnat_hip_ctc_merge.h)
+template <bool MERGE>
+struct CmLds {};
+template <>
+struct CmLds<true> {
+    int id[2][CS_MAX_BEAM], pfx[2][CS_MAX_BEAM];
+    uint32_t hash[2][CS_MAX_BEAM];
+};
+
 template <int FUSE>
 struct CsFuseArgs {
     using type = CtcBeamArgs;
@@ -77,7 +95,7 @@ struct CsFuseArgs<CS_FUSE_BIAS> {
     using type = CtcBiasArgs;
 };
 
-template <int FUSE>
+template <int FUSE, bool MERGE>
 __global__ __launch_bounds__(256) void ctc_beam_kernel(typename CsFuseArgs<FUSE>::type a) {
     constexpr bool NGRAM = FUSE == CS_FUSE_NGRAM, BIAS = FUSE == CS_FUSE_BIAS;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -101,6 +119,7 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(typename CsFuseArgs<FUSE>
     int* clast = clen + NC;
     int* cnode = clast + NC;  // (bias only) the candidate's automaton node
     __shared__ CgLds<FUSE> ng;
+    __shared__ CmLds<MERGE> mg;
     __shared__ int s_nb, s_steps;
 
     const float* logp = a.logp + (long long)b * a.Tp * a.V;
@@ -117,10 +136,12 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(typename CsFuseArgs<FUSE>
         blast[0] = -1;
         if constexpr (NGRAM) cg_init(a.d, &ng.hyps[0][0]);
         if constexpr (BIAS) ng.st[0][0] = cb_init();
+        if constexpr (MERGE) mg.id[0][0] = 0, mg.pfx[0][0] = -1, mg.hash[0][0] = 0u;
         s_nb = 1;
         s_steps = 0;
     }
     int cur = 0;
+    [[maybe_unused]] int mcur = 0;  // (merging) the buffer of mg that holds the kept hypotheses
     __syncthreads();
     for (int t = 0; t < a.Tp; ++t) {
         if (t > ssz) continue;
@@ -130,7 +151,8 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(typename CsFuseArgs<FUSE>
         const int ncand = nb * (P + 1);
         for (int i = tid; i < ncand; i += 256) {
             const int k = i / (P + 1), j = i - k * (P + 1);
-            const int c = j == 0 ? -1 : top[(long long)t * P + (j - 1)];
+            int c = j == 0 ? -1 : top[(long long)t * P + (j - 1)];
+            if constexpr (MERGE) c = cm_dedup(top + (long long)t * P, j, c);
             const CsCand r = cs_candidate(row, a.V, a.blank, k, j == 0, c, pb[k], pnb[k], blast[k], blen[k]);
             double slm = 0.0;
             if constexpr (NGRAM) {
@@ -160,6 +182,35 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(typename CsFuseArgs<FUSE>
             if (tid < W) ng.wflag[tid] = 0;
         }
         __syncthreads();
+        if constexpr (MERGE) {
+            // the fold: an extension (k, c) that spells the labels of a kept hypothesis kp goes into kp's stay candidate.  At most one
+            // extension folds into a given stay (the kept sequences differ pairwise, the list has no label twice): no two threads
+            // write the same stay, and nobody reads a stay's p_nblk / score / key in this phase but the thread that folds into it.
+            for (int i = tid; i < ncand; i += 256) {
+                if (cpar[i] < 0 || ctok[i] < 0) continue;
+                const int k = cpar[i], c = ctok[i], len1 = clen[i], idk = mg.id[mcur][k];
+                const uint32_t h = cm_hash(mg.hash[mcur][k], c);
+                int hit = -1;
+                for (int kp = 0; kp < nb; ++kp) {
+                    if (blen[kp] != len1 || blast[kp] != c) continue;
+                    // kp was made by appending c to what k has been since: the same labels.  Else (a prefix dropped and made again
+                    // has a new id) the chains decide, wherever the hash does not rule it out.
+                    if (mg.pfx[mcur][kp] == idk || (mg.hash[mcur][kp] == h && cm_same_sequence(hpar, htok, W, step, kp, k, c))) {
+                        hit = kp;
+                        break;
+                    }
+                }
+                if (hit >= 0) {
+                    const int sty = hit * (P + 1);
+                    cm_fold(cpb[sty], &cpnb[sty], &ctot[sty], cpnb[i]);
+                    double slm = 0.0;
+                    if constexpr (NGRAM || BIAS) slm = cslm[sty];
+                    ckey[sty] = cs_key(ctot[sty], slm, a.lp, clen[sty]);
+                    cpar[i] = -1;
+                }
+            }
+            __syncthreads();
+        }
         for (int i = tid; i < ncand; i += 256) {
             if (cpar[i] < 0) continue;
             const int rank = cs_rank(ckey, cpar, ncand, i);
@@ -183,6 +234,12 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(typename CsFuseArgs<FUSE>
                     st.node = cnode[i], st.pad = 0, st.banked = cbank[i];
                     ng.st[cur ^ 1][rank] = st;
                 }
+                if constexpr (MERGE) {
+                    const int k = cpar[i], c = ctok[i];
+                    mg.id[mcur ^ 1][rank] = c < 0 ? mg.id[mcur][k] : step * W + rank + 1;
+                    mg.pfx[mcur ^ 1][rank] = c < 0 ? mg.pfx[mcur][k] : mg.id[mcur][k];
+                    mg.hash[mcur ^ 1][rank] = c < 0 ? mg.hash[mcur][k] : cm_hash(mg.hash[mcur][k], c);
+                }
             }
         }
         // (pb / pnb / blen / blast were only read in the candidate phase above, behind the barrier: safe to overwrite)
@@ -199,6 +256,7 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(typename CsFuseArgs<FUSE>
             __syncthreads();
         }
         if constexpr (BIAS) cur ^= 1;
+        if constexpr (MERGE) mcur ^= 1;
     }
     const int nb = s_nb, steps = s_steps;
     int out = tid;  // the slot a kept hypothesis is written at
@@ -242,17 +300,17 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(typename CsFuseArgs<FUSE>
     }
 }
 
-template <int FUSE, class Args>
+template <int FUSE, bool MERGE = false, class Args>
 static int launch_beam(const Args& a, hipStream_t s) {
     constexpr bool BIAS = FUSE == CS_FUSE_BIAS;
     static CnAttrOnce attr_once;  // (one per instantiation)
     int attr_dev;
     if (attr_once.need(&attr_dev)) {
-        CN_HIP_CHECK(hipFuncSetAttribute((const void*)ctc_beam_kernel<FUSE>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
+        CN_HIP_CHECK(hipFuncSetAttribute((const void*)ctc_beam_kernel<FUSE, MERGE>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
         attr_once.mark(attr_dev);
     }
     const size_t lds = cs_lds_bytes(a.W, a.P, FUSE != CS_FUSE_NONE, 2, BIAS ? 5 : 4, BIAS ? 1 : 0);
-    hipLaunchKernelGGL(ctc_beam_kernel<FUSE>, dim3(a.B), dim3(256), lds, s, a);
+    hipLaunchKernelGGL((ctc_beam_kernel<FUSE, MERGE>), dim3(a.B), dim3(256), lds, s, a);
     CN_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -323,6 +381,35 @@ extern "C" int cn_ctc_bias_beam_host(const cn_bias_desc* desc, const float* logp
         return -1;
     }
     for (int32_t b = 0; b < B; ++b) cb_search_host(a, b);
+    return 0;
+}
+
+// the search that merges candidates by prefix (include/cassnat_hip_ctc_merge.h): the MERGE instantiation of the descriptor's policy
+int launch_ctc_merged_beam(const CtcMergeArgs& a, hipStream_t s) {
+    const std::string bad = cm_check(a, true);
+    if (!bad.empty()) {
+        cn_set_error("ctc_merged_beam: " + bad);
+        return -1;
+    }
+    if (a.ng) return launch_beam<CS_FUSE_NGRAM, true>(ctc_ngram_args(*a.ng, a.lm_scale, a), s);
+    if (a.bias) return launch_beam<CS_FUSE_BIAS, true>(ctc_bias_args(*a.bias, a), s);
+    return launch_beam<CS_FUSE_NONE, true>(static_cast<const CtcBeamArgs&>(a), s);
+}
+
+// the merging search on the host: every pointer a host pointer, no GPU call
+extern "C" int cn_ctc_merged_beam_host(const cn_ngram_desc* ngram_desc, double lm_scale, const cn_bias_desc* bias_desc, const float* logp,
+                                       const int32_t* top_idx, const float* size_ratio, int32_t B, int32_t Tp, int32_t V, int32_t beam,
+                                       int32_t pruning, double length_penalty, int32_t blank, int32_t* hyp, int32_t hyp_cap,
+                                       int32_t* hyp_len, double* score, double* score_lm, double* p_blk, double* p_nblk, int32_t* nbeam) {
+    const CtcMergeArgs a = ctc_merge_args(ngram_desc, lm_scale, bias_desc,
+                                          ctc_beam_args(logp, top_idx, size_ratio, B, Tp, V, beam, pruning, blank, length_penalty,
+                                                        ctc_beam_out(hyp, hyp_cap, hyp_len, score, score_lm, p_blk, p_nblk, nbeam)));
+    const std::string bad = cm_check(a, false);
+    if (!bad.empty()) {
+        cn_set_error("cn_ctc_merged_beam_host: " + bad);
+        return -1;
+    }
+    for (int32_t b = 0; b < B; ++b) cm_search_host(a, b);
     return 0;
 }
 

@@ -6,6 +6,7 @@
 #include <cmath>
 
 #include "ctc_bias_search.h"
+#include "ctc_merge_search.h"
 #include "ctc_ngram_search.h"
 #include "model.h"
 
@@ -770,6 +771,38 @@ extern "C" int cn_ctc_beam_bias(cn_model* m, const cn_bias_desc* desc, const flo
                            true, &search, s));
     ProfScope ps(m, "ctc_bias_beam", 0, (double)B * search.Tp * (pruning + 1) * 4, s);
     return launch_ctc_bias_beam(ctc_bias_args(*desc, search), s);
+}
+
+// The same search merging candidates by prefix (ctc_merge_search.h, include/cassnat_hip_ctc_merge.h; not in the reference), without
+// fusion, with the n-gram model or with the phrase list: one launch of the MERGE instantiation of that policy.  Outputs as
+// cn_ctc_beam_ngram.
+extern "C" int cn_ctc_beam_merged(cn_model* m, const cn_ngram_desc* ngram_desc, double lm_scale, const cn_bias_desc* bias_desc,
+                                  const float* feats_dev, const float* size_ratio_dev, int32_t B, int32_t T, int32_t F,
+                                  const cn_decode_opts* opts, int32_t beam, int32_t pruning, double length_penalty, int32_t* hyp_out_dev,
+                                  int32_t hyp_cap, int32_t* hyp_len_dev, double* score_dev, double* score_lm_dev, double* p_blk_dev,
+                                  double* p_nblk_dev, int32_t* nbeam_dev, void* stream) {
+    CN_TRY(check_call(m, B, T, F));
+    // (looked at before anything is launched)
+    if (ngram_desc && bias_desc) {
+        cn_set_error("cn_ctc_beam_merged: at most one of the n-gram and the bias descriptor may be set");
+        return -1;
+    }
+    if (!size_ratio_dev || !score_lm_dev || !(length_penalty == length_penalty) || (ngram_desc && !(lm_scale == lm_scale))) {
+        cn_set_error("cn_ctc_beam_merged: needs size ratios, length_penalty and lm_scale numbers and all output buffers");
+        return -1;
+    }
+    const std::string bad = ngram_desc ? ng_check_desc(*ngram_desc) : bias_desc ? cb_check_desc(*bias_desc) : std::string();
+    if (!bad.empty()) {
+        cn_set_error("cn_ctc_beam_merged: " + bad);
+        return -1;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    CtcBeamArgs search;
+    CN_TRY(ctc_search_open(m, "cn_ctc_beam_merged", feats_dev, size_ratio_dev, B, T, F, opts, beam, pruning, length_penalty,
+                           ctc_beam_out(hyp_out_dev, hyp_cap, hyp_len_dev, score_dev, score_lm_dev, p_blk_dev, p_nblk_dev, nbeam_dev), true,
+                           true, &search, s));
+    ProfScope ps(m, "ctc_merged_beam", 0, (double)B * search.Tp * (pruning + 1) * 4, s);
+    return launch_ctc_merged_beam(ctc_merge_args(ngram_desc, lm_scale, bias_desc, search), s);
 }
 
 // CassNAT.beam_decode with decode_type 'ctc_att' and sample_num 1 (src/models/cassnat.py:446-448, 391-414): the trigger mask

@@ -12,6 +12,7 @@
 #include "../../include/cassnat_hip.h"
 #include "../../include/cassnat_hip_attention_proj.h"
 #include "ctc_bias_search.h"
+#include "ctc_merge_search.h"
 #include "ctc_ngram_search.h"
 #include "ctc_times_search.h"
 #include "edit_align_search.h"
@@ -1602,6 +1603,28 @@ extern "C" int cn_op_ctc_bias_beam(const cn_bias_desc* desc, const float* logp, 
     a.hist_tok = (int*)sc.alloc((size_t)B * Tp * beam * 4);
     if (!sc.ok()) return -2;
     return sc.finish(launch_ctc_bias_beam(a, s));
+}
+
+// the merging search kernel (ctc_beam.hip, MERGE) alone on given log-posteriors and given pruned labels (cn_ctc_beam_merged runs it
+// behind the encoder)
+extern "C" int cn_op_ctc_merged_beam(const cn_ngram_desc* ngram_desc, double lm_scale, const cn_bias_desc* bias_desc, const float* logp,
+                                     const int32_t* top_idx, const float* size_ratio, int32_t B, int32_t Tp, int32_t V, int32_t beam,
+                                     int32_t pruning, double length_penalty, int32_t blank, int32_t* hyp, int32_t hyp_cap, int32_t* hyp_len,
+                                     double* score, double* score_lm, double* p_blk, double* p_nblk, int32_t* nbeam, void* stream) {
+    CtcMergeArgs a = ctc_merge_args(ngram_desc, lm_scale, bias_desc,
+                                    ctc_beam_args(logp, top_idx, size_ratio, B, Tp, V, beam, pruning, blank, length_penalty,
+                                                  ctc_beam_out(hyp, hyp_cap, hyp_len, score, score_lm, p_blk, p_nblk, nbeam)));
+    const std::string bad = cm_check(a, false);
+    if (!bad.empty()) {
+        cn_set_error("cn_op_ctc_merged_beam: " + bad);
+        return -1;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    Scratch sc("cn_op_ctc_merged_beam", s);
+    a.hist_parent = (unsigned char*)sc.alloc((size_t)B * Tp * beam);
+    a.hist_tok = (int*)sc.alloc((size_t)B * Tp * beam * 4);
+    if (!sc.ok()) return -2;
+    return sc.finish(launch_ctc_merged_beam(a, s));
 }
 
 extern "C" int cn_op_ffn_fused(float* x_dev, const float* ln_a_dev, const float* ln_b_dev, const float* w1_host,

@@ -820,6 +820,25 @@ class Engine:
                                           _ptr(pnb), _ptr(nb), current_stream()), "cn_ctc_beam_bias")
         return hyp, hlen, sc, slm, pb, pnb, nb
 
+    def ctc_beam_merged(self, feats, size_ratio, opts, beam, pruning, length_penalty, ngram_desc=None, lm_scale=0.0, bias_desc=None):
+        """CTC prefix beam search that merges candidates spelling the same prefix (``cn_ctc_beam_merged``;
+        include/cassnat_hip_ctc_merge.h): without fusion, with ``ngram_desc`` (a ``CnNgramDesc``; ``lm_scale`` = ctc_lm_weight * ln(10))
+        or with ``bias_desc`` (a ``CnBiasDesc``), at most one of the two -> ``ctc_beam_ngram``'s tuple (score_lm zeros without fusion)."""
+        import torch
+
+        B, T, F = feats.shape
+        cap = subsampled(T) + 1
+        dev = feats.device
+        hyp = torch.empty(B, beam, cap, dtype=torch.int32, device=dev)
+        hlen = torch.empty(B, beam, dtype=torch.int32, device=dev)
+        sc, slm, pb, pnb = (torch.empty(B, beam, dtype=torch.float64, device=dev) for _ in range(4))
+        nb = torch.empty(B, dtype=torch.int32, device=dev)
+        self._chk(self.L.cn_ctc_beam_merged(self.handle, C.byref(ngram_desc) if ngram_desc is not None else None, float(lm_scale),
+                                            C.byref(bias_desc) if bias_desc is not None else None, _ptr(feats), _ptr(size_ratio), B, T, F,
+                                            C.byref(opts), int(beam), int(pruning), float(length_penalty), _ptr(hyp), cap, _ptr(hlen),
+                                            _ptr(sc), _ptr(slm), _ptr(pb), _ptr(pnb), _ptr(nb), current_stream()), "cn_ctc_beam_merged")
+        return hyp, hlen, sc, slm, pb, pnb, nb
+
     # ---- word / token time stamps: forced CTC alignment with spans and confidences (include/cassnat_hip_ctc_times.h)
     def ctc_token_times(self, feats, size_ratio, opts, labels, label_len):
         """Forced CTC alignment of ``labels`` (B, ld) int32 (no sos / eos / blank; ``label_len`` (B,) int32 of them count) on this

@@ -154,6 +154,9 @@ class ArtTask(BaseTask):
                 raise NotImplementedError("--hip_bias biases the CTC prefix beam search (ArtTask: decode_type ctc_only); decode_type '%s' "
                                           "runs no such search (--hip_bias_search att biases the attention beam search of ctc_att)"
                                           % args.decode_type)
+        if int(getattr(args, "hip_ctc_merge", 0) or 0) and args.decode_type != "ctc_only":
+            raise NotImplementedError("--hip_ctc_merge merges the candidates of the CTC prefix beam search (ArtTask: decode_type ctc_only); "
+                                      "decode_type '%s' runs no such search" % args.decode_type)
         # (--hip_bias_search att: every pipeline's engine attaches the one list; its tables are shared read-only)
         bias = getattr(args, "hip_bias_model", None) if bias_att else None
         self._args = args

@@ -403,6 +403,10 @@ class CassNATTask(BaseTask):
                 path = "ESA (sample_num > 1)" if getattr(args, "sample_num", 0) > 1 else "decode_type '%s'" % args.decode_type
                 raise NotImplementedError("--hip_bias biases the CTC prefix beam search (decode_type ctc_only / ctc_att); %s runs no "
                                           "such search" % path)
+        if int(getattr(args, "hip_ctc_merge", 0) or 0) and args.decode_type not in ("ctc_only", "ctc_att"):
+            path = "ESA (sample_num > 1)" if getattr(args, "sample_num", 0) > 1 else "decode_type '%s'" % args.decode_type
+            raise NotImplementedError("--hip_ctc_merge merges the candidates of the CTC prefix beam search (decode_type ctc_only / ctc_att); "
+                                      "%s runs no such search" % path)
         plain_greedy = (args.beam_width == 1 and getattr(args, "sample_num", 0) <= 1 and not getattr(args, "hip_capture", False)
                         and args.decode_type == "att_only" and not getattr(args, "lm_weight", 0) > 0
                         and not getattr(args, "hip_ctm", ""))

@@ -21,6 +21,11 @@ With ``bias`` a ``models.bias.BiasList`` (``--hip_bias FILE``; the keyword, else
 phrases while they are being spelled (``cn_ctc_beam_bias``; include/cassnat_hip_ctc_bias.h; not in the reference): ``score_lm`` is the
 banked bonus of the completed phrases plus the value of the open match, which is taken back after the last frame.  A bias list together
 with a fused language model is refused.
+
+With ``merge`` true (``--hip_ctc_merge 1``; the keyword, else ``args.hip_ctc_merge``) candidates that spell the same label sequence are
+merged before they are ranked (``cn_ctc_beam_merged``; include/cassnat_hip_ctc_merge.h; not in the reference): the beam holds every
+sequence once and ``score_ctc`` is a prefix probability.  It serves the LM-free, the n-gram and the bias search; together with a
+TransformerLM in the loop it is refused.
 """
 import math
 
@@ -32,7 +37,7 @@ from ..models.ngram import NgramLM
 logzero, logone = -1e10, 0  # src/utils/ctc_prefix.py:11-12
 
 
-def ctc_beam_decode(model, src, src_mask, src_size, vocab, args, lm_model=None, engine=None, bias=None):
+def ctc_beam_decode(model, src, src_mask, src_size, vocab, args, lm_model=None, engine=None, bias=None, merge=None):
     """``model``: a CassNAT (src/tasks/cassnat_task.py:335-341) or the autoregressive Transformer with its CTC head
     (src/tasks/art_task.py:252-253).  ``engine``: run on this handle (a decode pipeline's) instead of the model's own."""
     ngram = isinstance(lm_model, NgramLM)
@@ -48,6 +53,12 @@ def ctc_beam_decode(model, src, src_mask, src_size, vocab, args, lm_model=None, 
     if bias is not None and lm_model is not None and float(getattr(args, "ctc_lm_weight", 0) or 0) != 0:
         raise NotImplementedError("--hip_bias together with a language model fused into the CTC beam search (ctc_lm_weight != 0) is not "
                                   "on the accelerated path: drop one of the two")
+    if merge is None:
+        merge = int(getattr(args, "hip_ctc_merge", 0) or 0)
+    if merge and lm_model is not None and not ngram and float(getattr(args, "ctc_lm_weight", 0) or 0) != 0:
+        raise NotImplementedError("--hip_ctc_merge together with a TransformerLM fused into the CTC beam search (ctc_lm_weight != 0) is not "
+                                  "on the accelerated path: that loop's score_lm is a running sum over a hypothesis' candidates and has "
+                                  "no per-prefix meaning")
     if args.ctc_lp is None:
         raise TypeError("ctc_lp must be a number (with None the reference's sort key is a lambda and sorted() fails)")
     sos = vocab.word2index["sos"]
@@ -63,7 +74,20 @@ def ctc_beam_decode(model, src, src_mask, src_size, vocab, args, lm_model=None, 
     opts.sos = sos
     lm_weight = float(getattr(args, "ctc_lm_weight", 0) or 0)
     slm = None
-    if bias is not None:
+    if merge:
+        kw = {}
+        if bias is not None:
+            if dev not in bias._dev:
+                bias.cuda(dev)
+            kw = dict(bias_desc=bias.desc(dev))
+        elif ngram and lm_weight != 0:
+            if dev not in lm_model._dev:
+                lm_model.cuda(dev)
+            kw = dict(ngram_desc=lm_model.desc(dev), lm_scale=lm_weight * math.log(10.0))
+        hyp, hlen, sc, slm, pb, pnb, nb = eng.ctc_beam_merged(feats, ratio, opts, int(args.ctc_beam), int(args.ctc_pruning), float(args.ctc_lp),
+                                                              **kw)
+        slm = slm.cpu().numpy()
+    elif bias is not None:
         if dev not in bias._dev:
             bias.cuda(dev)
         hyp, hlen, sc, slm, pb, pnb, nb = eng.ctc_beam_bias(bias.desc(dev), feats, ratio, opts, int(args.ctc_beam), int(args.ctc_pruning),

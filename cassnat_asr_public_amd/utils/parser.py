@@ -87,6 +87,10 @@ class DecodeParser(object):
         p.add_argument("--hip_ctm_unit", default="word", choices=["word", "token"],
                        help="--hip_ctm: word (default; pieces that begin with the separator start a word, a vocabulary without such "
                             "pieces is written per token) or token (one line per piece)")
+        p.add_argument("--hip_ctc_merge", default=0, type=int, choices=[0, 1],
+                       help="1: the CTC prefix beam search (decode_type ctc_only / ctc_att) merges candidates that spell the same label "
+                            "sequence before it ranks them, so the beam holds every sequence once and score_ctc is a prefix probability; "
+                            "with and without an n-gram model or --hip_bias.  0 (default): the reference's search, which does not merge")
         p.add_argument("--hip_bias", default="", type=str,
                        help="contextual phrase biasing of the CTC prefix beam search (decode_type ctc_only / ctc_att): a UTF-8 file with "
                             "one phrase per line as vocabulary pieces separated by blanks (e.g. '▁new ▁york'), optionally a tab and a "
