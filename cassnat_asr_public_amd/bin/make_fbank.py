@@ -4,7 +4,7 @@ project's own front end:
 
     python -m cassnat_asr_public_amd.bin.make_fbank --data_path data/test/wav.scp --out_dir data/fbank \\
         [--hip_fbank_conf conf/fbank.conf] [--compress true|false] [--batch_size 64] [--hip_audio auto|wav|flac] \\
-        [--hip_compress device|host]
+        [--hip_compress device|host] [--hip_segments data/test/segments]
 
 reads what `decode_asr` reads from audio (16-bit WAV, other rates and channels under the conf's --allow-* / --channel, FLAC) through
 the same dataset and the packed reader's wave / FLAC forms (``staging.PackedStaging``: one gather, one DMA, the fbank kernel), and
@@ -20,7 +20,8 @@ from a quarter of the float32 bytes.  Per pass: features on the device, ``hip.co
 stats, status words and payload bytes back to the host.  --hip_compress host brings the float32 rows back instead and runs the serial
 twins of the two kernels (the comparison leg, and the fallback).  No model, no engine handle.  The archives hold UNSPLICED features:
 left_ctx / right_ctx / skip_frame belong to the decoder.  A bad file or a non-zero status word ends the run naming the utterance;
-everything is written under temporary names and renamed at the end, so a failed run leaves nothing behind."""
+everything is written under temporary names and renamed at the end, so a failed run leaves nothing behind.  With --hip_segments (a
+Kaldi segments file over WAV recordings: ``data.segments``) the archives, utt2num_frames and the CMVN sums are per segment."""
 import argparse
 import collections
 import os
@@ -212,12 +213,12 @@ class DeviceLeg:
         return nbytes
 
 
-def open_dataset(data_path, fbank_conf="", hip_audio="auto"):
+def open_dataset(data_path, fbank_conf="", hip_audio="auto", segments=""):
     """The decoder's own dataset over the wav.scp (every header read and checked once: a bad or too short file is named here)."""
     from ..data.speech_loader import SpeechDataset
 
     args = SimpleNamespace(left_ctx=0, right_ctx=0, skip_frame=1, rank=0, hip_fbank_conf=fbank_conf or "",
-                           hip_audio="auto" if hip_audio == "auto" else "1")
+                           hip_audio="auto" if hip_audio == "auto" else "1", hip_segments=segments or "")
     ds = SpeechDataset(None, [{"name": "make_fbank", "scp_path": data_path}], args)
     if not ds.is_wave:
         raise ValueError("make_fbank: %s does not name sound files (RIFF/WAVE or FLAC)" % data_path)
@@ -236,16 +237,18 @@ def packed_batch(ds, idx, pool=None):
 
 
 def make_fbank(data_path, out_dir, fbank_conf="", compress=True, batch_size=64, hip_audio="auto", hip_compress="device", order="sorted",
-               rows_of=None):
+               rows_of=None, segments=""):
     """The tool as a function -> a dict of counters (utterances, frames, passes, the bytes copied back from the device).
     ``rows_of`` (the host leg only): a callable (list of utterance names) -> their float32 matrices, in place of the device's
     features - the seam the host-logic tests use; the entries of ``data_path`` are then only names."""
     if hip_compress not in ("device", "host"):
         raise ValueError("make_fbank: --hip_compress is device or host")
+    if rows_of is not None and segments:
+        raise ValueError("make_fbank: --hip_segments cuts audio, rows_of stands in for it")
     if rows_of is not None and hip_compress != "host":
         raise ValueError("make_fbank: rows_of stands in for the device's features on the host leg only")
     if rows_of is None:
-        ds = open_dataset(data_path, fbank_conf, hip_audio)
+        ds = open_dataset(data_path, fbank_conf, hip_audio, segments)
         utts, frames = [it[0] for it in ds._items], list(ds.wave_frames)
     else:
         ds, utts = None, [u for u, _ in kaldi_io.read_scp(data_path)]
@@ -297,10 +300,13 @@ def main(argv=None):
     p.add_argument("--hip_compress", default="device", choices=["device", "host"],
                    help="device (default): compression and statistics by the kernels behind the fbank kernel; host: the float32 rows come "
                         "back and the serial twins run (the comparison leg and the fallback)")
+    p.add_argument("--hip_segments", default="", help="a Kaldi segments file (`UTT REC START END`): the utterances are sample ranges of the WAV "
+                                                      "recordings --data_path names (decode_asr's --hip_segments)")
     a = p.parse_args(argv)
     if a.batch_size < 1:
         p.error("--batch_size must be at least 1")
-    c = make_fbank(a.data_path, a.out_dir, a.hip_fbank_conf, a.compress == "true", a.batch_size, a.hip_audio, a.hip_compress)
+    c = make_fbank(a.data_path, a.out_dir, a.hip_fbank_conf, a.compress == "true", a.batch_size, a.hip_audio, a.hip_compress,
+                   segments=a.hip_segments)
     print("make_fbank: %d utterances, %d frames in %d passes -> %s" % (c["utterances"], c["frames"], c["passes"], a.out_dir))
     return 0
 

@@ -9,7 +9,7 @@ from concurrent.futures import ThreadPoolExecutor
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libcassnat_hip.so")
 LIB_F16 = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libcassnat_hip_f16.so")
-SOURCES = ["gemm.hip", "fbank.hip", "resample.hip", "flac.hip", "conv2.hip", "conv1.hip", "rowops.hip", "attention.hip", "ctc_align.hip", "ctc_beam.hip", "fused.hip", "fused_x3.hip", "genmax.hip", "proj_x3.hip", "conformer.hip", "chain.hip", "ast.hip", "natlm.hip", "ctc_lm.hip", "ngram.hip", "ast_ngram.hip", "ast_bias.hip", "nat_ngram.hip", "ctc_times.hip", "edit_align.hip", "feats.hip", "model.hip", "handle.hip", "weights.hip", "workspace.hip", "sublayers.hip", "decode_ar.hip", "ops.hip"]
+SOURCES = ["gemm.hip", "fbank.hip", "resample.hip", "flac.hip", "conv2.hip", "conv1.hip", "rowops.hip", "attention.hip", "ctc_align.hip", "ctc_beam.hip", "fused.hip", "fused_x3.hip", "genmax.hip", "proj_x3.hip", "conformer.hip", "chain.hip", "ast.hip", "natlm.hip", "ctc_lm.hip", "ngram.hip", "ast_ngram.hip", "ast_bias.hip", "nat_ngram.hip", "ctc_times.hip", "edit_align.hip", "feats.hip", "vad.hip", "model.hip", "handle.hip", "weights.hip", "workspace.hip", "sublayers.hip", "decode_ar.hip", "ops.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 # conv1.hip: its matrix-core kernel converts every accumulator right behind the MFMAs - with the results in VGPRs (not AGPRs) the
 # 128 v_accvgpr_read per block of 128 cells go (the kernel is bound by its VALU instruction count)
@@ -30,7 +30,7 @@ def _stale(target, deps):
 def build(force=False, verbose=False, extra_flags=(), lib=LIB, objdir=None):
     """extra_flags / lib / objdir: measurement variants (e.g. -DFX_STAMPS into a library of their own); the product is the default."""
     headers = [os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".h")]
-    headers += [os.path.join(os.path.dirname(CSRC), "..", "include", h) for h in ("cassnat_hip.h", "cassnat_hip_ctc_ngram.h", "cassnat_hip_attention_proj.h", "cassnat_hip_ast_ngram.h", "cassnat_hip_nat_ngram.h", "cassnat_hip_ctc_times.h", "cassnat_hip_score.h", "cassnat_hip_ctc_bias.h", "cassnat_hip_ast_bias.h", "cassnat_hip_feats.h", "cassnat_hip_ctc_merge.h")]
+    headers += [os.path.join(os.path.dirname(CSRC), "..", "include", h) for h in ("cassnat_hip.h", "cassnat_hip_ctc_ngram.h", "cassnat_hip_attention_proj.h", "cassnat_hip_ast_ngram.h", "cassnat_hip_nat_ngram.h", "cassnat_hip_ctc_times.h", "cassnat_hip_score.h", "cassnat_hip_ctc_bias.h", "cassnat_hip_ast_bias.h", "cassnat_hip_feats.h", "cassnat_hip_ctc_merge.h", "cassnat_hip_vad.h")]
     objdir = objdir or os.path.join(CSRC, "build")
     os.makedirs(objdir, exist_ok=True)
 

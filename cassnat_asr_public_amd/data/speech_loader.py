@@ -2,6 +2,7 @@
 skip -> zero-padded batch + length ratios.  Only what CassNATTask("test") uses is mirrored (SpeechDataset,
 SpeechDataLoader); the training-only DynamicDataset / SSL loaders are out of scope.
 """
+import collections
 import functools
 import os
 import threading
@@ -10,16 +11,23 @@ import numpy as np
 import torch
 from torch.utils.data import DataLoader, Dataset
 
-from . import flac_io, kaldi_io, wave_io
+from . import flac_io, kaldi_io, segments, wave_io
 from .feat_op import context_feat, skip_feat
 
 
 class SingleSet(object):
     """One {name, scp_path[, text_label]} stream -> list of (utt, ark specifier, token ids)."""
 
-    def __init__(self, vocab, data_path, rank=0):
+    def __init__(self, vocab, data_path, rank=0, segs=None):
+        """``segs``: the segments of ``--hip_segments`` ([(utt, rec, start, end)]) - the entries of the scp are then recordings and
+        the items the segments of those recordings, in the segments file's order; ``ranges`` keeps their (rec, start, end)."""
         self.name = data_path["name"]
         entries = kaldi_io.read_scp(data_path["scp_path"])
+        self.ranges, self.recordings = None, [utt for utt, _ in entries]
+        if segs is not None:
+            table = dict(entries)
+            mine = [g for g in segs if g[1] in table]
+            entries, self.ranges = [(utt, table[rec]) for utt, rec, _, _ in mine], [(rec, start, end) for _, rec, start, end in mine]
         if rank == 0:
             print("Reading %d lines from %s" % (len(entries), data_path["scp_path"]))
         labels = None
@@ -163,6 +171,11 @@ def sniff_wave_set(items, mode="auto"):
     return True
 
 
+# --hip_segments keeps one memory map per recording; every map holds a descriptor of its file, so a set of more recordings than this
+# keeps the most recently used ones (a map that goes is closed with the last view into it, and mapped again when a segment asks)
+MAX_SEGMENT_MAPS = 256
+
+
 class SpeechDataset(Dataset):
     def __init__(self, vocab, data_paths, args):
         self.left_context, self.right_context = args.left_ctx, args.right_ctx
@@ -172,10 +185,21 @@ class SpeechDataset(Dataset):
         # set (by the pipelined decoder, for the length of a decode) when the consumer applies the global CMVN itself, on the
         # device (pipeline.DecodePipelines(cmvn=...)): the fast path below then hands the features over as they are in the archive
         self.device_cmvn = False
-        self.data_streams = [SingleSet(vocab, p, getattr(args, "rank", 0)) for p in data_paths]
+        # --hip_segments: the utterances are sample ranges of the recordings the scp names (``data.segments``)
+        seg_path = getattr(args, "hip_segments", "") or ""
+        segs = segments.read_segments(seg_path) if seg_path else None
+        self.data_streams = [SingleSet(vocab, p, getattr(args, "rank", 0), segs) for p in data_paths]
         self._items = [it for s in self.data_streams for it in s.items]
+        self.seg_ranges = [r for s in self.data_streams for r in s.ranges] if segs is not None else None
+        self.wave_ranges = self.segment_offsets = None
+        self._maps = collections.OrderedDict()
+        if segs is not None:
+            segments.check_recordings(segs, [r for s in self.data_streams for r in s.recordings], seg_path)
         self.is_flac = False
         found = sniff_wave_set(self._items, getattr(args, "hip_audio", "auto"))
+        if segs is not None and found is not True:
+            raise ValueError("--hip_segments %s: %s" % (seg_path, "cutting segments out of FLAC files is not implemented (WAV recordings only)"
+                                                        if found == "flac" else "the set is not audio: segments cut sample ranges out of WAV recordings"))
         if found:
             self._init_wave_set(args, flac=found == "flac")
 
@@ -195,13 +219,25 @@ class SpeechDataset(Dataset):
         self.wave_frames, self.wave_formats = [], []
         own = int(round(self.sample_rate))
         self.flac_infos = [] if flac else None  # a FLAC set: per file its path and metadata (``flac_io.Info``), read once here
-        for utt, spec, _ in self._items:
+        headers = {}  # (--hip_segments: one look at a recording's header, however many segments it carries)
+        if self.seg_ranges is not None:
+            self.wave_ranges, self.segment_offsets = [], {}
+        for k, (utt, spec, _) in enumerate(self._items):
             if flac:
                 path = flac_io.flac_path(spec)
                 info = flac_io.checked(path, self.sample_rate, utt, **self.wave_admit)
                 # (a STREAMINFO total of 0 means unknown: the index says how many samples the frames hold)
                 n, rate, channels = info.total or flac_io.frame_index(path, info, utt).samples, info.rate, info.channels
                 self.flac_infos.append((path, info, n))
+            elif self.seg_ranges is not None:
+                rec, start, end = self.seg_ranges[k]
+                if spec not in headers:
+                    headers[spec] = wave_io.wave_format(spec, self.sample_rate, rec, **self.wave_admit)
+                total, rate, channels = headers[spec]
+                first, last = segments.sample_range(start, end, rate, total, utt, rec)
+                n = last - first
+                self.wave_ranges.append((first, last))
+                self.segment_offsets[utt] = (rec, first / rate)
             else:
                 n, rate, channels = wave_io.wave_format(spec, self.sample_rate, utt, **self.wave_admit)
             if rate != own:
@@ -213,8 +249,9 @@ class SpeechDataset(Dataset):
                 n = hip.resample_num_samples(rate, own, n)
             frames = frames_of(self.fbank_opts, n)
             if frames < 1:
-                raise ValueError("utterance %s (%s): %d samples%s give no frame (shorter than one analysis window)"
-                                 % (utt, spec, n, "" if rate == own else " at %d Hz (resampled from %d Hz)" % (own, rate)))
+                raise ValueError("%s (%s): %d samples%s give no frame (shorter than one analysis window)"
+                                 % ("utterance %s" % utt if self.seg_ranges is None else "segment %s of recording %s" % (utt, self.seg_ranges[k][0]),
+                                    spec, n, "" if rate == own else " at %d Hz (resampled from %d Hz)" % (own, rate)))
             self.wave_frames.append(frames)
             self.wave_formats.append((rate, channels))
         # (a set of mono files at the front-end's rate - every set there was before the options - hands out plain sample views)
@@ -241,6 +278,18 @@ class SpeechDataset(Dataset):
             path, info, _ = self.flac_infos[idx]
             view = flac_io.audio_view(path, info)
             return utt, FlacFrames(view, flac_io.frame_index(path, info, utt, view)), text
+        if self.is_wave and self.wave_ranges is not None:
+            # (--hip_segments: the slice [first * channels, last * channels) of the recording's interleaved samples - for a mono file
+            # at the front-end's rate the plain int16 pass -, from ONE memory map per recording, kept for the life of the dataset)
+            view = self._maps.get(spec)
+            if view is None:
+                view = self._maps[spec] = wave_io.pcm_frames(spec, self.sample_rate, self.seg_ranges[idx][0], **self.wave_admit)[0]
+                if len(self._maps) > MAX_SEGMENT_MAPS:  # (a map holds a file descriptor: the least recently used one goes)
+                    self._maps.popitem(last=False)
+            else:
+                self._maps.move_to_end(spec)
+            (first, last), channels = self.wave_ranges[idx], self.wave_formats[idx][1]
+            return utt, view[first * channels:last * channels], text
         if self.is_wave:  # (the samples as the file holds them; normalisation happens with the features, on the device)
             if self.wave_plain:
                 return utt, wave_io.pcm_view(spec, self.sample_rate, utt), text

@@ -257,6 +257,61 @@ def feats_stats_host(feats, lens, payload=None, out_off=None, status=None, flavo
     return stats
 
 
+VAD_PARTS = abi.VAD_CONSTANTS["CN_VAD_PARTS"]
+
+
+def frame_energy(staged, staged_bytes, off, samples, out_off, rows, N, shift, channels, channel, remove_dc, max_frames, num, e, flavour=None):
+    """Per-frame integer energies of staged int16 audio on the device (cn_op_frame_energy; include/cassnat_hip_vad.h): ``staged`` uint8
+    CUDA bytes, row r a run of samples[r] sample frames of ``channels`` interleaved channels at BYTE offset off[r] (a multiple of 16);
+    frame t of row r -> index out_off[r] + t of ``num`` (int64 CUDA) and ``e`` (float64 CUDA: the log-energy), at most ``max_frames``
+    frames per row, on the current stream.  ``off`` / ``samples`` / ``out_off`` int32 CUDA.  Nothing else is written."""
+    assert staged.is_contiguous() and staged.element_size() == 1 and 0 <= int(staged_bytes) <= staged.numel()
+    assert min(off.numel(), samples.numel(), out_off.numel()) >= rows and num.element_size() == 8 and e.element_size() == 8
+    L = lib(flavour)
+    check(L.cn_op_frame_energy(_ptr(staged), int(staged_bytes), _ptr(off), _ptr(samples), _ptr(out_off), int(rows), int(N), int(shift),
+                               int(channels), int(channel), int(bool(remove_dc)), int(max_frames), _ptr(num), _ptr(e), current_stream()),
+          "cn_op_frame_energy", L)
+    return num, e
+
+
+def frame_energy_host(staged, off, samples, out_off, N, shift, channels, channel, remove_dc, max_frames, num, e, staged_bytes=None, flavour=None):
+    """``frame_energy`` on numpy arrays through the serial host entry (cn_frame_energy_host): no GPU call.  ``num`` (int64) and ``e``
+    (float64) are written in place."""
+    assert staged.dtype == np.uint8 and staged.flags.c_contiguous and num.dtype == np.int64 and e.dtype == np.float64
+    assert off.dtype == np.int32 and samples.dtype == np.int32 and out_off.dtype == np.int32 and off.size == samples.size == out_off.size
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    L = lib(flavour)
+    check(L.cn_frame_energy_host(p(staged), staged.size if staged_bytes is None else int(staged_bytes), p(off), p(samples), p(out_off), off.size,
+                                 int(N), int(shift), int(channels), int(channel), int(bool(remove_dc)), int(max_frames), p(num), p(e)),
+          "cn_frame_energy_host", L)
+    return num, e
+
+
+def vad_decide(e, rec_off, rec_frames, recs, thr0, mean_scale, context, proportion, thr, dec, flavour=None):
+    """Kaldi's energy VAD decision on the device (cn_op_vad_decide): recording i holds the frames e[rec_off[i] : rec_off[i] +
+    rec_frames[i]] (``e`` float64 CUDA, the offsets and counts int32 CUDA) -> ``dec`` (uint8 CUDA, one byte per frame at the frames'
+    indices) and ``thr`` (float64 CUDA of at least recs * (1 + VAD_PARTS): the thresholds first, the partial sums behind them), on the
+    current stream."""
+    assert e.element_size() == 8 and thr.element_size() == 8 and thr.numel() >= recs * (1 + VAD_PARTS) and dec.element_size() == 1
+    assert min(rec_off.numel(), rec_frames.numel()) >= recs
+    L = lib(flavour)
+    check(L.cn_op_vad_decide(_ptr(e), _ptr(rec_off), _ptr(rec_frames), int(recs), float(thr0), float(mean_scale), int(context),
+                             float(proportion), _ptr(thr), _ptr(dec), current_stream()), "cn_op_vad_decide", L)
+    return thr, dec
+
+
+def vad_decide_host(e, rec_off, rec_frames, thr0, mean_scale, context, proportion, thr, dec, flavour=None):
+    """``vad_decide`` on numpy arrays through the serial host entry (cn_vad_decide_host): ``thr`` (float64, one per recording) and
+    ``dec`` (uint8) are written in place."""
+    assert e.dtype == np.float64 and thr.dtype == np.float64 and dec.dtype == np.uint8 and rec_off.dtype == np.int32 and rec_frames.dtype == np.int32
+    assert rec_off.size == rec_frames.size <= thr.size
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    L = lib(flavour)
+    check(L.cn_vad_decide_host(p(e), p(rec_off), p(rec_frames), rec_off.size, float(thr0), float(mean_scale), int(context), float(proportion),
+                               p(thr), p(dec)), "cn_vad_decide_host", L)
+    return thr, dec
+
+
 def splice_rows(src, off, lens, out, left, right, skip, pad, mean=None, std=None):
     """Frame splicing and skipping on the device (cn_op_splice_rows): ``src`` float32 CUDA rows of F0 features, utterance r at row
     off[r] with lens[r] rows -> ``out`` (rows, T_out, (left + right + 1) * F0) on the current stream: the dataset's order - CMVN

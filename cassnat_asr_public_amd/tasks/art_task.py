@@ -24,6 +24,7 @@ import torch
 import torch.distributed as dist
 
 from .. import dist as cdist
+from ..data.segments import rough_frames, utterance_order
 from ..data.vocab import Vocab
 from ..models import make_conformer, make_transformer
 from ..utils import ctm, util
@@ -63,6 +64,8 @@ class ArtTask(BaseTask):
         """Indices of this rank's utterances (None = all): the length-sorted snake deal of CassNATTask."""
         if self.world == 1:
             return None
+        if getattr(args, "hip_segments", ""):  # (the utterances are the segments: their durations order the list)
+            return cdist.shard_indices(np.array(rough_frames(args)), self.world, self.rank)
         n = sum(1 for _ in open(args.test_paths[0]["scp_path"]))
         lengths = np.zeros(n)
         u2n = args.test_paths[0].get("utt2num_frames")
@@ -242,12 +245,12 @@ class ArtTask(BaseTask):
                 dist.all_gather_object(gathered, times)
                 times = {k: v for part in gathered for k, v in part.items()}
         if self.rank == 0:
-            order = [line.split()[0] for line in open(args.test_paths[0]["scp_path"]) if line.strip()]
+            order = utterance_order(args)
             with open(args.result_file, "w") as out_file:
                 for utt in order:
                     print(results[utt], flush=True, file=out_file)
             if getattr(args, "hip_ctm", ""):
-                missed = ctm.write(args.hip_ctm, order, times, ctm.seconds_per_frame(args), ctm.unit_of(args, self.vocab))
+                missed = ctm.write(args.hip_ctm, order, times, ctm.seconds_per_frame(args), ctm.unit_of(args, self.vocab), offsets=self.test_loader.dataset.segment_offsets)
                 print("CTM: %d of %d utterances could not be aligned (their units share the frames evenly, confidence 0)" % (missed, len(order)))
             if getattr(args, "hip_score", ""):  # (a post-pass over the words just printed: utils.score)
                 from ..utils import score

@@ -14,6 +14,7 @@ import torch
 import torch.distributed as dist
 
 from .. import dist as cdist
+from ..data.segments import rough_frames, utterance_order
 from ..data.vocab import Vocab
 from ..models import make_cassnat_model
 from ..utils import ctm, util
@@ -106,6 +107,8 @@ class CassNATTask(BaseTask):
         one, else - when `need`ed - the matrix headers of the ark entries; zeros otherwise."""
         from ..data import kaldi_io
 
+        if getattr(args, "hip_segments", ""):  # (the utterances are the segments: their durations order the list)
+            return np.array(rough_frames(args))
         scp = args.test_paths[0]["scp_path"]
         entries = kaldi_io.read_scp(scp)
         u2n = args.test_paths[0].get("utt2num_frames") or os.path.join(os.path.dirname(scp), "utt2num_frames")
@@ -436,7 +439,7 @@ class CassNATTask(BaseTask):
             dist.all_gather_object(gathered, results)
             results = {k: v for part in gathered for k, v in part.items()}
         if self.rank == 0:
-            order = [line.split()[0] for line in open(args.test_paths[0]["scp_path"]) if line.strip()]
+            order = utterance_order(args)
             with open(args.result_file, "w") as out:
                 for utt in order:
                     print(utt + " " + " ".join(results[utt][0]), flush=True, file=out)
@@ -446,7 +449,7 @@ class CassNATTask(BaseTask):
                         print(utt + " " + str(max(-3, min(3, results[utt][1]))), file=f)
             if getattr(args, "hip_ctm", ""):
                 missed = ctm.write(args.hip_ctm, order, {utt: results[utt][2] for utt in order}, ctm.seconds_per_frame(args),
-                                   ctm.unit_of(args, self.vocab))
+                                   ctm.unit_of(args, self.vocab), offsets=self.test_loader.dataset.segment_offsets)
                 print("CTM: %d of %d utterances could not be aligned (their units share the frames evenly, confidence 0)" % (missed, len(order)))
             if getattr(args, "hip_score", ""):  # (a post-pass over the words just printed: utils.score)
                 from ..utils import score

@@ -11,7 +11,8 @@ Timing.  One subsampled frame is ``4 * skip_frame * frame_shift`` seconds (two s
 frame shift that of ``--hip_fbank_conf`` when given, else 10 ms.  A span of frames [s, e) is written as start ``s`` and duration ``e - s``
 of those units: no receptive-field offset is applied, although a subsampled frame sees input frames on both sides of the four it stands for.
 
-Line.  ``UTT 1 START DUR WORD CONF`` with ``%.2f %.2f ... %.3f``.  An empty hypothesis writes no line.  An utterance the aligner could
+Line.  ``UTT 1 START DUR WORD CONF`` with ``%.2f %.2f ... %.3f``; with ``--hip_segments`` ``REC 1 (segment start + START) DUR WORD CONF``,
+the segment start being first / rate of its sample range (``data.segments``).  An empty hypothesis writes no line.  An utterance the aligner could
 not align (status not 0, a label the walk never entered, a path of probability zero) spreads its units evenly over its valid frames
 with confidence 0.000."""
 import math
@@ -117,31 +118,39 @@ def aligned(record):
     return status == 0 and all(s >= 0 and e > s for s, e in zip(start, end))
 
 
-def lines(utt, record, sec, unit):
-    """The CTM lines of one utterance."""
+def lines(utt, record, sec, unit, offset=None):
+    """The CTM lines of one utterance.  ``offset``: (recording, seconds) of an utterance that is a segment of a recording
+    (``--hip_segments``) - the lines then carry the recording's id and times in the recording."""
+    if offset is not None:
+        return ["%s 1 %.2f %.2f %s %.3f" % (offset[0], offset[1] + s, d, text, c) for s, d, text, c in _rows(record, sec, unit)]
+    return ["%s 1 %.2f %.2f %s %.3f" % (utt, s, d, text, c) for s, d, text, c in _rows(record, sec, unit)]
+
+
+def _rows(record, sec, unit):
+    """(start, duration, text, confidence) of every unit of one utterance, times in seconds from the utterance's start."""
     pieces, start, end, conf, status, n = record
     us = units(pieces, unit)
     out = []
     if not aligned(record):  # the units share the utterance's frames evenly, confidence 0
         for k, (_, _, text) in enumerate(us):
             s, e = n * k / len(us), n * (k + 1) / len(us)
-            out.append("%s 1 %.2f %.2f %s %.3f" % (utt, s * sec, (e - s) * sec, text, 0.0))
+            out.append((s * sec, (e - s) * sec, text, 0.0))
         return out
     for a, b, text in us:
         c = math.exp(min(conf[a:b + 1]))
-        out.append("%s 1 %.2f %.2f %s %.3f" % (utt, start[a] * sec, (end[b] - start[a]) * sec, text, min(1.0, max(0.0, c))))
+        out.append((start[a] * sec, (end[b] - start[a]) * sec, text, min(1.0, max(0.0, c))))
     return out
 
 
-def write(path, order, records, sec, unit):
+def write(path, order, records, sec, unit, offsets=None):
     """Writes the file in the utterance order ``order``; returns the number of utterances that were not aligned (empty hypotheses
-    do not count)."""
+    do not count).  ``offsets``: {utt: (recording, segment start in seconds)} under ``--hip_segments`` (``lines``)."""
     unaligned = 0
     with open(path, "w", encoding="utf-8") as f:
         for utt in order:
             rec = records[utt]
             if rec[0] and not aligned(rec):
                 unaligned += 1
-            for line in lines(utt, rec, sec, unit):
+            for line in lines(utt, rec, sec, unit, None if offsets is None else offsets[utt]):
                 print(line, file=f)
     return unaligned

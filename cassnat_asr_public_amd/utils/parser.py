@@ -72,6 +72,12 @@ class DecodeParser(object):
                        help="decode from audio: auto (default) - a --data_path whose entries are RIFF/WAVE files (a wav.scp of plain "
                             "paths: 16-bit PCM, one channel) is decoded from the sound files, the Kaldi fbank features computed on the "
                             "device; 0: never look, the entries are feature matrices; 1: the entries must be WAV files")
+        p.add_argument("--hip_segments", default="", type=str,
+                       help="decode from audio: a Kaldi segments file (`UTT REC START END` lines, seconds, END -1 = the end of the "
+                            "recording): the utterances are sample ranges of the WAV recordings --data_path names, cut from the memory "
+                            "maps (first = floor(START * rate + 0.5); no file is written); result file, --text_label, --hip_score and "
+                            "--hip_bias see segment ids, --hip_ctm writes times in the recording.  A bad segment is an error, not a warning; "
+                            "FLAC recordings and a fifth field are refused")
         p.add_argument("--hip_fbank_conf", default="", type=str,
                        help="Kaldi option file of the fbank front-end for audio input (--name=value lines: sample-frequency, frame-length, "
                             "frame-shift, preemphasis-coefficient, remove-dc-offset, window-type, num-mel-bins, low-freq, high-freq, "
