@@ -107,12 +107,12 @@ __global__ __launch_bounds__(256) void ctc_align_kernel(AlignArgs a) {
 
 int launch_ctc_align(const AlignArgs& a, hipStream_t s) {
     if (a.B <= 0 || a.Tp <= 0) return 0;
-    CN_HIP_CHECK(hipMemsetAsync(a.ymax, 0, sizeof(int), s));
     const size_t lds = (256 + 4 + 2 * (size_t)(a.Tp + 1)) * sizeof(int);
-    if (lds > 160 * 1024) {
+    if (lds > 160 * 1024) {  // (before the first write: a refused call leaves ymax as it was)
         cn_set_error("ctc_align: T' too large for one workgroup's LDS");
         return -1;
     }
+    CN_HIP_CHECK(hipMemsetAsync(a.ymax, 0, sizeof(int), s));
     static CnAttrOnce attr_once;
     int attr_dev;
     if (attr_once.need(&attr_dev)) {
@@ -160,7 +160,10 @@ __global__ __launch_bounds__(64) void ctc_collapse_kernel(const int* __restrict_
 
 int launch_ctc_collapse(const int* best, const unsigned char* km, int B, int Tp, int sos, int pad, int ld, int* tgt, int* len, int* keylen,
                         int* maxlen, hipStream_t s) {
-    if (B <= 0 || Tp <= 0 || ld < Tp + 1) return -1;
+    if (B <= 0 || Tp <= 0 || ld < Tp + 1) {
+        cn_set_error("ctc_collapse: need B >= 1, T' >= 1 and rows of at least T' + 1 labels (ld >= T' + 1)");
+        return -1;
+    }
     CN_HIP_CHECK(hipMemsetAsync(maxlen, 0, sizeof(int), s));
     hipLaunchKernelGGL(ctc_collapse_kernel, dim3(B), dim3(64), 0, s, best, km, B, Tp, sos, pad, ld, tgt, len, keylen, maxlen);
     CN_HIP_CHECK(hipGetLastError());

@@ -470,10 +470,11 @@ __global__ __launch_bounds__(256) void ctc_viterbi_kernel(ViterbiArgs a) {
     }
     if (tid == 0) {
         for (int t = 0; t < Tp; ++t) out[t] = a.blank;
-        if (xb >= 1 && xb <= Tp) {
+        if (xb >= 0 && xb <= Tp) {
             const int i1 = plen - 1, i2 = plen - 2 >= 0 ? plen - 2 : S - 1;  // (python index -1 wraps to the last state)
             int cur = alx[i1] > alx[i2] ? i1 : i2;
-            out[xb - 1] = path[cur];
+            // src_size 0: aligned[b, -1] is the LAST frame (python index -1 wraps) and the back-trace has no step; alx = alpha[0]
+            out[xb >= 1 ? xb - 1 : Tp - 1] = path[cur];
             for (int t = xb - 1; t >= 1; --t) {
                 cur = cur - (int)bp[(long long)t * S + cur];
                 if (cur < 0) cur += S;

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/cassnat_hip.h"
+#include "../../include/cassnat_hip_align.h"
 #include "../../include/cassnat_hip_attention_proj.h"
 #include "ctc_bias_search.h"
 #include "ctc_merge_search.h"
@@ -915,24 +916,72 @@ extern "C" int cn_op_logsoftmax_argmax(float* logits, int32_t M, int32_t V, int3
     return launch_logsoftmax_argmax(logits, M, V, V, arg, maxlp, write_logp, (hipStream_t)stream);
 }
 
+// Every form of the alignment kernel from one descriptor (include/cassnat_hip.h, cn_align_desc): everything that would be refused is
+// refused here, before anything touches the caller's buffers.
+static int op_ctc_align_desc(const char* who, const cn_align_desc* d, void* stream) {
+    static_assert(sizeof(UttMeta) == 4 * sizeof(int32_t), "cn_align_desc: utt_meta is [B][4] int32");
+    auto refuse = [&](const char* what) {
+        cn_set_error(std::string(who) + ": " + what);
+        return -1;
+    };
+    if (!d) return refuse("null descriptor");
+    if (!d->best || !d->keymask || !d->size_ratio) return refuse("null best, keymask or size_ratio");
+    if (!d->shift || !d->src_size || !d->ylen || !d->ymax || !d->intervals) return refuse("null shift, src_size, ylen, ymax or intervals");
+    if (d->B < 1 || d->Tp < 1) return refuse("B and Tp must be >= 1");
+    if (d->src_mod < 0 || d->left < 0 || d->right < 0) return refuse("src_mod, left and right must not be negative");
+    hipStream_t s = (hipStream_t)stream;
+    if (d->utt_meta) {  // the kernel indexes its LDS rows and the key mask by the records' T': check them where they can be read
+        const int n = d->src_mod > 0 ? std::min(d->src_mod, d->B) : d->B;
+        std::vector<UttMeta> meta((size_t)n);
+        CN_HIP_CHECK(hipMemcpyAsync(meta.data(), d->utt_meta, (size_t)n * sizeof(UttMeta), hipMemcpyDeviceToHost, s));
+        CN_HIP_CHECK(hipStreamSynchronize(s));
+        for (const UttMeta& m : meta)
+            if (m.tp < 1 || m.tp > d->Tp) return refuse("a utt_meta record's T' lies outside 1 .. Tp");
+    }
+    AlignArgs a;
+    a.best = d->best;
+    a.keymask = d->keymask;
+    a.size_ratio = d->size_ratio;
+    a.B = d->B;
+    a.Tp = d->Tp;
+    a.blank = d->blank;
+    a.left = d->left;
+    a.right = d->right;
+    a.src_mod = d->src_mod;
+    a.shift = d->shift;
+    a.src_size = d->src_size;
+    a.ylen = d->ylen;
+    a.ymax = d->ymax;
+    a.intervals = d->intervals;
+    a.raw_path = d->raw_path;
+    a.ylen_in = d->ylen_in;
+    a.utt_meta = reinterpret_cast<const UttMeta*>(d->utt_meta);
+    a.no_trigger = d->no_trigger;
+    return launch_ctc_align(a, s);
+}
+
+extern "C" int cn_op_ctc_align_desc(const cn_align_desc* d, void* stream) { return op_ctc_align_desc("cn_op_ctc_align_desc", d, stream); }
+extern "C" int32_t cn_align_desc_size(void) { return (int32_t)sizeof(cn_align_desc); }
+
+// cn_op_ctc_align: the descriptor of the plain form
 extern "C" int cn_op_ctc_align(const int32_t* best, const uint8_t* keymask, const float* size_ratio, int32_t B,
                                int32_t Tp, int32_t blank, int32_t left, int32_t right, int32_t* shift,
                                int32_t* src_size, int32_t* ylen, int32_t* ymax, int32_t* intervals, void* stream) {
-    AlignArgs a;
-    a.best = best;
-    a.keymask = keymask;
-    a.size_ratio = size_ratio;
-    a.B = B;
-    a.Tp = Tp;
-    a.blank = blank;
-    a.left = left;
-    a.right = right;
-    a.shift = shift;
-    a.src_size = src_size;
-    a.ylen = ylen;
-    a.ymax = ymax;
-    a.intervals = intervals;
-    return launch_ctc_align(a, (hipStream_t)stream);
+    cn_align_desc d = {};
+    d.best = best;
+    d.keymask = keymask;
+    d.size_ratio = size_ratio;
+    d.B = B;
+    d.Tp = Tp;
+    d.blank = blank;
+    d.left = left;
+    d.right = right;
+    d.shift = shift;
+    d.src_size = src_size;
+    d.ylen = ylen;
+    d.ymax = ymax;
+    d.intervals = intervals;
+    return op_ctc_align_desc("cn_op_ctc_align", &d, stream);
 }
 
 // the two kernels of decode_type ctc_only / ctc_att on given log-posteriors (test entries; all pointers device)
@@ -962,6 +1011,14 @@ extern "C" int cn_op_ctc_prefix_beam(const float* logp, const float* size_ratio,
 extern "C" int cn_op_ctc_viterbi(const float* logp, const uint8_t* keymask, const float* size_ratio, const int32_t* labels,
                                  const int32_t* label_len, int32_t B, int32_t Tp, int32_t V, int32_t ld, int32_t ymax, int32_t blank,
                                  int32_t* out_path, void* stream) {
+    if (!logp || !keymask || !size_ratio || !labels || !label_len || !out_path) {
+        cn_set_error("cn_op_ctc_viterbi: null pointer (logp, keymask, size_ratio, labels, label_len, out_path)");
+        return -1;
+    }
+    if (B < 1 || Tp < 1 || V < 1 || ymax < 1 || ld < ymax) {
+        cn_set_error("cn_op_ctc_viterbi: B, Tp, V and ymax must be >= 1, ld >= ymax");
+        return -1;
+    }
     hipStream_t s = (hipStream_t)stream;
     Scratch sc("cn_op_ctc_viterbi", s);
     unsigned char* bp = (unsigned char*)sc.alloc((size_t)B * Tp * (2 * (size_t)ymax + 1));
@@ -1027,10 +1084,123 @@ extern "C" int cn_op_edit_align(const int32_t* ref_dev, int64_t ref_total, const
     return sc.finish(launch_edit_align(a, bp_lds_limit, s));
 }
 
+static int op_greedy_pack(const char* who, const int32_t* tok, const float* val, const int32_t* ylen, int32_t B, int32_t U, int32_t sos,
+                          int32_t hyp_stride, int32_t* hyp, int32_t* hyp_len, double* score, int32_t sub, const int32_t* utt_meta_dev,
+                          const int32_t* ymax_dev, const int32_t* row_off_dev, void* stream) {
+    if (!tok || !val || !ylen || !hyp || !hyp_len || !score) {
+        cn_set_error(std::string(who) + ": null pointer (tok, val, ylen, hyp, hyp_len, score)");
+        return -1;
+    }
+    if (B < 1 || U < 1 || hyp_stride < 1 || sub < 0) {
+        cn_set_error(std::string(who) + ": B, U and hyp_stride must be >= 1, sub >= 0");
+        return -1;
+    }
+    // device-side records the kernel indexes by are read back and checked, as cn_op_ctc_align_desc checks its records' T': a batch
+    // inside the call; offsets that keep every utterance's rows inside the B * U rows tok / val hold (what a plan of <= U rows each gives)
+    hipStream_t s = (hipStream_t)stream;
+    if (utt_meta_dev) {
+        std::vector<UttMeta> meta((size_t)B);
+        CN_HIP_CHECK(hipMemcpyAsync(meta.data(), utt_meta_dev, (size_t)B * sizeof(UttMeta), hipMemcpyDeviceToHost, s));
+        CN_HIP_CHECK(hipStreamSynchronize(s));
+        for (const UttMeta& m : meta)
+            if (m.sub_lo < 0 || m.sub_hi < m.sub_lo || m.sub_hi > B) {
+                cn_set_error(std::string(who) + ": a utt_meta record's batch lies outside 0 .. B");
+                return -1;
+            }
+    }
+    if (row_off_dev) {
+        std::vector<int32_t> off((size_t)B + 1);
+        CN_HIP_CHECK(hipMemcpyAsync(off.data(), row_off_dev, ((size_t)B + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        CN_HIP_CHECK(hipStreamSynchronize(s));
+        for (int b = 0; b <= B; ++b)
+            if (off[b] < 0 || (long long)off[b] > (long long)b * U || (b > 0 && off[b] < off[b - 1])) {
+                cn_set_error(std::string(who) + ": row_off must be non-decreasing with 0 <= row_off[b] <= b * U");
+                return -1;
+            }
+    }
+    return launch_greedy_pack(tok, val, ylen, B, U, sos, hyp_stride, hyp, hyp_len, score, (hipStream_t)stream, sub,
+                              reinterpret_cast<const UttMeta*>(utt_meta_dev), ymax_dev, row_off_dev);
+}
+
 extern "C" int cn_op_greedy_pack(const int32_t* tok, const float* val, const int32_t* ylen, int32_t B, int32_t U,
                                  int32_t sos, int32_t hyp_stride, int32_t* hyp, int32_t* hyp_len, double* score,
                                  void* stream) {
-    return launch_greedy_pack(tok, val, ylen, B, U, sos, hyp_stride, hyp, hyp_len, score, (hipStream_t)stream);
+    return op_greedy_pack("cn_op_greedy_pack", tok, val, ylen, B, U, sos, hyp_stride, hyp, hyp_len, score, 0, nullptr, nullptr, nullptr, stream);
+}
+
+extern "C" int cn_op_greedy_pack_rows(const int32_t* tok, const float* val, const int32_t* ylen, int32_t B, int32_t U, int32_t sos,
+                                      int32_t hyp_stride, int32_t* hyp, int32_t* hyp_len, double* score, int32_t sub,
+                                      const int32_t* utt_meta_dev, const int32_t* ymax_dev, const int32_t* row_off_dev, void* stream) {
+    return op_greedy_pack("cn_op_greedy_pack_rows", tok, val, ylen, B, U, sos, hyp_stride, hyp, hyp_len, score, sub, utt_meta_dev, ymax_dev,
+                          row_off_dev, stream);
+}
+
+extern "C" int cn_op_ctc_collapse(const int32_t* best, const uint8_t* keymask, int32_t B, int32_t Tp, int32_t sos, int32_t pad, int32_t ld,
+                                  int32_t* tgt, int32_t* len, int32_t* keylen, int32_t* maxlen, void* stream) {
+    if (!best || !keymask || !tgt || !len || !keylen || !maxlen) {
+        cn_set_error("cn_op_ctc_collapse: null pointer (best, keymask, tgt, len, keylen, maxlen)");
+        return -1;
+    }
+    return launch_ctc_collapse(best, keymask, B, Tp, sos, pad, ld, tgt, len, keylen, maxlen, (hipStream_t)stream);
+}
+
+extern "C" int cn_op_esa_paths(const int32_t* top2_idx, const float* top2_val, const uint8_t* select, float threshold, int32_t* best,
+                               int32_t M, int32_t n, void* stream) {
+    if (!top2_idx || !top2_val || !best) {
+        cn_set_error("cn_op_esa_paths: null pointer (top2_idx, top2_val, best)");
+        return -1;
+    }
+    if (M < 1 || n < 1) {
+        cn_set_error("cn_op_esa_paths: M and n must be >= 1");
+        return -1;
+    }
+    return launch_esa_paths(top2_idx, top2_val, select, threshold, best, M, n, (hipStream_t)stream);
+}
+
+extern "C" int cn_op_keymask(const float* feats, int32_t B, int32_t T, int32_t F, int32_t Tp, int32_t stride, float padding, uint8_t* keymask,
+                             void* stream) {
+    if (!feats || !keymask) {
+        cn_set_error("cn_op_keymask: null pointer (feats, keymask)");
+        return -1;
+    }
+    if (B < 1 || T < 1 || F < 1 || Tp < 1 || stride < 1) {
+        cn_set_error("cn_op_keymask: B, T, F, Tp and stride must be >= 1");
+        return -1;
+    }
+    if ((long long)B * Tp > 0x7fffffffLL || (long long)stride * (Tp - 1) > 0x7fffffffLL) {
+        cn_set_error("cn_op_keymask: B * Tp and stride * (Tp - 1) exceed the kernel's int arithmetic (<= 2^31 - 1)");
+        return -1;
+    }
+    return launch_keymask(feats, B, T, F, Tp, stride, padding, keymask, (hipStream_t)stream);
+}
+
+extern "C" int cn_op_expand_meta(const int32_t* rows_host, const int32_t* frames_host, int32_t n, int32_t* utt_meta_dev, int32_t B,
+                                 void* stream) {
+    static_assert(sizeof(UttMeta) == 4 * sizeof(int32_t), "cn_op_expand_meta: utt_meta is [B][4] int32");
+    if (!rows_host || !frames_host || !utt_meta_dev) {
+        cn_set_error("cn_op_expand_meta: null pointer (rows, frames, utt_meta)");
+        return -1;
+    }
+    if (n < 1 || n > CN_MAX_SUB) {
+        cn_set_error("cn_op_expand_meta: a rows list holds 1 .. " + std::to_string(CN_MAX_SUB) + " batches");
+        return -1;
+    }
+    if (B < 1) {
+        cn_set_error("cn_op_expand_meta: B must be >= 1");
+        return -1;
+    }
+    SubList subs;
+    std::memset(&subs, 0, sizeof(subs));
+    subs.n = n;
+    for (int k = 0; k < n; ++k) {
+        if (rows_host[k] < 1 || frames_host[k] < 1) {
+            cn_set_error("cn_op_expand_meta: a batch needs rows >= 1 and frames >= 1");
+            return -1;
+        }
+        subs.rows[k] = rows_host[k];
+        subs.frames[k] = frames_host[k];
+    }
+    return launch_expand_meta(subs, reinterpret_cast<UttMeta*>(utt_meta_dev), B, (hipStream_t)stream);
 }
 
 extern "C" int cn_op_topk(const float* logp, int32_t M, int32_t V, int32_t k, int32_t* idx, float* val, void* stream) {

@@ -54,6 +54,8 @@ CnConfig, CnDecodeOpts, CnAstOpts, CnFbankOpts, CnAttnDesc, CnNgramDesc, CnChain
     "cn_proj_x3_desc"))
 # the descriptor of the phrase-biasing automaton (include/cassnat_hip_ctc_bias.h declares it beside its entry points)
 CnBiasDesc = abi.CTC_BIAS_STRUCTS["cn_bias_desc"]
+# the descriptor of the alignment kernel's forms (include/cassnat_hip_align.h declares it beside the entry points of its family)
+CnAlignDesc = abi.ALIGN_STRUCTS["cn_align_desc"]
 
 
 class HipError(RuntimeError):

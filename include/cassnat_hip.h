@@ -719,6 +719,8 @@ int cn_op_row_plan(const int32_t* ylen_dev, int32_t B, int32_t U, int32_t hyp_st
                    const int32_t* ymax_dev, int32_t* row_off_dev, void* stream);
 int cn_op_logsoftmax_argmax(float* logits, int32_t M, int32_t V, int32_t* arg, float* maxlp, int32_t write_logp,
                             void* stream);
+/* The plain form of cn_op_ctc_align_desc (include/cassnat_hip_align.h: every form, and the layouts).  Like it, this entry refuses
+ * (-1, message set, nothing written) a null pointer, B < 1 or Tp < 1 - the launcher behind it returns 0 for an empty call. */
 int cn_op_ctc_align(const int32_t* best, const uint8_t* keymask, const float* size_ratio, int32_t B, int32_t Tp,
                     int32_t blank, int32_t left, int32_t right, int32_t* shift, int32_t* src_size, int32_t* ylen,
                     int32_t* ymax, int32_t* intervals, void* stream);
@@ -731,6 +733,8 @@ int cn_op_ctc_prefix_beam(const float* logp, const float* size_ratio, int32_t B,
 int cn_op_ctc_viterbi(const float* logp, const uint8_t* keymask, const float* size_ratio, const int32_t* labels,
                       const int32_t* label_len, int32_t B, int32_t Tp, int32_t V, int32_t ld, int32_t ymax, int32_t blank,
                       int32_t* out_path, void* stream);
+/* cn_op_greedy_pack_rows (include/cassnat_hip_align.h) without row limits.  Refuses (-1, message set) a null pointer, B < 1, U < 1
+ * or hyp_stride < 1 - the launcher behind it returns 0 for an empty call. */
 int cn_op_greedy_pack(const int32_t* tok, const float* val, const int32_t* ylen, int32_t B, int32_t U, int32_t sos,
                       int32_t hyp_stride, int32_t* hyp, int32_t* hyp_len, double* score, void* stream);
 /* fused LN -> W1 -> ReLU -> W2 -> residual (-> next LN) sublayer, bf16 / d_model 256.  x_dev fp32 [M][256] is updated
