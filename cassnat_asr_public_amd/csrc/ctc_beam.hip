@@ -3,8 +3,9 @@
 //
 // The search is ctc_search.h's (ctc_beam_decode, src/utils/beam_decode.py:8-93, called from src/tasks/cassnat_task.py:335-341): one
 // workgroup of 256 per utterance, the frame loop inside the kernel, one candidate per thread (in rounds when there are more than
-// 256), the stable top-W by counting rank, (parent, label) back-pointers per processed frame, unrolled at the end.  One kernel
-// body, one instantiation per fusion policy:
+// 256), the stable top-W by counting rank, (parent, label) back-pointers per processed frame, unrolled at the end.  What to run is
+// one CtcSearchArgs (ctc_search.h) behind one check (ctc_search_host.h) and one launcher, launch_ctc_beam; the serial twin of every
+// search is ctc_search_host (cn_ctc_{ngram,bias,merged}_beam_host).  One kernel body, one instantiation per fusion policy:
 //   ctc_beam_kernel<CS_FUSE_NONE>   score_lm = 0: `ctc_lm_weight: 0`.
 //   ctc_beam_kernel<CS_FUSE_NGRAM>  score_lm = lm_scale * (the word scores of the words a hypothesis has closed): `rank_model: n-gram` with an
 //                           ARPA model and ctc_lm_weight > 0 (ctc_ngram_search.h; the reference has no such search).  On top of the
@@ -37,9 +38,7 @@
 // predecessors (torch.max).
 #include <type_traits>
 
-#include "ctc_bias_search.h"
-#include "ctc_merge_search.h"
-#include "ctc_ngram_search.h"
+#include "ctc_search_host.h"
 #include "kernels.h"
 
 enum { CS_FUSE_NONE = 0, CS_FUSE_NGRAM = 1, CS_FUSE_BIAS = 2 };  // how score_lm is formed
@@ -82,17 +81,26 @@ struct CmLds<true> {
     uint32_t hash[2][CS_MAX_BEAM];
 };
 
+// what an instantiation takes by value: without fusion the shared arguments alone, else its descriptor behind them (out.score_lm is
+// written)
+struct CsNgramArgs : CtcBeamArgs {
+    cn_ngram_desc d;
+    double lm_scale = 0.0;  // ctc_lm_weight * ln(10)
+};
+struct CsBiasArgs : CtcBeamArgs {
+    cn_bias_desc d;
+};
 template <int FUSE>
 struct CsFuseArgs {
     using type = CtcBeamArgs;
 };
 template <>
 struct CsFuseArgs<CS_FUSE_NGRAM> {
-    using type = CtcNgramArgs;
+    using type = CsNgramArgs;
 };
 template <>
 struct CsFuseArgs<CS_FUSE_BIAS> {
-    using type = CtcBiasArgs;
+    using type = CsBiasArgs;
 };
 
 template <int FUSE, bool MERGE>
@@ -300,7 +308,7 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(typename CsFuseArgs<FUSE>
     }
 }
 
-template <int FUSE, bool MERGE = false, class Args>
+template <int FUSE, bool MERGE, class Args>
 static int launch_beam(const Args& a, hipStream_t s) {
     constexpr bool BIAS = FUSE == CS_FUSE_BIAS;
     static CnAttrOnce attr_once;  // (one per instantiation)
@@ -315,102 +323,71 @@ static int launch_beam(const Args& a, hipStream_t s) {
     return 0;
 }
 
-int launch_ctc_prefix_beam(const CtcBeamArgs& a, hipStream_t s) {
-    if (a.B <= 0) return 0;
-    const char* bad = cs_check_limits(a.W, a.P, 0, 0);
-    if (bad || a.out.Lmax < 1) {
-        cn_set_error(std::string("ctc_beam: ") + (bad ? bad : "hyp_cap must be at least 1"));
-        return -1;
-    }
-    return launch_beam<CS_FUSE_NONE>(a, s);
-}
-
-int launch_ctc_ngram_beam(const CtcNgramArgs& a, hipStream_t s) {
-    const std::string bad = cg_check(a, true);
+// every search of this file: the one check, then the instantiation of the descriptor's policy, merging or not
+int launch_ctc_beam(const CtcSearchArgs& a, hipStream_t s) {
+    if (!a.ng && !a.bias && !a.merge && a.B <= 0) return 0;
+    const std::string bad = ctc_search_check(a, true);
     if (!bad.empty()) {
-        cn_set_error("ctc_ngram_beam: " + bad);
+        cn_set_error("ctc_beam: " + bad);
         return -1;
     }
-    return launch_beam<CS_FUSE_NGRAM>(a, s);
+    if (a.ng) {
+        CsNgramArgs k;
+        static_cast<CtcBeamArgs&>(k) = a;
+        k.d = *a.ng, k.lm_scale = a.lm_scale;
+        return a.merge ? launch_beam<CS_FUSE_NGRAM, true>(k, s) : launch_beam<CS_FUSE_NGRAM, false>(k, s);
+    }
+    if (a.bias) {
+        CsBiasArgs k;
+        static_cast<CtcBeamArgs&>(k) = a;
+        k.d = *a.bias;
+        return a.merge ? launch_beam<CS_FUSE_BIAS, true>(k, s) : launch_beam<CS_FUSE_BIAS, false>(k, s);
+    }
+    const CtcBeamArgs& k = a;
+    return a.merge ? launch_beam<CS_FUSE_NONE, true>(k, s) : launch_beam<CS_FUSE_NONE, false>(k, s);
 }
 
-// the n-gram search on the host: every pointer a host pointer, no GPU call
+// The serial search on the host (ctc_search_host.h): every pointer a host pointer, no GPU call.  `who` refuses with "null argument"
+// where its own descriptor is mandatory and missing.
+static int ctc_beam_host(const char* who, bool desc_missing, const CtcSearchArgs& a) {
+    const std::string bad = desc_missing ? "null argument" : ctc_search_check(a, false);
+    if (!bad.empty()) {
+        cn_set_error(std::string(who) + ": " + bad);
+        return -1;
+    }
+    for (int b = 0; b < a.B; ++b) ctc_search_host(a, b);
+    return 0;
+}
+
 extern "C" int cn_ctc_ngram_beam_host(const cn_ngram_desc* desc, const float* logp, const int32_t* top_idx, const float* size_ratio, int32_t B,
                                       int32_t Tp, int32_t V, int32_t beam, int32_t pruning, double length_penalty, double lm_scale,
                                       int32_t blank, int32_t* hyp, int32_t hyp_cap, int32_t* hyp_len, double* score, double* score_lm,
                                       double* p_blk, double* p_nblk, int32_t* nbeam) {
-    if (!desc) {
-        cn_set_error("cn_ctc_ngram_beam_host: null argument");
-        return -1;
-    }
-    const CtcNgramArgs a = ctc_ngram_args(*desc, lm_scale,
-                                          ctc_beam_args(logp, top_idx, size_ratio, B, Tp, V, beam, pruning, blank, length_penalty,
-                                                        ctc_beam_out(hyp, hyp_cap, hyp_len, score, score_lm, p_blk, p_nblk, nbeam)));
-    const std::string bad = cg_check(a, false);
-    if (!bad.empty()) {
-        cn_set_error("cn_ctc_ngram_beam_host: " + bad);
-        return -1;
-    }
-    for (int32_t b = 0; b < B; ++b) cg_search_host(a, b);
-    return 0;
+    return ctc_beam_host("cn_ctc_ngram_beam_host", !desc,
+                         ctc_search_args(ctc_beam_args(logp, top_idx, size_ratio, B, Tp, V, beam, pruning, blank, length_penalty,
+                                                       ctc_beam_out(hyp, hyp_cap, hyp_len, score, score_lm, p_blk, p_nblk, nbeam)),
+                                         desc, lm_scale));
 }
 
-int launch_ctc_bias_beam(const CtcBiasArgs& a, hipStream_t s) {
-    const std::string bad = cb_check(a, true);
-    if (!bad.empty()) {
-        cn_set_error("ctc_bias_beam: " + bad);
-        return -1;
-    }
-    return launch_beam<CS_FUSE_BIAS>(a, s);
-}
-
-// the bias search on the host: every pointer a host pointer, no GPU call
 extern "C" int cn_ctc_bias_beam_host(const cn_bias_desc* desc, const float* logp, const int32_t* top_idx, const float* size_ratio, int32_t B,
                                      int32_t Tp, int32_t V, int32_t beam, int32_t pruning, double length_penalty, int32_t blank,
                                      int32_t* hyp, int32_t hyp_cap, int32_t* hyp_len, double* score, double* score_lm, double* p_blk,
                                      double* p_nblk, int32_t* nbeam) {
-    if (!desc) {
-        cn_set_error("cn_ctc_bias_beam_host: null argument");
-        return -1;
-    }
-    const CtcBiasArgs a = ctc_bias_args(*desc, ctc_beam_args(logp, top_idx, size_ratio, B, Tp, V, beam, pruning, blank, length_penalty,
-                                                             ctc_beam_out(hyp, hyp_cap, hyp_len, score, score_lm, p_blk, p_nblk, nbeam)));
-    const std::string bad = cb_check(a, false);
-    if (!bad.empty()) {
-        cn_set_error("cn_ctc_bias_beam_host: " + bad);
-        return -1;
-    }
-    for (int32_t b = 0; b < B; ++b) cb_search_host(a, b);
-    return 0;
+    return ctc_beam_host("cn_ctc_bias_beam_host", !desc,
+                         ctc_search_args(ctc_beam_args(logp, top_idx, size_ratio, B, Tp, V, beam, pruning, blank, length_penalty,
+                                                       ctc_beam_out(hyp, hyp_cap, hyp_len, score, score_lm, p_blk, p_nblk, nbeam)),
+                                         nullptr, 0.0, desc));
 }
 
-// the search that merges candidates by prefix (include/cassnat_hip_ctc_merge.h): the MERGE instantiation of the descriptor's policy
-int launch_ctc_merged_beam(const CtcMergeArgs& a, hipStream_t s) {
-    const std::string bad = cm_check(a, true);
-    if (!bad.empty()) {
-        cn_set_error("ctc_merged_beam: " + bad);
-        return -1;
-    }
-    if (a.ng) return launch_beam<CS_FUSE_NGRAM, true>(ctc_ngram_args(*a.ng, a.lm_scale, a), s);
-    if (a.bias) return launch_beam<CS_FUSE_BIAS, true>(ctc_bias_args(*a.bias, a), s);
-    return launch_beam<CS_FUSE_NONE, true>(static_cast<const CtcBeamArgs&>(a), s);
-}
-
-// the merging search on the host: every pointer a host pointer, no GPU call
+// (merging by prefix, include/cassnat_hip_ctc_merge.h: both descriptors may be null)
 extern "C" int cn_ctc_merged_beam_host(const cn_ngram_desc* ngram_desc, double lm_scale, const cn_bias_desc* bias_desc, const float* logp,
                                        const int32_t* top_idx, const float* size_ratio, int32_t B, int32_t Tp, int32_t V, int32_t beam,
                                        int32_t pruning, double length_penalty, int32_t blank, int32_t* hyp, int32_t hyp_cap,
                                        int32_t* hyp_len, double* score, double* score_lm, double* p_blk, double* p_nblk, int32_t* nbeam) {
-    const CtcMergeArgs a = ctc_merge_args(ngram_desc, lm_scale, bias_desc,
-                                          ctc_beam_args(logp, top_idx, size_ratio, B, Tp, V, beam, pruning, blank, length_penalty,
-                                                        ctc_beam_out(hyp, hyp_cap, hyp_len, score, score_lm, p_blk, p_nblk, nbeam)));
-    const std::string bad = cm_check(a, false);
-    if (!bad.empty()) {
-        cn_set_error("cn_ctc_merged_beam_host: " + bad);
-        return -1;
-    }
-    for (int32_t b = 0; b < B; ++b) cm_search_host(a, b);
-    return 0;
+    return ctc_beam_host("cn_ctc_merged_beam_host", false,
+                         ctc_search_args(ctc_beam_args(logp, top_idx, size_ratio, B, Tp, V, beam, pruning, blank, length_penalty,
+                                                       ctc_beam_out(hyp, hyp_cap, hyp_len, score, score_lm, p_blk, p_nblk, nbeam)),
+                                         ngram_desc, lm_scale, bias_desc, true));
 }
 
 // ---- forced alignment ---------------------------------------------------------------------------------------------------

@@ -7,17 +7,19 @@
 // probability exceeds 0.95 are skipped.  All scores are Python floats (float64) made of float32 log-posteriors.
 //
 // The variants differ in how score_lm is formed and in where they keep their state, and in nothing else:
-//   ctc_beam.hip    no LM (score_lm = 0), the word n-gram model and the phrase-biasing automaton (ctc_bias_search.h): one launch, the
-//                   frame loop inside, state in LDS
-//   ctc_lm.hip      the TransformerLM in the loop: one launch per processed frame, state in global memory
-//   cg_search_host  the n-gram search once more, serial, with std::stable_sort (ctc_ngram_search.h)
+//   ctc_beam.hip     no LM (score_lm = 0), the word n-gram model (ctc_ngram_search.h) and the phrase-biasing automaton
+//                    (ctc_bias_search.h), each with or without merging by prefix (ctc_merge_search.h): one launch, the frame loop
+//                    inside, state in LDS; what to run is one CtcSearchArgs, below
+//   ctc_lm.hip       the TransformerLM in the loop: one launch per processed frame, state in global memory
+//   ctc_search_host  every policy of ctc_beam.hip once more, serial, with std::stable_sort (ctc_search_host.h)
 // Each forms score_lm itself and takes from here: the frame predicate, the CTC half of a candidate, the sort key, the stable top-W as
 // a counting rank, and the unrolling of the (parent, label) back-pointers into the output rows.  Integer / ordering work: the
 // hypotheses are those of the reference wherever two keys are not within an ulp of each other.
 #pragma once
 #include <cmath>
 
-#include "ngram_core.h"  // NG_HD
+#include "../../include/cassnat_hip_ctc_bias.h"
+#include "ngram_core.h"  // NG_HD, cn_ngram_desc
 
 #define CS_LOGZERO (-1e10)
 constexpr int CS_MAX_BEAM = 32, CS_MAX_PRUNE = 32;
@@ -49,6 +51,22 @@ inline CtcBeamArgs ctc_beam_args(const float* logp, const int* top_idx, const fl
     a.logp = logp, a.top_idx = top_idx, a.size_ratio = size_ratio;
     a.B = B, a.Tp = Tp, a.V = V, a.P = pruning, a.W = beam, a.blank = blank, a.lp = lp;
     a.out = out;
+    return a;
+}
+
+// One search of ctc_beam.hip or of its serial twin: the shared arguments, how score_lm is formed (neither descriptor: it is 0) and
+// whether candidates that spell the same labels are merged.  out.score_lm may be null only without fusion and without merging.
+struct CtcSearchArgs : CtcBeamArgs {
+    const cn_ngram_desc* ng = nullptr;  // at most one of ng / bias
+    double lm_scale = 0.0;              // (n-gram) ctc_lm_weight * ln(10)
+    const cn_bias_desc* bias = nullptr;
+    bool merge = false;
+};
+inline CtcSearchArgs ctc_search_args(const CtcBeamArgs& search, const cn_ngram_desc* ng = nullptr, double lm_scale = 0.0,
+                                     const cn_bias_desc* bias = nullptr, bool merge = false) {
+    CtcSearchArgs a;
+    static_cast<CtcBeamArgs&>(a) = search;
+    a.ng = ng, a.lm_scale = lm_scale, a.bias = bias, a.merge = merge;
     return a;
 }
 

@@ -231,8 +231,9 @@ int launch_ctc_collapse(const int* best, const unsigned char* km, int B, int Tp,
                         int* maxlen, hipStream_t s);
 
 // ---- CTC prefix beam search + forced alignment (decode_type ctc_only / ctc_att)              (ctc_beam.hip)
-// (CtcBeamArgs / CtcBeamOut: ctc_search.h, the search every CTC beam variant shares)
-int launch_ctc_prefix_beam(const CtcBeamArgs& a, hipStream_t s);
+// (CtcSearchArgs over CtcBeamArgs / CtcBeamOut: ctc_search.h, the search every CTC beam variant shares; a.B <= 0 without fusion
+// and without merging: nothing is launched)
+int launch_ctc_beam(const CtcSearchArgs& a, hipStream_t s);
 struct ViterbiArgs {
     const float* logp = nullptr;             // [B][Tp][V]
     const unsigned char* keymask = nullptr;  // [B][Tp]

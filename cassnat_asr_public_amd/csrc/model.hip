@@ -5,9 +5,7 @@
 #include <algorithm>
 #include <cmath>
 
-#include "ctc_bias_search.h"
-#include "ctc_merge_search.h"
-#include "ctc_ngram_search.h"
+#include "ctc_bias_search.h"  // cb_check_desc
 #include "model.h"
 
 using namespace cn_host;
@@ -703,6 +701,39 @@ int ctc_search_open(cn_model* m, const std::string& who, const float* feats_dev,
     a->hist_tok = (int*)htok;
     return 0;
 }
+// The body of cn_ctc_beam and of its n-gram, bias and merging forms (`who`; `scope`: the name in profiles): one launch of the search
+// kernel (ctc_beam.hip) behind encoder, CTC head and top-k.  `a` comes with the policy (ng / lm_scale / bias / merge), size ratios,
+// beam, pruning, length penalty and outputs; ctc_search_open fills the rest.  desc_missing: `who`'s own descriptor is mandatory and
+// null.  What a fusing or merging search refuses is looked at before anything is launched.
+int ctc_beam_call(cn_model* m, const char* who, const char* scope, bool desc_missing, CtcSearchArgs a, const float* feats_dev, int B, int T,
+                  int F, const cn_decode_opts* opts, void* stream) {
+    CN_TRY(check_call(m, B, T, F));
+    if (a.ng && a.bias) {
+        cn_set_error(std::string(who) + ": at most one of the n-gram and the bias descriptor may be set");
+        return -1;
+    }
+    if (a.ng || a.bias || a.merge || desc_missing) {
+        if (desc_missing || !a.size_ratio || !a.out.score_lm || !(a.lp == a.lp) || (a.ng && !(a.lm_scale == a.lm_scale))) {
+            cn_set_error(std::string(who) + ": needs its descriptor, size ratios, length_penalty and lm_scale numbers and all output buffers");
+            return -1;
+        }
+        const std::string bad = a.ng ? ng_check_desc(*a.ng) : a.bias ? cb_check_desc(*a.bias) : std::string();
+        if (!bad.empty()) {
+            cn_set_error(std::string(who) + ": " + bad);
+            return -1;
+        }
+    }
+    hipStream_t s = (hipStream_t)stream;
+    CN_TRY(ctc_search_open(m, who, feats_dev, a.size_ratio, B, T, F, opts, a.W, a.P, a.lp, a.out, true, true, &a, s));
+    ProfScope ps(m, scope, 0, (double)B * a.Tp * (a.P + 1) * 4, s);
+    return launch_ctc_beam(a, s);
+}
+// what the entries below know before the encoder has run
+CtcSearchArgs ctc_call_args(const float* size_ratio_dev, int beam, int pruning, double length_penalty, const CtcBeamOut& out,
+                            const cn_ngram_desc* ng = nullptr, double lm_scale = 0.0, const cn_bias_desc* bias = nullptr, bool merge = false) {
+    return ctc_search_args(ctc_beam_args(nullptr, nullptr, size_ratio_dev, 0, 0, 0, beam, pruning, 0, length_penalty, out), ng, lm_scale, bias,
+                           merge);
+}
 }  // namespace
 
 // ctc_beam_decode (src/utils/beam_decode.py:8-93) without a language model: hyp_out_dev [B][beam][hyp_cap] labels (no sos),
@@ -711,14 +742,9 @@ extern "C" int cn_ctc_beam(cn_model* m, const float* feats_dev, const float* siz
                            const cn_decode_opts* opts, int32_t beam, int32_t pruning, double length_penalty, int32_t* hyp_out_dev,
                            int32_t hyp_cap, int32_t* hyp_len_dev, double* score_dev, double* p_blk_dev, double* p_nblk_dev,
                            int32_t* nbeam_dev, void* stream) {
-    CN_TRY(check_call(m, B, T, F));
-    hipStream_t s = (hipStream_t)stream;
-    CtcBeamArgs a;
-    CN_TRY(ctc_search_open(m, "cn_ctc_beam", feats_dev, size_ratio_dev, B, T, F, opts, beam, pruning, length_penalty,
-                           ctc_beam_out(hyp_out_dev, hyp_cap, hyp_len_dev, score_dev, nullptr, p_blk_dev, p_nblk_dev, nbeam_dev), true, true,
-                           &a, s));
-    ProfScope ps(m, "ctc_prefix_beam", 0, (double)B * a.Tp * (pruning + 1) * 4, s);
-    return launch_ctc_prefix_beam(a, s);
+    const CtcBeamOut out = ctc_beam_out(hyp_out_dev, hyp_cap, hyp_len_dev, score_dev, nullptr, p_blk_dev, p_nblk_dev, nbeam_dev);
+    return ctc_beam_call(m, "cn_ctc_beam", "ctc_prefix_beam", false, ctc_call_args(size_ratio_dev, beam, pruning, length_penalty, out),
+                         feats_dev, B, T, F, opts, stream);
 }
 
 // The same search with a word n-gram model fused (ctc_ngram_search.h; not in the reference): one launch of the n-gram instantiation
@@ -727,24 +753,9 @@ extern "C" int cn_ctc_beam_ngram(cn_model* m, const cn_ngram_desc* desc, const f
                                  int32_t T, int32_t F, const cn_decode_opts* opts, int32_t beam, int32_t pruning, double length_penalty,
                                  double lm_scale, int32_t* hyp_out_dev, int32_t hyp_cap, int32_t* hyp_len_dev, double* score_dev,
                                  double* score_lm_dev, double* p_blk_dev, double* p_nblk_dev, int32_t* nbeam_dev, void* stream) {
-    CN_TRY(check_call(m, B, T, F));
-    // (looked at before anything is launched)
-    if (!desc || !size_ratio_dev || !score_lm_dev || !(lm_scale == lm_scale)) {
-        cn_set_error("cn_ctc_beam_ngram: needs a cn_ngram_desc, size ratios, lm_scale a number and all output buffers");
-        return -1;
-    }
-    const std::string bad = ng_check_desc(*desc);
-    if (!bad.empty()) {
-        cn_set_error("cn_ctc_beam_ngram: " + bad);
-        return -1;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    CtcBeamArgs search;
-    CN_TRY(ctc_search_open(m, "cn_ctc_beam_ngram", feats_dev, size_ratio_dev, B, T, F, opts, beam, pruning, length_penalty,
-                           ctc_beam_out(hyp_out_dev, hyp_cap, hyp_len_dev, score_dev, score_lm_dev, p_blk_dev, p_nblk_dev, nbeam_dev), true,
-                           true, &search, s));
-    ProfScope ps(m, "ctc_ngram_beam", 0, (double)B * search.Tp * (pruning + 1) * 4, s);
-    return launch_ctc_ngram_beam(ctc_ngram_args(*desc, lm_scale, search), s);
+    const CtcBeamOut out = ctc_beam_out(hyp_out_dev, hyp_cap, hyp_len_dev, score_dev, score_lm_dev, p_blk_dev, p_nblk_dev, nbeam_dev);
+    return ctc_beam_call(m, "cn_ctc_beam_ngram", "ctc_ngram_beam", !desc,
+                         ctc_call_args(size_ratio_dev, beam, pruning, length_penalty, out, desc, lm_scale), feats_dev, B, T, F, opts, stream);
 }
 
 // The same search with contextual phrase biasing (ctc_bias_search.h, include/cassnat_hip_ctc_bias.h; not in the reference): one launch
@@ -753,24 +764,9 @@ extern "C" int cn_ctc_beam_bias(cn_model* m, const cn_bias_desc* desc, const flo
                                 int32_t T, int32_t F, const cn_decode_opts* opts, int32_t beam, int32_t pruning, double length_penalty,
                                 int32_t* hyp_out_dev, int32_t hyp_cap, int32_t* hyp_len_dev, double* score_dev, double* score_lm_dev,
                                 double* p_blk_dev, double* p_nblk_dev, int32_t* nbeam_dev, void* stream) {
-    CN_TRY(check_call(m, B, T, F));
-    // (looked at before anything is launched)
-    if (!desc || !size_ratio_dev || !score_lm_dev || !(length_penalty == length_penalty)) {
-        cn_set_error("cn_ctc_beam_bias: needs a cn_bias_desc, size ratios, length_penalty a number and all output buffers");
-        return -1;
-    }
-    const std::string bad = cb_check_desc(*desc);
-    if (!bad.empty()) {
-        cn_set_error("cn_ctc_beam_bias: " + bad);
-        return -1;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    CtcBeamArgs search;
-    CN_TRY(ctc_search_open(m, "cn_ctc_beam_bias", feats_dev, size_ratio_dev, B, T, F, opts, beam, pruning, length_penalty,
-                           ctc_beam_out(hyp_out_dev, hyp_cap, hyp_len_dev, score_dev, score_lm_dev, p_blk_dev, p_nblk_dev, nbeam_dev), true,
-                           true, &search, s));
-    ProfScope ps(m, "ctc_bias_beam", 0, (double)B * search.Tp * (pruning + 1) * 4, s);
-    return launch_ctc_bias_beam(ctc_bias_args(*desc, search), s);
+    const CtcBeamOut out = ctc_beam_out(hyp_out_dev, hyp_cap, hyp_len_dev, score_dev, score_lm_dev, p_blk_dev, p_nblk_dev, nbeam_dev);
+    return ctc_beam_call(m, "cn_ctc_beam_bias", "ctc_bias_beam", !desc,
+                         ctc_call_args(size_ratio_dev, beam, pruning, length_penalty, out, nullptr, 0.0, desc), feats_dev, B, T, F, opts, stream);
 }
 
 // The same search merging candidates by prefix (ctc_merge_search.h, include/cassnat_hip_ctc_merge.h; not in the reference), without
@@ -781,28 +777,10 @@ extern "C" int cn_ctc_beam_merged(cn_model* m, const cn_ngram_desc* ngram_desc, 
                                   const cn_decode_opts* opts, int32_t beam, int32_t pruning, double length_penalty, int32_t* hyp_out_dev,
                                   int32_t hyp_cap, int32_t* hyp_len_dev, double* score_dev, double* score_lm_dev, double* p_blk_dev,
                                   double* p_nblk_dev, int32_t* nbeam_dev, void* stream) {
-    CN_TRY(check_call(m, B, T, F));
-    // (looked at before anything is launched)
-    if (ngram_desc && bias_desc) {
-        cn_set_error("cn_ctc_beam_merged: at most one of the n-gram and the bias descriptor may be set");
-        return -1;
-    }
-    if (!size_ratio_dev || !score_lm_dev || !(length_penalty == length_penalty) || (ngram_desc && !(lm_scale == lm_scale))) {
-        cn_set_error("cn_ctc_beam_merged: needs size ratios, length_penalty and lm_scale numbers and all output buffers");
-        return -1;
-    }
-    const std::string bad = ngram_desc ? ng_check_desc(*ngram_desc) : bias_desc ? cb_check_desc(*bias_desc) : std::string();
-    if (!bad.empty()) {
-        cn_set_error("cn_ctc_beam_merged: " + bad);
-        return -1;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    CtcBeamArgs search;
-    CN_TRY(ctc_search_open(m, "cn_ctc_beam_merged", feats_dev, size_ratio_dev, B, T, F, opts, beam, pruning, length_penalty,
-                           ctc_beam_out(hyp_out_dev, hyp_cap, hyp_len_dev, score_dev, score_lm_dev, p_blk_dev, p_nblk_dev, nbeam_dev), true,
-                           true, &search, s));
-    ProfScope ps(m, "ctc_merged_beam", 0, (double)B * search.Tp * (pruning + 1) * 4, s);
-    return launch_ctc_merged_beam(ctc_merge_args(ngram_desc, lm_scale, bias_desc, search), s);
+    const CtcBeamOut out = ctc_beam_out(hyp_out_dev, hyp_cap, hyp_len_dev, score_dev, score_lm_dev, p_blk_dev, p_nblk_dev, nbeam_dev);
+    return ctc_beam_call(m, "cn_ctc_beam_merged", "ctc_merged_beam", false,
+                         ctc_call_args(size_ratio_dev, beam, pruning, length_penalty, out, ngram_desc, lm_scale, bias_desc, true), feats_dev, B,
+                         T, F, opts, stream);
 }
 
 // CassNAT.beam_decode with decode_type 'ctc_att' and sample_num 1 (src/models/cassnat.py:446-448, 391-414): the trigger mask

@@ -12,9 +12,7 @@
 #include "../../include/cassnat_hip.h"
 #include "../../include/cassnat_hip_align.h"
 #include "../../include/cassnat_hip_attention_proj.h"
-#include "ctc_bias_search.h"
-#include "ctc_merge_search.h"
-#include "ctc_ngram_search.h"
+#include "ctc_search_host.h"
 #include "ctc_times_search.h"
 #include "edit_align_search.h"
 #include "flac_decode.h"
@@ -984,6 +982,23 @@ extern "C" int cn_op_ctc_align(const int32_t* best, const uint8_t* keymask, cons
     return op_ctc_align_desc("cn_op_ctc_align", &d, stream);
 }
 
+// The search kernel (ctc_beam.hip) alone on given log-posteriors and given pruned labels: the check (`who` in its message; a's own
+// mandatory descriptor null: desc_missing), which refuses before the GPU is touched, the back-pointers' scratch, the launch.
+static int op_ctc_beam(const char* who, bool desc_missing, CtcSearchArgs a, void* stream) {
+    if (!a.ng && !a.bias && !a.merge && a.B <= 0) return 0;
+    const std::string bad = desc_missing ? "null argument" : ctc_search_check(a, false);
+    if (!bad.empty()) {
+        cn_set_error(std::string(who) + ": " + bad);
+        return -1;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    Scratch sc(who, s);
+    a.hist_parent = (unsigned char*)sc.alloc((size_t)a.B * a.Tp * a.W);
+    a.hist_tok = (int*)sc.alloc((size_t)a.B * a.Tp * a.W * 4);
+    if (!sc.ok()) return -2;
+    return sc.finish(launch_ctc_beam(a, s));
+}
+
 // the two kernels of decode_type ctc_only / ctc_att on given log-posteriors (test entries; all pointers device)
 extern "C" int cn_op_ctc_prefix_beam(const float* logp, const float* size_ratio, int32_t B, int32_t Tp, int32_t V, int32_t beam,
                                      int32_t pruning, double length_penalty, int32_t blank, int32_t* hyp, int32_t hyp_cap,
@@ -994,18 +1009,13 @@ extern "C" int cn_op_ctc_prefix_beam(const float* logp, const float* size_ratio,
     Scratch sc("cn_op_ctc_prefix_beam", s);
     int* top_idx = (int*)sc.alloc(M * P * 4);
     float* top_val = (float*)sc.alloc(M * P * 4);
-    unsigned char* hpar = (unsigned char*)sc.alloc(M * (size_t)std::max(beam, 1));
-    int* htok = (int*)sc.alloc(M * (size_t)std::max(beam, 1) * 4);
     if (!sc.ok()) return -2;
-    int rc = pruning > 0 ? launch_topk(logp, (int)M, V, V, pruning, top_idx, top_val, s) : 0;
-    if (rc == 0) {
-        CtcBeamArgs a = ctc_beam_args(logp, top_idx, size_ratio, B, Tp, V, beam, pruning, blank, length_penalty,
-                                      ctc_beam_out(hyp, hyp_cap, hyp_len, score, nullptr, p_blk, p_nblk, nbeam));
-        a.hist_parent = hpar;
-        a.hist_tok = htok;
-        rc = launch_ctc_prefix_beam(a, s);
-    }
-    return sc.finish(rc);
+    const int rc = pruning > 0 ? launch_topk(logp, (int)M, V, V, pruning, top_idx, top_val, s) : 0;
+    if (rc != 0) return sc.finish(rc);
+    return op_ctc_beam("cn_op_ctc_prefix_beam", false,
+                       ctc_search_args(ctc_beam_args(logp, top_idx, size_ratio, B, Tp, V, beam, pruning, blank, length_penalty,
+                                                     ctc_beam_out(hyp, hyp_cap, hyp_len, score, nullptr, p_blk, p_nblk, nbeam))),
+                       stream);
 }
 
 extern "C" int cn_op_ctc_viterbi(const float* logp, const uint8_t* keymask, const float* size_ratio, const int32_t* labels,
@@ -1726,75 +1736,39 @@ extern "C" int cn_op_ctc_lm_rows(const float* fresh, const float* prv, float* nx
     return launch_ctc_lm_rows(fresh, prv, nxt, parent, stay, count, iter, slots, W, V, (hipStream_t)stream);
 }
 
-// the n-gram search kernel (ctc_beam.hip) alone on given log-posteriors and given pruned labels (cn_ctc_beam_ngram runs it behind the encoder)
+// op_ctc_beam with a policy, on the caller's pruned labels (cn_ctc_beam_ngram / _bias / _merged run the same kernels behind the encoder)
 extern "C" int cn_op_ctc_ngram_beam(const cn_ngram_desc* desc, const float* logp, const int32_t* top_idx, const float* size_ratio, int32_t B,
                                     int32_t Tp, int32_t V, int32_t beam, int32_t pruning, double length_penalty, double lm_scale,
                                     int32_t blank, int32_t* hyp, int32_t hyp_cap, int32_t* hyp_len, double* score, double* score_lm,
                                     double* p_blk, double* p_nblk, int32_t* nbeam, void* stream) {
-    if (!desc) {
-        cn_set_error("cn_op_ctc_ngram_beam: null argument");
-        return -1;
-    }
-    CtcNgramArgs a = ctc_ngram_args(*desc, lm_scale,
-                                    ctc_beam_args(logp, top_idx, size_ratio, B, Tp, V, beam, pruning, blank, length_penalty,
-                                                  ctc_beam_out(hyp, hyp_cap, hyp_len, score, score_lm, p_blk, p_nblk, nbeam)));
-    const std::string bad = cg_check(a, false);
-    if (!bad.empty()) {
-        cn_set_error("cn_op_ctc_ngram_beam: " + bad);
-        return -1;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    Scratch sc("cn_op_ctc_ngram_beam", s);
-    a.hist_parent = (unsigned char*)sc.alloc((size_t)B * Tp * beam);
-    a.hist_tok = (int*)sc.alloc((size_t)B * Tp * beam * 4);
-    if (!sc.ok()) return -2;
-    return sc.finish(launch_ctc_ngram_beam(a, s));
+    return op_ctc_beam("cn_op_ctc_ngram_beam", !desc,
+                       ctc_search_args(ctc_beam_args(logp, top_idx, size_ratio, B, Tp, V, beam, pruning, blank, length_penalty,
+                                                     ctc_beam_out(hyp, hyp_cap, hyp_len, score, score_lm, p_blk, p_nblk, nbeam)),
+                                       desc, lm_scale),
+                       stream);
 }
 
-// the bias search kernel (ctc_beam.hip) alone on given log-posteriors and given pruned labels (cn_ctc_beam_bias runs it behind the encoder)
 extern "C" int cn_op_ctc_bias_beam(const cn_bias_desc* desc, const float* logp, const int32_t* top_idx, const float* size_ratio, int32_t B,
                                    int32_t Tp, int32_t V, int32_t beam, int32_t pruning, double length_penalty, int32_t blank, int32_t* hyp,
                                    int32_t hyp_cap, int32_t* hyp_len, double* score, double* score_lm, double* p_blk, double* p_nblk,
                                    int32_t* nbeam, void* stream) {
-    if (!desc) {
-        cn_set_error("cn_op_ctc_bias_beam: null argument");
-        return -1;
-    }
-    CtcBiasArgs a = ctc_bias_args(*desc, ctc_beam_args(logp, top_idx, size_ratio, B, Tp, V, beam, pruning, blank, length_penalty,
-                                                       ctc_beam_out(hyp, hyp_cap, hyp_len, score, score_lm, p_blk, p_nblk, nbeam)));
-    const std::string bad = cb_check(a, false);
-    if (!bad.empty()) {
-        cn_set_error("cn_op_ctc_bias_beam: " + bad);
-        return -1;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    Scratch sc("cn_op_ctc_bias_beam", s);
-    a.hist_parent = (unsigned char*)sc.alloc((size_t)B * Tp * beam);
-    a.hist_tok = (int*)sc.alloc((size_t)B * Tp * beam * 4);
-    if (!sc.ok()) return -2;
-    return sc.finish(launch_ctc_bias_beam(a, s));
+    return op_ctc_beam("cn_op_ctc_bias_beam", !desc,
+                       ctc_search_args(ctc_beam_args(logp, top_idx, size_ratio, B, Tp, V, beam, pruning, blank, length_penalty,
+                                                     ctc_beam_out(hyp, hyp_cap, hyp_len, score, score_lm, p_blk, p_nblk, nbeam)),
+                                       nullptr, 0.0, desc),
+                       stream);
 }
 
-// the merging search kernel (ctc_beam.hip, MERGE) alone on given log-posteriors and given pruned labels (cn_ctc_beam_merged runs it
-// behind the encoder)
+// (merging by prefix, include/cassnat_hip_ctc_merge.h: both descriptors may be null)
 extern "C" int cn_op_ctc_merged_beam(const cn_ngram_desc* ngram_desc, double lm_scale, const cn_bias_desc* bias_desc, const float* logp,
                                      const int32_t* top_idx, const float* size_ratio, int32_t B, int32_t Tp, int32_t V, int32_t beam,
                                      int32_t pruning, double length_penalty, int32_t blank, int32_t* hyp, int32_t hyp_cap, int32_t* hyp_len,
                                      double* score, double* score_lm, double* p_blk, double* p_nblk, int32_t* nbeam, void* stream) {
-    CtcMergeArgs a = ctc_merge_args(ngram_desc, lm_scale, bias_desc,
-                                    ctc_beam_args(logp, top_idx, size_ratio, B, Tp, V, beam, pruning, blank, length_penalty,
-                                                  ctc_beam_out(hyp, hyp_cap, hyp_len, score, score_lm, p_blk, p_nblk, nbeam)));
-    const std::string bad = cm_check(a, false);
-    if (!bad.empty()) {
-        cn_set_error("cn_op_ctc_merged_beam: " + bad);
-        return -1;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    Scratch sc("cn_op_ctc_merged_beam", s);
-    a.hist_parent = (unsigned char*)sc.alloc((size_t)B * Tp * beam);
-    a.hist_tok = (int*)sc.alloc((size_t)B * Tp * beam * 4);
-    if (!sc.ok()) return -2;
-    return sc.finish(launch_ctc_merged_beam(a, s));
+    return op_ctc_beam("cn_op_ctc_merged_beam", false,
+                       ctc_search_args(ctc_beam_args(logp, top_idx, size_ratio, B, Tp, V, beam, pruning, blank, length_penalty,
+                                                     ctc_beam_out(hyp, hyp_cap, hyp_len, score, score_lm, p_blk, p_nblk, nbeam)),
+                                       ngram_desc, lm_scale, bias_desc, true),
+                       stream);
 }
 
 extern "C" int cn_op_ffn_fused(float* x_dev, const float* ln_a_dev, const float* ln_b_dev, const float* w1_host,

@@ -805,9 +805,9 @@ class Engine:
                                    hyp.shape[2], _ptr(hyp_len), _ptr(score), current_stream()), "cn_decode_ast")
 
     # ---- decode_type ctc_only / ctc_att, rank_model at_baseline
-    def ctc_beam(self, feats, size_ratio, opts, beam, pruning, length_penalty):
-        """CTC prefix beam search on the device -> (hyp (B, beam, T'+1) int32, hyp_len (B, beam) int32, score_ctc / p_blk /
-        p_nblk (B, beam) float64, nbeam (B,) int32) as cuda tensors; hypotheses carry no sos, best first."""
+    def _ctc_search(self, name, head, feats, size_ratio, opts, beam, pruning, length_penalty, mid=(), with_lm=True, tail=()):
+        """The call of a CTC prefix beam search entry ``name`` with freshly allocated outputs: ``head`` goes behind the handle, ``mid``
+        behind the length penalty, ``tail`` behind nbeam -> (hyp, hyp_len, score_ctc, [score_lm,] p_blk, p_nblk, nbeam)."""
         import torch
 
         B, T, F = feats.shape
@@ -815,86 +815,45 @@ class Engine:
         dev = feats.device
         hyp = torch.empty(B, beam, cap, dtype=torch.int32, device=dev)
         hlen = torch.empty(B, beam, dtype=torch.int32, device=dev)
-        sc, pb, pnb = (torch.empty(B, beam, dtype=torch.float64, device=dev) for _ in range(3))
+        scores = [torch.empty(B, beam, dtype=torch.float64, device=dev) for _ in range(4 if with_lm else 3)]  # score_ctc, [score_lm,] p_blk, p_nblk
         nb = torch.empty(B, dtype=torch.int32, device=dev)
-        self._chk(self.L.cn_ctc_beam(self.handle, _ptr(feats), _ptr(size_ratio), B, T, F, C.byref(opts), int(beam), int(pruning),
-                                 float(length_penalty), _ptr(hyp), cap, _ptr(hlen), _ptr(sc), _ptr(pb), _ptr(pnb), _ptr(nb),
-                                 current_stream()), "cn_ctc_beam")
-        return hyp, hlen, sc, pb, pnb, nb
+        self._chk(getattr(self.L, name)(self.handle, *head, _ptr(feats), _ptr(size_ratio), B, T, F, C.byref(opts), int(beam), int(pruning),
+                                        float(length_penalty), *mid, _ptr(hyp), cap, _ptr(hlen), *(_ptr(t) for t in scores), _ptr(nb), *tail,
+                                        current_stream()), name)
+        return (hyp, hlen, *scores, nb)
+
+    def ctc_beam(self, feats, size_ratio, opts, beam, pruning, length_penalty):
+        """CTC prefix beam search on the device -> (hyp (B, beam, T'+1) int32, hyp_len (B, beam) int32, score_ctc / p_blk /
+        p_nblk (B, beam) float64, nbeam (B,) int32) as cuda tensors; hypotheses carry no sos, best first."""
+        return self._ctc_search("cn_ctc_beam", (), feats, size_ratio, opts, beam, pruning, length_penalty, with_lm=False)
 
     def ctc_beam_lm(self, lm, feats, size_ratio, opts, beam, pruning, length_penalty, lm_weight):
         """CTC prefix beam search with the TransformerLM engine ``lm`` (same library) in the frame loop (``cn_ctc_beam_lm``) ->
         ``ctc_beam``'s tuple with score_lm (B, beam) float64 behind score_ctc, and the loop's iteration count last."""
-        import torch
-
         if lm is None or lm.L is not self.L:
             raise HipError("cn_ctc_beam_lm: the LM engine comes from the other library")
-        B, T, F = feats.shape
-        cap = subsampled(T) + 1
-        dev = feats.device
-        hyp = torch.empty(B, beam, cap, dtype=torch.int32, device=dev)
-        hlen = torch.empty(B, beam, dtype=torch.int32, device=dev)
-        sc, slm, pb, pnb = (torch.empty(B, beam, dtype=torch.float64, device=dev) for _ in range(4))
-        nb = torch.empty(B, dtype=torch.int32, device=dev)
         iters = C.c_int32()
-        self._chk(self.L.cn_ctc_beam_lm(self.handle, lm.handle, _ptr(feats), _ptr(size_ratio), B, T, F, C.byref(opts), int(beam),
-                                        int(pruning), float(length_penalty), float(lm_weight), _ptr(hyp), cap, _ptr(hlen), _ptr(sc),
-                                        _ptr(slm), _ptr(pb), _ptr(pnb), _ptr(nb), C.byref(iters), current_stream()), "cn_ctc_beam_lm")
-        return hyp, hlen, sc, slm, pb, pnb, nb, iters.value
+        out = self._ctc_search("cn_ctc_beam_lm", (lm.handle,), feats, size_ratio, opts, beam, pruning, length_penalty, mid=(float(lm_weight),),
+                               tail=(C.byref(iters),))
+        return (*out, iters.value)
 
     def ctc_beam_ngram(self, desc, feats, size_ratio, opts, beam, pruning, length_penalty, lm_scale):
         """CTC prefix beam search with a word n-gram model in the frame loop (``cn_ctc_beam_ngram``): ``desc`` a ``CnNgramDesc`` over
         tables on the feats' device, ``lm_scale`` = ctc_lm_weight * ln(10) -> ``ctc_beam``'s tuple with score_lm (B, beam) float64
         behind score_ctc."""
-        import torch
-
-        B, T, F = feats.shape
-        cap = subsampled(T) + 1
-        dev = feats.device
-        hyp = torch.empty(B, beam, cap, dtype=torch.int32, device=dev)
-        hlen = torch.empty(B, beam, dtype=torch.int32, device=dev)
-        sc, slm, pb, pnb = (torch.empty(B, beam, dtype=torch.float64, device=dev) for _ in range(4))
-        nb = torch.empty(B, dtype=torch.int32, device=dev)
-        self._chk(self.L.cn_ctc_beam_ngram(self.handle, C.byref(desc), _ptr(feats), _ptr(size_ratio), B, T, F, C.byref(opts), int(beam),
-                                           int(pruning), float(length_penalty), float(lm_scale), _ptr(hyp), cap, _ptr(hlen), _ptr(sc),
-                                           _ptr(slm), _ptr(pb), _ptr(pnb), _ptr(nb), current_stream()), "cn_ctc_beam_ngram")
-        return hyp, hlen, sc, slm, pb, pnb, nb
+        return self._ctc_search("cn_ctc_beam_ngram", (C.byref(desc),), feats, size_ratio, opts, beam, pruning, length_penalty, mid=(float(lm_scale),))
 
     def ctc_beam_bias(self, desc, feats, size_ratio, opts, beam, pruning, length_penalty):
         """CTC prefix beam search with contextual phrase biasing in the frame loop (``cn_ctc_beam_bias``): ``desc`` a ``CnBiasDesc``
         over tables on the feats' device (``models.bias.BiasList.desc``) -> ``ctc_beam_ngram``'s tuple, score_lm the banked bonus."""
-        import torch
-
-        B, T, F = feats.shape
-        cap = subsampled(T) + 1
-        dev = feats.device
-        hyp = torch.empty(B, beam, cap, dtype=torch.int32, device=dev)
-        hlen = torch.empty(B, beam, dtype=torch.int32, device=dev)
-        sc, slm, pb, pnb = (torch.empty(B, beam, dtype=torch.float64, device=dev) for _ in range(4))
-        nb = torch.empty(B, dtype=torch.int32, device=dev)
-        self._chk(self.L.cn_ctc_beam_bias(self.handle, C.byref(desc), _ptr(feats), _ptr(size_ratio), B, T, F, C.byref(opts), int(beam),
-                                          int(pruning), float(length_penalty), _ptr(hyp), cap, _ptr(hlen), _ptr(sc), _ptr(slm), _ptr(pb),
-                                          _ptr(pnb), _ptr(nb), current_stream()), "cn_ctc_beam_bias")
-        return hyp, hlen, sc, slm, pb, pnb, nb
+        return self._ctc_search("cn_ctc_beam_bias", (C.byref(desc),), feats, size_ratio, opts, beam, pruning, length_penalty)
 
     def ctc_beam_merged(self, feats, size_ratio, opts, beam, pruning, length_penalty, ngram_desc=None, lm_scale=0.0, bias_desc=None):
         """CTC prefix beam search that merges candidates spelling the same prefix (``cn_ctc_beam_merged``;
         include/cassnat_hip_ctc_merge.h): without fusion, with ``ngram_desc`` (a ``CnNgramDesc``; ``lm_scale`` = ctc_lm_weight * ln(10))
         or with ``bias_desc`` (a ``CnBiasDesc``), at most one of the two -> ``ctc_beam_ngram``'s tuple (score_lm zeros without fusion)."""
-        import torch
-
-        B, T, F = feats.shape
-        cap = subsampled(T) + 1
-        dev = feats.device
-        hyp = torch.empty(B, beam, cap, dtype=torch.int32, device=dev)
-        hlen = torch.empty(B, beam, dtype=torch.int32, device=dev)
-        sc, slm, pb, pnb = (torch.empty(B, beam, dtype=torch.float64, device=dev) for _ in range(4))
-        nb = torch.empty(B, dtype=torch.int32, device=dev)
-        self._chk(self.L.cn_ctc_beam_merged(self.handle, C.byref(ngram_desc) if ngram_desc is not None else None, float(lm_scale),
-                                            C.byref(bias_desc) if bias_desc is not None else None, _ptr(feats), _ptr(size_ratio), B, T, F,
-                                            C.byref(opts), int(beam), int(pruning), float(length_penalty), _ptr(hyp), cap, _ptr(hlen),
-                                            _ptr(sc), _ptr(slm), _ptr(pb), _ptr(pnb), _ptr(nb), current_stream()), "cn_ctc_beam_merged")
-        return hyp, hlen, sc, slm, pb, pnb, nb
+        head = (C.byref(ngram_desc) if ngram_desc is not None else None, float(lm_scale), C.byref(bias_desc) if bias_desc is not None else None)
+        return self._ctc_search("cn_ctc_beam_merged", head, feats, size_ratio, opts, beam, pruning, length_penalty)
 
     # ---- word / token time stamps: forced CTC alignment with spans and confidences (include/cassnat_hip_ctc_times.h)
     def ctc_token_times(self, feats, size_ratio, opts, labels, label_len):

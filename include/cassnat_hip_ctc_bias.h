@@ -37,7 +37,8 @@
  * cn_op_ctc_bias_beam: the kernel alone on given log-posteriors logp [B][Tp][V] and given pruned labels top_idx [B][Tp][pruning]
  * (list order is the caller's; blank and ids outside [0, V) make no candidate; may be NULL when pruning = 0); all pointers device.
  * cn_ctc_bias_beam_host: the same arguments as host pointers, no GPU call: a serial loop over the same candidate and step functions,
- * ordered by std::stable_sort.  It agrees with the device on hypotheses and order, on score_lm bit for bit when the sums of the
+ * ordered by std::stable_sort (ctc_search_host of csrc/ctc_search_host.h).  It agrees with the device on hypotheses and order, on
+ * score_lm bit for bit when the sums of the
  * values are exact in float64, and on the other scores up to the last bits of log1p / exp.
  * Refused without a launch (-1): a null pointer, beam outside 1 .. 32, pruning outside 0 .. 32, a slot count that is no power of
  * two, a negative node count, a null table when the node count exceeds 1, hash_bits outside 0 .. 32, B, Tp or V < 1, blank outside

@@ -51,7 +51,8 @@
  * cn_op_ctc_merged_beam: the kernel alone on given log-posteriors logp [B][Tp][V] and given pruned labels top_idx [B][Tp][pruning]
  * (list order is the caller's; may be NULL when pruning = 0); all pointers device.  cn_op_ctc_prefix_beam's outputs plus score_lm.
  * cn_ctc_merged_beam_host: the same arguments as host pointers, no GPU call: a serial loop over the same candidate and step functions,
- * ordered by std::stable_sort, identity by comparing label vectors.  It agrees with the device on hypotheses and order, on score_lm
+ * ordered by std::stable_sort, identity by comparing label vectors (ctc_search_host of csrc/ctc_search_host.h with `merge` set).  It
+ * agrees with the device on hypotheses and order, on score_lm
  * bit for bit when the sums are exact in float64, and on the other scores up to the last bits of log1p / exp.
  * Refused without a launch (-1): both descriptors set; and what cn_op_ctc_ngram_beam / cn_op_ctc_bias_beam refuse: a null pointer,
  * beam outside 1 .. 32, pruning outside 0 .. 32, a bad descriptor, B, Tp or V < 1, blank outside [0, V), hyp_cap < Tp + 1, a

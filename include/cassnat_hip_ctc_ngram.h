@@ -25,8 +25,9 @@ extern "C" {
  * cn_op_ctc_ngram_beam: the kernel alone on given log-posteriors logp [B][Tp][V] and given pruned labels top_idx [B][Tp][pruning]
  * (list order is the caller's; blank and ids outside [0, V) make no candidate; may be NULL when pruning = 0); all pointers device.
  * cn_ctc_ngram_beam_host: the same arguments as host pointers, no GPU call: a serial loop over the same candidate, state-update and
- * word-score functions.  It agrees with the device on hypotheses and order, on score_lm bit for bit when the word scores are exact
- * in float32, and on the other scores up to the last bits of log1p / exp.
+ * word-score functions (ctc_search_host of csrc/ctc_search_host.h, the one loop behind every host entry).  It agrees with the
+ * device on hypotheses and order, on score_lm bit for bit when the word scores are exact in float32, and on the other scores up to
+ * the last bits of log1p / exp.
  * Refused without a launch (-1): a null pointer, beam outside 1 .. 32, pruning outside 0 .. 32, an order outside 1 .. 8, a slot
  * count that is no power of two, B, Tp or V < 1, blank outside [0, V), hyp_cap < Tp + 1, a length_penalty or lm_scale that is NaN. */
 int cn_ctc_beam_ngram(cn_model* m, const cn_ngram_desc* desc, const float* feats_dev, const float* size_ratio_dev, int32_t B, int32_t T,

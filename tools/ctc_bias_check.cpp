@@ -1,8 +1,8 @@
 // Stand-alone host check of the CTC prefix beam search with phrase biasing: the step functions and the serial search the library and
-// its kernel are built from (csrc/ctc_search.h, csrc/ctc_bias_search.h) run on the CPU, on automata and random log-posteriors made in
+// its kernel are built from (csrc/ctc_search_host.h over csrc/ctc_search.h and csrc/ctc_bias_search.h) run on the CPU, on automata and random log-posteriors made in
 // memory, every array a heap block of exactly the size the search was told.  The automaton's tables are built here (trie, failure
 // links, hits, hashed edges - a small hash_bits among them, so that probe runs wrap).  Checked:
-//   * cb_search_host gives the bytes of a naive search that keeps every hypothesis' labels and rescans ALL of them against the phrase
+//   * ctc_search_host with a bias descriptor gives the bytes of a naive search that keeps every hypothesis' labels and rescans ALL of them against the phrase
 //     list for every candidate (no automaton, no state): hypotheses, order, lengths and all four scores;
 //   * the beam comes back sorted by its key, lengths and labels are in range;
 //   * with the root alone (with and without tables) score_lm is 0 and every other output is the same bytes whatever the descriptor;
@@ -17,7 +17,7 @@
 #include <memory>
 #include <random>
 
-#include "ctc_bias_search.h"
+#include "ctc_search_host.h"
 
 static int failures = 0;
 #define CHECK(cond, ...)                                  \
@@ -192,13 +192,14 @@ Outputs outputs(int B, int W, int cap) {
 
 Outputs search(const cn_bias_desc& d, const Inputs& in, int W, double lp) {
     Outputs o = outputs(in.B, W, in.Tp + 1);
-    const CtcBiasArgs a = ctc_bias_args(
-        d, ctc_beam_args(in.logp.get(), in.P > 0 ? in.top.get() : nullptr, in.ratio.get(), in.B, in.Tp, in.V, W, in.P, 0, lp,
-                         ctc_beam_out(o.hyp.get(), o.cap, o.hlen.get(), o.sc.get(), o.slm.get(), o.pb.get(), o.pnb.get(), o.nb.get())));
-    const std::string bad = cb_check(a, false);
+    const CtcSearchArgs a = ctc_search_args(
+        ctc_beam_args(in.logp.get(), in.P > 0 ? in.top.get() : nullptr, in.ratio.get(), in.B, in.Tp, in.V, W, in.P, 0, lp,
+                      ctc_beam_out(o.hyp.get(), o.cap, o.hlen.get(), o.sc.get(), o.slm.get(), o.pb.get(), o.pnb.get(), o.nb.get())),
+        nullptr, 0.0, &d);
+    const std::string bad = ctc_search_check(a, false);
     CHECK(bad.empty(), "%s", bad.c_str());
     if (bad.empty())
-        for (int b = 0; b < in.B; ++b) cb_search_host(a, b);
+        for (int b = 0; b < in.B; ++b) ctc_search_host(a, b);
     else
         memset(o.nb.get(), 0, (size_t)in.B * 4);
     return o;
@@ -317,7 +318,7 @@ int main() {
     }
     {  // refusals
         const auto a = build(sets[2], 32);
-        CHECK(!cb_check(ctc_bias_args(a->d, CtcBeamArgs()), false).empty(), "null arguments accepted");
+        CHECK(!ctc_search_check(ctc_search_args(CtcBeamArgs(), nullptr, 0.0, &a->d), false).empty(), "null arguments accepted");
         cn_bias_desc d = a->d;
         d.slots = 3;
         CHECK(!cb_check_desc(d).empty(), "a slot count that is no power of two accepted");

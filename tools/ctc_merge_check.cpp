@@ -1,7 +1,7 @@
 // Stand-alone host check of the CTC prefix beam search that merges candidates by prefix: the functions and the serial search the
-// library and its kernel are built from (csrc/ctc_search.h, csrc/ctc_merge_search.h) run on the CPU on random log-posteriors made in
-// memory, every array a heap block of exactly the size the search was told.  Checked:
-//   * cm_search_host gives the bytes of a naive search that keeps every hypothesis' labels in a map from label sequence to
+// library and its kernel are built from (csrc/ctc_search_host.h over csrc/ctc_search.h and csrc/ctc_merge_search.h) run on the CPU on
+// random log-posteriors made in memory, every array a heap block of exactly the size the search was told.  Checked:
+//   * ctc_search_host with `merge` set gives the bytes of a naive search that keeps every hypothesis' labels in a map from label sequence to
 //     (p_blk, p_nblk): hypotheses, order, lengths and all scores; pruned lists with duplicate labels, blanks and ids outside [0, V),
 //     size ratios that cut frames, frames that are skipped, beams up to 32 x 32;
 //   * the kept hypotheses spell pairwise different sequences, lengths and labels are in range;
@@ -9,7 +9,8 @@
 //     hypothesis) pair of every frame as the comparison of the label vectors does, and so does cm_same_sequence alone; the runs
 //     contain folds into hypotheses whose prefix was dropped and made again (counted);
 //   * the empty bias descriptor (with the root alone) gives the LM-free bytes;
-//   * with beam 1 or pruning 0 the bytes are the unmerged search's (cb_search_host with the root alone);
+//   * with beam 1 or pruning 0 the fold has nothing to do: the bytes are those of the same function with `merge` off (and the root
+//     alone as its bias descriptor);
 //   * the refusals refuse.
 // Meant to be built with sanitizers:
 //   c++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -I cassnat_asr_public_amd/csrc tools/ctc_merge_check.cpp -o ctc_merge_check
@@ -20,7 +21,7 @@
 #include <memory>
 #include <random>
 
-#include "ctc_merge_search.h"
+#include "ctc_search_host.h"
 
 static int failures = 0;
 #define CHECK(cond, ...)                                  \
@@ -102,9 +103,15 @@ Case make_case(std::mt19937& rng, int B, int Tp, int V, int W, int P, int labels
     return c;
 }
 
-CtcMergeArgs args_of(const Case& c, Out& o, const cn_bias_desc* bias) {
-    return ctc_merge_args(nullptr, 0.0, bias,
-                          ctc_beam_args(c.logp.get(), c.P ? c.top.get() : nullptr, c.ratio.get(), c.B, c.Tp, c.V, c.W, c.P, c.blank, c.lp, o.view()));
+cn_bias_desc no_bias() {  // the root alone: a valid descriptor whose tables are not read
+    cn_bias_desc d = {};
+    d.slots = 1, d.nodes = 0, d.hash_bits = 32;
+    return d;
+}
+
+CtcSearchArgs args_of(const Case& c, Out& o, const cn_bias_desc* bias, bool merge = true) {
+    return ctc_search_args(ctc_beam_args(c.logp.get(), c.P ? c.top.get() : nullptr, c.ratio.get(), c.B, c.Tp, c.V, c.W, c.P, c.blank, c.lp, o.view()),
+                           nullptr, 0.0, bias, merge);
 }
 
 struct Stats {
@@ -236,13 +243,13 @@ void naive(const Case& c, int b, Out& o, Stats* st) {
 void check_case(const Case& c, Stats* st) {
     const int cap = c.Tp + 1;
     Out got(c.B, c.W, cap), want(c.B, c.W, cap), empty(c.B, c.W, cap);
-    const CtcMergeArgs a = args_of(c, got, nullptr);
-    CHECK(cm_check(a, false).empty(), "cm_check: %s", cm_check(a, false).c_str());
-    const cn_bias_desc root = cm_no_bias();
-    const CtcMergeArgs ae = args_of(c, empty, &root);
+    const CtcSearchArgs a = args_of(c, got, nullptr);
+    CHECK(ctc_search_check(a, false).empty(), "ctc_search_check: %s", ctc_search_check(a, false).c_str());
+    const cn_bias_desc root = no_bias();
+    const CtcSearchArgs ae = args_of(c, empty, &root);
     for (int b = 0; b < c.B; ++b) {
-        cm_search_host(a, b);
-        cm_search_host(ae, b);
+        ctc_search_host(a, b);
+        ctc_search_host(ae, b);
         naive(c, b, want, st);
     }
     CHECK(got.same(want), "host search and naive search differ (T' %d, %d / %d)", c.Tp, c.W, c.P);
@@ -262,9 +269,8 @@ void check_case(const Case& c, Stats* st) {
     }
     if (c.W == 1 || c.P == 0) {  // nothing can fold: the unmerged search (the odd lists apart, whose duplicates it would take twice)
         Out plain(c.B, c.W, cap);
-        const CtcBiasArgs ab = ctc_bias_args(root, ctc_beam_args(c.logp.get(), c.P ? c.top.get() : nullptr, c.ratio.get(), c.B, c.Tp, c.V, c.W, c.P,
-                                                                 c.blank, c.lp, plain.view()));
-        for (int b = 0; b < c.B; ++b) cb_search_host(ab, b);
+        const CtcSearchArgs ab = args_of(c, plain, &root, false);
+        for (int b = 0; b < c.B; ++b) ctc_search_host(ab, b);
         CHECK(got.same(plain), "beam %d pruning %d: not the unmerged search", c.W, c.P);
     }
 }
@@ -273,31 +279,31 @@ void check_refusals() {
     std::mt19937 rng(5);
     Case c = make_case(rng, 2, 6, 5, 3, 2, 0, false, 0.0);
     Out o(c.B, c.W, c.Tp + 1);
-    CtcMergeArgs a = args_of(c, o, nullptr);
+    CtcSearchArgs a = args_of(c, o, nullptr);
     cn_ngram_desc ng = {};
-    cn_bias_desc root = cm_no_bias();
-    CtcMergeArgs x = a;
+    cn_bias_desc root = no_bias();
+    CtcSearchArgs x = a;
     x.ng = &ng, x.bias = &root;
-    CHECK(cm_check(x, false).find("at most one") != std::string::npos, "both descriptors must be refused");
+    CHECK(ctc_search_check(x, false).find("at most one") != std::string::npos, "both descriptors must be refused");
     x = a, x.W = 33;
-    CHECK(!cm_check(x, false).empty(), "beam 33");
+    CHECK(!ctc_search_check(x, false).empty(), "beam 33");
     x = a, x.P = -1;
-    CHECK(!cm_check(x, false).empty(), "pruning -1");
+    CHECK(!ctc_search_check(x, false).empty(), "pruning -1");
     x = a, x.logp = nullptr;
-    CHECK(!cm_check(x, false).empty(), "null logp");
+    CHECK(!ctc_search_check(x, false).empty(), "null logp");
     x = a, x.out.score_lm = nullptr;
-    CHECK(!cm_check(x, false).empty(), "null score_lm");
+    CHECK(!ctc_search_check(x, false).empty(), "null score_lm");
     x = a, x.out.Lmax = c.Tp;
-    CHECK(!cm_check(x, false).empty(), "hyp_cap");
+    CHECK(!ctc_search_check(x, false).empty(), "hyp_cap");
     x = a, x.blank = c.V;
-    CHECK(!cm_check(x, false).empty(), "blank");
+    CHECK(!ctc_search_check(x, false).empty(), "blank");
     x = a, x.lp = std::nan("");
-    CHECK(!cm_check(x, false).empty(), "length_penalty");
-    CHECK(!cm_check(a, true).empty(), "missing scratch must be refused where it is needed");
+    CHECK(!ctc_search_check(x, false).empty(), "length_penalty");
+    CHECK(!ctc_search_check(a, true).empty(), "missing scratch must be refused where it is needed");
     cn_bias_desc odd = root;
     odd.slots = 3;
     x = a, x.bias = &odd;
-    CHECK(!cm_check(x, false).empty(), "slot count");
+    CHECK(!ctc_search_check(x, false).empty(), "slot count");
 }
 
 }  // namespace

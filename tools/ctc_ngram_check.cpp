@@ -1,5 +1,6 @@
 // Stand-alone host check of the CTC prefix beam search with word n-gram fusion: the scoring core (csrc/ngram_core.h) and the step
-// functions and serial search the library and its kernels are built from (csrc/ctc_search.h, csrc/ctc_ngram_search.h) run on the CPU, on a small n-gram
+// functions and serial search the library and its kernels are built from (csrc/ctc_search.h, csrc/ctc_ngram_search.h, csrc/ctc_search_host.h)
+// run on the CPU, on a small n-gram
 // model and random log-posteriors made in memory, every array a heap block of exactly the size the search was told.  Checked:
 //   * the word score put together from independent probes (ng_probe / ng_probe_score) has ng_word_score's bits;
 //   * every returned score_lm is lm_scale times the word scores of the hypothesis' words, glued and summed as the ranker does
@@ -12,6 +13,8 @@
 //   c++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -I cassnat_asr_public_amd/csrc -I tools tools/ctc_ngram_check.cpp -o ctc_ngram_check
 // Exit status 0 when every check held.
 #include "ngram_check_model.h"
+
+#include "ctc_search_host.h"
 
 namespace {
 
@@ -92,14 +95,14 @@ Outputs search(const Model& m, const Inputs& in, int W, double lp, double lm_sca
     Outputs o{W, cap, std::unique_ptr<int[]>(new int[(size_t)n * cap]), std::unique_ptr<int[]>(new int[n]), std::unique_ptr<int[]>(new int[B]),
               std::unique_ptr<double[]>(new double[n]), std::unique_ptr<double[]>(new double[n]), std::unique_ptr<double[]>(new double[n]),
               std::unique_ptr<double[]>(new double[n])};
-    const CtcNgramArgs a = ctc_ngram_args(
-        m.d, lm_scale,
+    const CtcSearchArgs a = ctc_search_args(
         ctc_beam_args(in.logp.get(), in.P > 0 ? in.top.get() : nullptr, in.ratio.get(), B, in.Tp, in.V, W, in.P, 0, lp,
-                      ctc_beam_out(o.hyp.get(), cap, o.hlen.get(), o.sc.get(), o.slm.get(), o.pb.get(), o.pnb.get(), o.nb.get())));
-    const std::string bad = cg_check(a, false);
+                      ctc_beam_out(o.hyp.get(), cap, o.hlen.get(), o.sc.get(), o.slm.get(), o.pb.get(), o.pnb.get(), o.nb.get())),
+        &m.d, lm_scale);
+    const std::string bad = ctc_search_check(a, false);
     CHECK(bad.empty(), "%s", bad.c_str());
     if (bad.empty())
-        for (int b = 0; b < B; ++b) cg_search_host(a, b);
+        for (int b = 0; b < B; ++b) ctc_search_host(a, b);
     else
         memset(o.nb.get(), 0, (size_t)B * 4);
     return o;
@@ -174,7 +177,7 @@ int main() {
         check_foreign(*m, rng, 12, 5, 3, 0.25, 0.5);
         check_foreign(*m, rng, 40, 32, 8, 0.3, 0.0);
         // refusals
-        CHECK(!cg_check(ctc_ngram_args(m->d, 0.5, CtcBeamArgs()), false).empty(), "null arguments accepted");
+        CHECK(!ctc_search_check(ctc_search_args(CtcBeamArgs(), &m->d, 0.5), false).empty(), "null arguments accepted");
     }
     if (failures) {
         fprintf(stderr, "%d checks failed\n", failures);
