@@ -4,7 +4,7 @@ its companions include/cassnat_hip_ctc_ngram.h, include/cassnat_hip_attention_pr
 include/cassnat_hip_nat_ngram.h, include/cassnat_hip_ctc_times.h, include/cassnat_hip_score.h, include/cassnat_hip_ctc_bias.h,
 include/cassnat_hip_ast_bias.h and include/cassnat_hip_feats.h, read the same way; ``CTC_MERGE_FUNCTIONS``: those of
 include/cassnat_hip_ctc_merge.h; ``VAD_FUNCTIONS``: those of include/cassnat_hip_vad.h; ``ALIGN_FUNCTIONS`` / ``ALIGN_STRUCTS``: those of
-include/cassnat_hip_align.h): ``FUNCTIONS`` name -> (restype, argtypes),
+include/cassnat_hip_align.h; ``GENMAX_FUNCTIONS`` / ``GENMAX_STRUCTS`` / ``GENMAX_CONSTANTS``: those of include/cassnat_hip_genmax.h): ``FUNCTIONS`` name -> (restype, argtypes),
 ``STRUCTS`` C name -> ctypes.Structure, ``CONSTANTS`` enum / #define name -> int.  It reads this project's header, not C in general:
 what it does not recognise raises ``AbiError`` naming the declaration.  Standard library only (no torch, numpy, library or GPU)."""
 import ctypes as C
@@ -161,12 +161,18 @@ with open(ALIGN_HEADER_PATH) as _f:
     ALIGN_HEADER = parse(_f.read(), base=HEADER)
 ALIGN_FUNCTIONS = ALIGN_HEADER.functions
 ALIGN_STRUCTS = {"cn_align_desc": ALIGN_HEADER.structs["cn_align_desc"]}
+# the companion header of the fused generator tail: its descriptor (cn_genmax_desc), the form query, the pack query and their constants
+GENMAX_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "cassnat_hip_genmax.h")
+with open(GENMAX_HEADER_PATH) as _f:
+    GENMAX_HEADER = parse(_f.read(), base=HEADER)
+GENMAX_FUNCTIONS, GENMAX_CONSTANTS = GENMAX_HEADER.functions, GENMAX_HEADER.constants
+GENMAX_STRUCTS = {"cn_genmax_desc": GENMAX_HEADER.structs["cn_genmax_desc"]}
 
 
 def bind(L):
     """Set ``restype`` / ``argtypes`` of every declared function on the loaded library ``L``; a function a header declares and the
     library lacks raises AttributeError."""
-    for name, (restype, argtypes) in list(FUNCTIONS.items()) + list(EXTRA_FUNCTIONS.items()) + list(PROJ_FUNCTIONS.items()) + list(AST_NGRAM_FUNCTIONS.items()) + list(NAT_NGRAM_FUNCTIONS.items()) + list(CTC_TIMES_FUNCTIONS.items()) + list(SCORE_FUNCTIONS.items()) + list(CTC_BIAS_FUNCTIONS.items()) + list(AST_BIAS_FUNCTIONS.items()) + list(FEATS_FUNCTIONS.items()) + list(CTC_MERGE_FUNCTIONS.items()) + list(VAD_FUNCTIONS.items()) + list(ALIGN_FUNCTIONS.items()):
+    for name, (restype, argtypes) in list(FUNCTIONS.items()) + list(EXTRA_FUNCTIONS.items()) + list(PROJ_FUNCTIONS.items()) + list(AST_NGRAM_FUNCTIONS.items()) + list(NAT_NGRAM_FUNCTIONS.items()) + list(CTC_TIMES_FUNCTIONS.items()) + list(SCORE_FUNCTIONS.items()) + list(CTC_BIAS_FUNCTIONS.items()) + list(AST_BIAS_FUNCTIONS.items()) + list(FEATS_FUNCTIONS.items()) + list(CTC_MERGE_FUNCTIONS.items()) + list(VAD_FUNCTIONS.items()) + list(ALIGN_FUNCTIONS.items()) + list(GENMAX_FUNCTIONS.items()):
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     return L

@@ -30,7 +30,7 @@ def _stale(target, deps):
 def build(force=False, verbose=False, extra_flags=(), lib=LIB, objdir=None):
     """extra_flags / lib / objdir: measurement variants (e.g. -DFX_STAMPS into a library of their own); the product is the default."""
     headers = [os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".h")]
-    headers += [os.path.join(os.path.dirname(CSRC), "..", "include", h) for h in ("cassnat_hip.h", "cassnat_hip_ctc_ngram.h", "cassnat_hip_attention_proj.h", "cassnat_hip_ast_ngram.h", "cassnat_hip_nat_ngram.h", "cassnat_hip_ctc_times.h", "cassnat_hip_score.h", "cassnat_hip_ctc_bias.h", "cassnat_hip_ast_bias.h", "cassnat_hip_feats.h", "cassnat_hip_ctc_merge.h", "cassnat_hip_vad.h", "cassnat_hip_align.h")]
+    headers += [os.path.join(os.path.dirname(CSRC), "..", "include", h) for h in ("cassnat_hip.h", "cassnat_hip_ctc_ngram.h", "cassnat_hip_attention_proj.h", "cassnat_hip_ast_ngram.h", "cassnat_hip_nat_ngram.h", "cassnat_hip_ctc_times.h", "cassnat_hip_score.h", "cassnat_hip_ctc_bias.h", "cassnat_hip_ast_bias.h", "cassnat_hip_feats.h", "cassnat_hip_ctc_merge.h", "cassnat_hip_vad.h", "cassnat_hip_align.h", "cassnat_hip_genmax.h")]
     objdir = objdir or os.path.join(CSRC, "build")
     os.makedirs(objdir, exist_ok=True)
 

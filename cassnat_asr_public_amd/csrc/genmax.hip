@@ -15,6 +15,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <string>
 
 #include "kernels.h"
 
@@ -408,32 +409,26 @@ __global__ __launch_bounds__(512, 1) void genmax_x3_kernel(GenmaxParams p) {
 #undef GM_TT
 #undef GM_EPILOGUE
 
-template <int MT, bool GATHER, bool LSE> static int launch_genmax_x3_variant(const GenmaxParams& p, hipStream_t s) {
-    const int main_ = MT * 32768 + GM3_WAVES * p.vtw * 32 * 4, merge_ = GM3_WAVES * 32 * MT * 16;
-    const int lds = main_ > merge_ ? main_ : merge_;
+template <int MT, bool GATHER, bool LSE> static int launch_genmax_x3_variant(const GenmaxParams& p, const GenmaxForm& f, hipStream_t s) {
     static CnAttrOnce attr_once;
     int attr_dev;
     if (attr_once.need(&attr_dev)) {
         CN_HIP_CHECK(hipFuncSetAttribute((const void*)genmax_x3_kernel<MT, GATHER, LSE>, hipFuncAttributeMaxDynamicSharedMemorySize, gm3_lds_bytes<MT>()));
         attr_once.mark(attr_dev);
     }
-    hipLaunchKernelGGL((genmax_x3_kernel<MT, GATHER, LSE>), dim3(cn_ceil_div(p.M, 32 * MT)), dim3(512), lds, s, p);
+    hipLaunchKernelGGL((genmax_x3_kernel<MT, GATHER, LSE>), dim3(f.grid), dim3(f.block), f.lds, s, p);
     CN_HIP_CHECK(hipGetLastError());
     return 0;
 }
 
-
-template <int MT, bool GATHER, bool LSE> static int launch_genmax_variant(const GenmaxParams& p, hipStream_t s) {
-    // (sized for this vocabulary, not for the largest one: at V = 5000 three workgroups fit a CU's LDS)
-    const int main_ = MT * 16384 + 4 * p.vtw * 32 * 4, merge_ = 4 * 32 * MT * 16;
-    const int lds = main_ > merge_ ? main_ : merge_;
+template <int MT, bool GATHER, bool LSE> static int launch_genmax_variant(const GenmaxParams& p, const GenmaxForm& f, hipStream_t s) {
     static CnAttrOnce attr_once;
     int attr_dev;
     if (attr_once.need(&attr_dev)) {
         CN_HIP_CHECK(hipFuncSetAttribute((const void*)genmax_kernel<MT, GATHER, LSE>, hipFuncAttributeMaxDynamicSharedMemorySize, gm_lds_bytes<MT>()));
         attr_once.mark(attr_dev);
     }
-    hipLaunchKernelGGL((genmax_kernel<MT, GATHER, LSE>), dim3(cn_ceil_div(p.M, 32 * MT)), dim3(256), lds, s, p);
+    hipLaunchKernelGGL((genmax_kernel<MT, GATHER, LSE>), dim3(f.grid), dim3(f.block), f.lds, s, p);
     CN_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -450,13 +445,58 @@ bool genmax_applies(int prec, int d, int V) {
     return false;
 }
 
-int launch_genmax(const GenmaxArgs& a, hipStream_t s) {
-    const int vtw = a.x3 ? genmax_x3_vtw(a.V) : genmax_vtw(a.V);
-    if (!genmax_applies(a.x3 ? CN_PREC_X3 : CN_PREC_BF16, a.d, a.V)) {
-        cn_set_error("genmax: needs d_model == 256 and V <= 6144");
+// The host-only half of a launch: the checks and the choice of kernel.  Nothing here touches the device, and nothing is sized from
+// V before V is known to be in range.  0, or -1 with the error set to a message that starts with `who`.  packed == false: a.wp /
+// a.bp are not looked at (the entry that packs them asks before it packs).  launch_genmax launches what this decides;
+// cn_genmax_form reports it.
+int decide_genmax(const GenmaxArgs& a, GenmaxForm* f, const char* who, bool packed) {
+    auto refuse = [&](const std::string& what) {
+        cn_set_error(std::string(who) + ": " + what);
         return -1;
+    };
+    *f = GenmaxForm();
+    if (a.d != 256) return refuse("needs d_model == 256");
+    if (a.V < 1 || a.V > 32 * 4 * GM_MAX_VTW || !genmax_applies(a.x3 ? CN_PREC_X3 : CN_PREC_BF16, a.d, a.V))
+        return refuse("V=" + std::to_string(a.V) + ": the vocabulary must hold 1 .. 6144 entries");
+    if (a.M < 0) return refuse("M=" + std::to_string(a.M) + " must not be negative");
+    if (!a.h) return refuse("null activations");
+    if (packed && (!a.wp || !a.bp)) return refuse("null packed weights or biases");
+    if (a.maxlp && !a.arg && !a.tgt) return refuse("maxlp without arg: the maximum's log-probability comes with its index");
+    if (!a.arg && !a.tgt) return refuse("neither an arg-max output nor targets: nothing to compute");
+    if (a.tgt) {
+        if (a.arg || a.maxlp) return refuse("the target gather writes neither the arg-max nor its log-probability (arg and maxlp must be null)");
+        if (!a.tgt_lp) return refuse("the target gather needs an output buffer (tgt_lp)");
+        if (a.tgt_U < 1 || a.tgt_ld < a.tgt_U || a.M % a.tgt_U != 0)
+            return refuse("the target gather needs rows = B x U with U >= 1 and ld >= U (M=" + std::to_string(a.M) + ", U=" +
+                          std::to_string(a.tgt_U) + ", ld=" + std::to_string(a.tgt_ld) + ")");
     }
-    if (a.M <= 0) return 0;
+    f->x3 = a.x3;
+    f->kind = a.tgt ? GENMAX_GATHER : a.maxlp ? GENMAX_ARGMAX_LSE : GENMAX_ARGMAX;
+    f->vtw = a.x3 ? genmax_x3_vtw(a.V) : genmax_vtw(a.V);
+    if (a.M == 0) return 0;  // (mt == 0: nothing to launch)
+    if (a.x3) {
+        // split-bf16: one workgroup (8 waves) per CU; 32 rows each while that fills the chip in one round, 64 beyond (half the
+        // weight stream per row)
+        f->mt = a.M > 256 * 32 ? 2 : 1;
+        const int main_ = f->mt * 32768 + GM3_WAVES * f->vtw * 32 * 4, merge_ = GM3_WAVES * 32 * f->mt * 16;
+        f->lds = main_ > merge_ ? main_ : merge_;
+        f->block = 64 * GM3_WAVES;
+    } else {
+        f->mt = a.M > 32 ? 2 : 1;
+        // (sized for this vocabulary, not for the largest one: at V = 5000 three workgroups fit a CU's LDS)
+        const int main_ = f->mt * 16384 + 4 * f->vtw * 32 * 4, merge_ = 4 * 32 * f->mt * 16;
+        f->lds = main_ > merge_ ? main_ : merge_;
+        f->block = 256;
+    }
+    f->grid = (a.M - 1) / (32 * f->mt) + 1;  // (cn_ceil_div's a + b - 1 overflows for the last 63 values of M)
+    return 0;
+}
+
+// the launch of what decide_genmax decided
+int launch_genmax(const GenmaxArgs& a, hipStream_t s) {
+    GenmaxForm f;
+    if (decide_genmax(a, &f, "genmax") != 0) return -1;
+    if (f.mt == 0) return 0;
     GenmaxParams p;
     p.h = reinterpret_cast<const bf16*>(a.h);  // (split-bf16 rows when a.x3: 1024 bytes each)
     p.wp = reinterpret_cast<const uint4*>(a.wp);
@@ -466,29 +506,21 @@ int launch_genmax(const GenmaxArgs& a, hipStream_t s) {
     p.M = a.M;
     p.m_dev = a.m_dev;
     p.V = a.V;
-    p.vtw = vtw;
+    p.vtw = f.vtw;
     p.tgt = a.tgt;
     p.tgt_lp = a.tgt_lp;
     p.tgt_U = a.tgt_U;
     p.tgt_ld = a.tgt_ld;
-    // split-bf16: one workgroup (8 waves) per CU; 32 rows each while that fills the chip in one round, 64 beyond (half the
-    // weight stream per row)
-    const bool wide = cn_ceil_div(a.M, 32) > 256;
-    if (a.tgt) {
-        if (!a.tgt_lp || a.tgt_U < 1 || a.tgt_ld < a.tgt_U || a.M % a.tgt_U != 0) {
-            cn_set_error("genmax: the target gather needs rows = B x U, an output buffer and ld >= U");
-            return -1;
-        }
-        if (a.x3) return wide ? launch_genmax_x3_variant<2, true, true>(p, s) : launch_genmax_x3_variant<1, true, true>(p, s);
-        return a.M > 32 ? launch_genmax_variant<2, true, true>(p, s) : launch_genmax_variant<1, true, true>(p, s);
+    const bool wide = f.mt == 2;
+    if (f.x3) {
+        if (f.kind == GENMAX_GATHER) return wide ? launch_genmax_x3_variant<2, true, true>(p, f, s) : launch_genmax_x3_variant<1, true, true>(p, f, s);
+        if (f.kind == GENMAX_ARGMAX) return wide ? launch_genmax_x3_variant<2, false, false>(p, f, s) : launch_genmax_x3_variant<1, false, false>(p, f, s);
+        return wide ? launch_genmax_x3_variant<2, false, true>(p, f, s) : launch_genmax_x3_variant<1, false, true>(p, f, s);
     }
-    if (a.x3) {
-        if (!a.maxlp) return wide ? launch_genmax_x3_variant<2, false, false>(p, s) : launch_genmax_x3_variant<1, false, false>(p, s);
-        return wide ? launch_genmax_x3_variant<2, false, true>(p, s) : launch_genmax_x3_variant<1, false, true>(p, s);
-    }
-    if (!a.maxlp)  // arg-max only
-        return a.M > 32 ? launch_genmax_variant<2, false, false>(p, s) : launch_genmax_variant<1, false, false>(p, s);
-    return a.M > 32 ? launch_genmax_variant<2, false, true>(p, s) : launch_genmax_variant<1, false, true>(p, s);
+    if (f.kind == GENMAX_GATHER) return wide ? launch_genmax_variant<2, true, true>(p, f, s) : launch_genmax_variant<1, true, true>(p, f, s);
+    if (f.kind == GENMAX_ARGMAX)  // arg-max only
+        return wide ? launch_genmax_variant<2, false, false>(p, f, s) : launch_genmax_variant<1, false, false>(p, f, s);
+    return wide ? launch_genmax_variant<2, false, true>(p, f, s) : launch_genmax_variant<1, false, true>(p, f, s);
 }
 
 static inline uint16_t gm_bf16_bits(float f) { return cn_host_op16(f); }  // (the engine's 16-bit operand: common.h)

@@ -492,6 +492,15 @@ struct GenmaxArgs {
     float* tgt_lp = nullptr;
     int tgt_U = 0, tgt_ld = 0;
 };
+// what a launch computes per row, and the kernel decide_genmax chooses for it: genmax_x3_kernel (x3) or genmax_kernel<mt, kind ==
+// GENMAX_GATHER, kind != GENMAX_ARGMAX> on `grid` workgroups of `block` lanes and 32 mt rows with `lds` bytes; mt == 0: no rows,
+// nothing is launched
+enum { GENMAX_ARGMAX_LSE = 0, GENMAX_ARGMAX = 1, GENMAX_GATHER = 2 };
+struct GenmaxForm {
+    bool x3 = false;
+    int mt = 0, kind = 0, vtw = 0, lds = 0, grid = 0, block = 0;
+};
+int decide_genmax(const GenmaxArgs& a, GenmaxForm* f, const char* who, bool packed = true);
 int launch_genmax(const GenmaxArgs& a, hipStream_t s);
 int genmax_vtw(int V);  // vocabulary tiles per wave; packed sizes: weights 4*vtw*16 KiB, biases 4*vtw*32 floats
 void pack_genmax(const float* w, const float* b, int V, uint16_t* wout, float* bout);

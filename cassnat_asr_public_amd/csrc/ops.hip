@@ -12,6 +12,7 @@
 #include "../../include/cassnat_hip.h"
 #include "../../include/cassnat_hip_align.h"
 #include "../../include/cassnat_hip_attention_proj.h"
+#include "../../include/cassnat_hip_genmax.h"
 #include "ctc_search_host.h"
 #include "ctc_times_search.h"
 #include "edit_align_search.h"
@@ -2114,81 +2115,151 @@ extern "C" int cn_op_chain_rows(float* x_dev, const void* ctx_dev, int32_t ldctx
 extern "C" int cn_op_chain_desc(const cn_chain_desc* d, void* stream) { return op_chain_desc("cn_op_chain_desc", d, stream); }
 extern "C" int32_t cn_chain_desc_size(void) { return (int32_t)sizeof(cn_chain_desc); }
 
-static int op_genmax_impl(const void* h_dev, const float* w_host, const float* b_host, int32_t M, int32_t V,
-                          int32_t* arg_dev, float* maxlp_dev, const int32_t* tgt_dev, float* tgt_lp_dev, int32_t U, int32_t ld,
-                          void* stream) {
-    const int vtw = genmax_vtw(V);
-    if (vtw > 48) {
-        cn_set_error("cn_op_genmax: V too large");
+// cn_genmax_desc -> GenmaxArgs without the packed operands: the checks of the descriptor itself (cassnat_hip_genmax.h lists them);
+// the shape and pointer-combination checks are decide_genmax's, which launch_genmax runs for the engine's calls too.  0, or -1 with
+// the error set.  Nothing is sized from V here: genmax_vtw of a V below -127 is negative.
+static int genmax_args_of(const char* who, const cn_genmax_desc* d, GenmaxArgs* a) {
+    auto refuse = [&](const char* what) {
+        cn_set_error(std::string(who) + ": " + what);
         return -1;
-    }
-    std::vector<uint16_t> hw((size_t)4 * vtw * 16 * 512);
-    std::vector<float> hb((size_t)4 * vtw * 32);
-    pack_genmax(w_host, b_host, V, hw.data(), hb.data());
-    Scratch sc("cn_op_genmax", (hipStream_t)stream);
+    };
+    if (!d) return refuse("null descriptor");
+    if (d->reserved != 0) return refuse("the reserved word must be 0");
+    if (d->precision != CN_PRECISION_BF16 && d->precision != CN_PRECISION_F16 && d->precision != CN_PRECISION_BF16X3)
+        return refuse("precision must be the library's 16-bit operand (CN_PRECISION_BF16 or CN_PRECISION_F16) or CN_PRECISION_BF16X3");
+    const int prec = cn_own_precision(d->precision, who);
+    if (prec < 0) return -1;
+    if (!d->h_dev || !d->w_host || !d->b_host) return refuse("null h_dev, w_host or b_host");
+    *a = GenmaxArgs();
+    a->x3 = prec == CN_PREC_X3;
+    a->h = d->h_dev;
+    a->arg = d->arg_dev;
+    a->maxlp = d->maxlp_dev;
+    a->M = d->M;
+    a->V = d->V;
+    a->d = 256;
+    a->m_dev = d->m_dev;
+    a->tgt = d->tgt_dev;
+    a->tgt_lp = d->tgt_lp_dev;
+    a->tgt_U = d->U;
+    a->tgt_ld = d->ld;
+    return 0;
+}
+
+static int op_genmax_desc(const char* who, const cn_genmax_desc* d, void* stream) {
     GenmaxArgs a;
-    a.h = h_dev;
+    GenmaxForm f;
+    if (genmax_args_of(who, d, &a) != 0 || decide_genmax(a, &f, who, false) != 0) return -1;
+    if (f.mt == 0) return 0;
+    const size_t waves = a.x3 ? 8 : 4;
+    std::vector<uint16_t> hw(waves * f.vtw * 16 * (a.x3 ? 1024 : 512));
+    std::vector<float> hb(waves * f.vtw * 32);
+    (a.x3 ? pack_genmax_x3 : pack_genmax)(d->w_host, d->b_host, a.V, hw.data(), hb.data());
+    Scratch sc(who, (hipStream_t)stream);
     a.wp = sc.upload(hw.data(), hw.size() * 2);
     a.bp = (const float*)sc.upload(hb.data(), hb.size() * 4);
     if (!sc.ok()) return -2;
-    a.arg = arg_dev;
-    a.maxlp = maxlp_dev;
-    a.M = M;
-    a.V = V;
-    a.d = 256;
-    a.tgt = tgt_dev;
-    a.tgt_lp = tgt_lp_dev;
-    a.tgt_U = U;
-    a.tgt_ld = ld;
     int rc = launch_genmax(a, (hipStream_t)stream);
     if (const char* rep = cn_exp_env("CASSNAT_GENMAX_REPEAT"))  // timing runs only
         for (int i = 1, n = atoi(rep); rc == 0 && i < n; ++i) rc = launch_genmax(a, (hipStream_t)stream);
     return sc.finish(rc);
 }
 
+extern "C" int cn_op_genmax_desc(const cn_genmax_desc* d, void* stream) { return op_genmax_desc("cn_op_genmax_desc", d, stream); }
+extern "C" int32_t cn_genmax_desc_size(void) { return (int32_t)sizeof(cn_genmax_desc); }
+
+static_assert(CN_GENMAX_KIND_ARGMAX_LSE == GENMAX_ARGMAX_LSE && CN_GENMAX_KIND_ARGMAX == GENMAX_ARGMAX && CN_GENMAX_KIND_GATHER == GENMAX_GATHER,
+              "the public output kinds are the kernel's");
+
+extern "C" int32_t cn_genmax_form_launch(const cn_genmax_desc* d, int32_t* lds_bytes, int32_t* grid) {
+    GenmaxArgs a;
+    GenmaxForm f;
+    if (genmax_args_of("cn_genmax_form", d, &a) != 0 || decide_genmax(a, &f, "cn_genmax_form", false) != 0) return -1;
+    if (lds_bytes) *lds_bytes = f.lds;
+    if (grid) *grid = f.grid;
+    return (f.x3 ? CN_GENMAX_KERNEL_SPLIT : CN_GENMAX_KERNEL_16) | f.mt << 4 | f.kind << 8 | f.vtw << 12;
+}
+extern "C" int32_t cn_genmax_form(const cn_genmax_desc* d) { return cn_genmax_form_launch(d, nullptr, nullptr); }
+
+extern "C" int cn_genmax_pack(int32_t precision, const float* w_host, const float* b_host, int32_t V, void* w_out, int64_t w_bytes,
+                              float* b_out, int64_t b_floats) {
+    static const int32_t one = 0;  // (a stand-in for the descriptor's device pointers: the checks follow none)
+    cn_genmax_desc d = {};
+    d.precision = precision;
+    d.h_dev = &one;
+    d.w_host = w_host;
+    d.b_host = b_host;
+    d.M = 0;
+    d.V = V;
+    d.arg_dev = const_cast<int32_t*>(&one);
+    GenmaxArgs a;
+    GenmaxForm f;
+    if (genmax_args_of("cn_genmax_pack", &d, &a) != 0 || decide_genmax(a, &f, "cn_genmax_pack", false) != 0) return -1;
+    const int64_t waves = a.x3 ? 8 : 4, wb = waves * f.vtw * (a.x3 ? 32768 : 16384), bf = waves * f.vtw * 32;
+    if (!w_out || !b_out || w_bytes != wb || b_floats != bf) {
+        cn_set_error("cn_genmax_pack: V=" + std::to_string(V) + " packs into exactly " + std::to_string(wb) + " bytes of weights and " +
+                     std::to_string(bf) + " biases (non-null buffers of that size)");
+        return -1;
+    }
+    (a.x3 ? pack_genmax_x3 : pack_genmax)(w_host, b_host, V, static_cast<uint16_t*>(w_out), b_out);
+    return 0;
+}
+
+#ifdef CN_OP16_F16
+static const int32_t kOwn16 = CN_PRECISION_F16;
+#else
+static const int32_t kOwn16 = CN_PRECISION_BF16;
+#endif
+
+static cn_genmax_desc genmax_desc_of(int32_t precision, const void* h_dev, const float* w_host, const float* b_host, int32_t M, int32_t V,
+                                     int32_t* arg_dev, float* maxlp_dev, const int32_t* tgt_dev, int32_t U, int32_t ld, float* tgt_lp_dev) {
+    cn_genmax_desc d = {};
+    d.precision = precision;
+    d.h_dev = h_dev;
+    d.w_host = w_host;
+    d.b_host = b_host;
+    d.M = M;
+    d.V = V;
+    d.arg_dev = arg_dev;
+    d.maxlp_dev = maxlp_dev;
+    d.tgt_dev = tgt_dev;
+    d.U = U;
+    d.ld = ld;
+    d.tgt_lp_dev = tgt_lp_dev;
+    return d;
+}
+
 extern "C" int cn_op_genmax(const void* h_dev, const float* w_host, const float* b_host, int32_t M, int32_t V,
                             int32_t* arg_dev, float* maxlp_dev, void* stream) {
-    return op_genmax_impl(h_dev, w_host, b_host, M, V, arg_dev, maxlp_dev, nullptr, nullptr, 0, 0, stream);
+    const cn_genmax_desc d = genmax_desc_of(kOwn16, h_dev, w_host, b_host, M, V, arg_dev, maxlp_dev, nullptr, 0, 0, nullptr);
+    return op_genmax_desc("cn_op_genmax", &d, stream);
 }
 
 extern "C" int cn_op_genmax_gather(const void* h_dev, const float* w_host, const float* b_host, int32_t B, int32_t U, int32_t V,
                                    const int32_t* tgt_dev, int32_t ld, float* tgt_lp_dev, void* stream) {
-    return op_genmax_impl(h_dev, w_host, b_host, B * U, V, nullptr, nullptr, tgt_dev, tgt_lp_dev, U, ld, stream);
+    if (B < 0 || U < 1 || (int64_t)B * U > INT32_MAX) {
+        cn_set_error("cn_op_genmax_gather: B must not be negative, U at least 1 and B x U an int32");
+        return -1;
+    }
+    const cn_genmax_desc d = genmax_desc_of(kOwn16, h_dev, w_host, b_host, B * U, V, nullptr, nullptr, tgt_dev, U, ld, tgt_lp_dev);
+    return op_genmax_desc("cn_op_genmax_gather", &d, stream);
 }
 
 // the split-bf16 form (CN_PRECISION_BF16X3): h_host fp32 [M][256] is split into hi + lo halves and uploaded by the call;
 // tgt_dev == NULL: arg-max (+ maxlp when maxlp_dev), else the target gather with M = rows, U per sequence, ld the target stride
 extern "C" int cn_op_genmax_x3(const float* h_host, const float* w_host, const float* b_host, int32_t M, int32_t V, int32_t* arg_dev,
                                float* maxlp_dev, const int32_t* tgt_dev, int32_t U, int32_t ld, float* tgt_lp_dev, void* stream) {
-    if (!genmax_applies(CN_PREC_X3, 256, V) || M < 1) {
-        cn_set_error("cn_op_genmax_x3: V too large");
-        return -1;
-    }
-    const int vtw = genmax_x3_vtw(V);
-    std::vector<uint16_t> hw((size_t)8 * vtw * 16 * 1024);
-    std::vector<float> hb((size_t)8 * vtw * 32);
-    pack_genmax_x3(w_host, b_host, V, hw.data(), hb.data());
+    // the descriptor's checks first, with the host rows standing in for the device's: nothing is split or uploaded for a refused call
+    cn_genmax_desc d = genmax_desc_of(CN_PRECISION_BF16X3, h_host, w_host, b_host, M, V, arg_dev, maxlp_dev, tgt_dev, U, ld, tgt_lp_dev);
+    GenmaxArgs a;
+    GenmaxForm f;
+    if (genmax_args_of("cn_op_genmax_x3", &d, &a) != 0 || decide_genmax(a, &f, "cn_op_genmax_x3", false) != 0) return -1;
+    if (f.mt == 0) return 0;
     const std::vector<unsigned char> hx = split_rows256(h_host, M);
     Scratch sc("cn_op_genmax_x3", (hipStream_t)stream);
-    GenmaxArgs a;
-    a.x3 = true;
-    a.h = sc.upload(hx.data(), hx.size());
-    a.wp = sc.upload(hw.data(), hw.size() * 2);
-    a.bp = (const float*)sc.upload(hb.data(), hb.size() * 4);
+    d.h_dev = sc.upload(hx.data(), hx.size());
     if (!sc.ok()) return -2;
-    a.arg = arg_dev;
-    a.maxlp = maxlp_dev;
-    a.M = M;
-    a.V = V;
-    a.d = 256;
-    a.tgt = tgt_dev;
-    a.tgt_lp = tgt_lp_dev;
-    a.tgt_U = U;
-    a.tgt_ld = ld;
-    int rc = launch_genmax(a, (hipStream_t)stream);
-    if (const char* rep = cn_exp_env("CASSNAT_GENMAX_REPEAT"))  // timing runs only
-        for (int i = 1, n = atoi(rep); rc == 0 && i < n; ++i) rc = launch_genmax(a, (hipStream_t)stream);
-    return sc.finish(rc);
+    return sc.finish(op_genmax_desc("cn_op_genmax_x3", &d, stream));
 }
 
 // d_model-deep projection of the split-bf16 engine (proj_x3.hip): a_host fp32 [M][256] and w_host fp32 [N][256] are split into

@@ -56,6 +56,8 @@ CnConfig, CnDecodeOpts, CnAstOpts, CnFbankOpts, CnAttnDesc, CnNgramDesc, CnChain
 CnBiasDesc = abi.CTC_BIAS_STRUCTS["cn_bias_desc"]
 # the descriptor of the alignment kernel's forms (include/cassnat_hip_align.h declares it beside the entry points of its family)
 CnAlignDesc = abi.ALIGN_STRUCTS["cn_align_desc"]
+# the descriptor of the fused generator tail's forms (include/cassnat_hip_genmax.h)
+CnGenmaxDesc = abi.GENMAX_STRUCTS["cn_genmax_desc"]
 
 
 class HipError(RuntimeError):

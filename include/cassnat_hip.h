@@ -775,7 +775,9 @@ int cn_op_x3_chain(float* x_dev, const void* ctx_dev, const float* wo_host, cons
                    void* tail_out_dev, int32_t tail_n, int32_t M, int32_t dff, float eps, int32_t mix /* as cn_op_ffn_x3 */,
                    void* stream);
 /* fused generator tail, bf16 / d_model 256: arg[m] = argmax_v, maxlp[m] = max_v of log_softmax(W h[m] + b); h_dev bf16 [M][256],
- * W/b HOST fp32 nn.Linear parameters (packed and uploaded by the call; the model packs once at cn_model_finalize). */
+ * W/b HOST fp32 nn.Linear parameters (packed and uploaded by the call; the model packs once at cn_model_finalize).  This entry
+ * and the two below are plain forms of cn_op_genmax_desc (include/cassnat_hip_genmax.h: every form, the refusals - theirs start
+ * with their own names - and the gather's contract for a target outside the vocabulary). */
 int cn_op_genmax(const void* h_dev, const float* w_host, const float* b_host, int32_t M, int32_t V, int32_t* arg_dev,
                  float* maxlp_dev, void* stream);
 /* the same kernel with a target gather (TransformerLM scoring, src/models/cassnat.py:507-520): h_dev bf16 [B * U][256];
